@@ -2,7 +2,7 @@
 
     python bench.py --gpus N --steps K --warmup W
 
-N > 1 without a launcher (no WORLD_SIZE in the environment): bench.py re-executes itself under
+N > 1 without a launcher (no WORLD_SIZE in the environment): bench.py runs itself in a child process under
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1` -- one rank per GPU over RCCL; it
 refuses to start when fewer than N GPUs are visible.  Launched BY torch.distributed.run it reads RANK / LOCAL_RANK / WORLD_SIZE.
 
@@ -44,6 +44,7 @@ import argparse
 import json
 import os
 import platform
+import subprocess
 import sys
 import time
 
@@ -125,6 +126,8 @@ class Workload:
         self.keep_codes = None                        # a list: utterance() appends the content codes of every chunk (parity_in_bench)
         self.stage_ev = None                          # a list: utterance() appends (name, event) marks around its stages (stage_times)
         self.t_first = None                           # host clock at the first 8-token group of a `sync_first` utterance
+        self.keep_wav = False                         # --dump-outputs: utterance() keeps every vocoder chunk of the utterance in wav_chunks
+        self.wav_chunks = []
 
     def utterance(self, u, record=False, sync_first=False, registered=False):
         m, eng = self.model, self.eng
@@ -146,6 +149,8 @@ class Workload:
         ready.record()
         cond_future = None
         src = self.src[u % 4]
+        if self.keep_wav:
+            self.wav_chunks = []
         def mark(name):
             if self.stage_ev is not None:
                 e = torch.cuda.Event(enable_timing=True)
@@ -181,6 +186,8 @@ class Workload:
                 mark("decode steps")
                 # vocoder every 8 tokens (x4 interpolation + HiFi-GAN -> 8192 samples), inference_utils.py:195-205
                 self.wav = m.hifigan.forward_latents(lat_view[:, g:g + GROUP], 4)
+                if self.keep_wav:
+                    self.wav_chunks.append(self.wav)
                 mark("vocoder")
                 if record and c == 0 and g == 0:
                     self.ev[1].record()                                                # first 8-token group done
@@ -204,6 +211,36 @@ def _guarded(name, fn):
         except Exception:                                    # noqa: BLE001
             pass
         return {"error": f"{type(e).__name__}: {e}"}
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, wl, gathered=None):
+    """--dump-outputs: what the timed path handed its caller in its last step, as out_dir/<name>.npy -- token ids [S, n] (float64: exact),
+    latents [S, n, d] and the concatenated vocoder chunks [S, samples] (float32); with N > 1 also the all-gathered ids [N, S, n].  Past
+    DUMP_BUDGET_BYTES a fixed seeded sample of the streams is kept (streams.npy names them).  Returns the names written."""
+    import numpy as np
+    S = wl.S
+    arrays = {"tokens": wl.toks.cpu().numpy().astype(np.float64),
+              "latents": wl.lats.cpu().numpy().astype(np.float32),
+              "waveform": torch.cat(wl.wav_chunks, -1).reshape(S, -1).cpu().numpy().astype(np.float32)}
+    per_stream = sum(a.nbytes for a in arrays.values()) // S
+    keep = max(1, min(S, DUMP_BUDGET_BYTES // 2 // per_stream))
+    if keep < S:
+        idx = np.sort(np.random.default_rng(0).choice(S, keep, replace=False))
+        arrays = {k: a[idx] for k, a in arrays.items()}
+        arrays["streams"] = idx.astype(np.float64)
+    if gathered is not None:
+        arrays["tokens_all_ranks"] = torch.stack(gathered).cpu().numpy().astype(np.float64)
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_BUDGET_BYTES, "--dump-outputs: over the 64 MB budget"
+    if not os.path.isdir(out_dir):
+        os.makedirs(out_dir)
+        with open(os.path.join(out_dir, ".gitignore"), "w") as f:
+            f.write("*\n")                                   # a dump made inside a checkout never shows up in its status
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(arrays)
 
 
 def _cpu_model():
@@ -779,10 +816,24 @@ def cold_probe(device, rank, weights, max_slots):
     return out, wl
 
 
+def _positive(s):
+    v = int(s)
+    if v < 1:
+        raise argparse.ArgumentTypeError(f"{s}: must be at least 1")
+    return v
+
+
+def _visible_gpus():
+    """device count read in a child process: the launching process itself never opens the GPU"""
+    r = subprocess.run([sys.executable, "-c", "import torch; print(torch.cuda.device_count())"], capture_output=True, text=True)
+    return int(r.stdout.strip() or 0) if r.returncode == 0 else 0
+
+
 def self_launch(args):
-    """`python bench.py --gpus N` with N > 1 and no launcher: become `torch.distributed.run` with one rank per GPU"""
+    """`python bench.py --gpus N` with N > 1 and no launcher: run `torch.distributed.run` with one rank per GPU as a child process
+    (this process never touches the GPU) and exit with its status"""
     import socket
-    n_dev = torch.cuda.device_count()
+    n_dev = _visible_gpus()
     if n_dev < args.gpus and not os.environ.get("GVC_BENCH_SAME_DEVICE"):
         sys.exit(f"bench.py --gpus {args.gpus}: only {n_dev} GPU(s) visible on this node (set GVC_BENCH_SAME_DEVICE=1 with "
                  "GVC_BENCH_BACKEND=gloo for a dry run of the multi-rank path on one GPU)")
@@ -795,13 +846,13 @@ def self_launch(args):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     sys.stdout.flush()
-    os.execvpe(sys.executable, cmd, env)
+    sys.exit(subprocess.run(cmd, env=env).returncode)
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=8)
+    ap.add_argument("--steps", type=_positive, default=8, help="timed steps (utterances per GPU); ms_per_step = their mean")
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-offline", action="store_true", help="skip the batched-offline leg (BASELINE configs[2])")
@@ -811,10 +862,11 @@ def main():
     ap.add_argument("--streams", type=int, default=1, help="concurrent streams per GPU (1 = headline configuration)")
     ap.add_argument("--weights", default="fp32", choices=["fp32", "bf16", "bf16_kv", "bf16_act"],
                     help="GPT weight / KV-cache storage (fp32 = headline configuration; bf16_kv with --streams 8 = BASELINE configs[3])")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs (token ids, latents, waveform) as DIR/<name>.npy")
     args = ap.parse_args()
-    assert torch.cuda.is_available(), "bench.py needs a GPU (the product path has no CPU fallback)"
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         self_launch(args)                         # does not return
+    assert torch.cuda.is_available(), "bench.py needs a GPU (the product path has no CPU fallback)"
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -853,6 +905,7 @@ def main():
         cold, wl = cold_probe(device, rank, args.weights, slots_needed)
     else:
         wl = Workload(device, rank, args.streams, args.weights, max_slots=slots_needed)
+    wl.keep_wav = bool(args.dump_outputs)        # on for the warm-up too: the timed steps allocate as the warm-up did
     for u in range(args.warmup):
         wl.utterance(u)
 
@@ -876,6 +929,8 @@ def main():
         t = torch.tensor([dt], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    dumped = dump_outputs(args.dump_outputs, wl, gathered) if args.dump_outputs and rank == 0 else None
+    wl.keep_wav, wl.wav_chunks = False, []
 
     offline = offline_leg(wl, rank, world, dist, device) if do_offline else None
     do_extra = headline and args.weights == "fp32" and not args.no_extra
@@ -998,6 +1053,8 @@ def main():
                          "decode_step_us_launch_per_phase": whole_us},
             "kernels": kern,
         }
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped, "step": args.steps - 1}
         out["stages_ms_per_utterance"] = _guarded("stage_times", lambda: stage_times(wl))
         if offline is not None:
             out["offline"] = offline

@@ -12,8 +12,9 @@ DEV = "cuda"
 
 def test_mel_matches_oracle_within_1e4():
     from genvc_amd.engine import MelEngine
+    from genvc_amd.utils import DEFAULT_MEL_NORM_FILE
     from oracle import genvc_oracle as O
-    norms = np.load("genvc_amd/assets/mel_stats.npy")
+    norms = np.load(DEFAULT_MEL_NORM_FILE)
     eng = MelEngine(norms)
     for T, frames in ((72000, 282), (144000, 563), (96000, 376), (98835, 387), (8000, 32)):
         wav = synth.synth_audio(21, f"ref{T}", T)

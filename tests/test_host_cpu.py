@@ -332,37 +332,79 @@ def test_convert_batch_packs_classes_by_kv_slots():
     assert all(sum(c) <= 2 or len(c) == 1 for c in small.gpt.group_calls)
 
 
-def test_bench_self_launches_n_ranks(monkeypatch):
-    """`python bench.py --gpus N` (N > 1) with no launcher in the environment becomes `torch.distributed.run --nproc-per-node N` on
-    127.0.0.1 with the caller's flags; with fewer than N GPUs visible it refuses instead of running one process and printing
-    `n_gpus: 1` (missing item 1)."""
+def _load_bench():
     import importlib.util
-    import argparse
     spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
     bench = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(bench)
+    return bench
+
+
+def test_bench_self_launches_n_ranks(monkeypatch):
+    """`python bench.py --gpus N` (N > 1) with no launcher in the environment starts `torch.distributed.run --nproc-per-node N` on
+    127.0.0.1 with the caller's flags as a child process and exits with its status; with fewer than N GPUs visible it refuses instead of
+    running one process and printing `n_gpus: 1` (missing item 1)."""
+    import argparse
+    bench = _load_bench()
     seen = {}
 
-    def fake_exec(exe, cmd, env):
-        seen["exe"], seen["cmd"], seen["env"] = exe, cmd, env
-        raise SystemExit(0)
+    def fake_run(cmd, env):
+        seen["cmd"], seen["env"] = cmd, env
+        return subprocess.CompletedProcess(cmd, 0)
 
-    monkeypatch.setattr(bench.os, "execvpe", fake_exec)
+    monkeypatch.setattr(bench.subprocess, "run", fake_run)
     monkeypatch.setattr(bench.sys, "argv", ["bench.py", "--gpus", "4", "--steps", "3", "--warmup", "1"])
-    monkeypatch.setattr(bench.torch.cuda, "device_count", lambda: 8)
+    monkeypatch.setattr(bench, "_visible_gpus", lambda: 8)
     monkeypatch.delenv("GVC_BENCH_SAME_DEVICE", raising=False)
-    with pytest.raises(SystemExit):
+    with pytest.raises(SystemExit) as e:
         bench.self_launch(argparse.Namespace(gpus=4))
+    assert e.value.code == 0
     cmd = seen["cmd"]
     assert cmd[1:4] == ["-m", "torch.distributed.run", "--nnodes=1"] and "--nproc-per-node=4" in cmd
     assert cmd[cmd.index("--master-addr") + 1] == "127.0.0.1"
     assert cmd[-6:] == ["--gpus", "4", "--steps", "3", "--warmup", "1"] and cmd[-7].endswith("bench.py")
     assert seen["env"]["HSA_ENABLE_IPC_MODE_LEGACY"] == "0"
     # too few GPUs: a loud refusal, not a silent 1-process run
-    monkeypatch.setattr(bench.torch.cuda, "device_count", lambda: 1)
+    monkeypatch.setattr(bench, "_visible_gpus", lambda: 1)
     with pytest.raises(SystemExit) as e:
         bench.self_launch(argparse.Namespace(gpus=4))
     assert "only 1 GPU" in str(e.value)
+
+
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs: token ids (float64, exact), latents and the concatenated vocoder chunks (float32) of the last timed step; past the
+    64 MB budget the same seeded sample of streams from every array, named in streams.npy; a directory it creates ignores itself in git"""
+    from types import SimpleNamespace
+    bench = _load_bench()
+    S, n, d = 2, 240, 1024
+    wl = SimpleNamespace(S=S, toks=torch.arange(S * n, dtype=torch.int32).view(S, n), lats=torch.randn(S, n, d),
+                         wav_chunks=[torch.full((S, 1, 8192), float(i)) for i in range(30)])
+    out = tmp_path / "dump"
+    names = bench.dump_outputs(str(out), wl)
+    assert names == ["latents", "tokens", "waveform"]
+    assert (out / ".gitignore").read_text() == "*\n"
+    t, lat, wav = (np.load(out / f"{k}.npy") for k in ("tokens", "latents", "waveform"))
+    assert t.dtype == np.float64 and np.array_equal(t, wl.toks.numpy())
+    assert lat.dtype == np.float32 and np.array_equal(lat, wl.lats.numpy())
+    assert wav.shape == (S, 30 * 8192) and wav[1, 8192 * 7] == 7.0
+    # 40 streams (~79 MB) -> a sample of the streams, identical from run to run, every array under the budget
+    S = 40
+    big = SimpleNamespace(S=S, toks=torch.arange(S * n, dtype=torch.int32).view(S, n), lats=torch.randn(S, n, d),
+                          wav_chunks=[torch.randn(S, 1, 8192) for _ in range(30)])
+    a, b = tmp_path / "a", tmp_path / "b"
+    assert "streams" in bench.dump_outputs(str(a), big) and "streams" in bench.dump_outputs(str(b), big)
+    idx = np.load(a / "streams.npy")
+    assert np.array_equal(idx, np.load(b / "streams.npy")) and 0 < len(idx) < S
+    assert np.array_equal(np.load(a / "tokens.npy"), big.toks.numpy()[idx.astype(np.int64)])
+    assert sum(os.path.getsize(p) for p in a.glob("*.npy")) <= 64 << 20
+
+
+def test_bench_steps_must_be_positive():
+    import argparse
+    bench = _load_bench()
+    assert bench._positive("3") == 3
+    with pytest.raises(argparse.ArgumentTypeError):
+        bench._positive("0")
 
 
 def test_convert_offline_rolling_matches_waves():

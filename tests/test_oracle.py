@@ -115,7 +115,8 @@ def test_sampler_processors_vs_hf(gold):
 def test_mel_fp32_vs_float64_dft():
     """mel is 'parity unpinned' (torchaudio absent): cross-check the fp32 restatement against an
     independent float64 direct-DFT formulation, within the north_star tolerance 1e-4."""
-    mel_norms = torch.from_numpy(np.load("genvc_amd/assets/mel_stats.npy"))
+    from genvc_amd.utils import DEFAULT_MEL_NORM_FILE
+    mel_norms = torch.from_numpy(np.load(DEFAULT_MEL_NORM_FILE))
     wav = synth.synth_audio(21, "ref3s", 72000)
     m32 = O.mel_spectrogram(wav, mel_norms)
     assert m32.shape == (1, 80, 282)
