@@ -22,6 +22,12 @@ class SampleParams(C.Structure):
                 ("top_k", C.c_int32), ("eos_token", C.c_int32), ("vocab", C.c_int32), ("seed", C.c_uint64)]
 
 
+class RowSampling(C.Structure):
+    """gvc_row_sampling: per-row sampling settings and RNG key (32 bytes; layout fixed in include/genvc_hip.h)"""
+    _fields_ = [("repetition_penalty", C.c_float), ("temperature", C.c_float), ("top_p", C.c_float), ("top_k", C.c_int32),
+                ("seed", C.c_uint64), ("rng_row", C.c_int32), ("rng_step0", C.c_int32)]
+
+
 class PerceiverDims(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("dim", "depth", "dim_context", "num_latents", "dim_head", "heads",
                                          "ff_mult", "max_batch", "max_frames")]
@@ -63,6 +69,10 @@ _SIGNATURES = {
     "gvc_sample": (C.c_int, [_P, C.c_int32, _P, C.c_int32, _P, _P, C.POINTER(SampleParams), C.c_int32, _P, _P]),
     "gvc_gpt_generate": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, _P, _P, C.POINTER(SampleParams), C.c_int32,
                                    C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_int32, _P]),
+    "gvc_sample_rows": (C.c_int, [_P, C.c_int32, _P, C.c_int32, _P, _P, C.POINTER(SampleParams), C.POINTER(RowSampling),
+                                  C.c_int32, _P, _P]),
+    "gvc_gpt_generate_rows": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, _P, _P, C.POINTER(SampleParams), C.POINTER(RowSampling),
+                                        C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_int32, _P]),
     "gvc_gpt_decode_variant": (C.c_int, [_P]),
     "gvc_gpt_rows_step_launches": (C.c_longlong, [_P]),
     "gvc_gpt_health": (C.c_int, [_P]),

@@ -177,14 +177,15 @@ __global__ void k_transpose(const float* src, float* dst, int K, int N) {
 struct GenCall {
     SampleCall sc;
     int32_t slots[64];
+    gvc_row_sampling rows[kMaxSampleRows];   // per-row settings and keys of a gvc_gpt_generate_rows call (sc.rows points here)
 };
 
 // Start / end of a gvc_gpt_generate call in ONE launch each (they used to be a memset, k_set_gen_call and two k_stage_rows before the
 // step graphs and two k_stage_rows after them: six 4-5 us operations around every group of eight streaming steps).
 // begin: workgroup b < B un-parks the next-step logits and latent of stream b; workgroup B resets the step counter and stores the
 // call parameters.  end: workgroup b parks them again.
-__global__ void k_gen_begin(GenCall* dst, SampleCall sc, const int32_t* slots, int B, int32_t* step_ctr, float* logits, float* slot_logits,
-                            int vocab, float* latent, float* slot_latent, int d) {
+__device__ __forceinline__ void gen_begin(GenCall* dst, const SampleCall& sc, const int32_t* slots, int B, int32_t* step_ctr, float* logits,
+                                          const float* slot_logits, int vocab, float* latent, const float* slot_latent, int d) {
     const int b = blockIdx.x;
     if (b == B) {
         if (threadIdx.x == 0) { dst->sc = sc; *step_ctr = 0; }
@@ -194,6 +195,20 @@ __global__ void k_gen_begin(GenCall* dst, SampleCall sc, const int32_t* slots, i
     const size_t sl = (size_t)slots[b];
     for (int i = threadIdx.x; i < vocab; i += blockDim.x) logits[(size_t)b * vocab + i] = slot_logits[sl * vocab + i];
     for (int i = threadIdx.x; i < d; i += blockDim.x) latent[(size_t)b * d + i] = slot_latent[sl * d + i];
+}
+
+__global__ void k_gen_begin(GenCall* dst, SampleCall sc, const int32_t* slots, int B, int32_t* step_ctr, float* logits, float* slot_logits,
+                            int vocab, float* latent, float* slot_latent, int d) {
+    gen_begin(dst, sc, slots, B, step_ctr, logits, slot_logits, vocab, latent, slot_latent, d);
+}
+
+// gvc_gpt_generate_rows: the same, and workgroup B also stores the call's row entries, which travel as a kernel argument (copied by
+// the runtime when the launch is enqueued: the caller's host array is free when the call returns, and no staging buffer of the context
+// can be overwritten by a later call before this launch has read it -- there is none)
+__global__ void k_gen_begin_rows(GenCall* dst, SampleCall sc, const int32_t* slots, int B, int32_t* step_ctr, float* logits,
+                                 float* slot_logits, int vocab, float* latent, float* slot_latent, int d, SampleRows rows) {
+    if ((int)blockIdx.x == B && (int)threadIdx.x < B) dst->rows[threadIdx.x] = rows.r[threadIdx.x];
+    gen_begin(dst, sc, slots, B, step_ctr, logits, slot_logits, vocab, latent, slot_latent, d);
 }
 
 __global__ void k_gen_end(const int32_t* slots, const float* logits, float* slot_logits, int vocab, const float* latent, float* slot_latent,
@@ -1596,13 +1611,15 @@ extern "C" int gvc_gpt_rearm(gvc_gpt* c) {
     return GVC_OK;
 }
 
-extern "C" int gvc_gpt_generate(gvc_gpt* c, const int32_t* slots, int32_t B, int32_t* ids, int32_t ids_stride,
-                                int32_t* ids_len, int32_t* finished, const gvc_sample_params* p, int32_t i0,
-                                int32_t n_steps, int32_t max_keys, int32_t* tokens_out, int32_t tok_stride, float* latents_out,
-                                int32_t lat_stride, gvc_stream sv) {
+// rows: null (gvc_gpt_generate: p's settings for every row) or B host entries (gvc_gpt_generate_rows)
+static int generate_impl(gvc_gpt* c, const int32_t* slots, int32_t B, int32_t* ids, int32_t ids_stride, int32_t* ids_len, int32_t* finished,
+                         const gvc_sample_params* p, const gvc_row_sampling* rows, int32_t i0, int32_t n_steps, int32_t max_keys,
+                         int32_t* tokens_out, int32_t tok_stride, float* latents_out, int32_t lat_stride, gvc_stream sv) {
     int rc = check_ready(c);
     if (rc) return rc;
     GVC_REQUIRE(B >= 1 && B <= c->dm.max_slots && p && n_steps >= 0 && max_keys >= 0, GVC_ERR_ARG, "generate: bad argument");
+    bool rows_greedy = false;
+    if (rows && (rc = check_sample_rows(rows, B, c->dm.vocab, &rows_greedy))) return rc;
     // cached positions of the longest stream once this call has run: the caller's bound, else the whole ids row
     const int key_bound = max_keys > 0 ? max_keys : ids_stride;
     GVC_REQUIRE(max_keys == 0 || max_keys < c->dm.max_seq, GVC_ERR_STATE,
@@ -1615,11 +1632,21 @@ extern "C" int gvc_gpt_generate(gvc_gpt* c, const int32_t* slots, int32_t B, int
     sc.finished = finished; sc.p = *p; sc.step = 0; sc.step_ptr = c->step_ctr; sc.tok_out = c->tok_buf;
     sc.tokens_out = tokens_out; sc.tok_stride = tok_stride; sc.i0 = i0; sc.latent_src = c->latent;
     sc.latents_out = latents_out; sc.lat_stride = lat_stride; sc.d = c->dm.d_model;
-    hipLaunchKernelGGL(k_gen_begin, dim3(B + 1), dim3(256), 0, s, c->gen_call, sc, slots, B, c->step_ctr, c->logits, c->slot_logits,
-                       c->dm.vocab, c->latent, c->slot_latent, c->dm.d_model);
+    if (rows) {
+        SampleRows sr;
+        memset(&sr, 0, sizeof(sr));
+        memcpy(sr.r, rows, (size_t)B * sizeof(gvc_row_sampling));
+        sc.rows = c->gen_call->rows;          // (device address: GenCall lives in device memory)
+        hipLaunchKernelGGL(k_gen_begin_rows, dim3(B + 1), dim3(256), 0, s, c->gen_call, sc, slots, B, c->step_ctr, c->logits,
+                           c->slot_logits, c->dm.vocab, c->latent, c->slot_latent, c->dm.d_model, sr);
+    } else {
+        hipLaunchKernelGGL(k_gen_begin, dim3(B + 1), dim3(256), 0, s, c->gen_call, sc, slots, B, c->step_ctr, c->logits, c->slot_logits,
+                           c->dm.vocab, c->latent, c->slot_latent, c->dm.d_model);
+    }
     GVC_LAUNCH_CHECK();
     GenPlan pl;
-    if ((rc = plan_generate(c, B, key_bound, p->top_k, &pl))) return rc;
+    // (a keyed call replays the greedy graphs when every row is greedy, the sampling ones otherwise: the step graphs are the same)
+    if ((rc = plan_generate(c, B, key_bound, rows ? (rows_greedy ? 1 : 0) : p->top_k, &pl))) return rc;
     c->last_variant = pl.variant;
     const int kStepUnroll = step_unroll();
     int left = n_steps;
@@ -1637,6 +1664,23 @@ extern "C" int gvc_gpt_generate(gvc_gpt* c, const int32_t* slots, int32_t B, int
                        c->dm.d_model);
     GVC_LAUNCH_CHECK();
     return GVC_OK;
+}
+
+extern "C" int gvc_gpt_generate(gvc_gpt* c, const int32_t* slots, int32_t B, int32_t* ids, int32_t ids_stride,
+                                int32_t* ids_len, int32_t* finished, const gvc_sample_params* p, int32_t i0,
+                                int32_t n_steps, int32_t max_keys, int32_t* tokens_out, int32_t tok_stride, float* latents_out,
+                                int32_t lat_stride, gvc_stream sv) {
+    return generate_impl(c, slots, B, ids, ids_stride, ids_len, finished, p, nullptr, i0, n_steps, max_keys, tokens_out, tok_stride,
+                         latents_out, lat_stride, sv);
+}
+
+extern "C" int gvc_gpt_generate_rows(gvc_gpt* c, const int32_t* slots, int32_t B, int32_t* ids, int32_t ids_stride, int32_t* ids_len,
+                                     int32_t* finished, const gvc_sample_params* common, const gvc_row_sampling* rows, int32_t i0,
+                                     int32_t n_steps, int32_t max_keys, int32_t* tokens_out, int32_t tok_stride, float* latents_out,
+                                     int32_t lat_stride, gvc_stream sv) {
+    GVC_REQUIRE(rows, GVC_ERR_ARG, "generate_rows: null rows");
+    return generate_impl(c, slots, B, ids, ids_stride, ids_len, finished, common, rows, i0, n_steps, max_keys, tokens_out, tok_stride,
+                         latents_out, lat_stride, sv);
 }
 
 

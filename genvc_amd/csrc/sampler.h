@@ -24,14 +24,30 @@ struct SampleCall {
     const float* latent_src; // nullable: [B][d] latent that predicted this token
     float* latents_out;      // nullable: [B][lat_stride][d]
     int lat_stride, d;
+    // nullable: [B] per-row settings and RNG keys (gvc_row_sampling, device memory).  Null: every row uses p and draws
+    // rng_uniform(p.seed, i0 + step, b).  Set: row b uses rows[b]'s processor settings and draws
+    // rng_uniform(seed_b, rng_step0_b + step, rng_row_b); p then carries eos_token / vocab only, and p.top_k == 1 tells
+    // launch_sample that every row is greedy.
+    const gvc_row_sampling* rows;
 };
 
 int launch_sample(const SampleCall& sc, hipStream_t s);
 // the call parameters live in device memory (graph replay)
-// greedy: the call has top_k == 1 (sample_greedy_ok): the argmax-only kernel
+// greedy: the call has top_k == 1 (sample_greedy_ok), or every row of a keyed call has: the argmax-only kernel
 int launch_sample_indirect(const SampleCall* sc_dev, int B, bool greedy, hipStream_t s);
 static inline bool sample_greedy_ok(int top_k, int d) {
     return top_k == 1 && d % 4 == 0;
 }
+
+// per-row entries of one call, passed BY VALUE as a kernel argument: the runtime copies kernel arguments when the launch is
+// enqueued, so the caller's host array is free again when the launching call returns and no staging buffer has to outlive it
+constexpr int kMaxSampleRows = 64;
+struct SampleRows {
+    gvc_row_sampling r[kMaxSampleRows];
+};
+// host-side checks of a keyed call: B <= 64, 0 < temperature, top_k <= vocab; *all_greedy = every row has top_k == 1
+int check_sample_rows(const gvc_row_sampling* rows, int B, int vocab, bool* all_greedy);
+// rows[0..B) -> dst[0..B) on stream s (one small launch; the host array is not read after the launch is enqueued)
+int launch_stage_rows(gvc_row_sampling* dst, const gvc_row_sampling* rows, int B, hipStream_t s);
 
 }  // namespace gvc

@@ -60,6 +60,12 @@ __global__ __launch_bounds__(kSampThreads) void k_sample(SampleCall cv, const Sa
     const float* lg = C.logits + (size_t)b * V;
     int32_t* ids = C.ids + (size_t)b * C.ids_stride;
     const int len = C.ids_len[b];
+    // processor settings and RNG key of this row (uniform over the workgroup: one workgroup = one row)
+    const gvc_row_sampling* R = C.rows ? C.rows + b : nullptr;
+    const float rep_pen = R ? R->repetition_penalty : C.p.repetition_penalty;
+    const float temp = R ? R->temperature : C.p.temperature;
+    const float top_p = R ? R->top_p : C.p.top_p;
+    const int top_k = R ? R->top_k : C.p.top_k;
 
     for (int i = tid; i < kSortN; i += kSampThreads) seen[i] = 0;
     __syncthreads();
@@ -73,8 +79,8 @@ __global__ __launch_bounds__(kSampThreads) void k_sample(SampleCall cv, const Sa
         float v = -INFINITY;
         if (i < V) {
             v = lg[i];
-            if (seen[i]) v = v < 0.f ? v * C.p.repetition_penalty : v / C.p.repetition_penalty;
-            v = v / C.p.temperature;
+            if (seen[i]) v = v < 0.f ? v * rep_pen : v / rep_pen;
+            v = v / temp;
         }
         sc[i] = v;
         srt[i] = v;
@@ -82,7 +88,7 @@ __global__ __launch_bounds__(kSampThreads) void k_sample(SampleCall cv, const Sa
     __syncthreads();
 
     int tok;
-    if (C.p.top_k == 1) {
+    if (top_k == 1) {
         // exactly one candidate survives TopK(1): argmax of the penalised scores, first index on ties
         float bv = -INFINITY; int bi = 0x7fffffff;
         for (int i = tid; i < V; i += kSampThreads)
@@ -138,7 +144,7 @@ __global__ __launch_bounds__(kSampThreads) void k_sample(SampleCall cv, const Sa
         const float mx = srt[0];
         // TopK: keep scores >= k-th largest (ties kept); nk = how many lead the descending order
         float thresh = -INFINITY;
-        if (C.p.top_k > 0 && C.p.top_k < V) thresh = srt[C.p.top_k - 1];
+        if (top_k > 0 && top_k < V) thresh = srt[top_k - 1];
         if (tid == 0) s_nk = 0;
         __syncthreads();
         for (int i = tid; i < kSortN; i += kSampThreads) {
@@ -148,7 +154,7 @@ __global__ __launch_bounds__(kSampThreads) void k_sample(SampleCall cv, const Sa
         }
         __syncthreads();
         const int nk = s_nk;
-        if (C.p.top_p < 1.0f && nk > 1) {
+        if (top_p < 1.0f && nk > 1) {
             // ascending order j = 0..nk-1 <-> descending index nk-1-j; p_j = exp(s - max) / Z; drop the leading run with
             // cumulative mass <= 1 - top_p, always keeping the largest
             const int j0 = 2 * tid, j1 = 2 * tid + 1;
@@ -161,8 +167,8 @@ __global__ __launch_bounds__(kSampThreads) void k_sample(SampleCall cv, const Sa
             const float ex = block_scan_excl<float>(q0 + q1, fscr, &tot);
             const float c0 = ex + q0, c1 = c0 + q1;
             int removed = 0;
-            if (j0 < nk - 1 && c0 <= 1.0f - C.p.top_p) ++removed;
-            if (j1 < nk - 1 && c1 <= 1.0f - C.p.top_p) ++removed;
+            if (j0 < nk - 1 && c0 <= 1.0f - top_p) ++removed;
+            if (j1 < nk - 1 && c1 <= 1.0f - top_p) ++removed;
             int nrem;
             (void)block_scan_excl<int>(removed, iscr, &nrem);
             thresh = srt[nk - nrem - 1];
@@ -174,8 +180,10 @@ __global__ __launch_bounds__(kSampThreads) void k_sample(SampleCall cv, const Sa
             const double w0 = k0 ? (double)expf(sc[i0v] - mx) : 0.0, w1 = k1 ? (double)expf(sc[i1v] - mx) : 0.0;
             double total;
             const double ex = block_scan_excl<double>(w0 + w1, dscr, &total);
-            // the RNG counter is the position of the step in the whole run (i0 + step), not in this call
-            const double target = (double)rng_uniform(C.p.seed, (uint64_t)(C.i0 + step), (uint64_t)b) * total;
+            // the RNG counter is the position of the step in the whole run of the stream (i0 + step, or rng_step0 + step of a keyed
+            // row), not in this call; a keyed row is numbered inside its own job, not by its place in the call
+            const double target = (R ? (double)rng_uniform(R->seed, (uint64_t)(R->rng_step0 + step), (uint64_t)R->rng_row)
+                                     : (double)rng_uniform(C.p.seed, (uint64_t)(C.i0 + step), (uint64_t)b)) * total;
             const double a0 = ex + w0, a1 = a0 + w1;
             int pick = 0x7fffffff, lastk = -1;
             if (k0) { lastk = i0v; if (a0 >= target) pick = i0v; }
@@ -225,6 +233,8 @@ __global__ __launch_bounds__(kGreedyThreads) void k_sample_greedy(SampleCall cv,
     const float* lg = C.logits + (size_t)b * V;
     int32_t* ids = C.ids + (size_t)b * C.ids_stride;
     const int len = C.ids_len[b];
+    const float rep_pen = C.rows ? C.rows[b].repetition_penalty : C.p.repetition_penalty;
+    const float temp = C.rows ? C.rows[b].temperature : C.p.temperature;
     // this thread's logits are requested before the id pass (they do not depend on it)
     constexpr int PER = kSortN / kGreedyThreads;
     float v[PER];
@@ -243,8 +253,8 @@ __global__ __launch_bounds__(kGreedyThreads) void k_sample_greedy(SampleCall cv,
         const int i = tid + u * kGreedyThreads;
         if (i < V) {
             float x = v[u];
-            if (seen[i]) x = x < 0.f ? x * C.p.repetition_penalty : x / C.p.repetition_penalty;
-            x = x / C.p.temperature;
+            if (seen[i]) x = x < 0.f ? x * rep_pen : x / rep_pen;
+            x = x / temp;
             if (x > bv || (x == bv && i < bi)) { bv = x; bi = i; }
         }
     }
@@ -272,6 +282,33 @@ __global__ __launch_bounds__(kGreedyThreads) void k_sample_greedy(SampleCall cv,
         for (int k = tid * 4; k < C.d; k += kGreedyThreads * 4) *reinterpret_cast<float4*>(dst + k) = *reinterpret_cast<const float4*>(src + k);
     }
 }
+__global__ void k_stage_rows(gvc_row_sampling* dst, SampleRows src, int B) {
+    if ((int)threadIdx.x < B) dst[threadIdx.x] = src.r[threadIdx.x];
+}
+
+int check_sample_rows(const gvc_row_sampling* rows, int B, int vocab, bool* all_greedy) {
+    GVC_REQUIRE(rows && B >= 1 && B <= kMaxSampleRows, GVC_ERR_ARG, "sample rows: need 1..%d host rows, got %d", kMaxSampleRows, B);
+    bool g = true;
+    for (int b = 0; b < B; ++b) {
+        const gvc_row_sampling& r = rows[b];
+        GVC_REQUIRE(r.temperature > 0.f && r.top_k <= vocab && r.repetition_penalty > 0.f, GVC_ERR_ARG,
+                    "sample rows: row %d has temperature %g, top_k %d (vocab %d), repetition_penalty %g", b, (double)r.temperature,
+                    r.top_k, vocab, (double)r.repetition_penalty);
+        g = g && r.top_k == 1;
+    }
+    *all_greedy = g;
+    return GVC_OK;
+}
+
+int launch_stage_rows(gvc_row_sampling* dst, const gvc_row_sampling* rows, int B, hipStream_t s) {
+    SampleRows sr;
+    memset(&sr, 0, sizeof(sr));
+    memcpy(sr.r, rows, (size_t)B * sizeof(gvc_row_sampling));
+    hipLaunchKernelGGL(k_stage_rows, dim3(1), dim3(kMaxSampleRows), 0, s, dst, sr, B);
+    GVC_LAUNCH_CHECK();
+    return GVC_OK;
+}
+
 int launch_sample(const SampleCall& sc, hipStream_t s) {
     GVC_REQUIRE(sc.p.vocab > 0 && sc.p.vocab <= kSortN, GVC_ERR_UNSUPPORTED, "sample: vocab %d > %d", sc.p.vocab, kSortN);
     if (sample_greedy_ok(sc.p.top_k, sc.latents_out ? sc.d : 0)) hipLaunchKernelGGL(k_sample_greedy, dim3(sc.B), dim3(kGreedyThreads), 0, s, sc, (const SampleCall*)nullptr);
@@ -300,4 +337,31 @@ extern "C" int gvc_sample(const float* logits, int32_t B, int32_t* ids, int32_t 
     sc.logits = logits; sc.B = B; sc.ids = ids; sc.ids_stride = ids_stride; sc.ids_len = ids_len;
     sc.finished = finished; sc.p = *p; sc.step = step; sc.tok_out = tok_out;
     return gvc::launch_sample(sc, (hipStream_t)s);
+}
+
+extern "C" int gvc_sample_rows(const float* logits, int32_t B, int32_t* ids, int32_t ids_stride, int32_t* ids_len,
+                               int32_t* finished, const gvc_sample_params* common, const gvc_row_sampling* rows, int32_t step,
+                               int32_t* tok_out, gvc_stream sv) {
+    GVC_REQUIRE(logits && ids && ids_len && finished && common && tok_out && B >= 1, GVC_ERR_ARG, "gvc_sample_rows: bad argument");
+    bool greedy = false;
+    int rc = gvc::check_sample_rows(rows, B, common->vocab, &greedy);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)sv;
+    // the rows need device memory for the duration of this call only: a stream-ordered allocation, freed behind the sampler launch
+    // (no synchronisation; this context-free entry point serves tests and callers that sample themselves, not the generation loop)
+    gvc_row_sampling* d_rows = nullptr;
+    GVC_CHECK_HIP(hipMallocAsync((void**)&d_rows, (size_t)B * sizeof(gvc_row_sampling), s));
+    rc = gvc::launch_stage_rows(d_rows, rows, B, s);
+    if (rc == GVC_OK) {
+        gvc::SampleCall sc;
+        memset(&sc, 0, sizeof(sc));
+        sc.logits = logits; sc.B = B; sc.ids = ids; sc.ids_stride = ids_stride; sc.ids_len = ids_len;
+        sc.finished = finished; sc.p = *common; sc.step = step; sc.tok_out = tok_out; sc.rows = d_rows;
+        sc.p.top_k = greedy ? 1 : 0;          // (kernel choice only: every row's settings come from d_rows)
+        rc = gvc::launch_sample(sc, s);
+    }
+    const hipError_t e = hipFreeAsync(d_rows, s);
+    if (rc) return rc;
+    GVC_CHECK_HIP(e);
+    return GVC_OK;
 }

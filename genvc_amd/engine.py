@@ -23,6 +23,25 @@ def sample_params(sampling, vocab, eos, seed=0):
                              float(sampling["top_p"]), int(sampling["top_k"]), int(eos), int(vocab), int(seed))
 
 
+def row_sampling(rows):
+    """rows: an iterable of per-row settings and keys, each a mapping with repetition_penalty, temperature, top_p,
+    top_k, seed, rng_row (the row's index inside its job) and rng_step0 (tokens its stream has drawn before this call) ->
+    a gvc_row_sampling array (include/genvc_hip.h)"""
+    rows = list(rows)
+    arr = (_lib.RowSampling * len(rows))()
+    for i, r in enumerate(rows):
+        arr[i] = _lib.RowSampling(float(r["repetition_penalty"]), float(r["temperature"]), float(r["top_p"]), int(r["top_k"]),
+                                  int(r["seed"]), int(r["rng_row"]), int(r["rng_step0"]))
+    return arr
+
+
+def _rows_arg(rows, B):
+    arr = rows if isinstance(rows, C.Array) else row_sampling(rows)
+    if len(arr) != B:
+        raise ValueError(f"{len(arr)} row entries for {B} rows")
+    return arr
+
+
 class GptEngine:
     """KV-cached GPT-2 stack of GenVC (reference layers/gpt.py + layers/gpt_inference.py)."""
 
@@ -154,6 +173,36 @@ class GptEngine:
         check(lib().gvc_gpt_generate(self._h, ptr(_i32(slots)), B, ptr(_i32(ids)), ids.shape[1], ptr(_i32(ids_len)),
                                      ptr(_i32(finished)), C.byref(params), i0, n_steps, int(max_keys), ptr(tokens_out),
                                      tokens_out.stride(0), ptr(latents_out), lat_stride, stream()), "generate")
+
+    def sample_rows(self, logits, ids, ids_len, finished, rows, step):
+        """sample() with per-row settings and RNG keys (include/genvc_hip.h: gvc_sample_rows): row b draws
+        rng_uniform(seed_b, rng_step0_b + step, rng_row_b).  rows: see row_sampling()"""
+        B = logits.shape[0]
+        arr = _rows_arg(rows, B)
+        common = sample_params(dict(repetition_penalty=1.0, temperature=1.0, top_p=1.0, top_k=0), self.V, self.dims["stop_audio_token"])
+        tok = torch.empty(B, device=logits.device, dtype=torch.int32)
+        check(lib().gvc_sample_rows(ptr(_f32(logits)), B, ptr(_i32(ids)), ids.shape[1], ptr(_i32(ids_len)), ptr(_i32(finished)),
+                                    C.byref(common), arr, int(step), ptr(tok), stream()), "sample_rows")
+        return tok
+
+    def generate_rows(self, slots, ids, ids_len, finished, rows, i0, n_steps, tokens_out, latents_out, max_keys=0):
+        """generate() with per-row settings and RNG keys (include/genvc_hip.h: gvc_gpt_generate_rows): tokens and latents of step i
+        land in column i0 + i as in generate(); row b draws rng_uniform(seed_b, rng_step0_b + i, rng_row_b), so its tokens do not
+        depend on which rows share the call.  rows: see row_sampling() (B entries, or a prepared gvc_row_sampling array)"""
+        self._join_side()
+        B = slots.shape[0]
+        arr = _rows_arg(rows, B)
+        assert tokens_out.is_cuda and tokens_out.dtype == torch.int32 and tokens_out.stride(1) == 1
+        lat_stride = 0
+        if latents_out is not None:
+            assert latents_out.is_cuda and latents_out.dtype == torch.float32 and latents_out.stride(2) == 1
+            assert latents_out.stride(1) == self.d and latents_out.stride(0) % self.d == 0
+            lat_stride = latents_out.stride(0) // self.d
+        common = sample_params(dict(repetition_penalty=1.0, temperature=1.0, top_p=1.0, top_k=0), self.V, self.dims["stop_audio_token"])
+        check(lib().gvc_gpt_generate_rows(self._h, ptr(_i32(slots)), B, ptr(_i32(ids)), ids.shape[1], ptr(_i32(ids_len)),
+                                          ptr(_i32(finished)), C.byref(common), arr, int(i0), int(n_steps), int(max_keys),
+                                          ptr(tokens_out), tokens_out.stride(0), ptr(latents_out), lat_stride, stream()),
+              "generate_rows")
 
     def decode_variant(self):
         """which decode step the last generate() call replayed (include/genvc_hip.h: gvc_gpt_decode_variant)"""

@@ -15,6 +15,13 @@ from ..engine import GptEngine, sample_params
 from .perceiver_encoder import PerceiverResampler
 
 
+# Sampled joint / rolling decodes key every row by its own stream (gvc_gpt_generate_rows), so they return the serial path's tokens exactly
+# when a row's logits on the rows step do not depend on how many rows share the step.  Measured on the one-launch rows step (d_model 1024):
+# they do depend on it (not bit-identical for 5 / 8 / 16 rows), so a near-tie draw can differ from the serial path and the joint sampled
+# decode stays opt-in (joint_sampling=True).  tests/test_gpu_row_sampling.py pins this flag to that measurement; DESIGN.md 4.6.
+JOINT_SAMPLING_DEFAULT = False
+
+
 class _Holder(nn.Module):
     pass
 
@@ -49,6 +56,8 @@ def _ln(d):
 
 
 class GPT(nn.Module):
+    rolling_samples = True          # generate_rolling samples with per-job keys (job_seeds): parallel_offline rolls sampled runs too
+
     def __init__(self, start_text_token=256, stop_text_token=257, layers=8, model_dim=512, heads=8,
                  max_text_tokens=120, max_mel_tokens=250, max_prompt_tokens=70, max_conditioning_inputs=1,
                  code_stride_len=1024, number_text_tokens=258, num_audio_tokens=1026, start_audio_token=1024,
@@ -233,9 +242,13 @@ class GPT(nn.Module):
         """Several generate() calls decoded TOGETHER: groups = [(cond_latents [B_i, 32, d], text_inputs [B_i, Tc_i]), ...] with
         different code lengths.  Each group is prefilled on its own (its rows share a prefix length) into its own KV slots; the
         decode steps then run over all streams at once, so the weights stream once per step for the whole set.  Streams are
-        independent, so with deterministic decoding (top_k = 1) every group's result is what generate() returns for it (bit for
-        bit when both land on the same decode kernels, i.e. the rows path from 5 streams up; within float rounding otherwise);
-        with sampling the per-row random streams would be numbered differently, so that case runs the groups one after another.
+        independent, so with greedy decoding every group's result is what generate() returns for it (bit for bit when both land on
+        the same decode kernels, i.e. the rows path from 5 streams up; within float rounding otherwise).  A sampling run draws class g
+        with its class seed -- class_seeds[g], else seed + 7919 * g (with one shared seed all classes would draw identical per-row
+        sequences) -- and by default runs the groups one after another (one generate() per group).  `joint_sampling=True` decodes them
+        jointly instead, row r of group g keyed (class seed, r, tokens drawn so far): the key generate(seed=class seed) gives it, so
+        each group draws what its own generate() draws from the same logits.  It is opt-in because the rows step's logits are not
+        bit-identical across row counts (JOINT_SAMPLING_DEFAULT): a draw within rounding of a CDF boundary can still differ.
         `max_new_tokens` may be a list with one budget per group (benchmark mode: synthetic weights seldom stop, SURVEY.md 8d fixes
         the tokens of a segment by its duration): a group whose budget is spent leaves the joint decode, and the steps that remain
         run over the live streams only (fewer rows per step: the 8-row instead of the 16-row one-launch step for configs[2]'s tail).
@@ -244,6 +257,7 @@ class GPT(nn.Module):
         kw = dict(generate_kwargs)
         group = kw.pop("group", 16)          # decode steps per engine call (one host look at the finished flags per call)
         class_seeds = kw.pop("class_seeds", None)      # sampling runs: one seed per group (default: seed + 7919 * group index)
+        joint_sampling = bool(kw.pop("joint_sampling", JOINT_SAMPLING_DEFAULT))
         budgets = kw.get("max_new_tokens")
         if isinstance(budgets, (list, tuple)):
             if len(budgets) != len(groups):
@@ -255,26 +269,34 @@ class GPT(nn.Module):
         greedy = kw.get("top_k", 0) == 1 or not kw.get("do_sample", True)
         total = sum(int(t.shape[0]) for _, t in groups)
         stats = getattr(self, "groups_stats", None)        # {"joint": n, "separate": n}: bench.py / tests count the two paths
-        if not greedy or len(groups) == 1 or total > self.max_slots or kw.get("num_beams", 1) != 1:
+        seeds = None
+        if not greedy:
+            # Seed semantics: class gi of THIS call draws with class_seeds[gi] when the caller numbers its classes across calls
+            # (parallel_offline.convert_batch does: several calls per job), else with seed + 7919 * gi
+            seeds = [int(class_seeds[gi]) if class_seeds is not None else int(kw.get("seed", 0)) + 7919 * gi for gi in range(len(groups))]
+        if (not greedy and not joint_sampling) or len(groups) == 1 or total > self.max_slots or kw.get("num_beams", 1) != 1:
             if stats is not None and len(groups) > 1:
                 stats["separate"] += 1
             # one generate() per class; a sampling run gives every class its own random stream (the rows of one class keep the
-            # per-row numbering of the counter RNG): with one shared seed all classes would draw identical per-row sequences.
-            # Seed semantics: class gi of THIS call draws with class_seeds[gi] when the caller numbers its classes across calls
-            # (parallel_offline.convert_batch does: several calls per job), else with seed + 7919 * gi
+            # per-row numbering of the counter RNG)
             outs = []
             for gi, (c, t) in enumerate(groups):
                 kg = dict(kw)
                 if not greedy:
-                    kg["seed"] = int(class_seeds[gi]) if class_seeds is not None else int(kw.get("seed", 0)) + 7919 * gi
+                    kg["seed"] = seeds[gi]
                 if budgets is not None:
                     kg["max_new_tokens"] = budgets[gi]
                 outs.append(self.generate(c, t, **kg))
             self.last_latents = None      # (same contract as the joint path: callers of generate_groups want tokens)
             return outs
-        return self._recovering(total, lambda: self._generate_groups_joint(groups, kw, budgets, group, stats))
+        return self._recovering(total, lambda: self._generate_groups_joint(groups, kw, budgets, group, stats, seeds))
 
-    def _generate_groups_joint(self, groups, kw, budgets, group, stats):
+    def _row_settings(self, kw):
+        """the processor settings generate() would use for these kwargs (see _start), as a gvc_row_sampling entry without its key"""
+        return dict(repetition_penalty=kw.get("repetition_penalty", 1.0), temperature=kw.get("temperature", 1.0),
+                    top_p=kw.get("top_p", 1.0), top_k=kw.get("top_k", 0) if kw.get("do_sample", True) else 1)
+
+    def _generate_groups_joint(self, groups, kw, budgets, group, stats, seeds=None):
         total = sum(int(t.shape[0]) for _, t in groups)
         if stats is not None:
             stats["joint"] += 1
@@ -283,6 +305,7 @@ class GPT(nn.Module):
         # rows in order of falling budget: the live streams are always the first rows of every buffer
         order = sorted(range(len(groups)), key=lambda i: -(budgets[i] if budgets else max_new))
         groups = [groups[i] for i in order]
+        seeds = [seeds[i] for i in order] if seeds is not None else None
         gb = [budgets[i] if budgets else max_new for i in order]
         prefixes = [self.engine.prefix_embeddings(c.to(torch.float32).contiguous(), t.to(torch.int32).contiguous()) for c, t in groups]
         n0s = [int(p.shape[1]) + 1 for p in prefixes]
@@ -305,13 +328,21 @@ class GPT(nn.Module):
         samp = dict(repetition_penalty=kw.get("repetition_penalty", 1.0), temperature=kw.get("temperature", 1.0),
                     top_p=kw.get("top_p", 1.0), top_k=1)
         params = sample_params(samp, self.num_audio_tokens, self.stop_audio_token, kw.get("seed", 0))
+        rs = self._row_settings(kw)
         done = 0
         while done < max_new:
             live_groups = [g for g in range(len(groups)) if gb[g] > done]
             live = spans[live_groups[-1]][1]                                   # rows [0, live) still have tokens to produce
             n = min(group, min(gb[g] for g in live_groups) - done)              # (a call never crosses the end of a budget)
-            self.engine.generate(slots[:live], ids[:live], ids_len[:live], finished[:live], params, done, n, toks[:live], lats[:live],
-                                 max_keys=max(n0s[g] for g in live_groups) + done + n)
+            mk = max(n0s[g] for g in live_groups) + done + n
+            if seeds is None:
+                self.engine.generate(slots[:live], ids[:live], ids_len[:live], finished[:live], params, done, n, toks[:live], lats[:live],
+                                     max_keys=mk)
+            else:
+                # sampling: row r of class g is keyed (class seed, r, done) -- what generate(seed=class seed) draws for it
+                rows = [dict(rs, seed=seeds[g], rng_row=r, rng_step0=done) for g in live_groups for r in range(spans[g][1] - spans[g][0])]
+                self.engine.generate_rows(slots[:live], ids[:live], ids_len[:live], finished[:live], rows, done, n, toks[:live], lats[:live],
+                                          max_keys=mk)
             done += n
             stop = bool(finished[:live].all().item())
             self.engine.health()
@@ -326,7 +357,7 @@ class GPT(nn.Module):
 
     @torch.inference_mode()
     def generate_rolling(self, jobs, **generate_kwargs):
-        """generate_groups with a ROLLING set of streams (greedy decoding only): jobs = [(cond_latents [B_i, 32, d], text_inputs
+        """generate_groups with a ROLLING set of streams: jobs = [(cond_latents [B_i, 32, d], text_inputs
         [B_i, Tc_i]), ...] are admitted in order as KV slots become free.  Retirement is PER ROW, as the reference's loop tracks
         `unfinished_sequences` per row (stream_generator.py:861-874): a row that has emitted the stop token gives its KV slot back at
         the next host look (every `group` steps) and stops taking a row of the decode step; the rows of a job whose budget is spent
@@ -336,14 +367,23 @@ class GPT(nn.Module):
         generate() returns for it: finished rows padded with the stop token up to the step where the job's last row stops
         (reference gpt.py:594-609).  `max_new_tokens`: one budget, or a list with one per job.  Returns a list of int64 [B_i, n_i]
         in job order.  `self.rolling_stats` (if the attribute is a dict) accumulates row_steps_issued / row_steps_live: rows x steps
-        the decode calls ran, and how many of them produced a token the reference's loop would have produced."""
+        the decode calls ran, and how many of them produced a token the reference's loop would have produced.
+        Sampling (top_k != 1) needs `job_seeds`, one per job: row r of job j is keyed (job_seeds[j], r, tokens job j has drawn), so
+        job j draws what generate(c_j, t_j, seed=job_seeds[j]) draws from the same logits, whatever it shares the decode step with (the
+        rows step's logits themselves are not bit-identical across row counts: JOINT_SAMPLING_DEFAULT).  Without job_seeds a sampling
+        call raises NotImplementedError."""
         self._need_engine()
         kw = dict(generate_kwargs)
         group = kw.pop("group", 16)
         kw.pop("class_seeds", None)
+        job_seeds = kw.pop("job_seeds", None)
         max_rows = kw.pop("max_rows", None)      # streams in flight at most (default: every KV slot of the context)
-        if not (kw.get("top_k", 0) == 1 or not kw.get("do_sample", True)) or kw.get("num_beams", 1) != 1:
-            raise NotImplementedError("generate_rolling serves greedy decoding (top_k = 1): with sampling use generate_groups")
+        greedy = kw.get("top_k", 0) == 1 or not kw.get("do_sample", True)
+        if (not greedy and job_seeds is None) or kw.get("num_beams", 1) != 1:
+            raise NotImplementedError("generate_rolling samples with one seed per job (job_seeds=...); without them it serves greedy "
+                                      "decoding (top_k = 1) only")
+        if job_seeds is not None and len(job_seeds) != len(jobs):
+            raise ValueError(f"generate_rolling: {len(job_seeds)} job seeds for {len(jobs)} jobs")
         budgets = kw.get("max_new_tokens")
         if isinstance(budgets, (list, tuple)):
             if len(budgets) != len(jobs):
@@ -358,9 +398,10 @@ class GPT(nn.Module):
         S = min(self.max_slots, int(max_rows)) if max_rows else self.max_slots
         if max(int(t.shape[0]) for _, t in jobs) > S:
             raise ValueError(f"generate_rolling: a job has more rows than streams may be in flight ({S}; KV slots {self.max_slots})")
-        return self._recovering(S, lambda: self._rolling(jobs, kw, budgets, group, n0s, width, S))
+        seeds = None if greedy else [int(x) for x in job_seeds]
+        return self._recovering(S, lambda: self._rolling(jobs, kw, budgets, group, n0s, width, S, seeds))
 
-    def _rolling(self, jobs, kw, budgets, group, n0s, width, S):
+    def _rolling(self, jobs, kw, budgets, group, n0s, width, S, seeds=None):
         dev = jobs[0][1].device
         eng = self.engine
         stop = self.stop_audio_token
@@ -370,6 +411,7 @@ class GPT(nn.Module):
         samp = dict(repetition_penalty=kw.get("repetition_penalty", 1.0), temperature=kw.get("temperature", 1.0),
                     top_p=kw.get("top_p", 1.0), top_k=1)
         params = sample_params(samp, self.num_audio_tokens, stop, kw.get("seed", 0))
+        rs = self._row_settings(kw)
         stats = getattr(self, "groups_stats", None)
         rstats = getattr(self, "rolling_stats", None)
         free = list(range(S))
@@ -401,7 +443,12 @@ class GPT(nn.Module):
             ids_len = len_all[idx].contiguous()
             fin = fin_all[idx].contiguous()
             toks = torch.full((len(row_slots), n), stop, device=dev, dtype=torch.int32)
-            eng.generate(rows, ids, ids_len, fin, params, 0, n, toks, None, max_keys=W - 8)
+            if seeds is None:
+                eng.generate(rows, ids, ids_len, fin, params, 0, n, toks, None, max_keys=W - 8)
+            else:
+                # row r of job j keyed (job seed, r, tokens the job has drawn): the key generate(seed=job_seeds[j]) gives that row
+                keys = [dict(rs, seed=seeds[j["job"]], rng_row=r, rng_step0=j["done"]) for j in live for r in j["alive"]]
+                eng.generate_rows(rows, ids, ids_len, fin, keys, 0, n, toks, None, max_keys=W - 8)
             ids_all[idx, :W] = ids
             len_all[idx] = ids_len
             fin_all[idx] = fin

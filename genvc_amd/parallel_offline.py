@@ -11,6 +11,7 @@ import torch.distributed as dist
 import torch.nn.functional as F
 
 from .inference.inference_utils import segments, _sampling_kwargs
+from .layers.gpt import JOINT_SAMPLING_DEFAULT
 
 
 def plan(lengths, rank, world):
@@ -56,8 +57,9 @@ def convert_batch(model, src_wavs, cond_latent, seg_len=6.0, max_len=None, n_seg
     one class (same prefix length: all full segments of the batch, and equal-length tails), prefilled in one batched call;
     tails of other lengths are classes of their own -- never padded, which would change the reference's result
     (inference_utils.py:43-50).  With greedy decoding (top_k = 1, the configuration BASELINE configs[2] names) the classes are
-    then decoded TOGETHER, as many per joint decode as the context has KV slots; a sampling run (top_k > 1) decodes one class
-    after another, each with its own random stream (layers/gpt.py generate_groups).
+    then decoded TOGETHER, as many per joint decode as the context has KV slots.  A sampling run (top_k > 1) gives every class its own
+    random stream and decodes one class after another, or -- joint_sampling=True -- together with every row keyed by its class's stream
+    (layers/gpt.py generate_groups).
     tokens_per_second (benchmark mode, SURVEY.md 8d: synthetic weights seldom emit the stop token): a class of segments of t seconds
     gets the fixed budget round(t * tokens_per_second) instead of max_new_tokens (23.4375: 141 tokens for 6 s, 94 for 4 s); a class
     whose budget is spent leaves the joint decode.
@@ -128,12 +130,15 @@ def _wave_classes(m, src_wavs, seg, min_len, n_seg):
 
 
 @torch.inference_mode()
-def convert_rolling(model, src_wavs, cond_latent, seg_len=6.0, micro_batch=8, max_len=None, n_seg=None, tokens_per_second=None, **gen_kwargs):
-    """convert_batch over ALL of a rank's utterances with a rolling decode (layers/gpt.py generate_rolling; greedy decoding): the
+def convert_rolling(model, src_wavs, cond_latent, seg_len=6.0, micro_batch=8, max_len=None, n_seg=None, tokens_per_second=None, utt_ids=None,
+                    **gen_kwargs):
+    """convert_batch over ALL of a rank's utterances with a rolling decode (layers/gpt.py generate_rolling): the
     utterances are taken in waves of `micro_batch` -- a wave shares its ContentVec / DVAE / prefill calls per (segment, length) class
     exactly as in convert_batch -- but a class joins the decode as soon as KV slots are free and leaves it when its budget is spent or
     its rows have stopped, so the step keeps 2 x micro_batch rows busy across wave boundaries instead of draining to the longest class
-    of every wave.  Same tokens as convert_batch (streams are independent given their prefix).  Returns int32 [n, n_seg, max_len]."""
+    of every wave.  Same tokens as convert_batch (streams are independent given their prefix).  utt_ids: the utterances' indices in the
+    whole job (default 0..n-1); a sampling run keys every class by the seed convert_batch gives it, seed + 7919 * (u * n_seg + s) with
+    u the job index of the class's first utterance (generate_rolling's job_seeds).  Returns int32 [n, n_seg, max_len]."""
     m = model
     stop = m.gpt.stop_audio_token
     max_len = max_len or m.gpt.max_gen_mel_tokens
@@ -144,13 +149,17 @@ def convert_rolling(model, src_wavs, cond_latent, seg_len=6.0, micro_batch=8, ma
     kw = dict(_sampling_kwargs(m))
     kw.update(gen_kwargs)
     cap = kw.get("max_new_tokens") or max_len
-    jobs, where, budgets = [], [], []
+    ids = list(range(len(src_wavs))) if utt_ids is None else list(utt_ids)
+    jobs, where, budgets, seeds = [], [], [], []
     for i in range(0, len(src_wavs), micro_batch):
         for s, rows, codes, ns in _wave_classes(m, src_wavs[i:i + micro_batch], seg, min_len, n_seg):
             jobs.append((cond_latent.expand(len(rows), -1, -1).contiguous(), codes))
             where.append((s, [i + r for r in rows]))
             budgets.append(max(1, min(cap, int(round(ns / m.content_sample_rate * tokens_per_second)))) if tokens_per_second else cap)
+            seeds.append(int(kw.get("seed", 0)) + 7919 * (ids[i + rows[0]] * n_seg + s))
     kw["max_new_tokens"] = budgets
+    if not (kw.get("top_k", 0) == 1 or not kw.get("do_sample", True)):
+        kw["job_seeds"] = seeds
     # streams in flight: what one wave holds (its classes decoded jointly, as in convert_batch) -- the rolling decode never runs a
     # larger step than the fixed micro-batch does, it only keeps that step full
     kw.setdefault("max_rows", max(max(len(r) for _, r in where), min(n_seg * micro_batch, getattr(m.gpt, "max_slots", 8))))
@@ -164,8 +173,9 @@ def convert_rolling(model, src_wavs, cond_latent, seg_len=6.0, micro_batch=8, ma
 def convert_offline(model, src_wavs, ref_audio, seg_len=6.0, micro_batch=8, rank=0, world=1, process_group=None, **gen_kwargs):
     """All utterances of the job (any lengths), sharded by rank (see plan), in waves of `micro_batch`; no collective while
     converting, ONE all_gather of the padded token ids at the end.  Returns int32 [n_utts, n_seg, max_len] on every rank.
-    rolling (gen_kwargs, default False): greedy runs only -- decode with a rolling set of streams (convert_rolling) instead of one joint
-    decode per wave: same tokens, no drain at the end of every wave.
+    rolling (gen_kwargs, default False): decode with a rolling set of streams (convert_rolling) instead of one joint decode per wave:
+    same tokens, no drain at the end of every wave.  A sampling run rolls only with joint_sampling=True (its rows then keyed per class,
+    as generate_groups(joint_sampling=True) keys them); otherwise it keeps the waves.
     process_group: the torch.distributed group of the all_gather (default: the world).  Everything in gen_kwargs goes to
     GPT.generate_groups -- including its `group` (decode steps per host look at the finished flags), which this function's
     process-group parameter used to shadow: with `group=48` in the kwargs every N > 1 run died in the all_gather."""
@@ -181,9 +191,14 @@ def convert_offline(model, src_wavs, ref_audio, seg_len=6.0, micro_batch=8, rank
     n_seg = max(_n_segments(n, seg) for n in lengths)
     max_len = m.gpt.max_gen_mel_tokens
     local = torch.full((len(mine), n_seg, max_len), m.gpt.stop_audio_token, dtype=torch.int32, device=m.device)
-    rolling = bool(gen_kwargs.pop("rolling", False)) and gen_kwargs.get("top_k", m.config.top_k) == 1 and hasattr(m.gpt, "generate_rolling")
+    # a sampling run rolls when joint sampled decodes are asked for (joint_sampling, default layers/gpt.py JOINT_SAMPLING_DEFAULT) and the
+    # GPT keys its rows per job (generate_rolling(job_seeds=...): GPT.rolling_samples); otherwise it keeps the wave-by-wave driver
+    greedy = gen_kwargs.get("top_k", m.config.top_k) == 1 or not gen_kwargs.get("do_sample", True)
+    keyed = getattr(m.gpt, "rolling_samples", False) and bool(gen_kwargs.get("joint_sampling", JOINT_SAMPLING_DEFAULT))
+    rolling = bool(gen_kwargs.pop("rolling", False)) and (greedy or keyed) and hasattr(m.gpt, "generate_rolling")
     if rolling and mine:
-        local[:] = convert_rolling(m, [src_wavs[j] for j in mine], cond, seg_len, micro_batch, max_len, n_seg, **gen_kwargs)
+        gen_kwargs.pop("joint_sampling", None)
+        local[:] = convert_rolling(m, [src_wavs[j] for j in mine], cond, seg_len, micro_batch, max_len, n_seg, utt_ids=mine, **gen_kwargs)
         return gather_token_ids(local, len(src_wavs), m.gpt.stop_audio_token, rank, world, process_group, lengths)
     for i in range(0, len(mine), micro_batch):
         wave = mine[i:i + micro_batch]

@@ -13,7 +13,7 @@ per open stream and, at every `step()`, batches whatever the open streams need n
     `handle_chunks` does inside `synthesize_utt_streaming`.
 
 Each stream produces the tokens and the waveform of `synthesize_utt_streaming(model, its_source, its_reference,
-seg_len)` at top_k = 1.
+seg_len)` at top_k = 1, and with per_session_sampling at any settings (see below).
 
 `left_context_s` (extension beyond the reference, SURVEY.md 8f row f4: "chunked ContentVec with left context"): the reference feeds
 ContentVec one segment at a time, so the first frames of every segment see no past (its positional conv spans +-64 frames =
@@ -22,7 +22,12 @@ that many seconds of its already fed source audio (a multiple of 320 samples, Co
 [kept past | new segment], passing only the segment's frames on to the content tokeniser; frame i of the window starts at sample
 320 i, so the segment's frames are exactly the last ones.  The default (0) is the reference's behaviour.
 
-With top_k > 1 the draws differ from a solo run: the counter RNG is keyed by the position in the call, not in the utterance.
+Sampling (top_k != 1).  By default every session shares the model config's settings and each decode call draws with a fresh
+seed, keyed by the row's position in the call: with top_k > 1 a session's draws then depend on which other sessions shared its
+steps, and differ from a solo run.  With `per_session_sampling=True` every session has its own settings and seed
+(`open(ref_audio, sampling={...}, seed=s)`) and its row is keyed by its own stream -- (seed, 0, tokens of the segment drawn so far),
+the key `synthesize_utt_streaming` gives a lone stream -- so its tokens are those of its solo run with the same settings, whoever
+shares its steps, and a segment re-run after a recovered time-out draws the same tokens again.
 """
 import time
 
@@ -48,7 +53,8 @@ class _Session:
 
 
 class StreamSessions:
-    def __init__(self, model, max_sessions=8, group=8, left_context_s=0.0, rearm_after_s=5.0, rearm_max_tries=3, prefill_speaker=True):
+    def __init__(self, model, max_sessions=8, group=8, left_context_s=0.0, rearm_after_s=5.0, rearm_max_tries=3, prefill_speaker=True,
+                 per_session_sampling=False):
         m = self.m = model
         self.ctx = int(round(left_context_s * model.content_sample_rate / 320.0)) * 320       # whole ContentVec hops
         g = m.gpt
@@ -64,6 +70,8 @@ class StreamSessions:
         kw = _sampling_kwargs(m)
         samp = dict(repetition_penalty=kw["repetition_penalty"], temperature=kw["temperature"], top_p=kw["top_p"], top_k=kw["top_k"])
         self.params = sample_params(samp, g.num_audio_tokens, g.stop_audio_token, 0)
+        self.default_sampling = samp
+        self.per_session_sampling = bool(per_session_sampling)    # every session its own settings and RNG stream (gvc_gpt_generate_rows)
         self.calls = 0
         self.recoveries = 0          # decode calls dropped and re-run after a hand-off time-out (gvc_gpt_health)
         self._rearm = False          # a recovery happened: the one-launch steps may be re-armed (policy: maybe_rearm)
@@ -83,14 +91,27 @@ class StreamSessions:
 
     # ------------------------------------------------------------------------------------------
     @torch.inference_mode()
-    def open(self, ref_audio):
-        """ref_audio [1, n] at the model rate -> session id"""
+    def open(self, ref_audio, sampling=None, seed=0):
+        """ref_audio [1, n] at the model rate -> session id.  With per_session_sampling: `sampling` (top_k, top_p, temperature,
+        repetition_penalty; missing keys come from the model config) and `seed` are this session's own; otherwise passing either raises."""
+        if not self.per_session_sampling and (sampling is not None or seed != 0):
+            raise ValueError("open(sampling=..., seed=...) needs StreamSessions(..., per_session_sampling=True): this scheduler samples "
+                             "every session with the model config's settings")
+        samp = dict(self.default_sampling)
+        if sampling is not None:
+            unknown = set(sampling) - set(samp)
+            if unknown:
+                raise ValueError(f"open: unknown sampling settings {sorted(unknown)} (known: {sorted(samp)})")
+            samp.update(sampling)
+            if not float(samp["temperature"]) > 0.0 or int(samp["top_k"]) > self.m.gpt.num_audio_tokens:
+                raise ValueError(f"open: temperature must be > 0 and top_k <= {self.m.gpt.num_audio_tokens}, got {samp}")
         if not self.free:
             raise RuntimeError("no free stream slot")
         cond = self.m.get_gpt_cond_latents(ref_audio.to(self.m.device), self.m.config.audio.sample_rate)
         sid = self._next_id
         self._next_id += 1
         s = self.sessions[sid] = _Session(self.free.pop(0), cond)
+        s.sampling, s.seed = samp, int(seed)
         if self.prefill_speaker:
             # the speaker is known before the first source segment arrives: its 32 conditioning rows go into the slot's KV cache NOW
             # (gvc_gpt_prefill_cond), so the first segment too computes only its text rows + start token -- the first audio chunk of a
@@ -178,7 +199,8 @@ class StreamSessions:
         started in this step goes back to the start of its segment (slots reset), and the next step() re-runs them on the
         launch-per-phase paths the library has switched to.  Greedy decoding repeats the tokens, so the audio continues where it
         stopped; with top_k > 1 the re-run draws with new per-call seeds -- the groups already emitted are skipped, what follows
-        comes from a different token sequence (an audible splice is possible)."""
+        comes from a different token sequence (an audible splice is possible) -- unless per_session_sampling keys every session by its
+        own stream, in which case the re-run draws the same tokens too."""
         self._popped = []
         self.maybe_rearm()           # (a no-op unless a time-out recovery is pending, the scheduler is idle and the back-off has run out)
         try:
@@ -254,9 +276,14 @@ class StreamSessions:
         B = len(act)
         toks = torch.full((B, n), self.stop, device=dev, dtype=torch.int32)
         lats = torch.empty(B, n, m.gpt.model_dim, device=dev, dtype=torch.float32)
-        self.params.seed = self.calls          # a fresh counter-RNG stream per call (only matters for top_k > 1)
         self.calls += 1
-        eng.generate(slots, ids, ids_len, fin, self.params, 0, n, toks, lats, max_keys=W - 8)
+        if self.per_session_sampling:
+            # each session's row keyed by its own stream: (its seed, row 0 of a lone stream, tokens of this segment drawn so far)
+            rows = [dict(s.sampling, seed=s.seed, rng_row=0, rng_step0=s.done) for _, s in act]
+            eng.generate_rows(slots, ids, ids_len, fin, rows, 0, n, toks, lats, max_keys=W - 8)
+        else:
+            self.params.seed = self.calls - 1      # a fresh counter-RNG stream per call (only matters for top_k > 1)
+            eng.generate(slots, ids, ids_len, fin, self.params, 0, n, toks, lats, max_keys=W - 8)
         th = toks.cpu()                                           # (synchronises: the steps above have run)
         # a hand-off of the one-launch step that timed out (not all workgroups resident, e.g. another context on the GPU) raises here:
         # these tokens and latents are garbage and so are the K/V rows the steps appended.  Nothing of this call is kept or vocoded

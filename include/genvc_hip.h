@@ -175,6 +175,25 @@ int gvc_sample(const float* logits, int32_t B, int32_t* ids, int32_t ids_stride,
                int32_t* finished, const gvc_sample_params* p, int32_t step, int32_t* tok_out,
                gvc_stream s);
 
+/* Per-row sampling settings and RNG key (no reference counterpart: the reference decodes one stream per call).  A row that
+ * belongs to stream `rng_row` of a job keyed `seed` draws rng_uniform(seed, rng_step0 + i, rng_row) at step i of a call, so its
+ * tokens do not depend on which other rows share the call or where in the batch it sits.  The layout is fixed: 32 bytes,
+ * seed at offset 16. */
+typedef struct gvc_row_sampling {
+    float repetition_penalty, temperature, top_p;   /* as gvc_sample_params; temperature > 0 */
+    int32_t top_k;                                  /* as gvc_sample_params; <= vocab */
+    uint64_t seed;                                  /* RNG key of the row's stream */
+    int32_t rng_row;                                /* the row's index inside ITS job (0 for a lone stream) */
+    int32_t rng_step0;                              /* tokens this stream has already drawn (its RNG counter at step 0 of this call) */
+} gvc_row_sampling;
+
+/* gvc_sample with per-row settings and keys.  rows: HOST array of B (<= 64) entries, free for reuse when the call returns;
+ * common supplies eos_token and vocab only (its other fields are ignored).  Row b draws rng_uniform(rows[b].seed,
+ * rows[b].rng_step0 + step, rows[b].rng_row).  A row with top_k == 1 gets the argmax token gvc_sample gives it at top_k = 1. */
+int gvc_sample_rows(const float* logits, int32_t B, int32_t* ids, int32_t ids_stride, int32_t* ids_len, int32_t* finished,
+                    const gvc_sample_params* common, const gvc_row_sampling* rows, int32_t step, int32_t* tok_out,
+                    gvc_stream s);
+
 /* ------------------------------------------------------------------------------------------
  * Fused generation loop: prefill state -> n_steps x (sample, decode step) replayed from one
  * captured hipGraph with all step state on the device (no host sync per token; the reference
@@ -199,6 +218,17 @@ int gvc_gpt_generate(gvc_gpt* ctx, const int32_t* slots, int32_t B, int32_t* ids
                      int32_t* ids_len, int32_t* finished, const gvc_sample_params* p, int32_t i0,
                      int32_t n_steps, int32_t max_keys, int32_t* tokens_out, int32_t tok_stride, float* latents_out,
                      int32_t lat_stride, gvc_stream s);
+
+/* gvc_gpt_generate with per-row settings and RNG keys (see gvc_row_sampling): rows is a HOST array of B (<= 64) entries, copied
+ * into the call's device state by the call's first launch (a kernel argument: the caller may reuse the array as soon as the call
+ * returns; no allocation and no synchronisation per call).  common supplies eos_token and vocab only.  Tokens and latents land
+ * at column i0 + i as in gvc_gpt_generate; only the RNG counter is per row (rng_step0 + i).  The same captured step graphs serve
+ * both calls: the greedy sampler when every row has top_k == 1, the sampling one otherwise (gvc_gpt_warmup with top_k 1 / not 1).
+ * With rows[b] = {p's settings, p->seed, b, i0} for every b the result is bit-identical to gvc_gpt_generate(p, i0). */
+int gvc_gpt_generate_rows(gvc_gpt* ctx, const int32_t* slots, int32_t B, int32_t* ids, int32_t ids_stride, int32_t* ids_len,
+                          int32_t* finished, const gvc_sample_params* common, const gvc_row_sampling* rows, int32_t i0,
+                          int32_t n_steps, int32_t max_keys, int32_t* tokens_out, int32_t tok_stride, float* latents_out,
+                          int32_t lat_stride, gvc_stream s);
 
 /* Which decode step the last gvc_gpt_generate call replayed (diagnostic): 0 none yet, 1 launch-per-phase with split-key attention,
  * 2 launch-per-phase with the fused short-context attention launch, 3 the one-launch step (one stream), 4 the MFMA rows path
