@@ -28,6 +28,14 @@ class RowSampling(C.Structure):
                 ("seed", C.c_uint64), ("rng_row", C.c_int32), ("rng_step0", C.c_int32)]
 
 
+class BeamState(C.Structure):
+    """gvc_beam_state (include/genvc_hip.h): sizes, settings and the device arrays of one beam search"""
+    _fields_ = [(n, C.c_int32) for n in ("B", "K", "vocab", "eos", "n0", "ids_stride", "max_new", "length_mode")] + \
+        [("length_penalty", C.c_float), ("repetition_penalty", C.c_float)] + \
+        [(n, C.c_void_p) for n in ("ids", "scores", "tokens", "parents", "done", "hyp_score", "hyp_len", "hyp_tok", "hyp_count",
+                                   "hyp_worst", "copies", "n_copies")]
+
+
 class PerceiverDims(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("dim", "depth", "dim_context", "num_latents", "dim_head", "heads",
                                          "ff_mult", "max_batch", "max_frames")]
@@ -73,6 +81,9 @@ _SIGNATURES = {
                                   C.c_int32, _P, _P]),
     "gvc_gpt_generate_rows": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, _P, _P, C.POINTER(SampleParams), C.POINTER(RowSampling),
                                         C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_int32, _P]),
+    "gvc_beam_select": (C.c_int, [C.POINTER(BeamState), _P, _P, C.c_int32, _P]),
+    "gvc_gpt_beam_generate": (C.c_int, [_P, _P, C.POINTER(BeamState), C.c_int32, C.c_int32, C.c_int32, _P]),
+    "gvc_gpt_warmup_beam": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32]),
     "gvc_gpt_decode_variant": (C.c_int, [_P]),
     "gvc_gpt_rows_step_launches": (C.c_longlong, [_P]),
     "gvc_gpt_health": (C.c_int, [_P]),

@@ -1,0 +1,342 @@
+// Deterministic beam search: select step and KV span copies (beam.h; semantics in include/genvc_hip.h and DESIGN.md 4.7).
+#include "beam.h"
+
+namespace gvc {
+
+__device__ __forceinline__ uint32_t f2key(float v) {         // monotone: a larger float has a larger key
+    const uint32_t u = __float_as_uint(v);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+// One workgroup per item.  Candidate e = k * V + x (beam k, token x) of the item lives in thread e % 512's registers, slot e / 512.
+// The top-2K is a 4-pass 8-bit radix select on the keys (histograms in LDS), then a one-wave rank sort of the <= 32 survivors
+// (ties by lower flat index); one lane walks them.
+__global__ void __launch_bounds__(kBeamThreads) k_beam_select(gvc_beam_state st_arg, const BeamCall* call, const float* logits,
+                                                              int32_t* slots, int t_arg, int32_t* seq_len, int32_t* mel_pos,
+                                                              int32_t* tok_buf) {
+    const gvc_beam_state& st = call ? call->st : st_arg;
+    const int t = call ? call->step : t_arg;
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int K = st.K, V = st.vocab, N = K * V, M = 2 * K, eos = st.eos;
+    const int BK = st.B * K, W = st.ids_stride, L = st.n0 + t;
+    const int32_t* ids_in = st.ids + (size_t)(t & 1) * BK * W;
+    int32_t* ids_out = st.ids + (size_t)((t + 1) & 1) * BK * W;
+
+    __shared__ float lse[kBeamMaxK], run[kBeamMaxK];
+    __shared__ uint32_t pen[kBeamMaxK * 33];                    // repetition-penalty bitmaps, V <= 1056
+    __shared__ int hist[256];
+    __shared__ uint32_t sh_prefix;
+    __shared__ int sh_need, cnt_gt, cnt_eq;
+    __shared__ float cv[32], sv[32];
+    __shared__ int ci[32], si[32];
+    __shared__ int nx_tok[kBeamMaxK], nx_par[kBeamMaxK], new_slot[kBeamMaxK], pend[kBeamMaxK];
+    __shared__ float nx_sc[kBeamMaxK];
+    __shared__ int sh_done;
+
+    if (tid == 0) sh_done = st.done[b];
+    for (int i = tid; i < K * 33; i += kBeamThreads) pen[i] = 0u;
+    __syncthreads();
+    const int was_done = sh_done;
+    if (!was_done) {
+        // log-sum-exp per beam row: beam k on wave k % 8, accurate expf / logf
+        for (int k = wv; k < K; k += kBeamThreads / 64) {
+            const float* row = logits + (size_t)(b * K + k) * V;
+            float m = -INFINITY;
+            for (int x = lane; x < V; x += 64) m = fmaxf(m, row[x]);
+            m = wave_max(m);
+            float sum = 0.f;
+            for (int x = lane; x < V; x += 64) sum += expf(row[x] - m);
+            sum = wave_sum(sum);
+            if (lane == 0) { lse[k] = m; run[k] = logf(sum); }
+        }
+        for (int k = 0; k < K; ++k) {
+            const int32_t* r = ids_in + (size_t)(b * K + k) * W;
+            for (int p = tid; p < L; p += kBeamThreads) {
+                const int id = r[p];
+                if (id >= 0 && id < V) atomicOr(&pen[k * 33 + (id >> 5)], 1u << (id & 31));
+            }
+        }
+        __syncthreads();
+    }
+    const float rp = st.repetition_penalty;
+    uint32_t key[kBeamPer];
+    float val[kBeamPer];
+    if (!was_done) {
+#pragma unroll
+        for (int i = 0; i < kBeamPer; ++i) {
+            const int e = tid + i * kBeamThreads;
+            float v = -INFINITY;
+            if (e < N) {
+                const int k = e / V, x = e - k * V;
+                v = (logits[(size_t)(b * K + k) * V + x] - lse[k]) - run[k];
+                if (pen[k * 33 + (x >> 5)] & (1u << (x & 31))) v = v < 0.f ? v * rp : v / rp;
+                v += st.scores[b * K + k];
+            }
+            val[i] = v;
+            key[i] = e < N ? f2key(v) : 0u;
+        }
+        // radix select of the M-th largest key
+        uint32_t prefix = 0u, mask = 0u;
+        int need = M;
+        for (int pass = 0; pass < 4; ++pass) {
+            const int shift = 24 - 8 * pass;
+            if (tid < 256) hist[tid] = 0;
+            __syncthreads();
+#pragma unroll
+            for (int i = 0; i < kBeamPer; ++i)
+                if (tid + i * kBeamThreads < N && (key[i] & mask) == prefix) atomicAdd(&hist[(key[i] >> shift) & 255], 1);
+            __syncthreads();
+            if (wv == 0) {
+                // lane l owns digits 255 - 4l .. 252 - 4l; inclusive scan from the top digit down
+                int h[4], own = 0;
+                for (int j = 0; j < 4; ++j) { h[j] = hist[255 - 4 * lane - j]; own += h[j]; }
+                int incl = own;
+                for (int o = 1; o < 64; o <<= 1) {
+                    const int y = __shfl_up(incl, o);
+                    if (lane >= o) incl += y;
+                }
+                const int excl = incl - own;
+                if (excl < need && incl >= need) {
+                    int c = excl;
+                    for (int j = 0; j < 4; ++j) {
+                        if (c + h[j] >= need) {
+                            sh_prefix = prefix | ((uint32_t)(255 - 4 * lane - j) << shift);
+                            sh_need = need - c;
+                            break;
+                        }
+                        c += h[j];
+                    }
+                }
+            }
+            __syncthreads();
+            prefix = sh_prefix;
+            need = sh_need;
+            mask |= 255u << shift;
+            __syncthreads();
+        }
+        // survivors: every key above the threshold, and `need` keys equal to it
+        if (tid == 0) { cnt_gt = 0; cnt_eq = 0; }
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < kBeamPer; ++i) {
+            const int e = tid + i * kBeamThreads;
+            if (e >= N) continue;
+            if (key[i] > prefix) {
+                const int pos = atomicAdd(&cnt_gt, 1);
+                cv[pos] = val[i]; ci[pos] = e;
+            } else if (key[i] == prefix) {
+                const int pos = atomicAdd(&cnt_eq, 1);
+                if (pos < need) { cv[M - need + pos] = val[i]; ci[M - need + pos] = e; }
+            }
+        }
+        __syncthreads();
+        if (wv == 0 && lane < M) {
+            const float v = cv[lane];
+            const int e = ci[lane];
+            int r = 0;
+            for (int j = 0; j < M; ++j) {
+                const float w = cv[j];
+                r += (w > v) || (w == v && ci[j] < e);
+            }
+            sv[r] = v; si[r] = e;
+        }
+        __syncthreads();
+        // the scorer walk (BeamSearchScorer.process / BeamHypotheses.add, is_done with early_stopping=False)
+        if (tid == 0) {
+            const int len = st.length_mode == 0 ? st.n0 + t : t + 1;
+            const float denom = powf((float)len, st.length_penalty);
+            float* hs = st.hyp_score + b * K;
+            int32_t* hl = st.hyp_len + b * K;
+            int cnt = st.hyp_count[b];
+            float worst = st.hyp_worst[b];
+            for (int k = 0; k < K; ++k) pend[k] = -1;
+            int j = 0;
+            for (int r = 0; r < M && j < K; ++r) {
+                const int e = si[r], p = e / V, x = e - p * V;
+                if (x == eos) {
+                    if (r >= K) continue;
+                    const float sc = sv[r] / denom;
+                    int dst = -1;
+                    if (cnt < K) {
+                        dst = cnt++;
+                        worst = fminf(sc, worst);
+                    } else if (sc > worst) {
+                        dst = 0;
+                        for (int q = 1; q < K; ++q) if (hs[q] < hs[dst]) dst = q;
+                    }
+                    if (dst >= 0) {
+                        hs[dst] = sc; hl[dst] = t; pend[dst] = p;
+                        if (cnt == K && dst >= 0) {
+                            float w = hs[0];
+                            for (int q = 1; q < K; ++q) w = fminf(w, hs[q]);
+                            worst = w;
+                        }
+                    }
+                } else {
+                    nx_tok[j] = x; nx_par[j] = p; nx_sc[j] = sv[r];
+                    ++j;
+                }
+            }
+            int done = 0;
+            if (cnt == K) {
+                const float best = st.length_mode == 0 ? sv[0] : nx_sc[0];
+                done = worst >= best / denom;
+            }
+            st.hyp_count[b] = cnt;
+            st.hyp_worst[b] = worst;
+            st.done[b] = done;
+            // slot permutation: a parent's slot goes to its first child; further children take the slots of childless parents
+            int first[kBeamMaxK], free_s[kBeamMaxK], nf = 0;
+            int old_slot[kBeamMaxK];
+            for (int k = 0; k < K; ++k) { first[k] = -1; old_slot[k] = slots[b * K + k]; }
+            for (int q = 0; q < K; ++q) if (first[nx_par[q]] < 0) first[nx_par[q]] = q;
+            for (int k = 0; k < K; ++k) if (first[k] < 0) free_s[nf++] = old_slot[k];
+            int nc = 0, taken = 0;
+            const int lo = t == 0 ? 0 : st.n0;
+            for (int q = 0; q < K; ++q) {
+                const int p = nx_par[q];
+                if (first[p] == q) {
+                    new_slot[q] = old_slot[p];
+                } else {
+                    const int dst = free_s[taken++];
+                    new_slot[q] = dst;
+                    int32_t* c = st.copies + ((size_t)b * K + nc) * 3;
+                    c[0] = old_slot[p]; c[1] = dst; c[2] = lo;
+                    ++nc;
+                    if (seq_len) { seq_len[dst] = seq_len[old_slot[p]]; mel_pos[dst] = mel_pos[old_slot[p]]; }
+                }
+            }
+            st.n_copies[b] = nc;
+            for (int q = 0; q < K; ++q) {
+                slots[b * K + q] = new_slot[q];
+                st.tokens[b * K + q] = nx_tok[q];
+                if (tok_buf) tok_buf[b * K + q] = nx_tok[q];
+                st.parents[b * K + q] = nx_par[q];
+                st.scores[b * K + q] = nx_sc[q];
+            }
+        }
+    } else if (tid < K) {
+        nx_tok[tid] = eos; nx_par[tid] = tid; pend[tid] = -1;
+        st.tokens[b * K + tid] = eos;
+        if (tok_buf) tok_buf[b * K + tid] = eos;
+        st.parents[b * K + tid] = tid;
+        if (tid == 0) st.n_copies[b] = 0;
+    }
+    __syncthreads();
+    // hypothesis tokens (the parent's generated tokens, read before any ids row is rewritten) and the ids gather into the other buffer
+    for (int k = 0; k < K; ++k) {
+        const int p = pend[k];
+        if (p < 0) continue;
+        const int32_t* src = ids_in + (size_t)(b * K + p) * W + st.n0;
+        int32_t* dst = st.hyp_tok + ((size_t)b * K + k) * st.max_new;
+        for (int i = tid; i < t; i += kBeamThreads) dst[i] = src[i];
+    }
+    for (int q = 0; q < K; ++q) {
+        const int32_t* src = ids_in + (size_t)(b * K + nx_par[q]) * W;
+        int32_t* dst = ids_out + (size_t)(b * K + q) * W;
+        for (int i = tid; i < L; i += kBeamThreads) dst[i] = src[i];
+        if (tid == 0 && L < W) dst[L] = nx_tok[q];
+    }
+}
+
+// one block column per possible copy (blockIdx.y = item * (K-1) + copy), blockIdx.x strides over the (layer, k|v, head) runs; each
+// run copies positions [lo, cur) of one head, contiguous, in 16-byte vectors
+__global__ void __launch_bounds__(256) k_kv_copy_span(BeamCall* call, int K, char* kv, int runs, int n_head, size_t lw_bytes,
+                                                      size_t slot_bytes, size_t head_bytes, int row_bytes, const int32_t* seq_len) {
+    const int b = blockIdx.y / (K - 1), q = blockIdx.y - b * (K - 1);
+    const int nc = call->st.n_copies[b];
+    const int32_t* c = call->st.copies + ((size_t)b * K + q) * 3;
+    __syncthreads();                                     // (every thread has read call->step's neighbours before it moves)
+    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) call->step += 1;
+    if (q >= nc) return;
+    const int src = c[0], dst = c[1], lo = c[2];
+    const int cur = seq_len[src];
+    if (cur <= lo) return;
+    const size_t off = (size_t)lo * row_bytes, n16 = (size_t)(cur - lo) * row_bytes / 16;
+    for (int r = blockIdx.x; r < runs; r += gridDim.x) {
+        const int lw = r / n_head, h = r - lw * n_head;
+        const char* s = kv + lw * lw_bytes + (size_t)src * slot_bytes + h * head_bytes + off;
+        char* d = kv + lw * lw_bytes + (size_t)dst * slot_bytes + h * head_bytes + off;
+        const uint4* s4 = reinterpret_cast<const uint4*>(s);
+        uint4* d4 = reinterpret_cast<uint4*>(d);
+        for (size_t i = threadIdx.x; i < n16; i += blockDim.x) d4[i] = s4[i];
+    }
+}
+
+__global__ void k_beam_begin(BeamCall* dst, gvc_beam_state st, int i0, const int32_t* slots_in, int32_t* slot_table, float* logits,
+                             const float* slot_logits) {
+    const int BK = st.B * st.K, r = blockIdx.x;
+    if (r == BK) {
+        if (threadIdx.x == 0) { dst->st = st; dst->step = i0; }
+        if ((int)threadIdx.x < BK) slot_table[threadIdx.x] = slots_in[threadIdx.x];
+        return;
+    }
+    // the first call starts every beam of an item from the logits its prefill parked in slot[b*K]
+    const size_t sl = (size_t)(i0 == 0 ? slots_in[(r / st.K) * st.K] : slots_in[r]);
+    for (int i = threadIdx.x; i < st.vocab; i += blockDim.x) logits[(size_t)r * st.vocab + i] = slot_logits[sl * st.vocab + i];
+}
+
+__global__ void k_beam_end(const int32_t* slot_table, int32_t* slots_out, const float* logits, float* slot_logits, int vocab) {
+    const int r = blockIdx.x;
+    const size_t sl = (size_t)slot_table[r];
+    if (threadIdx.x == 0) slots_out[r] = slot_table[r];
+    for (int i = threadIdx.x; i < vocab; i += blockDim.x) slot_logits[sl * vocab + i] = logits[(size_t)r * vocab + i];
+}
+
+int beam_check(const gvc_beam_state& st) {
+    GVC_REQUIRE(st.B >= 1 && st.K >= 2 && st.K <= kBeamMaxK && st.vocab >= 2 && st.vocab <= 33 * 32 && st.K * st.vocab <= kBeamMaxN &&
+                    st.B * st.K <= 64,
+                GVC_ERR_ARG, "beam: B=%d K=%d vocab=%d outside the supported range (2 <= K <= 16, K*vocab <= %d, B*K <= 64)", st.B, st.K,
+                st.vocab, kBeamMaxN);
+    GVC_REQUIRE(st.eos >= 0 && st.eos < st.vocab && st.n0 >= 1 && st.max_new >= 1 && st.ids_stride >= st.n0 + st.max_new &&
+                    (st.length_mode == 0 || st.length_mode == 1) && st.repetition_penalty > 0.f,
+                GVC_ERR_ARG, "beam: bad state (n0 %d, max_new %d, ids_stride %d, length_mode %d)", st.n0, st.max_new, st.ids_stride,
+                st.length_mode);
+    GVC_REQUIRE(st.ids && st.scores && st.tokens && st.parents && st.done && st.hyp_score && st.hyp_len && st.hyp_tok && st.hyp_count &&
+                    st.hyp_worst && st.copies && st.n_copies,
+                GVC_ERR_ARG, "beam: null state array");
+    return GVC_OK;
+}
+
+int launch_beam_select(const gvc_beam_state& st, const BeamCall* call, int B, int K, const float* logits, int32_t* slots, int t,
+                       int32_t* seq_len, int32_t* mel_pos, int32_t* tok_buf, hipStream_t s) {
+    (void)K;
+    hipLaunchKernelGGL(k_beam_select, dim3(B), dim3(kBeamThreads), 0, s, st, call, logits, slots, t, seq_len, mel_pos, tok_buf);
+    GVC_LAUNCH_CHECK();
+    return GVC_OK;
+}
+
+int launch_kv_copy_span(BeamCall* call, int B, int K, void* kv, int n_layer, int n_head, int max_seq, int hd, int max_slots, int esz,
+                        const int32_t* seq_len, hipStream_t s) {
+    GVC_REQUIRE((hd * esz) % 16 == 0, GVC_ERR_UNSUPPORTED, "kv_copy_span: head row of %d bytes is not a multiple of 16", hd * esz);
+    const size_t head_bytes = (size_t)max_seq * hd * esz, slot_bytes = head_bytes * n_head, lw_bytes = slot_bytes * max_slots;
+    hipLaunchKernelGGL(k_kv_copy_span, dim3(64, B * (K - 1)), dim3(256), 0, s, call, K, (char*)kv, 2 * n_layer * n_head, n_head, lw_bytes,
+                       slot_bytes, head_bytes, hd * esz, seq_len);
+    GVC_LAUNCH_CHECK();
+    return GVC_OK;
+}
+
+int launch_beam_begin(BeamCall* dst, const gvc_beam_state& st, int i0, const int32_t* slots_in, int32_t* slot_table, float* logits,
+                      const float* slot_logits, hipStream_t s) {
+    const int BK = st.B * st.K;
+    hipLaunchKernelGGL(k_beam_begin, dim3(BK + 1), dim3(256), 0, s, dst, st, i0, slots_in, slot_table, logits, slot_logits);
+    GVC_LAUNCH_CHECK();
+    return GVC_OK;
+}
+
+int launch_beam_end(const int32_t* slot_table, int32_t* slots_out, int BK, const float* logits, float* slot_logits, int vocab,
+                    hipStream_t s) {
+    hipLaunchKernelGGL(k_beam_end, dim3(BK), dim3(256), 0, s, slot_table, slots_out, logits, slot_logits, vocab);
+    GVC_LAUNCH_CHECK();
+    return GVC_OK;
+}
+
+}  // namespace gvc
+
+extern "C" int gvc_beam_select(const gvc_beam_state* st, const float* logits, int32_t* slots, int32_t t, gvc_stream sv) {
+    GVC_REQUIRE(st && logits && slots && t >= 0, GVC_ERR_ARG, "beam_select: bad argument");
+    int rc = gvc::beam_check(*st);
+    if (rc) return rc;
+    GVC_REQUIRE(t < st->max_new && st->n0 + t < st->ids_stride, GVC_ERR_ARG, "beam_select: step %d past max_new %d", t, st->max_new);
+    return gvc::launch_beam_select(*st, nullptr, st->B, st->K, logits, slots, t, nullptr, nullptr, nullptr, (hipStream_t)sv);
+}

@@ -13,6 +13,7 @@
 #include "persist_kernel.h"
 #include "persist_rows.h"
 #include "persist_rows_b16.h"
+#include "beam.h"
 #include "sampler.h"
 
 namespace gvc {
@@ -267,6 +268,7 @@ struct gvc_gpt {
     GptState st;
     int32_t *tok_buf = nullptr, *step_ctr = nullptr;
     GenCall* gen_call = nullptr;
+    BeamCall* beam_call = nullptr;    // parameters of the running gvc_gpt_beam_generate call (device)
     hipStream_t cap_stream = nullptr;
     std::map<int, hipGraphExec_t> graphs;   // 2*B + fused -> step graph
     int prof_only = -1;               // gvc_gpt_time_kernel(): launch only this kernel class
@@ -404,6 +406,7 @@ extern "C" int gvc_gpt_create(const gvc_gpt_dims* dims, gvc_gpt** out) {
     c->tok_buf = c->state + 2 * D.max_slots;
     c->step_ctr = c->state + 3 * D.max_slots;
     GVC_CHECK_HIP(hipMalloc((void**)&c->gen_call, sizeof(GenCall)));
+    GVC_CHECK_HIP(hipMalloc((void**)&c->beam_call, sizeof(BeamCall)));
     GVC_CHECK_HIP(hipStreamCreateWithFlags(&c->cap_stream, hipStreamNonBlocking));
     if ((rc = gemv_init())) { gvc_gpt_destroy(c); return rc; }
     GVC_CHECK_HIP(hipHostMalloc((void**)&c->seam_err_host, sizeof(int), hipHostMallocMapped));
@@ -431,7 +434,7 @@ extern "C" int gvc_gpt_destroy(gvc_gpt* c) {
         if (p) hipFree(p);
     for (void* p : {(void*)c->wbase, (void*)c->wfm, (void*)c->wh, (void*)c->kv, (void*)c->x, (void*)c->a, (void*)c->q, (void*)c->h,
                     (void*)c->part, (void*)c->work, (void*)c->logits, (void*)c->latent, (void*)c->slot_logits, (void*)c->slot_latent, (void*)c->state, (void*)c->x2, (void*)c->part2,
-                    (void*)c->gen_call})
+                    (void*)c->gen_call, (void*)c->beam_call})
         if (p) hipFree(p);
     delete c;
     return GVC_OK;
@@ -1683,6 +1686,124 @@ extern "C" int gvc_gpt_generate_rows(gvc_gpt* c, const int32_t* slots, int32_t B
                          latents_out, lat_stride, sv);
 }
 
+
+// ---------------------------------------------------------------------------------------------
+// beam search: one captured graph = [k_beam_select -> k_kv_copy_span -> decode step over B*K rows], replayed n_steps times.  The
+// decode step is the one plan_generate picks for B*K rows (the one-launch rows step for 2..16 rows where it applies); it addresses the
+// KV cache through the device-resident slot table gen_call->slots, which the select step permutes (beam.h).  The graphs share the
+// context's graph map under negative keys, so every path that drops the step graphs (time-out fallback, rearm, destroy) drops them too.
+// ---------------------------------------------------------------------------------------------
+static int build_beam_graph(gvc_gpt* c, int B, int K, const GenPlan& pl, int n_unroll, hipGraphExec_t* out) {
+    hipStream_t cs = c->cap_stream;
+    const int BK = B * K;
+    int32_t* table = c->gen_call->slots;
+    int rc = GVC_OK;
+    gvc_beam_state dummy;
+    memset(&dummy, 0, sizeof(dummy));
+    GVC_CHECK_HIP(hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal));
+    for (int u = 0; u < n_unroll && rc == GVC_OK; ++u) {
+        rc = launch_beam_select(dummy, c->beam_call, B, K, c->logits, table, 0, c->st.seq_len, c->st.mel_pos, c->tok_buf, cs);
+        if (rc == GVC_OK)
+            rc = launch_kv_copy_span(c->beam_call, B, K, c->kv, c->dm.n_layer, c->dm.n_head, c->dm.max_seq, c->hd, c->dm.max_slots,
+                                     c->kv_bf16 ? 2 : 4, c->st.seq_len, cs);
+        if (rc == GVC_OK && rows_decode_ok(c, BK))
+            rc = decode_rows(c, table, BK, c->tok_buf, c->logits, c->latent, nullptr, cs, pl.key_chunks);
+        else
+            for (int g = 0; g < BK && rc == GVC_OK; g += 8) {
+                const int Bg = BK - g < 8 ? BK - g : 8;
+                rc = decode_group(c, table + g, Bg, g, c->tok_buf + g, c->logits + (size_t)g * c->dm.vocab,
+                                  c->latent + (size_t)g * c->dm.d_model, nullptr, cs, pl.fused);
+            }
+    }
+    hipGraph_t graph = nullptr;
+    hipError_t e = hipStreamEndCapture(cs, &graph);
+    if (rc != GVC_OK) {
+        if (graph) hipGraphDestroy(graph);
+        return rc;
+    }
+    GVC_CHECK_HIP(e);
+    e = hipGraphInstantiate(out, graph, nullptr, nullptr, 0);
+    hipGraphDestroy(graph);
+    GVC_CHECK_HIP(e);
+    return GVC_OK;
+}
+
+static int beam_graph(gvc_gpt* c, int B, int K, const GenPlan& pl, int unroll, hipGraphExec_t* ge) {
+    const int k = -(1 + pl.key + (K << 16) + (unroll << 24));      // (pl.key < 2^16, K <= 16, unroll <= 32)
+    auto it = c->graphs.find(k);
+    if (it == c->graphs.end()) {
+        hipGraphExec_t g1;
+        note_lazy(c);
+        int r = build_beam_graph(c, B, K, pl, unroll, &g1);
+        if (r) return r;
+        it = c->graphs.emplace(k, g1).first;
+    }
+    *ge = it->second;
+    return GVC_OK;
+}
+
+static int beam_plan(gvc_gpt* c, int B, int K, int key_bound, GenPlan* pl) {
+    GVC_REQUIRE(B >= 1 && K >= 2 && K <= kBeamMaxK && B * K <= c->dm.max_slots, GVC_ERR_ARG,
+                "beam: B*K = %d*%d rows exceed the context's %d KV slots", B, K, c->dm.max_slots);
+    GVC_REQUIRE(!persist_ok(c, B * K), GVC_ERR_STATE, "beam: the one-stream step cannot serve %d rows", B * K);
+    return plan_generate(c, B * K, key_bound, 1, pl);
+}
+
+extern "C" int gvc_gpt_warmup_beam(gvc_gpt* c, int32_t B, int32_t K, int32_t max_keys) {
+    int rc = check_ready(c);
+    if (rc) return rc;
+    GVC_REQUIRE(max_keys >= 0 && max_keys < c->dm.max_seq, GVC_ERR_ARG, "warmup_beam: bad max_keys %d", max_keys);
+    GVC_REQUIRE(B >= 1 && K >= 2 && B * K <= c->dm.max_slots, GVC_ERR_ARG, "warmup_beam: B*K = %d*%d outside [2, %d]", B, K, c->dm.max_slots);
+    if ((rc = gvc_gpt_warmup(c, B * K, max_keys, 1))) return rc;
+    c->in_warmup = 1;
+    struct Leave { gvc_gpt* c; ~Leave() { c->in_warmup = 0; } } leave{c};
+    // every context class a search reaching max_keys passes through (the calls' bounds grow with the search)
+    const int hi = max_keys > 0 ? max_keys : c->dm.max_seq - 1;
+    int last_key = -1;
+    for (int mk = 1; mk <= hi; ++mk) {
+        GenPlan pl;
+        if ((rc = beam_plan(c, B, K, mk, &pl))) return rc;
+        if (pl.key == last_key) continue;
+        last_key = pl.key;
+        hipGraphExec_t ge;
+        if (step_unroll() > 1 && (rc = beam_graph(c, B, K, pl, step_unroll(), &ge))) return rc;
+        if ((rc = beam_graph(c, B, K, pl, 1, &ge))) return rc;
+    }
+    GVC_CHECK_HIP(hipDeviceSynchronize());
+    return GVC_OK;
+}
+
+extern "C" int gvc_gpt_beam_generate(gvc_gpt* c, int32_t* slots, const gvc_beam_state* st, int32_t i0, int32_t n_steps, int32_t max_keys,
+                                     gvc_stream sv) {
+    int rc = check_ready(c);
+    if (rc) return rc;
+    GVC_REQUIRE(slots && st && i0 >= 0 && n_steps >= 0 && max_keys >= 0, GVC_ERR_ARG, "beam_generate: bad argument");
+    if ((rc = beam_check(*st))) return rc;
+    GVC_REQUIRE(st->vocab == c->dm.vocab, GVC_ERR_ARG, "beam_generate: vocab mismatch");
+    GVC_REQUIRE(i0 + n_steps <= st->max_new, GVC_ERR_ARG, "beam_generate: steps %d..%d past max_new %d", i0, i0 + n_steps, st->max_new);
+    const int key_bound = max_keys > 0 ? max_keys : st->n0 + i0 + n_steps;
+    GVC_REQUIRE(key_bound < c->dm.max_seq, GVC_ERR_STATE, "beam_generate: %d cached positions would overflow the KV cache (max_seq %d)",
+                key_bound, c->dm.max_seq);
+    hipStream_t s = (hipStream_t)sv;
+    const int B = st->B, K = st->K, BK = B * K;
+    GenPlan pl;
+    if ((rc = beam_plan(c, B, K, key_bound, &pl))) return rc;
+    if ((rc = launch_beam_begin(c->beam_call, *st, i0, slots, c->gen_call->slots, c->logits, c->slot_logits, s))) return rc;
+    c->last_variant = pl.variant;
+    const int kStepUnroll = step_unroll();
+    int left = n_steps;
+    if (kStepUnroll > 1 && left >= kStepUnroll) {
+        hipGraphExec_t ge;
+        if ((rc = beam_graph(c, B, K, pl, kStepUnroll, &ge))) return rc;
+        for (; left >= kStepUnroll; left -= kStepUnroll) GVC_CHECK_HIP(hipGraphLaunch(ge, s));
+    }
+    if (left > 0) {
+        hipGraphExec_t ge;
+        if ((rc = beam_graph(c, B, K, pl, 1, &ge))) return rc;
+        for (; left > 0; --left) GVC_CHECK_HIP(hipGraphLaunch(ge, s));
+    }
+    return launch_beam_end(c->gen_call->slots, slots, BK, c->logits, c->slot_logits, c->dm.vocab, s);
+}
 
 // ---------------------------------------------------------------------------------------------
 // measurement hook (bench.py roofline): launch ONLY one kernel class of the decode step (0 qkv, 1 attention,

@@ -42,6 +42,86 @@ def _rows_arg(rows, B):
     return arr
 
 
+BEAM_LENGTH_MODES = {"4.33": 0, "generated": 1}
+
+
+class BeamSearch:
+    """device state of one deterministic beam search (gvc_beam_state, include/genvc_hip.h) over B items of K beams: double-buffered
+    ids rows, running scores, the finished-hypothesis store, the copy lists of the last reorder.  `fake` [B, n0] are the fake ids of
+    compute_embeddings (every beam of an item starts from them)."""
+
+    def __init__(self, fake, K, max_new, eos, vocab, length_penalty=1.0, repetition_penalty=1.0, length_mode="4.33"):
+        if length_mode not in BEAM_LENGTH_MODES:
+            raise ValueError(f"beam_length_mode must be one of {sorted(BEAM_LENGTH_MODES)}, not {length_mode!r}")
+        dev = fake.device
+        B, n0 = fake.shape
+        self.B, self.K, self.n0, self.max_new, self.eos = B, K, n0, max_new, eos
+        W = n0 + max_new + 8
+        i32 = dict(device=dev, dtype=torch.int32)
+        self.ids = torch.full((2, B * K, W), eos, **i32)
+        self.ids[0, :, :n0] = fake.to(torch.int32).repeat_interleave(K, 0)
+        self.scores = torch.zeros(B, K, device=dev, dtype=torch.float32)
+        self.scores[:, 1:] = -1e9
+        self.scores = self.scores.reshape(-1).contiguous()
+        self.tokens = torch.zeros(B * K, **i32)
+        self.parents = torch.zeros(B * K, **i32)
+        self.done = torch.zeros(B, **i32)
+        self.hyp_score = torch.zeros(B, K, device=dev, dtype=torch.float32)
+        self.hyp_len = torch.zeros(B, K, **i32)
+        self.hyp_tok = torch.full((B, K, max_new), eos, **i32)
+        self.hyp_count = torch.zeros(B, **i32)
+        self.hyp_worst = torch.full((B,), 1e9, device=dev, dtype=torch.float32)
+        self.copies = torch.zeros(B, K, 3, **i32)
+        self.n_copies = torch.zeros(B, **i32)
+        self.steps = 0
+        self.c = _lib.BeamState(B, K, int(vocab), int(eos), n0, W, int(max_new), BEAM_LENGTH_MODES[length_mode], float(length_penalty),
+                                float(repetition_penalty), *[t.data_ptr() for t in (
+                                    self.ids, self.scores, self.tokens, self.parents, self.done, self.hyp_score, self.hyp_len,
+                                    self.hyp_tok, self.hyp_count, self.hyp_worst, self.copies, self.n_copies)])
+        self.length_mode = length_mode
+        self.length_penalty = float(length_penalty)
+
+    def finalize(self):
+        """BeamSearchScorer.finalize: the running beams of the items not done join their hypotheses (length n0 + T in mode "4.33", T
+        in mode "generated"), the best hypothesis per item wins; rows are its tokens, then eos (= pad) up to the longest row + 1 (at
+        most max_new).  Returns (ids int64 [B, n], best scores [B]); once per call, host-side torch on the device"""
+        B, K, T = self.B, self.K, self.steps
+        L = self.n0 + T if BEAM_LENGTH_MODES[self.length_mode] == 0 else T
+        ids = self.ids[T & 1].view(B, K, -1)[:, :, self.n0:self.n0 + T]
+        done = self.done.bool().cpu()
+        cnt = self.hyp_count.cpu()
+        hs, hl = self.hyp_score.cpu(), self.hyp_len.cpu()
+        run = (self.scores.view(B, K) / (float(L) ** self.length_penalty)).cpu()
+        best = []
+        for b in range(B):
+            items = [(float(hs[b, i]), ("h", i)) for i in range(int(cnt[b]))]
+            if not done[b]:
+                # (BeamHypotheses.add in beam order, so the kept set is the one the reference keeps)
+                for k in range(K):
+                    sc = float(run[b, k])
+                    if len(items) < K:
+                        items.append((sc, ("r", k)))
+                    elif sc > min(s for s, _ in items):
+                        del items[min(range(len(items)), key=lambda i: (items[i][0], i))]
+                        items.append((sc, ("r", k)))
+            best.append(sorted(items, key=lambda x: x[0])[-1])
+        rows = []
+        for b, (sc, (kind, i)) in enumerate(best):
+            rows.append(self.hyp_tok[b, i, :int(hl[b, i])] if kind == "h" else ids[b, i])
+        width = min(max(int(r.shape[0]) for r in rows) + 1, self.max_new)
+        out = torch.full((B, width), self.eos, device=self.ids.device, dtype=torch.long)
+        for b, r in enumerate(rows):
+            n = min(int(r.shape[0]), width)
+            out[b, :n] = r[:n].long()
+        return out, torch.tensor([sc for sc, _ in best], dtype=torch.float64)
+
+
+def beam_select(beam, logits, slots, t):
+    """one select step of `beam` (a BeamSearch) on logits [B*K, vocab] at step t; slots [B*K] int32 are permuted in place
+    (include/genvc_hip.h: gvc_beam_select)"""
+    check(lib().gvc_beam_select(C.byref(beam.c), ptr(_f32(logits)), ptr(_i32(slots)), int(t), stream()), "beam_select")
+
+
 class GptEngine:
     """KV-cached GPT-2 stack of GenVC (reference layers/gpt.py + layers/gpt_inference.py)."""
 
@@ -203,6 +283,18 @@ class GptEngine:
                                           ptr(_i32(finished)), C.byref(common), arr, int(i0), int(n_steps), int(max_keys),
                                           ptr(tokens_out), tokens_out.stride(0), ptr(latents_out), lat_stride, stream()),
               "generate_rows")
+
+    def beam_generate(self, slots, beam, n_steps, max_keys=0):
+        """n_steps steps of `beam` (a BeamSearch) on the device, continuing at beam.steps (include/genvc_hip.h: gvc_gpt_beam_generate):
+        item b was prefilled into slots[b*K]; slots [B*K] int32 is rewritten to the beams' slots"""
+        self._join_side()
+        check(lib().gvc_gpt_beam_generate(self._h, ptr(_i32(slots)), C.byref(beam.c), int(beam.steps), int(n_steps), int(max_keys),
+                                          stream()), "beam_generate")
+        beam.steps += int(n_steps)
+
+    def warmup_beam(self, B, K, max_keys=0):
+        """warmup() for beam_generate over B items of K beams (include/genvc_hip.h: gvc_gpt_warmup_beam)"""
+        check(lib().gvc_gpt_warmup_beam(self._h, int(B), int(K), int(max_keys)), "warmup_beam")
 
     def decode_variant(self):
         """which decode step the last generate() call replayed (include/genvc_hip.h: gvc_gpt_decode_variant)"""

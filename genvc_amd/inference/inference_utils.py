@@ -72,8 +72,9 @@ def _segment_latents(m, cond_latent, codes, gen, repass_latents):
 
 
 @torch.inference_mode()
-def synthesize_utt(genVC_mdl, src_wav, tgt_audio, seg_len=6.0, return_details=False, repass_latents=False):
-    """non-streaming conversion, latent-level concatenation (reference :23-89)"""
+def synthesize_utt(genVC_mdl, src_wav, tgt_audio, seg_len=6.0, return_details=False, repass_latents=False, num_beams=1):
+    """non-streaming conversion, latent-level concatenation (reference :23-89).  num_beams = K > 1: every segment decodes with
+    deterministic beam search (GPT.generate(num_beams=K, do_sample=False)); its latents come from the re-pass"""
     m = genVC_mdl
     min_len = int(0.32 * m.content_sample_rate)
     src_wav = src_wav.to(m.device)
@@ -83,7 +84,8 @@ def synthesize_utt(genVC_mdl, src_wav, tgt_audio, seg_len=6.0, return_details=Fa
     for src_seg in segments(src_wav, seg, min_len):
         feat = m.content_extractor.extract_content_features(src_seg)
         codes = m.content_dvae.get_codebook_indices(feat.transpose(1, 2))
-        gen = m.gpt.generate(cond_latent, codes, output_attentions=False, **_sampling_kwargs(m))[0]
+        kw = _sampling_kwargs(m) if num_beams == 1 else dict(_sampling_kwargs(m), do_sample=False, num_beams=int(num_beams))
+        gen = m.gpt.generate(cond_latent, codes, output_attentions=False, **kw)[0]
         gen = gen[gen != m.gpt.stop_audio_token]                        # reference :68 (0-d collapse guarded)
         if gen.numel() == 0:
             continue

@@ -92,13 +92,14 @@ class GenVCModel(nn.Module):
         return _CondFuture(self, audio, sr, length, chunk_length, after)
 
     @torch.inference_mode()
-    def warmup(self, seg_len=1.0, streams=1, ref_seconds=3.0, stream_chunk_size=8, top_k=None, max_new_tokens=None):
+    def warmup(self, seg_len=1.0, streams=1, ref_seconds=3.0, stream_chunk_size=8, top_k=None, max_new_tokens=None, num_beams=1):
         """Everything the FIRST conversion of this shape would otherwise pay inside its latency window (the reference leaves warm-up
         to the user: /root/reference/infer.py:27-30 runs a conversion first).  For `streams` concurrent streams of `seg_len`-second
         segments and a `ref_seconds` reference:
           * GPT context: gvc_gpt_warmup for every context class the generation calls of a segment reach (the one-launch steps' buffers,
             weight pack and topology probe; the captured step graphs) -- after it no GPT data-path call allocates or synchronises;
           * ContentVec / DVAE / HiFi-GAN / mel + Perceiver: one pass over zeros of the real shapes (their per-shape graphs and plans).
+        num_beams = K > 1: also the beam step graphs of `streams` items x K beams (GPT.generate(num_beams=K, do_sample=False)).
         No token is generated and no KV slot is left occupied."""
         dev = self.device
         g = self.gpt
@@ -120,6 +121,8 @@ class GenVCModel(nn.Module):
         # that range (its thresholds are its own: gvc_gpt_warmup_range)
         hi = min(n0 + max_new, eng.dims["max_seq"] - 1)
         eng.warmup_range(streams, min(n0 + grp, hi), hi, top_k)
+        if int(num_beams) > 1:
+            eng.warmup_beam(streams, int(num_beams), hi)
         if self.hifigan is not None:
             lat = torch.zeros(streams, grp, g.model_dim, device=dev)
             for n in {grp, max(1, max_new % grp)}:

@@ -11,7 +11,7 @@ import torch
 from torch import nn
 
 from .._lib import GenvcHipError
-from ..engine import GptEngine, sample_params
+from ..engine import BEAM_LENGTH_MODES, BeamSearch, GptEngine, sample_params
 from .perceiver_encoder import PerceiverResampler
 
 
@@ -20,6 +20,34 @@ from .perceiver_encoder import PerceiverResampler
 # they do depend on it (not bit-identical for 5 / 8 / 16 rows), so a near-tie draw can differ from the serial path and the joint sampled
 # decode stays opt-in (joint_sampling=True).  tests/test_gpu_row_sampling.py pins this flag to that measurement; DESIGN.md 4.6.
 JOINT_SAMPLING_DEFAULT = False
+
+
+def _no_beams(kw, where):
+    """the paths that decode one beam per stream: num_beams > 1 raises, naming the path"""
+    if int(kw.get("num_beams", 1) or 1) != 1:
+        raise NotImplementedError(f"beam search (num_beams={kw.get('num_beams')}) is not on the {where} path: GPT.generate serves it "
+                                  "(the reference streams with num_beams=1 only, inference_utils.py:62,178)")
+
+
+def _beam_kwargs(kw):
+    """the modes of HF generate(num_beams > 1) this build does not serve raise NotImplementedError, naming the mode; returns the
+    (K, length_penalty, repetition_penalty, beam_length_mode) of a deterministic beam search"""
+    K = int(kw.get("num_beams", 1))
+    if kw.get("do_sample", True):
+        raise NotImplementedError(f"beam sampling (do_sample=True, num_beams={K}) is not implemented: deterministic beam search needs "
+                                  "do_sample=False")
+    if int(kw.get("num_beam_groups", 1) or 1) != 1 or kw.get("diversity_penalty"):
+        raise NotImplementedError("group / diverse beam search (num_beam_groups > 1, diversity_penalty) is not implemented")
+    if kw.get("constraints") or kw.get("force_words_ids"):
+        raise NotImplementedError("constrained beam search (constraints, force_words_ids) is not implemented")
+    if int(kw.get("num_return_sequences", 1) or 1) != 1:
+        raise NotImplementedError("beam search returns one sequence per item (num_return_sequences=1)")
+    if kw.get("early_stopping", False) is not False:
+        raise NotImplementedError("beam search runs with early_stopping=False (the GenerationConfig default) only")
+    mode = kw.get("beam_length_mode", "4.33")
+    if mode not in BEAM_LENGTH_MODES:
+        raise ValueError(f"beam_length_mode must be one of {sorted(BEAM_LENGTH_MODES)}, not {mode!r}")
+    return K, float(kw.get("length_penalty", 1.0)), float(kw.get("repetition_penalty", 1.0)), mode
 
 
 class _Holder(nn.Module):
@@ -179,8 +207,7 @@ class GPT(nn.Module):
 
     def _start(self, fake_inputs, kw):
         """prefill + device-side loop state for the stored prefix"""
-        if kw.get("num_beams", 1) != 1:
-            raise NotImplementedError("beam search is not on GenVC's inference path (num_beams=1)")
+        _no_beams(kw, "streaming (get_generator)")
         B, n0 = fake_inputs.shape
         dev = fake_inputs.device
         max_new = kw.get("max_new_tokens") or self.max_gen_mel_tokens                     # gpt.py:606,618
@@ -217,7 +244,10 @@ class GPT(nn.Module):
     @torch.inference_mode()
     def generate(self, cond_latents, text_inputs, **generate_kwargs):
         """reference gpt.py:594-609 -> int64 [B, n_generated]; finished rows are padded with the stop token.
-        `group` (extra kwarg) = decode steps per host check of the finished flags."""
+        `group` (extra kwarg) = decode steps per host check of the finished flags.
+        num_beams = K > 1 with do_sample=False: deterministic beam search on the device (_generate_beams)."""
+        if int(generate_kwargs.get("num_beams", 1) or 1) > 1:
+            return self._generate_beams(cond_latents, text_inputs, generate_kwargs)
         fake = self.compute_embeddings(cond_latents, text_inputs)
         group = generate_kwargs.pop("group", 16)
 
@@ -237,6 +267,45 @@ class GPT(nn.Module):
         self.last_latents = st["lats"][:, :n]
         return toks[:, :n]
 
+    def _generate_beams(self, cond_latents, text_inputs, generate_kwargs):
+        """HF generate(num_beams=K, do_sample=False) semantics (length_penalty, early_stopping=False, num_return_sequences=1, the
+        repetition penalty on log-probs, pad = eos, max_length = max_gen_mel_tokens + prompt): item b is prefilled ONCE into KV slot
+        b*K; every step runs [select -> KV span copies -> decode step over B*K rows] from a captured graph (include/genvc_hip.h:
+        gvc_gpt_beam_generate), the host looks at the done flags once per `group` steps; the hypothesis store is finalised on the
+        device at the end.  beam_length_mode: "4.33" (default: the lengths the reference's pinned transformers normalises by) or
+        "generated" (those of the installed transformers).  Needs B*K <= the context's KV slots (ValueError otherwise).  Returns
+        int64 [B, n] (gpt.py:609: the prompt sliced away); the best normalised score per item lands in `last_beam_scores`, and
+        `last_latents` is None (the caller's latents come from the teacher-forced re-pass, hifigan_trainer.py:489-494)."""
+        kw = dict(generate_kwargs)
+        K, lp, rep, mode = _beam_kwargs(kw)
+        self._need_engine()
+        group = int(kw.pop("group", 16))
+        B = int(text_inputs.shape[0])
+        if B * K > self.max_slots:
+            raise ValueError(f"beam search over {B} items x {K} beams needs {B * K} KV slots; the context has {self.max_slots} "
+                             "(init_gpt_for_inference(max_slots=...))")
+        fake = self.compute_embeddings(cond_latents, text_inputs)
+        n0 = int(fake.shape[1])
+        max_new = int(kw.get("max_new_tokens") or self.max_gen_mel_tokens)                   # gpt.py:606
+        dev = fake.device
+
+        def run():
+            slots = torch.arange(B * K, device=dev, dtype=torch.int32)
+            self.engine.prefill(slots[::K].contiguous(), self._prefix, want_outputs=False)      # each item once; the first step fans out
+            beam = BeamSearch(fake, K, max_new, self.stop_audio_token, self.num_audio_tokens, lp, rep, mode)
+            while beam.steps < max_new:
+                n = min(group, max_new - beam.steps)
+                self.engine.beam_generate(slots, beam, n, max_keys=n0 + beam.steps + n)
+                stop = bool(beam.done.all().item())
+                self.engine.health()          # (the .item() above synchronised)
+                if stop:
+                    break
+            return beam.finalize()
+        ids, scores = self._recovering(B * K, run)
+        self.last_latents = None
+        self.last_beam_scores = scores
+        return ids
+
     @torch.inference_mode()
     def generate_groups(self, groups, **generate_kwargs):
         """Several generate() calls decoded TOGETHER: groups = [(cond_latents [B_i, 32, d], text_inputs [B_i, Tc_i]), ...] with
@@ -253,6 +322,7 @@ class GPT(nn.Module):
         the tokens of a segment by its duration): a group whose budget is spent leaves the joint decode, and the steps that remain
         run over the live streams only (fewer rows per step: the 8-row instead of the 16-row one-launch step for configs[2]'s tail).
         Returns a list of int64 [B_i, n_i] (reference gpt.py:594-609 per group)."""
+        _no_beams(generate_kwargs, "grouped (generate_groups)")
         self._need_engine()
         kw = dict(generate_kwargs)
         group = kw.pop("group", 16)          # decode steps per engine call (one host look at the finished flags per call)
@@ -372,6 +442,7 @@ class GPT(nn.Module):
         job j draws what generate(c_j, t_j, seed=job_seeds[j]) draws from the same logits, whatever it shares the decode step with (the
         rows step's logits themselves are not bit-identical across row counts: JOINT_SAMPLING_DEFAULT).  Without job_seeds a sampling
         call raises NotImplementedError."""
+        _no_beams(generate_kwargs, "rolling (generate_rolling)")
         self._need_engine()
         kw = dict(generate_kwargs)
         group = kw.pop("group", 16)
@@ -498,6 +569,7 @@ class GPT(nn.Module):
         """reference gpt.py:612-621 + stream_generator.py:865: yields (tokens int64[B], latent float[B,d]) per step,
         the EOS step included.  Steps run in groups of `stream_group` (default 8, the vocoder chunk of
         inference_utils.py:195) with one host check of the finished flags per group."""
+        _no_beams(generate_kwargs, "streaming (get_generator)")
         self._need_engine()
         group = generate_kwargs.pop("stream_group", 8)
         B = int(fake_inputs.shape[0])

@@ -230,6 +230,59 @@ int gvc_gpt_generate_rows(gvc_gpt* ctx, const int32_t* slots, int32_t B, int32_t
                           int32_t n_steps, int32_t max_keys, int32_t* tokens_out, int32_t tok_stride, float* latents_out,
                           int32_t lat_stride, gvc_stream s);
 
+/* ------------------------------------------------------------------------------------------
+ * Deterministic beam search (HF generate(num_beams=K, do_sample=False); reference layers/gpt.py:594-609 hands num_beams /
+ * length_penalty to HF generate, trainers/hifigan_trainer.py:457-500 forwards them, layers/gpt_inference.py:84-89 widens the
+ * prefix to B x K rows and :126-136 reorders the KV cache by beam).  Here the KV cache is not reordered: a beam is a slot, and a
+ * reorder is a permutation of the slot table plus at most K-1 span copies per item.
+ *
+ * Per step and item b (one workgroup): s = log_softmax(logits) in fp32 over the vocab of each of its K beam rows; repetition
+ * penalty on the log-probs over the ids of the beam's input_ids row (s < 0 ? s * p : s / p, each id once); s += running score;
+ * top-2K of the K x vocab candidates (descending); walk them in rank order: an eos candidate at rank < K becomes a finished
+ * hypothesis with score / len ** length_penalty, kept in a set of at most K (BeamHypotheses.add), an eos candidate at rank >= K is
+ * skipped, the first K other candidates become the next beams.  The item is done once its set is full and its worst kept score is
+ * >= best / len ** length_penalty.  length_mode 0 ("4.33", transformers 4.33 = the reference's pin): len = n0 + t for both, best =
+ * the best candidate of the step; 1 ("generated", transformers >= 4.50): len = t + 1 for both, best = the best next beam; t =
+ * tokens generated before the step.  A done item keeps its beams: tokens = eos, parents = identity, no copies.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct {
+    int32_t B, K;                   /* items, beams per item: 2 <= K <= 16, K * vocab <= 16 * 1026 */
+    int32_t vocab, eos;
+    int32_t n0;                     /* prompt length = positions of the fake ids (compute_embeddings) = KV positions after the prefill */
+    int32_t ids_stride;             /* >= n0 + max_new */
+    int32_t max_new;                /* hypothesis capacity in tokens (max_gen_mel_tokens) */
+    int32_t length_mode;            /* 0 "4.33", 1 "generated" */
+    float length_penalty, repetition_penalty;
+    int32_t* ids;                   /* [2][B*K][ids_stride] input_ids rows, double-buffered: step t reads buffer t & 1 (positions
+                                       [0, n0 + t)) and writes buffer (t + 1) & 1 gathered by parent, plus the new token at n0 + t */
+    float* scores;                  /* [B*K] running sums of the beams (start: 0 for beam 0, -1e9 for the others) */
+    int32_t* tokens;                /* [B*K] out: token of each next beam (the input of the next decode step) */
+    int32_t* parents;               /* [B*K] out: beam (0..K-1 within the item) each next beam continues */
+    int32_t* done;                  /* [B] item done (0 / 1) */
+    float* hyp_score;               /* [B][K] finished hypotheses: normalised score */
+    int32_t* hyp_len;               /* [B][K] ... generated tokens, eos excluded */
+    int32_t* hyp_tok;               /* [B][K][max_new] ... the tokens */
+    int32_t* hyp_count;             /* [B] hypotheses kept (start 0) */
+    float* hyp_worst;               /* [B] worst kept score (start 1e9) */
+    int32_t* copies;                /* [B][K][3] (src slot, dst slot, first position) of the KV spans the reorder needs */
+    int32_t* n_copies;              /* [B] copies of the last step (<= K - 1) */
+} gvc_beam_state;
+
+/* One select step on caller-given logits [B*K][vocab] (device), state st (device arrays), slots [B*K] (device, in/out: the KV slot of
+ * each beam row; rewritten by the slot permutation: a parent's slot goes to its first child, further children take the slots of
+ * childless parents, each such take is a copies entry) at step t (t tokens generated before).  The KV cache itself is not touched.
+ * For tests and for callers that decode themselves. */
+int gvc_beam_select(const gvc_beam_state* st, const float* logits, int32_t* slots, int32_t t, gvc_stream s);
+
+/* n_steps beam steps [select -> KV span copies -> decode step over B*K rows], replayed from captured graphs (eight steps per graph,
+ * as gvc_gpt_generate) with all state on the device.  The caller has prefilled item b into slots[b*K] (gvc_gpt_prefill) and
+ * initialised st (i0 == 0); slots[b*K+1 .. b*K+K-1] are free slots the first step fans the prefix out to (the item is prefilled
+ * once).  Step i of the call is step t = i0 + i of the search; slots is rewritten to the beams' slots at return; consecutive calls
+ * continue the search.  max_keys as in gvc_gpt_generate (n0 + i0 + n_steps).  Status codes as gvc_gpt_generate: a hand-off
+ * time-out is reported by gvc_gpt_health / the next call as GVC_ERR_TIMEOUT and the search must be repeated from its prefill. */
+int gvc_gpt_beam_generate(gvc_gpt* ctx, int32_t* slots, const gvc_beam_state* st, int32_t i0, int32_t n_steps, int32_t max_keys,
+                          gvc_stream s);
+
 /* Which decode step the last gvc_gpt_generate call replayed (diagnostic): 0 none yet, 1 launch-per-phase with split-key attention,
  * 2 launch-per-phase with the fused short-context attention launch, 3 the one-launch step (one stream), 4 the MFMA rows path
  * (launch per phase: 17+ streams, or shapes the one-launch rows step does not serve), 5 the one-launch rows step (2..16 streams,
@@ -258,6 +311,9 @@ int gvc_gpt_warmup(gvc_gpt* ctx, int32_t B, int32_t max_keys, int32_t top_k);
  * cached positions (the library keys its step graphs by classes of the context length -- fused / split-key attention, 1 / 2 / 4 key chunks
  * of the rows steps -- whose thresholds are its own business: callers name the range, not the classes). */
 int gvc_gpt_warmup_range(gvc_gpt* ctx, int32_t B, int32_t min_keys, int32_t max_keys, int32_t top_k);
+/* gvc_gpt_warmup for gvc_gpt_beam_generate over B items of K beams: the beam step graphs of every context class up to max_keys cached
+ * positions (and everything gvc_gpt_warmup(B*K) prepares).  Afterwards such calls neither allocate nor synchronise */
+int gvc_gpt_warmup_beam(gvc_gpt* ctx, int32_t B, int32_t K, int32_t max_keys);
 /* Diagnostic: allocations / device-wide synchronisations / graph captures this context has done INSIDE data-path calls (first use
  * of a path that gvc_gpt_warmup had not prepared; a rebind after the weight pack was built; the fallback after a hand-off
  * time-out).  gvc_gpt_warmup's own work does not count.  Tests assert it stays put across warmed-up calls. */

@@ -29,7 +29,11 @@ if __name__ == "__main__":
     parser.add_argument("--save_tokens", type=str, default=None)
     parser.add_argument("--weights", type=str, default="fp32", choices=["fp32", "bf16", "bf16_kv", "bf16_act"],
                         help="GPT weight / KV-cache storage on the GPU (fp32 = the reference's numerics)")
+    parser.add_argument("--num_beams", type=int, default=1,
+                        help="non-streaming only: > 1 decodes with deterministic beam search (do_sample=False) of this width")
     args = parser.parse_args()
+    if args.num_beams < 1 or (args.streaming and args.num_beams != 1):
+        raise SystemExit("--num_beams must be >= 1, and 1 with --streaming")
 
     if args.synthetic:
         from genvc_amd import config as gcfg
@@ -48,7 +52,7 @@ if __name__ == "__main__":
         toks = torch.cat(out["tokens"], 1)
         lat = torch.cat(out["latents"], 1)
     else:
-        out = synthesize_utt(model, src_wav, ref_audio, seg_len=args.seg_len, return_details=True)
+        out = synthesize_utt(model, src_wav, ref_audio, seg_len=args.seg_len, return_details=True, num_beams=args.num_beams)
         toks = torch.cat(out["codes"]).unsqueeze(0)
         lat = out["latents"]
     print(f"generated {toks.shape[-1]} codec tokens, latents {tuple(lat.shape)}")
