@@ -36,6 +36,14 @@ class BeamState(C.Structure):
                                    "hyp_worst", "copies", "n_copies")]
 
 
+class LogitsProcessors(C.Structure):
+    """gvc_logits_processors (include/genvc_hip.h): one call's length / repetition processors; all zero = every processor off"""
+    _fields_ = [(n, C.c_int32) for n in ("no_repeat_ngram_size", "min_length", "min_new_tokens", "decay_start")] + \
+        [("decay_factor", C.c_float), ("min_p", C.c_float)] + \
+        [(n, C.c_int32) for n in ("prompt_len", "n_suppress", "n_begin_suppress", "reserved")] + \
+        [("prompt_lens", C.c_void_p), ("suppress", C.c_uint32 * 33), ("begin_suppress", C.c_uint32 * 33)]
+
+
 class PerceiverDims(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("dim", "depth", "dim_context", "num_latents", "dim_head", "heads",
                                          "ff_mult", "max_batch", "max_frames")]
@@ -84,6 +92,14 @@ _SIGNATURES = {
     "gvc_beam_select": (C.c_int, [C.POINTER(BeamState), _P, _P, C.c_int32, _P]),
     "gvc_gpt_beam_generate": (C.c_int, [_P, _P, C.POINTER(BeamState), C.c_int32, C.c_int32, C.c_int32, _P]),
     "gvc_gpt_warmup_beam": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32]),
+    "gvc_sample_proc": (C.c_int, [_P, C.c_int32, _P, C.c_int32, _P, _P, C.POINTER(SampleParams), C.POINTER(RowSampling),
+                                  C.POINTER(LogitsProcessors), C.c_int32, _P, _P]),
+    "gvc_gpt_generate_proc": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, _P, _P, C.POINTER(SampleParams), C.POINTER(RowSampling),
+                                        C.POINTER(LogitsProcessors), C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_int32,
+                                        _P]),
+    "gvc_beam_select_proc": (C.c_int, [C.POINTER(BeamState), C.POINTER(LogitsProcessors), _P, _P, C.c_int32, _P]),
+    "gvc_gpt_beam_generate_proc": (C.c_int, [_P, _P, C.POINTER(BeamState), C.POINTER(LogitsProcessors), C.c_int32, C.c_int32,
+                                             C.c_int32, _P]),
     "gvc_gpt_decode_variant": (C.c_int, [_P]),
     "gvc_gpt_rows_step_launches": (C.c_longlong, [_P]),
     "gvc_gpt_health": (C.c_int, [_P]),

@@ -3,6 +3,7 @@
 // KV span copies a reorder needs.  The step graph that chains them with the decode step lives in gpt.hip.
 #pragma once
 #include "common.h"
+#include "logits_proc.h"
 
 namespace gvc {
 
@@ -15,21 +16,25 @@ constexpr int kBeamPer = (kBeamMaxN + kBeamThreads - 1) / kBeamThreads;
 struct BeamCall {
     gvc_beam_state st;
     int32_t step;                 // t of the next select (advanced by the span-copy launch of every step)
+    int32_t has_proc;             // proc applies (gvc_gpt_beam_generate_proc); 0: the select step computes what it does without it
+    gvc_logits_processors proc;
 };
 
 int beam_check(const gvc_beam_state& st);
 // one select step: st by value (call == nullptr, step t) or from the device-resident call (graph replay: call->st, call->step).
 // seq_len / mel_pos (nullable): per-slot decode state, copied from a copy's source slot to its destination; tok_buf (nullable): a second
 // home of the next tokens (the decode step's input)
-int launch_beam_select(const gvc_beam_state& st, const BeamCall* call, int B, int K, const float* logits, int32_t* slots, int t,
+// proc (device, nullable) serves the by-value form; graph replay reads call->has_proc / call->proc
+int launch_beam_select(const gvc_beam_state& st, const gvc_logits_processors* proc, const BeamCall* call, int B, int K, const float* logits, int32_t* slots, int t,
                        int32_t* seq_len, int32_t* mel_pos, int32_t* tok_buf, hipStream_t s);
 // the spans of the last select's copy lists (call->st.copies), for every (layer, k|v, head) run of the cache
 // [L][2][slot][H][max_seq][hd] (esz bytes per element); a fixed grid over B*(K-1) possible copies (graph replay) with early exit.
 // Advances call->step by one
 int launch_kv_copy_span(BeamCall* call, int B, int K, void* kv, int n_layer, int n_head, int max_seq, int hd, int max_slots, int esz,
                         const int32_t* seq_len, hipStream_t s);
-// start / end of a gvc_gpt_beam_generate call: store the call state, un-park (park) the logits of every beam row
-int launch_beam_begin(BeamCall* dst, const gvc_beam_state& st, int i0, const int32_t* slots_in, int32_t* slot_table, float* logits,
+// start / end of a gvc_gpt_beam_generate call: store the call state (and the processors, host proc nullable), un-park (park) the
+// logits of every beam row
+int launch_beam_begin(BeamCall* dst, const gvc_beam_state& st, const gvc_logits_processors* proc, int i0, const int32_t* slots_in, int32_t* slot_table, float* logits,
                       const float* slot_logits, hipStream_t s);
 int launch_beam_end(const int32_t* slot_table, int32_t* slots_out, int BK, const float* logits, float* slot_logits, int vocab,
                     hipStream_t s);

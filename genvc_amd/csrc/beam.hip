@@ -11,11 +11,12 @@ __device__ __forceinline__ uint32_t f2key(float v) {         // monotone: a larg
 // One workgroup per item.  Candidate e = k * V + x (beam k, token x) of the item lives in thread e % 512's registers, slot e / 512.
 // The top-2K is a 4-pass 8-bit radix select on the keys (histograms in LDS), then a one-wave rank sort of the <= 32 survivors
 // (ties by lower flat index); one lane walks them.
-__global__ void __launch_bounds__(kBeamThreads) k_beam_select(gvc_beam_state st_arg, const BeamCall* call, const float* logits,
-                                                              int32_t* slots, int t_arg, int32_t* seq_len, int32_t* mel_pos,
-                                                              int32_t* tok_buf) {
+__global__ void __launch_bounds__(kBeamThreads) k_beam_select(gvc_beam_state st_arg, const gvc_logits_processors* proc_arg,
+                                                              const BeamCall* call, const float* logits, int32_t* slots, int t_arg,
+                                                              int32_t* seq_len, int32_t* mel_pos, int32_t* tok_buf) {
     const gvc_beam_state& st = call ? call->st : st_arg;
     const int t = call ? call->step : t_arg;
+    const gvc_logits_processors* P = call ? (call->has_proc ? &call->proc : nullptr) : proc_arg;
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int K = st.K, V = st.vocab, N = K * V, M = 2 * K, eos = st.eos;
     const int BK = st.B * K, W = st.ids_stride, L = st.n0 + t;
@@ -32,7 +33,9 @@ __global__ void __launch_bounds__(kBeamThreads) k_beam_select(gvc_beam_state st_
     __shared__ int nx_tok[kBeamMaxK], nx_par[kBeamMaxK], new_slot[kBeamMaxK], pend[kBeamMaxK];
     __shared__ float nx_sc[kBeamMaxK];
     __shared__ int sh_done;
+    __shared__ uint32_t kill[kBeamMaxK * kProcWords];           // processor bans per beam (logits_proc.h)
 
+    ProcStep ps{false, 0.f};
     if (tid == 0) sh_done = st.done[b];
     for (int i = tid; i < K * 33; i += kBeamThreads) pen[i] = 0u;
     __syncthreads();
@@ -56,6 +59,13 @@ __global__ void __launch_bounds__(kBeamThreads) k_beam_select(gvc_beam_state st_
                 if (id >= 0 && id < V) atomicOr(&pen[k * 33 + (id >> 5)], 1u << (id & 31));
             }
         }
+        if (P) {
+            // every beam row has length L = n0 + t and prompt n0: the scalar bans are the item's, the n-gram bans each beam's own
+            for (int k = 0; k < K; ++k) ps = proc_row_begin(*P, L, st.n0, eos, kill + k * kProcWords, tid);
+            __syncthreads();
+            for (int k = 0; k < K; ++k)
+                proc_ngram(ids_in + (size_t)(b * K + k) * W, L, P->no_repeat_ngram_size, V, kill + k * kProcWords, tid, kBeamThreads);
+        }
         __syncthreads();
     }
     const float rp = st.repetition_penalty;
@@ -70,6 +80,7 @@ __global__ void __launch_bounds__(kBeamThreads) k_beam_select(gvc_beam_state st_
                 const int k = e / V, x = e - k * V;
                 v = (logits[(size_t)(b * K + k) * V + x] - lse[k]) - run[k];
                 if (pen[k * 33 + (x >> 5)] & (1u << (x & 31))) v = v < 0.f ? v * rp : v / rp;
+                if (P) v = proc_score(v, x, eos, ps, kill + k * kProcWords);
                 v += st.scores[b * K + k];
             }
             val[i] = v;
@@ -267,7 +278,7 @@ __global__ void k_beam_begin(BeamCall* dst, gvc_beam_state st, int i0, const int
                              const float* slot_logits) {
     const int BK = st.B * st.K, r = blockIdx.x;
     if (r == BK) {
-        if (threadIdx.x == 0) { dst->st = st; dst->step = i0; }
+        if (threadIdx.x == 0) { dst->st = st; dst->step = i0; dst->has_proc = 0; }
         if ((int)threadIdx.x < BK) slot_table[threadIdx.x] = slots_in[threadIdx.x];
         return;
     }
@@ -298,10 +309,14 @@ int beam_check(const gvc_beam_state& st) {
     return GVC_OK;
 }
 
-int launch_beam_select(const gvc_beam_state& st, const BeamCall* call, int B, int K, const float* logits, int32_t* slots, int t,
-                       int32_t* seq_len, int32_t* mel_pos, int32_t* tok_buf, hipStream_t s) {
+__global__ void k_beam_proc(BeamCall* dst, gvc_logits_processors proc) {
+    if (threadIdx.x == 0) { dst->proc = proc; dst->has_proc = 1; }
+}
+
+int launch_beam_select(const gvc_beam_state& st, const gvc_logits_processors* proc, const BeamCall* call, int B, int K,
+                       const float* logits, int32_t* slots, int t, int32_t* seq_len, int32_t* mel_pos, int32_t* tok_buf, hipStream_t s) {
     (void)K;
-    hipLaunchKernelGGL(k_beam_select, dim3(B), dim3(kBeamThreads), 0, s, st, call, logits, slots, t, seq_len, mel_pos, tok_buf);
+    hipLaunchKernelGGL(k_beam_select, dim3(B), dim3(kBeamThreads), 0, s, st, proc, call, logits, slots, t, seq_len, mel_pos, tok_buf);
     GVC_LAUNCH_CHECK();
     return GVC_OK;
 }
@@ -316,11 +331,16 @@ int launch_kv_copy_span(BeamCall* call, int B, int K, void* kv, int n_layer, int
     return GVC_OK;
 }
 
-int launch_beam_begin(BeamCall* dst, const gvc_beam_state& st, int i0, const int32_t* slots_in, int32_t* slot_table, float* logits,
-                      const float* slot_logits, hipStream_t s) {
+int launch_beam_begin(BeamCall* dst, const gvc_beam_state& st, const gvc_logits_processors* proc, int i0, const int32_t* slots_in,
+                      int32_t* slot_table, float* logits, const float* slot_logits, hipStream_t s) {
     const int BK = st.B * st.K;
     hipLaunchKernelGGL(k_beam_begin, dim3(BK + 1), dim3(256), 0, s, dst, st, i0, slots_in, slot_table, logits, slot_logits);
     GVC_LAUNCH_CHECK();
+    if (proc) {
+        // (a second tiny launch, stream-ordered behind the begin that cleared has_proc; the struct travels as a kernel argument)
+        hipLaunchKernelGGL(k_beam_proc, dim3(1), dim3(64), 0, s, dst, *proc);
+        GVC_LAUNCH_CHECK();
+    }
     return GVC_OK;
 }
 
@@ -338,5 +358,29 @@ extern "C" int gvc_beam_select(const gvc_beam_state* st, const float* logits, in
     int rc = gvc::beam_check(*st);
     if (rc) return rc;
     GVC_REQUIRE(t < st->max_new && st->n0 + t < st->ids_stride, GVC_ERR_ARG, "beam_select: step %d past max_new %d", t, st->max_new);
-    return gvc::launch_beam_select(*st, nullptr, st->B, st->K, logits, slots, t, nullptr, nullptr, nullptr, (hipStream_t)sv);
+    return gvc::launch_beam_select(*st, nullptr, nullptr, st->B, st->K, logits, slots, t, nullptr, nullptr, nullptr, (hipStream_t)sv);
+}
+
+extern "C" int gvc_beam_select_proc(const gvc_beam_state* st, const gvc_logits_processors* proc, const float* logits, int32_t* slots,
+                                    int32_t t, gvc_stream sv) {
+    GVC_REQUIRE(st && proc && logits && slots && t >= 0, GVC_ERR_ARG, "beam_select_proc: bad argument");
+    int rc = gvc::beam_check(*st);
+    if (rc) return rc;
+    if ((rc = gvc::check_procs(*proc, st->vocab))) return rc;
+    GVC_REQUIRE(t < st->max_new && st->n0 + t < st->ids_stride, GVC_ERR_ARG, "beam_select: step %d past max_new %d", t, st->max_new);
+    hipStream_t s = (hipStream_t)sv;
+    // a context-free entry point (tests, callers that decode themselves): the processors are staged for this call only
+    gvc::BeamCall* d = nullptr;
+    GVC_CHECK_HIP(hipMallocAsync((void**)&d, sizeof(gvc::BeamCall), s));
+    hipLaunchKernelGGL(gvc::k_beam_proc, dim3(1), dim3(64), 0, s, d, *proc);
+    const hipError_t e = hipGetLastError();
+    if (e == hipSuccess)
+        rc = gvc::launch_beam_select(*st, &d->proc, nullptr, st->B, st->K, logits, slots, t, nullptr, nullptr, nullptr, s);
+    else
+        gvc::set_error("beam_select_proc: staging launch failed: %s", hipGetErrorString(e));
+    const hipError_t e2 = hipFreeAsync(d, s);
+    if (e != hipSuccess) return GVC_ERR_HIP;
+    if (rc) return rc;
+    GVC_CHECK_HIP(e2);
+    return GVC_OK;
 }

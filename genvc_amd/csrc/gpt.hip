@@ -179,6 +179,7 @@ struct GenCall {
     SampleCall sc;
     int32_t slots[64];
     gvc_row_sampling rows[kMaxSampleRows];   // per-row settings and keys of a gvc_gpt_generate_rows call (sc.rows points here)
+    gvc_logits_processors proc;              // processors of a gvc_gpt_generate_proc call (sc.proc points here)
 };
 
 // Start / end of a gvc_gpt_generate call in ONE launch each (they used to be a memset, k_set_gen_call and two k_stage_rows before the
@@ -209,6 +210,18 @@ __global__ void k_gen_begin(GenCall* dst, SampleCall sc, const int32_t* slots, i
 __global__ void k_gen_begin_rows(GenCall* dst, SampleCall sc, const int32_t* slots, int B, int32_t* step_ctr, float* logits,
                                  float* slot_logits, int vocab, float* latent, float* slot_latent, int d, SampleRows rows) {
     if ((int)blockIdx.x == B && (int)threadIdx.x < B) dst->rows[threadIdx.x] = rows.r[threadIdx.x];
+    gen_begin(dst, sc, slots, B, step_ctr, logits, slot_logits, vocab, latent, slot_latent, d);
+}
+
+// gvc_gpt_generate_proc: the same, and workgroup B also stores the call's processors (and row entries when ROWS), both kernel arguments
+template <bool ROWS>
+__global__ void k_gen_begin_proc(GenCall* dst, SampleCall sc, const int32_t* slots, int B, int32_t* step_ctr, float* logits,
+                                 float* slot_logits, int vocab, float* latent, float* slot_latent, int d, SampleRows rows,
+                                 gvc_logits_processors proc) {
+    if ((int)blockIdx.x == B) {
+        if (ROWS && (int)threadIdx.x < B) dst->rows[threadIdx.x] = rows.r[threadIdx.x];
+        if (threadIdx.x == 0) dst->proc = proc;
+    }
     gen_begin(dst, sc, slots, B, step_ctr, logits, slot_logits, vocab, latent, slot_latent, d);
 }
 
@@ -1616,13 +1629,15 @@ extern "C" int gvc_gpt_rearm(gvc_gpt* c) {
 
 // rows: null (gvc_gpt_generate: p's settings for every row) or B host entries (gvc_gpt_generate_rows)
 static int generate_impl(gvc_gpt* c, const int32_t* slots, int32_t B, int32_t* ids, int32_t ids_stride, int32_t* ids_len, int32_t* finished,
-                         const gvc_sample_params* p, const gvc_row_sampling* rows, int32_t i0, int32_t n_steps, int32_t max_keys,
-                         int32_t* tokens_out, int32_t tok_stride, float* latents_out, int32_t lat_stride, gvc_stream sv) {
+                         const gvc_sample_params* p, const gvc_row_sampling* rows, const gvc_logits_processors* proc, int32_t i0,
+                         int32_t n_steps, int32_t max_keys, int32_t* tokens_out, int32_t tok_stride, float* latents_out, int32_t lat_stride,
+                         gvc_stream sv) {
     int rc = check_ready(c);
     if (rc) return rc;
     GVC_REQUIRE(B >= 1 && B <= c->dm.max_slots && p && n_steps >= 0 && max_keys >= 0, GVC_ERR_ARG, "generate: bad argument");
     bool rows_greedy = false;
     if (rows && (rc = check_sample_rows(rows, B, c->dm.vocab, &rows_greedy))) return rc;
+    if (proc && (rc = check_procs(*proc, c->dm.vocab))) return rc;
     // cached positions of the longest stream once this call has run: the caller's bound, else the whole ids row
     const int key_bound = max_keys > 0 ? max_keys : ids_stride;
     GVC_REQUIRE(max_keys == 0 || max_keys < c->dm.max_seq, GVC_ERR_STATE,
@@ -1635,7 +1650,22 @@ static int generate_impl(gvc_gpt* c, const int32_t* slots, int32_t B, int32_t* i
     sc.finished = finished; sc.p = *p; sc.step = 0; sc.step_ptr = c->step_ctr; sc.tok_out = c->tok_buf;
     sc.tokens_out = tokens_out; sc.tok_stride = tok_stride; sc.i0 = i0; sc.latent_src = c->latent;
     sc.latents_out = latents_out; sc.lat_stride = lat_stride; sc.d = c->dm.d_model;
-    if (rows) {
+    if (proc) {
+        // (the processors travel as a kernel argument, as the rows do: nothing to allocate, and the caller's struct is free on return)
+        SampleRows sr;
+        memset(&sr, 0, sizeof(sr));
+        if (rows) {
+            memcpy(sr.r, rows, (size_t)B * sizeof(gvc_row_sampling));
+            sc.rows = c->gen_call->rows;
+        }
+        sc.proc = &c->gen_call->proc;
+        if (rows)
+            hipLaunchKernelGGL(k_gen_begin_proc<true>, dim3(B + 1), dim3(256), 0, s, c->gen_call, sc, slots, B, c->step_ctr, c->logits,
+                               c->slot_logits, c->dm.vocab, c->latent, c->slot_latent, c->dm.d_model, sr, *proc);
+        else
+            hipLaunchKernelGGL(k_gen_begin_proc<false>, dim3(B + 1), dim3(256), 0, s, c->gen_call, sc, slots, B, c->step_ctr, c->logits,
+                               c->slot_logits, c->dm.vocab, c->latent, c->slot_latent, c->dm.d_model, sr, *proc);
+    } else if (rows) {
         SampleRows sr;
         memset(&sr, 0, sizeof(sr));
         memcpy(sr.r, rows, (size_t)B * sizeof(gvc_row_sampling));
@@ -1673,8 +1703,8 @@ extern "C" int gvc_gpt_generate(gvc_gpt* c, const int32_t* slots, int32_t B, int
                                 int32_t* ids_len, int32_t* finished, const gvc_sample_params* p, int32_t i0,
                                 int32_t n_steps, int32_t max_keys, int32_t* tokens_out, int32_t tok_stride, float* latents_out,
                                 int32_t lat_stride, gvc_stream sv) {
-    return generate_impl(c, slots, B, ids, ids_stride, ids_len, finished, p, nullptr, i0, n_steps, max_keys, tokens_out, tok_stride,
-                         latents_out, lat_stride, sv);
+    return generate_impl(c, slots, B, ids, ids_stride, ids_len, finished, p, nullptr, nullptr, i0, n_steps, max_keys, tokens_out,
+                         tok_stride, latents_out, lat_stride, sv);
 }
 
 extern "C" int gvc_gpt_generate_rows(gvc_gpt* c, const int32_t* slots, int32_t B, int32_t* ids, int32_t ids_stride, int32_t* ids_len,
@@ -1682,7 +1712,15 @@ extern "C" int gvc_gpt_generate_rows(gvc_gpt* c, const int32_t* slots, int32_t B
                                      int32_t n_steps, int32_t max_keys, int32_t* tokens_out, int32_t tok_stride, float* latents_out,
                                      int32_t lat_stride, gvc_stream sv) {
     GVC_REQUIRE(rows, GVC_ERR_ARG, "generate_rows: null rows");
-    return generate_impl(c, slots, B, ids, ids_stride, ids_len, finished, common, rows, i0, n_steps, max_keys, tokens_out, tok_stride,
+    return generate_impl(c, slots, B, ids, ids_stride, ids_len, finished, common, rows, nullptr, i0, n_steps, max_keys, tokens_out,
+                         tok_stride, latents_out, lat_stride, sv);
+}
+
+extern "C" int gvc_gpt_generate_proc(gvc_gpt* c, const int32_t* slots, int32_t B, int32_t* ids, int32_t ids_stride, int32_t* ids_len,
+                                     int32_t* finished, const gvc_sample_params* p, const gvc_row_sampling* rows,
+                                     const gvc_logits_processors* proc, int32_t i0, int32_t n_steps, int32_t max_keys, int32_t* tokens_out,
+                                     int32_t tok_stride, float* latents_out, int32_t lat_stride, gvc_stream sv) {
+    return generate_impl(c, slots, B, ids, ids_stride, ids_len, finished, p, rows, proc, i0, n_steps, max_keys, tokens_out, tok_stride,
                          latents_out, lat_stride, sv);
 }
 
@@ -1702,7 +1740,7 @@ static int build_beam_graph(gvc_gpt* c, int B, int K, const GenPlan& pl, int n_u
     memset(&dummy, 0, sizeof(dummy));
     GVC_CHECK_HIP(hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal));
     for (int u = 0; u < n_unroll && rc == GVC_OK; ++u) {
-        rc = launch_beam_select(dummy, c->beam_call, B, K, c->logits, table, 0, c->st.seq_len, c->st.mel_pos, c->tok_buf, cs);
+        rc = launch_beam_select(dummy, nullptr, c->beam_call, B, K, c->logits, table, 0, c->st.seq_len, c->st.mel_pos, c->tok_buf, cs);
         if (rc == GVC_OK)
             rc = launch_kv_copy_span(c->beam_call, B, K, c->kv, c->dm.n_layer, c->dm.n_head, c->dm.max_seq, c->hd, c->dm.max_slots,
                                      c->kv_bf16 ? 2 : 4, c->st.seq_len, cs);
@@ -1773,12 +1811,13 @@ extern "C" int gvc_gpt_warmup_beam(gvc_gpt* c, int32_t B, int32_t K, int32_t max
     return GVC_OK;
 }
 
-extern "C" int gvc_gpt_beam_generate(gvc_gpt* c, int32_t* slots, const gvc_beam_state* st, int32_t i0, int32_t n_steps, int32_t max_keys,
-                                     gvc_stream sv) {
+static int beam_generate_impl(gvc_gpt* c, int32_t* slots, const gvc_beam_state* st, const gvc_logits_processors* proc, int32_t i0,
+                              int32_t n_steps, int32_t max_keys, gvc_stream sv) {
     int rc = check_ready(c);
     if (rc) return rc;
     GVC_REQUIRE(slots && st && i0 >= 0 && n_steps >= 0 && max_keys >= 0, GVC_ERR_ARG, "beam_generate: bad argument");
     if ((rc = beam_check(*st))) return rc;
+    if (proc && (rc = check_procs(*proc, st->vocab))) return rc;
     GVC_REQUIRE(st->vocab == c->dm.vocab, GVC_ERR_ARG, "beam_generate: vocab mismatch");
     GVC_REQUIRE(i0 + n_steps <= st->max_new, GVC_ERR_ARG, "beam_generate: steps %d..%d past max_new %d", i0, i0 + n_steps, st->max_new);
     const int key_bound = max_keys > 0 ? max_keys : st->n0 + i0 + n_steps;
@@ -1788,7 +1827,7 @@ extern "C" int gvc_gpt_beam_generate(gvc_gpt* c, int32_t* slots, const gvc_beam_
     const int B = st->B, K = st->K, BK = B * K;
     GenPlan pl;
     if ((rc = beam_plan(c, B, K, key_bound, &pl))) return rc;
-    if ((rc = launch_beam_begin(c->beam_call, *st, i0, slots, c->gen_call->slots, c->logits, c->slot_logits, s))) return rc;
+    if ((rc = launch_beam_begin(c->beam_call, *st, proc, i0, slots, c->gen_call->slots, c->logits, c->slot_logits, s))) return rc;
     c->last_variant = pl.variant;
     const int kStepUnroll = step_unroll();
     int left = n_steps;
@@ -1803,6 +1842,16 @@ extern "C" int gvc_gpt_beam_generate(gvc_gpt* c, int32_t* slots, const gvc_beam_
         for (; left > 0; --left) GVC_CHECK_HIP(hipGraphLaunch(ge, s));
     }
     return launch_beam_end(c->gen_call->slots, slots, BK, c->logits, c->slot_logits, c->dm.vocab, s);
+}
+
+extern "C" int gvc_gpt_beam_generate(gvc_gpt* c, int32_t* slots, const gvc_beam_state* st, int32_t i0, int32_t n_steps, int32_t max_keys,
+                                     gvc_stream sv) {
+    return beam_generate_impl(c, slots, st, nullptr, i0, n_steps, max_keys, sv);
+}
+
+extern "C" int gvc_gpt_beam_generate_proc(gvc_gpt* c, int32_t* slots, const gvc_beam_state* st, const gvc_logits_processors* proc,
+                                          int32_t i0, int32_t n_steps, int32_t max_keys, gvc_stream sv) {
+    return beam_generate_impl(c, slots, st, proc, i0, n_steps, max_keys, sv);
 }
 
 // ---------------------------------------------------------------------------------------------

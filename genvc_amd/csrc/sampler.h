@@ -5,6 +5,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "logits_proc.h"
 
 namespace gvc {
 
@@ -29,6 +30,9 @@ struct SampleCall {
     // rng_uniform(seed_b, rng_step0_b + step, rng_row_b); p then carries eos_token / vocab only, and p.top_k == 1 tells
     // launch_sample that every row is greedy.
     const gvc_row_sampling* rows;
+    // nullable: the call's length / repetition processors (gvc_logits_processors, device memory).  Null: none, and the kernels
+    // compute exactly what they compute without this field
+    const gvc_logits_processors* proc;
 };
 
 int launch_sample(const SampleCall& sc, hipStream_t s);

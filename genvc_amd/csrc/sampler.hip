@@ -53,6 +53,7 @@ __global__ __launch_bounds__(kSampThreads) void k_sample(SampleCall cv, const Sa
     __shared__ float fscr[17];
     __shared__ int iscr[17];
     __shared__ double dscr[17];
+    __shared__ uint32_t kill[kProcWords];
     const SampleCall& C = cp ? *cp : cv;
     const int b = blockIdx.x, tid = threadIdx.x;
     const int V = C.p.vocab;
@@ -66,20 +67,25 @@ __global__ __launch_bounds__(kSampThreads) void k_sample(SampleCall cv, const Sa
     const float temp = R ? R->temperature : C.p.temperature;
     const float top_p = R ? R->top_p : C.p.top_p;
     const int top_k = R ? R->top_k : C.p.top_k;
+    const gvc_logits_processors* P = C.proc;
 
     for (int i = tid; i < kSortN; i += kSampThreads) seen[i] = 0;
+    ProcStep ps{false, 0.f};
+    if (P) ps = proc_row_begin(*P, len, P->prompt_lens ? P->prompt_lens[b] : P->prompt_len, C.p.eos_token, kill, tid);
     __syncthreads();
     for (int i = tid; i < len; i += kSampThreads) {
         const int id = ids[i];
         if (id >= 0 && id < V) seen[id] = 1;
     }
+    if (P) proc_ngram(ids, len, P->no_repeat_ngram_size, V, kill, tid, kSampThreads);
     __syncthreads();
-    // RepetitionPenalty (every id of input_ids incl. the fake prefix, once) then Temperature
+    // RepetitionPenalty (every id of input_ids incl. the fake prefix, once), the processors, then Temperature
     for (int i = tid; i < kSortN; i += kSampThreads) {
         float v = -INFINITY;
         if (i < V) {
             v = lg[i];
             if (seen[i]) v = v < 0.f ? v * rep_pen : v / rep_pen;
+            if (P) v = proc_score(v, i, C.p.eos_token, ps, kill);
             v = v / temp;
         }
         sc[i] = v;
@@ -176,7 +182,13 @@ __global__ __launch_bounds__(kSampThreads) void k_sample(SampleCall cv, const Sa
         // draw: first kept vocabulary index whose running mass (double, vocabulary order) reaches u * total
         {
             const int i0v = 2 * tid, i1v = 2 * tid + 1;
-            const bool k0 = i0v < V && sc[i0v] >= thresh, k1 = i1v < V && sc[i1v] >= thresh;
+            bool k0 = i0v < V && sc[i0v] >= thresh, k1 = i1v < V && sc[i1v] >= thresh;
+            // MinP (after TopP): softmax(s)_i < min_p * max softmax  <=>  exp(s_i - max) < min_p; the top score always stays
+            const float min_p = P ? P->min_p : 0.f;
+            if (min_p > 0.f) {
+                if (k0 && expf(sc[i0v] - mx) < min_p) k0 = false;
+                if (k1 && expf(sc[i1v] - mx) < min_p) k1 = false;
+            }
             const double w0 = k0 ? (double)expf(sc[i0v] - mx) : 0.0, w1 = k1 ? (double)expf(sc[i1v] - mx) : 0.0;
             double total;
             const double ex = block_scan_excl<double>(w0 + w1, dscr, &total);
@@ -217,7 +229,7 @@ __global__ __launch_bounds__(kSampThreads) void k_sample(SampleCall cv, const Sa
 }
 
 // top_k = 1 (the configuration of every BASELINE workload that fixes top_k: TopK(1) leaves one candidate, so top-p and the draw are
-// no-ops): RepetitionPenalty -> Temperature -> argmax with the arithmetic of k_sample, on 256 threads -- four waves meet at four
+// no-ops): RepetitionPenalty -> [processors] -> Temperature -> argmax with the arithmetic of k_sample, on 256 threads -- four waves meet at four
 // barriers instead of sixteen at six, and nothing is sorted (7.7 -> ~5 us per decode step)
 constexpr int kGreedyThreads = 256;
 __global__ __launch_bounds__(kGreedyThreads) void k_sample_greedy(SampleCall cv, const SampleCall* cp) {
@@ -225,6 +237,7 @@ __global__ __launch_bounds__(kGreedyThreads) void k_sample_greedy(SampleCall cv,
     __shared__ float red_v[kGreedyThreads / 64];
     __shared__ int red_i[kGreedyThreads / 64];
     __shared__ int s_tok;
+    __shared__ uint32_t kill[kProcWords];
     unsigned char* seen = reinterpret_cast<unsigned char*>(seen_w);
     const SampleCall& C = cp ? *cp : cv;
     const int b = blockIdx.x, tid = threadIdx.x;
@@ -241,11 +254,15 @@ __global__ __launch_bounds__(kGreedyThreads) void k_sample_greedy(SampleCall cv,
 #pragma unroll
     for (int u = 0; u < PER; ++u) { const int i = tid + u * kGreedyThreads; v[u] = i < V ? lg[i] : -INFINITY; }
     for (int i = tid; i < kSortN / 4; i += kGreedyThreads) seen_w[i] = 0u;
+    const gvc_logits_processors* P = C.proc;
+    ProcStep ps{false, 0.f};
+    if (P) ps = proc_row_begin(*P, len, P->prompt_lens ? P->prompt_lens[b] : P->prompt_len, C.p.eos_token, kill, tid);
     __syncthreads();
     for (int i = tid; i < len; i += kGreedyThreads) {
         const int id = ids[i];
         if (id >= 0 && id < V) seen[id] = 1;
     }
+    if (P) proc_ngram(ids, len, P->no_repeat_ngram_size, V, kill, tid, kGreedyThreads);
     __syncthreads();
     float bv = -INFINITY; int bi = 0x7fffffff;
 #pragma unroll
@@ -254,6 +271,7 @@ __global__ __launch_bounds__(kGreedyThreads) void k_sample_greedy(SampleCall cv,
         if (i < V) {
             float x = v[u];
             if (seen[i]) x = x < 0.f ? x * rep_pen : x / rep_pen;
+            if (P) x = proc_score(x, i, C.p.eos_token, ps, kill);
             x = x / temp;
             if (x > bv || (x == bv && i < bi)) { bv = x; bi = i; }
         }
@@ -284,6 +302,28 @@ __global__ __launch_bounds__(kGreedyThreads) void k_sample_greedy(SampleCall cv,
 }
 __global__ void k_stage_rows(gvc_row_sampling* dst, SampleRows src, int B) {
     if ((int)threadIdx.x < B) dst[threadIdx.x] = src.r[threadIdx.x];
+}
+
+__global__ void k_stage_proc(gvc_logits_processors* dst, gvc_logits_processors src) {
+    if (threadIdx.x == 0) *dst = src;
+}
+
+int check_procs(const gvc_logits_processors& P, int vocab) {
+    GVC_REQUIRE(vocab <= 32 * kProcWords, GVC_ERR_UNSUPPORTED, "processors: vocab %d > %d", vocab, 32 * kProcWords);
+    GVC_REQUIRE(P.no_repeat_ngram_size >= 0 && P.no_repeat_ngram_size <= GVC_PROC_MAX_NGRAM, GVC_ERR_ARG,
+                "processors: no_repeat_ngram_size %d outside [0, %d]", P.no_repeat_ngram_size, GVC_PROC_MAX_NGRAM);
+    GVC_REQUIRE(P.min_length >= 0 && P.min_new_tokens >= 0 && P.prompt_len >= 0 && P.n_suppress >= 0 && P.n_begin_suppress >= 0,
+                GVC_ERR_ARG, "processors: negative min_length %d / min_new_tokens %d / prompt_len %d", P.min_length, P.min_new_tokens,
+                P.prompt_len);
+    GVC_REQUIRE(P.decay_factor >= 0.f && P.min_p >= 0.f && P.min_p <= 1.f, GVC_ERR_ARG,
+                "processors: decay factor %g (0 = off, else > 0), min_p %g outside [0, 1]", (double)P.decay_factor, (double)P.min_p);
+    // ids past the vocabulary would never be scored: a set bit there is a caller error
+    const int w = vocab >> 5, b = vocab & 31;
+    for (int i = w; i < kProcWords; ++i) {
+        const uint32_t m = i == w ? ~((1u << b) - 1u) : ~0u;
+        GVC_REQUIRE(!(P.suppress[i] & m) && !(P.begin_suppress[i] & m), GVC_ERR_ARG, "processors: suppressed id >= vocab %d", vocab);
+    }
+    return GVC_OK;
 }
 
 int check_sample_rows(const gvc_row_sampling* rows, int B, int vocab, bool* all_greedy) {
@@ -363,5 +403,39 @@ extern "C" int gvc_sample_rows(const float* logits, int32_t B, int32_t* ids, int
     const hipError_t e = hipFreeAsync(d_rows, s);
     if (rc) return rc;
     GVC_CHECK_HIP(e);
+    return GVC_OK;
+}
+
+extern "C" int gvc_sample_proc(const float* logits, int32_t B, int32_t* ids, int32_t ids_stride, int32_t* ids_len, int32_t* finished,
+                               const gvc_sample_params* p, const gvc_row_sampling* rows, const gvc_logits_processors* proc, int32_t step,
+                               int32_t* tok_out, gvc_stream sv) {
+    GVC_REQUIRE(logits && ids && ids_len && finished && p && proc && tok_out && B >= 1, GVC_ERR_ARG, "gvc_sample_proc: bad argument");
+    int rc = gvc::check_procs(*proc, p->vocab);
+    if (rc) return rc;
+    bool greedy = p->top_k == 1;
+    if (rows && (rc = gvc::check_sample_rows(rows, B, p->vocab, &greedy))) return rc;
+    hipStream_t s = (hipStream_t)sv;
+    // the processors (and rows) need device memory for the duration of this call only: stream-ordered, freed behind the sampler launch
+    const size_t bytes = sizeof(gvc_logits_processors) + (rows ? (size_t)B * sizeof(gvc_row_sampling) : 0);
+    char* d = nullptr;
+    GVC_CHECK_HIP(hipMallocAsync((void**)&d, bytes, s));
+    gvc_logits_processors* d_proc = reinterpret_cast<gvc_logits_processors*>(d);
+    gvc_row_sampling* d_rows = rows ? reinterpret_cast<gvc_row_sampling*>(d + sizeof(gvc_logits_processors)) : nullptr;
+    hipLaunchKernelGGL(gvc::k_stage_proc, dim3(1), dim3(64), 0, s, d_proc, *proc);
+    hipError_t e = hipGetLastError();
+    rc = e == hipSuccess ? GVC_OK : GVC_ERR_HIP;
+    if (rc == GVC_OK && rows) rc = gvc::launch_stage_rows(d_rows, rows, B, s);
+    if (rc == GVC_OK) {
+        gvc::SampleCall sc;
+        memset(&sc, 0, sizeof(sc));
+        sc.logits = logits; sc.B = B; sc.ids = ids; sc.ids_stride = ids_stride; sc.ids_len = ids_len;
+        sc.finished = finished; sc.p = *p; sc.step = step; sc.tok_out = tok_out; sc.rows = d_rows; sc.proc = d_proc;
+        if (rows) sc.p.top_k = greedy ? 1 : 0;          // (kernel choice only: every row's settings come from d_rows)
+        rc = gvc::launch_sample(sc, s);
+    }
+    const hipError_t e2 = hipFreeAsync(d, s);
+    if (e != hipSuccess) gvc::set_error("gvc_sample_proc: staging launch failed: %s", hipGetErrorString(e));
+    if (rc) return rc;
+    GVC_CHECK_HIP(e2);
     return GVC_OK;
 }

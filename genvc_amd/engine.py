@@ -42,6 +42,77 @@ def _rows_arg(rows, B):
     return arr
 
 
+# HF generate kwargs of the length / repetition processors (include/genvc_hip.h: gvc_logits_processors)
+PROC_KWARGS = ("no_repeat_ngram_size", "min_length", "min_new_tokens", "exponential_decay_length_penalty", "suppress_tokens",
+               "begin_suppress_tokens", "min_p")
+MAX_NGRAM = 8          # GVC_PROC_MAX_NGRAM
+
+
+def _nonneg_int(kw, name):
+    v = kw.get(name)
+    if v is None:
+        return 0
+    if isinstance(v, bool) or int(v) != v or int(v) < 0:
+        raise ValueError(f"{name} must be an integer >= 0, not {v!r}")
+    return int(v)
+
+
+def _token_bits(kw, name, vocab):
+    toks = kw.get(name)
+    if toks is None:
+        return [], 0
+    toks = [toks] if isinstance(toks, int) else list(toks)
+    words = [0] * 33
+    for x in toks:
+        if isinstance(x, bool) or int(x) != x or not 0 <= int(x) < vocab:
+            raise ValueError(f"{name}: token {x!r} outside [0, {vocab})")
+        words[int(x) >> 5] |= 1 << (int(x) & 31)
+    return words, len(toks)
+
+
+def logits_processors(kw, prompt_len, vocab, sampling=True, prompt_lens=None):
+    """the processor kwargs of one call (PROC_KWARGS, HF semantics) -> a gvc_logits_processors, or None when every one is at its
+    default (the kernels then run exactly as without processors).  prompt_len: the prompt length of every row (HF's
+    input_ids_seq_length, fake ids included); prompt_lens: a device int32 [B] tensor with one per row instead (kept alive by the
+    caller while the call's work runs).  min_p is a warper: it applies only when sampling.  Malformed settings raise ValueError."""
+    ngram = _nonneg_int(kw, "no_repeat_ngram_size")
+    if ngram > MAX_NGRAM:
+        raise ValueError(f"no_repeat_ngram_size {ngram} is above the supported {MAX_NGRAM} (the ban scans the whole row every step)")
+    min_length = _nonneg_int(kw, "min_length")
+    min_new = _nonneg_int(kw, "min_new_tokens")
+    decay = kw.get("exponential_decay_length_penalty")
+    start, factor = 0, 0.0
+    if decay is not None:
+        if not isinstance(decay, (tuple, list)) or len(decay) != 2:
+            raise ValueError(f"exponential_decay_length_penalty must be a pair (start, factor), not {decay!r}")
+        start, factor = decay
+        if isinstance(start, bool) or int(start) != start:
+            raise ValueError(f"exponential_decay_length_penalty start must be an integer, not {start!r}")
+        if not float(factor) > 0.0:
+            raise ValueError(f"exponential_decay_length_penalty factor must be > 0, not {factor!r}")
+        start, factor = int(start), float(factor)
+    min_p = kw.get("min_p")
+    min_p = 0.0 if min_p is None else float(min_p)
+    if not 0.0 <= min_p <= 1.0:
+        raise ValueError(f"min_p must be in [0, 1], not {min_p!r}")
+    if not sampling:
+        min_p = 0.0
+    sup, n_sup = _token_bits(kw, "suppress_tokens", vocab)
+    bsup, n_bsup = _token_bits(kw, "begin_suppress_tokens", vocab)
+    if not (ngram or min_length or min_new or factor or min_p or n_sup or n_bsup):
+        return None
+    pr = _lib.LogitsProcessors()
+    pr.no_repeat_ngram_size, pr.min_length, pr.min_new_tokens, pr.decay_start = ngram, min_length, min_new, start
+    pr.decay_factor, pr.min_p, pr.prompt_len = factor, min_p, int(prompt_len)
+    pr.n_suppress, pr.n_begin_suppress = n_sup, n_bsup
+    if prompt_lens is not None:
+        pr.prompt_lens = _i32(prompt_lens).data_ptr()
+    for i in range(33):
+        pr.suppress[i] = sup[i] if n_sup else 0
+        pr.begin_suppress[i] = bsup[i] if n_bsup else 0
+    return pr
+
+
 BEAM_LENGTH_MODES = {"4.33": 0, "generated": 1}
 
 
@@ -50,7 +121,7 @@ class BeamSearch:
     ids rows, running scores, the finished-hypothesis store, the copy lists of the last reorder.  `fake` [B, n0] are the fake ids of
     compute_embeddings (every beam of an item starts from them)."""
 
-    def __init__(self, fake, K, max_new, eos, vocab, length_penalty=1.0, repetition_penalty=1.0, length_mode="4.33"):
+    def __init__(self, fake, K, max_new, eos, vocab, length_penalty=1.0, repetition_penalty=1.0, length_mode="4.33", proc=None):
         if length_mode not in BEAM_LENGTH_MODES:
             raise ValueError(f"beam_length_mode must be one of {sorted(BEAM_LENGTH_MODES)}, not {length_mode!r}")
         dev = fake.device
@@ -80,6 +151,7 @@ class BeamSearch:
                                     self.hyp_tok, self.hyp_count, self.hyp_worst, self.copies, self.n_copies)])
         self.length_mode = length_mode
         self.length_penalty = float(length_penalty)
+        self.proc = proc          # gvc_logits_processors (logits_processors()) or None
 
     def finalize(self):
         """BeamSearchScorer.finalize: the running beams of the items not done join their hypotheses (length n0 + T in mode "4.33", T
@@ -119,7 +191,11 @@ class BeamSearch:
 def beam_select(beam, logits, slots, t):
     """one select step of `beam` (a BeamSearch) on logits [B*K, vocab] at step t; slots [B*K] int32 are permuted in place
     (include/genvc_hip.h: gvc_beam_select)"""
-    check(lib().gvc_beam_select(C.byref(beam.c), ptr(_f32(logits)), ptr(_i32(slots)), int(t), stream()), "beam_select")
+    if beam.proc is None:
+        check(lib().gvc_beam_select(C.byref(beam.c), ptr(_f32(logits)), ptr(_i32(slots)), int(t), stream()), "beam_select")
+    else:
+        check(lib().gvc_beam_select_proc(C.byref(beam.c), C.byref(beam.proc), ptr(_f32(logits)), ptr(_i32(slots)), int(t), stream()),
+              "beam_select_proc")
 
 
 class GptEngine:
@@ -238,10 +314,20 @@ class GptEngine:
                                ptr(_i32(finished)), C.byref(params), step, ptr(tok), stream()), "sample")
         return tok
 
-    def generate(self, slots, ids, ids_len, finished, params, i0, n_steps, tokens_out, latents_out, max_keys=0):
+    def sample_proc(self, logits, ids, ids_len, finished, params, proc, step, rows=None):
+        """sample() (rows None) or sample_rows() with the processors `proc` (logits_processors(); include/genvc_hip.h: gvc_sample_proc)"""
+        B = logits.shape[0]
+        arr = _rows_arg(rows, B) if rows is not None else None
+        tok = torch.empty(B, device=logits.device, dtype=torch.int32)
+        check(lib().gvc_sample_proc(ptr(_f32(logits)), B, ptr(_i32(ids)), ids.shape[1], ptr(_i32(ids_len)), ptr(_i32(finished)),
+                                    C.byref(params), arr, C.byref(proc), int(step), ptr(tok), stream()), "sample_proc")
+        return tok
+
+    def generate(self, slots, ids, ids_len, finished, params, i0, n_steps, tokens_out, latents_out, max_keys=0, proc=None):
         """tokens_out [B, >= i0+n_steps] int32 and latents_out [B, >= i0+n_steps, d] may be column slices of larger
         buffers (row strides are passed on); step i of this call lands in column i0 + i.  max_keys: cached positions of the
-        longest stream after the call (0: unknown, the width of `ids` is taken)."""
+        longest stream after the call (0: unknown, the width of `ids` is taken).  proc: the call's processors (logits_processors(),
+        include/genvc_hip.h: gvc_gpt_generate_proc) or None."""
         self._join_side()
         B = slots.shape[0]
         assert tokens_out.is_cuda and tokens_out.dtype == torch.int32 and tokens_out.stride(1) == 1
@@ -250,6 +336,12 @@ class GptEngine:
             assert latents_out.is_cuda and latents_out.dtype == torch.float32 and latents_out.stride(2) == 1
             assert latents_out.stride(1) == self.d and latents_out.stride(0) % self.d == 0
             lat_stride = latents_out.stride(0) // self.d
+        if proc is not None:
+            check(lib().gvc_gpt_generate_proc(self._h, ptr(_i32(slots)), B, ptr(_i32(ids)), ids.shape[1], ptr(_i32(ids_len)),
+                                              ptr(_i32(finished)), C.byref(params), None, C.byref(proc), i0, n_steps, int(max_keys),
+                                              ptr(tokens_out), tokens_out.stride(0), ptr(latents_out), lat_stride, stream()),
+                  "generate_proc")
+            return
         check(lib().gvc_gpt_generate(self._h, ptr(_i32(slots)), B, ptr(_i32(ids)), ids.shape[1], ptr(_i32(ids_len)),
                                      ptr(_i32(finished)), C.byref(params), i0, n_steps, int(max_keys), ptr(tokens_out),
                                      tokens_out.stride(0), ptr(latents_out), lat_stride, stream()), "generate")
@@ -265,7 +357,7 @@ class GptEngine:
                                     C.byref(common), arr, int(step), ptr(tok), stream()), "sample_rows")
         return tok
 
-    def generate_rows(self, slots, ids, ids_len, finished, rows, i0, n_steps, tokens_out, latents_out, max_keys=0):
+    def generate_rows(self, slots, ids, ids_len, finished, rows, i0, n_steps, tokens_out, latents_out, max_keys=0, proc=None):
         """generate() with per-row settings and RNG keys (include/genvc_hip.h: gvc_gpt_generate_rows): tokens and latents of step i
         land in column i0 + i as in generate(); row b draws rng_uniform(seed_b, rng_step0_b + i, rng_row_b), so its tokens do not
         depend on which rows share the call.  rows: see row_sampling() (B entries, or a prepared gvc_row_sampling array)"""
@@ -279,6 +371,12 @@ class GptEngine:
             assert latents_out.stride(1) == self.d and latents_out.stride(0) % self.d == 0
             lat_stride = latents_out.stride(0) // self.d
         common = sample_params(dict(repetition_penalty=1.0, temperature=1.0, top_p=1.0, top_k=0), self.V, self.dims["stop_audio_token"])
+        if proc is not None:
+            check(lib().gvc_gpt_generate_proc(self._h, ptr(_i32(slots)), B, ptr(_i32(ids)), ids.shape[1], ptr(_i32(ids_len)),
+                                              ptr(_i32(finished)), C.byref(common), arr, C.byref(proc), int(i0), int(n_steps),
+                                              int(max_keys), ptr(tokens_out), tokens_out.stride(0), ptr(latents_out), lat_stride,
+                                              stream()), "generate_rows_proc")
+            return
         check(lib().gvc_gpt_generate_rows(self._h, ptr(_i32(slots)), B, ptr(_i32(ids)), ids.shape[1], ptr(_i32(ids_len)),
                                           ptr(_i32(finished)), C.byref(common), arr, int(i0), int(n_steps), int(max_keys),
                                           ptr(tokens_out), tokens_out.stride(0), ptr(latents_out), lat_stride, stream()),
@@ -288,8 +386,12 @@ class GptEngine:
         """n_steps steps of `beam` (a BeamSearch) on the device, continuing at beam.steps (include/genvc_hip.h: gvc_gpt_beam_generate):
         item b was prefilled into slots[b*K]; slots [B*K] int32 is rewritten to the beams' slots"""
         self._join_side()
-        check(lib().gvc_gpt_beam_generate(self._h, ptr(_i32(slots)), C.byref(beam.c), int(beam.steps), int(n_steps), int(max_keys),
-                                          stream()), "beam_generate")
+        if beam.proc is not None:
+            check(lib().gvc_gpt_beam_generate_proc(self._h, ptr(_i32(slots)), C.byref(beam.c), C.byref(beam.proc), int(beam.steps),
+                                                   int(n_steps), int(max_keys), stream()), "beam_generate_proc")
+        else:
+            check(lib().gvc_gpt_beam_generate(self._h, ptr(_i32(slots)), C.byref(beam.c), int(beam.steps), int(n_steps), int(max_keys),
+                                              stream()), "beam_generate")
         beam.steps += int(n_steps)
 
     def warmup_beam(self, B, K, max_keys=0):

@@ -72,9 +72,12 @@ def _segment_latents(m, cond_latent, codes, gen, repass_latents):
 
 
 @torch.inference_mode()
-def synthesize_utt(genVC_mdl, src_wav, tgt_audio, seg_len=6.0, return_details=False, repass_latents=False, num_beams=1):
+def synthesize_utt(genVC_mdl, src_wav, tgt_audio, seg_len=6.0, return_details=False, repass_latents=False, num_beams=1,
+                   generate_kwargs=None):
     """non-streaming conversion, latent-level concatenation (reference :23-89).  num_beams = K > 1: every segment decodes with
-    deterministic beam search (GPT.generate(num_beams=K, do_sample=False)); its latents come from the re-pass"""
+    deterministic beam search (GPT.generate(num_beams=K, do_sample=False)); its latents come from the re-pass.
+    generate_kwargs: more GPT.generate kwargs (the logits processors: min_new_tokens, no_repeat_ngram_size, ...), merged into every
+    segment's call"""
     m = genVC_mdl
     min_len = int(0.32 * m.content_sample_rate)
     src_wav = src_wav.to(m.device)
@@ -85,7 +88,7 @@ def synthesize_utt(genVC_mdl, src_wav, tgt_audio, seg_len=6.0, return_details=Fa
         feat = m.content_extractor.extract_content_features(src_seg)
         codes = m.content_dvae.get_codebook_indices(feat.transpose(1, 2))
         kw = _sampling_kwargs(m) if num_beams == 1 else dict(_sampling_kwargs(m), do_sample=False, num_beams=int(num_beams))
-        gen = m.gpt.generate(cond_latent, codes, output_attentions=False, **kw)[0]
+        gen = m.gpt.generate(cond_latent, codes, output_attentions=False, **dict(kw, **(generate_kwargs or {})))[0]
         gen = gen[gen != m.gpt.stop_audio_token]                        # reference :68 (0-d collapse guarded)
         if gen.numel() == 0:
             continue
@@ -102,10 +105,10 @@ def synthesize_utt(genVC_mdl, src_wav, tgt_audio, seg_len=6.0, return_details=Fa
 
 
 @torch.inference_mode()
-def synthesize_utt_chunked(genVC_mdl, src_wav, tgt_audio, seg_len=6.0, repass_latents=False):
+def synthesize_utt_chunked(genVC_mdl, src_wav, tgt_audio, seg_len=6.0, repass_latents=False, generate_kwargs=None):
     """non-streaming conversion with waveform-level concatenation (reference :92-133): every segment goes through
     `genVC_mdl.inference` (trainers/hifigan_trainer.py:457-500) and the segment waveforms are joined by `handle_chunks`
-    (1024 samples dropped from each, cross-fade over the previous tail)."""
+    (1024 samples dropped from each, cross-fade over the previous tail).  generate_kwargs: as synthesize_utt"""
     m = genVC_mdl
     wav_gen_prev, wav_overlap = None, None
     pred_audios = []
@@ -116,7 +119,8 @@ def synthesize_utt_chunked(genVC_mdl, src_wav, tgt_audio, seg_len=6.0, repass_la
     c = m.config
     for src_seg in segments(src_wav, seg, min_len):
         audio_pred = m.inference(src_seg, cond_latent, top_p=c.top_p, top_k=c.top_k, temperature=c.temperature,
-                                 length_penalty=c.length_penalty, repetition_penalty=c.repetition_penalty, repass_latents=repass_latents)
+                                 length_penalty=c.length_penalty, repetition_penalty=c.repetition_penalty, repass_latents=repass_latents,
+                                 **({"generate_kwargs": generate_kwargs} if generate_kwargs else {}))
         wav_chunk, wav_gen_prev, wav_overlap = handle_chunks(audio_pred.squeeze(), wav_gen_prev, wav_overlap, 1024)
         pred_audios.append(wav_chunk)
     return torch.cat(pred_audios, dim=-1)
@@ -124,8 +128,9 @@ def synthesize_utt_chunked(genVC_mdl, src_wav, tgt_audio, seg_len=6.0, repass_la
 
 @torch.inference_mode()
 def synthesize_utt_streaming(genVC_mdl, src_wav, tgt_audio, seg_len=6.0, stream_chunk_size=8, verbose=True,
-                             return_details=False):
-    """streaming conversion (reference :135-217); the clock starts before the host->device copies (:148)"""
+                             return_details=False, generate_kwargs=None):
+    """streaming conversion (reference :135-217); the clock starts before the host->device copies (:148).  generate_kwargs: more
+    GPT.get_generator kwargs (the logits processors), merged into every segment's call"""
     m = genVC_mdl
     wav_gen_prev, wav_overlap = None, None
     total = src_wav.shape[-1]
@@ -157,7 +162,7 @@ def synthesize_utt_streaming(genVC_mdl, src_wav, tgt_audio, seg_len=6.0, stream_
         fake = m.gpt.compute_embeddings(cond_latent, codes)
         gen = m.gpt.get_generator(fake_inputs=fake, num_return_sequences=1, output_attentions=False,
                                   output_hidden_states=True, stream_group=max(stream_chunk_size, 1),
-                                  cached_cond_rows=cached, **_sampling_kwargs(m))
+                                  cached_cond_rows=cached, **dict(_sampling_kwargs(m), **(generate_kwargs or {})))
         cached = cond_latent.shape[1]
         last_tokens, all_latents = [], []
         is_end = False

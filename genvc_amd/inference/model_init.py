@@ -132,17 +132,18 @@ class GenVCModel(nn.Module):
 
     @torch.no_grad()
     def inference(self, src_audio, cond_latent, do_sample=True, top_p=0.85, top_k=15, temperature=0.75, num_beams=1,
-                  length_penalty=1.0, repetition_penalty=10.0, output_attentions=False, repass_latents=False):
+                  length_penalty=1.0, repetition_penalty=10.0, output_attentions=False, repass_latents=False, generate_kwargs=None):
         """reference trainers/hifigan_trainer.py:457-500: one source segment [1,T] + conditioning latents -> waveform
         [1,1,1024 n]: ContentVec -> content codes -> generate -> strip stop tokens -> latent re-pass -> x4 linear
         interpolation -> HiFi-GAN.  (The reference's 0-d collapse at exactly one non-stop token, SURVEY appendix B.9, is
         guarded: boolean indexing keeps the dimension.)  The latents are the decode loop's own unless `repass_latents=True`
-        (inference_utils._segment_latents)."""
+        (inference_utils._segment_latents).  generate_kwargs (extension): more GPT.generate kwargs (the logits processors:
+        min_new_tokens, no_repeat_ngram_size, ...), merged over the ones above."""
         feat = self.content_extractor.extract_content_features(src_audio)
         codes = self.content_dvae.get_codebook_indices(feat.transpose(1, 2))
-        gen = self.gpt.generate(cond_latent, codes, do_sample=do_sample, top_p=top_p, top_k=top_k, temperature=temperature,
-                                num_beams=num_beams, length_penalty=length_penalty, repetition_penalty=repetition_penalty,
-                                output_attentions=output_attentions)[0]
+        kw = dict(do_sample=do_sample, top_p=top_p, top_k=top_k, temperature=temperature, num_beams=num_beams,
+                  length_penalty=length_penalty, repetition_penalty=repetition_penalty, output_attentions=output_attentions)
+        gen = self.gpt.generate(cond_latent, codes, **dict(kw, **(generate_kwargs or {})))[0]
         gen = gen[gen != self.gpt.stop_audio_token]
         if gen.numel() == 0:
             return torch.zeros(1, 1, 0, device=self.device)

@@ -11,7 +11,7 @@ import torch
 from torch import nn
 
 from .._lib import GenvcHipError
-from ..engine import BEAM_LENGTH_MODES, BeamSearch, GptEngine, sample_params
+from ..engine import BEAM_LENGTH_MODES, PROC_KWARGS, BeamSearch, GptEngine, logits_processors, sample_params
 from .perceiver_encoder import PerceiverResampler
 
 
@@ -48,6 +48,16 @@ def _beam_kwargs(kw):
     if mode not in BEAM_LENGTH_MODES:
         raise ValueError(f"beam_length_mode must be one of {sorted(BEAM_LENGTH_MODES)}, not {mode!r}")
     return K, float(kw.get("length_penalty", 1.0)), float(kw.get("repetition_penalty", 1.0)), mode
+
+
+def _any_proc(kw):
+    """a processor kwarg is given (engine.logits_processors may still find every one at its default)"""
+    return any(kw.get(k) is not None for k in PROC_KWARGS)
+
+
+def _proc_arg(proc):
+    """the engine call's processor argument: none at all without processors (the call is exactly the one without them)"""
+    return {} if proc is None else {"proc": proc}
 
 
 class _Holder(nn.Module):
@@ -223,6 +233,8 @@ class GPT(nn.Module):
         samp = dict(repetition_penalty=kw.get("repetition_penalty", 1.0), temperature=kw.get("temperature", 1.0),
                     top_p=kw.get("top_p", 1.0), top_k=kw.get("top_k", 0) if kw.get("do_sample", True) else 1)
         st["params"] = sample_params(samp, self.num_audio_tokens, self.stop_audio_token, kw.get("seed", 0))
+        # length / repetition processors (HF kwargs, engine.PROC_KWARGS): the prompt is the fake ids
+        st["proc"] = logits_processors(kw, n0, self.num_audio_tokens, sampling=kw.get("do_sample", True))
         # `cached_cond_rows` (extension): the leading rows of the prefix -- the conditioning latents, identical for every
         # segment of an utterance -- are still in the KV cache from the previous segment's prefill of these slots
         self.engine.prefill(slots, self._prefix, want_outputs=False, n_cached=int(kw.get("cached_cond_rows", 0)))
@@ -235,7 +247,7 @@ class GPT(nn.Module):
             # the cache holds n0 positions after the prefill and one more per step: the library picks its decode kernels for the
             # context length this call reaches (not for the 602-token cap the ids rows are sized for)
             self.engine.generate(st["slots"], st["ids"], st["ids_len"], st["finished"], st["params"], st["done"], n,
-                                 st["toks"], st["lats"], max_keys=st["n0"] + st["done"] + n)
+                                 st["toks"], st["lats"], max_keys=st["n0"] + st["done"] + n, **_proc_arg(st["proc"]))
             st["done"] += n
         end = bool(st["finished"].all().item()) or st["done"] >= st["max_new"]
         self.engine.health()          # (the .item() above synchronised: a hand-off timeout of these steps surfaces here, not a call later)
@@ -288,11 +300,12 @@ class GPT(nn.Module):
         n0 = int(fake.shape[1])
         max_new = int(kw.get("max_new_tokens") or self.max_gen_mel_tokens)                   # gpt.py:606
         dev = fake.device
+        proc = logits_processors(kw, n0, self.num_audio_tokens, sampling=False)
 
         def run():
             slots = torch.arange(B * K, device=dev, dtype=torch.int32)
             self.engine.prefill(slots[::K].contiguous(), self._prefix, want_outputs=False)      # each item once; the first step fans out
-            beam = BeamSearch(fake, K, max_new, self.stop_audio_token, self.num_audio_tokens, lp, rep, mode)
+            beam = BeamSearch(fake, K, max_new, self.stop_audio_token, self.num_audio_tokens, lp, rep, mode, **_proc_arg(proc))
             while beam.steps < max_new:
                 n = min(group, max_new - beam.steps)
                 self.engine.beam_generate(slots, beam, n, max_keys=n0 + beam.steps + n)
@@ -399,6 +412,11 @@ class GPT(nn.Module):
                     top_p=kw.get("top_p", 1.0), top_k=1)
         params = sample_params(samp, self.num_audio_tokens, self.stop_audio_token, kw.get("seed", 0))
         rs = self._row_settings(kw)
+        # processors: one set for the call, each row counting from its own prompt (its group's fake ids)
+        proc = None
+        if _any_proc(kw):
+            plens = torch.cat([torch.full((hi - lo,), n0, dtype=torch.int32) for (lo, hi), n0 in zip(spans, n0s)]).to(dev)
+            proc = logits_processors(kw, 0, self.num_audio_tokens, sampling=seeds is not None, prompt_lens=plens)
         done = 0
         while done < max_new:
             live_groups = [g for g in range(len(groups)) if gb[g] > done]
@@ -407,12 +425,12 @@ class GPT(nn.Module):
             mk = max(n0s[g] for g in live_groups) + done + n
             if seeds is None:
                 self.engine.generate(slots[:live], ids[:live], ids_len[:live], finished[:live], params, done, n, toks[:live], lats[:live],
-                                     max_keys=mk)
+                                     max_keys=mk, **_proc_arg(proc))
             else:
                 # sampling: row r of class g is keyed (class seed, r, done) -- what generate(seed=class seed) draws for it
                 rows = [dict(rs, seed=seeds[g], rng_row=r, rng_step0=done) for g in live_groups for r in range(spans[g][1] - spans[g][0])]
                 self.engine.generate_rows(slots[:live], ids[:live], ids_len[:live], finished[:live], rows, done, n, toks[:live], lats[:live],
-                                          max_keys=mk)
+                                          max_keys=mk, **_proc_arg(proc))
             done += n
             stop = bool(finished[:live].all().item())
             self.engine.health()
@@ -514,12 +532,17 @@ class GPT(nn.Module):
             ids_len = len_all[idx].contiguous()
             fin = fin_all[idx].contiguous()
             toks = torch.full((len(row_slots), n), stop, device=dev, dtype=torch.int32)
+            # processors: one set for the call, each row counting from its own job's prompt
+            proc = None
+            if _any_proc(kw):
+                plens = torch.tensor([j["n0"] for j in live for _ in j["alive"]], dtype=torch.int32).to(dev)
+                proc = logits_processors(kw, 0, self.num_audio_tokens, sampling=seeds is not None, prompt_lens=plens)
             if seeds is None:
-                eng.generate(rows, ids, ids_len, fin, params, 0, n, toks, None, max_keys=W - 8)
+                eng.generate(rows, ids, ids_len, fin, params, 0, n, toks, None, max_keys=W - 8, **_proc_arg(proc))
             else:
                 # row r of job j keyed (job seed, r, tokens the job has drawn): the key generate(seed=job_seeds[j]) gives that row
                 keys = [dict(rs, seed=seeds[j["job"]], rng_row=r, rng_step0=j["done"]) for j in live for r in j["alive"]]
-                eng.generate_rows(rows, ids, ids_len, fin, keys, 0, n, toks, None, max_keys=W - 8)
+                eng.generate_rows(rows, ids, ids_len, fin, keys, 0, n, toks, None, max_keys=W - 8, **_proc_arg(proc))
             ids_all[idx, :W] = ids
             len_all[idx] = ids_len
             fin_all[idx] = fin

@@ -283,6 +283,57 @@ int gvc_beam_select(const gvc_beam_state* st, const float* logits, int32_t* slot
 int gvc_gpt_beam_generate(gvc_gpt* ctx, int32_t* slots, const gvc_beam_state* st, int32_t i0, int32_t n_steps, int32_t max_keys,
                           gvc_stream s);
 
+/* ------------------------------------------------------------------------------------------
+ * Length and repetition logits processors (HF generate kwargs; the reference hands them to HF generate, layers/gpt.py:594-621).
+ * One set per call, for every row.  Applied after the repetition penalty, in the order HF's _get_logits_processor builds them:
+ *   no_repeat_ngram_size -> min_length -> min_new_tokens -> exponential_decay_length_penalty -> suppress_tokens ->
+ *   begin_suppress_tokens -> [sampling only: temperature -> top_k -> top_p] -> min_p (sampling only).
+ * Lengths are those of the row's input_ids (fake prompt included): len = the row's length before the step, plen = its prompt
+ * length.  no_repeat_ngram_size n: every window of n ids of the whole row whose first n-1 ids equal the row's last n-1 ids bans its
+ * last id (nothing while len < n).  min_length: eos -inf while len < min_length.  min_new_tokens: eos -inf while len - plen <
+ * min_new_tokens.  Decay (start, factor): once len > plen + start, s_eos += |s_eos| * (factor ** (len - plen - start) - 1) (a
+ * banned eos stays -inf; HF would make it NaN).  suppress: those ids -inf at every step; begin_suppress: at the step with
+ * len == plen.  min_p: after top-p, ids with exp(s - max) < min_p are dropped (the top one always stays).  With beams the
+ * processors act on each beam's penalised log-probs before the running score is added, and plen = the state's n0.
+ * An all-zero struct is "every processor off": every kernel then computes exactly what it computes without one.
+ * ------------------------------------------------------------------------------------------ */
+#define GVC_PROC_MAX_NGRAM 8            /* no_repeat_ngram_size cap: the ban scans the row once per step, n-1 compares per window */
+#define GVC_PROC_VOCAB_WORDS 33         /* bitmap words: vocab <= 1056 */
+typedef struct gvc_logits_processors {
+    int32_t no_repeat_ngram_size;       /* 0 off; 1..GVC_PROC_MAX_NGRAM */
+    int32_t min_length;                 /* 0 off */
+    int32_t min_new_tokens;             /* 0 off */
+    int32_t decay_start;                /* exponential_decay_length_penalty start (new tokens) */
+    float decay_factor;                 /* exponential_decay_length_penalty factor: 0 off, else > 0 */
+    float min_p;                        /* 0 off, else in (0, 1]; ignored by the greedy (top_k == 1) sampler and by beams */
+    int32_t prompt_len;                 /* plen of every row when prompt_lens is null */
+    int32_t n_suppress;                 /* ids set in suppress (0: skip the bitmap) */
+    int32_t n_begin_suppress;           /* ids set in begin_suppress */
+    int32_t reserved;                   /* 0 */
+    const int32_t* prompt_lens;         /* nullable DEVICE [B]: plen per row (rows / rolling decodes); must outlive the call's work */
+    uint32_t suppress[GVC_PROC_VOCAB_WORDS];        /* bit x of word x / 32: id x suppressed */
+    uint32_t begin_suppress[GVC_PROC_VOCAB_WORDS];
+} gvc_logits_processors;
+
+/* gvc_sample / gvc_sample_rows with processors: rows (nullable HOST array of B entries) as gvc_sample_rows, null = p's settings for
+ * every row; proc (HOST) is staged on the stream for this call.  top_k == 1 rows go to the argmax kernel as in gvc_sample. */
+int gvc_sample_proc(const float* logits, int32_t B, int32_t* ids, int32_t ids_stride, int32_t* ids_len, int32_t* finished,
+                    const gvc_sample_params* p, const gvc_row_sampling* rows, const gvc_logits_processors* proc, int32_t step,
+                    int32_t* tok_out, gvc_stream s);
+/* gvc_gpt_generate (rows null) or gvc_gpt_generate_rows (rows set) with processors.  proc (HOST, nullable) travels by value in the
+ * call's first launch into the device-resident call state, as rows do: the same captured step graphs, no allocation and no
+ * synchronisation per call.  proc null: exactly gvc_gpt_generate / gvc_gpt_generate_rows. */
+int gvc_gpt_generate_proc(gvc_gpt* ctx, const int32_t* slots, int32_t B, int32_t* ids, int32_t ids_stride, int32_t* ids_len,
+                          int32_t* finished, const gvc_sample_params* p, const gvc_row_sampling* rows,
+                          const gvc_logits_processors* proc, int32_t i0, int32_t n_steps, int32_t max_keys, int32_t* tokens_out,
+                          int32_t tok_stride, float* latents_out, int32_t lat_stride, gvc_stream s);
+/* gvc_beam_select / gvc_gpt_beam_generate with processors (proc HOST, nullable: null = the calls without it).  min_p and
+ * prompt_len / prompt_lens are ignored (beams are deterministic; the prompt is st->n0). */
+int gvc_beam_select_proc(const gvc_beam_state* st, const gvc_logits_processors* proc, const float* logits, int32_t* slots, int32_t t,
+                         gvc_stream s);
+int gvc_gpt_beam_generate_proc(gvc_gpt* ctx, int32_t* slots, const gvc_beam_state* st, const gvc_logits_processors* proc, int32_t i0,
+                               int32_t n_steps, int32_t max_keys, gvc_stream s);
+
 /* Which decode step the last gvc_gpt_generate call replayed (diagnostic): 0 none yet, 1 launch-per-phase with split-key attention,
  * 2 launch-per-phase with the fused short-context attention launch, 3 the one-launch step (one stream), 4 the MFMA rows path
  * (launch per phase: 17+ streams, or shapes the one-launch rows step does not serve), 5 the one-launch rows step (2..16 streams,

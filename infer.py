@@ -31,9 +31,27 @@ if __name__ == "__main__":
                         help="GPT weight / KV-cache storage on the GPU (fp32 = the reference's numerics)")
     parser.add_argument("--num_beams", type=int, default=1,
                         help="non-streaming only: > 1 decodes with deterministic beam search (do_sample=False) of this width")
+    parser.add_argument("--min_new_tokens", type=int, default=None, help="no stop token before this many tokens per segment")
+    parser.add_argument("--no_repeat_ngram_size", type=int, default=None,
+                        help="no n-gram of codec tokens (fake prompt included) occurs twice in a segment (1..8)")
+    parser.add_argument("--eos_decay", type=float, nargs=2, default=None, metavar=("START", "FACTOR"),
+                        help="exponential_decay_length_penalty: from START new tokens on, the stop score grows by FACTOR per token")
+    parser.add_argument("--min_p", type=float, default=None, help="min-p sampling cut-off in [0, 1]")
     args = parser.parse_args()
     if args.num_beams < 1 or (args.streaming and args.num_beams != 1):
         raise SystemExit("--num_beams must be >= 1, and 1 with --streaming")
+    gen_kw = {k: v for k, v in (("min_new_tokens", args.min_new_tokens), ("no_repeat_ngram_size", args.no_repeat_ngram_size),
+                                ("min_p", args.min_p)) if v is not None}
+    if args.eos_decay is not None:
+        start, factor = args.eos_decay
+        if start != int(start):
+            raise SystemExit(f"--eos_decay START must be an integer, not {start}")
+        gen_kw["exponential_decay_length_penalty"] = (int(start), factor)
+    try:
+        from genvc_amd.engine import logits_processors
+        logits_processors(gen_kw, 0, 1026)
+    except ValueError as e:
+        raise SystemExit(f"bad processor flag: {e}")
 
     if args.synthetic:
         from genvc_amd import config as gcfg
@@ -48,11 +66,12 @@ if __name__ == "__main__":
 
     if args.streaming:
         out = synthesize_utt_streaming(model, src_wav, ref_audio, seg_len=args.seg_len,
-                                       stream_chunk_size=args.stream_chunk_size, return_details=True)
+                                       stream_chunk_size=args.stream_chunk_size, return_details=True, generate_kwargs=gen_kw or None)
         toks = torch.cat(out["tokens"], 1)
         lat = torch.cat(out["latents"], 1)
     else:
-        out = synthesize_utt(model, src_wav, ref_audio, seg_len=args.seg_len, return_details=True, num_beams=args.num_beams)
+        out = synthesize_utt(model, src_wav, ref_audio, seg_len=args.seg_len, return_details=True, num_beams=args.num_beams,
+                             generate_kwargs=gen_kw or None)
         toks = torch.cat(out["codes"]).unsqueeze(0)
         lat = out["latents"]
     print(f"generated {toks.shape[-1]} codec tokens, latents {tuple(lat.shape)}")
