@@ -100,6 +100,11 @@ _SIGNATURES = {
     "gvc_beam_select_proc": (C.c_int, [C.POINTER(BeamState), C.POINTER(LogitsProcessors), _P, _P, C.c_int32, _P]),
     "gvc_gpt_beam_generate_proc": (C.c_int, [_P, _P, C.POINTER(BeamState), C.POINTER(LogitsProcessors), C.c_int32, C.c_int32,
                                              C.c_int32, _P]),
+    "gvc_sample_proc_sets": (C.c_int, [_P, C.c_int32, _P, C.c_int32, _P, _P, C.POINTER(SampleParams), C.POINTER(RowSampling),
+                                       C.POINTER(LogitsProcessors), C.c_int32, c_i32p, C.c_int32, _P, _P]),
+    "gvc_gpt_generate_proc_sets": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, _P, _P, C.POINTER(SampleParams), C.POINTER(RowSampling),
+                                             C.POINTER(LogitsProcessors), C.c_int32, c_i32p, C.c_int32, C.c_int32, C.c_int32, _P,
+                                             C.c_int32, _P, C.c_int32, _P]),
     "gvc_gpt_decode_variant": (C.c_int, [_P]),
     "gvc_gpt_rows_step_launches": (C.c_longlong, [_P]),
     "gvc_gpt_health": (C.c_int, [_P]),

@@ -180,6 +180,8 @@ struct GenCall {
     int32_t slots[64];
     gvc_row_sampling rows[kMaxSampleRows];   // per-row settings and keys of a gvc_gpt_generate_rows call (sc.rows points here)
     gvc_logits_processors proc;              // processors of a gvc_gpt_generate_proc call (sc.proc points here)
+    gvc_logits_processors sets[kMaxSampleRows];   // processor sets of a gvc_gpt_generate_proc_sets call (sc.proc_sets points here)
+    int32_t set_of_row[kMaxSampleRows];      // ... and each row's index into them, -1: none (sc.set_of_row points here)
 };
 
 // Start / end of a gvc_gpt_generate call in ONE launch each (they used to be a memset, k_set_gen_call and two k_stage_rows before the
@@ -221,6 +223,18 @@ __global__ void k_gen_begin_proc(GenCall* dst, SampleCall sc, const int32_t* slo
     if ((int)blockIdx.x == B) {
         if (ROWS && (int)threadIdx.x < B) dst->rows[threadIdx.x] = rows.r[threadIdx.x];
         if (threadIdx.x == 0) dst->proc = proc;
+    }
+    gen_begin(dst, sc, slots, B, step_ctr, logits, slot_logits, vocab, latent, slot_latent, d);
+}
+
+// gvc_gpt_generate_proc_sets: the same, and workgroup B stores each row's set index (and row entries when ROWS), kernel arguments both.
+// The sets themselves went ahead on the stream in launches of their own (launch_stage_proc_sets): 64 of them would not fit one argument
+template <bool ROWS>
+__global__ void k_gen_begin_sets(GenCall* dst, SampleCall sc, const int32_t* slots, int B, int32_t* step_ctr, float* logits,
+                                 float* slot_logits, int vocab, float* latent, float* slot_latent, int d, SampleRows rows, SetIndex sor) {
+    if ((int)blockIdx.x == B && (int)threadIdx.x < B) {
+        if (ROWS) dst->rows[threadIdx.x] = rows.r[threadIdx.x];
+        dst->set_of_row[threadIdx.x] = sor.k[threadIdx.x];
     }
     gen_begin(dst, sc, slots, B, step_ctr, logits, slot_logits, vocab, latent, slot_latent, d);
 }
@@ -1627,9 +1641,11 @@ extern "C" int gvc_gpt_rearm(gvc_gpt* c) {
     return GVC_OK;
 }
 
-// rows: null (gvc_gpt_generate: p's settings for every row) or B host entries (gvc_gpt_generate_rows)
+// rows: null (gvc_gpt_generate: p's settings for every row) or B host entries (gvc_gpt_generate_rows).  proc: null or the call's
+// processors (gvc_gpt_generate_proc); set_of_row: null or B host indices into the n_sets host sets (gvc_gpt_generate_proc_sets, proc null)
 static int generate_impl(gvc_gpt* c, const int32_t* slots, int32_t B, int32_t* ids, int32_t ids_stride, int32_t* ids_len, int32_t* finished,
-                         const gvc_sample_params* p, const gvc_row_sampling* rows, const gvc_logits_processors* proc, int32_t i0,
+                         const gvc_sample_params* p, const gvc_row_sampling* rows, const gvc_logits_processors* proc,
+                         const gvc_logits_processors* sets, int32_t n_sets, const int32_t* set_of_row, int32_t i0,
                          int32_t n_steps, int32_t max_keys, int32_t* tokens_out, int32_t tok_stride, float* latents_out, int32_t lat_stride,
                          gvc_stream sv) {
     int rc = check_ready(c);
@@ -1638,6 +1654,7 @@ static int generate_impl(gvc_gpt* c, const int32_t* slots, int32_t B, int32_t* i
     bool rows_greedy = false;
     if (rows && (rc = check_sample_rows(rows, B, c->dm.vocab, &rows_greedy))) return rc;
     if (proc && (rc = check_procs(*proc, c->dm.vocab))) return rc;
+    if (set_of_row && (rc = check_proc_sets(sets, n_sets, set_of_row, B, c->dm.vocab))) return rc;
     // cached positions of the longest stream once this call has run: the caller's bound, else the whole ids row
     const int key_bound = max_keys > 0 ? max_keys : ids_stride;
     GVC_REQUIRE(max_keys == 0 || max_keys < c->dm.max_seq, GVC_ERR_STATE,
@@ -1650,7 +1667,27 @@ static int generate_impl(gvc_gpt* c, const int32_t* slots, int32_t B, int32_t* i
     sc.finished = finished; sc.p = *p; sc.step = 0; sc.step_ptr = c->step_ctr; sc.tok_out = c->tok_buf;
     sc.tokens_out = tokens_out; sc.tok_stride = tok_stride; sc.i0 = i0; sc.latent_src = c->latent;
     sc.latents_out = latents_out; sc.lat_stride = lat_stride; sc.d = c->dm.d_model;
-    if (proc) {
+    if (set_of_row) {
+        // each set some row uses travels by value into the device-resident call state, ahead of the begin launch, which carries the
+        // rows' indices (and row entries): nothing to allocate, no staging buffer, and the caller's arrays are free on return
+        if ((rc = launch_stage_proc_sets(c->gen_call->sets, sets, n_sets, set_of_row, B, s))) return rc;
+        SampleRows sr;
+        memset(&sr, 0, sizeof(sr));
+        SetIndex si;
+        memset(&si, 0, sizeof(si));
+        memcpy(si.k, set_of_row, (size_t)B * sizeof(int32_t));
+        sc.proc_sets = c->gen_call->sets;
+        sc.set_of_row = c->gen_call->set_of_row;
+        if (rows) {
+            memcpy(sr.r, rows, (size_t)B * sizeof(gvc_row_sampling));
+            sc.rows = c->gen_call->rows;
+            hipLaunchKernelGGL(k_gen_begin_sets<true>, dim3(B + 1), dim3(256), 0, s, c->gen_call, sc, slots, B, c->step_ctr, c->logits,
+                               c->slot_logits, c->dm.vocab, c->latent, c->slot_latent, c->dm.d_model, sr, si);
+        } else {
+            hipLaunchKernelGGL(k_gen_begin_sets<false>, dim3(B + 1), dim3(256), 0, s, c->gen_call, sc, slots, B, c->step_ctr, c->logits,
+                               c->slot_logits, c->dm.vocab, c->latent, c->slot_latent, c->dm.d_model, sr, si);
+        }
+    } else if (proc) {
         // (the processors travel as a kernel argument, as the rows do: nothing to allocate, and the caller's struct is free on return)
         SampleRows sr;
         memset(&sr, 0, sizeof(sr));
@@ -1703,8 +1740,8 @@ extern "C" int gvc_gpt_generate(gvc_gpt* c, const int32_t* slots, int32_t B, int
                                 int32_t* ids_len, int32_t* finished, const gvc_sample_params* p, int32_t i0,
                                 int32_t n_steps, int32_t max_keys, int32_t* tokens_out, int32_t tok_stride, float* latents_out,
                                 int32_t lat_stride, gvc_stream sv) {
-    return generate_impl(c, slots, B, ids, ids_stride, ids_len, finished, p, nullptr, nullptr, i0, n_steps, max_keys, tokens_out,
-                         tok_stride, latents_out, lat_stride, sv);
+    return generate_impl(c, slots, B, ids, ids_stride, ids_len, finished, p, nullptr, nullptr, nullptr, 0, nullptr, i0, n_steps, max_keys,
+                         tokens_out, tok_stride, latents_out, lat_stride, sv);
 }
 
 extern "C" int gvc_gpt_generate_rows(gvc_gpt* c, const int32_t* slots, int32_t B, int32_t* ids, int32_t ids_stride, int32_t* ids_len,
@@ -1712,16 +1749,26 @@ extern "C" int gvc_gpt_generate_rows(gvc_gpt* c, const int32_t* slots, int32_t B
                                      int32_t n_steps, int32_t max_keys, int32_t* tokens_out, int32_t tok_stride, float* latents_out,
                                      int32_t lat_stride, gvc_stream sv) {
     GVC_REQUIRE(rows, GVC_ERR_ARG, "generate_rows: null rows");
-    return generate_impl(c, slots, B, ids, ids_stride, ids_len, finished, common, rows, nullptr, i0, n_steps, max_keys, tokens_out,
-                         tok_stride, latents_out, lat_stride, sv);
+    return generate_impl(c, slots, B, ids, ids_stride, ids_len, finished, common, rows, nullptr, nullptr, 0, nullptr, i0, n_steps, max_keys,
+                         tokens_out, tok_stride, latents_out, lat_stride, sv);
 }
 
 extern "C" int gvc_gpt_generate_proc(gvc_gpt* c, const int32_t* slots, int32_t B, int32_t* ids, int32_t ids_stride, int32_t* ids_len,
                                      int32_t* finished, const gvc_sample_params* p, const gvc_row_sampling* rows,
                                      const gvc_logits_processors* proc, int32_t i0, int32_t n_steps, int32_t max_keys, int32_t* tokens_out,
                                      int32_t tok_stride, float* latents_out, int32_t lat_stride, gvc_stream sv) {
-    return generate_impl(c, slots, B, ids, ids_stride, ids_len, finished, p, rows, proc, i0, n_steps, max_keys, tokens_out, tok_stride,
-                         latents_out, lat_stride, sv);
+    return generate_impl(c, slots, B, ids, ids_stride, ids_len, finished, p, rows, proc, nullptr, 0, nullptr, i0, n_steps, max_keys,
+                         tokens_out, tok_stride, latents_out, lat_stride, sv);
+}
+
+extern "C" int gvc_gpt_generate_proc_sets(gvc_gpt* c, const int32_t* slots, int32_t B, int32_t* ids, int32_t ids_stride, int32_t* ids_len,
+                                          int32_t* finished, const gvc_sample_params* p, const gvc_row_sampling* rows,
+                                          const gvc_logits_processors* sets, int32_t n_sets, const int32_t* set_of_row, int32_t i0,
+                                          int32_t n_steps, int32_t max_keys, int32_t* tokens_out, int32_t tok_stride, float* latents_out,
+                                          int32_t lat_stride, gvc_stream sv) {
+    GVC_REQUIRE(sets && set_of_row, GVC_ERR_ARG, "generate_proc_sets: null sets or set_of_row");
+    return generate_impl(c, slots, B, ids, ids_stride, ids_len, finished, p, rows, nullptr, sets, n_sets, set_of_row, i0, n_steps, max_keys,
+                         tokens_out, tok_stride, latents_out, lat_stride, sv);
 }
 
 

@@ -33,7 +33,18 @@ struct SampleCall {
     // nullable: the call's length / repetition processors (gvc_logits_processors, device memory).  Null: none, and the kernels
     // compute exactly what they compute without this field
     const gvc_logits_processors* proc;
+    // nullable: per-row processor sets (gvc_*_proc_sets calls, device memory).  Set: row b uses proc_sets[set_of_row[b]], or no
+    // processors when the index is -1, and proc is not read.  Null: proc serves every row as above
+    const gvc_logits_processors* proc_sets;
+    const int32_t* set_of_row;
 };
+
+// the processors of row b (uniform over the row's workgroup)
+__device__ __forceinline__ const gvc_logits_processors* row_procs(const SampleCall& C, int b) {
+    if (!C.set_of_row) return C.proc;
+    const int k = C.set_of_row[b];
+    return k >= 0 ? C.proc_sets + k : nullptr;
+}
 
 int launch_sample(const SampleCall& sc, hipStream_t s);
 // the call parameters live in device memory (graph replay)
@@ -53,5 +64,19 @@ struct SampleRows {
 int check_sample_rows(const gvc_row_sampling* rows, int B, int vocab, bool* all_greedy);
 // rows[0..B) -> dst[0..B) on stream s (one small launch; the host array is not read after the launch is enqueued)
 int launch_stage_rows(gvc_row_sampling* dst, const gvc_row_sampling* rows, int B, hipStream_t s);
+
+// per-row processor sets: the set index of every row, passed BY VALUE like SampleRows (256 bytes)
+struct SetIndex {
+    int32_t k[kMaxSampleRows];
+};
+// host-side checks of a sets call: 1 <= B <= 64, 1 <= n_sets <= B, every index in [-1, n_sets), every set passes check_procs
+int check_proc_sets(const gvc_logits_processors* sets, int n_sets, const int32_t* set_of_row, int B, int vocab);
+// sets[k] -> dst[k] on stream s for every k some row refers to (a set no row uses is not staged), kProcSetChunk sets per launch
+// (1.3 KB of kernel argument, below the 2 KB row entries of the begin launches); the host arrays are free when this returns
+constexpr int kProcSetChunk = 4;
+int launch_stage_proc_sets(gvc_logits_processors* dst, const gvc_logits_processors* sets, int n_sets, const int32_t* set_of_row, int B,
+                           hipStream_t s);
+// set_of_row[0..B) -> dst[0..B) on stream s (one small launch)
+int launch_stage_set_index(int32_t* dst, const int32_t* set_of_row, int B, hipStream_t s);
 
 }  // namespace gvc

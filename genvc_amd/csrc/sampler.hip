@@ -67,7 +67,7 @@ __global__ __launch_bounds__(kSampThreads) void k_sample(SampleCall cv, const Sa
     const float temp = R ? R->temperature : C.p.temperature;
     const float top_p = R ? R->top_p : C.p.top_p;
     const int top_k = R ? R->top_k : C.p.top_k;
-    const gvc_logits_processors* P = C.proc;
+    const gvc_logits_processors* P = row_procs(C, b);
 
     for (int i = tid; i < kSortN; i += kSampThreads) seen[i] = 0;
     ProcStep ps{false, 0.f};
@@ -254,7 +254,7 @@ __global__ __launch_bounds__(kGreedyThreads) void k_sample_greedy(SampleCall cv,
 #pragma unroll
     for (int u = 0; u < PER; ++u) { const int i = tid + u * kGreedyThreads; v[u] = i < V ? lg[i] : -INFINITY; }
     for (int i = tid; i < kSortN / 4; i += kGreedyThreads) seen_w[i] = 0u;
-    const gvc_logits_processors* P = C.proc;
+    const gvc_logits_processors* P = row_procs(C, b);
     ProcStep ps{false, 0.f};
     if (P) ps = proc_row_begin(*P, len, P->prompt_lens ? P->prompt_lens[b] : P->prompt_len, C.p.eos_token, kill, tid);
     __syncthreads();
@@ -308,6 +308,20 @@ __global__ void k_stage_proc(gvc_logits_processors* dst, gvc_logits_processors s
     if (threadIdx.x == 0) *dst = src;
 }
 
+// up to kProcSetChunk sets by value: set j goes to dst[at[j]]
+struct ProcSetChunk {
+    gvc_logits_processors s[kProcSetChunk];
+    int32_t at[kProcSetChunk];
+    int32_t n;
+};
+__global__ void k_stage_proc_sets(gvc_logits_processors* dst, ProcSetChunk c) {
+    if ((int)threadIdx.x < c.n) dst[c.at[threadIdx.x]] = c.s[threadIdx.x];
+}
+
+__global__ void k_stage_set_index(int32_t* dst, SetIndex src, int B) {
+    if ((int)threadIdx.x < B) dst[threadIdx.x] = src.k[threadIdx.x];
+}
+
 int check_procs(const gvc_logits_processors& P, int vocab) {
     GVC_REQUIRE(vocab <= 32 * kProcWords, GVC_ERR_UNSUPPORTED, "processors: vocab %d > %d", vocab, 32 * kProcWords);
     GVC_REQUIRE(P.no_repeat_ngram_size >= 0 && P.no_repeat_ngram_size <= GVC_PROC_MAX_NGRAM, GVC_ERR_ARG,
@@ -345,6 +359,51 @@ int launch_stage_rows(gvc_row_sampling* dst, const gvc_row_sampling* rows, int B
     memset(&sr, 0, sizeof(sr));
     memcpy(sr.r, rows, (size_t)B * sizeof(gvc_row_sampling));
     hipLaunchKernelGGL(k_stage_rows, dim3(1), dim3(kMaxSampleRows), 0, s, dst, sr, B);
+    GVC_LAUNCH_CHECK();
+    return GVC_OK;
+}
+
+int check_proc_sets(const gvc_logits_processors* sets, int n_sets, const int32_t* set_of_row, int B, int vocab) {
+    GVC_REQUIRE(sets && set_of_row && B >= 1 && B <= kMaxSampleRows, GVC_ERR_ARG, "processor sets: need host sets and 1..%d rows, got %d",
+                kMaxSampleRows, B);
+    GVC_REQUIRE(n_sets >= 1 && n_sets <= B, GVC_ERR_ARG, "processor sets: %d sets for %d rows (1..B)", n_sets, B);
+    for (int b = 0; b < B; ++b)
+        GVC_REQUIRE(set_of_row[b] >= -1 && set_of_row[b] < n_sets, GVC_ERR_ARG, "processor sets: row %d has set %d outside [-1, %d)", b,
+                    set_of_row[b], n_sets);
+    for (int k = 0; k < n_sets; ++k) {
+        const int rc = check_procs(sets[k], vocab);
+        if (rc) return rc;
+    }
+    return GVC_OK;
+}
+
+int launch_stage_proc_sets(gvc_logits_processors* dst, const gvc_logits_processors* sets, int n_sets, const int32_t* set_of_row, int B,
+                           hipStream_t s) {
+    bool used[kMaxSampleRows] = {};
+    for (int b = 0; b < B; ++b)
+        if (set_of_row[b] >= 0) used[set_of_row[b]] = true;
+    ProcSetChunk c;
+    memset(&c, 0, sizeof(c));
+    for (int k = 0; k <= n_sets; ++k) {
+        if (c.n == kProcSetChunk || (k == n_sets && c.n > 0)) {
+            hipLaunchKernelGGL(k_stage_proc_sets, dim3(1), dim3(64), 0, s, dst, c);
+            GVC_LAUNCH_CHECK();
+            c.n = 0;
+        }
+        if (k < n_sets && used[k]) {
+            c.s[c.n] = sets[k];
+            c.at[c.n] = k;
+            ++c.n;
+        }
+    }
+    return GVC_OK;
+}
+
+int launch_stage_set_index(int32_t* dst, const int32_t* set_of_row, int B, hipStream_t s) {
+    SetIndex si;
+    memset(&si, 0, sizeof(si));
+    memcpy(si.k, set_of_row, (size_t)B * sizeof(int32_t));
+    hipLaunchKernelGGL(k_stage_set_index, dim3(1), dim3(kMaxSampleRows), 0, s, dst, si, B);
     GVC_LAUNCH_CHECK();
     return GVC_OK;
 }
@@ -437,5 +496,40 @@ extern "C" int gvc_sample_proc(const float* logits, int32_t B, int32_t* ids, int
     if (e != hipSuccess) gvc::set_error("gvc_sample_proc: staging launch failed: %s", hipGetErrorString(e));
     if (rc) return rc;
     GVC_CHECK_HIP(e2);
+    return GVC_OK;
+}
+
+extern "C" int gvc_sample_proc_sets(const float* logits, int32_t B, int32_t* ids, int32_t ids_stride, int32_t* ids_len, int32_t* finished,
+                                    const gvc_sample_params* p, const gvc_row_sampling* rows, const gvc_logits_processors* sets,
+                                    int32_t n_sets, const int32_t* set_of_row, int32_t step, int32_t* tok_out, gvc_stream sv) {
+    GVC_REQUIRE(logits && ids && ids_len && finished && p && tok_out && B >= 1, GVC_ERR_ARG, "gvc_sample_proc_sets: bad argument");
+    int rc = gvc::check_proc_sets(sets, n_sets, set_of_row, B, p->vocab);
+    if (rc) return rc;
+    bool greedy = p->top_k == 1;
+    if (rows && (rc = gvc::check_sample_rows(rows, B, p->vocab, &greedy))) return rc;
+    hipStream_t s = (hipStream_t)sv;
+    // sets, rows and indices need device memory for the duration of this call only: stream-ordered, freed behind the sampler launch
+    const size_t set_bytes = (size_t)n_sets * sizeof(gvc_logits_processors);
+    const size_t row_bytes = rows ? (size_t)B * sizeof(gvc_row_sampling) : 0;
+    char* d = nullptr;
+    GVC_CHECK_HIP(hipMallocAsync((void**)&d, set_bytes + row_bytes + (size_t)B * sizeof(int32_t), s));
+    gvc_logits_processors* d_sets = reinterpret_cast<gvc_logits_processors*>(d);
+    gvc_row_sampling* d_rows = rows ? reinterpret_cast<gvc_row_sampling*>(d + set_bytes) : nullptr;
+    int32_t* d_sor = reinterpret_cast<int32_t*>(d + set_bytes + row_bytes);
+    rc = gvc::launch_stage_proc_sets(d_sets, sets, n_sets, set_of_row, B, s);
+    if (rc == GVC_OK) rc = gvc::launch_stage_set_index(d_sor, set_of_row, B, s);
+    if (rc == GVC_OK && rows) rc = gvc::launch_stage_rows(d_rows, rows, B, s);
+    if (rc == GVC_OK) {
+        gvc::SampleCall sc;
+        memset(&sc, 0, sizeof(sc));
+        sc.logits = logits; sc.B = B; sc.ids = ids; sc.ids_stride = ids_stride; sc.ids_len = ids_len;
+        sc.finished = finished; sc.p = *p; sc.step = step; sc.tok_out = tok_out; sc.rows = d_rows;
+        sc.proc_sets = d_sets; sc.set_of_row = d_sor;
+        if (rows) sc.p.top_k = greedy ? 1 : 0;          // (kernel choice only: every row's settings come from d_rows)
+        rc = gvc::launch_sample(sc, s);
+    }
+    const hipError_t e = hipFreeAsync(d, s);
+    if (rc) return rc;
+    GVC_CHECK_HIP(e);
     return GVC_OK;
 }

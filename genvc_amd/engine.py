@@ -113,6 +113,89 @@ def logits_processors(kw, prompt_len, vocab, sampling=True, prompt_lens=None):
     return pr
 
 
+MAX_SET_ROWS = 64      # kMaxSampleRows: rows of a call with per-row processor sets
+
+
+def check_proc_kwargs(kw, where):
+    """a per-row / per-group / per-job / per-session processor dict may hold PROC_KWARGS only: anything else raises ValueError naming
+    the key and `where` it came from"""
+    if kw is None:
+        return
+    if not isinstance(kw, dict):
+        raise ValueError(f"{where}: processor kwargs must be a dict or None, not {type(kw).__name__}")
+    unknown = sorted(set(kw) - set(PROC_KWARGS))
+    if unknown:
+        raise ValueError(f"{where}: {unknown[0]!r} is not a processor kwarg (allowed: {', '.join(PROC_KWARGS)})")
+
+
+def _kw_key(kw):
+    """hashable form of a processor dict (lists become tuples), for de-duplication before packing"""
+    key = tuple(sorted((k, tuple(v) if isinstance(v, (list, tuple)) else v) for k, v in kw.items() if v is not None))
+    try:
+        hash(key)
+    except TypeError:           # (an array-like value: its repr still tells identical dicts apart)
+        key = repr(key)
+    return key
+
+
+class ProcessorSets:
+    """per-row processor sets of one call (include/genvc_hip.h: gvc_gpt_generate_proc_sets): `sets` (n_sets gvc_logits_processors) and
+    `set_of_row` (B int32 indices into them, -1 = no processors), both host arrays.  `prompt_lens` keeps the caller's device tensor
+    alive (the sets point at it)."""
+
+    def __init__(self, sets, set_of_row, prompt_lens=None):
+        self.n_sets = len(sets)
+        self.sets = (_lib.LogitsProcessors * self.n_sets)(*sets)
+        self.set_of_row = (C.c_int32 * len(set_of_row))(*set_of_row)
+        self.prompt_lens = prompt_lens
+
+    def __len__(self):
+        return len(self.set_of_row)
+
+
+def logits_processor_sets(kws, prompt_len, vocab, sampling=True, prompt_lens=None):
+    """per-row processor kwargs -> ProcessorSets, or None when no row has a processor (the call then passes no sets at all).
+    kws: one entry per row, a dict of PROC_KWARGS (validated as logits_processors() does) or None for a row without processors.
+    prompt_len: the prompt length of every row (int) or of each row (a sequence of B ints: rows with equal dicts and different prompts
+    then get sets of their own); prompt_lens: a device int32 [B] tensor with one per row instead, as in logits_processors().
+    Identical dicts, and dicts that pack to the same set, share one set.  Errors name the offending row."""
+    kws = list(kws)
+    B = len(kws)
+    if not 1 <= B <= MAX_SET_ROWS:
+        raise ValueError(f"per-row processor sets serve 1..{MAX_SET_ROWS} rows, not {B}")
+    plens = [prompt_len] * B if isinstance(prompt_len, int) else [int(x) for x in prompt_len]
+    if len(plens) != B:
+        raise ValueError(f"{len(plens)} prompt lengths for {B} rows")
+    if prompt_lens is not None:
+        if int(prompt_lens.numel()) != B:
+            raise ValueError(f"{int(prompt_lens.numel())} prompt lengths for {B} rows")
+        plens = [0] * B
+    by_kw, by_bytes, sets, index = {}, {}, [], []
+    for b, kw in enumerate(kws):
+        check_proc_kwargs(kw, f"row {b}")
+        if not kw:
+            index.append(-1)
+            continue
+        key = (_kw_key(kw), plens[b])
+        if key not in by_kw:
+            try:
+                pr = logits_processors(kw, plens[b], vocab, sampling=sampling, prompt_lens=prompt_lens)
+            except ValueError as e:
+                raise ValueError(f"row {b}: {e}") from None
+            if pr is None:
+                by_kw[key] = -1
+            else:
+                raw = C.string_at(C.addressof(pr), C.sizeof(pr))
+                if raw not in by_bytes:
+                    by_bytes[raw] = len(sets)
+                    sets.append(pr)
+                by_kw[key] = by_bytes[raw]
+        index.append(by_kw[key])
+    if not sets:
+        return None
+    return ProcessorSets(sets, index, prompt_lens)
+
+
 BEAM_LENGTH_MODES = {"4.33": 0, "generated": 1}
 
 
@@ -381,6 +464,41 @@ class GptEngine:
                                           ptr(_i32(finished)), C.byref(common), arr, int(i0), int(n_steps), int(max_keys),
                                           ptr(tokens_out), tokens_out.stride(0), ptr(latents_out), lat_stride, stream()),
               "generate_rows")
+
+    def sample_proc_sets(self, logits, ids, ids_len, finished, params, sets, step, rows=None):
+        """sample_proc() with per-row processor sets (logits_processor_sets(); include/genvc_hip.h: gvc_sample_proc_sets): row b uses
+        sets.sets[sets.set_of_row[b]], none for -1.  rows: as in sample_proc (then params carries eos / vocab only)"""
+        B = logits.shape[0]
+        if len(sets) != B:
+            raise ValueError(f"{len(sets)} set indices for {B} rows")
+        arr = _rows_arg(rows, B) if rows is not None else None
+        tok = torch.empty(B, device=logits.device, dtype=torch.int32)
+        check(lib().gvc_sample_proc_sets(ptr(_f32(logits)), B, ptr(_i32(ids)), ids.shape[1], ptr(_i32(ids_len)), ptr(_i32(finished)),
+                                         C.byref(params), arr, sets.sets, sets.n_sets, sets.set_of_row, int(step), ptr(tok), stream()),
+              "sample_proc_sets")
+        return tok
+
+    def generate_proc_sets(self, slots, ids, ids_len, finished, params, sets, i0, n_steps, tokens_out, latents_out, max_keys=0, rows=None):
+        """generate() (rows None: params for every row) or generate_rows() (rows set: params may be None) with per-row processor sets
+        (logits_processor_sets(); include/genvc_hip.h: gvc_gpt_generate_proc_sets): row b uses sets.sets[sets.set_of_row[b]], none for
+        -1.  The sets travel with the call: the step graphs are generate()'s, and nothing is allocated or captured once warm."""
+        self._join_side()
+        B = slots.shape[0]
+        if len(sets) != B:
+            raise ValueError(f"{len(sets)} set indices for {B} rows")
+        arr = _rows_arg(rows, B) if rows is not None else None
+        assert tokens_out.is_cuda and tokens_out.dtype == torch.int32 and tokens_out.stride(1) == 1
+        lat_stride = 0
+        if latents_out is not None:
+            assert latents_out.is_cuda and latents_out.dtype == torch.float32 and latents_out.stride(2) == 1
+            assert latents_out.stride(1) == self.d and latents_out.stride(0) % self.d == 0
+            lat_stride = latents_out.stride(0) // self.d
+        if rows is not None:
+            params = sample_params(dict(repetition_penalty=1.0, temperature=1.0, top_p=1.0, top_k=0), self.V, self.dims["stop_audio_token"])
+        check(lib().gvc_gpt_generate_proc_sets(self._h, ptr(_i32(slots)), B, ptr(_i32(ids)), ids.shape[1], ptr(_i32(ids_len)),
+                                               ptr(_i32(finished)), C.byref(params), arr, sets.sets, sets.n_sets, sets.set_of_row,
+                                               int(i0), int(n_steps), int(max_keys), ptr(tokens_out), tokens_out.stride(0),
+                                               ptr(latents_out), lat_stride, stream()), "generate_proc_sets")
 
     def beam_generate(self, slots, beam, n_steps, max_keys=0):
         """n_steps steps of `beam` (a BeamSearch) on the device, continuing at beam.steps (include/genvc_hip.h: gvc_gpt_beam_generate):

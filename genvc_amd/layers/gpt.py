@@ -11,7 +11,8 @@ import torch
 from torch import nn
 
 from .._lib import GenvcHipError
-from ..engine import BEAM_LENGTH_MODES, PROC_KWARGS, BeamSearch, GptEngine, logits_processors, sample_params
+from ..engine import (BEAM_LENGTH_MODES, PROC_KWARGS, BeamSearch, GptEngine, check_proc_kwargs, logits_processor_sets, logits_processors,
+                      sample_params)
 from .perceiver_encoder import PerceiverResampler
 
 
@@ -58,6 +59,25 @@ def _any_proc(kw):
 def _proc_arg(proc):
     """the engine call's processor argument: none at all without processors (the call is exactly the one without them)"""
     return {} if proc is None else {"proc": proc}
+
+
+def _per_item_procs(kw, item_kwargs, n, name, vocab):
+    """group_kwargs / job_kwargs: one processor dict (or None) per item, merged over the call-wide processor kwargs of `kw` -> the
+    merged dict of every item.  Keys other than PROC_KWARGS, a wrong count and malformed settings raise ValueError naming the item."""
+    item_kwargs = list(item_kwargs)
+    if len(item_kwargs) != n:
+        raise ValueError(f"{name}: {len(item_kwargs)} processor dicts for {n} items")
+    base = {k: kw[k] for k in PROC_KWARGS if kw.get(k) is not None}
+    out = []
+    for i, d in enumerate(item_kwargs):
+        check_proc_kwargs(d, f"{name}[{i}]")
+        m = dict(base, **(d or {}))
+        try:
+            logits_processors(m, 0, vocab)
+        except ValueError as e:
+            raise ValueError(f"{name}[{i}]: {e}") from None
+        out.append(m)
+    return out
 
 
 class _Holder(nn.Module):
@@ -320,7 +340,7 @@ class GPT(nn.Module):
         return ids
 
     @torch.inference_mode()
-    def generate_groups(self, groups, **generate_kwargs):
+    def generate_groups(self, groups, group_kwargs=None, **generate_kwargs):
         """Several generate() calls decoded TOGETHER: groups = [(cond_latents [B_i, 32, d], text_inputs [B_i, Tc_i]), ...] with
         different code lengths.  Each group is prefilled on its own (its rows share a prefix length) into its own KV slots; the
         decode steps then run over all streams at once, so the weights stream once per step for the whole set.  Streams are
@@ -334,10 +354,16 @@ class GPT(nn.Module):
         `max_new_tokens` may be a list with one budget per group (benchmark mode: synthetic weights seldom stop, SURVEY.md 8d fixes
         the tokens of a segment by its duration): a group whose budget is spent leaves the joint decode, and the steps that remain
         run over the live streams only (fewer rows per step: the 8-row instead of the 16-row one-launch step for configs[2]'s tail).
+        `group_kwargs` (one dict or None per group): each group's own logits processors (PROC_KWARGS only), merged over the call-wide
+        ones -- the reference runs one HF generate per segment, so they may differ between groups; each group then gets what
+        generate(**its merged kwargs) returns for it, the joint decode giving every row its group's set (gvc_gpt_generate_proc_sets).
         Returns a list of int64 [B_i, n_i] (reference gpt.py:594-609 per group)."""
         _no_beams(generate_kwargs, "grouped (generate_groups)")
-        self._need_engine()
         kw = dict(generate_kwargs)
+        gkw = None
+        if group_kwargs is not None:
+            gkw = _per_item_procs(kw, group_kwargs, len(groups), "group_kwargs", self.num_audio_tokens)
+        self._need_engine()
         group = kw.pop("group", 16)          # decode steps per engine call (one host look at the finished flags per call)
         class_seeds = kw.pop("class_seeds", None)      # sampling runs: one seed per group (default: seed + 7919 * group index)
         joint_sampling = bool(kw.pop("joint_sampling", JOINT_SAMPLING_DEFAULT))
@@ -364,7 +390,7 @@ class GPT(nn.Module):
             # per-row numbering of the counter RNG)
             outs = []
             for gi, (c, t) in enumerate(groups):
-                kg = dict(kw)
+                kg = dict(kw, **gkw[gi]) if gkw is not None else dict(kw)
                 if not greedy:
                     kg["seed"] = seeds[gi]
                 if budgets is not None:
@@ -372,14 +398,14 @@ class GPT(nn.Module):
                 outs.append(self.generate(c, t, **kg))
             self.last_latents = None      # (same contract as the joint path: callers of generate_groups want tokens)
             return outs
-        return self._recovering(total, lambda: self._generate_groups_joint(groups, kw, budgets, group, stats, seeds))
+        return self._recovering(total, lambda: self._generate_groups_joint(groups, kw, budgets, group, stats, seeds, gkw))
 
     def _row_settings(self, kw):
         """the processor settings generate() would use for these kwargs (see _start), as a gvc_row_sampling entry without its key"""
         return dict(repetition_penalty=kw.get("repetition_penalty", 1.0), temperature=kw.get("temperature", 1.0),
                     top_p=kw.get("top_p", 1.0), top_k=kw.get("top_k", 0) if kw.get("do_sample", True) else 1)
 
-    def _generate_groups_joint(self, groups, kw, budgets, group, stats, seeds=None):
+    def _generate_groups_joint(self, groups, kw, budgets, group, stats, seeds=None, gkw=None):
         total = sum(int(t.shape[0]) for _, t in groups)
         if stats is not None:
             stats["joint"] += 1
@@ -389,6 +415,7 @@ class GPT(nn.Module):
         order = sorted(range(len(groups)), key=lambda i: -(budgets[i] if budgets else max_new))
         groups = [groups[i] for i in order]
         seeds = [seeds[i] for i in order] if seeds is not None else None
+        gkw = [gkw[i] for i in order] if gkw is not None else None
         gb = [budgets[i] if budgets else max_new for i in order]
         prefixes = [self.engine.prefix_embeddings(c.to(torch.float32).contiguous(), t.to(torch.int32).contiguous()) for c, t in groups]
         n0s = [int(p.shape[1]) + 1 for p in prefixes]
@@ -414,7 +441,7 @@ class GPT(nn.Module):
         rs = self._row_settings(kw)
         # processors: one set for the call, each row counting from its own prompt (its group's fake ids)
         proc = None
-        if _any_proc(kw):
+        if gkw is None and _any_proc(kw):
             plens = torch.cat([torch.full((hi - lo,), n0, dtype=torch.int32) for (lo, hi), n0 in zip(spans, n0s)]).to(dev)
             proc = logits_processors(kw, 0, self.num_audio_tokens, sampling=seeds is not None, prompt_lens=plens)
         done = 0
@@ -423,7 +450,20 @@ class GPT(nn.Module):
             live = spans[live_groups[-1]][1]                                   # rows [0, live) still have tokens to produce
             n = min(group, min(gb[g] for g in live_groups) - done)              # (a call never crosses the end of a budget)
             mk = max(n0s[g] for g in live_groups) + done + n
-            if seeds is None:
+            # group_kwargs: every row its group's set, counted from its group's prompt (None: no row has a processor)
+            sets = None
+            if gkw is not None:
+                sets = logits_processor_sets([gkw[g] for g in live_groups for _ in range(spans[g][1] - spans[g][0])],
+                                             [n0s[g] for g in live_groups for _ in range(spans[g][1] - spans[g][0])],
+                                             self.num_audio_tokens, sampling=seeds is not None)
+            if sets is not None:
+                rows = None
+                if seeds is not None:
+                    rows = [dict(rs, seed=seeds[g], rng_row=r, rng_step0=done) for g in live_groups
+                            for r in range(spans[g][1] - spans[g][0])]
+                self.engine.generate_proc_sets(slots[:live], ids[:live], ids_len[:live], finished[:live], params, sets, done, n, toks[:live],
+                                               lats[:live], max_keys=mk, rows=rows)
+            elif seeds is None:
                 self.engine.generate(slots[:live], ids[:live], ids_len[:live], finished[:live], params, done, n, toks[:live], lats[:live],
                                      max_keys=mk, **_proc_arg(proc))
             else:
@@ -444,7 +484,7 @@ class GPT(nn.Module):
         return out
 
     @torch.inference_mode()
-    def generate_rolling(self, jobs, **generate_kwargs):
+    def generate_rolling(self, jobs, job_kwargs=None, **generate_kwargs):
         """generate_groups with a ROLLING set of streams: jobs = [(cond_latents [B_i, 32, d], text_inputs
         [B_i, Tc_i]), ...] are admitted in order as KV slots become free.  Retirement is PER ROW, as the reference's loop tracks
         `unfinished_sequences` per row (stream_generator.py:861-874): a row that has emitted the stop token gives its KV slot back at
@@ -459,10 +499,16 @@ class GPT(nn.Module):
         Sampling (top_k != 1) needs `job_seeds`, one per job: row r of job j is keyed (job_seeds[j], r, tokens job j has drawn), so
         job j draws what generate(c_j, t_j, seed=job_seeds[j]) draws from the same logits, whatever it shares the decode step with (the
         rows step's logits themselves are not bit-identical across row counts: JOINT_SAMPLING_DEFAULT).  Without job_seeds a sampling
-        call raises NotImplementedError."""
+        call raises NotImplementedError.
+        `job_kwargs` (one dict or None per job): each job's own logits processors (PROC_KWARGS only), merged over the call-wide ones;
+        job j then gets what generate(c_j, t_j, **its merged kwargs) returns (seed=job_seeds[j] when sampling), each row of a decode
+        call carrying its job's set (gvc_gpt_generate_proc_sets)."""
         _no_beams(generate_kwargs, "rolling (generate_rolling)")
-        self._need_engine()
         kw = dict(generate_kwargs)
+        jkw = None
+        if job_kwargs is not None:
+            jkw = _per_item_procs(kw, job_kwargs, len(jobs), "job_kwargs", self.num_audio_tokens)
+        self._need_engine()
         group = kw.pop("group", 16)
         kw.pop("class_seeds", None)
         job_seeds = kw.pop("job_seeds", None)
@@ -488,9 +534,9 @@ class GPT(nn.Module):
         if max(int(t.shape[0]) for _, t in jobs) > S:
             raise ValueError(f"generate_rolling: a job has more rows than streams may be in flight ({S}; KV slots {self.max_slots})")
         seeds = None if greedy else [int(x) for x in job_seeds]
-        return self._recovering(S, lambda: self._rolling(jobs, kw, budgets, group, n0s, width, S, seeds))
+        return self._recovering(S, lambda: self._rolling(jobs, kw, budgets, group, n0s, width, S, seeds, jkw))
 
-    def _rolling(self, jobs, kw, budgets, group, n0s, width, S, seeds=None):
+    def _rolling(self, jobs, kw, budgets, group, n0s, width, S, seeds=None, jkw=None):
         dev = jobs[0][1].device
         eng = self.engine
         stop = self.stop_audio_token
@@ -533,11 +579,20 @@ class GPT(nn.Module):
             fin = fin_all[idx].contiguous()
             toks = torch.full((len(row_slots), n), stop, device=dev, dtype=torch.int32)
             # processors: one set for the call, each row counting from its own job's prompt
-            proc = None
-            if _any_proc(kw):
+            proc = sets = None
+            if jkw is not None:
+                # job_kwargs: every row its job's set, counted from its job's prompt (None: no row has a processor)
+                sets = logits_processor_sets([jkw[j["job"]] for j in live for _ in j["alive"]], [j["n0"] for j in live for _ in j["alive"]],
+                                             self.num_audio_tokens, sampling=seeds is not None)
+            elif _any_proc(kw):
                 plens = torch.tensor([j["n0"] for j in live for _ in j["alive"]], dtype=torch.int32).to(dev)
                 proc = logits_processors(kw, 0, self.num_audio_tokens, sampling=seeds is not None, prompt_lens=plens)
-            if seeds is None:
+            if sets is not None:
+                keys = None
+                if seeds is not None:
+                    keys = [dict(rs, seed=seeds[j["job"]], rng_row=r, rng_step0=j["done"]) for j in live for r in j["alive"]]
+                eng.generate_proc_sets(rows, ids, ids_len, fin, params, sets, 0, n, toks, None, max_keys=W - 8, rows=keys)
+            elif seeds is None:
                 eng.generate(rows, ids, ids_len, fin, params, 0, n, toks, None, max_keys=W - 8, **_proc_arg(proc))
             else:
                 # row r of job j keyed (job seed, r, tokens the job has drawn): the key generate(seed=job_seeds[j]) gives that row

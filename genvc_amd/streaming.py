@@ -28,13 +28,19 @@ steps, and differ from a solo run.  With `per_session_sampling=True` every sessi
 (`open(ref_audio, sampling={...}, seed=s)`) and its row is keyed by its own stream -- (seed, 0, tokens of the segment drawn so far),
 the key `synthesize_utt_streaming` gives a lone stream -- so its tokens are those of its solo run with the same settings, whoever
 shares its steps, and a segment re-run after a recovered time-out draws the same tokens again.
+
+Logits processors (PROC_KWARGS: no_repeat_ngram_size, min_new_tokens, suppress_tokens, ...).  `StreamSessions(generate_kwargs={...})`
+sets a scheduler-wide default and `open(ref_audio, generate_kwargs={...})` a session's own, merged over it, with or without
+per_session_sampling.  Every decode call gives each session's row its own set (gvc_gpt_generate_proc_sets), counted from the prompt of
+the segment it is decoding, so a session gets the tokens of its solo `synthesize_utt_streaming(generate_kwargs=...)` whoever shares its
+steps; a call in which no session has a processor passes no sets at all.
 """
 import time
 
 import torch
 
 from .inference.inference_utils import _sampling_kwargs, _vocode, handle_chunks
-from .engine import sample_params
+from .engine import check_proc_kwargs, logits_processor_sets, logits_processors, sample_params
 from ._lib import GenvcHipError
 
 
@@ -48,13 +54,14 @@ class _Session:
         self.prev = self.overlap = None
         self.tokens = []           # per segment: int64 [1, n]
         self.past = None           # left context: the tail of the source audio fed so far [1, <= ctx samples]
+        self.procs = None          # the session's logits processor kwargs (merged over the scheduler's default), None: none
         self.current = None        # the segment being decoded and its ContentVec left context as they were when it started (recovery)
         self.skip = 0              # tokens of the current segment already emitted before a failed step (recovery re-run)
 
 
 class StreamSessions:
     def __init__(self, model, max_sessions=8, group=8, left_context_s=0.0, rearm_after_s=5.0, rearm_max_tries=3, prefill_speaker=True,
-                 per_session_sampling=False):
+                 per_session_sampling=False, generate_kwargs=None):
         m = self.m = model
         self.ctx = int(round(left_context_s * model.content_sample_rate / 320.0)) * 320       # whole ContentVec hops
         g = m.gpt
@@ -72,6 +79,7 @@ class StreamSessions:
         self.params = sample_params(samp, g.num_audio_tokens, g.stop_audio_token, 0)
         self.default_sampling = samp
         self.per_session_sampling = bool(per_session_sampling)    # every session its own settings and RNG stream (gvc_gpt_generate_rows)
+        self.default_procs = self._procs(generate_kwargs, {}, "StreamSessions(generate_kwargs=...)")
         self.calls = 0
         self.recoveries = 0          # decode calls dropped and re-run after a hand-off time-out (gvc_gpt_health)
         self._rearm = False          # a recovery happened: the one-launch steps may be re-armed (policy: maybe_rearm)
@@ -90,13 +98,25 @@ class StreamSessions:
         self.finished = torch.zeros(max_sessions, device=dev, dtype=torch.int32)
 
     # ------------------------------------------------------------------------------------------
+    def _procs(self, kw, base, where):
+        """a processor dict (PROC_KWARGS only) merged over `base`, validated -> the merged dict, or None when it is empty"""
+        check_proc_kwargs(kw, where)
+        m = dict(base, **{k: v for k, v in (kw or {}).items() if v is not None})
+        try:
+            logits_processors(m, 0, self.m.gpt.num_audio_tokens)
+        except ValueError as e:
+            raise ValueError(f"{where}: {e}") from None
+        return m or None
+
     @torch.inference_mode()
-    def open(self, ref_audio, sampling=None, seed=0):
+    def open(self, ref_audio, sampling=None, seed=0, generate_kwargs=None):
         """ref_audio [1, n] at the model rate -> session id.  With per_session_sampling: `sampling` (top_k, top_p, temperature,
-        repetition_penalty; missing keys come from the model config) and `seed` are this session's own; otherwise passing either raises."""
+        repetition_penalty; missing keys come from the model config) and `seed` are this session's own; otherwise passing either raises.
+        `generate_kwargs`: the session's logits processors (PROC_KWARGS only), merged over the scheduler's default; any other key raises."""
         if not self.per_session_sampling and (sampling is not None or seed != 0):
             raise ValueError("open(sampling=..., seed=...) needs StreamSessions(..., per_session_sampling=True): this scheduler samples "
                              "every session with the model config's settings")
+        procs = self._procs(generate_kwargs, self.default_procs or {}, "open(generate_kwargs=...)")
         samp = dict(self.default_sampling)
         if sampling is not None:
             unknown = set(sampling) - set(samp)
@@ -111,7 +131,7 @@ class StreamSessions:
         sid = self._next_id
         self._next_id += 1
         s = self.sessions[sid] = _Session(self.free.pop(0), cond)
-        s.sampling, s.seed = samp, int(seed)
+        s.sampling, s.seed, s.procs = samp, int(seed), procs
         if self.prefill_speaker:
             # the speaker is known before the first source segment arrives: its 32 conditioning rows go into the slot's KV cache NOW
             # (gvc_gpt_prefill_cond), so the first segment too computes only its text rows + start token -- the first audio chunk of a
@@ -277,10 +297,20 @@ class StreamSessions:
         toks = torch.full((B, n), self.stop, device=dev, dtype=torch.int32)
         lats = torch.empty(B, n, m.gpt.model_dim, device=dev, dtype=torch.float32)
         self.calls += 1
+        # each session's processors, counted from the prompt of the segment it decodes (None when no session has any: no sets at all)
+        sets = None
+        if any(s.procs for _, s in act):
+            sets = logits_processor_sets([s.procs for _, s in act], [s.p1 for _, s in act], m.gpt.num_audio_tokens)
         if self.per_session_sampling:
             # each session's row keyed by its own stream: (its seed, row 0 of a lone stream, tokens of this segment drawn so far)
             rows = [dict(s.sampling, seed=s.seed, rng_row=0, rng_step0=s.done) for _, s in act]
-            eng.generate_rows(slots, ids, ids_len, fin, rows, 0, n, toks, lats, max_keys=W - 8)
+            if sets is not None:
+                eng.generate_proc_sets(slots, ids, ids_len, fin, None, sets, 0, n, toks, lats, max_keys=W - 8, rows=rows)
+            else:
+                eng.generate_rows(slots, ids, ids_len, fin, rows, 0, n, toks, lats, max_keys=W - 8)
+        elif sets is not None:
+            self.params.seed = self.calls - 1
+            eng.generate_proc_sets(slots, ids, ids_len, fin, self.params, sets, 0, n, toks, lats, max_keys=W - 8)
         else:
             self.params.seed = self.calls - 1      # a fresh counter-RNG stream per call (only matters for top_k > 1)
             eng.generate(slots, ids, ids_len, fin, self.params, 0, n, toks, lats, max_keys=W - 8)

@@ -334,6 +334,23 @@ int gvc_beam_select_proc(const gvc_beam_state* st, const gvc_logits_processors* 
 int gvc_gpt_beam_generate_proc(gvc_gpt* ctx, int32_t* slots, const gvc_beam_state* st, const gvc_logits_processors* proc, int32_t i0,
                                int32_t n_steps, int32_t max_keys, gvc_stream s);
 
+/* Per-row processor sets: row b uses sets[set_of_row[b]], or no processors at all when the index is -1 (such a row computes exactly
+ * what it computes in the call without processors).  sets (n_sets entries, 1 <= n_sets <= B <= 64) and set_of_row (B entries, each in
+ * [-1, n_sets)) are HOST arrays, free again when the call returns; GVC_ERR_ARG otherwise, and every set is checked as proc is.  A set's
+ * prompt length rule is proc's: prompt_lens[b] (device, indexed by the row's place in the call) when set, else prompt_len.  rows
+ * (nullable HOST) as in gvc_sample_proc / gvc_gpt_generate_proc.
+ * gvc_gpt_generate_proc_sets stages each set some row uses into the device-resident call state in launches of its own (four sets per
+ * launch) ahead of the call's first launch, which carries the indices: the same captured step graphs, no allocation and no
+ * synchronisation per call.  Not on the beam path. */
+int gvc_sample_proc_sets(const float* logits, int32_t B, int32_t* ids, int32_t ids_stride, int32_t* ids_len, int32_t* finished,
+                         const gvc_sample_params* p, const gvc_row_sampling* rows, const gvc_logits_processors* sets, int32_t n_sets,
+                         const int32_t* set_of_row, int32_t step, int32_t* tok_out, gvc_stream s);
+int gvc_gpt_generate_proc_sets(gvc_gpt* ctx, const int32_t* slots, int32_t B, int32_t* ids, int32_t ids_stride, int32_t* ids_len,
+                               int32_t* finished, const gvc_sample_params* p, const gvc_row_sampling* rows,
+                               const gvc_logits_processors* sets, int32_t n_sets, const int32_t* set_of_row, int32_t i0, int32_t n_steps,
+                               int32_t max_keys, int32_t* tokens_out, int32_t tok_stride, float* latents_out, int32_t lat_stride,
+                               gvc_stream s);
+
 /* Which decode step the last gvc_gpt_generate call replayed (diagnostic): 0 none yet, 1 launch-per-phase with split-key attention,
  * 2 launch-per-phase with the fused short-context attention launch, 3 the one-launch step (one stream), 4 the MFMA rows path
  * (launch per phase: 17+ streams, or shapes the one-launch rows step does not serve), 5 the one-launch rows step (2..16 streams,
