@@ -44,6 +44,11 @@ class LogitsProcessors(C.Structure):
         [("prompt_lens", C.c_void_p), ("suppress", C.c_uint32 * 33), ("begin_suppress", C.c_uint32 * 33)]
 
 
+class LogitsWarpers(C.Structure):
+    """gvc_logits_warpers (include/genvc_hip.h): typical / epsilon / eta sampling warpers of one set (16 bytes); 0 = off"""
+    _fields_ = [("typical_p", C.c_float), ("epsilon_cutoff", C.c_float), ("eta_cutoff", C.c_float), ("reserved", C.c_int32)]
+
+
 class PerceiverDims(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("dim", "depth", "dim_context", "num_latents", "dim_head", "heads",
                                          "ff_mult", "max_batch", "max_frames")]
@@ -105,6 +110,11 @@ _SIGNATURES = {
     "gvc_gpt_generate_proc_sets": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, _P, _P, C.POINTER(SampleParams), C.POINTER(RowSampling),
                                              C.POINTER(LogitsProcessors), C.c_int32, c_i32p, C.c_int32, C.c_int32, C.c_int32, _P,
                                              C.c_int32, _P, C.c_int32, _P]),
+    "gvc_sample_warp": (C.c_int, [_P, C.c_int32, _P, C.c_int32, _P, _P, C.POINTER(SampleParams), C.POINTER(RowSampling),
+                                  C.POINTER(LogitsProcessors), C.POINTER(LogitsWarpers), C.c_int32, c_i32p, C.c_int32, _P, _P]),
+    "gvc_gpt_generate_warp": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, _P, _P, C.POINTER(SampleParams), C.POINTER(RowSampling),
+                                        C.POINTER(LogitsProcessors), C.POINTER(LogitsWarpers), C.c_int32, c_i32p, C.c_int32, C.c_int32,
+                                        C.c_int32, _P, C.c_int32, _P, C.c_int32, _P]),
     "gvc_gpt_decode_variant": (C.c_int, [_P]),
     "gvc_gpt_rows_step_launches": (C.c_longlong, [_P]),
     "gvc_gpt_health": (C.c_int, [_P]),

@@ -182,6 +182,7 @@ struct GenCall {
     gvc_logits_processors proc;              // processors of a gvc_gpt_generate_proc call (sc.proc points here)
     gvc_logits_processors sets[kMaxSampleRows];   // processor sets of a gvc_gpt_generate_proc_sets call (sc.proc_sets points here)
     int32_t set_of_row[kMaxSampleRows];      // ... and each row's index into them, -1: none (sc.set_of_row points here)
+    gvc_logits_warpers warps[kMaxSampleRows];     // warpers of a gvc_gpt_generate_warp call, one per set (sc.warps points here)
 };
 
 // Start / end of a gvc_gpt_generate call in ONE launch each (they used to be a memset, k_set_gen_call and two k_stage_rows before the
@@ -1643,9 +1644,11 @@ extern "C" int gvc_gpt_rearm(gvc_gpt* c) {
 
 // rows: null (gvc_gpt_generate: p's settings for every row) or B host entries (gvc_gpt_generate_rows).  proc: null or the call's
 // processors (gvc_gpt_generate_proc); set_of_row: null or B host indices into the n_sets host sets (gvc_gpt_generate_proc_sets, proc null)
+// and, when warps is set (gvc_gpt_generate_warp), into the n_sets host warpers too; sets is then nullable
 static int generate_impl(gvc_gpt* c, const int32_t* slots, int32_t B, int32_t* ids, int32_t ids_stride, int32_t* ids_len, int32_t* finished,
                          const gvc_sample_params* p, const gvc_row_sampling* rows, const gvc_logits_processors* proc,
-                         const gvc_logits_processors* sets, int32_t n_sets, const int32_t* set_of_row, int32_t i0,
+                         const gvc_logits_processors* sets, const gvc_logits_warpers* warps, int32_t n_sets, const int32_t* set_of_row,
+                         int32_t i0,
                          int32_t n_steps, int32_t max_keys, int32_t* tokens_out, int32_t tok_stride, float* latents_out, int32_t lat_stride,
                          gvc_stream sv) {
     int rc = check_ready(c);
@@ -1654,7 +1657,11 @@ static int generate_impl(gvc_gpt* c, const int32_t* slots, int32_t B, int32_t* i
     bool rows_greedy = false;
     if (rows && (rc = check_sample_rows(rows, B, c->dm.vocab, &rows_greedy))) return rc;
     if (proc && (rc = check_procs(*proc, c->dm.vocab))) return rc;
-    if (set_of_row && (rc = check_proc_sets(sets, n_sets, set_of_row, B, c->dm.vocab))) return rc;
+    if (warps) {
+        if ((rc = check_warp_sets(sets, warps, n_sets, set_of_row, B, c->dm.vocab))) return rc;
+    } else if (set_of_row && (rc = check_proc_sets(sets, n_sets, set_of_row, B, c->dm.vocab))) {
+        return rc;
+    }
     // cached positions of the longest stream once this call has run: the caller's bound, else the whole ids row
     const int key_bound = max_keys > 0 ? max_keys : ids_stride;
     GVC_REQUIRE(max_keys == 0 || max_keys < c->dm.max_seq, GVC_ERR_STATE,
@@ -1670,14 +1677,17 @@ static int generate_impl(gvc_gpt* c, const int32_t* slots, int32_t B, int32_t* i
     if (set_of_row) {
         // each set some row uses travels by value into the device-resident call state, ahead of the begin launch, which carries the
         // rows' indices (and row entries): nothing to allocate, no staging buffer, and the caller's arrays are free on return
-        if ((rc = launch_stage_proc_sets(c->gen_call->sets, sets, n_sets, set_of_row, B, s))) return rc;
+        // (the warpers likewise, all n_sets of them in one launch)
+        if (sets && (rc = launch_stage_proc_sets(c->gen_call->sets, sets, n_sets, set_of_row, B, s))) return rc;
+        if (warps && (rc = launch_stage_warps(c->gen_call->warps, warps, n_sets, s))) return rc;
         SampleRows sr;
         memset(&sr, 0, sizeof(sr));
         SetIndex si;
         memset(&si, 0, sizeof(si));
         memcpy(si.k, set_of_row, (size_t)B * sizeof(int32_t));
-        sc.proc_sets = c->gen_call->sets;
+        sc.proc_sets = sets ? c->gen_call->sets : nullptr;
         sc.set_of_row = c->gen_call->set_of_row;
+        sc.warps = warps ? c->gen_call->warps : nullptr;
         if (rows) {
             memcpy(sr.r, rows, (size_t)B * sizeof(gvc_row_sampling));
             sc.rows = c->gen_call->rows;
@@ -1740,7 +1750,7 @@ extern "C" int gvc_gpt_generate(gvc_gpt* c, const int32_t* slots, int32_t B, int
                                 int32_t* ids_len, int32_t* finished, const gvc_sample_params* p, int32_t i0,
                                 int32_t n_steps, int32_t max_keys, int32_t* tokens_out, int32_t tok_stride, float* latents_out,
                                 int32_t lat_stride, gvc_stream sv) {
-    return generate_impl(c, slots, B, ids, ids_stride, ids_len, finished, p, nullptr, nullptr, nullptr, 0, nullptr, i0, n_steps, max_keys,
+    return generate_impl(c, slots, B, ids, ids_stride, ids_len, finished, p, nullptr, nullptr, nullptr, nullptr, 0, nullptr, i0, n_steps, max_keys,
                          tokens_out, tok_stride, latents_out, lat_stride, sv);
 }
 
@@ -1749,7 +1759,7 @@ extern "C" int gvc_gpt_generate_rows(gvc_gpt* c, const int32_t* slots, int32_t B
                                      int32_t n_steps, int32_t max_keys, int32_t* tokens_out, int32_t tok_stride, float* latents_out,
                                      int32_t lat_stride, gvc_stream sv) {
     GVC_REQUIRE(rows, GVC_ERR_ARG, "generate_rows: null rows");
-    return generate_impl(c, slots, B, ids, ids_stride, ids_len, finished, common, rows, nullptr, nullptr, 0, nullptr, i0, n_steps, max_keys,
+    return generate_impl(c, slots, B, ids, ids_stride, ids_len, finished, common, rows, nullptr, nullptr, nullptr, 0, nullptr, i0, n_steps, max_keys,
                          tokens_out, tok_stride, latents_out, lat_stride, sv);
 }
 
@@ -1757,7 +1767,7 @@ extern "C" int gvc_gpt_generate_proc(gvc_gpt* c, const int32_t* slots, int32_t B
                                      int32_t* finished, const gvc_sample_params* p, const gvc_row_sampling* rows,
                                      const gvc_logits_processors* proc, int32_t i0, int32_t n_steps, int32_t max_keys, int32_t* tokens_out,
                                      int32_t tok_stride, float* latents_out, int32_t lat_stride, gvc_stream sv) {
-    return generate_impl(c, slots, B, ids, ids_stride, ids_len, finished, p, rows, proc, nullptr, 0, nullptr, i0, n_steps, max_keys,
+    return generate_impl(c, slots, B, ids, ids_stride, ids_len, finished, p, rows, proc, nullptr, nullptr, 0, nullptr, i0, n_steps, max_keys,
                          tokens_out, tok_stride, latents_out, lat_stride, sv);
 }
 
@@ -1767,8 +1777,22 @@ extern "C" int gvc_gpt_generate_proc_sets(gvc_gpt* c, const int32_t* slots, int3
                                           int32_t n_steps, int32_t max_keys, int32_t* tokens_out, int32_t tok_stride, float* latents_out,
                                           int32_t lat_stride, gvc_stream sv) {
     GVC_REQUIRE(sets && set_of_row, GVC_ERR_ARG, "generate_proc_sets: null sets or set_of_row");
-    return generate_impl(c, slots, B, ids, ids_stride, ids_len, finished, p, rows, nullptr, sets, n_sets, set_of_row, i0, n_steps, max_keys,
+    return generate_impl(c, slots, B, ids, ids_stride, ids_len, finished, p, rows, nullptr, sets, nullptr, n_sets, set_of_row, i0, n_steps, max_keys,
                          tokens_out, tok_stride, latents_out, lat_stride, sv);
+}
+
+extern "C" int gvc_gpt_generate_warp(gvc_gpt* c, const int32_t* slots, int32_t B, int32_t* ids, int32_t ids_stride, int32_t* ids_len,
+                                     int32_t* finished, const gvc_sample_params* p, const gvc_row_sampling* rows,
+                                     const gvc_logits_processors* sets, const gvc_logits_warpers* warps, int32_t n_sets,
+                                     const int32_t* set_of_row, int32_t i0, int32_t n_steps, int32_t max_keys, int32_t* tokens_out,
+                                     int32_t tok_stride, float* latents_out, int32_t lat_stride, gvc_stream sv) {
+    GVC_REQUIRE(B >= 1 && B <= kMaxSampleRows, GVC_ERR_ARG, "generate_warp: need 1..%d rows, got %d", kMaxSampleRows, B);
+    if (!warps && !sets)           // neither: the call without processors
+        return generate_impl(c, slots, B, ids, ids_stride, ids_len, finished, p, rows, nullptr, nullptr, nullptr, 0, nullptr, i0, n_steps,
+                             max_keys, tokens_out, tok_stride, latents_out, lat_stride, sv);
+    int32_t zeros[kMaxSampleRows] = {};
+    return generate_impl(c, slots, B, ids, ids_stride, ids_len, finished, p, rows, nullptr, sets, warps, n_sets,
+                         set_of_row ? set_of_row : zeros, i0, n_steps, max_keys, tokens_out, tok_stride, latents_out, lat_stride, sv);
 }
 
 

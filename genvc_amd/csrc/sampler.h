@@ -37,13 +37,23 @@ struct SampleCall {
     // processors when the index is -1, and proc is not read.  Null: proc serves every row as above
     const gvc_logits_processors* proc_sets;
     const int32_t* set_of_row;
+    // nullable: typical / epsilon / eta warpers (gvc_*_warp calls, device memory), one per set: row b uses warps[set_of_row[b]] (none
+    // for -1), warps[0] when set_of_row is null.  Null: none, and k_sample computes exactly what it computes without this field
+    const gvc_logits_warpers* warps;
 };
 
 // the processors of row b (uniform over the row's workgroup)
 __device__ __forceinline__ const gvc_logits_processors* row_procs(const SampleCall& C, int b) {
     if (!C.set_of_row) return C.proc;
     const int k = C.set_of_row[b];
-    return k >= 0 ? C.proc_sets + k : nullptr;
+    return k >= 0 && C.proc_sets ? C.proc_sets + k : nullptr;     // (a warpers call may pass indices without processor sets)
+}
+
+// the warpers of row b (uniform over the row's workgroup)
+__device__ __forceinline__ const gvc_logits_warpers* row_warps(const SampleCall& C, int b) {
+    if (!C.warps) return nullptr;
+    const int k = C.set_of_row ? C.set_of_row[b] : 0;
+    return k >= 0 ? C.warps + k : nullptr;
 }
 
 int launch_sample(const SampleCall& sc, hipStream_t s);
@@ -78,5 +88,17 @@ int launch_stage_proc_sets(gvc_logits_processors* dst, const gvc_logits_processo
                            hipStream_t s);
 // set_of_row[0..B) -> dst[0..B) on stream s (one small launch)
 int launch_stage_set_index(int32_t* dst, const int32_t* set_of_row, int B, hipStream_t s);
+
+// warpers of a gvc_*_warp call, all n_sets of them BY VALUE in one launch (1 KB of kernel argument)
+struct WarpTable {
+    gvc_logits_warpers w[kMaxSampleRows];
+    int32_t n;
+};
+// host-side checks of a warp call: 1 <= B <= 64, 1 <= n_sets <= B, set_of_row (nullable) in [-1, n_sets), sets (nullable) pass
+// check_procs, warps (nullable) hold 0 or a value in (0, 1) each and reserved == 0
+int check_warp_sets(const gvc_logits_processors* sets, const gvc_logits_warpers* warps, int n_sets, const int32_t* set_of_row, int B,
+                    int vocab);
+// warps[0..n_sets) -> dst[0..n_sets) on stream s (one small launch)
+int launch_stage_warps(gvc_logits_warpers* dst, const gvc_logits_warpers* warps, int n_sets, hipStream_t s);
 
 }  // namespace gvc

@@ -43,6 +43,101 @@ __device__ __forceinline__ T block_scan_excl(T v, T* scr /*[17]*/, T* total) {
     return base + inc - v;
 }
 
+// sum of (a, b) over the workgroup, the same bits in every thread and on every run: the xor butterfly gives all 64 lanes of a wave one
+// value (each pairing adds x + y and y + x, which round alike), and every thread adds the 16 wave sums in wave order.  scr: [32] floats
+// that no thread reads past the leading barrier
+__device__ __forceinline__ void block_sum2(float& a, float& b, float* scr) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) { a += __shfl_xor(a, off); b += __shfl_xor(b, off); }
+    __syncthreads();
+    if (lane == 0) { scr[wave] = a; scr[16 + wave] = b; }
+    __syncthreads();
+    a = 0.f; b = 0.f;
+#pragma unroll
+    for (int w = 0; w < kSampThreads / 64; ++w) { a += scr[w]; b += scr[16 + w]; }
+}
+
+__device__ __forceinline__ float block_max(float v, float* scr) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
+    __syncthreads();
+    if (lane == 0) scr[wave] = v;
+    __syncthreads();
+    v = -INFINITY;
+#pragma unroll
+    for (int w = 0; w < kSampThreads / 64; ++w) v = fmaxf(v, scr[w]);
+    return v;
+}
+
+// softmax mass (.x) and entropy (.y) of the survivors (k0, k1) of this thread's pair (s0, s1); m = the largest surviving score.
+// HF's log_softmax / Categorical(logits).entropy() arithmetic: logp = (s - m) - log Z, H = -sum p logp
+__device__ __forceinline__ float2 survivor_entropy(float s0, float s1, bool k0, bool k1, float m, float* scr) {
+    const float e0 = k0 ? expf(s0 - m) : 0.f, e1 = k1 ? expf(s1 - m) : 0.f;
+    float Z = e0 + e1, unused = 0.f;
+    block_sum2(Z, unused, scr);
+    const float lZ = logf(Z);
+    float h = 0.f;
+    if (k0) h -= (e0 / Z) * ((s0 - m) - lZ);
+    if (k1) h -= (e1 / Z) * ((s1 - m) - lZ);
+    block_sum2(h, unused, scr);
+    return make_float2(Z, h);
+}
+
+// TypicalLogitsWarper -> EpsilonLogitsWarper -> EtaLogitsWarper (transformers' order) on the survivors k0 / k1 of this thread's pair
+// (s0, s1); m: the largest surviving score; scr: [32] floats.  Returns the largest score that survives them (typical may drop the
+// argmax; the cutoffs never drop it).  Every sum is a fixed-order workgroup sum: the same row, key and settings keep the same ids on
+// every run.
+__device__ float apply_warpers(const gvc_logits_warpers& W, float s0, float s1, bool& k0, bool& k1, float m, float* scr) {
+    if (W.typical_p > 0.f) {
+        const float2 zh = survivor_entropy(s0, s1, k0, k1, m, scr);
+        const float lZ = logf(zh.x), H = zh.y;
+        // key = |-logp - H| >= 0: its bit pattern orders like its value.  T = the smallest key value at which the mass of ids with
+        // key <= T reaches typical_p (HF's sort / cumsum / last_ind), found bit by bit from the top: one fixed-order workgroup sum of
+        // the mass at or below a candidate per bit (a radix select of radix 2 weighted by mass; radix 4 -- 16 digits of three sums --
+        // measured slower)
+        const float p0 = k0 ? expf(s0 - m) / zh.x : 0.f, p1 = k1 ? expf(s1 - m) / zh.x : 0.f;
+        const uint32_t kb0 = k0 ? __float_as_uint(fabsf(-((s0 - m) - lZ) - H)) : 0xffffffffu;
+        const uint32_t kb1 = k1 ? __float_as_uint(fabsf(-((s1 - m) - lZ) - H)) : 0xffffffffu;
+        // One barrier per bit: the wave sums alternate between the two halves of scr, so a half is rewritten only after the barrier
+        // of the next bit, which every thread passes once it has read that half
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+        uint32_t T = 0;
+        __syncthreads();                                         // (scr: survivor_entropy's last sum may still be read)
+        for (int bit = 30; bit >= 0; --bit) {
+            const uint32_t cand = T | ((1u << bit) - 1u);       // T so far, this bit clear, every lower bit set
+            float a = (kb0 <= cand ? p0 : 0.f) + (kb1 <= cand ? p1 : 0.f);
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) a += __shfl_xor(a, off);
+            float* half = scr + ((bit & 1) << 4);
+            if (lane == 0) half[wave] = a;
+            __syncthreads();
+            a = 0.f;
+#pragma unroll
+            for (int w = 0; w < kSampThreads / 64; ++w) a += half[w];
+            if (!(a >= W.typical_p)) T |= 1u << bit;            // (no key reaches the mass: T ends above every key, all stay)
+        }
+        k0 = k0 && kb0 <= T;
+        k1 = k1 && kb1 <= T;
+        m = block_max(fmaxf(k0 ? s0 : -INFINITY, k1 ? s1 : -INFINITY), scr);
+    }
+    if (W.epsilon_cutoff > 0.f) {
+        const float e0 = k0 ? expf(s0 - m) : 0.f, e1 = k1 ? expf(s1 - m) : 0.f;
+        float Z = e0 + e1, unused = 0.f;
+        block_sum2(Z, unused, scr);
+        if (k0 && e0 / Z < W.epsilon_cutoff && s0 < m) k0 = false;
+        if (k1 && e1 / Z < W.epsilon_cutoff && s1 < m) k1 = false;
+    }
+    if (W.eta_cutoff > 0.f) {
+        const float2 zh = survivor_entropy(s0, s1, k0, k1, m, scr);
+        const float eta = fminf(W.eta_cutoff, sqrtf(W.eta_cutoff) * expf(-zh.y));
+        if (k0 && expf(s0 - m) / zh.x < eta && s0 < m) k0 = false;
+        if (k1 && expf(s1 - m) / zh.x < eta && s1 < m) k1 = false;
+    }
+    return m;
+}
+
 __global__ __launch_bounds__(kSampThreads) void k_sample(SampleCall cv, const SampleCall* cp) {
     __shared__ float sc[kSortN];        // processed scores in vocabulary order
     __shared__ float srt[kSortN];       // descending sort of the scores
@@ -53,6 +148,7 @@ __global__ __launch_bounds__(kSampThreads) void k_sample(SampleCall cv, const Sa
     __shared__ float fscr[17];
     __shared__ int iscr[17];
     __shared__ double dscr[17];
+    __shared__ float wscr[32];
     __shared__ uint32_t kill[kProcWords];
     const SampleCall& C = cp ? *cp : cv;
     const int b = blockIdx.x, tid = threadIdx.x;
@@ -189,7 +285,13 @@ __global__ __launch_bounds__(kSampThreads) void k_sample(SampleCall cv, const Sa
                 if (k0 && expf(sc[i0v] - mx) < min_p) k0 = false;
                 if (k1 && expf(sc[i1v] - mx) < min_p) k1 = false;
             }
-            const double w0 = k0 ? (double)expf(sc[i0v] - mx) : 0.0, w1 = k1 ? (double)expf(sc[i1v] - mx) : 0.0;
+            // Typical / Epsilon / Eta (after MinP); off -- every field 0, or no warpers -- leaves the arithmetic as it was.  The
+            // weights are taken relative to the largest surviving score (typical may drop mx)
+            float dmx = mx;
+            const gvc_logits_warpers* W = row_warps(C, b);
+            if (W && (W->typical_p > 0.f || W->epsilon_cutoff > 0.f || W->eta_cutoff > 0.f))
+                dmx = apply_warpers(*W, i0v < V ? sc[i0v] : -INFINITY, i1v < V ? sc[i1v] : -INFINITY, k0, k1, mx, wscr);
+            const double w0 = k0 ? (double)expf(sc[i0v] - dmx) : 0.0, w1 = k1 ? (double)expf(sc[i1v] - dmx) : 0.0;
             double total;
             const double ex = block_scan_excl<double>(w0 + w1, dscr, &total);
             // the RNG counter is the position of the step in the whole run of the stream (i0 + step, or rng_step0 + step of a keyed
@@ -322,6 +424,10 @@ __global__ void k_stage_set_index(int32_t* dst, SetIndex src, int B) {
     if ((int)threadIdx.x < B) dst[threadIdx.x] = src.k[threadIdx.x];
 }
 
+__global__ void k_stage_warps(gvc_logits_warpers* dst, WarpTable t) {
+    if ((int)threadIdx.x < t.n) dst[threadIdx.x] = t.w[threadIdx.x];
+}
+
 int check_procs(const gvc_logits_processors& P, int vocab) {
     GVC_REQUIRE(vocab <= 32 * kProcWords, GVC_ERR_UNSUPPORTED, "processors: vocab %d > %d", vocab, 32 * kProcWords);
     GVC_REQUIRE(P.no_repeat_ngram_size >= 0 && P.no_repeat_ngram_size <= GVC_PROC_MAX_NGRAM, GVC_ERR_ARG,
@@ -404,6 +510,42 @@ int launch_stage_set_index(int32_t* dst, const int32_t* set_of_row, int B, hipSt
     memset(&si, 0, sizeof(si));
     memcpy(si.k, set_of_row, (size_t)B * sizeof(int32_t));
     hipLaunchKernelGGL(k_stage_set_index, dim3(1), dim3(kMaxSampleRows), 0, s, dst, si, B);
+    GVC_LAUNCH_CHECK();
+    return GVC_OK;
+}
+
+int check_warp_sets(const gvc_logits_processors* sets, const gvc_logits_warpers* warps, int n_sets, const int32_t* set_of_row, int B,
+                    int vocab) {
+    GVC_REQUIRE(B >= 1 && B <= kMaxSampleRows, GVC_ERR_ARG, "warpers: need 1..%d rows, got %d", kMaxSampleRows, B);
+    GVC_REQUIRE(n_sets >= 1 && n_sets <= B, GVC_ERR_ARG, "warpers: %d sets for %d rows (1..B)", n_sets, B);
+    if (set_of_row)
+        for (int b = 0; b < B; ++b)
+            GVC_REQUIRE(set_of_row[b] >= -1 && set_of_row[b] < n_sets, GVC_ERR_ARG, "warpers: row %d has set %d outside [-1, %d)", b,
+                        set_of_row[b], n_sets);
+    for (int k = 0; k < n_sets; ++k) {
+        if (sets) {
+            const int rc = check_procs(sets[k], vocab);
+            if (rc) return rc;
+        }
+        if (warps) {
+            const gvc_logits_warpers& w = warps[k];
+            const bool ok = [](float x) { return x == 0.f || (x > 0.f && x < 1.f); }(w.typical_p) &&
+                            [](float x) { return x == 0.f || (x > 0.f && x < 1.f); }(w.epsilon_cutoff) &&
+                            [](float x) { return x == 0.f || (x > 0.f && x < 1.f); }(w.eta_cutoff);
+            GVC_REQUIRE(ok && w.reserved == 0, GVC_ERR_ARG,
+                        "warpers: set %d has typical_p %g, epsilon_cutoff %g, eta_cutoff %g (each 0 = off or in (0, 1)), reserved %d", k,
+                        (double)w.typical_p, (double)w.epsilon_cutoff, (double)w.eta_cutoff, w.reserved);
+        }
+    }
+    return GVC_OK;
+}
+
+int launch_stage_warps(gvc_logits_warpers* dst, const gvc_logits_warpers* warps, int n_sets, hipStream_t s) {
+    WarpTable t;
+    memset(&t, 0, sizeof(t));
+    memcpy(t.w, warps, (size_t)n_sets * sizeof(gvc_logits_warpers));
+    t.n = n_sets;
+    hipLaunchKernelGGL(k_stage_warps, dim3(1), dim3(kMaxSampleRows), 0, s, dst, t);
     GVC_LAUNCH_CHECK();
     return GVC_OK;
 }
@@ -525,6 +667,47 @@ extern "C" int gvc_sample_proc_sets(const float* logits, int32_t B, int32_t* ids
         sc.logits = logits; sc.B = B; sc.ids = ids; sc.ids_stride = ids_stride; sc.ids_len = ids_len;
         sc.finished = finished; sc.p = *p; sc.step = step; sc.tok_out = tok_out; sc.rows = d_rows;
         sc.proc_sets = d_sets; sc.set_of_row = d_sor;
+        if (rows) sc.p.top_k = greedy ? 1 : 0;          // (kernel choice only: every row's settings come from d_rows)
+        rc = gvc::launch_sample(sc, s);
+    }
+    const hipError_t e = hipFreeAsync(d, s);
+    if (rc) return rc;
+    GVC_CHECK_HIP(e);
+    return GVC_OK;
+}
+
+extern "C" int gvc_sample_warp(const float* logits, int32_t B, int32_t* ids, int32_t ids_stride, int32_t* ids_len, int32_t* finished,
+                               const gvc_sample_params* p, const gvc_row_sampling* rows, const gvc_logits_processors* sets,
+                               const gvc_logits_warpers* warps, int32_t n_sets, const int32_t* set_of_row, int32_t step, int32_t* tok_out,
+                               gvc_stream sv) {
+    GVC_REQUIRE(logits && ids && ids_len && finished && p && tok_out && B >= 1, GVC_ERR_ARG, "gvc_sample_warp: bad argument");
+    int rc = gvc::check_warp_sets(sets, warps, n_sets, set_of_row, B, p->vocab);
+    if (rc) return rc;
+    bool greedy = p->top_k == 1;
+    if (rows && (rc = gvc::check_sample_rows(rows, B, p->vocab, &greedy))) return rc;
+    int32_t zeros[gvc::kMaxSampleRows] = {};
+    const int32_t* sor = set_of_row ? set_of_row : zeros;             // (null: every row uses entry 0)
+    hipStream_t s = (hipStream_t)sv;
+    // sets, warpers, rows and indices need device memory for the duration of this call only: stream-ordered, freed behind the launch
+    const size_t set_bytes = sets ? (size_t)n_sets * sizeof(gvc_logits_processors) : 0;
+    const size_t warp_bytes = warps ? (size_t)n_sets * sizeof(gvc_logits_warpers) : 0;
+    const size_t row_bytes = rows ? (size_t)B * sizeof(gvc_row_sampling) : 0;
+    char* d = nullptr;
+    GVC_CHECK_HIP(hipMallocAsync((void**)&d, set_bytes + warp_bytes + row_bytes + (size_t)B * sizeof(int32_t), s));
+    gvc_logits_processors* d_sets = sets ? reinterpret_cast<gvc_logits_processors*>(d) : nullptr;
+    gvc_logits_warpers* d_warps = warps ? reinterpret_cast<gvc_logits_warpers*>(d + set_bytes) : nullptr;
+    gvc_row_sampling* d_rows = rows ? reinterpret_cast<gvc_row_sampling*>(d + set_bytes + warp_bytes) : nullptr;
+    int32_t* d_sor = reinterpret_cast<int32_t*>(d + set_bytes + warp_bytes + row_bytes);
+    if (sets) rc = gvc::launch_stage_proc_sets(d_sets, sets, n_sets, sor, B, s);
+    if (rc == GVC_OK && warps) rc = gvc::launch_stage_warps(d_warps, warps, n_sets, s);
+    if (rc == GVC_OK) rc = gvc::launch_stage_set_index(d_sor, sor, B, s);
+    if (rc == GVC_OK && rows) rc = gvc::launch_stage_rows(d_rows, rows, B, s);
+    if (rc == GVC_OK) {
+        gvc::SampleCall sc;
+        memset(&sc, 0, sizeof(sc));
+        sc.logits = logits; sc.B = B; sc.ids = ids; sc.ids_stride = ids_stride; sc.ids_len = ids_len;
+        sc.finished = finished; sc.p = *p; sc.step = step; sc.tok_out = tok_out; sc.rows = d_rows;
+        sc.proc_sets = d_sets; sc.set_of_row = d_sor; sc.warps = d_warps;
         if (rows) sc.p.top_k = greedy ? 1 : 0;          // (kernel choice only: every row's settings come from d_rows)
         rc = gvc::launch_sample(sc, s);
     }

@@ -116,16 +116,60 @@ def logits_processors(kw, prompt_len, vocab, sampling=True, prompt_lens=None):
 MAX_SET_ROWS = 64      # kMaxSampleRows: rows of a call with per-row processor sets
 
 
+# HF generate kwargs of the entropy-aware sampling warpers (include/genvc_hip.h: gvc_logits_warpers), applied after min_p
+WARP_KWARGS = ("typical_p", "epsilon_cutoff", "eta_cutoff")
+
+
+def _warp_value(kw, name):
+    v = kw.get(name)
+    if v is None:
+        return None
+    if isinstance(v, bool):
+        raise ValueError(f"{name} must be a number, not {v!r}")
+    try:
+        return float(v)
+    except (TypeError, ValueError):
+        raise ValueError(f"{name} must be a number, not {v!r}") from None
+
+
+def logits_warpers(kw, sampling=True):
+    """the warper kwargs of one call (WARP_KWARGS) -> a gvc_logits_warpers, or None when every one is off or `sampling` is False (the
+    call then passes no warpers at all).  On / off follow transformers' _get_logits_processor: typical_p < 1 builds the warper, which
+    raises ValueError for typical_p <= 0; epsilon_cutoff and eta_cutoff act inside (0, 1) and are silently off outside it; with
+    do_sample=False none is built."""
+    typ, eps, eta = (_warp_value(kw, k) for k in WARP_KWARGS)
+    if not sampling:
+        return None
+    w = _lib.LogitsWarpers()
+    if typ is not None and typ < 1.0:
+        if not typ > 0.0:
+            raise ValueError(f"`typical_p` has to be a float > 0 and < 1, but is {typ}")
+        w.typical_p = typ
+    if eps is not None and 0.0 < eps < 1.0:
+        w.epsilon_cutoff = eps
+    if eta is not None and 0.0 < eta < 1.0:
+        w.eta_cutoff = eta
+    # an on value that rounds to 0 or 1 in float32 (0 is "off" on the device, 1 is out of range) stays just inside (0, 1)
+    for f, v in zip(WARP_KWARGS, (typ, eps, eta)):
+        if getattr(w, f) >= 1.0:
+            setattr(w, f, 1.0 - 2.0 ** -24)
+        elif getattr(w, f) == 0.0 and v is not None and 0.0 < v < 1.0:
+            setattr(w, f, 2.0 ** -126)
+    if not (w.typical_p or w.epsilon_cutoff or w.eta_cutoff):
+        return None
+    return w
+
+
 def check_proc_kwargs(kw, where):
-    """a per-row / per-group / per-job / per-session processor dict may hold PROC_KWARGS only: anything else raises ValueError naming
-    the key and `where` it came from"""
+    """a per-row / per-group / per-job / per-session processor dict may hold PROC_KWARGS and WARP_KWARGS only: anything else raises
+    ValueError naming the key and `where` it came from"""
     if kw is None:
         return
     if not isinstance(kw, dict):
         raise ValueError(f"{where}: processor kwargs must be a dict or None, not {type(kw).__name__}")
-    unknown = sorted(set(kw) - set(PROC_KWARGS))
+    unknown = sorted(set(kw) - set(PROC_KWARGS) - set(WARP_KWARGS))
     if unknown:
-        raise ValueError(f"{where}: {unknown[0]!r} is not a processor kwarg (allowed: {', '.join(PROC_KWARGS)})")
+        raise ValueError(f"{where}: {unknown[0]!r} is not a processor kwarg (allowed: {', '.join(PROC_KWARGS + WARP_KWARGS)})")
 
 
 def _kw_key(kw):
@@ -194,6 +238,60 @@ def logits_processor_sets(kws, prompt_len, vocab, sampling=True, prompt_lens=Non
     if not sets:
         return None
     return ProcessorSets(sets, index, prompt_lens)
+
+
+class WarperSets:
+    """per-row processor sets with warpers (include/genvc_hip.h: gvc_gpt_generate_warp): n_sets entries, each a gvc_logits_processors
+    (`sets` is None when no entry has one; an entry without one is the all-zero struct) paired with a gvc_logits_warpers, and
+    `set_of_row` (B int32 indices, -1 = neither), all host arrays.  `prompt_lens` keeps the caller's device tensor alive."""
+
+    def __init__(self, procs, warps, set_of_row, prompt_lens=None):
+        self.n_sets = len(warps)
+        self.sets = None
+        if any(p is not None for p in procs):
+            self.sets = (_lib.LogitsProcessors * self.n_sets)(*[_lib.LogitsProcessors() if p is None else p for p in procs])
+        self.warps = (_lib.LogitsWarpers * self.n_sets)(*[_lib.LogitsWarpers() if w is None else w for w in warps])
+        self.set_of_row = (C.c_int32 * len(set_of_row))(*set_of_row)
+        self.prompt_lens = prompt_lens
+
+    @classmethod
+    def one(cls, proc, warp, B):
+        """one call-wide entry (proc may be None) for all B rows"""
+        if not 1 <= B <= MAX_SET_ROWS:
+            raise ValueError(f"the sampling warpers serve calls of 1..{MAX_SET_ROWS} rows, not {B}")
+        return cls([proc], [warp], [0] * B)
+
+    def __len__(self):
+        return len(self.set_of_row)
+
+
+def logits_sets(kws, prompt_len, vocab, sampling=True, prompt_lens=None):
+    """logits_processor_sets() whose per-row dicts may also hold WARP_KWARGS.  When no row has a warper on, this returns exactly what
+    logits_processor_sets() returns (a ProcessorSets or None); otherwise a WarperSets, rows with equal processors and warpers sharing
+    an entry.  Errors name the offending row."""
+    kws = list(kws)
+    ps = logits_processor_sets(kws, prompt_len, vocab, sampling=sampling, prompt_lens=prompt_lens)      # (validates every row)
+    warps = []
+    for b, kw in enumerate(kws):
+        try:
+            warps.append(logits_warpers(kw or {}, sampling))
+        except ValueError as e:
+            raise ValueError(f"row {b}: {e}") from None
+    if all(w is None for w in warps):
+        return ps
+    pidx = list(ps.set_of_row) if ps is not None else [-1] * len(kws)
+    by, procs, wl, index = {}, [], [], []
+    for b, w in enumerate(warps):
+        if pidx[b] < 0 and w is None:
+            index.append(-1)
+            continue
+        key = (pidx[b], None if w is None else C.string_at(C.addressof(w), C.sizeof(w)))
+        if key not in by:
+            by[key] = len(wl)
+            procs.append(ps.sets[pidx[b]] if pidx[b] >= 0 else None)
+            wl.append(w)
+        index.append(by[key])
+    return WarperSets(procs, wl, index, prompt_lens)
 
 
 BEAM_LENGTH_MODES = {"4.33": 0, "generated": 1}
@@ -468,6 +566,8 @@ class GptEngine:
     def sample_proc_sets(self, logits, ids, ids_len, finished, params, sets, step, rows=None):
         """sample_proc() with per-row processor sets (logits_processor_sets(); include/genvc_hip.h: gvc_sample_proc_sets): row b uses
         sets.sets[sets.set_of_row[b]], none for -1.  rows: as in sample_proc (then params carries eos / vocab only)"""
+        if isinstance(sets, WarperSets):
+            return self.sample_warp(logits, ids, ids_len, finished, params, sets, step, rows=rows)
         B = logits.shape[0]
         if len(sets) != B:
             raise ValueError(f"{len(sets)} set indices for {B} rows")
@@ -481,7 +581,11 @@ class GptEngine:
     def generate_proc_sets(self, slots, ids, ids_len, finished, params, sets, i0, n_steps, tokens_out, latents_out, max_keys=0, rows=None):
         """generate() (rows None: params for every row) or generate_rows() (rows set: params may be None) with per-row processor sets
         (logits_processor_sets(); include/genvc_hip.h: gvc_gpt_generate_proc_sets): row b uses sets.sets[sets.set_of_row[b]], none for
-        -1.  The sets travel with the call: the step graphs are generate()'s, and nothing is allocated or captured once warm."""
+        -1.  The sets travel with the call: the step graphs are generate()'s, and nothing is allocated or captured once warm.
+        A WarperSets (logits_sets()) goes to generate_warp()."""
+        if isinstance(sets, WarperSets):
+            return self.generate_warp(slots, ids, ids_len, finished, params, sets, i0, n_steps, tokens_out, latents_out, max_keys=max_keys,
+                                      rows=rows)
         self._join_side()
         B = slots.shape[0]
         if len(sets) != B:
@@ -499,6 +603,40 @@ class GptEngine:
                                                ptr(_i32(finished)), C.byref(params), arr, sets.sets, sets.n_sets, sets.set_of_row,
                                                int(i0), int(n_steps), int(max_keys), ptr(tokens_out), tokens_out.stride(0),
                                                ptr(latents_out), lat_stride, stream()), "generate_proc_sets")
+
+    def sample_warp(self, logits, ids, ids_len, finished, params, sets, step, rows=None):
+        """sample_proc_sets() with the typical / epsilon / eta warpers of a WarperSets (include/genvc_hip.h: gvc_sample_warp)"""
+        B = logits.shape[0]
+        if len(sets) != B:
+            raise ValueError(f"{len(sets)} set indices for {B} rows")
+        arr = _rows_arg(rows, B) if rows is not None else None
+        tok = torch.empty(B, device=logits.device, dtype=torch.int32)
+        check(lib().gvc_sample_warp(ptr(_f32(logits)), B, ptr(_i32(ids)), ids.shape[1], ptr(_i32(ids_len)), ptr(_i32(finished)),
+                                    C.byref(params), arr, sets.sets, sets.warps, sets.n_sets, sets.set_of_row, int(step), ptr(tok),
+                                    stream()), "sample_warp")
+        return tok
+
+    def generate_warp(self, slots, ids, ids_len, finished, params, sets, i0, n_steps, tokens_out, latents_out, max_keys=0, rows=None):
+        """generate_proc_sets() with the warpers of a WarperSets (logits_sets() / WarperSets.one(); include/genvc_hip.h:
+        gvc_gpt_generate_warp): row b uses entry sets.set_of_row[b], none for -1.  The warpers travel with the call in one staging
+        launch: the step graphs are generate()'s, and nothing is allocated or captured once warm."""
+        self._join_side()
+        B = slots.shape[0]
+        if len(sets) != B:
+            raise ValueError(f"{len(sets)} set indices for {B} rows")
+        arr = _rows_arg(rows, B) if rows is not None else None
+        assert tokens_out.is_cuda and tokens_out.dtype == torch.int32 and tokens_out.stride(1) == 1
+        lat_stride = 0
+        if latents_out is not None:
+            assert latents_out.is_cuda and latents_out.dtype == torch.float32 and latents_out.stride(2) == 1
+            assert latents_out.stride(1) == self.d and latents_out.stride(0) % self.d == 0
+            lat_stride = latents_out.stride(0) // self.d
+        if rows is not None:
+            params = sample_params(dict(repetition_penalty=1.0, temperature=1.0, top_p=1.0, top_k=0), self.V, self.dims["stop_audio_token"])
+        check(lib().gvc_gpt_generate_warp(self._h, ptr(_i32(slots)), B, ptr(_i32(ids)), ids.shape[1], ptr(_i32(ids_len)),
+                                          ptr(_i32(finished)), C.byref(params), arr, sets.sets, sets.warps, sets.n_sets, sets.set_of_row,
+                                          int(i0), int(n_steps), int(max_keys), ptr(tokens_out), tokens_out.stride(0), ptr(latents_out),
+                                          lat_stride, stream()), "generate_warp")
 
     def beam_generate(self, slots, beam, n_steps, max_keys=0):
         """n_steps steps of `beam` (a BeamSearch) on the device, continuing at beam.steps (include/genvc_hip.h: gvc_gpt_beam_generate):

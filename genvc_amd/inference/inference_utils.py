@@ -76,8 +76,8 @@ def synthesize_utt(genVC_mdl, src_wav, tgt_audio, seg_len=6.0, return_details=Fa
                    generate_kwargs=None):
     """non-streaming conversion, latent-level concatenation (reference :23-89).  num_beams = K > 1: every segment decodes with
     deterministic beam search (GPT.generate(num_beams=K, do_sample=False)); its latents come from the re-pass.
-    generate_kwargs: more GPT.generate kwargs (the logits processors: min_new_tokens, no_repeat_ngram_size, ...), merged into every
-    segment's call"""
+    generate_kwargs: more GPT.generate kwargs (the logits processors: min_new_tokens, no_repeat_ngram_size, ...; the
+    sampling warpers typical_p, epsilon_cutoff, eta_cutoff), merged into every segment's call"""
     m = genVC_mdl
     min_len = int(0.32 * m.content_sample_rate)
     src_wav = src_wav.to(m.device)

@@ -138,7 +138,7 @@ class GenVCModel(nn.Module):
         interpolation -> HiFi-GAN.  (The reference's 0-d collapse at exactly one non-stop token, SURVEY appendix B.9, is
         guarded: boolean indexing keeps the dimension.)  The latents are the decode loop's own unless `repass_latents=True`
         (inference_utils._segment_latents).  generate_kwargs (extension): more GPT.generate kwargs (the logits processors:
-        min_new_tokens, no_repeat_ngram_size, ...), merged over the ones above."""
+        min_new_tokens, no_repeat_ngram_size, ...; typical_p, epsilon_cutoff, eta_cutoff), merged over the ones above."""
         feat = self.content_extractor.extract_content_features(src_audio)
         codes = self.content_dvae.get_codebook_indices(feat.transpose(1, 2))
         kw = dict(do_sample=do_sample, top_p=top_p, top_k=top_k, temperature=temperature, num_beams=num_beams,

@@ -11,8 +11,8 @@ import torch
 from torch import nn
 
 from .._lib import GenvcHipError
-from ..engine import (BEAM_LENGTH_MODES, PROC_KWARGS, BeamSearch, GptEngine, check_proc_kwargs, logits_processor_sets, logits_processors,
-                      sample_params)
+from ..engine import (BEAM_LENGTH_MODES, PROC_KWARGS, WARP_KWARGS, BeamSearch, GptEngine, WarperSets, check_proc_kwargs, logits_processors,
+                      logits_sets, logits_warpers, sample_params)
 from .perceiver_encoder import PerceiverResampler
 
 
@@ -62,18 +62,20 @@ def _proc_arg(proc):
 
 
 def _per_item_procs(kw, item_kwargs, n, name, vocab):
-    """group_kwargs / job_kwargs: one processor dict (or None) per item, merged over the call-wide processor kwargs of `kw` -> the
-    merged dict of every item.  Keys other than PROC_KWARGS, a wrong count and malformed settings raise ValueError naming the item."""
+    """group_kwargs / job_kwargs: one processor dict (or None) per item, merged over the call-wide processor and warper kwargs of `kw`
+    -> the merged dict of every item.  Keys other than PROC_KWARGS / WARP_KWARGS, a wrong count and malformed settings raise
+    ValueError naming the item."""
     item_kwargs = list(item_kwargs)
     if len(item_kwargs) != n:
         raise ValueError(f"{name}: {len(item_kwargs)} processor dicts for {n} items")
-    base = {k: kw[k] for k in PROC_KWARGS if kw.get(k) is not None}
+    base = {k: kw[k] for k in PROC_KWARGS + WARP_KWARGS if kw.get(k) is not None}
     out = []
     for i, d in enumerate(item_kwargs):
         check_proc_kwargs(d, f"{name}[{i}]")
         m = dict(base, **(d or {}))
         try:
             logits_processors(m, 0, vocab)
+            logits_warpers(m, sampling=kw.get("do_sample", True))
         except ValueError as e:
             raise ValueError(f"{name}[{i}]: {e}") from None
         out.append(m)
@@ -255,6 +257,9 @@ class GPT(nn.Module):
         st["params"] = sample_params(samp, self.num_audio_tokens, self.stop_audio_token, kw.get("seed", 0))
         # length / repetition processors (HF kwargs, engine.PROC_KWARGS): the prompt is the fake ids
         st["proc"] = logits_processors(kw, n0, self.num_audio_tokens, sampling=kw.get("do_sample", True))
+        # typical / epsilon / eta warpers (engine.WARP_KWARGS): with any on, the call carries them with its processors as one entry
+        warp = logits_warpers(kw, sampling=kw.get("do_sample", True))
+        st["warp"] = None if warp is None else WarperSets.one(st["proc"], warp, B)
         # `cached_cond_rows` (extension): the leading rows of the prefix -- the conditioning latents, identical for every
         # segment of an utterance -- are still in the KV cache from the previous segment's prefill of these slots
         self.engine.prefill(slots, self._prefix, want_outputs=False, n_cached=int(kw.get("cached_cond_rows", 0)))
@@ -266,8 +271,12 @@ class GPT(nn.Module):
         if n > 0:
             # the cache holds n0 positions after the prefill and one more per step: the library picks its decode kernels for the
             # context length this call reaches (not for the 602-token cap the ids rows are sized for)
-            self.engine.generate(st["slots"], st["ids"], st["ids_len"], st["finished"], st["params"], st["done"], n,
-                                 st["toks"], st["lats"], max_keys=st["n0"] + st["done"] + n, **_proc_arg(st["proc"]))
+            if st["warp"] is not None:
+                self.engine.generate_warp(st["slots"], st["ids"], st["ids_len"], st["finished"], st["params"], st["warp"], st["done"], n,
+                                          st["toks"], st["lats"], max_keys=st["n0"] + st["done"] + n)
+            else:
+                self.engine.generate(st["slots"], st["ids"], st["ids_len"], st["finished"], st["params"], st["done"], n,
+                                     st["toks"], st["lats"], max_keys=st["n0"] + st["done"] + n, **_proc_arg(st["proc"]))
             st["done"] += n
         end = bool(st["finished"].all().item()) or st["done"] >= st["max_new"]
         self.engine.health()          # (the .item() above synchronised: a hand-off timeout of these steps surfaces here, not a call later)
@@ -354,9 +363,10 @@ class GPT(nn.Module):
         `max_new_tokens` may be a list with one budget per group (benchmark mode: synthetic weights seldom stop, SURVEY.md 8d fixes
         the tokens of a segment by its duration): a group whose budget is spent leaves the joint decode, and the steps that remain
         run over the live streams only (fewer rows per step: the 8-row instead of the 16-row one-launch step for configs[2]'s tail).
-        `group_kwargs` (one dict or None per group): each group's own logits processors (PROC_KWARGS only), merged over the call-wide
-        ones -- the reference runs one HF generate per segment, so they may differ between groups; each group then gets what
-        generate(**its merged kwargs) returns for it, the joint decode giving every row its group's set (gvc_gpt_generate_proc_sets).
+        `group_kwargs` (one dict or None per group): each group's own logits processors and warpers (PROC_KWARGS, WARP_KWARGS), merged
+        over the call-wide ones -- the reference runs one HF generate per segment, so they may differ between groups; each group then
+        gets what generate(**its merged kwargs) returns for it, the joint decode giving every row its group's set
+        (gvc_gpt_generate_proc_sets, or gvc_gpt_generate_warp when a warper is on).
         Returns a list of int64 [B_i, n_i] (reference gpt.py:594-609 per group)."""
         _no_beams(generate_kwargs, "grouped (generate_groups)")
         kw = dict(generate_kwargs)
@@ -416,6 +426,9 @@ class GPT(nn.Module):
         groups = [groups[i] for i in order]
         seeds = [seeds[i] for i in order] if seeds is not None else None
         gkw = [gkw[i] for i in order] if gkw is not None else None
+        if gkw is None and seeds is not None and logits_warpers(kw) is not None:
+            # call-wide warpers: every group carries the call's processor and warper kwargs, one shared entry (logits_sets)
+            gkw = _per_item_procs(kw, [None] * len(groups), len(groups), "generate_kwargs", self.num_audio_tokens)
         gb = [budgets[i] if budgets else max_new for i in order]
         prefixes = [self.engine.prefix_embeddings(c.to(torch.float32).contiguous(), t.to(torch.int32).contiguous()) for c, t in groups]
         n0s = [int(p.shape[1]) + 1 for p in prefixes]
@@ -453,9 +466,9 @@ class GPT(nn.Module):
             # group_kwargs: every row its group's set, counted from its group's prompt (None: no row has a processor)
             sets = None
             if gkw is not None:
-                sets = logits_processor_sets([gkw[g] for g in live_groups for _ in range(spans[g][1] - spans[g][0])],
-                                             [n0s[g] for g in live_groups for _ in range(spans[g][1] - spans[g][0])],
-                                             self.num_audio_tokens, sampling=seeds is not None)
+                sets = logits_sets([gkw[g] for g in live_groups for _ in range(spans[g][1] - spans[g][0])],
+                                   [n0s[g] for g in live_groups for _ in range(spans[g][1] - spans[g][0])],
+                                   self.num_audio_tokens, sampling=seeds is not None)
             if sets is not None:
                 rows = None
                 if seeds is not None:
@@ -500,9 +513,9 @@ class GPT(nn.Module):
         job j draws what generate(c_j, t_j, seed=job_seeds[j]) draws from the same logits, whatever it shares the decode step with (the
         rows step's logits themselves are not bit-identical across row counts: JOINT_SAMPLING_DEFAULT).  Without job_seeds a sampling
         call raises NotImplementedError.
-        `job_kwargs` (one dict or None per job): each job's own logits processors (PROC_KWARGS only), merged over the call-wide ones;
-        job j then gets what generate(c_j, t_j, **its merged kwargs) returns (seed=job_seeds[j] when sampling), each row of a decode
-        call carrying its job's set (gvc_gpt_generate_proc_sets)."""
+        `job_kwargs` (one dict or None per job): each job's own logits processors and warpers (PROC_KWARGS, WARP_KWARGS), merged over
+        the call-wide ones; job j then gets what generate(c_j, t_j, **its merged kwargs) returns (seed=job_seeds[j] when sampling), each
+        row of a decode call carrying its job's set (gvc_gpt_generate_proc_sets, or gvc_gpt_generate_warp when a warper is on)."""
         _no_beams(generate_kwargs, "rolling (generate_rolling)")
         kw = dict(generate_kwargs)
         jkw = None
@@ -538,6 +551,9 @@ class GPT(nn.Module):
 
     def _rolling(self, jobs, kw, budgets, group, n0s, width, S, seeds=None, jkw=None):
         dev = jobs[0][1].device
+        if jkw is None and seeds is not None and logits_warpers(kw) is not None:
+            # call-wide warpers: every job carries the call's processor and warper kwargs, one shared entry (logits_sets)
+            jkw = _per_item_procs(kw, [None] * len(jobs), len(jobs), "generate_kwargs", self.num_audio_tokens)
         eng = self.engine
         stop = self.stop_audio_token
         ids_all = torch.ones(S, width, device=dev, dtype=torch.int32)
@@ -582,8 +598,8 @@ class GPT(nn.Module):
             proc = sets = None
             if jkw is not None:
                 # job_kwargs: every row its job's set, counted from its job's prompt (None: no row has a processor)
-                sets = logits_processor_sets([jkw[j["job"]] for j in live for _ in j["alive"]], [j["n0"] for j in live for _ in j["alive"]],
-                                             self.num_audio_tokens, sampling=seeds is not None)
+                sets = logits_sets([jkw[j["job"]] for j in live for _ in j["alive"]], [j["n0"] for j in live for _ in j["alive"]],
+                                   self.num_audio_tokens, sampling=seeds is not None)
             elif _any_proc(kw):
                 plens = torch.tensor([j["n0"] for j in live for _ in j["alive"]], dtype=torch.int32).to(dev)
                 proc = logits_processors(kw, 0, self.num_audio_tokens, sampling=seeds is not None, prompt_lens=plens)

@@ -33,14 +33,16 @@ Logits processors (PROC_KWARGS: no_repeat_ngram_size, min_new_tokens, suppress_t
 sets a scheduler-wide default and `open(ref_audio, generate_kwargs={...})` a session's own, merged over it, with or without
 per_session_sampling.  Every decode call gives each session's row its own set (gvc_gpt_generate_proc_sets), counted from the prompt of
 the segment it is decoding, so a session gets the tokens of its solo `synthesize_utt_streaming(generate_kwargs=...)` whoever shares its
-steps; a call in which no session has a processor passes no sets at all.
+steps; a call in which no session has a processor passes no sets at all.  The sampling warpers (WARP_KWARGS: typical_p,
+epsilon_cutoff, eta_cutoff) go in the same dicts; a call in which some session has one on carries them with the sets
+(gvc_gpt_generate_warp).
 """
 import time
 
 import torch
 
 from .inference.inference_utils import _sampling_kwargs, _vocode, handle_chunks
-from .engine import check_proc_kwargs, logits_processor_sets, logits_processors, sample_params
+from .engine import check_proc_kwargs, logits_processors, logits_sets, logits_warpers, sample_params
 from ._lib import GenvcHipError
 
 
@@ -99,11 +101,13 @@ class StreamSessions:
 
     # ------------------------------------------------------------------------------------------
     def _procs(self, kw, base, where):
-        """a processor dict (PROC_KWARGS only) merged over `base`, validated -> the merged dict, or None when it is empty"""
+        """a processor dict (PROC_KWARGS and WARP_KWARGS only) merged over `base`, validated -> the merged dict, or None when it is
+        empty"""
         check_proc_kwargs(kw, where)
         m = dict(base, **{k: v for k, v in (kw or {}).items() if v is not None})
         try:
             logits_processors(m, 0, self.m.gpt.num_audio_tokens)
+            logits_warpers(m)
         except ValueError as e:
             raise ValueError(f"{where}: {e}") from None
         return m or None
@@ -112,7 +116,8 @@ class StreamSessions:
     def open(self, ref_audio, sampling=None, seed=0, generate_kwargs=None):
         """ref_audio [1, n] at the model rate -> session id.  With per_session_sampling: `sampling` (top_k, top_p, temperature,
         repetition_penalty; missing keys come from the model config) and `seed` are this session's own; otherwise passing either raises.
-        `generate_kwargs`: the session's logits processors (PROC_KWARGS only), merged over the scheduler's default; any other key raises."""
+        `generate_kwargs`: the session's logits processors and warpers (PROC_KWARGS, WARP_KWARGS), merged over the scheduler's default;
+        any other key raises."""
         if not self.per_session_sampling and (sampling is not None or seed != 0):
             raise ValueError("open(sampling=..., seed=...) needs StreamSessions(..., per_session_sampling=True): this scheduler samples "
                              "every session with the model config's settings")
@@ -300,7 +305,7 @@ class StreamSessions:
         # each session's processors, counted from the prompt of the segment it decodes (None when no session has any: no sets at all)
         sets = None
         if any(s.procs for _, s in act):
-            sets = logits_processor_sets([s.procs for _, s in act], [s.p1 for _, s in act], m.gpt.num_audio_tokens)
+            sets = logits_sets([s.procs for _, s in act], [s.p1 for _, s in act], m.gpt.num_audio_tokens)
         if self.per_session_sampling:
             # each session's row keyed by its own stream: (its seed, row 0 of a lone stream, tokens of this segment drawn so far)
             rows = [dict(s.sampling, seed=s.seed, rng_row=0, rng_step0=s.done) for _, s in act]

@@ -351,6 +351,40 @@ int gvc_gpt_generate_proc_sets(gvc_gpt* ctx, const int32_t* slots, int32_t B, in
                                int32_t max_keys, int32_t* tokens_out, int32_t tok_stride, float* latents_out, int32_t lat_stride,
                                gvc_stream s);
 
+/* ------------------------------------------------------------------------------------------
+ * Entropy-aware sampling warpers (HF typical_p, epsilon_cutoff, eta_cutoff), applied by the sampling kernel after min_p and before
+ * the draw, in that order, each to the scores the previous step left (masked ids are -inf; p = softmax over the survivors):
+ *   typical_p m: logp = log_softmax(s), H = -sum p logp, key = |-logp - H|.  T = the smallest key whose ids with key <= T hold mass
+ *                >= m (the largest key if none does); every id with key <= T stays, ties included.  May drop the argmax.
+ *   epsilon_cutoff e: ids with p < e are dropped, except those whose score equals the largest surviving score.
+ *   eta_cutoff e: H = the survivors' entropy; the epsilon rule with min(e, sqrt(e) * exp(-H)).
+ * 0 is "off" for each; on values lie in (0, 1) (HF: typical_p >= 1 and cutoffs outside (0, 1) are off, typical_p <= 0 raises: the
+ * caller maps those).  An all-zero struct computes exactly what the call without it computes.  The argmax sampler (top_k == 1 rows,
+ * every greedy call) and beams never read them: one candidate is left, and every warper keeps one.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct gvc_logits_warpers {
+    float typical_p;                    /* 0 off, else in (0, 1) */
+    float epsilon_cutoff;               /* 0 off, else in (0, 1) */
+    float eta_cutoff;                   /* 0 off, else in (0, 1) */
+    int32_t reserved;                   /* 0 */
+} gvc_logits_warpers;
+
+/* Processor sets with warpers: row b uses sets[set_of_row[b]] and warps[set_of_row[b]], neither when the index is -1.  sets (nullable:
+ * no processors for any row), warps (nullable: no warpers) and set_of_row (nullable: every row uses entry 0) are HOST arrays as in
+ * gvc_sample_proc_sets, n_sets entries each (1 <= n_sets <= B <= 64); a bad value is GVC_ERR_ARG.  With warps null these are
+ * gvc_sample_proc_sets / gvc_gpt_generate_proc_sets (sets null too: the calls without processors).  gvc_gpt_generate_warp stages the
+ * warpers into the device-resident call state in one launch of its own ahead of the call's first launch: the same captured step
+ * graphs, no allocation and no synchronisation per call.  Not on the beam path. */
+int gvc_sample_warp(const float* logits, int32_t B, int32_t* ids, int32_t ids_stride, int32_t* ids_len, int32_t* finished,
+                    const gvc_sample_params* p, const gvc_row_sampling* rows, const gvc_logits_processors* sets,
+                    const gvc_logits_warpers* warps, int32_t n_sets, const int32_t* set_of_row, int32_t step, int32_t* tok_out,
+                    gvc_stream s);
+int gvc_gpt_generate_warp(gvc_gpt* ctx, const int32_t* slots, int32_t B, int32_t* ids, int32_t ids_stride, int32_t* ids_len,
+                          int32_t* finished, const gvc_sample_params* p, const gvc_row_sampling* rows, const gvc_logits_processors* sets,
+                          const gvc_logits_warpers* warps, int32_t n_sets, const int32_t* set_of_row, int32_t i0, int32_t n_steps,
+                          int32_t max_keys, int32_t* tokens_out, int32_t tok_stride, float* latents_out, int32_t lat_stride,
+                          gvc_stream s);
+
 /* Which decode step the last gvc_gpt_generate call replayed (diagnostic): 0 none yet, 1 launch-per-phase with split-key attention,
  * 2 launch-per-phase with the fused short-context attention launch, 3 the one-launch step (one stream), 4 the MFMA rows path
  * (launch per phase: 17+ streams, or shapes the one-launch rows step does not serve), 5 the one-launch rows step (2..16 streams,

@@ -37,6 +37,9 @@ if __name__ == "__main__":
     parser.add_argument("--eos_decay", type=float, nargs=2, default=None, metavar=("START", "FACTOR"),
                         help="exponential_decay_length_penalty: from START new tokens on, the stop score grows by FACTOR per token")
     parser.add_argument("--min_p", type=float, default=None, help="min-p sampling cut-off in [0, 1]")
+    parser.add_argument("--typical_p", type=float, default=None, help="typical sampling mass in (0, 1] (1: off)")
+    parser.add_argument("--epsilon_cutoff", type=float, default=None, help="epsilon sampling cut-off in [0, 1) (0: off)")
+    parser.add_argument("--eta_cutoff", type=float, default=None, help="eta sampling cut-off in [0, 1) (0: off)")
     args = parser.parse_args()
     if args.num_beams < 1 or (args.streaming and args.num_beams != 1):
         raise SystemExit("--num_beams must be >= 1, and 1 with --streaming")
@@ -47,9 +50,18 @@ if __name__ == "__main__":
         if start != int(start):
             raise SystemExit(f"--eos_decay START must be an integer, not {start}")
         gen_kw["exponential_decay_length_penalty"] = (int(start), factor)
+    for k, lo_open, hi_open in (("typical_p", True, False), ("epsilon_cutoff", False, True), ("eta_cutoff", False, True)):
+        v = getattr(args, k)
+        if v is None:
+            continue
+        # (transformers ignores a cut-off outside (0, 1) and typical_p above 1 without a word: on the command line that is a typo)
+        if not ((v > 0.0 if lo_open else v >= 0.0) and (v < 1.0 if hi_open else v <= 1.0)):
+            raise SystemExit(f"bad warper flag: --{k} must be in {'(' if lo_open else '['}0, 1{')' if hi_open else ']'}, not {v}")
+        gen_kw[k] = v
     try:
-        from genvc_amd.engine import logits_processors
+        from genvc_amd.engine import logits_processors, logits_warpers
         logits_processors(gen_kw, 0, 1026)
+        logits_warpers(gen_kw)
     except ValueError as e:
         raise SystemExit(f"bad processor flag: {e}")
 
