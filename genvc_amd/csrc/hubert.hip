@@ -34,7 +34,9 @@ static __global__ void k_hb_repack_conv(const float* w, float* out, int Co, int 
     }
 }
 
-// layer 0: wav [B][T] -> y [B][T0][C] (raw conv), part [B][nchunk][C][2] = (sum, sum of squares) over the chunk
+// layer 0: wav [B][T] -> y [B][T0][C] (raw conv), part [B][nchunk][C][2] = (mean, M2) over the chunk.  The sums run on y - y[t0], the
+// chunk's first output: a DC-dominated input gives channels with |mean| / std in the hundreds, and a raw sum of squares would cancel
+// most of its bits in E[y^2] - mean^2
 static __global__ __launch_bounds__(256) void k_hb_conv0(const float* wav, const float* w, float* y, float* part, int T,
                                                         int T0, int C, int k, int stride) {
     extern __shared__ float xs[];
@@ -50,7 +52,7 @@ static __global__ __launch_bounds__(256) void k_hb_conv0(const float* wav, const
         float wr[16];
 #pragma unroll
         for (int j = 0; j < 16; ++j) wr[j] = j < k ? w[(size_t)c * k + j] : 0.f;
-        float s = 0.f, ss = 0.f;
+        float s = 0.f, ss = 0.f, a = 0.f;
         float* yo = y + ((size_t)b * T0 + t0) * C + c;
         for (int t = 0; t < nt; ++t) {
             float acc = 0.f;
@@ -58,14 +60,18 @@ static __global__ __launch_bounds__(256) void k_hb_conv0(const float* wav, const
             for (int j = 0; j < 16; ++j)
                 if (j < k) acc = fmaf(wr[j], xs[t * stride + j], acc);
             yo[(size_t)t * C] = acc;
-            s += acc; ss = fmaf(acc, acc, ss);
+            if (t == 0) a = acc;
+            const float dv = acc - a;
+            s += dv; ss = fmaf(dv, dv, ss);
         }
         float* po = part + (((size_t)b * gridDim.x + chunk) * C + c) * 2;
-        po[0] = s; po[1] = ss;
+        const float dm = s / (float)nt;
+        po[0] = a + dm; po[1] = fmaxf(ss - s * dm, 0.f);
     }
 }
 
-// GroupNorm(C groups over C channels) statistics: per (b, channel) over time; chunks combined in double.
+// GroupNorm(C groups over C channels) statistics: per (b, channel) over time; the chunks' (mean, M2) combined in double as
+// sum y = sum n_i m_i and sum y^2 = sum (M2_i + n_i m_i^2) (the cancellation in sum y^2 / T - mean^2 costs double's bits, not fp32's).
 // A workgroup owns 8 channels; 32 lanes per channel take every 32nd chunk (all their requests in flight at once) and combine with a
 // fixed-order shuffle tree (two workgroups walking the chunks serially took 9 us for a 1 s chunk: 7 dependent round trips).
 static __global__ __launch_bounds__(256) void k_hb_gn_stats(const float* part, float* stats, int nchunk, int T0, int C) {
@@ -79,7 +85,10 @@ static __global__ __launch_bounds__(256) void k_hb_gn_stats(const float* part, f
             pv[u] = *reinterpret_cast<const float2*>(part + (((size_t)b * nchunk + min(i0 + 32 * u, nchunk - 1)) * C + c) * 2);
 #pragma unroll
         for (int u = 0; u < 8; ++u)
-            if (i0 + 32 * u < nchunk) { s += (double)pv[u].x; ss += (double)pv[u].y; }
+            if (i0 + 32 * u < nchunk) {
+                const double n = (double)min(kC0Chunk, T0 - (i0 + 32 * u) * kC0Chunk), m = (double)pv[u].x;
+                s += n * m; ss += (double)pv[u].y + n * m * m;
+            }
     }
 #pragma unroll
     for (int o = 16; o >= 1; o >>= 1) { s += __shfl_xor(s, o, 32); ss += __shfl_xor(ss, o, 32); }

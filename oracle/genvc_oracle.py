@@ -241,7 +241,8 @@ def compute_embeddings(w, dims, cond_latents, codes):
 
 
 def _bf16(t):
-    return t.to(torch.bfloat16).to(torch.float32)
+    """round to bf16 (nearest even) and widen back to t's own dtype: a float64 run keeps the same rounding points"""
+    return t.to(torch.bfloat16).to(t.dtype)
 
 
 def _ln_fold_bf16(x, w, ln, proj):
@@ -286,7 +287,7 @@ def gpt_blocks(w, dims, x, cache=None):
         if dims.get("kv_bf16"):
             # the build's bf16 KV cache (include/genvc_hip.h: weight_dtype 2): every k and v is rounded to nearest even when
             # it enters the cache, and attention reads the cache for the new rows too
-            k, v = k.to(torch.bfloat16).to(torch.float32), v.to(torch.bfloat16).to(torch.float32)
+            k, v = _bf16(k), _bf16(v)
         if cache is not None:
             k = torch.cat([cache[l][0], k], dim=2)
             v = torch.cat([cache[l][1], v], dim=2)
