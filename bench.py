@@ -1,6 +1,6 @@
 """Headline benchmark of the GenVC codec-token generation hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
 
 N > 1 without a launcher (no WORLD_SIZE in the environment): bench.py runs itself in a child process under
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1` -- one rank per GPU over RCCL; it
@@ -21,7 +21,11 @@ fixed: round(1 s * 23.4375) = 23 tokens + the EOS step = 24 decode steps per chu
 N > 1: one process per GPU, utterances sharded by rank, no collective on the data path; the generated
 token ids are all-gathered (RCCL) inside the timed region.  value = utterances/s of the whole job.
 
-Extra legs, outside the K timed steps (their numbers are extra keys of the same JSON line):
+A plain run does only what that figure needs: it sets up (the model; on one GPU with one stream also GenVCModel.warmup()), runs the W warm-up and the K timed steps,
+writes --dump-outputs and prints the JSON line.  `--full` adds everything else, after the timed steps on the same workload (its numbers
+are extra keys of the same JSON line): first-chunk latency (`first_chunk_latency_ms`, also with a registered speaker), the dominant
+kernel's `roofline` and the per-kernel times, `stages_ms_per_utterance`, the cold-start probe (before the workload is built), the
+CPU baseline with `parity_in_bench`, and these legs:
   * `offline` (every rank): BASELINE configs[2] -- 64 synthetic 10 s utterances (segments 6 s + 4 s, 141 + 94 tokens, top_k=1)
     through parallel_offline.convert_offline: utterances sharded over the ranks, a FIXED micro-batch of 8 utterances per
     GPU, no collective while converting, ONE all_gather of the token ids at the end.  N = 1 also reports the fully batched
@@ -783,12 +787,19 @@ def config4_leg(wl, rank, world, dist, device, steps=3, parity=True):
             "parity": _guarded("config4 parity", lambda: config4_parity(c4)) if parity and rank == 0 else None}
 
 
+def warm_up_model(wl):
+    """GenVCModel.warmup() for the headline shape (include/genvc_hip.h: gvc_gpt_warmup): after it no call of an utterance allocates,
+    synchronises or captures a graph"""
+    wl.model.warmup(seg_len=CHUNK_SECONDS, streams=1, ref_seconds=REF_SECONDS, stream_chunk_size=GROUP, top_k=1, max_new_tokens=STEPS_PER_CHUNK)
+
+
 def cold_probe(device, rank, weights, max_slots):
     """First-chunk latency of the FIRST utterance after model_init (host clock from the call to the first vocoder chunk, device
     synchronised; inputs resident): once on a fresh model as it comes out of model_init, once on a fresh model after
     GenVCModel.warmup() (include/genvc_hip.h: gvc_gpt_warmup).  `gpt_lazy_inits_*`: allocations / device syncs / graph captures the
     GPT context did inside data-path calls of that first utterance (0 after the warm-up: SURVEY.md 8(b)(iii)).  Returns the numbers
-    and the warmed-up workload, which the rest of the bench goes on to use."""
+    and the warmed-up workload, which the rest of the bench goes on to use.  (--full only: a plain run builds the second workload
+    and warms it up, without the probes.)"""
     out = {}
     t0 = time.perf_counter()
     wl = Workload(device, rank, 1, weights, max_slots=8)
@@ -804,7 +815,7 @@ def cold_probe(device, rank, weights, max_slots):
     wl = Workload(device, rank, 1, weights, max_slots=max_slots)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    wl.model.warmup(seg_len=CHUNK_SECONDS, streams=1, ref_seconds=REF_SECONDS, stream_chunk_size=GROUP, top_k=1, max_new_tokens=STEPS_PER_CHUNK)
+    warm_up_model(wl)
     out["warmup_call_s"] = time.perf_counter() - t0
     t0 = time.perf_counter()
     wl.utterance(0, sync_first=True)
@@ -849,16 +860,146 @@ def self_launch(args):
     sys.exit(subprocess.run(cmd, env=env).returncode)
 
 
+def full_report(wl, args, world, device, cold, offline, config4, do_extra):
+    """--full, rank 0: the keys of the JSON line beyond the headline figure, measured after the timed steps on the same workload"""
+    # latency / per-stage numbers from one recorded utterance (device events on the launch stream)
+    wl.utterance(0, record=True)
+    torch.cuda.synchronize()
+    first_ms = wl.ev[0].elapsed_time(wl.ev[1])
+    utt_ms = wl.ev[0].elapsed_time(wl.ev[2])
+    wl.utterance(0, record=True, registered=True)
+    torch.cuda.synchronize()
+    first_registered_ms = wl.ev[0].elapsed_time(wl.ev[1])
+    # ---- roofline of the dominant kernel, measured live with HIP events on the launch stream (gvc_gpt_time_kernel) ----
+    S = wl.P + 1 + STEPS_PER_CHUNK // 2
+    tok = torch.zeros(1, device=device, dtype=torch.int32)
+    s1 = wl.slots[:1].contiguous()
+
+    def fresh():
+        wl.eng.prefill(s1, wl.eng.prefix_embeddings(wl.model.get_gpt_cond_latents(wl.ref[0], 24000),
+                                                    torch.zeros(1, wl.Tc, device=device, dtype=torch.int32)), want_outputs=False)
+    reps = 40
+    wb = 4 if args.weights == "fp32" else 2
+    kvb = 2 if args.weights in ("bf16_kv", "bf16_act") else 4
+    fresh()
+    whole_us, _ = wl.eng.time_kernel(6, s1, tok, reps)          # launch-per-phase step (the fallback path; the bf16 contexts' path)
+    # which step the B = 1 generation loop really replays is the engine's to say (3 = the one-launch step): a device with fewer
+    # than 256 CUs, a failed LDS opt-in, GVC_PERSIST=0 or bf16 storage all leave it on the launch-per-phase step
+    probe_ids = torch.ones(1, wl.P + 1 + 16, device=device, dtype=torch.int32)
+    probe_ids[:, wl.P] = wl.dims["start_audio_token"]
+    fresh()
+    wl.eng.generate(s1, probe_ids, torch.full((1,), wl.P + 1, device=device, dtype=torch.int32), torch.zeros(1, device=device, dtype=torch.int32),
+                    wl.sp, 0, 2, torch.zeros(1, 2, device=device, dtype=torch.int32), torch.zeros(1, 2, wl.dims["d_model"], device=device),
+                    max_keys=wl.P + 4)
+    torch.cuda.synchronize()
+    one_launch = wl.eng.decode_variant() == 3
+    kern = []
+    if one_launch:
+        # the one-stream decode step is ONE launch (csrc/persist_kernel.h) = 80 % of the utterance: it IS the dominant kernel.
+        # `reps` launches replayed from a graph between two events; the context grows from wl.P + 1 by one position per launch
+        fresh()
+        step_us, n = wl.eng.time_kernel(7, s1, tok, 24)
+        s_mid = wl.P + 1 + 12
+        kern.append({"kernel": f"k_decode_persist<{wl.dims['d_model'] // 256}> (whole decode step of one stream, one launch; instantiation "
+                               f"<{wl.dims['d_model'] // 256}, {int(wb == 2)}, {int(kvb == 2)}, XL>: the MLP's hidden units stay inside their XCD at d_model 1024)", "avg_us": step_us,
+                     "launches_per_step": 1, "bytes": step_bytes(wl.dims, s_mid, wb, kvb)})
+        dom = 0
+    else:
+        # whole step and the step without each class, replayed back to back: in-situ cost of a class = (whole - without) /
+        # launches.  (Single-kernel event pairs are useless at 5 us; a class launched alone re-reads its own stale inputs
+        # from L2 and looks 5-12 % faster than rocprofv3 sees it in the step.)
+        for which in range(6):
+            per_step = 1 if which == 5 else wl.dims["n_layer"]
+            fresh()
+            iso, n = wl.eng.time_kernel(which, s1, tok, 128 if which == 5 else 32)
+            if n == 0:
+                continue
+            fresh()
+            without_us, _ = wl.eng.time_kernel(16 + which, s1, tok, reps)
+            kern.append({"kernel": KERNEL_NAMES[which], "avg_us": (whole_us - without_us) / per_step, "avg_us_launched_alone": iso,
+                         "launches_per_step": per_step, "bytes": kernel_bytes(wl.dims, which, S, wb, kvb)})
+        # dominant = the weight-streaming GEMV with the largest share of the step
+        cand = [i for i, k in enumerate(kern) if "gemv" in k["kernel"] and "head" not in k["kernel"]]
+        dom = max(cand, key=lambda i: kern[i]["avg_us"] * kern[i]["launches_per_step"])
+    achieved = kern[dom]["bytes"] / (kern[dom]["avg_us"] * 1e-6) / 1e9
+    traffic, traffic_source = None, None
+    pmc = os.path.join(ROOT, "profiles", "pmc_traffic.json")
+    if os.path.exists(pmc) and args.weights == "fp32":      # the PMC passes were taken on the fp32 build
+        tj = json.load(open(pmc))
+        key = kern[dom]["kernel"].split(" ")[0]
+        if key in tj:
+            traffic = tj[key]
+            traffic_source = ("imported from profiles/pmc_traffic.json (a separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE run of this kernel, "
+                              + tj.get("_source_" + key, "see the file's notes") + "); `achieved` / `frac` are this run's timing")
+    out = {
+        "first_chunk_latency_ms": first_ms,
+        "first_chunk_latency_window": "device events, inputs resident in HBM (the harness-level window with the host->device "
+                                      "copies inside is `harness.first_chunk_latency_ms`)",
+        "ms_per_utterance_device": utt_ms,
+        "first_chunk_latency_ms_registered_speaker": first_registered_ms,
+        "first_chunk_latency_ms_registered_speaker_note": "a streaming session whose target speaker was registered before the source arrives "
+                                                          "(conditioning latents + gvc_gpt_prefill_cond outside the window: StreamSessions.open); the reference's window, "
+                                                          "`first_chunk_latency_ms`, starts before the conditioning latents (inference_utils.py:148-154)",
+        "roofline": {"bound": "hbm", "kernel": kern[dom]["kernel"], "achieved": achieved, "peak": HBM_PEAK_GBS,
+                     "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source,
+                     "bytes_per_launch": kern[dom]["bytes"], "avg_us": kern[dom]["avg_us"],
+                     "decode_step_us": kern[dom]["avg_us"] if one_launch else whole_us,
+                     "decode_step_us_launch_per_phase": whole_us},
+        "kernels": kern,
+    }
+    out["stages_ms_per_utterance"] = _guarded("stage_times", lambda: stage_times(wl))
+    if offline is not None:
+        out["offline"] = offline
+        out["offline_utts_per_s"] = offline["offline_utts_per_s"]
+    if config4 is not None:
+        out["config4"] = config4
+    if do_extra:
+        out["prefill_5x110"] = _guarded("prefill_5x110", lambda: prefill_leg(wl))
+    headline = args.streams == 1
+    if headline and not args.no_harness:
+        out["harness"] = _guarded("harness", lambda: harness_leg(wl))
+    if cold is not None:
+        out["cold_start"] = cold
+        out["cold_first_chunk_latency_ms"] = cold["cold_first_chunk_latency_ms"]
+    if world == 1 and not args.no_cpu_baseline:
+        gpu = None
+        if headline:                        # the ids of utterance 0 (src[0], ref[0]) from the timed path, for parity_in_bench
+            wl.keep_codes = []
+            g_toks = wl.utterance(0)[0].clone()
+            torch.cuda.synchronize()
+            gpu = (g_toks.cpu(), wl.keep_codes)
+            wl.keep_codes = None
+        cb = _guarded("cpu_baseline", lambda: cpu_baseline(wl, gpu=gpu))
+        out["parity_in_bench"] = cb.pop("parity", None)
+        out["cpu_baseline"] = cb
+    if do_extra:
+        # BASELINE configs[3]: bf16 weights + KV cache + bf16 activations across the rows step's hand-offs (weight_dtype 3), with its parity
+        # block; beside it the same leg with fp32 activations (weight_dtype 2: what this key measured up to round 5)
+        def both():
+            leg = streams_leg(device, 0, weights="bf16_act", parity=not args.no_cpu_baseline)
+            ref2 = streams_leg(device, 0, weights="bf16_kv", parity=False)
+            leg["fp32_activations_bf16_kv"] = {k: ref2[k] for k in ("utts_per_s", "decode_step_us", "first_chunk_latency_ms", "decode_variant")}
+            leg["fp32_activations_bf16_kv"]["roofline_frac"] = ref2["roofline"]["frac"]
+            return leg
+        out["streams8_bf16_kv"] = _guarded("streams8_bf16_kv", both)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=_positive, default=8, help="timed steps (utterances per GPU); ms_per_step = their mean")
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline figure, also measure and check everything else: first-chunk latency, roofline and per-kernel "
+                         "times, per-stage times, the cold-start probe, the offline / harness / configs[3] / configs[4] / prefill legs, the "
+                         "CPU baseline and the parity blocks (the --no-* options below skip parts of it)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-offline", action="store_true", help="skip the batched-offline leg (BASELINE configs[2])")
     ap.add_argument("--no-harness", action="store_true", help="skip the harness-level leg")
     ap.add_argument("--no-extra", action="store_true", help="skip the configs[3] / configs[4] / prefill legs")
-    ap.add_argument("--no-cold", action="store_true", help="skip the cold-start probe (first utterance after model_init, with / without warm-up)")
+    ap.add_argument("--no-cold", action="store_true", help="skip the cold-start probe (first utterance after model_init, with / without warm-up) "
+                                                           "and the GenVCModel.warmup() call ahead of the warm-up steps")
     ap.add_argument("--streams", type=int, default=1, help="concurrent streams per GPU (1 = headline configuration)")
     ap.add_argument("--weights", default="fp32", choices=["fp32", "bf16", "bf16_kv", "bf16_act"],
                     help="GPT weight / KV-cache storage (fp32 = headline configuration; bf16_kv with --streams 8 = BASELINE configs[3])")
@@ -895,14 +1036,20 @@ def main():
             dist.init_process_group(backend)
 
     headline = args.streams == 1
-    do_offline = headline and not args.no_offline and args.weights == "fp32"
+    offline_sized = headline and not args.no_offline and args.weights == "fp32"
+    do_offline = args.full and offline_sized
     # KV slots: a micro-batch of OFFLINE_MICRO_BATCH utterances is OFFLINE_SEGMENTS segment-streams per utterance decoded JOINTLY
     # (layers/gpt.py generate_groups), so every rank needs that many slots whatever the world size -- the per-rank path at N > 1
-    # must be the one N = 1 is measured on; N = 1 also runs the fully batched figure (one class of OFFLINE_UTTS streams at a time)
-    slots_needed = max(16, OFFLINE_SEGMENTS * OFFLINE_MICRO_BATCH, OFFLINE_UTTS if (do_offline and world == 1) else 0)
+    # must be the one N = 1 is measured on; N = 1 also runs the fully batched figure (one class of OFFLINE_UTTS streams at a time).
+    # Sized so with or without --full: a plain run times the very context a --full run times
+    slots_needed = max(16, OFFLINE_SEGMENTS * OFFLINE_MICRO_BATCH, OFFLINE_UTTS if (offline_sized and world == 1) else 0)
     cold = None
     if world == 1 and headline and not args.no_cold:
-        cold, wl = cold_probe(device, rank, args.weights, slots_needed)
+        if args.full:
+            cold, wl = cold_probe(device, rank, args.weights, slots_needed)
+        else:                                     # the workload cold_probe hands on, without the probes
+            wl = Workload(device, rank, 1, args.weights, max_slots=slots_needed)
+            warm_up_model(wl)
     else:
         wl = Workload(device, rank, args.streams, args.weights, max_slots=slots_needed)
     wl.keep_wav = bool(args.dump_outputs)        # on for the warm-up too: the timed steps allocate as the warm-up did
@@ -933,7 +1080,7 @@ def main():
     wl.keep_wav, wl.wav_chunks = False, []
 
     offline = offline_leg(wl, rank, world, dist, device) if do_offline else None
-    do_extra = headline and args.weights == "fp32" and not args.no_extra
+    do_extra = args.full and headline and args.weights == "fp32" and not args.no_extra
     config4 = config4_leg(wl, rank, world, dist, device, parity=not args.no_cpu_baseline) if do_extra else None
     rccl_ranks = None
     if dist is not None:
@@ -951,75 +1098,6 @@ def main():
         dist.all_gather_object(device_uuids, my_uuid)
 
     if rank == 0:
-        # latency / per-stage numbers from one recorded utterance (device events on the launch stream)
-        wl.utterance(0, record=True)
-        torch.cuda.synchronize()
-        first_ms = wl.ev[0].elapsed_time(wl.ev[1])
-        utt_ms = wl.ev[0].elapsed_time(wl.ev[2])
-        wl.utterance(0, record=True, registered=True)
-        torch.cuda.synchronize()
-        first_registered_ms = wl.ev[0].elapsed_time(wl.ev[1])
-        # ---- roofline of the dominant kernel, measured live with HIP events on the launch stream (gvc_gpt_time_kernel) ----
-        S = wl.P + 1 + STEPS_PER_CHUNK // 2
-        tok = torch.zeros(1, device=device, dtype=torch.int32)
-        s1 = wl.slots[:1].contiguous()
-
-        def fresh():
-            wl.eng.prefill(s1, wl.eng.prefix_embeddings(wl.model.get_gpt_cond_latents(wl.ref[0], 24000),
-                                                        torch.zeros(1, wl.Tc, device=device, dtype=torch.int32)), want_outputs=False)
-        reps = 40
-        wb = 4 if args.weights == "fp32" else 2
-        kvb = 2 if args.weights in ("bf16_kv", "bf16_act") else 4
-        fresh()
-        whole_us, _ = wl.eng.time_kernel(6, s1, tok, reps)          # launch-per-phase step (the fallback path; the bf16 contexts' path)
-        # which step the B = 1 generation loop really replays is the engine's to say (3 = the one-launch step): a device with fewer
-        # than 256 CUs, a failed LDS opt-in, GVC_PERSIST=0 or bf16 storage all leave it on the launch-per-phase step
-        probe_ids = torch.ones(1, wl.P + 1 + 16, device=device, dtype=torch.int32)
-        probe_ids[:, wl.P] = wl.dims["start_audio_token"]
-        fresh()
-        wl.eng.generate(s1, probe_ids, torch.full((1,), wl.P + 1, device=device, dtype=torch.int32), torch.zeros(1, device=device, dtype=torch.int32),
-                        wl.sp, 0, 2, torch.zeros(1, 2, device=device, dtype=torch.int32), torch.zeros(1, 2, wl.dims["d_model"], device=device),
-                        max_keys=wl.P + 4)
-        torch.cuda.synchronize()
-        one_launch = wl.eng.decode_variant() == 3
-        kern = []
-        if one_launch:
-            # the one-stream decode step is ONE launch (csrc/persist_kernel.h) = 80 % of the utterance: it IS the dominant kernel.
-            # `reps` launches replayed from a graph between two events; the context grows from wl.P + 1 by one position per launch
-            fresh()
-            step_us, n = wl.eng.time_kernel(7, s1, tok, 24)
-            s_mid = wl.P + 1 + 12
-            kern.append({"kernel": f"k_decode_persist<{wl.dims['d_model'] // 256}> (whole decode step of one stream, one launch; instantiation "
-                                   f"<{wl.dims['d_model'] // 256}, {int(wb == 2)}, {int(kvb == 2)}, XL>: the MLP's hidden units stay inside their XCD at d_model 1024)", "avg_us": step_us,
-                         "launches_per_step": 1, "bytes": step_bytes(wl.dims, s_mid, wb, kvb)})
-            dom = 0
-        else:
-            # whole step and the step without each class, replayed back to back: in-situ cost of a class = (whole - without) /
-            # launches.  (Single-kernel event pairs are useless at 5 us; a class launched alone re-reads its own stale inputs
-            # from L2 and looks 5-12 % faster than rocprofv3 sees it in the step.)
-            for which in range(6):
-                per_step = 1 if which == 5 else wl.dims["n_layer"]
-                fresh()
-                iso, n = wl.eng.time_kernel(which, s1, tok, 128 if which == 5 else 32)
-                if n == 0:
-                    continue
-                fresh()
-                without_us, _ = wl.eng.time_kernel(16 + which, s1, tok, reps)
-                kern.append({"kernel": KERNEL_NAMES[which], "avg_us": (whole_us - without_us) / per_step, "avg_us_launched_alone": iso,
-                             "launches_per_step": per_step, "bytes": kernel_bytes(wl.dims, which, S, wb, kvb)})
-            # dominant = the weight-streaming GEMV with the largest share of the step
-            cand = [i for i, k in enumerate(kern) if "gemv" in k["kernel"] and "head" not in k["kernel"]]
-            dom = max(cand, key=lambda i: kern[i]["avg_us"] * kern[i]["launches_per_step"])
-        achieved = kern[dom]["bytes"] / (kern[dom]["avg_us"] * 1e-6) / 1e9
-        traffic, traffic_source = None, None
-        pmc = os.path.join(ROOT, "profiles", "pmc_traffic.json")
-        if os.path.exists(pmc) and args.weights == "fp32":      # the PMC passes were taken on the fp32 build
-            tj = json.load(open(pmc))
-            key = kern[dom]["kernel"].split(" ")[0]
-            if key in tj:
-                traffic = tj[key]
-                traffic_source = ("imported from profiles/pmc_traffic.json (a separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE run of this kernel, "
-                                  + tj.get("_source_" + key, "see the file's notes") + "); `achieved` / `frac` are this run's timing")
         n_utts = args.steps * world * args.streams
         ms_step = dt / args.steps * 1e3
         out = {
@@ -1030,14 +1108,7 @@ def main():
             "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": ms_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "f32" if args.weights == "fp32" else "bf16 storage, f32 arithmetic", "data": "synthetic", "weights": args.weights,
-            "rtf": (dt / args.steps) / SRC_SECONDS, "first_chunk_latency_ms": first_ms, "streams_per_gpu": args.streams,
-            "first_chunk_latency_window": "device events, inputs resident in HBM (the harness-level window with the host->device "
-                                          "copies inside is `harness.first_chunk_latency_ms`)",
-            "ms_per_utterance_device": utt_ms,
-            "first_chunk_latency_ms_registered_speaker": first_registered_ms,
-            "first_chunk_latency_ms_registered_speaker_note": "a streaming session whose target speaker was registered before the source arrives "
-                                                              "(conditioning latents + gvc_gpt_prefill_cond outside the window: StreamSessions.open); the reference's window, "
-                                                              "`first_chunk_latency_ms`, starts before the conditioning latents (inference_utils.py:148-154)",
+            "rtf": (dt / args.steps) / SRC_SECONDS, "streams_per_gpu": args.streams,
             "config": {"workload": ("GenVC_small streaming, 1 s chunks, top_k=1, batch 1 per GPU (BASELINE configs[1])" if args.streams == 1
                                     else f"GenVC_small streaming, 1 s chunks, top_k=1, {args.streams} concurrent streams per GPU stepped together "
                                          f"(BASELINE configs[3] shape, weights/KV: {args.weights}); one step = that many utterances"),
@@ -1046,49 +1117,12 @@ def main():
                        "per_chunk": f"ContentVec (HuBERT-base) + DVAE/VQ + prefill {wl.P + 1} rows (chunks after the first: {wl.P + 1 - 32} rows, the 32 conditioning rows stay cached) + {STEPS_PER_CHUNK} decode steps; HiFi-GAN vocoder every {GROUP} tokens",
                        "excluded_from_timed_path": [],
                        "parallelism": f"replicas x{world}, utterances sharded by rank, all_gather of token ids"},
-            "roofline": {"bound": "hbm", "kernel": kern[dom]["kernel"], "achieved": achieved, "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source,
-                         "bytes_per_launch": kern[dom]["bytes"], "avg_us": kern[dom]["avg_us"],
-                         "decode_step_us": kern[dom]["avg_us"] if one_launch else whole_us,
-                         "decode_step_us_launch_per_phase": whole_us},
-            "kernels": kern,
+            "full": args.full,
         }
         if dumped is not None:
             out["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped, "step": args.steps - 1}
-        out["stages_ms_per_utterance"] = _guarded("stage_times", lambda: stage_times(wl))
-        if offline is not None:
-            out["offline"] = offline
-            out["offline_utts_per_s"] = offline["offline_utts_per_s"]
-        if config4 is not None:
-            out["config4"] = config4
-        if do_extra and world == 1:
-            out["prefill_5x110"] = _guarded("prefill_5x110", lambda: prefill_leg(wl))
-        if headline and not args.no_harness:
-            out["harness"] = _guarded("harness", lambda: harness_leg(wl))
-        if cold is not None:
-            out["cold_start"] = cold
-            out["cold_first_chunk_latency_ms"] = cold["cold_first_chunk_latency_ms"]
-        if world == 1 and not args.no_cpu_baseline:
-            gpu = None
-            if headline:                        # the ids of utterance 0 (src[0], ref[0]) from the timed path, for parity_in_bench
-                wl.keep_codes = []
-                g_toks = wl.utterance(0)[0].clone()
-                torch.cuda.synchronize()
-                gpu = (g_toks.cpu(), wl.keep_codes)
-                wl.keep_codes = None
-            cb = _guarded("cpu_baseline", lambda: cpu_baseline(wl, gpu=gpu))
-            out["parity_in_bench"] = cb.pop("parity", None)
-            out["cpu_baseline"] = cb
-        if do_extra and world == 1:
-            # BASELINE configs[3]: bf16 weights + KV cache + bf16 activations across the rows step's hand-offs (weight_dtype 3), with its parity
-            # block; beside it the same leg with fp32 activations (weight_dtype 2: what this key measured up to round 5)
-            def both():
-                leg = streams_leg(device, rank, weights="bf16_act", parity=not args.no_cpu_baseline)
-                ref2 = streams_leg(device, rank, weights="bf16_kv", parity=False)
-                leg["fp32_activations_bf16_kv"] = {k: ref2[k] for k in ("utts_per_s", "decode_step_us", "first_chunk_latency_ms", "decode_variant")}
-                leg["fp32_activations_bf16_kv"]["roofline_frac"] = ref2["roofline"]["frac"]
-                return leg
-            out["streams8_bf16_kv"] = _guarded("streams8_bf16_kv", both)
+        if args.full:
+            out.update(full_report(wl, args, world, device, cold, offline, config4, do_extra and world == 1))
         print(json.dumps(out))
     if dist is not None:
         dist.barrier()

@@ -7,7 +7,7 @@ R=${1:-r06}
 OUT=$PWD/gpurun_out
 export TMPDIR=/tmp
 cd /tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_bench -- python $OLDPWD/bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-cold > $OUT/${R}_bench_under_rocprof.json 2> $OUT/${R}_bench_under_rocprof.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_bench -- python $OLDPWD/bench.py --steps 4 --warmup 1 --full --no-cpu-baseline --no-cold > $OUT/${R}_bench_under_rocprof.json 2> $OUT/${R}_bench_under_rocprof.err
 cp $(find $OUT/prof_bench -name '*kernel_stats.csv' | head -1) $OUT/${R}_rocprofv3_kernel_stats_bench.csv
 cp $(find $OUT/prof_bench -name '*domain_stats.csv' | head -1) $OUT/${R}_rocprofv3_domain_stats_bench.csv 2>/dev/null
 rm -rf $OUT/prof_bench
