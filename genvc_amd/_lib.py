@@ -36,6 +36,13 @@ class BeamState(C.Structure):
                                    "hyp_worst", "copies", "n_copies")]
 
 
+class ContrastiveState(C.Structure):
+    """gvc_contrastive_state (include/genvc_hip.h): sizes, settings and the device arrays of one contrastive search"""
+    _fields_ = [(n, C.c_int32) for n in ("B", "K", "vocab", "eos", "n0", "ids_stride", "max_new")] + \
+        [("penalty_alpha", C.c_float), ("repetition_penalty", C.c_float), ("reserved", C.c_int32)] + \
+        [(n, C.c_void_p) for n in ("ids", "finished", "tokens_out", "latents_out", "hidden0")]
+
+
 class LogitsProcessors(C.Structure):
     """gvc_logits_processors (include/genvc_hip.h): one call's length / repetition processors; all zero = every processor off"""
     _fields_ = [(n, C.c_int32) for n in ("no_repeat_ngram_size", "min_length", "min_new_tokens", "decay_start")] + \
@@ -105,6 +112,11 @@ _SIGNATURES = {
     "gvc_beam_select_proc": (C.c_int, [C.POINTER(BeamState), C.POINTER(LogitsProcessors), _P, _P, C.c_int32, _P]),
     "gvc_gpt_beam_generate_proc": (C.c_int, [_P, _P, C.POINTER(BeamState), C.POINTER(LogitsProcessors), C.c_int32, C.c_int32,
                                              C.c_int32, _P]),
+    "gvc_gpt_prefill_hidden": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, C.c_int32, _P, _P]),
+    "gvc_gpt_contrastive_generate": (C.c_int, [_P, _P, C.POINTER(ContrastiveState), C.c_int32, C.c_int32, C.c_int32, _P]),
+    "gvc_gpt_contrastive_generate_proc": (C.c_int, [_P, _P, C.POINTER(ContrastiveState), C.POINTER(LogitsProcessors), C.c_int32,
+                                                    C.c_int32, C.c_int32, _P]),
+    "gvc_gpt_warmup_contrastive": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32]),
     "gvc_sample_proc_sets": (C.c_int, [_P, C.c_int32, _P, C.c_int32, _P, _P, C.POINTER(SampleParams), C.POINTER(RowSampling),
                                        C.POINTER(LogitsProcessors), C.c_int32, c_i32p, C.c_int32, _P, _P]),
     "gvc_gpt_generate_proc_sets": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, _P, _P, C.POINTER(SampleParams), C.POINTER(RowSampling),

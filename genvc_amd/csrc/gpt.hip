@@ -14,6 +14,7 @@
 #include "persist_rows.h"
 #include "persist_rows_b16.h"
 #include "beam.h"
+#include "contrastive.h"
 #include "sampler.h"
 
 namespace gvc {
@@ -297,6 +298,8 @@ struct gvc_gpt {
     int32_t *tok_buf = nullptr, *step_ctr = nullptr;
     GenCall* gen_call = nullptr;
     BeamCall* beam_call = nullptr;    // parameters of the running gvc_gpt_beam_generate call (device)
+    CsCall* cs_call = nullptr;        // ... of the running gvc_gpt_contrastive_generate call (device)
+    CsBufs cs = {};                   // contrastive context rows and scratch (gvc_gpt_warmup_contrastive, or the first call)
     hipStream_t cap_stream = nullptr;
     std::map<int, hipGraphExec_t> graphs;   // 2*B + fused -> step graph
     int prof_only = -1;               // gvc_gpt_time_kernel(): launch only this kernel class
@@ -435,6 +438,7 @@ extern "C" int gvc_gpt_create(const gvc_gpt_dims* dims, gvc_gpt** out) {
     c->step_ctr = c->state + 3 * D.max_slots;
     GVC_CHECK_HIP(hipMalloc((void**)&c->gen_call, sizeof(GenCall)));
     GVC_CHECK_HIP(hipMalloc((void**)&c->beam_call, sizeof(BeamCall)));
+    GVC_CHECK_HIP(hipMalloc((void**)&c->cs_call, sizeof(CsCall)));
     GVC_CHECK_HIP(hipStreamCreateWithFlags(&c->cap_stream, hipStreamNonBlocking));
     if ((rc = gemv_init())) { gvc_gpt_destroy(c); return rc; }
     GVC_CHECK_HIP(hipHostMalloc((void**)&c->seam_err_host, sizeof(int), hipHostMallocMapped));
@@ -462,8 +466,9 @@ extern "C" int gvc_gpt_destroy(gvc_gpt* c) {
         if (p) hipFree(p);
     for (void* p : {(void*)c->wbase, (void*)c->wfm, (void*)c->wh, (void*)c->kv, (void*)c->x, (void*)c->a, (void*)c->q, (void*)c->h,
                     (void*)c->part, (void*)c->work, (void*)c->logits, (void*)c->latent, (void*)c->slot_logits, (void*)c->slot_latent, (void*)c->state, (void*)c->x2, (void*)c->part2,
-                    (void*)c->gen_call, (void*)c->beam_call})
+                    (void*)c->gen_call, (void*)c->beam_call, (void*)c->cs_call})
         if (p) hipFree(p);
+    cs_free(&c->cs);
     delete c;
     return GVC_OK;
 }
@@ -1418,8 +1423,9 @@ extern "C" int gvc_gpt_prefill(gvc_gpt* c, const int32_t* slots, int32_t B, cons
     return gvc_gpt_prefill_cached(c, slots, B, prefix_emb, P, 0, start_tok, logits_out, latent_out, sv);
 }
 
-extern "C" int gvc_gpt_prefill_cached(gvc_gpt* c, const int32_t* slots, int32_t B, const float* prefix_emb, int32_t P,
-                                      int32_t n_cached, int32_t start_tok, float* logits_out, float* latent_out, gvc_stream sv) {
+// hidden_out (nullable, n_cached == 0): ln_f of every computed row [B][P+1][d] (gvc_gpt_prefill_hidden)
+static int prefill_impl(gvc_gpt* c, const int32_t* slots, int32_t B, const float* prefix_emb, int32_t P, int32_t n_cached,
+                        int32_t start_tok, float* logits_out, float* latent_out, float* hidden_out, gvc_stream sv) {
     int rc = check_ready(c);
     if (rc) return rc;
     const int T = P + 1, d = c->dm.d_model;
@@ -1442,6 +1448,11 @@ extern "C" int gvc_gpt_prefill_cached(gvc_gpt* c, const int32_t* slots, int32_t 
         GVC_LAUNCH_CHECK();
         if ((rc = run_rows(c, slots, B, Tn, s, c->st.seq_len))) return rc;
     } else if ((rc = run_rows(c, slots, B, T, s))) return rc;
+    if (hidden_out) {
+        hipLaunchKernelGGL(k_ln_rows, dim3(cdiv(B * Tn, 4)), dim3(256), 0, s, c->x, hidden_out, B * Tn, d, c->lnf_w, c->lnf_b,
+                           (const float*)nullptr, (const float*)nullptr, 0);
+        GVC_LAUNCH_CHECK();
+    }
     if ((rc = launch_head(c, slots, B, 0, c->x, Tn, Tn - 1, logits_out, latent_out, 0, nullptr, s))) return rc;
     hipLaunchKernelGGL(k_set_state, dim3(cdiv(B, 64)), dim3(64), 0, s, c->st, slots, B, T, 1);
     GVC_LAUNCH_CHECK();
@@ -1450,6 +1461,17 @@ extern "C" int gvc_gpt_prefill_cached(gvc_gpt* c, const int32_t* slots, int32_t 
     hipLaunchKernelGGL(k_stage_rows, dim3(B), dim3(256), 0, s, latent_out, c->slot_latent, slots, d, 1);
     GVC_LAUNCH_CHECK();
     return GVC_OK;
+}
+
+extern "C" int gvc_gpt_prefill_cached(gvc_gpt* c, const int32_t* slots, int32_t B, const float* prefix_emb, int32_t P,
+                                      int32_t n_cached, int32_t start_tok, float* logits_out, float* latent_out, gvc_stream sv) {
+    return prefill_impl(c, slots, B, prefix_emb, P, n_cached, start_tok, logits_out, latent_out, nullptr, sv);
+}
+
+extern "C" int gvc_gpt_prefill_hidden(gvc_gpt* c, const int32_t* slots, int32_t B, const float* prefix_emb, int32_t P, int32_t start_tok,
+                                      float* hidden_out, gvc_stream sv) {
+    GVC_REQUIRE(hidden_out, GVC_ERR_ARG, "prefill_hidden: null hidden_out");
+    return prefill_impl(c, slots, B, prefix_emb, P, 0, start_tok, nullptr, nullptr, hidden_out, sv);
 }
 
 // The conditioning rows alone (no text rows, no start token, no head): K/V of rows 0..n_cond-1 into the slots' caches, length n_cond.
@@ -1923,6 +1945,145 @@ extern "C" int gvc_gpt_beam_generate(gvc_gpt* c, int32_t* slots, const gvc_beam_
 extern "C" int gvc_gpt_beam_generate_proc(gvc_gpt* c, int32_t* slots, const gvc_beam_state* st, const gvc_logits_processors* proc,
                                           int32_t i0, int32_t n_steps, int32_t max_keys, gvc_stream sv) {
     return beam_generate_impl(c, slots, st, proc, i0, n_steps, max_keys, sv);
+}
+
+// ---------------------------------------------------------------------------------------------
+// contrastive search: one captured graph = [k_cs_recall -> decode step over B*K rows -> k_cs_hidden -> k_cs_sim -> k_cs_select ->
+// k_kv_copy_span], replayed n_steps times.  The decode step is the one beam_plan picks for B*K rows; it reads the candidates from tok_buf
+// and leaves every row's residual in c->x (all decode variants do: launch_head reads it there), which k_cs_hidden turns into ln_f rows.
+// The graphs share the context's graph map under negative keys with bit 30 set (beam graphs never set it), so time-out fallback, rearm
+// and destroy drop them too.
+// ---------------------------------------------------------------------------------------------
+static int cs_prepare(gvc_gpt* c) {
+    if (c->cs.ctx) return GVC_OK;
+    note_lazy(c);
+    const int items = c->dm.max_slots / 2 > 0 ? c->dm.max_slots / 2 : 1;
+    return cs_alloc(&c->cs, items, c->dm.max_slots, c->dm.max_seq, c->dm.d_model);
+}
+
+static int build_cs_graph(gvc_gpt* c, int B, int K, const GenPlan& pl, int n_unroll, hipGraphExec_t* out) {
+    hipStream_t cs = c->cap_stream;
+    const int BK = B * K;
+    int32_t* table = c->gen_call->slots;
+    int rc = GVC_OK;
+    GVC_CHECK_HIP(hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal));
+    for (int u = 0; u < n_unroll && rc == GVC_OK; ++u) {
+        rc = launch_cs_recall(c->cs_call, c->cs, B, c->logits, c->latent, c->tok_buf, cs);
+        if (rc == GVC_OK && rows_decode_ok(c, BK))
+            rc = decode_rows(c, table, BK, c->tok_buf, c->logits, c->latent, nullptr, cs, pl.key_chunks);
+        else
+            for (int g = 0; g < BK && rc == GVC_OK; g += 8) {
+                const int Bg = BK - g < 8 ? BK - g : 8;
+                rc = decode_group(c, table + g, Bg, g, c->tok_buf + g, c->logits + (size_t)g * c->dm.vocab,
+                                  c->latent + (size_t)g * c->dm.d_model, nullptr, cs, pl.fused);
+            }
+        if (rc == GVC_OK) rc = launch_cs_hidden(c->x, c->cs, BK, c->lnf_w, c->lnf_b, cs);
+        if (rc == GVC_OK) rc = launch_cs_sim(c->cs_call, c->cs, B, cs);
+        if (rc == GVC_OK) rc = launch_cs_select(c->cs_call, c->cs, B, c->tok_buf, table, c->st.seq_len, cs);
+        if (rc == GVC_OK)
+            rc = launch_kv_copy_span(&c->cs_call->bc, B, K, c->kv, c->dm.n_layer, c->dm.n_head, c->dm.max_seq, c->hd, c->dm.max_slots,
+                                     c->kv_bf16 ? 2 : 4, c->st.seq_len, cs);
+    }
+    hipGraph_t graph = nullptr;
+    hipError_t e = hipStreamEndCapture(cs, &graph);
+    if (rc != GVC_OK) {
+        if (graph) hipGraphDestroy(graph);
+        return rc;
+    }
+    GVC_CHECK_HIP(e);
+    e = hipGraphInstantiate(out, graph, nullptr, nullptr, 0);
+    hipGraphDestroy(graph);
+    GVC_CHECK_HIP(e);
+    return GVC_OK;
+}
+
+static int cs_graph(gvc_gpt* c, int B, int K, const GenPlan& pl, int unroll, hipGraphExec_t* ge) {
+    const int k = -(1 + pl.key + (K << 16) + (unroll << 24) + (1 << 30));      // (pl.key < 2^16, K <= 16, unroll <= 8)
+    auto it = c->graphs.find(k);
+    if (it == c->graphs.end()) {
+        hipGraphExec_t g1;
+        note_lazy(c);
+        int r = build_cs_graph(c, B, K, pl, unroll, &g1);
+        if (r) return r;
+        it = c->graphs.emplace(k, g1).first;
+    }
+    *ge = it->second;
+    return GVC_OK;
+}
+
+extern "C" int gvc_gpt_warmup_contrastive(gvc_gpt* c, int32_t B, int32_t K, int32_t max_keys) {
+    int rc = check_ready(c);
+    if (rc) return rc;
+    GVC_REQUIRE(max_keys >= 0 && max_keys < c->dm.max_seq, GVC_ERR_ARG, "warmup_contrastive: bad max_keys %d", max_keys);
+    GVC_REQUIRE(B >= 1 && K >= 2 && K <= kCsMaxK && B * K <= c->dm.max_slots, GVC_ERR_ARG,
+                "warmup_contrastive: B*K = %d*%d outside [2, %d] (K <= %d)", B, K, c->dm.max_slots, kCsMaxK);
+    if ((rc = cs_check_shape(B, K, c->dm.vocab, c->dm.d_model))) return rc;      // (what every call checks: no graph the calls refuse)
+    if ((rc = gvc_gpt_warmup(c, B * K, max_keys, 1))) return rc;
+    c->in_warmup = 1;
+    struct Leave { gvc_gpt* c; ~Leave() { c->in_warmup = 0; } } leave{c};
+    if ((rc = cs_prepare(c))) return rc;
+    const int hi = max_keys > 0 ? max_keys : c->dm.max_seq - 1;
+    int last_key = -1;
+    for (int mk = 1; mk <= hi; ++mk) {
+        GenPlan pl;
+        if ((rc = beam_plan(c, B, K, mk, &pl))) return rc;
+        if (pl.key == last_key) continue;
+        last_key = pl.key;
+        hipGraphExec_t ge;
+        if (step_unroll() > 1 && (rc = cs_graph(c, B, K, pl, step_unroll(), &ge))) return rc;
+        if ((rc = cs_graph(c, B, K, pl, 1, &ge))) return rc;
+    }
+    GVC_CHECK_HIP(hipDeviceSynchronize());
+    return GVC_OK;
+}
+
+static int cs_generate_impl(gvc_gpt* c, const int32_t* slots, const gvc_contrastive_state* st, const gvc_logits_processors* proc, int32_t i0,
+                            int32_t n_steps, int32_t max_keys, gvc_stream sv) {
+    int rc = check_ready(c);
+    if (rc) return rc;
+    GVC_REQUIRE(slots && st && i0 >= 0 && n_steps >= 0 && max_keys >= 0, GVC_ERR_ARG, "contrastive_generate: bad argument");
+    if ((rc = cs_check(*st, c->dm.d_model))) return rc;
+    if (proc && (rc = check_procs(*proc, st->vocab))) return rc;
+    GVC_REQUIRE(st->vocab == c->dm.vocab, GVC_ERR_ARG, "contrastive_generate: vocab mismatch");
+    GVC_REQUIRE(i0 + n_steps <= st->max_new, GVC_ERR_ARG, "contrastive_generate: steps %d..%d past max_new %d", i0, i0 + n_steps,
+                st->max_new);
+    const int key_bound = max_keys > 0 ? max_keys : st->n0 + i0 + n_steps;
+    GVC_REQUIRE(key_bound < c->dm.max_seq && st->n0 + i0 + n_steps < c->dm.max_seq, GVC_ERR_STATE,
+                "contrastive_generate: %d cached positions would overflow the KV cache (max_seq %d)", st->n0 + i0 + n_steps, c->dm.max_seq);
+    hipStream_t s = (hipStream_t)sv;
+    const int B = st->B, K = st->K;
+    GenPlan pl;
+    if ((rc = beam_plan(c, B, K, key_bound, &pl))) return rc;
+    if ((rc = cs_prepare(c))) return rc;
+    if ((rc = launch_cs_begin(c->cs_call, c->cs, *st, proc, i0, slots, c->gen_call->slots, c->logits, c->slot_logits, c->latent,
+                              c->slot_latent, c->st.seq_len, c->st.mel_pos, c->kv, c->dm.n_layer, c->dm.n_head, c->dm.max_seq, c->hd, c->dm.max_slots, c->kv_bf16 ? 2 : 4,
+                              s)))
+        return rc;
+    c->last_variant = pl.variant;
+    const int kStepUnroll = step_unroll();
+    int left = n_steps;
+    if (kStepUnroll > 1 && left >= kStepUnroll) {
+        hipGraphExec_t ge;
+        if ((rc = cs_graph(c, B, K, pl, kStepUnroll, &ge))) return rc;
+        for (; left >= kStepUnroll; left -= kStepUnroll) GVC_CHECK_HIP(hipGraphLaunch(ge, s));
+    }
+    if (left > 0) {
+        hipGraphExec_t ge;
+        if ((rc = cs_graph(c, B, K, pl, 1, &ge))) return rc;
+        for (; left > 0; --left) GVC_CHECK_HIP(hipGraphLaunch(ge, s));
+    }
+    return launch_cs_end(c->cs, slots, B, K, c->logits, c->slot_logits, c->dm.vocab, c->latent, c->slot_latent, s);
+}
+
+extern "C" int gvc_gpt_contrastive_generate(gvc_gpt* c, const int32_t* slots, const gvc_contrastive_state* st, int32_t i0, int32_t n_steps,
+                                            int32_t max_keys, gvc_stream sv) {
+    return cs_generate_impl(c, slots, st, nullptr, i0, n_steps, max_keys, sv);
+}
+
+extern "C" int gvc_gpt_contrastive_generate_proc(gvc_gpt* c, const int32_t* slots, const gvc_contrastive_state* st,
+                                                 const gvc_logits_processors* proc, int32_t i0, int32_t n_steps, int32_t max_keys,
+                                                 gvc_stream sv) {
+    return cs_generate_impl(c, slots, st, proc, i0, n_steps, max_keys, sv);
 }
 
 // ---------------------------------------------------------------------------------------------

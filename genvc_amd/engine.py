@@ -379,6 +379,33 @@ def beam_select(beam, logits, slots, t):
               "beam_select_proc")
 
 
+MAX_CONTRASTIVE_K = 16    # kCsMaxK (csrc/contrastive.h)
+
+
+class ContrastiveSearch:
+    """device state of one contrastive search (gvc_contrastive_state, include/genvc_hip.h) over B items of K candidates: the ids rows,
+    finished flags, tokens and latents, and the prompt's hidden rows [B, n0, d] that the prefill writes (GptEngine.prefill_hidden).
+    `fake` [B, n0] are the fake ids of compute_embeddings."""
+
+    def __init__(self, fake, K, max_new, eos, vocab, d, penalty_alpha, repetition_penalty=1.0, proc=None, latents=True):
+        dev = fake.device
+        B, n0 = fake.shape
+        self.B, self.K, self.n0, self.max_new, self.eos = B, K, n0, max_new, eos
+        W = n0 + max_new + 8
+        i32 = dict(device=dev, dtype=torch.int32)
+        self.ids = torch.full((B, W), eos, **i32)
+        self.ids[:, :n0] = fake.to(torch.int32)
+        self.finished = torch.zeros(B, **i32)
+        self.tokens = torch.full((B, max_new), eos, **i32)
+        self.latents = torch.empty(B, max_new, d, device=dev, dtype=torch.float32) if latents else None
+        self.hidden0 = torch.empty(B, n0, d, device=dev, dtype=torch.float32)
+        self.steps = 0
+        self.c = _lib.ContrastiveState(B, K, int(vocab), int(eos), n0, W, int(max_new), float(penalty_alpha), float(repetition_penalty), 0,
+                                       self.ids.data_ptr(), self.finished.data_ptr(), self.tokens.data_ptr(),
+                                       self.latents.data_ptr() if latents else None, self.hidden0.data_ptr())
+        self.proc = proc          # gvc_logits_processors (logits_processors()) or None
+
+
 class GptEngine:
     """KV-cached GPT-2 stack of GenVC (reference layers/gpt.py + layers/gpt_inference.py)."""
 
@@ -649,6 +676,31 @@ class GptEngine:
             check(lib().gvc_gpt_beam_generate(self._h, ptr(_i32(slots)), C.byref(beam.c), int(beam.steps), int(n_steps), int(max_keys),
                                               stream()), "beam_generate")
         beam.steps += int(n_steps)
+
+    def prefill_hidden(self, slots, prefix_emb, hidden_out):
+        """prefill (logits and latent parked per slot) that also writes hidden_out [B, P+1, d] = ln_f of every row
+        (include/genvc_hip.h: gvc_gpt_prefill_hidden)"""
+        self._join_side()
+        B, P, _ = prefix_emb.shape
+        assert hidden_out.shape == (B, P + 1, self.d)
+        check(lib().gvc_gpt_prefill_hidden(self._h, ptr(_i32(slots)), B, ptr(_f32(prefix_emb)), P, self.dims["start_audio_token"],
+                                           ptr(_f32(hidden_out)), stream()), "prefill_hidden")
+
+    def contrastive_generate(self, slots, cs, n_steps, max_keys=0):
+        """n_steps steps of `cs` (a ContrastiveSearch) on the device, continuing at cs.steps (include/genvc_hip.h:
+        gvc_gpt_contrastive_generate): item b was prefilled into slots[b*K] with prefill_hidden(..., cs.hidden0)"""
+        self._join_side()
+        if cs.proc is not None:
+            check(lib().gvc_gpt_contrastive_generate_proc(self._h, ptr(_i32(slots)), C.byref(cs.c), C.byref(cs.proc), int(cs.steps),
+                                                          int(n_steps), int(max_keys), stream()), "contrastive_generate_proc")
+        else:
+            check(lib().gvc_gpt_contrastive_generate(self._h, ptr(_i32(slots)), C.byref(cs.c), int(cs.steps), int(n_steps), int(max_keys),
+                                                     stream()), "contrastive_generate")
+        cs.steps += int(n_steps)
+
+    def warmup_contrastive(self, B, K, max_keys=0):
+        """warmup() for contrastive_generate over B items of K candidates (include/genvc_hip.h: gvc_gpt_warmup_contrastive)"""
+        check(lib().gvc_gpt_warmup_contrastive(self._h, int(B), int(K), int(max_keys)), "warmup_contrastive")
 
     def warmup_beam(self, B, K, max_keys=0):
         """warmup() for beam_generate over B items of K beams (include/genvc_hip.h: gvc_gpt_warmup_beam)"""

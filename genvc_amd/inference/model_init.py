@@ -92,7 +92,8 @@ class GenVCModel(nn.Module):
         return _CondFuture(self, audio, sr, length, chunk_length, after)
 
     @torch.inference_mode()
-    def warmup(self, seg_len=1.0, streams=1, ref_seconds=3.0, stream_chunk_size=8, top_k=None, max_new_tokens=None, num_beams=1):
+    def warmup(self, seg_len=1.0, streams=1, ref_seconds=3.0, stream_chunk_size=8, top_k=None, max_new_tokens=None, num_beams=1,
+               contrastive_top_k=None):
         """Everything the FIRST conversion of this shape would otherwise pay inside its latency window (the reference leaves warm-up
         to the user: /root/reference/infer.py:27-30 runs a conversion first).  For `streams` concurrent streams of `seg_len`-second
         segments and a `ref_seconds` reference:
@@ -100,6 +101,8 @@ class GenVCModel(nn.Module):
             weight pack and topology probe; the captured step graphs) -- after it no GPT data-path call allocates or synchronises;
           * ContentVec / DVAE / HiFi-GAN / mel + Perceiver: one pass over zeros of the real shapes (their per-shape graphs and plans).
         num_beams = K > 1: also the beam step graphs of `streams` items x K beams (GPT.generate(num_beams=K, do_sample=False)).
+        contrastive_top_k = K > 1: also the contrastive-search buffers and step graphs of `streams` items x K candidates
+        (GPT.generate(top_k=K, do_sample=False, penalty_alpha=a)).
         No token is generated and no KV slot is left occupied."""
         dev = self.device
         g = self.gpt
@@ -123,6 +126,8 @@ class GenVCModel(nn.Module):
         eng.warmup_range(streams, min(n0 + grp, hi), hi, top_k)
         if int(num_beams) > 1:
             eng.warmup_beam(streams, int(num_beams), hi)
+        if contrastive_top_k is not None and int(contrastive_top_k) > 1:
+            eng.warmup_contrastive(streams, int(contrastive_top_k), hi)
         if self.hifigan is not None:
             lat = torch.zeros(streams, grp, g.model_dim, device=dev)
             for n in {grp, max(1, max_new % grp)}:

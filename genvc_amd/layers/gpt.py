@@ -11,8 +11,8 @@ import torch
 from torch import nn
 
 from .._lib import GenvcHipError
-from ..engine import (BEAM_LENGTH_MODES, PROC_KWARGS, WARP_KWARGS, BeamSearch, GptEngine, WarperSets, check_proc_kwargs, logits_processors,
-                      logits_sets, logits_warpers, sample_params)
+from ..engine import (BEAM_LENGTH_MODES, MAX_CONTRASTIVE_K, PROC_KWARGS, WARP_KWARGS, BeamSearch, ContrastiveSearch, GptEngine, WarperSets,
+                      check_proc_kwargs, logits_processors, logits_sets, logits_warpers, sample_params)
 from .perceiver_encoder import PerceiverResampler
 
 
@@ -49,6 +49,52 @@ def _beam_kwargs(kw):
     if mode not in BEAM_LENGTH_MODES:
         raise ValueError(f"beam_length_mode must be one of {sorted(BEAM_LENGTH_MODES)}, not {mode!r}")
     return K, float(kw.get("length_penalty", 1.0)), float(kw.get("repetition_penalty", 1.0)), mode
+
+
+def _contrastive_mode(kw):
+    """HF 4.33's contrastive-search test, which takes precedence over num_beams: top_k > 1, do_sample=False, penalty_alpha > 0 -> (K,
+    penalty_alpha), else None.  top_k absent is GenerationConfig's 50; an explicit top_k=None fails the test (GenerationConfig.update
+    keeps the None), so such a call decodes greedily as in 4.33.  A non-finite penalty_alpha raises ValueError.  do_sample=True with
+    penalty_alpha stays sampling (4.33 ignores the alpha)."""
+    alpha = kw.get("penalty_alpha")
+    if alpha is None or kw.get("do_sample", True) is not False:
+        return None
+    K = kw["top_k"] if "top_k" in kw else 50
+    if K is None or int(K) <= 1:
+        return None
+    alpha = float(alpha)
+    if alpha != alpha or alpha in (float("inf"), float("-inf")):
+        raise ValueError(f"penalty_alpha must be finite, not {kw.get('penalty_alpha')!r}")
+    if alpha <= 0.0:
+        return None
+    return int(K), alpha
+
+
+def _contrastive_kwargs(kw, B=None, max_slots=None):
+    """_contrastive_mode, validated for the device: None when the kwargs do not select contrastive search, else (K, penalty_alpha,
+    repetition_penalty).  num_return_sequences > 1 raises ValueError (4.33 raises it), K > 16 NotImplementedError; with B and
+    max_slots given, B * K > max_slots raises ValueError."""
+    mode = _contrastive_mode(kw)
+    if mode is None:
+        return None
+    K, alpha = mode
+    if int(kw.get("num_return_sequences", 1) or 1) > 1:
+        raise ValueError(f"num_return_sequences has to be 1, but is {kw.get('num_return_sequences')} when doing contrastive search")
+    if K > MAX_CONTRASTIVE_K:
+        raise NotImplementedError(f"contrastive search with top_k={K} is not implemented: the device ranks at most {MAX_CONTRASTIVE_K} "
+                                  "candidates per step")
+    if B is not None and max_slots is not None and B * K > max_slots:
+        raise ValueError(f"contrastive search over {B} items x {K} candidates needs {B * K} KV slots; the context has {max_slots} "
+                         "(init_gpt_for_inference(max_slots=...))")
+    return K, alpha, float(kw.get("repetition_penalty", 1.0))
+
+
+def _no_contrastive(kw, where):
+    """the paths that decode one row per stream: the contrastive-search kwargs raise, naming the path (before any check of K)"""
+    if _contrastive_mode(kw) is not None:
+        raise NotImplementedError(f"contrastive search (penalty_alpha={kw.get('penalty_alpha')}, top_k={kw.get('top_k', 50)}, "
+                                  f"do_sample=False) is not on the {where} path: GPT.generate serves it (the reference's streaming "
+                                  "harness always samples, inference_utils.py:178)")
 
 
 def _any_proc(kw):
@@ -240,6 +286,7 @@ class GPT(nn.Module):
     def _start(self, fake_inputs, kw):
         """prefill + device-side loop state for the stored prefix"""
         _no_beams(kw, "streaming (get_generator)")
+        _no_contrastive(kw, "streaming (get_generator)")
         B, n0 = fake_inputs.shape
         dev = fake_inputs.device
         max_new = kw.get("max_new_tokens") or self.max_gen_mel_tokens                     # gpt.py:606,618
@@ -286,7 +333,11 @@ class GPT(nn.Module):
     def generate(self, cond_latents, text_inputs, **generate_kwargs):
         """reference gpt.py:594-609 -> int64 [B, n_generated]; finished rows are padded with the stop token.
         `group` (extra kwarg) = decode steps per host check of the finished flags.
-        num_beams = K > 1 with do_sample=False: deterministic beam search on the device (_generate_beams)."""
+        num_beams = K > 1 with do_sample=False: deterministic beam search on the device (_generate_beams).
+        top_k = K > 1 with do_sample=False and penalty_alpha > 0: contrastive search on the device (_generate_contrastive), before
+        num_beams as in transformers 4.33."""
+        if _contrastive_kwargs(generate_kwargs) is not None:
+            return self._generate_contrastive(cond_latents, text_inputs, generate_kwargs)
         if int(generate_kwargs.get("num_beams", 1) or 1) > 1:
             return self._generate_beams(cond_latents, text_inputs, generate_kwargs)
         fake = self.compute_embeddings(cond_latents, text_inputs)
@@ -348,6 +399,43 @@ class GPT(nn.Module):
         self.last_beam_scores = scores
         return ids
 
+    def _generate_contrastive(self, cond_latents, text_inputs, generate_kwargs):
+        """transformers 4.33 contrastive_search semantics (include/genvc_hip.h: gvc_contrastive_state): item b is prefilled ONCE into
+        KV slot b*K, which also writes the ln_f rows of its prompt (the context the degeneration penalty compares with); every step runs
+        [recall -> decode step over B*K rows -> hidden rows -> similarity -> select -> KV span copies] from a captured graph, the host
+        looks at the finished flags once per `group` steps.  No logits warper (temperature, top_p, ... have no effect); the repetition
+        penalty and the processor kwargs apply.  Needs B*K <= the context's KV slots (ValueError otherwise).  Returns int64 [B, n]
+        (gpt.py:609), trimmed after the step where the last row emits the stop token as generate() trims; `last_latents` holds the
+        chosen candidates' final_norm latents, as the sampling path fills it."""
+        kw = dict(generate_kwargs)
+        self._need_engine()
+        B = int(text_inputs.shape[0])
+        K, alpha, rep = _contrastive_kwargs(kw, B, self.max_slots)
+        group = int(kw.pop("group", 16))
+        fake = self.compute_embeddings(cond_latents, text_inputs)
+        n0 = int(fake.shape[1])
+        max_new = int(kw.get("max_new_tokens") or self.max_gen_mel_tokens)                   # gpt.py:606
+        dev = fake.device
+        proc = logits_processors(kw, n0, self.num_audio_tokens, sampling=False)
+
+        def run():
+            slots = torch.arange(B * K, device=dev, dtype=torch.int32)
+            cs = ContrastiveSearch(fake, K, max_new, self.stop_audio_token, self.num_audio_tokens, self.model_dim, alpha, rep, proc=proc)
+            self.engine.prefill_hidden(slots[::K].contiguous(), self._prefix, cs.hidden0)      # each item once; the first step fans out
+            while cs.steps < max_new:
+                n = min(group, max_new - cs.steps)
+                self.engine.contrastive_generate(slots, cs, n, max_keys=n0 + cs.steps + n)
+                stop = bool(cs.finished.all().item())
+                self.engine.health()          # (the .item() above synchronised)
+                if stop:
+                    break
+            return cs
+        cs = self._recovering(B * K, run)
+        toks = cs.tokens[:, :cs.steps].long()
+        n = self._stop_len(toks)
+        self.last_latents = cs.latents[:, :n]
+        return toks[:, :n]
+
     @torch.inference_mode()
     def generate_groups(self, groups, group_kwargs=None, **generate_kwargs):
         """Several generate() calls decoded TOGETHER: groups = [(cond_latents [B_i, 32, d], text_inputs [B_i, Tc_i]), ...] with
@@ -369,6 +457,7 @@ class GPT(nn.Module):
         (gvc_gpt_generate_proc_sets, or gvc_gpt_generate_warp when a warper is on).
         Returns a list of int64 [B_i, n_i] (reference gpt.py:594-609 per group)."""
         _no_beams(generate_kwargs, "grouped (generate_groups)")
+        _no_contrastive(generate_kwargs, "grouped (generate_groups)")
         kw = dict(generate_kwargs)
         gkw = None
         if group_kwargs is not None:
@@ -517,6 +606,7 @@ class GPT(nn.Module):
         the call-wide ones; job j then gets what generate(c_j, t_j, **its merged kwargs) returns (seed=job_seeds[j] when sampling), each
         row of a decode call carrying its job's set (gvc_gpt_generate_proc_sets, or gvc_gpt_generate_warp when a warper is on)."""
         _no_beams(generate_kwargs, "rolling (generate_rolling)")
+        _no_contrastive(generate_kwargs, "rolling (generate_rolling)")
         kw = dict(generate_kwargs)
         jkw = None
         if job_kwargs is not None:
@@ -664,6 +754,7 @@ class GPT(nn.Module):
         the EOS step included.  Steps run in groups of `stream_group` (default 8, the vocoder chunk of
         inference_utils.py:195) with one host check of the finished flags per group."""
         _no_beams(generate_kwargs, "streaming (get_generator)")
+        _no_contrastive(generate_kwargs, "streaming (get_generator)")
         self._need_engine()
         group = generate_kwargs.pop("stream_group", 8)
         B = int(fake_inputs.shape[0])

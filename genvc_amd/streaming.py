@@ -43,6 +43,7 @@ import torch
 
 from .inference.inference_utils import _sampling_kwargs, _vocode, handle_chunks
 from .engine import check_proc_kwargs, logits_processors, logits_sets, logits_warpers, sample_params
+from .layers.gpt import _no_contrastive
 from ._lib import GenvcHipError
 
 
@@ -102,7 +103,8 @@ class StreamSessions:
     # ------------------------------------------------------------------------------------------
     def _procs(self, kw, base, where):
         """a processor dict (PROC_KWARGS and WARP_KWARGS only) merged over `base`, validated -> the merged dict, or None when it is
-        empty"""
+        empty.  The contrastive-search kwargs raise NotImplementedError (sessions decode one row per stream)"""
+        _no_contrastive(kw or {}, f"session (StreamSessions, {where})")
         check_proc_kwargs(kw, where)
         m = dict(base, **{k: v for k, v in (kw or {}).items() if v is not None})
         try:

@@ -334,6 +334,57 @@ int gvc_beam_select_proc(const gvc_beam_state* st, const gvc_logits_processors* 
 int gvc_gpt_beam_generate_proc(gvc_gpt* ctx, int32_t* slots, const gvc_beam_state* st, const gvc_logits_processors* proc, int32_t i0,
                                int32_t n_steps, int32_t max_keys, gvc_stream s);
 
+/* ------------------------------------------------------------------------------------------
+ * Contrastive search (HF generate(top_k=K > 1, do_sample=False, penalty_alpha=a > 0); reference layers/gpt.py:594-609 hands every kwarg
+ * to HF generate, whose pinned 4.33 selects this mode by that test, layers/stream_generator.py:264-270 restates it and :366-385 routes it
+ * to contrastive_search without a logits warper).  The semantics are transformers 4.33's contrastive_search + _ranking_fast:
+ *   prefill: ctx = ln_f of EVERY prompt row (hidden_states[-1], not the final_norm latent); logits = the last row's.
+ *   step t (t tokens generated before it), item b: s = processors(ids row, logits) (repetition penalty on the raw logits, then the
+ *   gvc_logits_processors in HF's order; no warper: temperature, top_p, min_p ... have no effect); p = softmax(s) in fp32; the top-K
+ *   (p_k, x_k) descending; the K candidates run one decode step each from the item's KV (rows b*K + k of a B*K-row step, at the cache and
+ *   mel positions greedy step t uses); h_k = ln_f of candidate k's residual; pen_k = max_j cos(ctx_j, h_k) over the n0 + t context rows;
+ *   score_k = (1 - a) p_k - a pen_k; k* = the first argmax.  Token = x_{k*}, or eos (= pad) once the item has finished; ctx gains h_{k*},
+ *   the item's KV keeps candidate k*'s row, the next logits are candidate k*'s.  finished |= token == eos.
+ * A candidate is a KV slot (the item's K slots hold identical K/V between steps): after the ranking the slot of k* is copied to the
+ * other K-1 slots for the one new position (k_kv_copy_span, as beams reorder).  DESIGN.md 4.10.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct {
+    int32_t B, K;                   /* items, candidates per item: 2 <= K <= 16, B * K <= the context's slots */
+    int32_t vocab, eos;
+    int32_t n0;                     /* prompt length = positions of the fake ids (compute_embeddings) = KV positions after the prefill */
+    int32_t ids_stride;             /* >= n0 + max_new */
+    int32_t max_new;                /* tokens_out / latents_out capacity per item */
+    float penalty_alpha;            /* a: finite, > 0 (a > 1 is accepted, as HF accepts it) */
+    float repetition_penalty;       /* > 0; 1 = off */
+    int32_t reserved;               /* 0 */
+    int32_t* ids;                   /* [B][ids_stride] input_ids rows: the n0 fake ids at the start; step t writes column n0 + t */
+    int32_t* finished;              /* [B] 0 / 1 (start 0) */
+    int32_t* tokens_out;            /* [B][max_new]: token of step t at column t */
+    float* latents_out;             /* nullable [B][max_new][d]: step t's final_norm latent of the chosen candidate (what predicts the next
+                                       token, as gvc_gpt_generate's latents) */
+    const float* hidden0;           /* [B][n0][d] ln_f of the prompt rows (gvc_gpt_prefill_hidden); read by the call with i0 == 0 */
+} gvc_contrastive_state;
+
+/* gvc_gpt_prefill(logits_out = NULL) that also writes hidden_out [B][P+1][d] = ln_f of every row it computed (the P prefix rows and the
+ * start token): the context rows of a contrastive search.  The logits and latent are parked per slot as gvc_gpt_prefill parks them. */
+int gvc_gpt_prefill_hidden(gvc_gpt* ctx, const int32_t* slots, int32_t B, const float* prefix_emb, int32_t P, int32_t start_tok,
+                           float* hidden_out, gvc_stream s);
+/* n_steps contrastive steps [recall -> decode step over B*K rows -> hidden rows -> similarity -> select -> KV span copies], replayed from
+ * captured graphs (eight steps per graph) with all state on the device.  The caller has prefilled item b into slots[b*K]
+ * (gvc_gpt_prefill_hidden, its hidden rows in st->hidden0) and initialised st (i0 == 0: ids rows, finished = 0); slots[b*K+1 ..
+ * b*K+K-1] are free slots the call with i0 == 0 fans the prefix out to.  slots are not permuted.  Step i of the call is step t = i0 + i;
+ * consecutive calls continue the search (the context rows live in the context between them).  max_keys as in gvc_gpt_beam_generate.
+ * proc (HOST, nullable; min_p and prompt_len ignored: the prompt is st->n0) travels by value into the device-resident call state.
+ * Status codes as gvc_gpt_beam_generate. */
+int gvc_gpt_contrastive_generate(gvc_gpt* ctx, const int32_t* slots, const gvc_contrastive_state* st, int32_t i0, int32_t n_steps,
+                                 int32_t max_keys, gvc_stream s);
+int gvc_gpt_contrastive_generate_proc(gvc_gpt* ctx, const int32_t* slots, const gvc_contrastive_state* st, const gvc_logits_processors* proc,
+                                      int32_t i0, int32_t n_steps, int32_t max_keys, gvc_stream s);
+/* gvc_gpt_warmup for gvc_gpt_contrastive_generate over B items of K candidates: the context-row buffers and the step graphs of every
+ * context class up to max_keys cached positions (and everything gvc_gpt_warmup(B*K) prepares).  Afterwards such calls neither allocate
+ * nor synchronise */
+int gvc_gpt_warmup_contrastive(gvc_gpt* ctx, int32_t B, int32_t K, int32_t max_keys);
+
 /* Per-row processor sets: row b uses sets[set_of_row[b]], or no processors at all when the index is -1 (such a row computes exactly
  * what it computes in the call without processors).  sets (n_sets entries, 1 <= n_sets <= B <= 64) and set_of_row (B entries, each in
  * [-1, n_sets)) are HOST arrays, free again when the call returns; GVC_ERR_ARG otherwise, and every set is checked as proc is.  A set's

@@ -31,6 +31,8 @@ if __name__ == "__main__":
                         help="GPT weight / KV-cache storage on the GPU (fp32 = the reference's numerics)")
     parser.add_argument("--num_beams", type=int, default=1,
                         help="non-streaming only: > 1 decodes with deterministic beam search (do_sample=False) of this width")
+    parser.add_argument("--penalty_alpha", type=float, default=None,
+                        help="non-streaming only: > 0 decodes with contrastive search (do_sample=False) over --top_k candidates (2..16)")
     parser.add_argument("--min_new_tokens", type=int, default=None, help="no stop token before this many tokens per segment")
     parser.add_argument("--no_repeat_ngram_size", type=int, default=None,
                         help="no n-gram of codec tokens (fake prompt included) occurs twice in a segment (1..8)")
@@ -43,6 +45,9 @@ if __name__ == "__main__":
     args = parser.parse_args()
     if args.num_beams < 1 or (args.streaming and args.num_beams != 1):
         raise SystemExit("--num_beams must be >= 1, and 1 with --streaming")
+    if args.penalty_alpha is not None:
+        if args.streaming or not args.penalty_alpha > 0.0 or args.penalty_alpha == float("inf") or not 2 <= args.top_k <= 16:
+            raise SystemExit("--penalty_alpha must be finite and > 0, non-streaming, with --top_k in [2, 16]")
     gen_kw = {k: v for k, v in (("min_new_tokens", args.min_new_tokens), ("no_repeat_ngram_size", args.no_repeat_ngram_size),
                                 ("min_p", args.min_p)) if v is not None}
     if args.eos_decay is not None:
@@ -71,6 +76,10 @@ if __name__ == "__main__":
     else:
         model, config = model_init(args.model_path, args.device, weight_dtype=args.weights)
     model.config.top_k = args.top_k
+    if args.penalty_alpha is not None:
+        gen_kw.update(do_sample=False, penalty_alpha=args.penalty_alpha, top_k=args.top_k)
+        if model.gpt.max_slots < args.top_k:           # one KV slot per candidate
+            model.gpt.init_gpt_for_inference(max_slots=args.top_k, max_rows=max(4096, 128 * args.top_k), weight_dtype=args.weights)
     src_wav = load_audio(args.src_wav, model.content_sample_rate, device=args.device)
     ref_audio = load_audio(args.ref_audio, model.config.audio.sample_rate, device=args.device)
     if src_wav is None or ref_audio is None:
