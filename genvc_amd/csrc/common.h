@@ -42,6 +42,26 @@ void set_error(const char* fmt, ...);
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
+// ---- graph capture (host) -------------------------------------------------------------------
+// Captures what `body()` enqueues on `cs` (it returns a GVC_* code) and instantiates it into *out.  A failing body still ends the
+// capture and its code is returned; the temporary hipGraph_t never outlives the call.
+template <class Body>
+static inline int capture_graph(hipStream_t cs, hipGraphExec_t* out, Body&& body) {
+    GVC_CHECK_HIP(hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal));
+    const int rc = body();
+    hipGraph_t graph = nullptr;
+    hipError_t e = hipStreamEndCapture(cs, &graph);
+    if (rc != GVC_OK) {
+        if (graph) (void)hipGraphDestroy(graph);
+        return rc;
+    }
+    GVC_CHECK_HIP(e);
+    e = hipGraphInstantiate(out, graph, nullptr, nullptr, 0);
+    (void)hipGraphDestroy(graph);
+    GVC_CHECK_HIP(e);
+    return GVC_OK;
+}
+
 // ---- wave64 reductions (DPP inside a 16-lane row, readlane across rows) ----------------------
 template <int CTRL>
 __device__ __forceinline__ float dpp_mov(float v) {

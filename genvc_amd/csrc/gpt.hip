@@ -5,6 +5,7 @@
 
 #include <map>
 #include <string>
+#include <tuple>
 #include <vector>
 
 #include "gemm.h"
@@ -262,6 +263,21 @@ struct GptLayer {
     unsigned short *qkv_h = nullptr, *proj_h = nullptr, *fc_h = nullptr, *p2_h = nullptr;   // bf16 copies (bf16-weights contexts)
 };
 
+// What a captured generation graph bakes into its nodes, and so what tells two graphs of a context apart.
+enum GraphKind { kStepGraph, kBeamGraph, kContrastiveGraph };
+struct GraphKey {
+    int kind;       // GraphKind
+    int rows;       // rows of the decode step: the call's B streams, B * K of a search
+    int K;          // beams / candidates per item (0: step graphs)
+    int fused;      // GEMV groups with the fused attention + c_proj launch
+    int split;      // GenPlan::split
+    int unroll;     // steps in the graph
+    int greedy;     // step graphs: the sampler kernel (searches carry no sampler: 0)
+    bool operator<(const GraphKey& o) const {
+        return std::tie(kind, rows, K, fused, split, unroll, greedy) < std::tie(o.kind, o.rows, o.K, o.fused, o.split, o.unroll, o.greedy);
+    }
+};
+
 struct gvc_gpt {
     gvc_gpt_dims dm;
     int hd = 0, n_cu = 256;
@@ -301,7 +317,7 @@ struct gvc_gpt {
     CsCall* cs_call = nullptr;        // ... of the running gvc_gpt_contrastive_generate call (device)
     CsBufs cs = {};                   // contrastive context rows and scratch (gvc_gpt_warmup_contrastive, or the first call)
     hipStream_t cap_stream = nullptr;
-    std::map<int, hipGraphExec_t> graphs;   // 2*B + fused -> step graph
+    std::map<GraphKey, hipGraphExec_t> graphs;   // captured step, beam and contrastive graphs (get_graph / drop_graphs)
     int prof_only = -1;               // gvc_gpt_time_kernel(): launch only this kernel class
     int prof_skip_one = -1;           // ... or every class except this one
     unsigned long long* dbg = nullptr; // GVC_DEBUG_STAMPS: [launch][8] in-kernel timestamps of the eager decode step
@@ -455,9 +471,15 @@ extern "C" int gvc_gpt_create(const gvc_gpt_dims* dims, gvc_gpt** out) {
     return GVC_OK;
 }
 
+// every captured graph of the context, whatever its kind
+static void drop_graphs(gvc_gpt* c) {
+    for (auto& kvp : c->graphs) (void)hipGraphExecDestroy(kvp.second);
+    c->graphs.clear();
+}
+
 extern "C" int gvc_gpt_destroy(gvc_gpt* c) {
     if (!c) return GVC_OK;
-    for (auto& kvp : c->graphs) hipGraphExecDestroy(kvp.second);
+    drop_graphs(c);
     if (c->cap_stream) hipStreamDestroy(c->cap_stream);
     if (c->xalt) hipFree(c->xalt);
     if (c->seam_err_host) hipHostFree(c->seam_err_host);
@@ -1195,6 +1217,15 @@ static int decode_rows(gvc_gpt* c, const int32_t* slots, int B, const int32_t* t
     return launch_head(c, slots, B, 0, c->x, 1, 0, logits_out, latent_out, 1, step_ctr, s);
 }
 
+// Re-initialises the hand-off buffers of both one-launch steps (the device is idle); the first HIP error, for the caller to judge.
+static hipError_t reset_handoffs(gvc_gpt* c) {
+    const hipError_t e_bufs = c->r_bufs ? hipMemset(c->r_bufs, 0xff, c->act_bf16 ? rows_b16_buf_bytes() : rows_buf_bytes()) : hipSuccess;
+    // (the step epoch p_epoch[0] stays MONOTONIC: granule tags are (epoch + 1, layer, phase) and nothing zeroes the granules, so an epoch
+    //  that started over could accept a stale granule of the timed-out call; only the arrival counter and the per-XCD ranks are cleared)
+    const hipError_t e_epoch = c->p_epoch ? hipMemset(c->p_epoch + 1, 0, 15 * sizeof(unsigned)) : hipSuccess;
+    return e_bufs != hipSuccess ? e_bufs : e_epoch;
+}
+
 static int check_ready(gvc_gpt* c) {
     GVC_REQUIRE(c, GVC_ERR_ARG, "null context");
     const int dev_err = c->seam_err_host ? *(volatile int*)c->seam_err_host : 0;
@@ -1208,12 +1239,8 @@ static int check_ready(gvc_gpt* c) {
         // re-initialised -- and every later call runs on the launch-per-phase paths.
         (void)hipDeviceSynchronize();
         c->persist = 0;
-        for (auto& kvp : c->graphs) (void)hipGraphExecDestroy(kvp.second);
-        c->graphs.clear();
-        if (c->r_bufs) (void)hipMemset(c->r_bufs, 0xff, c->act_bf16 ? rows_b16_buf_bytes() : rows_buf_bytes());
-        // (the step epoch p_epoch[0] stays MONOTONIC: granule tags are (epoch + 1, layer, phase) and nothing zeroes the granules, so an epoch
-        //  that started over could accept a stale granule of the timed-out call; only the arrival counter and the per-XCD ranks are cleared)
-        if (c->p_epoch) (void)hipMemset(c->p_epoch + 1, 0, 15 * sizeof(unsigned));
+        drop_graphs(c);
+        (void)reset_handoffs(c);
         *c->seam_err_host = 0;
         c->fallbacks += 1;
         set_error("an in-kernel hand-off of a one-launch decode step timed out (code %d: were all 256 workgroups resident?); the outputs "
@@ -1226,6 +1253,22 @@ static int check_ready(gvc_gpt* c) {
     return GVC_OK;
 }
 
+// One decode step over the B rows of a slot table, eager or under capture: the one-stream one-launch step, else the rows path, else
+// GEMV groups of 8 streams (the nullable step counter goes to the last group only).  The one-launch steps are prepared by the caller.
+static int decode_step(gvc_gpt* c, const int32_t* slots, int B, const int32_t* tok_in, float* logits_out, float* latent_out,
+                       int32_t* step_ctr, hipStream_t s, bool fused, int key_chunks) {
+    if (persist_ok(c, B)) return launch_persist(c, slots, tok_in, logits_out, latent_out, step_ctr, s);
+    if (rows_decode_ok(c, B)) return decode_rows(c, slots, B, tok_in, logits_out, latent_out, step_ctr, s, key_chunks);
+    int rc = GVC_OK;
+    for (int g = 0; g < B && rc == GVC_OK; g += 8) {
+        const int Bg = B - g < 8 ? B - g : 8;
+        const bool last = g + 8 >= B;
+        rc = decode_group(c, slots + g, Bg, g, tok_in + g, logits_out + (size_t)g * c->dm.vocab, latent_out + (size_t)g * c->dm.d_model,
+                          last ? step_ctr : nullptr, s, fused);
+    }
+    return rc;
+}
+
 extern "C" int gvc_gpt_decode_step(gvc_gpt* c, const int32_t* slots, int32_t B, const int32_t* tok_in,
                                    float* logits_out, float* latent_out, gvc_stream sv) {
     int rc = check_ready(c);
@@ -1233,17 +1276,11 @@ extern "C" int gvc_gpt_decode_step(gvc_gpt* c, const int32_t* slots, int32_t B, 
     GVC_REQUIRE(B >= 1 && B <= c->dm.max_slots, GVC_ERR_ARG, "decode_step: B=%d outside [1,%d]", B, c->dm.max_slots);
     hipStream_t s = (hipStream_t)sv;
     if (persist_ok(c, B) && (rc = persist_prepare(c))) return rc;
-    if (persist_ok(c, B)) return launch_persist(c, slots, tok_in, logits_out, latent_out, nullptr, s);
-    if (rows_persist_ok(c, B, c->st.seq_len) && (rc = rows_persist_prepare(c))) return rc;
-    c->rows_keys_hint = c->dm.max_seq;            // (no bound from the caller: the key split for the longest possible context)
-    if (rows_decode_ok(c, B)) return decode_rows(c, slots, B, tok_in, logits_out, latent_out, nullptr, s);
-    for (int g = 0; g < B; g += 8) {
-        const int Bg = B - g < 8 ? B - g : 8;
-        if ((rc = decode_group(c, slots + g, Bg, g, tok_in + g, logits_out + (size_t)g * c->dm.vocab,
-                               latent_out + (size_t)g * c->dm.d_model, nullptr, s)))
-            return rc;
+    if (!persist_ok(c, B)) {
+        if (rows_persist_ok(c, B, c->st.seq_len) && (rc = rows_persist_prepare(c))) return rc;
+        c->rows_keys_hint = c->dm.max_seq;            // (no bound from the caller: the key split for the longest possible context)
     }
-    return GVC_OK;
+    return decode_step(c, slots, B, tok_in, logits_out, latent_out, nullptr, s, false, 1);
 }
 
 extern "C" int gvc_gpt_reset_slots(gvc_gpt* c, const int32_t* slots, int32_t B, gvc_stream sv) {
@@ -1523,57 +1560,25 @@ extern "C" int gvc_gpt_latents(gvc_gpt* c, const int32_t* slots, int32_t B, cons
 // ---------------------------------------------------------------------------------------------
 // generation loop: one captured graph = [sample -> decode step] for a fixed B, replayed n_steps times
 // ---------------------------------------------------------------------------------------------
-static int build_step_graph(gvc_gpt* c, int B, bool fused, int key_chunks, int n_unroll, bool greedy, hipGraphExec_t* out) {
-    hipStream_t cs = c->cap_stream;
-    int rc = GVC_OK;
-    GVC_CHECK_HIP(hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal));
-    // n_unroll consecutive steps in ONE graph: the boundary between two graph launches costs several times the boundary between
-    // two kernels of a graph, and the host looks at the finished flags once per group of steps anyway
-    for (int u = 0; u < n_unroll && rc == GVC_OK; ++u) {
-    rc = launch_sample_indirect(&c->gen_call->sc, B, greedy, cs);
-    if (rc == GVC_OK && persist_ok(c, B))
-        rc = launch_persist(c, c->gen_call->slots, c->tok_buf, c->logits, c->latent, c->step_ctr, cs);
-    else if (rc == GVC_OK && rows_decode_ok(c, B))
-        rc = decode_rows(c, c->gen_call->slots, B, c->tok_buf, c->logits, c->latent, c->step_ctr, cs, key_chunks);
-    else
-    for (int g = 0; g < B && rc == GVC_OK; g += 8) {
-        const int Bg = B - g < 8 ? B - g : 8;
-        const bool last = g + 8 >= B;
-        rc = decode_group(c, c->gen_call->slots + g, Bg, g, c->tok_buf + g, c->logits + (size_t)g * c->dm.vocab,
-                          c->latent + (size_t)g * c->dm.d_model, last ? c->step_ctr : nullptr, cs, fused);
-    }
-    }
-    hipGraph_t graph = nullptr;
-    hipError_t e = hipStreamEndCapture(cs, &graph);
-    if (rc != GVC_OK) {
-        if (graph) hipGraphDestroy(graph);
-        return rc;
-    }
-    GVC_CHECK_HIP(e);
-    e = hipGraphInstantiate(out, graph, nullptr, nullptr, 0);
-    hipGraphDestroy(graph);
-    GVC_CHECK_HIP(e);
-    return GVC_OK;
-}
-
-// What a gvc_gpt_generate call over B streams that reaches `key_bound` cached positions replays: the step variant, its key split and the
-// key of its captured graph.  Runs the one-time preparation of the one-launch steps first (they may switch a path off for this context --
-// r_ready / persist -- so nothing is derived from rows_decode_ok / persist_ok before).
+// What a gvc_gpt_generate call over B streams that reaches `key_bound` cached positions replays: the step variant, its key split and what
+// keys its captured graphs (GraphKey).  Runs the one-time preparation of the one-launch steps first (they may switch a path off for this
+// context -- r_ready / persist -- so nothing is derived from rows_decode_ok / persist_ok before).
 struct GenPlan {
     bool fused, greedy;
-    int key_chunks, key, variant;
+    int key_chunks, variant;
+    int split;      // GraphKey::split: key_chunks, or 8 + the key split of the one-launch rows step
 };
 
 static int step_unroll() {
-    // the steps of a call run as graphs of kStepUnroll consecutive steps, the remainder one by one
-    return 8;   // (<= 32: bits 24..29 of the graph key)
+    // the steps of a call run as graphs of this many consecutive steps, the remainder one by one
+    return 8;
 }
 
 static int plan_generate(gvc_gpt* c, int B, int key_bound, int top_k, GenPlan* pl) {
     int rc;
     pl->fused = fused_ok(c, B, key_bound);
-    // rows mode splits the keys of long contexts over 2 / 4 attention workgroups per (stream, head): two from GVC_ROWS_KEY_SPLIT
-    // cached positions on (default 144; 0: never), four beyond 320
+    // rows mode splits the keys of long contexts over 2 / 4 attention workgroups per (stream, head): two from key_split cached
+    // positions on (0: never), four beyond 320
     constexpr int key_split = 144;
     if (persist_ok(c, B) && (rc = persist_prepare(c))) return rc;
     if (!persist_ok(c, B) && rows_persist_ok(c, B, c->st.seq_len) && (rc = rows_persist_prepare(c))) return rc;
@@ -1581,24 +1586,83 @@ static int plan_generate(gvc_gpt* c, int B, int key_bound, int top_k, GenPlan* p
                          ? (key_bound > 320 ? 4 : (key_bound > key_split ? 2 : 1)) : 1;
     const bool rows1 = !persist_ok(c, B) && c->r_ready == 1 && rows_persist_ok(c, B, c->st.seq_len);      // one-launch rows step
     c->rows_keys_hint = key_bound;
-    pl->key = B * 2 + (pl->fused ? 1 : 0) + 4096 * (rows1 ? 8 + rows_persist_chunks(c, B, key_bound) : pl->key_chunks);   // (the one-launch steps are pure functions of B [and the key split])
+    pl->split = rows1 ? 8 + rows_persist_chunks(c, B, key_bound) : pl->key_chunks;   // (the one-launch steps are pure functions of B [and the key split])
     pl->variant = persist_ok(c, B) ? 3 : (rows1 ? 5 : (rows_decode_ok(c, B) ? 4 : (pl->fused ? 2 : 1)));
     // (the sampler kernel is chosen at capture time: a graph serves top_k = 1 or everything else)
     pl->greedy = sample_greedy_ok(top_k, c->dm.d_model);
     return GVC_OK;
 }
 
-static int step_graph(gvc_gpt* c, int B, const GenPlan& pl, int unroll, hipGraphExec_t* ge) {
-    const int k = pl.key + (unroll > 1 ? (1 << 24) * unroll : 0) + (pl.greedy ? (1 << 30) : 0);
-    auto it = c->graphs.find(k);
+// The context's graph for `key`, captured on first use (a lazy init outside warm-up) from key.unroll repetitions of `step`, which
+// enqueues one step of the loop on the capture stream it is given and returns a GVC_* code.
+template <class Step>
+static int get_graph(gvc_gpt* c, const GraphKey& key, hipGraphExec_t* ge, Step&& step) {
+    auto it = c->graphs.find(key);
     if (it == c->graphs.end()) {
         hipGraphExec_t g1;
         note_lazy(c);
-        int r = build_step_graph(c, B, pl.fused, pl.key_chunks, unroll, pl.greedy, &g1);
+        // key.unroll consecutive steps in ONE graph: the boundary between two graph launches costs several times the boundary between
+        // two kernels of a graph, and the host looks at the finished flags once per group of steps anyway
+        int r = capture_graph(c->cap_stream, &g1, [&] {
+            int rc = GVC_OK;
+            for (int u = 0; u < key.unroll && rc == GVC_OK; ++u) rc = step(c->cap_stream);
+            return rc;
+        });
         if (r) return r;
-        it = c->graphs.emplace(k, g1).first;
+        it = c->graphs.emplace(key, g1).first;
     }
     *ge = it->second;
+    return GVC_OK;
+}
+
+static int step_graph(gvc_gpt* c, int B, const GenPlan& pl, int unroll, hipGraphExec_t* ge) {
+    return get_graph(c, GraphKey{kStepGraph, B, 0, pl.fused, pl.split, unroll, pl.greedy}, ge, [&](hipStream_t cs) {
+        const int rc = launch_sample_indirect(&c->gen_call->sc, B, pl.greedy, cs);
+        return rc ? rc : decode_step(c, c->gen_call->slots, B, c->tok_buf, c->logits, c->latent, c->step_ctr, cs, pl.fused, pl.key_chunks);
+    });
+}
+
+// Replays n_steps steps on s: groups of step_unroll() steps, then the remainder one by one.  graph(unroll, &ge) hands out the graph of
+// that many steps; each of the two is asked for only when the call needs it.
+template <class Graph>
+static int replay_steps(int n_steps, hipStream_t s, Graph&& graph) {
+    const int unroll = step_unroll();
+    int rc, left = n_steps;
+    if (unroll > 1 && left >= unroll) {
+        hipGraphExec_t ge;
+        if ((rc = graph(unroll, &ge))) return rc;
+        for (; left >= unroll; left -= unroll) GVC_CHECK_HIP(hipGraphLaunch(ge, s));
+    }
+    if (left > 0) {
+        hipGraphExec_t ge;
+        if ((rc = graph(1, &ge))) return rc;
+        for (; left > 0; --left) GVC_CHECK_HIP(hipGraphLaunch(ge, s));
+    }
+    return GVC_OK;
+}
+
+// in_warmup for a scope: what a warm-up call allocates, synchronises and captures is no lazy init (note_lazy)
+struct WarmupScope {
+    gvc_gpt* c;
+    explicit WarmupScope(gvc_gpt* c_) : c(c_) { c->in_warmup = 1; }
+    ~WarmupScope() { c->in_warmup = 0; }
+};
+
+// Captures the unrolled and the single-step graph of every plan the key bounds lo..hi lead to (runs of bounds share one plan):
+// plan(bound, &pl) is the loop's plan function, graph(pl, unroll, &ge) its graph getter.
+template <class Plan, class Graph>
+static int warmup_sweep(int lo, int hi, Plan&& plan, Graph&& graph) {
+    int rc, last_fused = -1, last_split = -1;
+    for (int mk = lo; mk <= hi; ++mk) {
+        GenPlan pl;
+        if ((rc = plan(mk, &pl))) return rc;
+        if (pl.fused == last_fused && pl.split == last_split) continue;
+        last_fused = pl.fused;
+        last_split = pl.split;
+        hipGraphExec_t ge;
+        if (step_unroll() > 1 && (rc = graph(pl, step_unroll(), &ge))) return rc;
+        if ((rc = graph(pl, 1, &ge))) return rc;
+    }
     return GVC_OK;
 }
 
@@ -1610,8 +1674,7 @@ extern "C" int gvc_gpt_warmup(gvc_gpt* c, int32_t B, int32_t max_keys, int32_t t
     int rc = check_ready(c);
     if (rc) return rc;
     GVC_REQUIRE(B >= 1 && B <= c->dm.max_slots && max_keys >= 0 && max_keys < c->dm.max_seq, GVC_ERR_ARG, "warmup: bad argument");
-    c->in_warmup = 1;
-    struct Leave { gvc_gpt* c; ~Leave() { c->in_warmup = 0; } } leave{c};
+    WarmupScope warm(c);
     // the rows step also serves the <= 16 uncached rows of a cached chunk prefill, whatever B
     if (rows_persist_ok(c, 16, c->st.seq_len) && (rc = rows_persist_prepare(c))) return rc;
     GenPlan pl;
@@ -1628,18 +1691,10 @@ extern "C" int gvc_gpt_warmup_range(gvc_gpt* c, int32_t B, int32_t min_keys, int
     GVC_REQUIRE(min_keys >= 1 && min_keys <= max_keys && max_keys < c->dm.max_seq, GVC_ERR_ARG, "warmup_range: bad key range [%d, %d]", min_keys, max_keys);
     int rc = gvc_gpt_warmup(c, B, min_keys, top_k);          // (also prepares the one-launch steps: the plans below are then pure look-ups)
     if (rc) return rc;
-    c->in_warmup = 1;
-    struct Leave { gvc_gpt* c; ~Leave() { c->in_warmup = 0; } } leave{c};
-    int last_key = -1;
-    for (int mk = min_keys; mk <= max_keys; ++mk) {
-        GenPlan pl;
-        if ((rc = plan_generate(c, B, mk, top_k, &pl))) return rc;
-        if (pl.key == last_key) continue;
-        last_key = pl.key;
-        hipGraphExec_t ge;
-        if (step_unroll() > 1 && (rc = step_graph(c, B, pl, step_unroll(), &ge))) return rc;
-        if ((rc = step_graph(c, B, pl, 1, &ge))) return rc;
-    }
+    WarmupScope warm(c);
+    rc = warmup_sweep(min_keys, max_keys, [&](int mk, GenPlan* pl) { return plan_generate(c, B, mk, top_k, pl); },
+                      [&](const GenPlan& pl, int unroll, hipGraphExec_t* ge) { return step_graph(c, B, pl, unroll, ge); });
+    if (rc) return rc;
     GVC_CHECK_HIP(hipDeviceSynchronize());
     return GVC_OK;
 }
@@ -1655,10 +1710,8 @@ extern "C" int gvc_gpt_rearm(gvc_gpt* c) {
     if (rc) return rc;
     if (c->persist == c->persist_cfg) return GVC_OK;
     GVC_CHECK_HIP(hipDeviceSynchronize());
-    for (auto& kvp : c->graphs) (void)hipGraphExecDestroy(kvp.second);
-    c->graphs.clear();
-    if (c->r_bufs) GVC_CHECK_HIP(hipMemset(c->r_bufs, 0xff, c->act_bf16 ? rows_b16_buf_bytes() : rows_buf_bytes()));
-    if (c->p_epoch) GVC_CHECK_HIP(hipMemset(c->p_epoch + 1, 0, 15 * sizeof(unsigned)));      // (epoch [0] stays monotonic, see check_ready)
+    drop_graphs(c);
+    GVC_CHECK_HIP(reset_handoffs(c));
     GVC_CHECK_HIP(hipDeviceSynchronize());
     c->persist = c->persist_cfg;
     return GVC_OK;
@@ -1750,18 +1803,7 @@ static int generate_impl(gvc_gpt* c, const int32_t* slots, int32_t B, int32_t* i
     // (a keyed call replays the greedy graphs when every row is greedy, the sampling ones otherwise: the step graphs are the same)
     if ((rc = plan_generate(c, B, key_bound, rows ? (rows_greedy ? 1 : 0) : p->top_k, &pl))) return rc;
     c->last_variant = pl.variant;
-    const int kStepUnroll = step_unroll();
-    int left = n_steps;
-    if (kStepUnroll > 1 && left >= kStepUnroll) {
-        hipGraphExec_t ge;
-        if ((rc = step_graph(c, B, pl, kStepUnroll, &ge))) return rc;
-        for (; left >= kStepUnroll; left -= kStepUnroll) GVC_CHECK_HIP(hipGraphLaunch(ge, s));
-    }
-    if (left > 0) {
-        hipGraphExec_t ge;
-        if ((rc = step_graph(c, B, pl, 1, &ge))) return rc;
-        for (; left > 0; --left) GVC_CHECK_HIP(hipGraphLaunch(ge, s));
-    }
+    if ((rc = replay_steps(n_steps, s, [&](int unroll, hipGraphExec_t* ge) { return step_graph(c, B, pl, unroll, ge); }))) return rc;
     hipLaunchKernelGGL(k_gen_end, dim3(B), dim3(256), 0, s, slots, c->logits, c->slot_logits, c->dm.vocab, c->latent, c->slot_latent,
                        c->dm.d_model);
     GVC_LAUNCH_CHECK();
@@ -1821,56 +1863,21 @@ extern "C" int gvc_gpt_generate_warp(gvc_gpt* c, const int32_t* slots, int32_t B
 // ---------------------------------------------------------------------------------------------
 // beam search: one captured graph = [k_beam_select -> k_kv_copy_span -> decode step over B*K rows], replayed n_steps times.  The
 // decode step is the one plan_generate picks for B*K rows (the one-launch rows step for 2..16 rows where it applies); it addresses the
-// KV cache through the device-resident slot table gen_call->slots, which the select step permutes (beam.h).  The graphs share the
-// context's graph map under negative keys, so every path that drops the step graphs (time-out fallback, rearm, destroy) drops them too.
+// KV cache through the device-resident slot table gen_call->slots, which the select step permutes (beam.h).  The graphs live in the
+// context's graph map under kind kBeamGraph, so every path that drops the step graphs (time-out fallback, rearm, destroy) drops them too.
 // ---------------------------------------------------------------------------------------------
-static int build_beam_graph(gvc_gpt* c, int B, int K, const GenPlan& pl, int n_unroll, hipGraphExec_t* out) {
-    hipStream_t cs = c->cap_stream;
-    const int BK = B * K;
+static int beam_graph(gvc_gpt* c, int B, int K, const GenPlan& pl, int unroll, hipGraphExec_t* ge) {
     int32_t* table = c->gen_call->slots;
-    int rc = GVC_OK;
     gvc_beam_state dummy;
     memset(&dummy, 0, sizeof(dummy));
-    GVC_CHECK_HIP(hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal));
-    for (int u = 0; u < n_unroll && rc == GVC_OK; ++u) {
-        rc = launch_beam_select(dummy, nullptr, c->beam_call, B, K, c->logits, table, 0, c->st.seq_len, c->st.mel_pos, c->tok_buf, cs);
+    return get_graph(c, GraphKey{kBeamGraph, B * K, K, pl.fused, pl.split, unroll, 0}, ge, [&](hipStream_t cs) {
+        int rc = launch_beam_select(dummy, nullptr, c->beam_call, B, K, c->logits, table, 0, c->st.seq_len, c->st.mel_pos, c->tok_buf, cs);
         if (rc == GVC_OK)
             rc = launch_kv_copy_span(c->beam_call, B, K, c->kv, c->dm.n_layer, c->dm.n_head, c->dm.max_seq, c->hd, c->dm.max_slots,
                                      c->kv_bf16 ? 2 : 4, c->st.seq_len, cs);
-        if (rc == GVC_OK && rows_decode_ok(c, BK))
-            rc = decode_rows(c, table, BK, c->tok_buf, c->logits, c->latent, nullptr, cs, pl.key_chunks);
-        else
-            for (int g = 0; g < BK && rc == GVC_OK; g += 8) {
-                const int Bg = BK - g < 8 ? BK - g : 8;
-                rc = decode_group(c, table + g, Bg, g, c->tok_buf + g, c->logits + (size_t)g * c->dm.vocab,
-                                  c->latent + (size_t)g * c->dm.d_model, nullptr, cs, pl.fused);
-            }
-    }
-    hipGraph_t graph = nullptr;
-    hipError_t e = hipStreamEndCapture(cs, &graph);
-    if (rc != GVC_OK) {
-        if (graph) hipGraphDestroy(graph);
+        if (rc == GVC_OK) rc = decode_step(c, table, B * K, c->tok_buf, c->logits, c->latent, nullptr, cs, pl.fused, pl.key_chunks);
         return rc;
-    }
-    GVC_CHECK_HIP(e);
-    e = hipGraphInstantiate(out, graph, nullptr, nullptr, 0);
-    hipGraphDestroy(graph);
-    GVC_CHECK_HIP(e);
-    return GVC_OK;
-}
-
-static int beam_graph(gvc_gpt* c, int B, int K, const GenPlan& pl, int unroll, hipGraphExec_t* ge) {
-    const int k = -(1 + pl.key + (K << 16) + (unroll << 24));      // (pl.key < 2^16, K <= 16, unroll <= 32)
-    auto it = c->graphs.find(k);
-    if (it == c->graphs.end()) {
-        hipGraphExec_t g1;
-        note_lazy(c);
-        int r = build_beam_graph(c, B, K, pl, unroll, &g1);
-        if (r) return r;
-        it = c->graphs.emplace(k, g1).first;
-    }
-    *ge = it->second;
-    return GVC_OK;
+    });
 }
 
 static int beam_plan(gvc_gpt* c, int B, int K, int key_bound, GenPlan* pl) {
@@ -1886,20 +1893,12 @@ extern "C" int gvc_gpt_warmup_beam(gvc_gpt* c, int32_t B, int32_t K, int32_t max
     GVC_REQUIRE(max_keys >= 0 && max_keys < c->dm.max_seq, GVC_ERR_ARG, "warmup_beam: bad max_keys %d", max_keys);
     GVC_REQUIRE(B >= 1 && K >= 2 && B * K <= c->dm.max_slots, GVC_ERR_ARG, "warmup_beam: B*K = %d*%d outside [2, %d]", B, K, c->dm.max_slots);
     if ((rc = gvc_gpt_warmup(c, B * K, max_keys, 1))) return rc;
-    c->in_warmup = 1;
-    struct Leave { gvc_gpt* c; ~Leave() { c->in_warmup = 0; } } leave{c};
+    WarmupScope warm(c);
     // every context class a search reaching max_keys passes through (the calls' bounds grow with the search)
     const int hi = max_keys > 0 ? max_keys : c->dm.max_seq - 1;
-    int last_key = -1;
-    for (int mk = 1; mk <= hi; ++mk) {
-        GenPlan pl;
-        if ((rc = beam_plan(c, B, K, mk, &pl))) return rc;
-        if (pl.key == last_key) continue;
-        last_key = pl.key;
-        hipGraphExec_t ge;
-        if (step_unroll() > 1 && (rc = beam_graph(c, B, K, pl, step_unroll(), &ge))) return rc;
-        if ((rc = beam_graph(c, B, K, pl, 1, &ge))) return rc;
-    }
+    rc = warmup_sweep(1, hi, [&](int mk, GenPlan* pl) { return beam_plan(c, B, K, mk, pl); },
+                      [&](const GenPlan& pl, int unroll, hipGraphExec_t* ge) { return beam_graph(c, B, K, pl, unroll, ge); });
+    if (rc) return rc;
     GVC_CHECK_HIP(hipDeviceSynchronize());
     return GVC_OK;
 }
@@ -1922,18 +1921,7 @@ static int beam_generate_impl(gvc_gpt* c, int32_t* slots, const gvc_beam_state* 
     if ((rc = beam_plan(c, B, K, key_bound, &pl))) return rc;
     if ((rc = launch_beam_begin(c->beam_call, *st, proc, i0, slots, c->gen_call->slots, c->logits, c->slot_logits, s))) return rc;
     c->last_variant = pl.variant;
-    const int kStepUnroll = step_unroll();
-    int left = n_steps;
-    if (kStepUnroll > 1 && left >= kStepUnroll) {
-        hipGraphExec_t ge;
-        if ((rc = beam_graph(c, B, K, pl, kStepUnroll, &ge))) return rc;
-        for (; left >= kStepUnroll; left -= kStepUnroll) GVC_CHECK_HIP(hipGraphLaunch(ge, s));
-    }
-    if (left > 0) {
-        hipGraphExec_t ge;
-        if ((rc = beam_graph(c, B, K, pl, 1, &ge))) return rc;
-        for (; left > 0; --left) GVC_CHECK_HIP(hipGraphLaunch(ge, s));
-    }
+    if ((rc = replay_steps(n_steps, s, [&](int unroll, hipGraphExec_t* ge) { return beam_graph(c, B, K, pl, unroll, ge); }))) return rc;
     return launch_beam_end(c->gen_call->slots, slots, BK, c->logits, c->slot_logits, c->dm.vocab, s);
 }
 
@@ -1951,8 +1939,7 @@ extern "C" int gvc_gpt_beam_generate_proc(gvc_gpt* c, int32_t* slots, const gvc_
 // contrastive search: one captured graph = [k_cs_recall -> decode step over B*K rows -> k_cs_hidden -> k_cs_sim -> k_cs_select ->
 // k_kv_copy_span], replayed n_steps times.  The decode step is the one beam_plan picks for B*K rows; it reads the candidates from tok_buf
 // and leaves every row's residual in c->x (all decode variants do: launch_head reads it there), which k_cs_hidden turns into ln_f rows.
-// The graphs share the context's graph map under negative keys with bit 30 set (beam graphs never set it), so time-out fallback, rearm
-// and destroy drop them too.
+// The graphs live in the context's graph map under kind kContrastiveGraph, so time-out fallback, rearm and destroy drop them too.
 // ---------------------------------------------------------------------------------------------
 static int cs_prepare(gvc_gpt* c) {
     if (c->cs.ctx) return GVC_OK;
@@ -1961,54 +1948,19 @@ static int cs_prepare(gvc_gpt* c) {
     return cs_alloc(&c->cs, items, c->dm.max_slots, c->dm.max_seq, c->dm.d_model);
 }
 
-static int build_cs_graph(gvc_gpt* c, int B, int K, const GenPlan& pl, int n_unroll, hipGraphExec_t* out) {
-    hipStream_t cs = c->cap_stream;
-    const int BK = B * K;
+static int cs_graph(gvc_gpt* c, int B, int K, const GenPlan& pl, int unroll, hipGraphExec_t* ge) {
     int32_t* table = c->gen_call->slots;
-    int rc = GVC_OK;
-    GVC_CHECK_HIP(hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal));
-    for (int u = 0; u < n_unroll && rc == GVC_OK; ++u) {
-        rc = launch_cs_recall(c->cs_call, c->cs, B, c->logits, c->latent, c->tok_buf, cs);
-        if (rc == GVC_OK && rows_decode_ok(c, BK))
-            rc = decode_rows(c, table, BK, c->tok_buf, c->logits, c->latent, nullptr, cs, pl.key_chunks);
-        else
-            for (int g = 0; g < BK && rc == GVC_OK; g += 8) {
-                const int Bg = BK - g < 8 ? BK - g : 8;
-                rc = decode_group(c, table + g, Bg, g, c->tok_buf + g, c->logits + (size_t)g * c->dm.vocab,
-                                  c->latent + (size_t)g * c->dm.d_model, nullptr, cs, pl.fused);
-            }
-        if (rc == GVC_OK) rc = launch_cs_hidden(c->x, c->cs, BK, c->lnf_w, c->lnf_b, cs);
+    return get_graph(c, GraphKey{kContrastiveGraph, B * K, K, pl.fused, pl.split, unroll, 0}, ge, [&](hipStream_t cs) {
+        int rc = launch_cs_recall(c->cs_call, c->cs, B, c->logits, c->latent, c->tok_buf, cs);
+        if (rc == GVC_OK) rc = decode_step(c, table, B * K, c->tok_buf, c->logits, c->latent, nullptr, cs, pl.fused, pl.key_chunks);
+        if (rc == GVC_OK) rc = launch_cs_hidden(c->x, c->cs, B * K, c->lnf_w, c->lnf_b, cs);
         if (rc == GVC_OK) rc = launch_cs_sim(c->cs_call, c->cs, B, cs);
         if (rc == GVC_OK) rc = launch_cs_select(c->cs_call, c->cs, B, c->tok_buf, table, c->st.seq_len, cs);
         if (rc == GVC_OK)
             rc = launch_kv_copy_span(&c->cs_call->bc, B, K, c->kv, c->dm.n_layer, c->dm.n_head, c->dm.max_seq, c->hd, c->dm.max_slots,
                                      c->kv_bf16 ? 2 : 4, c->st.seq_len, cs);
-    }
-    hipGraph_t graph = nullptr;
-    hipError_t e = hipStreamEndCapture(cs, &graph);
-    if (rc != GVC_OK) {
-        if (graph) hipGraphDestroy(graph);
         return rc;
-    }
-    GVC_CHECK_HIP(e);
-    e = hipGraphInstantiate(out, graph, nullptr, nullptr, 0);
-    hipGraphDestroy(graph);
-    GVC_CHECK_HIP(e);
-    return GVC_OK;
-}
-
-static int cs_graph(gvc_gpt* c, int B, int K, const GenPlan& pl, int unroll, hipGraphExec_t* ge) {
-    const int k = -(1 + pl.key + (K << 16) + (unroll << 24) + (1 << 30));      // (pl.key < 2^16, K <= 16, unroll <= 8)
-    auto it = c->graphs.find(k);
-    if (it == c->graphs.end()) {
-        hipGraphExec_t g1;
-        note_lazy(c);
-        int r = build_cs_graph(c, B, K, pl, unroll, &g1);
-        if (r) return r;
-        it = c->graphs.emplace(k, g1).first;
-    }
-    *ge = it->second;
-    return GVC_OK;
+    });
 }
 
 extern "C" int gvc_gpt_warmup_contrastive(gvc_gpt* c, int32_t B, int32_t K, int32_t max_keys) {
@@ -2019,20 +1971,12 @@ extern "C" int gvc_gpt_warmup_contrastive(gvc_gpt* c, int32_t B, int32_t K, int3
                 "warmup_contrastive: B*K = %d*%d outside [2, %d] (K <= %d)", B, K, c->dm.max_slots, kCsMaxK);
     if ((rc = cs_check_shape(B, K, c->dm.vocab, c->dm.d_model))) return rc;      // (what every call checks: no graph the calls refuse)
     if ((rc = gvc_gpt_warmup(c, B * K, max_keys, 1))) return rc;
-    c->in_warmup = 1;
-    struct Leave { gvc_gpt* c; ~Leave() { c->in_warmup = 0; } } leave{c};
+    WarmupScope warm(c);
     if ((rc = cs_prepare(c))) return rc;
     const int hi = max_keys > 0 ? max_keys : c->dm.max_seq - 1;
-    int last_key = -1;
-    for (int mk = 1; mk <= hi; ++mk) {
-        GenPlan pl;
-        if ((rc = beam_plan(c, B, K, mk, &pl))) return rc;
-        if (pl.key == last_key) continue;
-        last_key = pl.key;
-        hipGraphExec_t ge;
-        if (step_unroll() > 1 && (rc = cs_graph(c, B, K, pl, step_unroll(), &ge))) return rc;
-        if ((rc = cs_graph(c, B, K, pl, 1, &ge))) return rc;
-    }
+    rc = warmup_sweep(1, hi, [&](int mk, GenPlan* pl) { return beam_plan(c, B, K, mk, pl); },
+                      [&](const GenPlan& pl, int unroll, hipGraphExec_t* ge) { return cs_graph(c, B, K, pl, unroll, ge); });
+    if (rc) return rc;
     GVC_CHECK_HIP(hipDeviceSynchronize());
     return GVC_OK;
 }
@@ -2060,18 +2004,7 @@ static int cs_generate_impl(gvc_gpt* c, const int32_t* slots, const gvc_contrast
                               s)))
         return rc;
     c->last_variant = pl.variant;
-    const int kStepUnroll = step_unroll();
-    int left = n_steps;
-    if (kStepUnroll > 1 && left >= kStepUnroll) {
-        hipGraphExec_t ge;
-        if ((rc = cs_graph(c, B, K, pl, kStepUnroll, &ge))) return rc;
-        for (; left >= kStepUnroll; left -= kStepUnroll) GVC_CHECK_HIP(hipGraphLaunch(ge, s));
-    }
-    if (left > 0) {
-        hipGraphExec_t ge;
-        if ((rc = cs_graph(c, B, K, pl, 1, &ge))) return rc;
-        for (; left > 0; --left) GVC_CHECK_HIP(hipGraphLaunch(ge, s));
-    }
+    if ((rc = replay_steps(n_steps, s, [&](int unroll, hipGraphExec_t* ge) { return cs_graph(c, B, K, pl, unroll, ge); }))) return rc;
     return launch_cs_end(c->cs, slots, B, K, c->logits, c->slot_logits, c->dm.vocab, c->latent, c->slot_latent, s);
 }
 
@@ -2117,20 +2050,16 @@ extern "C" int gvc_gpt_time_kernel(gvc_gpt* c, int32_t which, const int32_t* slo
     const bool fused = fused_ok(c, B, 0);       // the short-context variant bench.py's workload runs
     c->prof_only = whole ? -1 : which;
     c->prof_skip_one = which >= 16 ? which - 16 : -1;
-    hipGraph_t graph = nullptr;
     hipGraphExec_t ge = nullptr;
-    hipError_t e = hipStreamBeginCapture(c->cap_stream, hipStreamCaptureModeThreadLocal);
-    if (e == hipSuccess) {
-        rc = one_launch ? launch_persist(c, slots, tok_in, c->logits, c->latent, nullptr, c->cap_stream)
-                        : decode_group(c, slots, B, 0, tok_in, c->logits, c->latent, nullptr, c->cap_stream, fused);
-        e = hipStreamEndCapture(c->cap_stream, &graph);
-    }
+    rc = capture_graph(c->cap_stream, &ge, [&] {
+        return one_launch ? launch_persist(c, slots, tok_in, c->logits, c->latent, nullptr, c->cap_stream)
+                          : decode_group(c, slots, B, 0, tok_in, c->logits, c->latent, nullptr, c->cap_stream, fused);
+    });
     c->prof_only = -1;
     c->prof_skip_one = -1;
-    if (e == hipSuccess && rc == GVC_OK) e = hipGraphInstantiate(&ge, graph, nullptr, nullptr, 0);
-    if (graph) (void)hipGraphDestroy(graph);
+    hipError_t e = hipSuccess;
     float ms = 0.f;
-    if (e == hipSuccess && rc == GVC_OK) {
+    if (rc == GVC_OK) {
         (void)hipGraphLaunch(ge, s);                                   // warm-up pass
         (void)hipEventRecord(e0, s);
         for (int i = 0; i < n_steps; ++i) (void)hipGraphLaunch(ge, s);

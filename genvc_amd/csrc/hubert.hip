@@ -633,16 +633,8 @@ extern "C" int gvc_hubert_forward(gvc_hubert* c, const float* wav, int32_t B, in
                 for (auto& kv : c->graphs) hipGraphExecDestroy(kv.second);
                 c->graphs.clear();
             }
-            GVC_CHECK_HIP(hipStreamBeginCapture(c->cap_stream, hipStreamCaptureModeThreadLocal));
-            rc = hb_body(c, B, T, c->cap_stream);
-            hipGraph_t graph = nullptr;
-            hipError_t e = hipStreamEndCapture(c->cap_stream, &graph);
-            if (rc) { if (graph) hipGraphDestroy(graph); return rc; }
-            GVC_CHECK_HIP(e);
             hipGraphExec_t ge;
-            e = hipGraphInstantiate(&ge, graph, nullptr, nullptr, 0);
-            hipGraphDestroy(graph);
-            GVC_CHECK_HIP(e);
+            if ((rc = capture_graph(c->cap_stream, &ge, [&] { return hb_body(c, B, T, c->cap_stream); }))) return rc;
             it = c->graphs.emplace(key, ge).first;
         }
         GVC_CHECK_HIP(hipGraphLaunch(it->second, s));

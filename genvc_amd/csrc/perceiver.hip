@@ -362,16 +362,8 @@ extern "C" int gvc_perceiver_forward(gvc_perceiver* c, const float* x, int32_t B
                 c->graphs.erase(victim);
                 c->graph_used.erase(victim);
             }
-            hipGraph_t graph = nullptr;
-            GVC_CHECK_HIP(hipStreamBeginCapture(c->cap_stream, hipStreamCaptureModeThreadLocal));
-            rc = perc_launch(c, B, F, c->cap_stream);
-            hipError_t e = hipStreamEndCapture(c->cap_stream, &graph);
-            if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-            GVC_CHECK_HIP(e);
             hipGraphExec_t ge = nullptr;
-            e = hipGraphInstantiate(&ge, graph, nullptr, nullptr, 0);
-            (void)hipGraphDestroy(graph);
-            GVC_CHECK_HIP(e);
+            if ((rc = capture_graph(c->cap_stream, &ge, [&] { return perc_launch(c, B, F, c->cap_stream); }))) return rc;
             it = c->graphs.emplace(key, ge).first;
         }
         c->graph_used[key] = ++c->tick;
