@@ -93,6 +93,8 @@ _SIGNATURES = {
     "gvc_gpt_prefill_cond": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, _P]),
     "gvc_gpt_decode_step": (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P]),
     "gvc_gpt_reset_slots": (C.c_int, [_P, _P, C.c_int32, _P]),
+    "gvc_gpt_kv_fanout": (C.c_int, [_P, _P, _P, C.c_int32, _P]),
+    "gvc_gpt_sequence_logprobs": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "gvc_gpt_latents": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "gvc_sample": (C.c_int, [_P, C.c_int32, _P, C.c_int32, _P, _P, C.POINTER(SampleParams), C.c_int32, _P, _P]),
     "gvc_gpt_generate": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, _P, _P, C.POINTER(SampleParams), C.c_int32,

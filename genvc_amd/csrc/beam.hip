@@ -152,9 +152,10 @@ __global__ void __launch_bounds__(kBeamThreads) k_beam_select(gvc_beam_state st_
             sv[r] = v; si[r] = e;
         }
         __syncthreads();
-        // the scorer walk (BeamSearchScorer.process / BeamHypotheses.add, is_done with early_stopping=False)
+        // the scorer walk (BeamSearchScorer.process / BeamHypotheses.add, is_done by the early_stopping mode)
         if (tid == 0) {
-            const int len = st.length_mode == 0 ? st.n0 + t : t + 1;
+            const int lmode = st.length_mode & 0xff, early = (st.length_mode >> 8) & 0xff;
+            const int len = lmode == 0 ? st.n0 + t : t + 1;
             const float denom = powf((float)len, st.length_penalty);
             float* hs = st.hyp_score + b * K;
             int32_t* hl = st.hyp_len + b * K;
@@ -190,8 +191,11 @@ __global__ void __launch_bounds__(kBeamThreads) k_beam_select(gvc_beam_state st_
             }
             int done = 0;
             if (cnt == K) {
-                const float best = st.length_mode == 0 ? sv[0] : nx_sc[0];
-                done = worst >= best / denom;
+                const float best = lmode == 0 ? sv[0] : nx_sc[0];
+                if (early == 1) done = 1;
+                else if (early == 2 && st.length_penalty > 0.f)
+                    done = worst >= best / powf((float)(lmode == 0 ? st.n0 + st.max_new : st.max_new), st.length_penalty);
+                else done = worst >= best / denom;
             }
             st.hyp_count[b] = cnt;
             st.hyp_worst[b] = worst;
@@ -274,6 +278,33 @@ __global__ void __launch_bounds__(256) k_kv_copy_span(BeamCall* call, int K, cha
     }
 }
 
+// k_kv_copy_span's whole-slot sibling (gvc_gpt_kv_fanout): blockIdx.y = pair, blockIdx.x strides over the (layer, k|v, head) runs; each
+// run copies positions [0, seq_len[src]) of one head in 16-byte vectors.  Column 0 of a pair also copies the slot's decode state,
+// columns 1 and 2 its parked logits / latent.  A pair with a slot outside [0, max_slots) or with src == dst copies nothing
+__global__ void __launch_bounds__(256) k_kv_fanout(const int32_t* src_slots, const int32_t* dst_slots, char* kv, int runs, int n_head,
+                                                   size_t lw_bytes, size_t slot_bytes, size_t head_bytes, int row_bytes, int max_seq,
+                                                   int max_slots, int32_t* seq_len, int32_t* mel_pos, float* slot_logits, int vocab,
+                                                   float* slot_latent, int d) {
+    const int src = src_slots[blockIdx.y], dst = dst_slots[blockIdx.y];
+    if (src < 0 || src >= max_slots || dst < 0 || dst >= max_slots || src == dst) return;
+    const int cur = min(seq_len[src], max_seq);
+    const size_t n16 = (size_t)max(cur, 0) * row_bytes / 16;
+    for (int r = blockIdx.x; r < runs; r += gridDim.x) {
+        const int lw = r / n_head, h = r - lw * n_head;
+        const uint4* s4 = reinterpret_cast<const uint4*>(kv + lw * lw_bytes + (size_t)src * slot_bytes + h * head_bytes);
+        uint4* d4 = reinterpret_cast<uint4*>(kv + lw * lw_bytes + (size_t)dst * slot_bytes + h * head_bytes);
+        for (size_t i = threadIdx.x; i < n16; i += blockDim.x) d4[i] = s4[i];
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        seq_len[dst] = seq_len[src];
+        mel_pos[dst] = mel_pos[src];
+    }
+    if (blockIdx.x == 1 % gridDim.x)
+        for (int i = threadIdx.x; i < vocab; i += blockDim.x) slot_logits[(size_t)dst * vocab + i] = slot_logits[(size_t)src * vocab + i];
+    if (blockIdx.x == 2 % gridDim.x)
+        for (int i = threadIdx.x; i < d; i += blockDim.x) slot_latent[(size_t)dst * d + i] = slot_latent[(size_t)src * d + i];
+}
+
 __global__ void k_beam_begin(BeamCall* dst, gvc_beam_state st, int i0, const int32_t* slots_in, int32_t* slot_table, float* logits,
                              const float* slot_logits) {
     const int BK = st.B * st.K, r = blockIdx.x;
@@ -300,7 +331,7 @@ int beam_check(const gvc_beam_state& st) {
                 GVC_ERR_ARG, "beam: B=%d K=%d vocab=%d outside the supported range (2 <= K <= 16, K*vocab <= %d, B*K <= 64)", st.B, st.K,
                 st.vocab, kBeamMaxN);
     GVC_REQUIRE(st.eos >= 0 && st.eos < st.vocab && st.n0 >= 1 && st.max_new >= 1 && st.ids_stride >= st.n0 + st.max_new &&
-                    (st.length_mode == 0 || st.length_mode == 1) && st.repetition_penalty > 0.f,
+                    (st.length_mode & 0xff) <= 1 && (st.length_mode >> 8) >= 0 && (st.length_mode >> 8) <= 2 && st.repetition_penalty > 0.f,
                 GVC_ERR_ARG, "beam: bad state (n0 %d, max_new %d, ids_stride %d, length_mode %d)", st.n0, st.max_new, st.ids_stride,
                 st.length_mode);
     GVC_REQUIRE(st.ids && st.scores && st.tokens && st.parents && st.done && st.hyp_score && st.hyp_len && st.hyp_tok && st.hyp_count &&
@@ -327,6 +358,20 @@ int launch_kv_copy_span(BeamCall* call, int B, int K, void* kv, int n_layer, int
     const size_t head_bytes = (size_t)max_seq * hd * esz, slot_bytes = head_bytes * n_head, lw_bytes = slot_bytes * max_slots;
     hipLaunchKernelGGL(k_kv_copy_span, dim3(64, B * (K - 1)), dim3(256), 0, s, call, K, (char*)kv, 2 * n_layer * n_head, n_head, lw_bytes,
                        slot_bytes, head_bytes, hd * esz, seq_len);
+    GVC_LAUNCH_CHECK();
+    return GVC_OK;
+}
+
+int launch_kv_fanout(const int32_t* src_slots, const int32_t* dst_slots, int n, void* kv, int n_layer, int n_head, int max_seq, int hd,
+                     int max_slots, int esz, int32_t* seq_len, int32_t* mel_pos, float* slot_logits, int vocab, float* slot_latent, int d,
+                     hipStream_t s) {
+    GVC_REQUIRE((hd * esz) % 16 == 0, GVC_ERR_UNSUPPORTED, "kv_fanout: head row of %d bytes is not a multiple of 16", hd * esz);
+    const size_t head_bytes = (size_t)max_seq * hd * esz, slot_bytes = head_bytes * n_head, lw_bytes = slot_bytes * max_slots;
+    // one workgroup per run (960 at full size; a run is ~12 KB at a 48-row prompt).  With 64 strided workgroups per pair the call took
+    // 58-62 us for 1, 3 and 7 pairs alike (profiles/nbest_time_fanout_grid64.json): its time did not follow its bytes
+    const int runs = 2 * n_layer * n_head;
+    hipLaunchKernelGGL(k_kv_fanout, dim3(runs < 1024 ? runs : 1024, n), dim3(256), 0, s, src_slots, dst_slots, (char*)kv, runs, n_head, lw_bytes,
+                       slot_bytes, head_bytes, hd * esz, max_seq, max_slots, seq_len, mel_pos, slot_logits, vocab, slot_latent, d);
     GVC_LAUNCH_CHECK();
     return GVC_OK;
 }

@@ -17,6 +17,7 @@
 #include "beam.h"
 #include "contrastive.h"
 #include "sampler.h"
+#include "seqscore.h"
 
 namespace gvc {
 
@@ -1289,6 +1290,27 @@ extern "C" int gvc_gpt_reset_slots(gvc_gpt* c, const int32_t* slots, int32_t B, 
     hipLaunchKernelGGL(k_set_state, dim3(cdiv(B, 64)), dim3(64), 0, (hipStream_t)sv, c->st, slots, B, 0, 0);
     GVC_LAUNCH_CHECK();
     return GVC_OK;
+}
+
+extern "C" int gvc_gpt_kv_fanout(gvc_gpt* c, const int32_t* src_slots, const int32_t* dst_slots, int32_t n, gvc_stream sv) {
+    int rc = check_ready(c);
+    if (rc) return rc;
+    GVC_REQUIRE(src_slots && dst_slots && n >= 1 && n <= c->dm.max_slots, GVC_ERR_ARG, "kv_fanout: n=%d outside [1,%d] or a null slot list",
+                n, c->dm.max_slots);
+    return launch_kv_fanout(src_slots, dst_slots, n, c->kv, c->dm.n_layer, c->dm.n_head, c->dm.max_seq, c->hd, c->dm.max_slots,
+                            c->kv_bf16 ? 2 : 4, c->st.seq_len, c->st.mel_pos, c->slot_logits, c->dm.vocab, c->slot_latent, c->dm.d_model,
+                            (hipStream_t)sv);
+}
+
+extern "C" int gvc_gpt_sequence_logprobs(gvc_gpt* c, const int32_t* tokens, int32_t tokens_stride, const float* latents, int32_t R, int32_t n,
+                                         int32_t stop_tok, double* logprob_out, int32_t* length_out, float* token_logprobs_out,
+                                         gvc_stream sv) {
+    int rc = check_ready(c);
+    if (rc) return rc;
+    GVC_REQUIRE(tokens && latents && logprob_out && length_out && R >= 1 && n >= 1 && tokens_stride >= n, GVC_ERR_ARG,
+                "sequence_logprobs: bad argument (R %d, n %d, tokens_stride %d)", R, n, tokens_stride);
+    return launch_sequence_logprobs(latents, tokens, tokens_stride, R, n, c->dm.d_model, c->dm.vocab, stop_tok, c->head_w, c->head_b, c->work,
+                                    c->work_cap, logprob_out, length_out, token_logprobs_out, (hipStream_t)sv);
 }
 
 extern "C" int gvc_gpt_prefix_embeddings(gvc_gpt* c, const float* cond, int32_t n_cond, const int32_t* codes,

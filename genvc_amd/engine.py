@@ -297,12 +297,22 @@ def logits_sets(kws, prompt_len, vocab, sampling=True, prompt_lens=None):
 BEAM_LENGTH_MODES = {"4.33": 0, "generated": 1}
 
 
+def beam_early_stopping(value):
+    """HF's early_stopping (False, True or "never") -> the device's code (gvc_beam_state, bits 8..15 of length_mode)"""
+    for v, code in ((False, 0), (True, 1), ("never", 2)):
+        if value is v or (isinstance(v, str) and value == v):
+            return code
+    raise ValueError(f"early_stopping must be a boolean or 'never', but is {value!r}")
+
+
 class BeamSearch:
     """device state of one deterministic beam search (gvc_beam_state, include/genvc_hip.h) over B items of K beams: double-buffered
     ids rows, running scores, the finished-hypothesis store, the copy lists of the last reorder.  `fake` [B, n0] are the fake ids of
-    compute_embeddings (every beam of an item starts from them)."""
+    compute_embeddings (every beam of an item starts from them).  early_stopping: False, True or "never" (the item-done test of
+    k_beam_select)."""
 
-    def __init__(self, fake, K, max_new, eos, vocab, length_penalty=1.0, repetition_penalty=1.0, length_mode="4.33", proc=None):
+    def __init__(self, fake, K, max_new, eos, vocab, length_penalty=1.0, repetition_penalty=1.0, length_mode="4.33", proc=None,
+                 early_stopping=False):
         if length_mode not in BEAM_LENGTH_MODES:
             raise ValueError(f"beam_length_mode must be one of {sorted(BEAM_LENGTH_MODES)}, not {length_mode!r}")
         dev = fake.device
@@ -326,7 +336,9 @@ class BeamSearch:
         self.copies = torch.zeros(B, K, 3, **i32)
         self.n_copies = torch.zeros(B, **i32)
         self.steps = 0
-        self.c = _lib.BeamState(B, K, int(vocab), int(eos), n0, W, int(max_new), BEAM_LENGTH_MODES[length_mode], float(length_penalty),
+        self.early_stopping = early_stopping
+        self.c = _lib.BeamState(B, K, int(vocab), int(eos), n0, W, int(max_new),
+                                BEAM_LENGTH_MODES[length_mode] | (beam_early_stopping(early_stopping) << 8), float(length_penalty),
                                 float(repetition_penalty), *[t.data_ptr() for t in (
                                     self.ids, self.scores, self.tokens, self.parents, self.done, self.hyp_score, self.hyp_len,
                                     self.hyp_tok, self.hyp_count, self.hyp_worst, self.copies, self.n_copies)])
@@ -334,11 +346,15 @@ class BeamSearch:
         self.length_penalty = float(length_penalty)
         self.proc = proc          # gvc_logits_processors (logits_processors()) or None
 
-    def finalize(self):
+    def finalize(self, num_return=1):
         """BeamSearchScorer.finalize: the running beams of the items not done join their hypotheses (length n0 + T in mode "4.33", T
-        in mode "generated"), the best hypothesis per item wins; rows are its tokens, then eos (= pad) up to the longest row + 1 (at
-        most max_new).  Returns (ids int64 [B, n], best scores [B]); once per call, host-side torch on the device"""
+        in mode "generated"), the num_return best hypotheses per item win, best first at rows b * num_return + j; rows are their
+        tokens, then eos (= pad) up to the longest returned row + 1 (at most max_new).  Returns (ids int64 [B * num_return, n], their
+        scores [B * num_return]); once per call, host-side torch on the device"""
         B, K, T = self.B, self.K, self.steps
+        N = int(num_return)
+        if not 1 <= N <= K:
+            raise ValueError(f"`num_return_sequences` ({N}) has to be smaller or equal to `num_beams` ({K}), and at least 1")
         L = self.n0 + T if BEAM_LENGTH_MODES[self.length_mode] == 0 else T
         ids = self.ids[T & 1].view(B, K, -1)[:, :, self.n0:self.n0 + T]
         done = self.done.bool().cpu()
@@ -357,16 +373,16 @@ class BeamSearch:
                     elif sc > min(s for s, _ in items):
                         del items[min(range(len(items)), key=lambda i: (items[i][0], i))]
                         items.append((sc, ("r", k)))
-            best.append(sorted(items, key=lambda x: x[0])[-1])
+            best.extend((b, it) for it in sorted(items, key=lambda x: x[0])[::-1][:N])      # (sorted_hyps.pop(): the best first)
         rows = []
-        for b, (sc, (kind, i)) in enumerate(best):
+        for b, (sc, (kind, i)) in best:
             rows.append(self.hyp_tok[b, i, :int(hl[b, i])] if kind == "h" else ids[b, i])
         width = min(max(int(r.shape[0]) for r in rows) + 1, self.max_new)
-        out = torch.full((B, width), self.eos, device=self.ids.device, dtype=torch.long)
+        out = torch.full((B * N, width), self.eos, device=self.ids.device, dtype=torch.long)
         for b, r in enumerate(rows):
             n = min(int(r.shape[0]), width)
             out[b, :n] = r[:n].long()
-        return out, torch.tensor([sc for sc, _ in best], dtype=torch.float64)
+        return out, torch.tensor([sc for _, (sc, _) in best], dtype=torch.float64)
 
 
 def beam_select(beam, logits, slots, t):
@@ -504,6 +520,33 @@ class GptEngine:
 
     def reset(self, slots):
         check(lib().gvc_gpt_reset_slots(self._h, ptr(_i32(slots)), slots.shape[0], stream()), "reset_slots")
+
+    def kv_fanout(self, src_slots, dst_slots):
+        """slot src_slots[i] -> slot dst_slots[i] (int32 device tensors of equal length): the cached K/V rows, the length / mel position
+        and the parked logits / latent, so the destination continues as the source would (include/genvc_hip.h: gvc_gpt_kv_fanout)"""
+        self._join_side()
+        n = int(src_slots.shape[0])
+        if int(dst_slots.shape[0]) != n:
+            raise ValueError(f"kv_fanout: {n} source slots for {int(dst_slots.shape[0])} destinations")
+        check(lib().gvc_gpt_kv_fanout(self._h, ptr(_i32(src_slots)), ptr(_i32(dst_slots)), n, stream()), "kv_fanout")
+
+    def sequence_logprobs(self, tokens, latents, token_logprobs=False):
+        """tokens int32 [R, >= n], latents fp32 [R, n, d] (a generation loop's latents_out) -> (logprob [R] float64, length [R] int32):
+        the summed log-probability of each row's tokens up to and including its first stop token, under the raw model distribution
+        (include/genvc_hip.h: gvc_gpt_sequence_logprobs).  token_logprobs=True: also the per-token terms [R, n] fp32"""
+        self._join_side()
+        latents = _f32(latents.contiguous())
+        tokens = _i32(tokens.contiguous())
+        R, n, d = latents.shape
+        if d != self.d or tokens.shape[0] != R or tokens.shape[1] < n or n < 1:
+            raise ValueError(f"sequence_logprobs: tokens {tuple(tokens.shape)} do not go with latents {tuple(latents.shape)} "
+                             f"(d_model {self.d})")
+        lp = torch.empty(R, device=latents.device, dtype=torch.float64)
+        ln = torch.empty(R, device=latents.device, dtype=torch.int32)
+        tl = torch.empty(R, n, device=latents.device, dtype=torch.float32) if token_logprobs else None
+        check(lib().gvc_gpt_sequence_logprobs(self._h, ptr(tokens), tokens.stride(0), ptr(latents), R, n, self.dims["stop_audio_token"],
+                                              ptr(lp), ptr(ln), ptr(tl), stream()), "sequence_logprobs")
+        return (lp, ln, tl) if token_logprobs else (lp, ln)
 
     def latents(self, slots, prefix_emb, gen_codes):
         self._join_side()

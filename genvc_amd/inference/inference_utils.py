@@ -57,15 +57,16 @@ def _vocode(model, latents):
 
 
 @torch.inference_mode()
-def _segment_latents(m, cond_latent, codes, gen, repass_latents):
+def _segment_latents(m, cond_latent, codes, gen, repass_latents, row=0):
     """the acoustic latents of one segment's n non-stop tokens.  The reference recomputes them with a second, teacher-forced forward pass
     over [cond | codes | start, gen, stop x 4] and trims it with `sub = -5` (inference_utils.py:71-76, gpt.py:375-508, :491, :508); row i of
     that pass is the hidden state that predicted token i -- the very vector the decode loop already produced at step i
     (stream_generator.py:865; SURVEY.md 8a row 12: equal to <= 4.8e-7).  Default: reuse the decode-time latents of `GPT.generate`
-    (`last_latents`, the EOS-step latent dropped: the re-pass has n rows); `repass_latents=True` runs the reference's second pass."""
+    (`last_latents`, the EOS-step latent dropped: the re-pass has n rows); `repass_latents=True` runs the reference's second pass.
+    row: the row of the generate call `gen` came from (a candidate of generate(num_return_sequences=N))."""
     n = int(gen.shape[-1])
     if not repass_latents and getattr(m.gpt, "last_latents", None) is not None and m.gpt.last_latents.shape[1] >= n:
-        return m.gpt.last_latents[:1, :n]
+        return m.gpt.last_latents[row:row + 1, :n]
     out_len = torch.tensor([n * m.config.model_args.gpt_code_stride_len], device=m.device)
     clen = torch.tensor([codes.shape[-1]], device=m.device)
     return m.gpt(codes, clen, gen.unsqueeze(0), out_len, cond_latents=cond_latent, return_latent=True)
@@ -73,12 +74,22 @@ def _segment_latents(m, cond_latent, codes, gen, repass_latents):
 
 @torch.inference_mode()
 def synthesize_utt(genVC_mdl, src_wav, tgt_audio, seg_len=6.0, return_details=False, repass_latents=False, num_beams=1,
-                   generate_kwargs=None):
+                   generate_kwargs=None, num_return_sequences=None):
     """non-streaming conversion, latent-level concatenation (reference :23-89).  num_beams = K > 1: every segment decodes with
     deterministic beam search (GPT.generate(num_beams=K, do_sample=False)); its latents come from the re-pass.
     generate_kwargs: more GPT.generate kwargs (the logits processors: min_new_tokens, no_repeat_ngram_size, ...; the
-    sampling warpers typical_p, epsilon_cutoff, eta_cutoff), merged into every segment's call"""
+    sampling warpers typical_p, epsilon_cutoff, eta_cutoff), merged into every segment's call.
+    num_return_sequences = N > 1 (the keyword, or in generate_kwargs): a LIST of N results, candidate j of the utterance being the
+    concatenation of candidate j of every segment (GPT.generate(num_return_sequences=N) per segment: one prefill, N rows); with
+    return_details each dict also carries "score", the sum over the segments of the candidate's score (sampling: sequence_logprobs,
+    the raw model distribution; beam search: the normalised beam score)."""
     m = genVC_mdl
+    from genvc_amd.layers.gpt import _num_return
+    gkw = dict(generate_kwargs or {})
+    if num_return_sequences is not None:
+        gkw["num_return_sequences"] = num_return_sequences
+    if _num_return(gkw) > 1:
+        return _synthesize_candidates(m, src_wav, tgt_audio, seg_len, return_details, repass_latents, num_beams, gkw)
     min_len = int(0.32 * m.content_sample_rate)
     src_wav = src_wav.to(m.device)
     seg = int(seg_len * m.content_sample_rate)
@@ -104,12 +115,50 @@ def synthesize_utt(genVC_mdl, src_wav, tgt_audio, seg_len=6.0, return_details=Fa
     return wav[0].squeeze()
 
 
+def _synthesize_candidates(m, src_wav, tgt_audio, seg_len, return_details, repass_latents, num_beams, gkw):
+    """synthesize_utt for num_return_sequences = N > 1 (gkw carries it)"""
+    N = int(gkw["num_return_sequences"])
+    min_len = int(0.32 * m.content_sample_rate)
+    src_wav = src_wav.to(m.device)
+    seg = int(seg_len * m.content_sample_rate)
+    cond_latent = m.get_gpt_cond_latents(tgt_audio.to(m.device), m.config.audio.sample_rate)
+    lats, codes_out, score = [[] for _ in range(N)], [[] for _ in range(N)], [0.0] * N
+    kw = _sampling_kwargs(m) if num_beams == 1 else dict(_sampling_kwargs(m), do_sample=False, num_beams=int(num_beams))
+    for src_seg in segments(src_wav, seg, min_len):
+        feat = m.content_extractor.extract_content_features(src_seg)
+        codes = m.content_dvae.get_codebook_indices(feat.transpose(1, 2))
+        rows = m.gpt.generate(cond_latent, codes, output_attentions=False, **dict(kw, **gkw))
+        sc = m.gpt.last_sequence_logprobs if m.gpt.last_latents is not None else m.gpt.last_beam_scores
+        for j in range(N):
+            score[j] += float(sc[j])
+            gen = rows[j][rows[j] != m.gpt.stop_audio_token]
+            if gen.numel() == 0:
+                continue
+            lats[j].append(_segment_latents(m, cond_latent, codes, gen, repass_latents, row=j))
+            codes_out[j].append(gen)
+    out = []
+    for j in range(N):
+        if not lats[j]:
+            empty = torch.zeros(0, device=m.device)
+            out.append(dict(latents=None, codes=[], wav=empty, score=score[j]) if return_details else empty)
+            continue
+        latents = torch.cat(lats[j], dim=1)
+        wav = _vocode(m, latents)
+        if return_details or wav is None:
+            out.append(dict(latents=latents, codes=codes_out[j], wav=None if wav is None else wav[0].squeeze(), score=score[j]))
+        else:
+            out.append(wav[0].squeeze())
+    return out
+
+
 @torch.inference_mode()
 def synthesize_utt_chunked(genVC_mdl, src_wav, tgt_audio, seg_len=6.0, repass_latents=False, generate_kwargs=None):
     """non-streaming conversion with waveform-level concatenation (reference :92-133): every segment goes through
     `genVC_mdl.inference` (trainers/hifigan_trainer.py:457-500) and the segment waveforms are joined by `handle_chunks`
     (1024 samples dropped from each, cross-fade over the previous tail).  generate_kwargs: as synthesize_utt"""
     m = genVC_mdl
+    from genvc_amd.layers.gpt import _single_return
+    _single_return(generate_kwargs or {}, "chunked (synthesize_utt_chunked)")      # (it cross-fades ONE waveform per segment)
     wav_gen_prev, wav_overlap = None, None
     pred_audios = []
     min_len = int(0.32 * m.content_sample_rate)

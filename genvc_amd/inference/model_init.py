@@ -93,7 +93,7 @@ class GenVCModel(nn.Module):
 
     @torch.inference_mode()
     def warmup(self, seg_len=1.0, streams=1, ref_seconds=3.0, stream_chunk_size=8, top_k=None, max_new_tokens=None, num_beams=1,
-               contrastive_top_k=None):
+               contrastive_top_k=None, num_return_sequences=1):
         """Everything the FIRST conversion of this shape would otherwise pay inside its latency window (the reference leaves warm-up
         to the user: /root/reference/infer.py:27-30 runs a conversion first).  For `streams` concurrent streams of `seg_len`-second
         segments and a `ref_seconds` reference:
@@ -103,6 +103,8 @@ class GenVCModel(nn.Module):
         num_beams = K > 1: also the beam step graphs of `streams` items x K beams (GPT.generate(num_beams=K, do_sample=False)).
         contrastive_top_k = K > 1: also the contrastive-search buffers and step graphs of `streams` items x K candidates
         (GPT.generate(top_k=K, do_sample=False, penalty_alpha=a)).
+        num_return_sequences = N > 1: also the step graphs of the streams * N rows an N-candidate call decodes
+        (GPT.generate(do_sample=True, num_return_sequences=N); the KV fan-out and the candidates' score need no warm-up).
         No token is generated and no KV slot is left occupied."""
         dev = self.device
         g = self.gpt
@@ -124,6 +126,8 @@ class GenVCModel(nn.Module):
         # that range (its thresholds are its own: gvc_gpt_warmup_range)
         hi = min(n0 + max_new, eng.dims["max_seq"] - 1)
         eng.warmup_range(streams, min(n0 + grp, hi), hi, top_k)
+        if int(num_return_sequences) > 1:
+            eng.warmup_range(streams * int(num_return_sequences), min(n0 + grp, hi), hi, top_k)
         if int(num_beams) > 1:
             eng.warmup_beam(streams, int(num_beams), hi)
         if contrastive_top_k is not None and int(contrastive_top_k) > 1:
@@ -137,26 +141,59 @@ class GenVCModel(nn.Module):
 
     @torch.no_grad()
     def inference(self, src_audio, cond_latent, do_sample=True, top_p=0.85, top_k=15, temperature=0.75, num_beams=1,
-                  length_penalty=1.0, repetition_penalty=10.0, output_attentions=False, repass_latents=False, generate_kwargs=None):
+                  length_penalty=1.0, repetition_penalty=10.0, output_attentions=False, repass_latents=False, generate_kwargs=None,
+                  num_return_sequences=None):
         """reference trainers/hifigan_trainer.py:457-500: one source segment [1,T] + conditioning latents -> waveform
         [1,1,1024 n]: ContentVec -> content codes -> generate -> strip stop tokens -> latent re-pass -> x4 linear
         interpolation -> HiFi-GAN.  (The reference's 0-d collapse at exactly one non-stop token, SURVEY appendix B.9, is
         guarded: boolean indexing keeps the dimension.)  The latents are the decode loop's own unless `repass_latents=True`
         (inference_utils._segment_latents).  generate_kwargs (extension): more GPT.generate kwargs (the logits processors:
-        min_new_tokens, no_repeat_ngram_size, ...; typical_p, epsilon_cutoff, eta_cutoff), merged over the ones above."""
+        min_new_tokens, no_repeat_ngram_size, ...; typical_p, epsilon_cutoff, eta_cutoff), merged over the ones above.
+        num_return_sequences = N > 1 (the keyword, or in generate_kwargs; sampling only): a LIST of N waveforms, the candidates of
+        GPT.generate(num_return_sequences=N) in row order, each stripped of its stop tokens and vocoded from the decode loop's own
+        latents (or the re-pass with `repass_latents=True`); `last_sequence_logprobs` / `last_sequence_lengths` hold their scores
+        (GPT.sequence_logprobs: the raw model distribution).  N = 1 returns the one waveform, not a list."""
         feat = self.content_extractor.extract_content_features(src_audio)
         codes = self.content_dvae.get_codebook_indices(feat.transpose(1, 2))
         kw = dict(do_sample=do_sample, top_p=top_p, top_k=top_k, temperature=temperature, num_beams=num_beams,
                   length_penalty=length_penalty, repetition_penalty=repetition_penalty, output_attentions=output_attentions)
-        gen = self.gpt.generate(cond_latent, codes, **dict(kw, **(generate_kwargs or {})))[0]
+        kw.update(generate_kwargs or {})
+        if num_return_sequences is not None:
+            kw["num_return_sequences"] = num_return_sequences
+        from genvc_amd.layers.gpt import _num_return
+        if _num_return(kw) > 1:
+            return self._inference_candidates(cond_latent, codes, kw, repass_latents)
+        gen = self.gpt.generate(cond_latent, codes, **kw)[0]
         gen = gen[gen != self.gpt.stop_audio_token]
         if gen.numel() == 0:
             return torch.zeros(1, 1, 0, device=self.device)
+        return self._vocode_segment(cond_latent, codes, gen, repass_latents)
+
+    def _vocode_segment(self, cond_latent, codes, gen, repass_latents, row=0):
+        """the stop-free tokens `gen` of row `row` of the last generate call -> waveform [1, 1, 1024 n] (latents, x4 linear
+        interpolation, HiFi-GAN: trainers/hifigan_trainer.py:489-500)"""
         from genvc_amd.inference.inference_utils import _segment_latents
-        lat = _segment_latents(self, cond_latent, codes, gen, repass_latents)
+        lat = _segment_latents(self, cond_latent, codes, gen, repass_latents, row=row)
         mel_input = torch.nn.functional.interpolate(lat.transpose(1, 2), scale_factor=[self.hifigan_scale_factor],
                                                     mode="linear").squeeze(1)
         return self.hifigan.forward(mel_input)
+
+    def _inference_candidates(self, cond_latent, codes, kw, repass_latents):
+        """inference() for num_return_sequences = N > 1: one generate call, then each candidate row vocoded on its own"""
+        g = self.gpt
+        rows = g.generate(cond_latent, codes, **kw)
+        sampled = g.last_latents is not None
+        self.last_sequence_logprobs = g.last_sequence_logprobs if sampled else None
+        self.last_sequence_lengths = g.last_sequence_lengths if sampled else None
+        self.last_beam_scores = None if sampled else g.last_beam_scores
+        out = []
+        for j in range(rows.shape[0]):
+            gen = rows[j][rows[j] != g.stop_audio_token]
+            if gen.numel() == 0:
+                out.append(torch.zeros(1, 1, 0, device=self.device))
+            else:
+                out.append(self._vocode_segment(cond_latent, codes, gen, repass_latents, row=j))
+        return out
 
 
 class _CondFuture:

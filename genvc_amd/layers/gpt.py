@@ -11,7 +11,7 @@ import torch
 from torch import nn
 
 from .._lib import GenvcHipError
-from ..engine import (BEAM_LENGTH_MODES, MAX_CONTRASTIVE_K, PROC_KWARGS, WARP_KWARGS, BeamSearch, ContrastiveSearch, GptEngine, WarperSets,
+from ..engine import (BEAM_LENGTH_MODES, beam_early_stopping, MAX_CONTRASTIVE_K, PROC_KWARGS, WARP_KWARGS, BeamSearch, ContrastiveSearch, GptEngine, WarperSets,
                       check_proc_kwargs, logits_processors, logits_sets, logits_warpers, sample_params)
 from .perceiver_encoder import PerceiverResampler
 
@@ -30,9 +30,38 @@ def _no_beams(kw, where):
                                   "(the reference streams with num_beams=1 only, inference_utils.py:62,178)")
 
 
+def _num_return(kw):
+    """num_return_sequences of the call (absent or None: 1); below 1 raises ValueError"""
+    n = kw.get("num_return_sequences")
+    n = 1 if n is None else int(n)
+    if n < 1:
+        raise ValueError(f"num_return_sequences has to be at least 1, but is {kw.get('num_return_sequences')}")
+    return n
+
+
+def _single_return(kw, where):
+    """the paths that keep one row per stream: num_return_sequences > 1 raises, naming the path"""
+    if _num_return(kw) != 1:
+        raise NotImplementedError(f"num_return_sequences={kw.get('num_return_sequences')} is not on the {where} path: GPT.generate serves "
+                                  "it (one prefill per item, fanned out to the candidates' KV slots)")
+
+
+def _sample_return_kwargs(kw, B=None, max_slots=None):
+    """num_return_sequences = N of a call that is neither contrastive nor beam search, validated: N > 1 needs sampling (ValueError for
+    greedy decoding, as HF raises it); with B and max_slots given, B * N > max_slots raises ValueError.  -> N"""
+    N = _num_return(kw)
+    if N > 1 and not kw.get("do_sample", True):
+        raise ValueError(f"num_return_sequences has to be 1, but is {N} when doing greedy search")
+    if N > 1 and B is not None and max_slots is not None and B * N > max_slots:
+        raise ValueError(f"sampling {N} sequences for each of {B} items needs {B * N} KV slots; the context has {max_slots} "
+                         "(init_gpt_for_inference(max_slots=...))")
+    return N
+
+
 def _beam_kwargs(kw):
     """the modes of HF generate(num_beams > 1) this build does not serve raise NotImplementedError, naming the mode; returns the
-    (K, length_penalty, repetition_penalty, beam_length_mode) of a deterministic beam search"""
+    (K, length_penalty, repetition_penalty, beam_length_mode) of a deterministic beam search.  num_return_sequences outside [1, K] and an
+    early_stopping other than False, True or "never" raise ValueError (HF's rules); _beam_returns gives the two"""
     K = int(kw.get("num_beams", 1))
     if kw.get("do_sample", True):
         raise NotImplementedError(f"beam sampling (do_sample=True, num_beams={K}) is not implemented: deterministic beam search needs "
@@ -41,14 +70,22 @@ def _beam_kwargs(kw):
         raise NotImplementedError("group / diverse beam search (num_beam_groups > 1, diversity_penalty) is not implemented")
     if kw.get("constraints") or kw.get("force_words_ids"):
         raise NotImplementedError("constrained beam search (constraints, force_words_ids) is not implemented")
-    if int(kw.get("num_return_sequences", 1) or 1) != 1:
-        raise NotImplementedError("beam search returns one sequence per item (num_return_sequences=1)")
-    if kw.get("early_stopping", False) is not False:
-        raise NotImplementedError("beam search runs with early_stopping=False (the GenerationConfig default) only")
+    _beam_returns(kw)
     mode = kw.get("beam_length_mode", "4.33")
     if mode not in BEAM_LENGTH_MODES:
         raise ValueError(f"beam_length_mode must be one of {sorted(BEAM_LENGTH_MODES)}, not {mode!r}")
     return K, float(kw.get("length_penalty", 1.0)), float(kw.get("repetition_penalty", 1.0)), mode
+
+
+def _beam_returns(kw):
+    """(num_return_sequences, early_stopping) of a beam search, validated as HF validates them"""
+    K = int(kw.get("num_beams", 1))
+    N = _num_return(kw)
+    if N > K:
+        raise ValueError(f"`num_return_sequences` ({N}) has to be smaller or equal to `num_beams` ({K}).")
+    early = kw.get("early_stopping", False)
+    beam_early_stopping(early)
+    return N, early
 
 
 def _contrastive_mode(kw):
@@ -283,8 +320,10 @@ class GPT(nn.Module):
         ids[:, -1] = self.start_audio_token
         return ids
 
-    def _start(self, fake_inputs, kw):
-        """prefill + device-side loop state for the stored prefix"""
+    def _start(self, fake_inputs, kw, fan=1):
+        """prefill + device-side loop state for the stored prefix.  fan = N > 1 (generate(num_return_sequences=N)): fake_inputs has N
+        rows per item of the prefix, row b*N + j the j-th candidate of item b; item b is prefilled once, into slot b*N, and fanned out
+        to the slots of its other candidates (engine.kv_fanout)"""
         _no_beams(kw, "streaming (get_generator)")
         _no_contrastive(kw, "streaming (get_generator)")
         B, n0 = fake_inputs.shape
@@ -309,6 +348,11 @@ class GPT(nn.Module):
         st["warp"] = None if warp is None else WarperSets.one(st["proc"], warp, B)
         # `cached_cond_rows` (extension): the leading rows of the prefix -- the conditioning latents, identical for every
         # segment of an utterance -- are still in the KV cache from the previous segment's prefill of these slots
+        if fan > 1:
+            src = slots[::fan].contiguous()
+            self.engine.prefill(src, self._prefix, want_outputs=False, n_cached=int(kw.get("cached_cond_rows", 0)))
+            self.engine.kv_fanout(src.repeat_interleave(fan - 1), slots.view(-1, fan)[:, 1:].reshape(-1).contiguous())
+            return st
         self.engine.prefill(slots, self._prefix, want_outputs=False, n_cached=int(kw.get("cached_cond_rows", 0)))
         return st
 
@@ -335,19 +379,28 @@ class GPT(nn.Module):
         `group` (extra kwarg) = decode steps per host check of the finished flags.
         num_beams = K > 1 with do_sample=False: deterministic beam search on the device (_generate_beams).
         top_k = K > 1 with do_sample=False and penalty_alpha > 0: contrastive search on the device (_generate_contrastive), before
-        num_beams as in transformers 4.33."""
+        num_beams as in transformers 4.33.
+        num_return_sequences = N > 1 when sampling: int64 [B*N, n], row b*N + j the j-th candidate of item b, as HF's input expansion
+        (repeat_interleave(N)) orders them -- and draws them: the sampler keys a draw by (seed, step, row).  Item b is prefilled once
+        and its KV slot fanned out to its candidates' slots (needs B*N <= the context's KV slots, ValueError otherwise); the B*N rows
+        then decode together.  `last_latents` is [B*N, n, d]; `last_sequence_logprobs` / `last_sequence_lengths` hold
+        sequence_logprobs() of the candidates (an extension: a score to rank them by).  Greedy decoding with N > 1 raises ValueError."""
+        _num_return(generate_kwargs)
         if _contrastive_kwargs(generate_kwargs) is not None:
             return self._generate_contrastive(cond_latents, text_inputs, generate_kwargs)
         if int(generate_kwargs.get("num_beams", 1) or 1) > 1:
             return self._generate_beams(cond_latents, text_inputs, generate_kwargs)
+        N = _sample_return_kwargs(generate_kwargs, int(text_inputs.shape[0]), self.max_slots)
         fake = self.compute_embeddings(cond_latents, text_inputs)
+        if N > 1:
+            fake = fake.repeat_interleave(N, 0)
         group = generate_kwargs.pop("group", 16)
 
         attempt = []
 
         def run():
             # (a retry after a hand-off time-out prefills in full: the reset slots have lost any cached conditioning rows)
-            st = self._start(fake, dict(generate_kwargs, cached_cond_rows=0) if attempt else generate_kwargs)
+            st = self._start(fake, dict(generate_kwargs, cached_cond_rows=0) if attempt else generate_kwargs, fan=N)
             attempt.append(1)
             while not self._advance(st, group):
                 pass
@@ -357,10 +410,27 @@ class GPT(nn.Module):
         toks = st["toks"][:, :st["done"]].long()
         n = self._stop_len(toks)
         self.last_latents = st["lats"][:, :n]
+        self.last_sequence_logprobs = self.last_sequence_lengths = None
+        if N > 1:
+            self.last_sequence_logprobs, self.last_sequence_lengths = self.sequence_logprobs(toks[:, :n], self.last_latents)
         return toks[:, :n]
 
+    @torch.inference_mode()
+    def sequence_logprobs(self, tokens, latents):
+        """Extension (the reference has no such score): tokens [R, n] and the generation loop's latents [R, n, d] (`last_latents`) ->
+        (logprob [R] float64, length [R] int64), logprob[r] = sum over t < length[r] of log_softmax(mel_head(latents[r, t]))[tokens[r, t]],
+        length[r] up to and including row r's first stop token (n without one).  The loop's latents are final_norm(ln_f(h)), so mel_head of
+        them is the logits row each token was chosen from: this is the RAW model distribution -- no repetition penalty, logits
+        processor or warper, whatever the call that produced the tokens used.  On the device (include/genvc_hip.h:
+        gvc_gpt_sequence_logprobs)."""
+        self._need_engine()
+        n = int(latents.shape[1])
+        lp, ln = self.engine.sequence_logprobs(tokens[:, :n].to(torch.int32), latents.to(torch.float32))
+        return lp, ln.long()
+
     def _generate_beams(self, cond_latents, text_inputs, generate_kwargs):
-        """HF generate(num_beams=K, do_sample=False) semantics (length_penalty, early_stopping=False, num_return_sequences=1, the
+        """HF generate(num_beams=K, do_sample=False) semantics (length_penalty, early_stopping False / True / "never",
+        num_return_sequences = N <= K: the N best hypotheses of item b, best first, at rows b*N + j, `last_beam_scores` [B*N]; the
         repetition penalty on log-probs, pad = eos, max_length = max_gen_mel_tokens + prompt): item b is prefilled ONCE into KV slot
         b*K; every step runs [select -> KV span copies -> decode step over B*K rows] from a captured graph (include/genvc_hip.h:
         gvc_gpt_beam_generate), the host looks at the done flags once per `group` steps; the hypothesis store is finalised on the
@@ -370,6 +440,7 @@ class GPT(nn.Module):
         `last_latents` is None (the caller's latents come from the teacher-forced re-pass, hifigan_trainer.py:489-494)."""
         kw = dict(generate_kwargs)
         K, lp, rep, mode = _beam_kwargs(kw)
+        N, early = _beam_returns(kw)
         self._need_engine()
         group = int(kw.pop("group", 16))
         B = int(text_inputs.shape[0])
@@ -385,7 +456,8 @@ class GPT(nn.Module):
         def run():
             slots = torch.arange(B * K, device=dev, dtype=torch.int32)
             self.engine.prefill(slots[::K].contiguous(), self._prefix, want_outputs=False)      # each item once; the first step fans out
-            beam = BeamSearch(fake, K, max_new, self.stop_audio_token, self.num_audio_tokens, lp, rep, mode, **_proc_arg(proc))
+            beam = BeamSearch(fake, K, max_new, self.stop_audio_token, self.num_audio_tokens, lp, rep, mode, early_stopping=early,
+                              **_proc_arg(proc))
             while beam.steps < max_new:
                 n = min(group, max_new - beam.steps)
                 self.engine.beam_generate(slots, beam, n, max_keys=n0 + beam.steps + n)
@@ -393,7 +465,7 @@ class GPT(nn.Module):
                 self.engine.health()          # (the .item() above synchronised)
                 if stop:
                     break
-            return beam.finalize()
+            return beam.finalize(N)
         ids, scores = self._recovering(B * K, run)
         self.last_latents = None
         self.last_beam_scores = scores
@@ -458,6 +530,7 @@ class GPT(nn.Module):
         Returns a list of int64 [B_i, n_i] (reference gpt.py:594-609 per group)."""
         _no_beams(generate_kwargs, "grouped (generate_groups)")
         _no_contrastive(generate_kwargs, "grouped (generate_groups)")
+        _single_return(generate_kwargs, "grouped (generate_groups)")
         kw = dict(generate_kwargs)
         gkw = None
         if group_kwargs is not None:
@@ -607,6 +680,7 @@ class GPT(nn.Module):
         row of a decode call carrying its job's set (gvc_gpt_generate_proc_sets, or gvc_gpt_generate_warp when a warper is on)."""
         _no_beams(generate_kwargs, "rolling (generate_rolling)")
         _no_contrastive(generate_kwargs, "rolling (generate_rolling)")
+        _single_return(generate_kwargs, "rolling (generate_rolling)")
         kw = dict(generate_kwargs)
         jkw = None
         if job_kwargs is not None:
@@ -755,6 +829,7 @@ class GPT(nn.Module):
         inference_utils.py:195) with one host check of the finished flags per group."""
         _no_beams(generate_kwargs, "streaming (get_generator)")
         _no_contrastive(generate_kwargs, "streaming (get_generator)")
+        _single_return(generate_kwargs, "streaming (get_generator)")
         self._need_engine()
         group = generate_kwargs.pop("stream_group", 8)
         B = int(fake_inputs.shape[0])

@@ -145,6 +145,27 @@ int gvc_gpt_decode_step(gvc_gpt* ctx, const int32_t* slots, int32_t B, const int
  * nothing (used by tests). */
 int gvc_gpt_reset_slots(gvc_gpt* ctx, const int32_t* slots, int32_t B, gvc_stream s);
 
+/* KV fan-out: pair i copies slot src_slots[i] to slot dst_slots[i] (device arrays of n entries, n <= max_slots): positions
+ * [0, length of the source) of every (layer, k|v, head) run of the cache in 16-byte accesses (fp32 and bf16 caches alike), the slot's
+ * length and mel position, and the logits / latent its last prefill or generate call parked.  Afterwards the destination continues
+ * exactly as the source would: N candidates of one item cost one prefill (GPT.generate(num_return_sequences=N)).  One launch over a
+ * fixed grid, no allocation.  A destination must not be the source or destination of another pair; a pair with a slot outside
+ * [0, max_slots) or with src == dst copies nothing. */
+int gvc_gpt_kv_fanout(gvc_gpt* ctx, const int32_t* src_slots, const int32_t* dst_slots, int32_t n, gvc_stream s);
+
+/* Log-probability of generated sequences under the RAW model distribution (an extension: the reference has no such score):
+ * logprob_out[r] = sum over t < length_out[r] of log_softmax(mel_head(latents[r][t]))[tokens[r][t]], where length_out[r] runs up to and
+ * including the first stop_tok of row r, or is n without one.  latents [R][n][d] (contiguous) are the generation loop's
+ * final_norm(ln_f(h)) rows (latents_out of gvc_gpt_generate*), so mel_head of row t is the logits row token t was chosen from -- before
+ * any repetition penalty, logits processor or warper.  With bf16 weight storage (weight_dtype >= 1) the bound mel_head is held rounded to
+ * bf16 in both its copies, so the score uses the very weights the loop drew from; the loop's GEMV and this GEMM sum in different orders,
+ * so the logits agree to fp32 rounding, not bit for bit (in every mode).  tokens int32 [R][tokens_stride >= n].  token_logprobs_out (nullable) [R][n]:
+ * the per-token terms, 0 from length_out[r] on.  The fp32 head GEMM on the bound mel_head (into the context's scratch, in chunks of whole
+ * sequences) followed by a row kernel (max, log-sum-exp with the accurate expf / logf, the sum in double in a fixed order).  No
+ * allocation, no synchronisation; not part of any captured step graph. */
+int gvc_gpt_sequence_logprobs(gvc_gpt* ctx, const int32_t* tokens, int32_t tokens_stride, const float* latents, int32_t R, int32_t n,
+                              int32_t stop_tok, double* logprob_out, int32_t* length_out, float* token_logprobs_out, gvc_stream s);
+
 /* Teacher-forced latent re-pass, GPT.forward(..., cond_latents=, return_latent=True)
  * (gpt.py:375-508, call site inference_utils.py:71-76): rows = [prefix_emb (P) | start, codes(n),
  * stop x4]; out[b] = final_norm(ln_f(h)) of the first n mel rows -> [B,n,d].  Uses scratch slot
@@ -244,6 +265,11 @@ int gvc_gpt_generate_rows(gvc_gpt* ctx, const int32_t* slots, int32_t B, int32_t
  * >= best / len ** length_penalty.  length_mode 0 ("4.33", transformers 4.33 = the reference's pin): len = n0 + t for both, best =
  * the best candidate of the step; 1 ("generated", transformers >= 4.50): len = t + 1 for both, best = the best next beam; t =
  * tokens generated before the step.  A done item keeps its beams: tokens = eos, parents = identity, no copies.
+ * early_stopping (bits 8..15 of length_mode, so the struct keeps its size and a caller that sets the mode alone gets False): 0 False,
+ * the test above; 1 True, the item is done as soon as its set is full (BeamHypotheses.is_done of 4.33; in the installed _beam_search a
+ * full set takes no further hypothesis); 2 "never", the test above with len replaced by the longest possible length when
+ * length_penalty > 0 -- n0 + max_new in mode 0 (4.33's max_length), max_new in mode 1 (max_length - decoder_prompt_len) -- and
+ * unchanged otherwise.  The hypotheses' own normalisation is not affected.
  * ------------------------------------------------------------------------------------------ */
 typedef struct {
     int32_t B, K;                   /* items, beams per item: 2 <= K <= 16, K * vocab <= 16 * 1026 */
@@ -251,7 +277,7 @@ typedef struct {
     int32_t n0;                     /* prompt length = positions of the fake ids (compute_embeddings) = KV positions after the prefill */
     int32_t ids_stride;             /* >= n0 + max_new */
     int32_t max_new;                /* hypothesis capacity in tokens (max_gen_mel_tokens) */
-    int32_t length_mode;            /* 0 "4.33", 1 "generated" */
+    int32_t length_mode;            /* bits 0..7: 0 "4.33", 1 "generated"; bits 8..15: early_stopping 0 False, 1 True, 2 "never" */
     float length_penalty, repetition_penalty;
     int32_t* ids;                   /* [2][B*K][ids_stride] input_ids rows, double-buffered: step t reads buffer t & 1 (positions
                                        [0, n0 + t)) and writes buffer (t + 1) & 1 gathered by parent, plus the new token at n0 + t */

@@ -6,6 +6,7 @@ ships with the reference: run the same pipeline on deterministic synthetic weigh
 The waveform is written like the reference does (24 kHz PCM16); --save_tokens also stores the codec tokens/latents.
 """
 import argparse
+import os
 
 import torch
 
@@ -33,6 +34,9 @@ if __name__ == "__main__":
                         help="non-streaming only: > 1 decodes with deterministic beam search (do_sample=False) of this width")
     parser.add_argument("--penalty_alpha", type=float, default=None,
                         help="non-streaming only: > 0 decodes with contrastive search (do_sample=False) over --top_k candidates (2..16)")
+    parser.add_argument("--num_return_sequences", type=int, default=1,
+                        help="non-streaming only: N > 1 draws N candidates per segment from one prefill (or keeps the N best beams with "
+                             "--num_beams >= N) and writes <output stem>_<j>.wav, printing one score per file")
     parser.add_argument("--min_new_tokens", type=int, default=None, help="no stop token before this many tokens per segment")
     parser.add_argument("--no_repeat_ngram_size", type=int, default=None,
                         help="no n-gram of codec tokens (fake prompt included) occurs twice in a segment (1..8)")
@@ -45,6 +49,10 @@ if __name__ == "__main__":
     args = parser.parse_args()
     if args.num_beams < 1 or (args.streaming and args.num_beams != 1):
         raise SystemExit("--num_beams must be >= 1, and 1 with --streaming")
+    if args.num_return_sequences < 1 or (args.num_return_sequences > 1 and (args.streaming or args.penalty_alpha is not None)):
+        raise SystemExit("--num_return_sequences must be >= 1, and 1 with --streaming or --penalty_alpha")
+    if args.num_beams > 1 and args.num_return_sequences > args.num_beams:
+        raise SystemExit("--num_return_sequences must not exceed --num_beams")
     if args.penalty_alpha is not None:
         if args.streaming or not args.penalty_alpha > 0.0 or args.penalty_alpha == float("inf") or not 2 <= args.top_k <= 16:
             raise SystemExit("--penalty_alpha must be finite and > 0, non-streaming, with --top_k in [2, 16]")
@@ -80,25 +88,44 @@ if __name__ == "__main__":
         gen_kw.update(do_sample=False, penalty_alpha=args.penalty_alpha, top_k=args.top_k)
         if model.gpt.max_slots < args.top_k:           # one KV slot per candidate
             model.gpt.init_gpt_for_inference(max_slots=args.top_k, max_rows=max(4096, 128 * args.top_k), weight_dtype=args.weights)
+    if args.num_beams == 1 and model.gpt.max_slots < args.num_return_sequences:     # sampling: one KV slot per candidate
+        model.gpt.init_gpt_for_inference(max_slots=args.num_return_sequences, max_rows=max(4096, 128 * args.num_return_sequences),
+                                         weight_dtype=args.weights)
     src_wav = load_audio(args.src_wav, model.content_sample_rate, device=args.device)
     ref_audio = load_audio(args.ref_audio, model.config.audio.sample_rate, device=args.device)
     if src_wav is None or ref_audio is None:
         raise SystemExit("could not load the input audio")
 
-    if args.streaming:
-        out = synthesize_utt_streaming(model, src_wav, ref_audio, seg_len=args.seg_len,
-                                       stream_chunk_size=args.stream_chunk_size, return_details=True, generate_kwargs=gen_kw or None)
-        toks = torch.cat(out["tokens"], 1)
-        lat = torch.cat(out["latents"], 1)
+    if args.num_return_sequences > 1:
+        outs = synthesize_utt(model, src_wav, ref_audio, seg_len=args.seg_len, return_details=True, num_beams=args.num_beams,
+                              generate_kwargs=gen_kw or None, num_return_sequences=args.num_return_sequences)
+        stem, ext = os.path.splitext(args.output_path)
+        what = "beam score" if args.num_beams > 1 else "log-probability (raw model distribution)"
+        for j, o in enumerate(outs):
+            path = f"{stem}_{j}{ext}"
+            n = sum(int(c.numel()) for c in o["codes"])
+            if o["wav"] is not None and n:
+                save_wav(path, o["wav"], config.audio.sample_rate)
+            print(f"{path}: {n} codec tokens, {what} {o['score']:.4f}")
+        if args.save_tokens:
+            torch.save([dict(tokens=torch.cat(o["codes"]).cpu() if o["codes"] else None,
+                             latents=None if o["latents"] is None else o["latents"].cpu(), score=o["score"]) for o in outs],
+                       args.save_tokens)
     else:
-        out = synthesize_utt(model, src_wav, ref_audio, seg_len=args.seg_len, return_details=True, num_beams=args.num_beams,
-                             generate_kwargs=gen_kw or None)
-        toks = torch.cat(out["codes"]).unsqueeze(0)
-        lat = out["latents"]
-    print(f"generated {toks.shape[-1]} codec tokens, latents {tuple(lat.shape)}")
-    if out["wav"] is not None:
-        save_wav(args.output_path, out["wav"], config.audio.sample_rate)
-    else:
-        print("no vocoder in the model: waveform not written")
-    if args.save_tokens:
-        torch.save(dict(tokens=toks.cpu(), latents=lat.cpu()), args.save_tokens)
+        if args.streaming:
+            out = synthesize_utt_streaming(model, src_wav, ref_audio, seg_len=args.seg_len,
+                                           stream_chunk_size=args.stream_chunk_size, return_details=True, generate_kwargs=gen_kw or None)
+            toks = torch.cat(out["tokens"], 1)
+            lat = torch.cat(out["latents"], 1)
+        else:
+            out = synthesize_utt(model, src_wav, ref_audio, seg_len=args.seg_len, return_details=True, num_beams=args.num_beams,
+                                 generate_kwargs=gen_kw or None)
+            toks = torch.cat(out["codes"]).unsqueeze(0)
+            lat = out["latents"]
+        print(f"generated {toks.shape[-1]} codec tokens, latents {tuple(lat.shape)}")
+        if out["wav"] is not None:
+            save_wav(args.output_path, out["wav"], config.audio.sample_rate)
+        else:
+            print("no vocoder in the model: waveform not written")
+        if args.save_tokens:
+            torch.save(dict(tokens=toks.cpu(), latents=lat.cpu()), args.save_tokens)
