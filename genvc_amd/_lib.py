@@ -131,6 +131,7 @@ _SIGNATURES = {
                                         C.c_int32, _P, C.c_int32, _P, C.c_int32, _P]),
     "gvc_gpt_decode_variant": (C.c_int, [_P]),
     "gvc_gpt_rows_step_launches": (C.c_longlong, [_P]),
+    "gvc_gpt_one_stream_steps": (C.c_longlong, [_P]),
     "gvc_gpt_health": (C.c_int, [_P]),
     "gvc_gpt_warmup": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32]),
     "gvc_gpt_warmup_range": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),

@@ -33,11 +33,11 @@ int launch_beam_select(const gvc_beam_state& st, const gvc_logits_processors* pr
 int launch_kv_copy_span(BeamCall* call, int B, int K, void* kv, int n_layer, int n_head, int max_seq, int hd, int max_slots, int esz,
                         const int32_t* seq_len, hipStream_t s);
 // whole-slot fan-out (gvc_gpt_kv_fanout): pair i copies positions [0, seq_len[src_slots[i]]) of every (layer, k|v, head) run of the same
-// cache layout from slot src_slots[i] to slot dst_slots[i], with the slot's seq_len / mel_pos and its parked logits / latent; a fixed
+// cache layout from slot src_slots[i] to slot dst_slots[i], with the slot's seq_len / mel_pos / pending token and its parked logits / latent; a fixed
 // grid of (runs, n pairs) workgroups (device arrays)
 int launch_kv_fanout(const int32_t* src_slots, const int32_t* dst_slots, int n, void* kv, int n_layer, int n_head, int max_seq, int hd,
                      int max_slots, int esz, int32_t* seq_len, int32_t* mel_pos, float* slot_logits, int vocab, float* slot_latent, int d,
-                     hipStream_t s);
+                     int32_t* pending, hipStream_t s);
 // start / end of a gvc_gpt_beam_generate call: store the call state (and the processors, host proc nullable), un-park (park) the
 // logits of every beam row
 int launch_beam_begin(BeamCall* dst, const gvc_beam_state& st, const gvc_logits_processors* proc, int i0, const int32_t* slots_in, int32_t* slot_table, float* logits,

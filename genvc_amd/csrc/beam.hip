@@ -280,11 +280,11 @@ __global__ void __launch_bounds__(256) k_kv_copy_span(BeamCall* call, int K, cha
 
 // k_kv_copy_span's whole-slot sibling (gvc_gpt_kv_fanout): blockIdx.y = pair, blockIdx.x strides over the (layer, k|v, head) runs; each
 // run copies positions [0, seq_len[src]) of one head in 16-byte vectors.  Column 0 of a pair also copies the slot's decode state,
-// columns 1 and 2 its parked logits / latent.  A pair with a slot outside [0, max_slots) or with src == dst copies nothing
+// (the pending token of a deferred decode included), columns 1 and 2 its parked logits / latent.  A pair with a slot outside [0, max_slots) or with src == dst copies nothing
 __global__ void __launch_bounds__(256) k_kv_fanout(const int32_t* src_slots, const int32_t* dst_slots, char* kv, int runs, int n_head,
                                                    size_t lw_bytes, size_t slot_bytes, size_t head_bytes, int row_bytes, int max_seq,
                                                    int max_slots, int32_t* seq_len, int32_t* mel_pos, float* slot_logits, int vocab,
-                                                   float* slot_latent, int d) {
+                                                   float* slot_latent, int d, int32_t* pending) {
     const int src = src_slots[blockIdx.y], dst = dst_slots[blockIdx.y];
     if (src < 0 || src >= max_slots || dst < 0 || dst >= max_slots || src == dst) return;
     const int cur = min(seq_len[src], max_seq);
@@ -298,6 +298,7 @@ __global__ void __launch_bounds__(256) k_kv_fanout(const int32_t* src_slots, con
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         seq_len[dst] = seq_len[src];
         mel_pos[dst] = mel_pos[src];
+        pending[dst] = pending[src];          // a deferred decode travels with the slot (its parked logits / latent are then stale on both)
     }
     if (blockIdx.x == 1 % gridDim.x)
         for (int i = threadIdx.x; i < vocab; i += blockDim.x) slot_logits[(size_t)dst * vocab + i] = slot_logits[(size_t)src * vocab + i];
@@ -364,14 +365,14 @@ int launch_kv_copy_span(BeamCall* call, int B, int K, void* kv, int n_layer, int
 
 int launch_kv_fanout(const int32_t* src_slots, const int32_t* dst_slots, int n, void* kv, int n_layer, int n_head, int max_seq, int hd,
                      int max_slots, int esz, int32_t* seq_len, int32_t* mel_pos, float* slot_logits, int vocab, float* slot_latent, int d,
-                     hipStream_t s) {
+                     int32_t* pending, hipStream_t s) {
     GVC_REQUIRE((hd * esz) % 16 == 0, GVC_ERR_UNSUPPORTED, "kv_fanout: head row of %d bytes is not a multiple of 16", hd * esz);
     const size_t head_bytes = (size_t)max_seq * hd * esz, slot_bytes = head_bytes * n_head, lw_bytes = slot_bytes * max_slots;
     // one workgroup per run (960 at full size; a run is ~12 KB at a 48-row prompt).  With 64 strided workgroups per pair the call took
     // 58-62 us for 1, 3 and 7 pairs alike (profiles/nbest_time_fanout_grid64.json): its time did not follow its bytes
     const int runs = 2 * n_layer * n_head;
     hipLaunchKernelGGL(k_kv_fanout, dim3(runs < 1024 ? runs : 1024, n), dim3(256), 0, s, src_slots, dst_slots, (char*)kv, runs, n_head, lw_bytes,
-                       slot_bytes, head_bytes, hd * esz, max_seq, max_slots, seq_len, mel_pos, slot_logits, vocab, slot_latent, d);
+                       slot_bytes, head_bytes, hd * esz, max_seq, max_slots, seq_len, mel_pos, slot_logits, vocab, slot_latent, d, pending);
     GVC_LAUNCH_CHECK();
     return GVC_OK;
 }

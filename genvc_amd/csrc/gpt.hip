@@ -141,6 +141,7 @@ __global__ void k_set_state(GptState st, const int32_t* slots, int B, int seq_le
     if (b < B) {
         st.seq_len[slots[b]] = seq_len;
         st.mel_pos[slots[b]] = mel_pos;
+        st.pending[slots[b]] = -1;       // the slot starts over (prefill, reset, latents): a deferred decode of its old stream is dropped
     }
 }
 
@@ -192,8 +193,18 @@ struct GenCall {
 // step graphs and two k_stage_rows after them: six 4-5 us operations around every group of eight streaming steps).
 // begin: workgroup b < B un-parks the next-step logits and latent of stream b; workgroup B resets the step counter and stores the
 // call parameters.  end: workgroup b parks them again.
+// Deferred decode (one stream on the one-launch step; see the generation loop below): pending is set, and workgroup 0 either hands the
+// slot's pending token to the first decode launch (tok = pending, run flag up; the parked logits / latent are stale and stay where they
+// are) or, with nothing pending, un-parks as ever and lowers the flag so that the first decode launch of the call leaves at once.
+struct DeferRefs {
+    const int32_t* pending;      // GptState::pending, or null: the eager order
+    int32_t* run;                // run flag of the decode launches
+    int32_t* tok;                // their token source (tok_buf)
+};
+
 __device__ __forceinline__ void gen_begin(GenCall* dst, const SampleCall& sc, const int32_t* slots, int B, int32_t* step_ctr, float* logits,
-                                          const float* slot_logits, int vocab, float* latent, const float* slot_latent, int d) {
+                                          const float* slot_logits, int vocab, float* latent, const float* slot_latent, int d,
+                                          const DeferRefs& df) {
     const int b = blockIdx.x;
     if (b == B) {
         if (threadIdx.x == 0) { dst->sc = sc; *step_ctr = 0; }
@@ -201,46 +212,55 @@ __device__ __forceinline__ void gen_begin(GenCall* dst, const SampleCall& sc, co
         return;
     }
     const size_t sl = (size_t)slots[b];
+    if (df.pending) {
+        const int32_t t = df.pending[sl];
+        if (threadIdx.x == 0) {
+            *df.run = t >= 0;
+            if (t >= 0) df.tok[b] = t;
+        }
+        if (t >= 0) return;
+    }
     for (int i = threadIdx.x; i < vocab; i += blockDim.x) logits[(size_t)b * vocab + i] = slot_logits[sl * vocab + i];
     for (int i = threadIdx.x; i < d; i += blockDim.x) latent[(size_t)b * d + i] = slot_latent[sl * d + i];
 }
 
 __global__ void k_gen_begin(GenCall* dst, SampleCall sc, const int32_t* slots, int B, int32_t* step_ctr, float* logits, float* slot_logits,
-                            int vocab, float* latent, float* slot_latent, int d) {
-    gen_begin(dst, sc, slots, B, step_ctr, logits, slot_logits, vocab, latent, slot_latent, d);
+                            int vocab, float* latent, float* slot_latent, int d, DeferRefs df) {
+    gen_begin(dst, sc, slots, B, step_ctr, logits, slot_logits, vocab, latent, slot_latent, d, df);
 }
 
 // gvc_gpt_generate_rows: the same, and workgroup B also stores the call's row entries, which travel as a kernel argument (copied by
 // the runtime when the launch is enqueued: the caller's host array is free when the call returns, and no staging buffer of the context
 // can be overwritten by a later call before this launch has read it -- there is none)
 __global__ void k_gen_begin_rows(GenCall* dst, SampleCall sc, const int32_t* slots, int B, int32_t* step_ctr, float* logits,
-                                 float* slot_logits, int vocab, float* latent, float* slot_latent, int d, SampleRows rows) {
+                                 float* slot_logits, int vocab, float* latent, float* slot_latent, int d, DeferRefs df, SampleRows rows) {
     if ((int)blockIdx.x == B && (int)threadIdx.x < B) dst->rows[threadIdx.x] = rows.r[threadIdx.x];
-    gen_begin(dst, sc, slots, B, step_ctr, logits, slot_logits, vocab, latent, slot_latent, d);
+    gen_begin(dst, sc, slots, B, step_ctr, logits, slot_logits, vocab, latent, slot_latent, d, df);
 }
 
 // gvc_gpt_generate_proc: the same, and workgroup B also stores the call's processors (and row entries when ROWS), both kernel arguments
 template <bool ROWS>
 __global__ void k_gen_begin_proc(GenCall* dst, SampleCall sc, const int32_t* slots, int B, int32_t* step_ctr, float* logits,
-                                 float* slot_logits, int vocab, float* latent, float* slot_latent, int d, SampleRows rows,
-                                 gvc_logits_processors proc) {
+                                 float* slot_logits, int vocab, float* latent, float* slot_latent, int d, DeferRefs df,
+                                 SampleRows rows, gvc_logits_processors proc) {
     if ((int)blockIdx.x == B) {
         if (ROWS && (int)threadIdx.x < B) dst->rows[threadIdx.x] = rows.r[threadIdx.x];
         if (threadIdx.x == 0) dst->proc = proc;
     }
-    gen_begin(dst, sc, slots, B, step_ctr, logits, slot_logits, vocab, latent, slot_latent, d);
+    gen_begin(dst, sc, slots, B, step_ctr, logits, slot_logits, vocab, latent, slot_latent, d, df);
 }
 
 // gvc_gpt_generate_proc_sets: the same, and workgroup B stores each row's set index (and row entries when ROWS), kernel arguments both.
 // The sets themselves went ahead on the stream in launches of their own (launch_stage_proc_sets): 64 of them would not fit one argument
 template <bool ROWS>
 __global__ void k_gen_begin_sets(GenCall* dst, SampleCall sc, const int32_t* slots, int B, int32_t* step_ctr, float* logits,
-                                 float* slot_logits, int vocab, float* latent, float* slot_latent, int d, SampleRows rows, SetIndex sor) {
+                                 float* slot_logits, int vocab, float* latent, float* slot_latent, int d, DeferRefs df, SampleRows rows,
+                                 SetIndex sor) {
     if ((int)blockIdx.x == B && (int)threadIdx.x < B) {
         if (ROWS) dst->rows[threadIdx.x] = rows.r[threadIdx.x];
         dst->set_of_row[threadIdx.x] = sor.k[threadIdx.x];
     }
-    gen_begin(dst, sc, slots, B, step_ctr, logits, slot_logits, vocab, latent, slot_latent, d);
+    gen_begin(dst, sc, slots, B, step_ctr, logits, slot_logits, vocab, latent, slot_latent, d, df);
 }
 
 __global__ void k_gen_end(const int32_t* slots, const float* logits, float* slot_logits, int vocab, const float* latent, float* slot_latent,
@@ -249,6 +269,26 @@ __global__ void k_gen_end(const int32_t* slots, const float* logits, float* slot
     const size_t sl = (size_t)slots[b];
     for (int i = threadIdx.x; i < vocab; i += blockDim.x) slot_logits[sl * vocab + i] = logits[(size_t)b * vocab + i];
     for (int i = threadIdx.x; i < d; i += blockDim.x) slot_latent[sl * d + i] = latent[(size_t)b * d + i];
+}
+
+// end of a deferring call: the token of the last sample stays pending for the slot instead of being decoded for nobody.  (A call of
+// zero steps hands back what it found: the flag is still as the begin kernel set it, the token as it stored it.)
+__global__ void k_gen_end_defer(const int32_t* slots, int32_t* pending, const int32_t* run, const int32_t* tok) {
+    if (threadIdx.x == 0) pending[slots[0]] = *run ? tok[0] : -1;
+}
+
+// Flush of deferred decodes, ahead of anything that needs a slot's full state (a batched or searching call, an explicit decode step):
+// row b's pending token and run flag for the conditional one-stream decode that follows for it, and the slot marked settled.  One thread,
+// row after row: a slot listed twice is decoded once.
+__global__ void k_flush_begin(const int32_t* slots, int B, int32_t* pending, int32_t* ftok, int32_t* frun) {
+    if (threadIdx.x != 0) return;
+    for (int b = 0; b < B; ++b) {
+        const int sl = slots[b];
+        const int32_t t = pending[sl];
+        ftok[b] = t;
+        frun[b] = t >= 0;
+        pending[sl] = -1;
+    }
 }
 
 }  // namespace gvc
@@ -274,8 +314,10 @@ struct GraphKey {
     int split;      // GenPlan::split
     int unroll;     // steps in the graph
     int greedy;     // step graphs: the sampler kernel (searches carry no sampler: 0)
+    int defer;      // step graphs: 1 = [decode the pending token, sample], 0 = [sample, decode]
     bool operator<(const GraphKey& o) const {
-        return std::tie(kind, rows, K, fused, split, unroll, greedy) < std::tie(o.kind, o.rows, o.K, o.fused, o.split, o.unroll, o.greedy);
+        return std::tie(kind, rows, K, fused, split, unroll, greedy, defer) <
+               std::tie(o.kind, o.rows, o.K, o.fused, o.split, o.unroll, o.greedy, o.defer);
     }
 };
 
@@ -313,6 +355,14 @@ struct gvc_gpt {
     int32_t* state = nullptr;         // seq_len[slots], mel_pos[slots], tok[slots], step
     GptState st;
     int32_t *tok_buf = nullptr, *step_ctr = nullptr;
+    // deferred decode of a call's last token (one stream on the one-launch step; the generation loop below)
+    int defer = 1;                    // GVC_DEFER_DECODE=0: the eager order [sample, decode] everywhere
+    int defer_seen = 0;               // a deferring call has run: slots may hold pending tokens, and the entry points that need a slot's
+                                      // full state enqueue flush launches first (never before, so other contexts pay nothing)
+    int32_t *run_flag = nullptr;      // run flag of the decode launches of the deferring loop
+    int32_t *flush_tok = nullptr, *flush_run = nullptr;   // [slots] token and run flag per row of a flush
+    int32_t *flush_slot = nullptr;    // [1] slot table of the settling decode after a hand-off time-out
+    long long* exec_ctr = nullptr;    // one-stream one-launch steps that ran, early exits not counted (gvc_gpt_one_stream_steps)
     GenCall* gen_call = nullptr;
     BeamCall* beam_call = nullptr;    // parameters of the running gvc_gpt_beam_generate call (device)
     CsCall* cs_call = nullptr;        // ... of the running gvc_gpt_contrastive_generate call (device)
@@ -446,13 +496,23 @@ extern "C" int gvc_gpt_create(const gvc_gpt_dims* dims, gvc_gpt** out) {
         gvc_gpt_destroy(c);
         return rc;
     }
-    const size_t nstate = 3 * (size_t)D.max_slots + 4;
+    const size_t nstate = 6 * (size_t)D.max_slots + 8;
     GVC_CHECK_HIP(hipMalloc((void**)&c->state, nstate * sizeof(int32_t)));
     GVC_CHECK_HIP(hipMemset(c->state, 0, nstate * sizeof(int32_t)));
     c->st.seq_len = c->state;
     c->st.mel_pos = c->state + D.max_slots;
     c->tok_buf = c->state + 2 * D.max_slots;
     c->step_ctr = c->state + 3 * D.max_slots;
+    c->st.pending = c->state + 3 * D.max_slots + 4;
+    c->flush_tok = c->state + 4 * D.max_slots + 4;
+    c->flush_run = c->state + 5 * D.max_slots + 4;
+    c->run_flag = c->state + 6 * D.max_slots + 4;
+    c->flush_slot = c->state + 6 * D.max_slots + 5;
+    GVC_CHECK_HIP(hipMemset(c->st.pending, 0xff, (size_t)D.max_slots * sizeof(int32_t)));      // -1: nothing pending
+    GVC_CHECK_HIP(hipMalloc((void**)&c->exec_ctr, sizeof(long long)));
+    GVC_CHECK_HIP(hipMemset(c->exec_ctr, 0, sizeof(long long)));
+    GVC_CHECK_HIP(hipDeviceSynchronize());      // (the memsets went to the legacy default stream; callers may use non-blocking ones)
+    if (getenv("GVC_DEFER_DECODE")) c->defer = atoi(getenv("GVC_DEFER_DECODE")) != 0;
     GVC_CHECK_HIP(hipMalloc((void**)&c->gen_call, sizeof(GenCall)));
     GVC_CHECK_HIP(hipMalloc((void**)&c->beam_call, sizeof(BeamCall)));
     GVC_CHECK_HIP(hipMalloc((void**)&c->cs_call, sizeof(CsCall)));
@@ -489,7 +549,7 @@ extern "C" int gvc_gpt_destroy(gvc_gpt* c) {
         if (p) hipFree(p);
     for (void* p : {(void*)c->wbase, (void*)c->wfm, (void*)c->wh, (void*)c->kv, (void*)c->x, (void*)c->a, (void*)c->q, (void*)c->h,
                     (void*)c->part, (void*)c->work, (void*)c->logits, (void*)c->latent, (void*)c->slot_logits, (void*)c->slot_latent, (void*)c->state, (void*)c->x2, (void*)c->part2,
-                    (void*)c->gen_call, (void*)c->beam_call, (void*)c->cs_call})
+                    (void*)c->gen_call, (void*)c->beam_call, (void*)c->cs_call, (void*)c->exec_ctr})
         if (p) hipFree(p);
     cs_free(&c->cs);
     delete c;
@@ -879,8 +939,9 @@ static int persist_prepare(gvc_gpt* c) {
     return GVC_OK;
 }
 
+// run (nullable): device run flag, the grid leaves at once when it is zero; per_slot: the outputs are the per-slot parking tables
 static int launch_persist(gvc_gpt* c, const int32_t* slots, const int32_t* tok_in, float* logits_out, float* latent_out,
-                          int32_t* step_ctr, hipStream_t s) {
+                          int32_t* step_ctr, hipStream_t s, const int32_t* run = nullptr, int per_slot = 0) {
     GVC_REQUIRE(c->p_layers, GVC_ERR_STATE, "persistent decode step: not prepared");
     PersistArgs A;
     memset(&A, 0, sizeof(A));
@@ -891,6 +952,7 @@ static int launch_persist(gvc_gpt* c, const int32_t* slots, const int32_t* tok_i
     A.logits_out = logits_out; A.latent_out = latent_out; A.step_ctr = step_ctr; A.advance = 1;
     A.gran = c->p_gran; A.epoch = c->p_epoch; A.err = c->seam_err_dev; A.ring_slots = c->p_ring_slots; A.ascr_floats = c->p_ascr; A.hvec_floats = c->p_hvec;
     A.dbg = c->p_dbg;
+    A.run = run; A.per_slot = per_slot; A.exec_ctr = c->exec_ctr;
     if (c->bf16) A.head_w = reinterpret_cast<const float*>(c->head_h);
     void* kargs[] = {&A};
     GVC_CHECK_HIP(hipLaunchKernel((const void*)persist_kernel(c), dim3(persist_test_grid()), dim3(kPThreads), kargs, c->p_lds, s));
@@ -1227,6 +1289,44 @@ static hipError_t reset_handoffs(gvc_gpt* c) {
     return e_bufs != hipSuccess ? e_bufs : e_epoch;
 }
 
+// Deferred decodes of these slots, now: one conditional one-stream step per row, token from the slot's pending entry, logits and latent
+// to the slot's parked rows -- afterwards every slot looks as the eager order leaves it.  Rows with nothing pending cost an early exit.
+// Nothing is enqueued in a context where no deferring call has run.
+static int flush_pending(gvc_gpt* c, const int32_t* slots, int B, hipStream_t s) {
+    if (!c->defer_seen || !c->persist || !c->p_layers) return GVC_OK;
+    GVC_REQUIRE(slots && B >= 1 && B <= c->dm.max_slots, GVC_ERR_ARG, "flush of deferred decodes: %d rows outside [1,%d]", B, c->dm.max_slots);
+    hipLaunchKernelGGL(k_flush_begin, dim3(1), dim3(64), 0, s, slots, B, c->st.pending, c->flush_tok, c->flush_run);
+    GVC_LAUNCH_CHECK();
+    int rc = GVC_OK;
+    for (int b = 0; b < B && rc == GVC_OK; ++b)
+        rc = launch_persist(c, slots + b, c->flush_tok + b, c->slot_logits, c->slot_latent, nullptr, s, c->flush_run + b, 1);
+    return rc;
+}
+
+static int decode_step(gvc_gpt* c, const int32_t* slots, int B, const int32_t* tok_in, float* logits_out, float* latent_out,
+                       int32_t* step_ctr, hipStream_t s, bool fused, int key_chunks);
+
+// The context has just left the one-launch step (hand-off time-out; the device is idle): the pending tokens are decoded once on the
+// launch-per-phase path, slot by slot from a synchronous read of the pending table, so that the eager order that serves the context
+// from here on finds every slot complete.  Rare; errors are left to the next call's own checks.
+static void settle_pending(gvc_gpt* c) {
+    if (!c->defer_seen) return;
+    c->defer_seen = 0;
+    const int S = c->dm.max_slots;
+    std::vector<int32_t> pend((size_t)S, -1);
+    if (hipMemcpy(pend.data(), c->st.pending, (size_t)S * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess) return;
+    for (int32_t slot = 0; slot < S; ++slot) {
+        if (pend[slot] < 0) continue;
+        if (hipMemcpy(c->flush_slot, &slot, sizeof(slot), hipMemcpyHostToDevice) != hipSuccess) break;
+        if (decode_step(c, c->flush_slot, 1, c->st.pending + slot, c->slot_logits + (size_t)slot * c->dm.vocab,
+                        c->slot_latent + (size_t)slot * c->dm.d_model, nullptr, nullptr, false, 1) != GVC_OK) break;
+        if (hipDeviceSynchronize() != hipSuccess) break;
+    }
+    (void)hipMemset(c->st.pending, 0xff, (size_t)S * sizeof(int32_t));
+    (void)hipDeviceSynchronize();
+    (void)hipGetLastError();
+}
+
 static int check_ready(gvc_gpt* c) {
     GVC_REQUIRE(c, GVC_ERR_ARG, "null context");
     const int dev_err = c->seam_err_host ? *(volatile int*)c->seam_err_host : 0;
@@ -1243,6 +1343,7 @@ static int check_ready(gvc_gpt* c) {
         drop_graphs(c);
         (void)reset_handoffs(c);
         *c->seam_err_host = 0;
+        settle_pending(c);
         c->fallbacks += 1;
         set_error("an in-kernel hand-off of a one-launch decode step timed out (code %d: were all 256 workgroups resident?); the outputs "
                   "of the previous decode / generate / cached-prefill call are invalid.  The context has switched to the launch-per-phase "
@@ -1281,6 +1382,7 @@ extern "C" int gvc_gpt_decode_step(gvc_gpt* c, const int32_t* slots, int32_t B, 
         if (rows_persist_ok(c, B, c->st.seq_len) && (rc = rows_persist_prepare(c))) return rc;
         c->rows_keys_hint = c->dm.max_seq;            // (no bound from the caller: the key split for the longest possible context)
     }
+    if ((rc = flush_pending(c, slots, B, s))) return rc;
     return decode_step(c, slots, B, tok_in, logits_out, latent_out, nullptr, s, false, 1);
 }
 
@@ -1299,7 +1401,7 @@ extern "C" int gvc_gpt_kv_fanout(gvc_gpt* c, const int32_t* src_slots, const int
                 n, c->dm.max_slots);
     return launch_kv_fanout(src_slots, dst_slots, n, c->kv, c->dm.n_layer, c->dm.n_head, c->dm.max_seq, c->hd, c->dm.max_slots,
                             c->kv_bf16 ? 2 : 4, c->st.seq_len, c->st.mel_pos, c->slot_logits, c->dm.vocab, c->slot_latent, c->dm.d_model,
-                            (hipStream_t)sv);
+                            c->st.pending, (hipStream_t)sv);
 }
 
 extern "C" int gvc_gpt_sequence_logprobs(gvc_gpt* c, const int32_t* tokens, int32_t tokens_stride, const float* latents, int32_t R, int32_t n,
@@ -1587,6 +1689,7 @@ extern "C" int gvc_gpt_latents(gvc_gpt* c, const int32_t* slots, int32_t B, cons
 // context -- r_ready / persist -- so nothing is derived from rows_decode_ok / persist_ok before).
 struct GenPlan {
     bool fused, greedy;
+    bool defer;     // the deferring order [decode the pending token, sample]: one stream on the one-launch step
     int key_chunks, variant;
     int split;      // GraphKey::split: key_chunks, or 8 + the key split of the one-launch rows step
 };
@@ -1612,6 +1715,7 @@ static int plan_generate(gvc_gpt* c, int B, int key_bound, int top_k, GenPlan* p
     pl->variant = persist_ok(c, B) ? 3 : (rows1 ? 5 : (rows_decode_ok(c, B) ? 4 : (pl->fused ? 2 : 1)));
     // (the sampler kernel is chosen at capture time: a graph serves top_k = 1 or everything else)
     pl->greedy = sample_greedy_ok(top_k, c->dm.d_model);
+    pl->defer = c->defer && persist_ok(c, B);
     return GVC_OK;
 }
 
@@ -1638,7 +1742,13 @@ static int get_graph(gvc_gpt* c, const GraphKey& key, hipGraphExec_t* ge, Step&&
 }
 
 static int step_graph(gvc_gpt* c, int B, const GenPlan& pl, int unroll, hipGraphExec_t* ge) {
-    return get_graph(c, GraphKey{kStepGraph, B, 0, pl.fused, pl.split, unroll, pl.greedy}, ge, [&](hipStream_t cs) {
+    return get_graph(c, GraphKey{kStepGraph, B, 0, pl.fused, pl.split, unroll, pl.greedy, pl.defer}, ge, [&](hipStream_t cs) {
+        if (pl.defer) {
+            // the decode of the token sampled one step (or one call) ago, if there is one, then this step's sample; the sampler raises the
+            // run flag and advances the step counter
+            const int rc = launch_persist(c, c->gen_call->slots, c->tok_buf, c->logits, c->latent, nullptr, cs, c->run_flag, 0);
+            return rc ? rc : launch_sample_indirect(&c->gen_call->sc, B, pl.greedy, cs);
+        }
         const int rc = launch_sample_indirect(&c->gen_call->sc, B, pl.greedy, cs);
         return rc ? rc : decode_step(c, c->gen_call->slots, B, c->tok_buf, c->logits, c->latent, c->step_ctr, cs, pl.fused, pl.key_chunks);
     });
@@ -1765,8 +1875,23 @@ static int generate_impl(gvc_gpt* c, const int32_t* slots, int32_t B, int32_t* i
                 "generate: %d cached positions would overflow the KV cache (max_seq %d)", max_keys, c->dm.max_seq);
     GVC_REQUIRE(p->vocab == c->dm.vocab, GVC_ERR_ARG, "generate: vocab mismatch");
     hipStream_t s = (hipStream_t)sv;
+    GenPlan pl;
+    // (a keyed call replays the greedy graphs when every row is greedy, the sampling ones otherwise: the step graphs are the same)
+    if ((rc = plan_generate(c, B, key_bound, rows ? (rows_greedy ? 1 : 0) : p->top_k, &pl))) return rc;
+    c->last_variant = pl.variant;
+    // One stream on the one-launch step: each step is [decode the pending token, if any; sample], the call ends after its last sample and
+    // that token stays pending for the slot -- its decode opens the next call that continues the slot and never runs when the slot is
+    // prefilled or reset instead (the end of every chunk).  Every other call settles its slots first and keeps [sample, decode].
+    DeferRefs df = {nullptr, nullptr, nullptr};
+    if (pl.defer) {
+        df.pending = c->st.pending; df.run = c->run_flag; df.tok = c->tok_buf;
+        c->defer_seen = 1;
+    } else if ((rc = flush_pending(c, slots, B, s))) {
+        return rc;
+    }
     SampleCall sc;
     memset(&sc, 0, sizeof(sc));
+    sc.run_flag = pl.defer ? c->run_flag : nullptr;
     sc.logits = c->logits; sc.B = B; sc.ids = ids; sc.ids_stride = ids_stride; sc.ids_len = ids_len;
     sc.finished = finished; sc.p = *p; sc.step = 0; sc.step_ptr = c->step_ctr; sc.tok_out = c->tok_buf;
     sc.tokens_out = tokens_out; sc.tok_stride = tok_stride; sc.i0 = i0; sc.latent_src = c->latent;
@@ -1789,10 +1914,10 @@ static int generate_impl(gvc_gpt* c, const int32_t* slots, int32_t B, int32_t* i
             memcpy(sr.r, rows, (size_t)B * sizeof(gvc_row_sampling));
             sc.rows = c->gen_call->rows;
             hipLaunchKernelGGL(k_gen_begin_sets<true>, dim3(B + 1), dim3(256), 0, s, c->gen_call, sc, slots, B, c->step_ctr, c->logits,
-                               c->slot_logits, c->dm.vocab, c->latent, c->slot_latent, c->dm.d_model, sr, si);
+                               c->slot_logits, c->dm.vocab, c->latent, c->slot_latent, c->dm.d_model, df, sr, si);
         } else {
             hipLaunchKernelGGL(k_gen_begin_sets<false>, dim3(B + 1), dim3(256), 0, s, c->gen_call, sc, slots, B, c->step_ctr, c->logits,
-                               c->slot_logits, c->dm.vocab, c->latent, c->slot_latent, c->dm.d_model, sr, si);
+                               c->slot_logits, c->dm.vocab, c->latent, c->slot_latent, c->dm.d_model, df, sr, si);
         }
     } else if (proc) {
         // (the processors travel as a kernel argument, as the rows do: nothing to allocate, and the caller's struct is free on return)
@@ -1805,29 +1930,28 @@ static int generate_impl(gvc_gpt* c, const int32_t* slots, int32_t B, int32_t* i
         sc.proc = &c->gen_call->proc;
         if (rows)
             hipLaunchKernelGGL(k_gen_begin_proc<true>, dim3(B + 1), dim3(256), 0, s, c->gen_call, sc, slots, B, c->step_ctr, c->logits,
-                               c->slot_logits, c->dm.vocab, c->latent, c->slot_latent, c->dm.d_model, sr, *proc);
+                               c->slot_logits, c->dm.vocab, c->latent, c->slot_latent, c->dm.d_model, df, sr, *proc);
         else
             hipLaunchKernelGGL(k_gen_begin_proc<false>, dim3(B + 1), dim3(256), 0, s, c->gen_call, sc, slots, B, c->step_ctr, c->logits,
-                               c->slot_logits, c->dm.vocab, c->latent, c->slot_latent, c->dm.d_model, sr, *proc);
+                               c->slot_logits, c->dm.vocab, c->latent, c->slot_latent, c->dm.d_model, df, sr, *proc);
     } else if (rows) {
         SampleRows sr;
         memset(&sr, 0, sizeof(sr));
         memcpy(sr.r, rows, (size_t)B * sizeof(gvc_row_sampling));
         sc.rows = c->gen_call->rows;          // (device address: GenCall lives in device memory)
         hipLaunchKernelGGL(k_gen_begin_rows, dim3(B + 1), dim3(256), 0, s, c->gen_call, sc, slots, B, c->step_ctr, c->logits,
-                           c->slot_logits, c->dm.vocab, c->latent, c->slot_latent, c->dm.d_model, sr);
+                           c->slot_logits, c->dm.vocab, c->latent, c->slot_latent, c->dm.d_model, df, sr);
     } else {
         hipLaunchKernelGGL(k_gen_begin, dim3(B + 1), dim3(256), 0, s, c->gen_call, sc, slots, B, c->step_ctr, c->logits, c->slot_logits,
-                           c->dm.vocab, c->latent, c->slot_latent, c->dm.d_model);
+                           c->dm.vocab, c->latent, c->slot_latent, c->dm.d_model, df);
     }
     GVC_LAUNCH_CHECK();
-    GenPlan pl;
-    // (a keyed call replays the greedy graphs when every row is greedy, the sampling ones otherwise: the step graphs are the same)
-    if ((rc = plan_generate(c, B, key_bound, rows ? (rows_greedy ? 1 : 0) : p->top_k, &pl))) return rc;
-    c->last_variant = pl.variant;
     if ((rc = replay_steps(n_steps, s, [&](int unroll, hipGraphExec_t* ge) { return step_graph(c, B, pl, unroll, ge); }))) return rc;
-    hipLaunchKernelGGL(k_gen_end, dim3(B), dim3(256), 0, s, slots, c->logits, c->slot_logits, c->dm.vocab, c->latent, c->slot_latent,
-                       c->dm.d_model);
+    if (pl.defer)
+        hipLaunchKernelGGL(k_gen_end_defer, dim3(1), dim3(64), 0, s, slots, c->st.pending, c->run_flag, c->tok_buf);
+    else
+        hipLaunchKernelGGL(k_gen_end, dim3(B), dim3(256), 0, s, slots, c->logits, c->slot_logits, c->dm.vocab, c->latent, c->slot_latent,
+                           c->dm.d_model);
     GVC_LAUNCH_CHECK();
     return GVC_OK;
 }
@@ -1892,7 +2016,7 @@ static int beam_graph(gvc_gpt* c, int B, int K, const GenPlan& pl, int unroll, h
     int32_t* table = c->gen_call->slots;
     gvc_beam_state dummy;
     memset(&dummy, 0, sizeof(dummy));
-    return get_graph(c, GraphKey{kBeamGraph, B * K, K, pl.fused, pl.split, unroll, 0}, ge, [&](hipStream_t cs) {
+    return get_graph(c, GraphKey{kBeamGraph, B * K, K, pl.fused, pl.split, unroll, 0, 0}, ge, [&](hipStream_t cs) {
         int rc = launch_beam_select(dummy, nullptr, c->beam_call, B, K, c->logits, table, 0, c->st.seq_len, c->st.mel_pos, c->tok_buf, cs);
         if (rc == GVC_OK)
             rc = launch_kv_copy_span(c->beam_call, B, K, c->kv, c->dm.n_layer, c->dm.n_head, c->dm.max_seq, c->hd, c->dm.max_slots,
@@ -1941,6 +2065,7 @@ static int beam_generate_impl(gvc_gpt* c, int32_t* slots, const gvc_beam_state* 
     const int B = st->B, K = st->K, BK = B * K;
     GenPlan pl;
     if ((rc = beam_plan(c, B, K, key_bound, &pl))) return rc;
+    if ((rc = flush_pending(c, slots, BK, s))) return rc;
     if ((rc = launch_beam_begin(c->beam_call, *st, proc, i0, slots, c->gen_call->slots, c->logits, c->slot_logits, s))) return rc;
     c->last_variant = pl.variant;
     if ((rc = replay_steps(n_steps, s, [&](int unroll, hipGraphExec_t* ge) { return beam_graph(c, B, K, pl, unroll, ge); }))) return rc;
@@ -1972,7 +2097,7 @@ static int cs_prepare(gvc_gpt* c) {
 
 static int cs_graph(gvc_gpt* c, int B, int K, const GenPlan& pl, int unroll, hipGraphExec_t* ge) {
     int32_t* table = c->gen_call->slots;
-    return get_graph(c, GraphKey{kContrastiveGraph, B * K, K, pl.fused, pl.split, unroll, 0}, ge, [&](hipStream_t cs) {
+    return get_graph(c, GraphKey{kContrastiveGraph, B * K, K, pl.fused, pl.split, unroll, 0, 0}, ge, [&](hipStream_t cs) {
         int rc = launch_cs_recall(c->cs_call, c->cs, B, c->logits, c->latent, c->tok_buf, cs);
         if (rc == GVC_OK) rc = decode_step(c, table, B * K, c->tok_buf, c->logits, c->latent, nullptr, cs, pl.fused, pl.key_chunks);
         if (rc == GVC_OK) rc = launch_cs_hidden(c->x, c->cs, B * K, c->lnf_w, c->lnf_b, cs);
@@ -2021,6 +2146,7 @@ static int cs_generate_impl(gvc_gpt* c, const int32_t* slots, const gvc_contrast
     GenPlan pl;
     if ((rc = beam_plan(c, B, K, key_bound, &pl))) return rc;
     if ((rc = cs_prepare(c))) return rc;
+    if ((rc = flush_pending(c, slots, B * K, s))) return rc;
     if ((rc = launch_cs_begin(c->cs_call, c->cs, *st, proc, i0, slots, c->gen_call->slots, c->logits, c->slot_logits, c->latent,
                               c->slot_latent, c->st.seq_len, c->st.mel_pos, c->kv, c->dm.n_layer, c->dm.n_head, c->dm.max_seq, c->hd, c->dm.max_slots, c->kv_bf16 ? 2 : 4,
                               s)))
@@ -2064,6 +2190,7 @@ extern "C" int gvc_gpt_time_kernel(gvc_gpt* c, int32_t which, const int32_t* slo
     GVC_REQUIRE(!one_launch || persist_ok(c, B), GVC_ERR_UNSUPPORTED, "time_kernel: the one-launch decode step does not serve this context");
     if (one_launch && (rc = persist_prepare(c))) return rc;
     hipStream_t s = (hipStream_t)sv;
+    if ((rc = flush_pending(c, slots, B, s))) return rc;
     hipEvent_t e0, e1;
     GVC_CHECK_HIP(hipEventCreate(&e0));
     GVC_CHECK_HIP(hipEventCreate(&e1));
@@ -2102,6 +2229,16 @@ extern "C" int gvc_gpt_time_kernel(gvc_gpt* c, int32_t which, const int32_t* slo
 
 extern "C" int gvc_gpt_decode_variant(gvc_gpt* c) { return c ? c->last_variant : 0; }
 extern "C" long long gvc_gpt_rows_step_launches(gvc_gpt* c) { return c ? c->r_launches : 0; }
+
+// one-stream one-launch steps that RAN so far (generation loops, flushes, decode_step; launches that left at the run flag are not
+// counted).  Synchronises the device.
+extern "C" long long gvc_gpt_one_stream_steps(gvc_gpt* c) {
+    long long n = 0;
+    if (!c || !c->exec_ctr || hipDeviceSynchronize() != hipSuccess ||
+        hipMemcpy(&n, c->exec_ctr, sizeof(n), hipMemcpyDeviceToHost) != hipSuccess)
+        return -1;
+    return n;
+}
 
 // To be called after the caller has synchronised the stream of a decode / generate / cached-prefill call: 0 when that work ran
 // cleanly; otherwise the state error of check_ready (a timed-out hand-off has switched the context to the launch-per-phase paths,

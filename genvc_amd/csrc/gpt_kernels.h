@@ -16,6 +16,8 @@ constexpr int kAttnChunks = 8;   // key-axis split of one decode attention row (
 struct GptState {                // device-resident step state, one entry per slot
     int32_t* seq_len;            // cached positions
     int32_t* mel_pos;            // index into mel_pos_embedding of the next decode input
+    int32_t* pending;            // deferred decode: the slot's last sampled token, not yet run through the stack (-1: none, and the
+                                 // slot's parked logits / latent are current)
 };
 
 enum Prologue { PRO_LN = 0, PRO_MERGE = 1, PRO_COPY = 2, PRO_LN2X = 3, PRO_LN_SUM = 4 };

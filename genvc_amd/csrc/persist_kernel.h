@@ -24,6 +24,14 @@
 // Every spin is bounded: on a timeout the workgroup sets *err, and the host raises
 // GVC_ERR_STATE on the next call.
 //
+// Run flag (deferred decode, gpt.hip): the generation loop of one stream replays [decode the pending token, sample], so the launch sits
+// in the captured graph whether or not a token is pending.  PersistArgs::run (nullable) points at the device word that says which: zero
+// and the whole grid leaves before it takes a rank, loads a weight or publishes a granule, passing only the end-of-step arrival counter
+// (the reasoning is at the flag's load in the kernel).  A chunk of 24 tokens is a prefill plus 23 executed steps: the first launch of a
+// call after a prefill exits early, and the decode of the chunk's last token never runs.  per_slot = 1 (the flush of a pending token ahead
+// of a call that needs the slot's full state) writes logits and latent to the slot's rows of the parking tables; exec_ctr counts the
+// steps that ran.
+//
 // XL (round 4, d_model 1024): the hidden units of the MLP never leave their XCD.  A hand-off between workgroups that share an L2
 // costs 1.0 us idle / 2.6 us beside the weight stream when the producer uses PLAIN stores (they stay in the XCD's L2) and the
 // consumers sc1 loads, against 2.4 / 3.7 us for the device-wide write-through hand-off (scripts/ubench/seam_xcd.hip).  Which XCD a
@@ -76,6 +84,9 @@ struct PersistArgs {
     int ring_slots;                 // power of two
     int hvec_floats, ascr_floats;
     unsigned long long* dbg;        // nullable: wall-clock stamps
+    const int32_t* run;             // nullable run flag: when *run == 0 the whole grid leaves at once (see the early exit in the kernel)
+    int per_slot;                   // 1: logits_out / latent_out are per-slot tables [slots][vocab] / [slots][d] (the flush of a deferred decode)
+    long long* exec_ctr;            // nullable: ++ once per step that ran (gvc_gpt_one_stream_steps)
 };
 
 // granules of the hand-off buffers (host: allocation size)
@@ -458,9 +469,18 @@ __global__ __launch_bounds__(kPThreads) void k_decode_persist(const PersistArgs 
     float* ascr = xvec + D;                      // attention: q_h | k_h | v_h of this step, then m_s, l_s
     unsigned* ctl = reinterpret_cast<unsigned*>(ascr + A.ascr_floats);
     if (threadIdx.x < kCtlWords) ctl[threadIdx.x] = 0u;
+    // Deferred decode (gpt.hip: the generation loop runs [decode the pending token, sample]): the launch is in the captured graph whether
+    // or not a token is pending; the run flag says which.  Nothing writes the flag while this grid runs (the begin kernel of the call / the
+    // sampler of the step before set it, on the same stream), so all 256 workgroups read the same value.  With the flag down nobody takes
+    // an XCD rank, publishes a granule, loads a weight or touches the cache, the lengths, the logits or the latent; the grid only passes
+    // the arrival counter below.  That is safe for the epoch / tag scheme because the scheme asks two things of a launch: that it leaves the
+    // arrival counter and the per-XCD rank counters at zero (the last workgroup to arrive stores zeros, as after a full step; the ranks
+    // were never raised), and that no granule carries the tag of a LATER step.  The epoch is bumped as after a full step, so the next step
+    // expects tags (epoch + 2, ...) that no launch has written yet; an early exit writes no granule at all.
+    const bool run = !A.run || __hip_atomic_load(A.run, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
     // XL: this workgroup's XCD and its rank among the XCD's workgroups (requested here, used after the barrier)
     unsigned xcc = 0, xrank = 0;
-    if (XL && threadIdx.x == kPCW * 64) {
+    if (XL && run && threadIdx.x == kPCW * 64) {
         asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
         xcc &= 7u;
         xrank = __hip_atomic_fetch_add(A.epoch + 4 + xcc, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -482,8 +502,8 @@ __global__ __launch_bounds__(kPThreads) void k_decode_persist(const PersistArgs 
             jj = __builtin_amdgcn_readfirstlane((int)(xrank & 31u));
             if (c.lane == 0) lds_st(ctl + kCtlXcd, 0x10000u | (unsigned)(xx << 8) | (unsigned)jj);
         }
-        persist_loader<ND, WB, XL>(A, c, ring, xx, jj);
-    } else {
+        if (run) persist_loader<ND, WB, XL>(A, c, ring, xx, jj);
+    } else if (run) {
         // `lane` is re-defined through an empty asm at every phase: without it the compiler hoists the per-lane addresses of all
         // phases out of the layer loop and spills them to scratch (vector memory behind the loader's DMA queue)
         int& lane = c.lane;
@@ -493,6 +513,8 @@ __global__ __launch_bounds__(kPThreads) void k_decode_persist(const PersistArgs 
         const int H = A.n_head, hd = A.head_dim;
         const int slot = A.slots[0];
         const int S = A.st.seq_len[slot];                // cached positions; this step's key goes to index S
+        float* const logits_out = A.per_slot ? A.logits_out + (size_t)slot * A.vocab : A.logits_out;
+        float* const latent_out = A.per_slot ? A.latent_out + (size_t)slot * D : A.latent_out;
         const int n_keys = S + 1;
         const int lpk = hd >> 2, kpw = 64 / lpk;         // lanes per key row, keys per wave-instruction
         const int pass_keys = kPU * kPCW * kpw;
@@ -993,7 +1015,7 @@ __global__ __launch_bounds__(kPThreads) void k_decode_persist(const PersistArgs 
             layer_norm_regs<ND>(xv, g2, b2);
             if (wg == 0 && wave == 0) {
 #pragma unroll
-                for (int i = 0; i < ND; ++i) *reinterpret_cast<float4*>(A.latent_out + i * 256 + lane * 4) = xv[i];
+                for (int i = 0; i < ND; ++i) *reinterpret_cast<float4*>(latent_out + i * 256 + lane * 4) = xv[i];
             }
             float val = 0.f;
             for (int i = 0; i < nmy; ++i) {
@@ -1002,12 +1024,12 @@ __global__ __launch_bounds__(kPThreads) void k_decode_persist(const PersistArgs 
                 const float s = wave_sum(row_partial<ND, WB>(ring, rmask, fs, off, lane, xv));
                 if (lane == i) val = s;
             }
-            if (lane < nmy) A.logits_out[row_g] = val + bias;
+            if (lane < nmy) logits_out[row_g] = val + bias;
             if (rm > 0) fs += (((rm * D * 4) >> WB) + kPSlot - 1) / kPSlot;
             if (tail) {
                 wait_fill(c, fs);
                 const float s = wave_sum(row_partial<ND, WB>(ring, rmask, fs, 0u, lane, xv));
-                if (lane == 0) A.logits_out[rm * kPG + wg] = s + tbias;
+                if (lane == 0) logits_out[rm * kPG + wg] = s + tbias;
             }
             if (wg < rem) fs += (((D * 4) >> WB) + kPSlot - 1) / kPSlot;
             phase_done();
@@ -1020,6 +1042,7 @@ __global__ __launch_bounds__(kPThreads) void k_decode_persist(const PersistArgs 
                     else *A.err = 951;
                 }
                 if (A.step_ctr) *A.step_ctr += 1;
+                if (A.exec_ctr) *A.exec_ctr += 1;
             }
         }
 #undef GVC_PHASE_BEGIN

@@ -40,6 +40,10 @@ struct SampleCall {
     // nullable: typical / epsilon / eta warpers (gvc_*_warp calls, device memory), one per set: row b uses warps[set_of_row[b]] (none
     // for -1), warps[0] when set_of_row is null.  Null: none, and k_sample computes exactly what it computes without this field
     const gvc_logits_warpers* warps;
+    // nullable: the run flag of a deferred-decode loop (gpt.hip: a step is [decode the pending token, sample]).  Set: the sampler raises
+    // it behind every sample -- tok_out now holds a token the next decode launch must run -- and advances *step_ptr itself, which the
+    // decode step does in the eager order.  One row only
+    int32_t* run_flag;
 };
 
 // the processors of row b (uniform over the row's workgroup)

@@ -322,6 +322,7 @@ __global__ __launch_bounds__(kSampThreads) void k_sample(SampleCall cv, const Sa
         if (tok == C.p.eos_token) C.finished[b] = 1;
         C.tok_out[b] = tok;
         if (C.tokens_out) C.tokens_out[(size_t)b * C.tok_stride + C.i0 + step] = tok;
+        if (C.run_flag) { *C.run_flag = 1; *const_cast<int32_t*>(C.step_ptr) = step + 1; }      // (every thread read `step` before the barriers above)
     }
     if (C.latents_out && C.latent_src) {
         const float* src = C.latent_src + (size_t)b * C.d;
@@ -395,6 +396,7 @@ __global__ __launch_bounds__(kGreedyThreads) void k_sample_greedy(SampleCall cv,
         if (tok == C.p.eos_token) C.finished[b] = 1;
         C.tok_out[b] = tok;
         if (C.tokens_out) C.tokens_out[(size_t)b * C.tok_stride + C.i0 + step] = tok;
+        if (C.run_flag) { *C.run_flag = 1; *const_cast<int32_t*>(C.step_ptr) = step + 1; }      // (every thread read `step` before the barriers above)
     }
     if (C.latents_out && C.latent_src) {
         const float* src = C.latent_src + (size_t)b * C.d;

@@ -776,6 +776,11 @@ class GptEngine:
         """back to the one-launch steps after a time-out fallback, when the GPU is the caller's own again (include/genvc_hip.h: gvc_gpt_rearm)"""
         check(lib().gvc_gpt_rearm(self._h), "rearm")
 
+    def one_stream_steps(self):
+        """one-stream one-launch decode steps that ran so far, early exits of deferred decodes not counted; synchronises the device
+        (include/genvc_hip.h: gvc_gpt_one_stream_steps)"""
+        return int(lib().gvc_gpt_one_stream_steps(self._h))
+
     def rows_step_launches(self):
         """one-launch rows steps issued so far (include/genvc_hip.h: gvc_gpt_rows_step_launches)"""
         return int(lib().gvc_gpt_rows_step_launches(self._h))

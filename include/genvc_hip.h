@@ -20,13 +20,16 @@
  *   - a context is bound to the device that was current at *_create and must not be used
  *     from two host threads at once; contexts are independent of each other.
  *
- * Environment switches read by the library (ten; everything else that used to be a run-time knob is a constant now, and the
+ * Environment switches read by the library (eleven; everything else that used to be a run-time knob is a constant now, and the
  * experiments that lost are gone from the kernels: profiles/r06_removed_experiments.patch).  All default to the shipped configuration.
  *   GVC_PERSIST=0            never use the one-launch steps (one stream and 2..16 rows then take the launch-per-phase paths)
  *   GVC_PERSIST_ROWS=0       2..16 rows keep the launch-per-phase rows path (the one-stream one-launch step stays on)
  *   GVC_PERSIST_XCD=0        one-stream step: device-wide hand-off of the MLP's hidden units instead of the XCD-local layout
  *                            (for partition modes in which a 256-workgroup grid is not dealt 8 x 32 over the XCDs; the topology
  *                            probe switches it off by itself when it sees such a deal)
+ *   GVC_DEFER_DECODE=0       one-stream generation on the one-launch step: the eager order [sample, decode] instead of deferring the
+ *                            decode of a call's last token to the next call that continues the slot (read at gvc_gpt_create; for A/B
+ *                            runs and the tests that compare the two orders)
  *   GVC_PERSIST_TEST_GRID=n  test hook: launch the one-launch steps with n < 256 workgroups (every hand-off then times out)
  *   GVC_PERSIST_STAMPS=1     in-kernel wall-clock stamps of the one-launch steps (scripts/stamps_persist.py, scripts/stamps_rows.py)
  *   GVC_DEBUG_STAMPS=1       in-kernel stamps of the launch-per-phase decode kernels (scripts/stamps.py)
@@ -471,6 +474,11 @@ int gvc_gpt_decode_variant(gvc_gpt* ctx);
  * steps, the uncached rows of a streaming chunk's prefill) this context has issued; a step captured into the generation loop's
  * graph counts once.  Tests use it to prove which path served a call. */
 long long gvc_gpt_rows_step_launches(gvc_gpt* ctx);
+/* Diagnostic: how many one-stream one-launch decode steps (csrc/persist_kernel.h) have RUN in this context -- generation loops,
+ * gvc_gpt_decode_step, flushes of deferred decodes.  A launch that left at its run flag (the first step of a deferring call with
+ * nothing pending, a flush row with nothing pending) is not counted: a prefill followed by 24 generated tokens counts 23, and 24
+ * under GVC_DEFER_DECODE=0.  Synchronises the device; -1 on an error. */
+long long gvc_gpt_one_stream_steps(gvc_gpt* ctx);
 /* Health of the work a caller has just synchronised (no reference counterpart: the reference has no in-kernel hand-offs).  The
  * one-launch steps need all 256 workgroups co-resident; when another process or stream holds CUs a hand-off times out (~0.2 s,
  * bounded spins), the step's outputs are garbage and a device-visible word records it.  This call -- and, failing that, the next
