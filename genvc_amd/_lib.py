@@ -36,6 +36,11 @@ class BeamState(C.Structure):
                                    "hyp_worst", "copies", "n_copies")]
 
 
+class BeamGroups(C.Structure):
+    """gvc_beam_groups (include/genvc_hip.h): the groups of a group (diverse) beam search and their per-(item, group) device arrays"""
+    _fields_ = [("G", C.c_int32), ("diversity_penalty", C.c_float)] + [(n, C.c_void_p) for n in ("done", "hyp_count", "hyp_worst")]
+
+
 class ContrastiveState(C.Structure):
     """gvc_contrastive_state (include/genvc_hip.h): sizes, settings and the device arrays of one contrastive search"""
     _fields_ = [(n, C.c_int32) for n in ("B", "K", "vocab", "eos", "n0", "ids_stride", "max_new")] + \
@@ -114,6 +119,10 @@ _SIGNATURES = {
     "gvc_beam_select_proc": (C.c_int, [C.POINTER(BeamState), C.POINTER(LogitsProcessors), _P, _P, C.c_int32, _P]),
     "gvc_gpt_beam_generate_proc": (C.c_int, [_P, _P, C.POINTER(BeamState), C.POINTER(LogitsProcessors), C.c_int32, C.c_int32,
                                              C.c_int32, _P]),
+    "gvc_group_beam_select": (C.c_int, [C.POINTER(BeamState), C.POINTER(BeamGroups), C.POINTER(LogitsProcessors), _P, _P, C.c_int32, _P]),
+    "gvc_gpt_group_beam_generate": (C.c_int, [_P, _P, C.POINTER(BeamState), C.POINTER(BeamGroups), C.POINTER(LogitsProcessors),
+                                              C.c_int32, C.c_int32, C.c_int32, _P]),
+    "gvc_gpt_warmup_group_beam": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "gvc_gpt_prefill_hidden": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, C.c_int32, _P, _P]),
     "gvc_gpt_contrastive_generate": (C.c_int, [_P, _P, C.POINTER(ContrastiveState), C.c_int32, C.c_int32, C.c_int32, _P]),
     "gvc_gpt_contrastive_generate_proc": (C.c_int, [_P, _P, C.POINTER(ContrastiveState), C.POINTER(LogitsProcessors), C.c_int32,

@@ -305,7 +305,7 @@ struct GptLayer {
 };
 
 // What a captured generation graph bakes into its nodes, and so what tells two graphs of a context apart.
-enum GraphKind { kStepGraph, kBeamGraph, kContrastiveGraph };
+enum GraphKind { kStepGraph, kBeamGraph, kContrastiveGraph, kGroupBeamGraph };
 struct GraphKey {
     int kind;       // GraphKind
     int rows;       // rows of the decode step: the call's B streams, B * K of a search
@@ -2066,7 +2066,7 @@ static int beam_generate_impl(gvc_gpt* c, int32_t* slots, const gvc_beam_state* 
     GenPlan pl;
     if ((rc = beam_plan(c, B, K, key_bound, &pl))) return rc;
     if ((rc = flush_pending(c, slots, BK, s))) return rc;
-    if ((rc = launch_beam_begin(c->beam_call, *st, proc, i0, slots, c->gen_call->slots, c->logits, c->slot_logits, s))) return rc;
+    if ((rc = launch_beam_begin(c->beam_call, *st, proc, nullptr, i0, slots, c->gen_call->slots, c->logits, c->slot_logits, s))) return rc;
     c->last_variant = pl.variant;
     if ((rc = replay_steps(n_steps, s, [&](int unroll, hipGraphExec_t* ge) { return beam_graph(c, B, K, pl, unroll, ge); }))) return rc;
     return launch_beam_end(c->gen_call->slots, slots, BK, c->logits, c->slot_logits, c->dm.vocab, s);
@@ -2080,6 +2080,80 @@ extern "C" int gvc_gpt_beam_generate(gvc_gpt* c, int32_t* slots, const gvc_beam_
 extern "C" int gvc_gpt_beam_generate_proc(gvc_gpt* c, int32_t* slots, const gvc_beam_state* st, const gvc_logits_processors* proc,
                                           int32_t i0, int32_t n_steps, int32_t max_keys, gvc_stream sv) {
     return beam_generate_impl(c, slots, st, proc, i0, n_steps, max_keys, sv);
+}
+
+// ---------------------------------------------------------------------------------------------
+// group (diverse) beam search: the beam graph with k_group_beam_select in k_beam_select's place, under kind kGroupBeamGraph.  The
+// select reads G and lambda from the device-resident call, so one graph serves every G of a (B, K).
+// ---------------------------------------------------------------------------------------------
+static int group_beam_graph(gvc_gpt* c, int B, int K, const GenPlan& pl, int unroll, hipGraphExec_t* ge) {
+    int32_t* table = c->gen_call->slots;
+    gvc_beam_state dummy;
+    gvc_beam_groups dummy_grp;
+    memset(&dummy, 0, sizeof(dummy));
+    memset(&dummy_grp, 0, sizeof(dummy_grp));
+    return get_graph(c, GraphKey{kGroupBeamGraph, B * K, K, pl.fused, pl.split, unroll, 0, 0}, ge, [&](hipStream_t cs) {
+        int rc = launch_group_beam_select(dummy, dummy_grp, nullptr, c->beam_call, B, c->logits, table, 0, c->st.seq_len, c->st.mel_pos,
+                                          c->tok_buf, cs);
+        if (rc == GVC_OK)
+            rc = launch_kv_copy_span(c->beam_call, B, K, c->kv, c->dm.n_layer, c->dm.n_head, c->dm.max_seq, c->hd, c->dm.max_slots,
+                                     c->kv_bf16 ? 2 : 4, c->st.seq_len, cs);
+        if (rc == GVC_OK) rc = decode_step(c, table, B * K, c->tok_buf, c->logits, c->latent, nullptr, cs, pl.fused, pl.key_chunks);
+        return rc;
+    });
+}
+
+extern "C" int gvc_gpt_warmup_group_beam(gvc_gpt* c, int32_t B, int32_t K, int32_t G, int32_t max_keys) {
+    int rc = check_ready(c);
+    if (rc) return rc;
+    GVC_REQUIRE(max_keys >= 0 && max_keys < c->dm.max_seq, GVC_ERR_ARG, "warmup_group_beam: bad max_keys %d", max_keys);
+    GVC_REQUIRE(B >= 1 && K >= 2 && K <= kBeamMaxK && B * K <= c->dm.max_slots, GVC_ERR_ARG,
+                "warmup_group_beam: B*K = %d*%d outside [2, %d] or K above %d", B, K, c->dm.max_slots, kBeamMaxK);
+    GVC_REQUIRE(G >= 1 && G <= K && K % G == 0, GVC_ERR_ARG, "warmup_group_beam: %d groups do not divide %d beams", G, K);
+    if ((rc = gvc_gpt_warmup(c, B * K, max_keys, 1))) return rc;
+    WarmupScope warm(c);
+    const int hi = max_keys > 0 ? max_keys : c->dm.max_seq - 1;
+    rc = warmup_sweep(1, hi, [&](int mk, GenPlan* pl) { return beam_plan(c, B, K, mk, pl); },
+                      [&](const GenPlan& pl, int unroll, hipGraphExec_t* ge) { return group_beam_graph(c, B, K, pl, unroll, ge); });
+    if (rc) return rc;
+    GVC_CHECK_HIP(hipDeviceSynchronize());
+    return GVC_OK;
+}
+
+extern "C" int gvc_gpt_group_beam_generate(gvc_gpt* c, int32_t* slots, const gvc_beam_state* st, const gvc_beam_groups* grp,
+                                           const gvc_logits_processors* proc, int32_t i0, int32_t n_steps, int32_t max_keys,
+                                           gvc_stream sv) {
+    int rc = check_ready(c);
+    if (rc) return rc;
+    GVC_REQUIRE(slots && st && grp && i0 >= 0 && n_steps >= 0 && max_keys >= 0, GVC_ERR_ARG, "group_beam_generate: bad argument");
+    if ((rc = beam_check(*st))) return rc;
+    if ((rc = group_beam_check(*st, *grp))) return rc;
+    if (proc && (rc = check_procs(*proc, st->vocab))) return rc;
+    GVC_REQUIRE(st->vocab == c->dm.vocab, GVC_ERR_ARG, "group_beam_generate: vocab mismatch");
+    GVC_REQUIRE(i0 + n_steps <= st->max_new, GVC_ERR_ARG, "group_beam_generate: steps %d..%d past max_new %d", i0, i0 + n_steps,
+                st->max_new);
+    const int key_bound = max_keys > 0 ? max_keys : st->n0 + i0 + n_steps;
+    GVC_REQUIRE(key_bound < c->dm.max_seq, GVC_ERR_STATE,
+                "group_beam_generate: %d cached positions would overflow the KV cache (max_seq %d)", key_bound, c->dm.max_seq);
+    hipStream_t s = (hipStream_t)sv;
+    const int B = st->B, K = st->K, BK = B * K;
+    GenPlan pl;
+    if ((rc = beam_plan(c, B, K, key_bound, &pl))) return rc;
+    if ((rc = flush_pending(c, slots, BK, s))) return rc;
+    if (i0 == 0 && grp->G > 1) {
+        // group g starts from beam g*S, but only slot b*K is prefilled: the whole prefix goes to the item's other slots first (tok_buf
+        // holds the source of every row until the first select rewrites it; a pair with src == dst copies nothing)
+        if ((rc = launch_group_fan_src(slots, c->tok_buf, BK, K, s))) return rc;
+        rc = launch_kv_fanout(c->tok_buf, slots, BK, c->kv, c->dm.n_layer, c->dm.n_head, c->dm.max_seq, c->hd, c->dm.max_slots,
+                              c->kv_bf16 ? 2 : 4, c->st.seq_len, c->st.mel_pos, c->slot_logits, c->dm.vocab, c->slot_latent, c->dm.d_model,
+                              c->st.pending, s);
+        if (rc) return rc;
+    }
+    if ((rc = launch_beam_begin(c->beam_call, *st, proc, grp, i0, slots, c->gen_call->slots, c->logits, c->slot_logits, s))) return rc;
+    c->last_variant = pl.variant;
+    if ((rc = replay_steps(n_steps, s, [&](int unroll, hipGraphExec_t* ge) { return group_beam_graph(c, B, K, pl, unroll, ge); })))
+        return rc;
+    return launch_beam_end(c->gen_call->slots, slots, BK, c->logits, c->slot_logits, c->dm.vocab, s);
 }
 
 // ---------------------------------------------------------------------------------------------

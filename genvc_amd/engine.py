@@ -395,6 +395,87 @@ def beam_select(beam, logits, slots, t):
               "beam_select_proc")
 
 
+def check_beam_groups(K, G, diversity_penalty):
+    """HF's rules for num_beams = K, num_beam_groups = G, diversity_penalty (ValueError each): G in [1, K], K % G == 0, a finite
+    diversity_penalty >= 0 that is positive only with G > 1 (plain beam search has no Hamming processor to hand it to)"""
+    K, G, lam = int(K), int(G), float(diversity_penalty)
+    if G < 1:
+        raise ValueError(f"`num_beam_groups` has to be an integer strictly greater than 0, but is {G}")
+    if G > K:
+        raise ValueError(f"`num_beam_groups` ({G}) has to be smaller or equal to `num_beams` ({K})")
+    if K % G != 0:
+        raise ValueError(f"`num_beams` ({K}) should be divisible by `num_beam_groups` ({G}) for group beam search")
+    if lam != lam or lam in (float("inf"), float("-inf")) or lam < 0.0:
+        raise ValueError(f"`diversity_penalty` has to be a finite float >= 0, but is {diversity_penalty!r}")
+    if lam > 0.0 and G == 1:
+        raise ValueError(f"`diversity_penalty` ({lam}) is not 0.0 but `num_beam_groups` is 1: it only has an effect in group beam search")
+    return K, G, lam
+
+
+class GroupBeamSearch(BeamSearch):
+    """device state of one group (diverse) beam search (gvc_beam_state + gvc_beam_groups, include/genvc_hip.h): BeamSearch's arrays
+    with the K rows of an item read as G groups of S = K / G (rows g*S .. g*S + S-1), the running score 0 at the first beam of every
+    group, and the per-(item, group) done flags, hypothesis counts and worst kept scores.  G == 1 is the plain search."""
+
+    def __init__(self, fake, K, G, diversity_penalty, max_new, eos, vocab, length_penalty=1.0, repetition_penalty=1.0, length_mode="4.33",
+                 proc=None, early_stopping=False):
+        K, G, lam = check_beam_groups(K, G, diversity_penalty)
+        super().__init__(fake, K, max_new, eos, vocab, length_penalty, repetition_penalty, length_mode, proc, early_stopping)
+        B, dev = self.B, fake.device
+        self.G, self.S, self.diversity_penalty = G, K // G, lam
+        self.scores.view(B, K)[:, ::self.S] = 0.0
+        self.group_done = torch.zeros(B, G, device=dev, dtype=torch.int32)
+        self.group_count = torch.zeros(B, G, device=dev, dtype=torch.int32)
+        self.group_worst = torch.full((B, G), 1e9, device=dev, dtype=torch.float32)
+        self.g = _lib.BeamGroups(G, lam, self.group_done.data_ptr(), self.group_count.data_ptr(), self.group_worst.data_ptr())
+
+    def finalize(self, num_return=1):
+        """BeamSearchScorer.finalize with num_beam_groups: the running beams of every group not done join that group's set (capacity
+        S, in beam order), the num_return best hypotheses over the G sets of an item win, best first at rows b * num_return + j (a
+        stable descending sort over the sets in group order, each in its kept order).  Returns as BeamSearch.finalize"""
+        B, K, G, S, T = self.B, self.K, self.G, self.S, self.steps
+        N = int(num_return)
+        if not 1 <= N <= K:
+            raise ValueError(f"`num_return_sequences` ({N}) has to be smaller or equal to `num_beams` ({K}), and at least 1")
+        L = self.n0 + T if BEAM_LENGTH_MODES[self.length_mode] == 0 else T
+        ids = self.ids[T & 1].view(B, K, -1)[:, :, self.n0:self.n0 + T]
+        done = self.group_done.bool().cpu()
+        cnt = self.group_count.cpu()
+        hs, hl = self.hyp_score.cpu(), self.hyp_len.cpu()
+        run = (self.scores.view(B, K) / (float(L) ** self.length_penalty)).cpu()
+        best = []
+        for b in range(B):
+            cand = []
+            for g in range(G):
+                items = [(float(hs[b, g * S + i]), ("h", g * S + i)) for i in range(int(cnt[b, g]))]
+                if not done[b, g]:
+                    for k in range(g * S, (g + 1) * S):
+                        sc = float(run[b, k])
+                        if len(items) < S:
+                            items.append((sc, ("r", k)))
+                        elif sc > min(s for s, _ in items):
+                            del items[min(range(len(items)), key=lambda i: (items[i][0], i))]
+                            items.append((sc, ("r", k)))
+                cand.extend(items)
+            best.extend((b, it) for it in sorted(cand, key=lambda x: x[0])[::-1][:N])
+        rows = []
+        for b, (sc, (kind, i)) in best:
+            rows.append(self.hyp_tok[b, i, :int(hl[b, i])] if kind == "h" else ids[b, i])
+        width = min(max(int(r.shape[0]) for r in rows) + 1, self.max_new)
+        out = torch.full((B * N, width), self.eos, device=self.ids.device, dtype=torch.long)
+        for b, r in enumerate(rows):
+            n = min(int(r.shape[0]), width)
+            out[b, :n] = r[:n].long()
+        return out, torch.tensor([sc for _, (sc, _) in best], dtype=torch.float64)
+
+
+def group_beam_select(beam, logits, slots, t):
+    """one select step of `beam` (a GroupBeamSearch) on logits [B*K, vocab] at step t, the groups walked in order inside one launch;
+    slots [B*K] int32 are permuted in place, group by group (include/genvc_hip.h: gvc_group_beam_select)"""
+    check(lib().gvc_group_beam_select(C.byref(beam.c), C.byref(beam.g), C.byref(beam.proc) if beam.proc is not None else None,
+                                      ptr(_f32(logits)), ptr(_i32(slots)), int(t), stream()), "group_beam_select")
+
+
 MAX_CONTRASTIVE_K = 16    # kCsMaxK (csrc/contrastive.h)
 
 
@@ -744,6 +825,19 @@ class GptEngine:
     def warmup_contrastive(self, B, K, max_keys=0):
         """warmup() for contrastive_generate over B items of K candidates (include/genvc_hip.h: gvc_gpt_warmup_contrastive)"""
         check(lib().gvc_gpt_warmup_contrastive(self._h, int(B), int(K), int(max_keys)), "warmup_contrastive")
+
+    def group_beam_generate(self, slots, beam, n_steps, max_keys=0):
+        """beam_generate for a GroupBeamSearch (include/genvc_hip.h: gvc_gpt_group_beam_generate): with G > 1 the first call fans the
+        prefilled slot of every item out to its other K-1 slots before the first step"""
+        self._join_side()
+        check(lib().gvc_gpt_group_beam_generate(self._h, ptr(_i32(slots)), C.byref(beam.c), C.byref(beam.g),
+                                                C.byref(beam.proc) if beam.proc is not None else None, int(beam.steps), int(n_steps),
+                                                int(max_keys), stream()), "group_beam_generate")
+        beam.steps += int(n_steps)
+
+    def warmup_group_beam(self, B, K, G, max_keys=0):
+        """warmup() for group_beam_generate over B items of K beams in G groups (include/genvc_hip.h: gvc_gpt_warmup_group_beam)"""
+        check(lib().gvc_gpt_warmup_group_beam(self._h, int(B), int(K), int(G), int(max_keys)), "warmup_group_beam")
 
     def warmup_beam(self, B, K, max_keys=0):
         """warmup() for beam_generate over B items of K beams (include/genvc_hip.h: gvc_gpt_warmup_beam)"""

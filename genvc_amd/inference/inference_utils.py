@@ -74,7 +74,7 @@ def _segment_latents(m, cond_latent, codes, gen, repass_latents, row=0):
 
 @torch.inference_mode()
 def synthesize_utt(genVC_mdl, src_wav, tgt_audio, seg_len=6.0, return_details=False, repass_latents=False, num_beams=1,
-                   generate_kwargs=None, num_return_sequences=None):
+                   generate_kwargs=None, num_return_sequences=None, num_beam_groups=None, diversity_penalty=None):
     """non-streaming conversion, latent-level concatenation (reference :23-89).  num_beams = K > 1: every segment decodes with
     deterministic beam search (GPT.generate(num_beams=K, do_sample=False)); its latents come from the re-pass.
     generate_kwargs: more GPT.generate kwargs (the logits processors: min_new_tokens, no_repeat_ngram_size, ...; the
@@ -82,12 +82,18 @@ def synthesize_utt(genVC_mdl, src_wav, tgt_audio, seg_len=6.0, return_details=Fa
     num_return_sequences = N > 1 (the keyword, or in generate_kwargs): a LIST of N results, candidate j of the utterance being the
     concatenation of candidate j of every segment (GPT.generate(num_return_sequences=N) per segment: one prefill, N rows); with
     return_details each dict also carries "score", the sum over the segments of the candidate's score (sampling: sequence_logprobs,
-    the raw model distribution; beam search: the normalised beam score)."""
+    the raw model distribution; beam search: the normalised beam score).
+    num_beam_groups = G > 1 with diversity_penalty > 0 (the keywords, or in generate_kwargs; needs num_beams = K, a multiple of G):
+    every segment decodes with group (diverse) beam search, whose N best hypotheses start from different groups."""
     m = genVC_mdl
     from genvc_amd.layers.gpt import _num_return
     gkw = dict(generate_kwargs or {})
     if num_return_sequences is not None:
         gkw["num_return_sequences"] = num_return_sequences
+    if num_beam_groups is not None:
+        gkw["num_beam_groups"] = num_beam_groups
+    if diversity_penalty is not None:
+        gkw["diversity_penalty"] = diversity_penalty
     if _num_return(gkw) > 1:
         return _synthesize_candidates(m, src_wav, tgt_audio, seg_len, return_details, repass_latents, num_beams, gkw)
     min_len = int(0.32 * m.content_sample_rate)
@@ -99,7 +105,7 @@ def synthesize_utt(genVC_mdl, src_wav, tgt_audio, seg_len=6.0, return_details=Fa
         feat = m.content_extractor.extract_content_features(src_seg)
         codes = m.content_dvae.get_codebook_indices(feat.transpose(1, 2))
         kw = _sampling_kwargs(m) if num_beams == 1 else dict(_sampling_kwargs(m), do_sample=False, num_beams=int(num_beams))
-        gen = m.gpt.generate(cond_latent, codes, output_attentions=False, **dict(kw, **(generate_kwargs or {})))[0]
+        gen = m.gpt.generate(cond_latent, codes, output_attentions=False, **dict(kw, **gkw))[0]
         gen = gen[gen != m.gpt.stop_audio_token]                        # reference :68 (0-d collapse guarded)
         if gen.numel() == 0:
             continue

@@ -93,7 +93,7 @@ class GenVCModel(nn.Module):
 
     @torch.inference_mode()
     def warmup(self, seg_len=1.0, streams=1, ref_seconds=3.0, stream_chunk_size=8, top_k=None, max_new_tokens=None, num_beams=1,
-               contrastive_top_k=None, num_return_sequences=1):
+               contrastive_top_k=None, num_return_sequences=1, num_beam_groups=1):
         """Everything the FIRST conversion of this shape would otherwise pay inside its latency window (the reference leaves warm-up
         to the user: /root/reference/infer.py:27-30 runs a conversion first).  For `streams` concurrent streams of `seg_len`-second
         segments and a `ref_seconds` reference:
@@ -101,6 +101,8 @@ class GenVCModel(nn.Module):
             weight pack and topology probe; the captured step graphs) -- after it no GPT data-path call allocates or synchronises;
           * ContentVec / DVAE / HiFi-GAN / mel + Perceiver: one pass over zeros of the real shapes (their per-shape graphs and plans).
         num_beams = K > 1: also the beam step graphs of `streams` items x K beams (GPT.generate(num_beams=K, do_sample=False)).
+        num_beam_groups = G > 1 (with num_beams = K): the group beam step graphs instead (GPT.generate(num_beams=K, num_beam_groups=G,
+        diversity_penalty=..., do_sample=False)).
         contrastive_top_k = K > 1: also the contrastive-search buffers and step graphs of `streams` items x K candidates
         (GPT.generate(top_k=K, do_sample=False, penalty_alpha=a)).
         num_return_sequences = N > 1: also the step graphs of the streams * N rows an N-candidate call decodes
@@ -128,7 +130,9 @@ class GenVCModel(nn.Module):
         eng.warmup_range(streams, min(n0 + grp, hi), hi, top_k)
         if int(num_return_sequences) > 1:
             eng.warmup_range(streams * int(num_return_sequences), min(n0 + grp, hi), hi, top_k)
-        if int(num_beams) > 1:
+        if int(num_beams) > 1 and int(num_beam_groups) > 1:
+            eng.warmup_group_beam(streams, int(num_beams), int(num_beam_groups), hi)
+        elif int(num_beams) > 1:
             eng.warmup_beam(streams, int(num_beams), hi)
         if contrastive_top_k is not None and int(contrastive_top_k) > 1:
             eng.warmup_contrastive(streams, int(contrastive_top_k), hi)
@@ -142,7 +146,7 @@ class GenVCModel(nn.Module):
     @torch.no_grad()
     def inference(self, src_audio, cond_latent, do_sample=True, top_p=0.85, top_k=15, temperature=0.75, num_beams=1,
                   length_penalty=1.0, repetition_penalty=10.0, output_attentions=False, repass_latents=False, generate_kwargs=None,
-                  num_return_sequences=None):
+                  num_return_sequences=None, num_beam_groups=None, diversity_penalty=None):
         """reference trainers/hifigan_trainer.py:457-500: one source segment [1,T] + conditioning latents -> waveform
         [1,1,1024 n]: ContentVec -> content codes -> generate -> strip stop tokens -> latent re-pass -> x4 linear
         interpolation -> HiFi-GAN.  (The reference's 0-d collapse at exactly one non-stop token, SURVEY appendix B.9, is
@@ -152,7 +156,9 @@ class GenVCModel(nn.Module):
         num_return_sequences = N > 1 (the keyword, or in generate_kwargs; sampling only): a LIST of N waveforms, the candidates of
         GPT.generate(num_return_sequences=N) in row order, each stripped of its stop tokens and vocoded from the decode loop's own
         latents (or the re-pass with `repass_latents=True`); `last_sequence_logprobs` / `last_sequence_lengths` hold their scores
-        (GPT.sequence_logprobs: the raw model distribution).  N = 1 returns the one waveform, not a list."""
+        (GPT.sequence_logprobs: the raw model distribution).  N = 1 returns the one waveform, not a list.
+        num_beam_groups = G > 1 with diversity_penalty > 0 (and num_beams = K, do_sample=False): group (diverse) beam search; with
+        num_return_sequences = N <= K the N waveforms are its N best hypotheses, `last_beam_scores` their scores."""
         feat = self.content_extractor.extract_content_features(src_audio)
         codes = self.content_dvae.get_codebook_indices(feat.transpose(1, 2))
         kw = dict(do_sample=do_sample, top_p=top_p, top_k=top_k, temperature=temperature, num_beams=num_beams,
@@ -160,6 +166,10 @@ class GenVCModel(nn.Module):
         kw.update(generate_kwargs or {})
         if num_return_sequences is not None:
             kw["num_return_sequences"] = num_return_sequences
+        if num_beam_groups is not None:
+            kw["num_beam_groups"] = num_beam_groups
+        if diversity_penalty is not None:
+            kw["diversity_penalty"] = diversity_penalty
         from genvc_amd.layers.gpt import _num_return
         if _num_return(kw) > 1:
             return self._inference_candidates(cond_latent, codes, kw, repass_latents)

@@ -11,7 +11,7 @@ import torch
 from torch import nn
 
 from .._lib import GenvcHipError
-from ..engine import (BEAM_LENGTH_MODES, beam_early_stopping, MAX_CONTRASTIVE_K, PROC_KWARGS, WARP_KWARGS, BeamSearch, ContrastiveSearch, GptEngine, WarperSets,
+from ..engine import (BEAM_LENGTH_MODES, beam_early_stopping, check_beam_groups, GroupBeamSearch, MAX_CONTRASTIVE_K, PROC_KWARGS, WARP_KWARGS, BeamSearch, ContrastiveSearch, GptEngine, WarperSets,
                       check_proc_kwargs, logits_processors, logits_sets, logits_warpers, sample_params)
 from .perceiver_encoder import PerceiverResampler
 
@@ -25,7 +25,7 @@ JOINT_SAMPLING_DEFAULT = False
 
 def _no_beams(kw, where):
     """the paths that decode one beam per stream: num_beams > 1 raises, naming the path"""
-    if int(kw.get("num_beams", 1) or 1) != 1:
+    if int(kw.get("num_beams", 1) or 1) != 1 or _grouped(kw):
         raise NotImplementedError(f"beam search (num_beams={kw.get('num_beams')}) is not on the {where} path: GPT.generate serves it "
                                   "(the reference streams with num_beams=1 only, inference_utils.py:62,178)")
 
@@ -62,12 +62,11 @@ def _beam_kwargs(kw):
     """the modes of HF generate(num_beams > 1) this build does not serve raise NotImplementedError, naming the mode; returns the
     (K, length_penalty, repetition_penalty, beam_length_mode) of a deterministic beam search.  num_return_sequences outside [1, K] and an
     early_stopping other than False, True or "never" raise ValueError (HF's rules); _beam_returns gives the two"""
-    K = int(kw.get("num_beams", 1))
+    K = int(kw.get("num_beams", 1) or 1)
+    _beam_groups(kw)
     if kw.get("do_sample", True):
         raise NotImplementedError(f"beam sampling (do_sample=True, num_beams={K}) is not implemented: deterministic beam search needs "
                                   "do_sample=False")
-    if int(kw.get("num_beam_groups", 1) or 1) != 1 or kw.get("diversity_penalty"):
-        raise NotImplementedError("group / diverse beam search (num_beam_groups > 1, diversity_penalty) is not implemented")
     if kw.get("constraints") or kw.get("force_words_ids"):
         raise NotImplementedError("constrained beam search (constraints, force_words_ids) is not implemented")
     _beam_returns(kw)
@@ -75,6 +74,35 @@ def _beam_kwargs(kw):
     if mode not in BEAM_LENGTH_MODES:
         raise ValueError(f"beam_length_mode must be one of {sorted(BEAM_LENGTH_MODES)}, not {mode!r}")
     return K, float(kw.get("length_penalty", 1.0)), float(kw.get("repetition_penalty", 1.0)), mode
+
+
+def _grouped(kw):
+    """the call names group beam search: num_beam_groups other than 1, or a diversity_penalty other than 0"""
+    g, lam = kw.get("num_beam_groups"), kw.get("diversity_penalty")
+    return (g is not None and int(g) != 1) or (lam is not None and float(lam) != 0.0)
+
+
+def _beam_groups(kw):
+    """(num_beam_groups, diversity_penalty) of a beam search, (1, 0.0) without groups; validated as HF validates them (ValueError:
+    do_sample=True with groups, K % G != 0, G > K, a diversity_penalty that is not finite and >= 0 or is positive with G == 1, a
+    non-default typical_p -- the reference's dispatcher, layers/stream_generator.py:522-524).  G > 1 without a positive
+    diversity_penalty is NotImplementedError: the groups would all run the same search."""
+    if not _grouped(kw):
+        return 1, 0.0
+    K = int(kw.get("num_beams", 1) or 1)
+    G = 1 if kw.get("num_beam_groups") is None else int(kw["num_beam_groups"])
+    lam = 0.0 if kw.get("diversity_penalty") is None else float(kw["diversity_penalty"])
+    if kw.get("do_sample", True):
+        raise ValueError("`diversity_penalty` / `num_beam_groups` is not a valid argument when `do_sample=True`: group beam search is "
+                         "deterministic")
+    K, G, lam = check_beam_groups(K, G, lam)
+    typ = kw.get("typical_p")
+    if typ is not None and float(typ) != 1.0:
+        raise ValueError("Decoder argument `typical_p` is not supported with beam groups.")
+    if lam == 0.0:
+        raise NotImplementedError(f"group beam search (num_beam_groups={G}) without a positive diversity_penalty is not implemented: "
+                                  "identical groups are not served")
+    return G, lam
 
 
 def _beam_returns(kw):
@@ -388,7 +416,7 @@ class GPT(nn.Module):
         _num_return(generate_kwargs)
         if _contrastive_kwargs(generate_kwargs) is not None:
             return self._generate_contrastive(cond_latents, text_inputs, generate_kwargs)
-        if int(generate_kwargs.get("num_beams", 1) or 1) > 1:
+        if int(generate_kwargs.get("num_beams", 1) or 1) > 1 or _grouped(generate_kwargs):
             return self._generate_beams(cond_latents, text_inputs, generate_kwargs)
         N = _sample_return_kwargs(generate_kwargs, int(text_inputs.shape[0]), self.max_slots)
         fake = self.compute_embeddings(cond_latents, text_inputs)
@@ -437,10 +465,14 @@ class GPT(nn.Module):
         device at the end.  beam_length_mode: "4.33" (default: the lengths the reference's pinned transformers normalises by) or
         "generated" (those of the installed transformers).  Needs B*K <= the context's KV slots (ValueError otherwise).  Returns
         int64 [B, n] (gpt.py:609: the prompt sliced away); the best normalised score per item lands in `last_beam_scores`, and
-        `last_latents` is None (the caller's latents come from the teacher-forced re-pass, hifigan_trainer.py:489-494)."""
+        `last_latents` is None (the caller's latents come from the teacher-forced re-pass, hifigan_trainer.py:489-494).
+        num_beam_groups = G > 1 with diversity_penalty > 0: group (diverse) beam search (include/genvc_hip.h: gvc_beam_groups,
+        DESIGN.md 4.12): the K beams are G groups of K / G searched one after the other within every step, each penalised for the
+        tokens the earlier groups chose at that step; the N best hypotheses over all groups are returned."""
         kw = dict(generate_kwargs)
         K, lp, rep, mode = _beam_kwargs(kw)
         N, early = _beam_returns(kw)
+        G, lam = _beam_groups(kw)
         self._need_engine()
         group = int(kw.pop("group", 16))
         B = int(text_inputs.shape[0])
@@ -456,11 +488,16 @@ class GPT(nn.Module):
         def run():
             slots = torch.arange(B * K, device=dev, dtype=torch.int32)
             self.engine.prefill(slots[::K].contiguous(), self._prefix, want_outputs=False)      # each item once; the first step fans out
-            beam = BeamSearch(fake, K, max_new, self.stop_audio_token, self.num_audio_tokens, lp, rep, mode, early_stopping=early,
-                              **_proc_arg(proc))
+            if G > 1:
+                beam = GroupBeamSearch(fake, K, G, lam, max_new, self.stop_audio_token, self.num_audio_tokens, lp, rep, mode,
+                                       early_stopping=early, **_proc_arg(proc))
+            else:
+                beam = BeamSearch(fake, K, max_new, self.stop_audio_token, self.num_audio_tokens, lp, rep, mode, early_stopping=early,
+                                  **_proc_arg(proc))
+            step = self.engine.group_beam_generate if G > 1 else self.engine.beam_generate
             while beam.steps < max_new:
                 n = min(group, max_new - beam.steps)
-                self.engine.beam_generate(slots, beam, n, max_keys=n0 + beam.steps + n)
+                step(slots, beam, n, max_keys=n0 + beam.steps + n)
                 stop = bool(beam.done.all().item())
                 self.engine.health()          # (the .item() above synchronised)
                 if stop:

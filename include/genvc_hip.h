@@ -364,6 +364,40 @@ int gvc_gpt_beam_generate_proc(gvc_gpt* ctx, int32_t* slots, const gvc_beam_stat
                                int32_t n_steps, int32_t max_keys, gvc_stream s);
 
 /* ------------------------------------------------------------------------------------------
+ * Group (diverse) beam search (HF generate(num_beams=K, num_beam_groups=G, diversity_penalty=lambda, do_sample=False); the reference
+ * hands every kwarg to HF generate, layers/gpt.py:594-609, and its pinned dispatcher routes the mode, layers/stream_generator.py:308-317,
+ * 512-556).  The semantics are transformers 4.33's group_beam_search, HammingDiversityLogitsProcessor and BeamSearchScorer with
+ * num_beam_groups, restated from the published source.  The K beams of an item are G groups of S = K / G: rows
+ * b*K + g*S + i belong to group g.  The running score starts at 0 for the first beam of every group and at -1e9 for the others.  Per
+ * step the groups run in order inside one launch; for the S rows of group g: s = log_softmax(logits); for g > 0, s[x] -= lambda * f[x],
+ * f[x] = how often token x was chosen at this step by the rows of groups 0..g-1 of the item (a done group: eos S times; eos is
+ * penalised like any x); then the repetition penalty, the processors and the running score as in the plain search; top-2S of the group's
+ * S x vocab candidates, walked as the plain search walks 2K with K replaced by S: the kept set (capacity S), its count, its worst score
+ * and the done flag are the (item, group)'s; parents are beams of the same group.  A done group keeps its beams (tokens = eos, parents
+ * = identity, no copies); the item (st->done) is done when all its groups are.  The state is a gvc_beam_state whose hypothesis store
+ * [B][K] reads [B][G][S]; st->hyp_count / st->hyp_worst are written for G == 1 only (then every output equals the plain search's).
+ * ------------------------------------------------------------------------------------------ */
+typedef struct {
+    int32_t G;                      /* groups per item: 1 <= G <= K, K % G == 0 */
+    float diversity_penalty;        /* lambda: finite, >= 0 */
+    int32_t* done;                  /* [B][G] group done (0 / 1; start 0) */
+    int32_t* hyp_count;             /* [B][G] hypotheses kept by the group (start 0) */
+    float* hyp_worst;               /* [B][G] worst kept score of the group (start 1e9) */
+} gvc_beam_groups;
+
+/* gvc_beam_select / gvc_beam_select_proc for a group search (proc HOST, nullable).  st->parents are beams within the item (0..K-1, inside
+ * the row's group); the slot permutation runs per group, so a step makes at most K - G copies per item.  At t == 0 the copies of a G > 1
+ * search start at n0 (the caller has fanned the prefix out to every slot); G == 1 computes gvc_beam_select bit for bit. */
+int gvc_group_beam_select(const gvc_beam_state* st, const gvc_beam_groups* grp, const gvc_logits_processors* proc, const float* logits,
+                          int32_t* slots, int32_t t, gvc_stream s);
+/* gvc_gpt_beam_generate / gvc_gpt_beam_generate_proc for a group search (proc HOST, nullable): [group select -> KV span copies -> decode
+ * step over B*K rows] from captured graphs of their own kind.  The caller has prefilled item b into slots[b*K]; with G > 1 the call
+ * with i0 == 0 first fans that slot out to the item's other K-1 slots (as gvc_gpt_kv_fanout), so every group starts from a whole prefix.
+ * K % G != 0, G > K, K > 16 and a lambda that is not finite or below 0 are GVC_ERR_ARG.  Status codes as gvc_gpt_beam_generate. */
+int gvc_gpt_group_beam_generate(gvc_gpt* ctx, int32_t* slots, const gvc_beam_state* st, const gvc_beam_groups* grp,
+                                const gvc_logits_processors* proc, int32_t i0, int32_t n_steps, int32_t max_keys, gvc_stream s);
+
+/* ------------------------------------------------------------------------------------------
  * Contrastive search (HF generate(top_k=K > 1, do_sample=False, penalty_alpha=a > 0); reference layers/gpt.py:594-609 hands every kwarg
  * to HF generate, whose pinned 4.33 selects this mode by that test, layers/stream_generator.py:264-270 restates it and :366-385 routes it
  * to contrastive_search without a logits warper).  The semantics are transformers 4.33's contrastive_search + _ranking_fast:
@@ -501,6 +535,8 @@ int gvc_gpt_warmup_range(gvc_gpt* ctx, int32_t B, int32_t min_keys, int32_t max_
 /* gvc_gpt_warmup for gvc_gpt_beam_generate over B items of K beams: the beam step graphs of every context class up to max_keys cached
  * positions (and everything gvc_gpt_warmup(B*K) prepares).  Afterwards such calls neither allocate nor synchronise */
 int gvc_gpt_warmup_beam(gvc_gpt* ctx, int32_t B, int32_t K, int32_t max_keys);
+/* ... for gvc_gpt_group_beam_generate over B items of K beams in G groups (the group step graphs do not depend on G beyond its checks) */
+int gvc_gpt_warmup_group_beam(gvc_gpt* ctx, int32_t B, int32_t K, int32_t G, int32_t max_keys);
 /* Diagnostic: allocations / device-wide synchronisations / graph captures this context has done INSIDE data-path calls (first use
  * of a path that gvc_gpt_warmup had not prepared; a rebind after the weight pack was built; the fallback after a hand-off
  * time-out).  gvc_gpt_warmup's own work does not count.  Tests assert it stays put across warmed-up calls. */

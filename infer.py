@@ -32,6 +32,11 @@ if __name__ == "__main__":
                         help="GPT weight / KV-cache storage on the GPU (fp32 = the reference's numerics)")
     parser.add_argument("--num_beams", type=int, default=1,
                         help="non-streaming only: > 1 decodes with deterministic beam search (do_sample=False) of this width")
+    parser.add_argument("--num_beam_groups", type=int, default=1,
+                        help="with --num_beams K: > 1 splits the beams into this many groups (K a multiple of it) searched one after the "
+                             "other, each penalised for the tokens the earlier groups chose (group beam search); needs --diversity_penalty")
+    parser.add_argument("--diversity_penalty", type=float, default=None,
+                        help="with --num_beam_groups > 1: the penalty (> 0) per earlier group's choice of the same token at a step")
     parser.add_argument("--penalty_alpha", type=float, default=None,
                         help="non-streaming only: > 0 decodes with contrastive search (do_sample=False) over --top_k candidates (2..16)")
     parser.add_argument("--num_return_sequences", type=int, default=1,
@@ -53,6 +58,12 @@ if __name__ == "__main__":
         raise SystemExit("--num_return_sequences must be >= 1, and 1 with --streaming or --penalty_alpha")
     if args.num_beams > 1 and args.num_return_sequences > args.num_beams:
         raise SystemExit("--num_return_sequences must not exceed --num_beams")
+    if args.num_beam_groups != 1 or args.diversity_penalty is not None:
+        lam = args.diversity_penalty
+        if (args.num_beam_groups < 2 or args.num_beams % args.num_beam_groups != 0 or args.num_beam_groups > args.num_beams or lam is None
+                or not lam > 0.0 or lam == float("inf") or args.penalty_alpha is not None):
+            raise SystemExit("--num_beam_groups must be >= 2 and divide --num_beams, with a finite --diversity_penalty > 0 and without "
+                             "--penalty_alpha")
     if args.penalty_alpha is not None:
         if args.streaming or not args.penalty_alpha > 0.0 or args.penalty_alpha == float("inf") or not 2 <= args.top_k <= 16:
             raise SystemExit("--penalty_alpha must be finite and > 0, non-streaming, with --top_k in [2, 16]")
@@ -71,6 +82,8 @@ if __name__ == "__main__":
         if not ((v > 0.0 if lo_open else v >= 0.0) and (v < 1.0 if hi_open else v <= 1.0)):
             raise SystemExit(f"bad warper flag: --{k} must be in {'(' if lo_open else '['}0, 1{')' if hi_open else ']'}, not {v}")
         gen_kw[k] = v
+    if args.num_beam_groups > 1:
+        gen_kw.update(num_beam_groups=args.num_beam_groups, diversity_penalty=args.diversity_penalty)
     try:
         from genvc_amd.engine import logits_processors, logits_warpers
         logits_processors(gen_kw, 0, 1026)
