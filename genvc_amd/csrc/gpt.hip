@@ -15,6 +15,7 @@
 #include "persist_rows.h"
 #include "persist_rows_b16.h"
 #include "beam.h"
+#include "cfg.h"
 #include "contrastive.h"
 #include "sampler.h"
 #include "seqscore.h"
@@ -187,6 +188,7 @@ struct GenCall {
     gvc_logits_processors sets[kMaxSampleRows];   // processor sets of a gvc_gpt_generate_proc_sets call (sc.proc_sets points here)
     int32_t set_of_row[kMaxSampleRows];      // ... and each row's index into them, -1: none (sc.set_of_row points here)
     gvc_logits_warpers warps[kMaxSampleRows];     // warpers of a gvc_gpt_generate_warp call, one per set (sc.warps points here)
+    float cfg_scale;                         // guidance scale of a gvc_gpt_generate_cfg call (k_cfg_guide reads it here)
 };
 
 // Start / end of a gvc_gpt_generate call in ONE launch each (they used to be a memset, k_set_gen_call and two k_stage_rows before the
@@ -305,10 +307,10 @@ struct GptLayer {
 };
 
 // What a captured generation graph bakes into its nodes, and so what tells two graphs of a context apart.
-enum GraphKind { kStepGraph, kBeamGraph, kContrastiveGraph, kGroupBeamGraph };
+enum GraphKind { kStepGraph, kBeamGraph, kContrastiveGraph, kGroupBeamGraph, kCfgGraph };
 struct GraphKey {
     int kind;       // GraphKind
-    int rows;       // rows of the decode step: the call's B streams, B * K of a search
+    int rows;       // rows of the decode step: the call's B streams, B * K of a search, 2B of a guided call
     int K;          // beams / candidates per item (0: step graphs)
     int fused;      // GEMV groups with the fused attention + c_proj launch
     int split;      // GenPlan::split
@@ -352,6 +354,7 @@ struct gvc_gpt {
                                                   // measured crossover: B=4 925 (GEMV) vs 975 us (rows), B=5 1242 vs 996 us
     float *logits = nullptr, *latent = nullptr;             // staging of the generation loop, indexed by position in the call
     float *slot_logits = nullptr, *slot_latent = nullptr;   // ... parked per slot between calls   // generate(): [slots][V], [slots][d]
+    float* guided = nullptr;          // [slots / 2][V] guided scores of a gvc_gpt_generate_cfg step (what its sampler reads as logits)
     int32_t* state = nullptr;         // seq_len[slots], mel_pos[slots], tok[slots], step
     GptState st;
     int32_t *tok_buf = nullptr, *step_ctr = nullptr;
@@ -492,7 +495,7 @@ extern "C" int gvc_gpt_create(const gvc_gpt_dims* dims, gvc_gpt** out) {
         (rc = alloc_f(&c->work, (size_t)c->work_cap)) || (rc = alloc_f(&c->logits, (size_t)D.max_slots * V)) ||
         (rc = alloc_f(&c->latent, (size_t)D.max_slots * d)) || (rc = alloc_f(&c->x2, (size_t)D.max_slots * d)) ||
         (rc = alloc_f(&c->slot_logits, (size_t)D.max_slots * V)) || (rc = alloc_f(&c->slot_latent, (size_t)D.max_slots * d)) ||
-        (rc = alloc_f(&c->part2, (size_t)D.max_slots * D.n_head * d))) {
+        (rc = alloc_f(&c->part2, (size_t)D.max_slots * D.n_head * d)) || (rc = alloc_f(&c->guided, (size_t)(D.max_slots / 2 + 1) * V))) {
         gvc_gpt_destroy(c);
         return rc;
     }
@@ -549,7 +552,7 @@ extern "C" int gvc_gpt_destroy(gvc_gpt* c) {
         if (p) hipFree(p);
     for (void* p : {(void*)c->wbase, (void*)c->wfm, (void*)c->wh, (void*)c->kv, (void*)c->x, (void*)c->a, (void*)c->q, (void*)c->h,
                     (void*)c->part, (void*)c->work, (void*)c->logits, (void*)c->latent, (void*)c->slot_logits, (void*)c->slot_latent, (void*)c->state, (void*)c->x2, (void*)c->part2,
-                    (void*)c->gen_call, (void*)c->beam_call, (void*)c->cs_call, (void*)c->exec_ctr})
+                    (void*)c->gen_call, (void*)c->beam_call, (void*)c->cs_call, (void*)c->exec_ctr, (void*)c->guided})
         if (p) hipFree(p);
     cs_free(&c->cs);
     delete c;
@@ -1754,6 +1757,22 @@ static int step_graph(gvc_gpt* c, int B, const GenPlan& pl, int unroll, hipGraph
     });
 }
 
+// Classifier-free guidance (gvc_gpt_generate_cfg): rows 0..B-1 of the slot table are the items' conditional slots, rows B..2B-1 their
+// unconditional ones.  One step = [k_cfg_guide over the logits rows (b, B + b) -> guided; the sampler over B rows, reading guided as its
+// logits; token b mirrored to row B + b; the decode step plan_generate picks for 2B rows].  The graphs live in the context's graph map
+// under kind kCfgGraph, so every path that drops the step graphs (time-out fallback, rearm, destroy) drops them too.
+static int cfg_graph(gvc_gpt* c, int B, const GenPlan& pl, int unroll, hipGraphExec_t* ge) {
+    const int V = c->dm.vocab;
+    return get_graph(c, GraphKey{kCfgGraph, 2 * B, 0, pl.fused, pl.split, unroll, pl.greedy, 0}, ge, [&](hipStream_t cs) {
+        int rc = launch_cfg_guide(c->logits, c->logits + (size_t)B * V, B, V, 1.f, &c->gen_call->cfg_scale, c->guided, cs);
+        if (rc == GVC_OK) rc = launch_sample_indirect(&c->gen_call->sc, B, pl.greedy, cs);
+        if (rc == GVC_OK) rc = launch_cfg_mirror(c->tok_buf, B, cs);
+        if (rc == GVC_OK)
+            rc = decode_step(c, c->gen_call->slots, 2 * B, c->tok_buf, c->logits, c->latent, c->step_ctr, cs, pl.fused, pl.key_chunks);
+        return rc;
+    });
+}
+
 // Replays n_steps steps on s: groups of step_unroll() steps, then the remainder one by one.  graph(unroll, &ge) hands out the graph of
 // that many steps; each of the two is asked for only when the call needs it.
 template <class Graph>
@@ -1851,16 +1870,20 @@ extern "C" int gvc_gpt_rearm(gvc_gpt* c) {
 
 // rows: null (gvc_gpt_generate: p's settings for every row) or B host entries (gvc_gpt_generate_rows).  proc: null or the call's
 // processors (gvc_gpt_generate_proc); set_of_row: null or B host indices into the n_sets host sets (gvc_gpt_generate_proc_sets, proc null)
-// and, when warps is set (gvc_gpt_generate_warp), into the n_sets host warpers too; sets is then nullable
+// and, when warps is set (gvc_gpt_generate_warp), into the n_sets host warpers too; sets is then nullable.  uslots: null, or the B
+// unconditional slots of a guided call (gvc_gpt_generate_cfg) with guidance scale `scale`
 static int generate_impl(gvc_gpt* c, const int32_t* slots, int32_t B, int32_t* ids, int32_t ids_stride, int32_t* ids_len, int32_t* finished,
                          const gvc_sample_params* p, const gvc_row_sampling* rows, const gvc_logits_processors* proc,
                          const gvc_logits_processors* sets, const gvc_logits_warpers* warps, int32_t n_sets, const int32_t* set_of_row,
                          int32_t i0,
                          int32_t n_steps, int32_t max_keys, int32_t* tokens_out, int32_t tok_stride, float* latents_out, int32_t lat_stride,
-                         gvc_stream sv) {
+                         gvc_stream sv, const int32_t* uslots = nullptr, float scale = 1.f) {
     int rc = check_ready(c);
     if (rc) return rc;
     GVC_REQUIRE(B >= 1 && B <= c->dm.max_slots && p && n_steps >= 0 && max_keys >= 0, GVC_ERR_ARG, "generate: bad argument");
+    GVC_REQUIRE(!uslots || 2 * B <= c->dm.max_slots, GVC_ERR_ARG, "generate_cfg: 2 * %d rows exceed the context's %d KV slots", B,
+                c->dm.max_slots);
+    const int Brows = uslots ? 2 * B : B;      // rows of the decode step
     bool rows_greedy = false;
     if (rows && (rc = check_sample_rows(rows, B, c->dm.vocab, &rows_greedy))) return rc;
     if (proc && (rc = check_procs(*proc, c->dm.vocab))) return rc;
@@ -1877,7 +1900,8 @@ static int generate_impl(gvc_gpt* c, const int32_t* slots, int32_t B, int32_t* i
     hipStream_t s = (hipStream_t)sv;
     GenPlan pl;
     // (a keyed call replays the greedy graphs when every row is greedy, the sampling ones otherwise: the step graphs are the same)
-    if ((rc = plan_generate(c, B, key_bound, rows ? (rows_greedy ? 1 : 0) : p->top_k, &pl))) return rc;
+    if ((rc = plan_generate(c, Brows, key_bound, rows ? (rows_greedy ? 1 : 0) : p->top_k, &pl))) return rc;
+    GVC_REQUIRE(!uslots || !pl.defer, GVC_ERR_STATE, "generate_cfg: the one-stream step cannot serve %d rows", Brows);
     c->last_variant = pl.variant;
     // One stream on the one-launch step: each step is [decode the pending token, if any; sample], the call ends after its last sample and
     // that token stays pending for the slot -- its decode opens the next call that continues the slot and never runs when the slot is
@@ -1886,13 +1910,13 @@ static int generate_impl(gvc_gpt* c, const int32_t* slots, int32_t B, int32_t* i
     if (pl.defer) {
         df.pending = c->st.pending; df.run = c->run_flag; df.tok = c->tok_buf;
         c->defer_seen = 1;
-    } else if ((rc = flush_pending(c, slots, B, s))) {
+    } else if ((rc = flush_pending(c, slots, B, s)) || (uslots && (rc = flush_pending(c, uslots, B, s)))) {
         return rc;
     }
     SampleCall sc;
     memset(&sc, 0, sizeof(sc));
     sc.run_flag = pl.defer ? c->run_flag : nullptr;
-    sc.logits = c->logits; sc.B = B; sc.ids = ids; sc.ids_stride = ids_stride; sc.ids_len = ids_len;
+    sc.logits = uslots ? c->guided : c->logits; sc.B = B; sc.ids = ids; sc.ids_stride = ids_stride; sc.ids_len = ids_len;
     sc.finished = finished; sc.p = *p; sc.step = 0; sc.step_ptr = c->step_ctr; sc.tok_out = c->tok_buf;
     sc.tokens_out = tokens_out; sc.tok_stride = tok_stride; sc.i0 = i0; sc.latent_src = c->latent;
     sc.latents_out = latents_out; sc.lat_stride = lat_stride; sc.d = c->dm.d_model;
@@ -1946,6 +1970,19 @@ static int generate_impl(gvc_gpt* c, const int32_t* slots, int32_t B, int32_t* i
                            c->dm.vocab, c->latent, c->slot_latent, c->dm.d_model, df);
     }
     GVC_LAUNCH_CHECK();
+    if (uslots) {
+        // the unconditional rows behind the conditional ones: slot table, parked logits and latents, and the scale
+        const int V = c->dm.vocab, d = c->dm.d_model;
+        if ((rc = launch_cfg_begin(c->gen_call->slots, uslots, B, scale, &c->gen_call->cfg_scale, c->logits, c->slot_logits, V, c->latent,
+                                   c->slot_latent, d, s)))
+            return rc;
+        if ((rc = replay_steps(n_steps, s, [&](int unroll, hipGraphExec_t* ge) { return cfg_graph(c, B, pl, unroll, ge); }))) return rc;
+        hipLaunchKernelGGL(k_gen_end, dim3(B), dim3(256), 0, s, slots, c->logits, c->slot_logits, V, c->latent, c->slot_latent, d);
+        hipLaunchKernelGGL(k_gen_end, dim3(B), dim3(256), 0, s, uslots, c->logits + (size_t)B * V, c->slot_logits, V,
+                           c->latent + (size_t)B * d, c->slot_latent, d);
+        GVC_LAUNCH_CHECK();
+        return GVC_OK;
+    }
     if ((rc = replay_steps(n_steps, s, [&](int unroll, hipGraphExec_t* ge) { return step_graph(c, B, pl, unroll, ge); }))) return rc;
     if (pl.defer)
         hipLaunchKernelGGL(k_gen_end_defer, dim3(1), dim3(64), 0, s, slots, c->st.pending, c->run_flag, c->tok_buf);
@@ -2005,6 +2042,39 @@ extern "C" int gvc_gpt_generate_warp(gvc_gpt* c, const int32_t* slots, int32_t B
                          set_of_row ? set_of_row : zeros, i0, n_steps, max_keys, tokens_out, tok_stride, latents_out, lat_stride, sv);
 }
 
+// Guided generation (classifier-free guidance, HF guidance_scale): gvc_gpt_generate_warp's call over B items of two KV slots each
+extern "C" int gvc_gpt_generate_cfg(gvc_gpt* c, const int32_t* slots, const int32_t* uncond_slots, int32_t B, float scale, int32_t* ids,
+                                    int32_t ids_stride, int32_t* ids_len, int32_t* finished, const gvc_sample_params* p,
+                                    const gvc_row_sampling* rows, const gvc_logits_processors* sets, const gvc_logits_warpers* warps,
+                                    int32_t n_sets, const int32_t* set_of_row, int32_t i0, int32_t n_steps, int32_t max_keys,
+                                    int32_t* tokens_out, int32_t tok_stride, float* latents_out, int32_t lat_stride, gvc_stream sv) {
+    GVC_REQUIRE(c && slots && uncond_slots, GVC_ERR_ARG, "generate_cfg: null argument");
+    GVC_REQUIRE(B >= 1 && 2 * B <= kMaxSampleRows, GVC_ERR_ARG, "generate_cfg: need 1..%d items, got %d", kMaxSampleRows / 2, B);
+    GVC_REQUIRE(scale == scale && fabsf(scale) <= 3.0e38f, GVC_ERR_ARG, "generate_cfg: the guidance scale is not finite");
+    GVC_REQUIRE(c->dm.vocab <= kCfgMaxVocab, GVC_ERR_UNSUPPORTED, "generate_cfg: vocab %d above %d", c->dm.vocab, kCfgMaxVocab);
+    int32_t zeros[kMaxSampleRows] = {};
+    const bool any = warps || sets;
+    return generate_impl(c, slots, B, ids, ids_stride, ids_len, finished, p, rows, nullptr, any ? sets : nullptr, any ? warps : nullptr,
+                         any ? n_sets : 0, any ? (set_of_row ? set_of_row : zeros) : nullptr, i0, n_steps, max_keys, tokens_out, tok_stride,
+                         latents_out, lat_stride, sv, uncond_slots, scale);
+}
+
+// gvc_gpt_warmup for gvc_gpt_generate_cfg over B items: everything gvc_gpt_warmup(2B) prepares, and the guided step graphs of every
+// context class up to max_keys cached positions
+extern "C" int gvc_gpt_warmup_cfg(gvc_gpt* c, int32_t B, int32_t max_keys, int32_t top_k) {
+    int rc = check_ready(c);
+    if (rc) return rc;
+    GVC_REQUIRE(B >= 1 && 2 * B <= c->dm.max_slots, GVC_ERR_ARG, "warmup_cfg: 2 * %d rows outside [2, %d]", B, c->dm.max_slots);
+    if ((rc = gvc_gpt_warmup(c, 2 * B, max_keys, top_k))) return rc;
+    WarmupScope warm(c);
+    // every context class a guided generation reaching max_keys passes through (the calls' bounds grow with the generation)
+    const int hi = max_keys > 0 ? max_keys : c->dm.max_seq - 1;
+    rc = warmup_sweep(1, hi, [&](int mk, GenPlan* pl) { return plan_generate(c, 2 * B, mk, top_k, pl); },
+                      [&](const GenPlan& pl, int unroll, hipGraphExec_t* ge) { return cfg_graph(c, B, pl, unroll, ge); });
+    if (rc) return rc;
+    GVC_CHECK_HIP(hipDeviceSynchronize());
+    return GVC_OK;
+}
 
 // ---------------------------------------------------------------------------------------------
 // beam search: one captured graph = [k_beam_select -> k_kv_copy_span -> decode step over B*K rows], replayed n_steps times.  The

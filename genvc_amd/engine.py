@@ -789,6 +789,47 @@ class GptEngine:
                                           int(i0), int(n_steps), int(max_keys), ptr(tokens_out), tokens_out.stride(0), ptr(latents_out),
                                           lat_stride, stream()), "generate_warp")
 
+    def cfg_guide(self, logits_cond, logits_uncond, scale):
+        """HF's classifier-free guidance combine on [B, V] rows (include/genvc_hip.h: gvc_cfg_guide):
+        scale * (log_softmax(cond) - log_softmax(uncond)) + log_softmax(uncond)"""
+        B, V = logits_cond.shape
+        assert logits_uncond.shape == (B, V) and logits_cond.is_cuda and logits_uncond.is_cuda
+        out = torch.empty(B, V, device=logits_cond.device, dtype=torch.float32)
+        check(lib().gvc_cfg_guide(ptr(_f32(logits_cond)), ptr(_f32(logits_uncond)), B, V, float(scale), ptr(out), stream()), "cfg_guide")
+        return out
+
+    def generate_cfg(self, slots, uncond_slots, scale, ids, ids_len, finished, params, sets, i0, n_steps, tokens_out, latents_out,
+                     max_keys=0, rows=None):
+        """generate_warp() under classifier-free guidance (include/genvc_hip.h: gvc_gpt_generate_cfg): item b decodes in slots[b]
+        (conditional prompt) and uncond_slots[b] (unconditional prompt), both prefilled; every step samples item b from
+        scale * (lsm(cond) - lsm(uncond)) + lsm(uncond) and feeds the token to both slots.  sets: a WarperSets over the B items, or
+        None.  ids / rows / tokens_out / latents_out have B rows: the conditional ones."""
+        self._join_side()
+        B = slots.shape[0]
+        if uncond_slots.shape[0] != B:
+            raise ValueError(f"{uncond_slots.shape[0]} unconditional slots for {B} items")
+        if sets is not None and len(sets) != B:
+            raise ValueError(f"{len(sets)} set indices for {B} rows")
+        arr = _rows_arg(rows, B) if rows is not None else None
+        assert tokens_out.is_cuda and tokens_out.dtype == torch.int32 and tokens_out.stride(1) == 1
+        lat_stride = 0
+        if latents_out is not None:
+            assert latents_out.is_cuda and latents_out.dtype == torch.float32 and latents_out.stride(2) == 1
+            assert latents_out.stride(1) == self.d and latents_out.stride(0) % self.d == 0
+            lat_stride = latents_out.stride(0) // self.d
+        if rows is not None:
+            params = sample_params(dict(repetition_penalty=1.0, temperature=1.0, top_p=1.0, top_k=0), self.V, self.dims["stop_audio_token"])
+        check(lib().gvc_gpt_generate_cfg(self._h, ptr(_i32(slots)), ptr(_i32(uncond_slots)), B, float(scale), ptr(_i32(ids)), ids.shape[1],
+                                         ptr(_i32(ids_len)), ptr(_i32(finished)), C.byref(params), arr,
+                                         sets.sets if sets is not None else None, sets.warps if sets is not None else None,
+                                         sets.n_sets if sets is not None else 0, sets.set_of_row if sets is not None else None,
+                                         int(i0), int(n_steps), int(max_keys), ptr(tokens_out), tokens_out.stride(0), ptr(latents_out),
+                                         lat_stride, stream()), "generate_cfg")
+
+    def warmup_cfg(self, B, max_keys=0, top_k=1):
+        """warmup() for generate_cfg over B items (include/genvc_hip.h: gvc_gpt_warmup_cfg)"""
+        check(lib().gvc_gpt_warmup_cfg(self._h, int(B), int(max_keys), int(top_k)), "warmup_cfg")
+
     def beam_generate(self, slots, beam, n_steps, max_keys=0):
         """n_steps steps of `beam` (a BeamSearch) on the device, continuing at beam.steps (include/genvc_hip.h: gvc_gpt_beam_generate):
         item b was prefilled into slots[b*K]; slots [B*K] int32 is rewritten to the beams' slots"""

@@ -57,6 +57,39 @@ def _vocode(model, latents):
 
 
 @torch.inference_mode()
+def negative_cond_latents(m, guidance_scale, negative_ref_audio, src_wav):
+    """the unconditional prompt's conditioning latents of a guided conversion (GPT.generate(guidance_scale=...,
+    negative_cond_latents=...)), or None when guidance is off.  negative_ref_audio: (wav [1, T], sample rate) of the negative speaker,
+    default the source utterance itself (src_wav at the content sample rate) -- the speaker whose timbre leaks; it goes through
+    get_gpt_cond_latents as the target reference does, resampled to the conditioning sample rate when it comes at another."""
+    from genvc_amd.layers.gpt import _guidance_scale
+    if _guidance_scale({"guidance_scale": guidance_scale}) is None:
+        return None
+    wav, sr = negative_ref_audio if negative_ref_audio is not None else (src_wav, m.content_sample_rate)
+    wav = wav.to(m.device)
+    if wav.ndim == 1:
+        wav = wav[None]
+    target = int(m.config.audio.sample_rate)
+    if int(sr) != target:
+        from genvc_amd.engine import resample
+        wav = resample(wav.to(torch.float32).contiguous(), int(sr), target)
+    return m.get_gpt_cond_latents(wav, target)
+
+
+def _guided_kwargs(m, gkw, guidance_scale, negative_ref_audio, src_wav):
+    """gkw with guidance_scale / negative_cond_latents of a guided conversion merged in (the negative latents computed here, once per
+    utterance, unless the caller's generate_kwargs already carry them); gkw itself when guidance is off"""
+    if guidance_scale is None:
+        guidance_scale = gkw.get("guidance_scale")
+    neg = gkw.get("negative_cond_latents")
+    if neg is None:
+        neg = negative_cond_latents(m, guidance_scale, negative_ref_audio, src_wav)
+    if neg is None:
+        return gkw if guidance_scale is None else dict(gkw, guidance_scale=guidance_scale)
+    return dict(gkw, guidance_scale=guidance_scale, negative_cond_latents=neg)
+
+
+@torch.inference_mode()
 def _segment_latents(m, cond_latent, codes, gen, repass_latents, row=0):
     """the acoustic latents of one segment's n non-stop tokens.  The reference recomputes them with a second, teacher-forced forward pass
     over [cond | codes | start, gen, stop x 4] and trims it with `sub = -5` (inference_utils.py:71-76, gpt.py:375-508, :491, :508); row i of
@@ -74,7 +107,8 @@ def _segment_latents(m, cond_latent, codes, gen, repass_latents, row=0):
 
 @torch.inference_mode()
 def synthesize_utt(genVC_mdl, src_wav, tgt_audio, seg_len=6.0, return_details=False, repass_latents=False, num_beams=1,
-                   generate_kwargs=None, num_return_sequences=None, num_beam_groups=None, diversity_penalty=None):
+                   generate_kwargs=None, num_return_sequences=None, num_beam_groups=None, diversity_penalty=None, guidance_scale=None,
+                   negative_ref_audio=None):
     """non-streaming conversion, latent-level concatenation (reference :23-89).  num_beams = K > 1: every segment decodes with
     deterministic beam search (GPT.generate(num_beams=K, do_sample=False)); its latents come from the re-pass.
     generate_kwargs: more GPT.generate kwargs (the logits processors: min_new_tokens, no_repeat_ngram_size, ...; the
@@ -84,7 +118,10 @@ def synthesize_utt(genVC_mdl, src_wav, tgt_audio, seg_len=6.0, return_details=Fa
     return_details each dict also carries "score", the sum over the segments of the candidate's score (sampling: sequence_logprobs,
     the raw model distribution; beam search: the normalised beam score).
     num_beam_groups = G > 1 with diversity_penalty > 0 (the keywords, or in generate_kwargs; needs num_beams = K, a multiple of G):
-    every segment decodes with group (diverse) beam search, whose N best hypotheses start from different groups."""
+    every segment decodes with group (diverse) beam search, whose N best hypotheses start from different groups.
+    guidance_scale = s != 1 (the keyword, or in generate_kwargs): classifier-free guidance (GPT.generate(guidance_scale=s)): every segment
+    decodes under the target reference and under a negative speaker, negative_ref_audio = (wav, sample rate), default the source
+    utterance itself; its conditioning latents are computed once for the utterance."""
     m = genVC_mdl
     from genvc_amd.layers.gpt import _num_return
     gkw = dict(generate_kwargs or {})
@@ -94,6 +131,7 @@ def synthesize_utt(genVC_mdl, src_wav, tgt_audio, seg_len=6.0, return_details=Fa
         gkw["num_beam_groups"] = num_beam_groups
     if diversity_penalty is not None:
         gkw["diversity_penalty"] = diversity_penalty
+    gkw = _guided_kwargs(m, gkw, guidance_scale, negative_ref_audio, src_wav)
     if _num_return(gkw) > 1:
         return _synthesize_candidates(m, src_wav, tgt_audio, seg_len, return_details, repass_latents, num_beams, gkw)
     min_len = int(0.32 * m.content_sample_rate)
@@ -158,13 +196,16 @@ def _synthesize_candidates(m, src_wav, tgt_audio, seg_len, return_details, repas
 
 
 @torch.inference_mode()
-def synthesize_utt_chunked(genVC_mdl, src_wav, tgt_audio, seg_len=6.0, repass_latents=False, generate_kwargs=None):
+def synthesize_utt_chunked(genVC_mdl, src_wav, tgt_audio, seg_len=6.0, repass_latents=False, generate_kwargs=None, guidance_scale=None,
+                           negative_ref_audio=None):
     """non-streaming conversion with waveform-level concatenation (reference :92-133): every segment goes through
     `genVC_mdl.inference` (trainers/hifigan_trainer.py:457-500) and the segment waveforms are joined by `handle_chunks`
-    (1024 samples dropped from each, cross-fade over the previous tail).  generate_kwargs: as synthesize_utt"""
+    (1024 samples dropped from each, cross-fade over the previous tail).  generate_kwargs, guidance_scale, negative_ref_audio: as
+    synthesize_utt (the negative latents are computed once here and handed to every segment's `inference` call)"""
     m = genVC_mdl
     from genvc_amd.layers.gpt import _single_return
     _single_return(generate_kwargs or {}, "chunked (synthesize_utt_chunked)")      # (it cross-fades ONE waveform per segment)
+    generate_kwargs = _guided_kwargs(m, dict(generate_kwargs or {}), guidance_scale, negative_ref_audio, src_wav)
     wav_gen_prev, wav_overlap = None, None
     pred_audios = []
     min_len = int(0.32 * m.content_sample_rate)

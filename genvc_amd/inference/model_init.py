@@ -93,7 +93,7 @@ class GenVCModel(nn.Module):
 
     @torch.inference_mode()
     def warmup(self, seg_len=1.0, streams=1, ref_seconds=3.0, stream_chunk_size=8, top_k=None, max_new_tokens=None, num_beams=1,
-               contrastive_top_k=None, num_return_sequences=1, num_beam_groups=1):
+               contrastive_top_k=None, num_return_sequences=1, num_beam_groups=1, guidance=False):
         """Everything the FIRST conversion of this shape would otherwise pay inside its latency window (the reference leaves warm-up
         to the user: /root/reference/infer.py:27-30 runs a conversion first).  For `streams` concurrent streams of `seg_len`-second
         segments and a `ref_seconds` reference:
@@ -107,6 +107,8 @@ class GenVCModel(nn.Module):
         (GPT.generate(top_k=K, do_sample=False, penalty_alpha=a)).
         num_return_sequences = N > 1: also the step graphs of the streams * N rows an N-candidate call decodes
         (GPT.generate(do_sample=True, num_return_sequences=N); the KV fan-out and the candidates' score need no warm-up).
+        guidance=True: also the guided step graphs of `streams` items x 2 KV slots (GPT.generate(guidance_scale=s,
+        negative_cond_latents=...)), for a negative prompt as long as the conditional one.
         No token is generated and no KV slot is left occupied."""
         dev = self.device
         g = self.gpt
@@ -136,6 +138,8 @@ class GenVCModel(nn.Module):
             eng.warmup_beam(streams, int(num_beams), hi)
         if contrastive_top_k is not None and int(contrastive_top_k) > 1:
             eng.warmup_contrastive(streams, int(contrastive_top_k), hi)
+        if guidance:
+            eng.warmup_cfg(streams, hi, top_k)
         if self.hifigan is not None:
             lat = torch.zeros(streams, grp, g.model_dim, device=dev)
             for n in {grp, max(1, max_new % grp)}:
@@ -146,7 +150,7 @@ class GenVCModel(nn.Module):
     @torch.no_grad()
     def inference(self, src_audio, cond_latent, do_sample=True, top_p=0.85, top_k=15, temperature=0.75, num_beams=1,
                   length_penalty=1.0, repetition_penalty=10.0, output_attentions=False, repass_latents=False, generate_kwargs=None,
-                  num_return_sequences=None, num_beam_groups=None, diversity_penalty=None):
+                  num_return_sequences=None, num_beam_groups=None, diversity_penalty=None, guidance_scale=None, negative_ref_audio=None):
         """reference trainers/hifigan_trainer.py:457-500: one source segment [1,T] + conditioning latents -> waveform
         [1,1,1024 n]: ContentVec -> content codes -> generate -> strip stop tokens -> latent re-pass -> x4 linear
         interpolation -> HiFi-GAN.  (The reference's 0-d collapse at exactly one non-stop token, SURVEY appendix B.9, is
@@ -158,7 +162,10 @@ class GenVCModel(nn.Module):
         latents (or the re-pass with `repass_latents=True`); `last_sequence_logprobs` / `last_sequence_lengths` hold their scores
         (GPT.sequence_logprobs: the raw model distribution).  N = 1 returns the one waveform, not a list.
         num_beam_groups = G > 1 with diversity_penalty > 0 (and num_beams = K, do_sample=False): group (diverse) beam search; with
-        num_return_sequences = N <= K the N waveforms are its N best hypotheses, `last_beam_scores` their scores."""
+        num_return_sequences = N <= K the N waveforms are its N best hypotheses, `last_beam_scores` their scores.
+        guidance_scale = s != 1 (the keyword, or in generate_kwargs): classifier-free guidance; the negative prompt's conditioning
+        latents are generate_kwargs["negative_cond_latents"] when given (synthesize_utt_chunked computes them once per utterance),
+        else those of negative_ref_audio = (wav, sample rate), default this source segment."""
         feat = self.content_extractor.extract_content_features(src_audio)
         codes = self.content_dvae.get_codebook_indices(feat.transpose(1, 2))
         kw = dict(do_sample=do_sample, top_p=top_p, top_k=top_k, temperature=temperature, num_beams=num_beams,
@@ -170,6 +177,8 @@ class GenVCModel(nn.Module):
             kw["num_beam_groups"] = num_beam_groups
         if diversity_penalty is not None:
             kw["diversity_penalty"] = diversity_penalty
+        from genvc_amd.inference.inference_utils import _guided_kwargs
+        kw = _guided_kwargs(self, kw, guidance_scale, negative_ref_audio, src_audio)
         from genvc_amd.layers.gpt import _num_return
         if _num_return(kw) > 1:
             return self._inference_candidates(cond_latent, codes, kw, repass_latents)

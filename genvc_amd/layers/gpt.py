@@ -30,6 +30,32 @@ def _no_beams(kw, where):
                                   "(the reference streams with num_beams=1 only, inference_utils.py:62,178)")
 
 
+def _guidance_scale(kw):
+    """HF's guidance_scale of the call: None when guidance is off (absent, None or == 1: transformers builds the processor for
+    `guidance_scale is not None and guidance_scale != 1` only, generation/utils.py _get_logits_processor), else the scale as a float.
+    A bool, a non-number or a non-finite value raises ValueError."""
+    s = kw.get("guidance_scale")
+    if s is None:
+        return None
+    if isinstance(s, bool):
+        raise ValueError(f"guidance_scale must be a finite number, not {s!r}")
+    try:
+        v = float(s)
+    except (TypeError, ValueError):
+        raise ValueError(f"guidance_scale must be a finite number, not {s!r}") from None
+    if v != v or v in (float("inf"), float("-inf")):
+        raise ValueError(f"guidance_scale must be a finite number, not {s!r}")
+    return None if v == 1.0 else v
+
+
+def _no_guidance(kw, where):
+    """the paths that decode one KV slot per stream: classifier-free guidance (guidance_scale != 1) raises, naming the path"""
+    s = _guidance_scale(kw)
+    if s is not None:
+        raise NotImplementedError(f"classifier-free guidance (guidance_scale={s}) is not on the {where} path: GPT.generate serves it "
+                                  "(two prefilled KV slots per item, decoded together)")
+
+
 def _num_return(kw):
     """num_return_sequences of the call (absent or None: 1); below 1 raises ValueError"""
     n = kw.get("num_return_sequences")
@@ -390,7 +416,13 @@ class GPT(nn.Module):
         if n > 0:
             # the cache holds n0 positions after the prefill and one more per step: the library picks its decode kernels for the
             # context length this call reaches (not for the 602-token cap the ids rows are sized for)
-            if st["warp"] is not None:
+            if st.get("uncond_slots") is not None:
+                # classifier-free guidance: the unconditional slots decode the same tokens; the longer of the two contexts bounds the keys
+                sets = st["warp"] if st["warp"] is not None else (None if st["proc"] is None else WarperSets.one(st["proc"], None, st["B"]))
+                self.engine.generate_cfg(st["slots"], st["uncond_slots"], st["guidance_scale"], st["ids"], st["ids_len"], st["finished"],
+                                         st["params"], sets, st["done"], n, st["toks"], st["lats"],
+                                         max_keys=max(st["n0"], st["n0_uncond"]) + st["done"] + n)
+            elif st["warp"] is not None:
                 self.engine.generate_warp(st["slots"], st["ids"], st["ids_len"], st["finished"], st["params"], st["warp"], st["done"], n,
                                           st["toks"], st["lats"], max_keys=st["n0"] + st["done"] + n)
             else:
@@ -412,8 +444,13 @@ class GPT(nn.Module):
         (repeat_interleave(N)) orders them -- and draws them: the sampler keys a draw by (seed, step, row).  Item b is prefilled once
         and its KV slot fanned out to its candidates' slots (needs B*N <= the context's KV slots, ValueError otherwise); the B*N rows
         then decode together.  `last_latents` is [B*N, n, d]; `last_sequence_logprobs` / `last_sequence_lengths` hold
-        sequence_logprobs() of the candidates (an extension: a score to rank them by).  Greedy decoding with N > 1 raises ValueError."""
+        sequence_logprobs() of the candidates (an extension: a score to rank them by).  Greedy decoding with N > 1 raises ValueError.
+        guidance_scale = s != 1 with negative_cond_latents: classifier-free guidance on the device (_generate_guided), checked before
+        the other modes; None or 1 is exactly the call without it (negative_* are then ignored, as HF ignores negative_prompt_ids)."""
         _num_return(generate_kwargs)
+        scale = _guidance_scale(generate_kwargs)
+        if scale is not None:
+            return self._generate_guided(cond_latents, text_inputs, scale, generate_kwargs)
         if _contrastive_kwargs(generate_kwargs) is not None:
             return self._generate_contrastive(cond_latents, text_inputs, generate_kwargs)
         if int(generate_kwargs.get("num_beams", 1) or 1) > 1 or _grouped(generate_kwargs):
@@ -441,6 +478,69 @@ class GPT(nn.Module):
         self.last_sequence_logprobs = self.last_sequence_lengths = None
         if N > 1:
             self.last_sequence_logprobs, self.last_sequence_lengths = self.sequence_logprobs(toks[:, :n], self.last_latents)
+        return toks[:, :n]
+
+    def _generate_guided(self, cond_latents, text_inputs, scale, generate_kwargs):
+        """HF generate(guidance_scale=s, negative_prompt_ids=...) semantics on a prefix-embedded model (include/genvc_hip.h:
+        gvc_gpt_generate_cfg; transformers' UnbatchedClassifierFreeGuidanceLogitsProcessor): item b decodes under two prompts, the
+        conditional (cond_latents[b], text_inputs[b]) in KV slot b and the unconditional (negative_cond_latents[b],
+        negative_text_inputs[b], default text_inputs[b]) in slot B + b; a leading dimension of 1 broadcasts, and the negative code
+        length may differ.  Every step samples item b from s * (lsm(cond) - lsm(uncond)) + lsm(uncond) -- the guidance processor comes
+        first in HF's list, so the repetition penalty, the processors, temperature / top-k / top-p and the warpers run on it with the
+        conditional row's ids -- and feeds the token to both slots.  The unconditional prompt always prefills in full.  Needs 2B <= the
+        context's KV slots.  Returns int64 [B, n] as generate(); `last_latents` are the conditional rows' latents.  Beams, beam
+        groups, contrastive search and num_return_sequences > 1 raise NotImplementedError under guidance."""
+        kw = dict(generate_kwargs)
+        if _contrastive_mode(kw) is not None:
+            raise NotImplementedError(f"guidance_scale={scale} with contrastive search (penalty_alpha={kw.get('penalty_alpha')}) is not "
+                                      "implemented")
+        if _grouped(kw):
+            raise NotImplementedError(f"guidance_scale={scale} with beam groups (num_beam_groups={kw.get('num_beam_groups')}, "
+                                      f"diversity_penalty={kw.get('diversity_penalty')}) is not implemented")
+        if int(kw.get("num_beams", 1) or 1) > 1:
+            raise NotImplementedError(f"guidance_scale={scale} with beam search (num_beams={kw.get('num_beams')}) is not implemented")
+        if _num_return(kw) > 1:
+            raise NotImplementedError(f"guidance_scale={scale} with num_return_sequences={kw.get('num_return_sequences')} is not "
+                                      "implemented")
+        neg = kw.pop("negative_cond_latents", None)
+        neg_text = kw.pop("negative_text_inputs", None)
+        if neg is None:
+            raise ValueError(f"guidance_scale={scale} needs negative_cond_latents: HF's default unconditional prompt is the bare last "
+                             "token, which means nothing to a model whose prompt is an embedded prefix")
+        B = int(text_inputs.shape[0])
+        if neg.ndim != 3 or int(neg.shape[0]) not in (1, B) or int(neg.shape[2]) != self.model_dim:
+            raise ValueError(f"negative_cond_latents must be [1 or {B}, n, {self.model_dim}], not {list(neg.shape)}")
+        if neg_text is None:
+            neg_text = text_inputs
+        if neg_text.ndim != 2 or int(neg_text.shape[0]) not in (1, B):
+            raise ValueError(f"negative_text_inputs must be [1 or {B}, n_codes], not {list(neg_text.shape)}")
+        if 2 * B > self.max_slots:
+            raise ValueError(f"classifier-free guidance over {B} items needs {2 * B} KV slots; the context has {self.max_slots} "
+                             "(init_gpt_for_inference(max_slots=...))")
+        self._need_engine()
+        group = kw.pop("group", 16)
+        fake = self.compute_embeddings(cond_latents, text_inputs)
+        dev = fake.device
+        neg = neg.to(device=dev, dtype=torch.float32).expand(B, -1, -1).contiguous()
+        neg_text = neg_text.to(device=dev, dtype=torch.int32).expand(B, -1).contiguous()
+        uprefix = self.engine.prefix_embeddings(neg, neg_text)
+        attempt = []
+
+        def run():
+            st = self._start(fake, dict(kw, cached_cond_rows=0) if attempt else kw)
+            attempt.append(1)
+            st["uncond_slots"] = torch.arange(B, 2 * B, device=dev, dtype=torch.int32)
+            st["guidance_scale"] = scale
+            st["n0_uncond"] = int(uprefix.shape[1]) + 1
+            self.engine.prefill(st["uncond_slots"], uprefix, want_outputs=False)      # (always in full: no cached rows on these slots)
+            while not self._advance(st, group):
+                pass
+            return st
+        st = self._recovering(2 * B, run)
+        toks = st["toks"][:, :st["done"]].long()
+        n = self._stop_len(toks)
+        self.last_latents = st["lats"][:, :n]
+        self.last_sequence_logprobs = self.last_sequence_lengths = None
         return toks[:, :n]
 
     @torch.inference_mode()
@@ -568,6 +668,7 @@ class GPT(nn.Module):
         _no_beams(generate_kwargs, "grouped (generate_groups)")
         _no_contrastive(generate_kwargs, "grouped (generate_groups)")
         _single_return(generate_kwargs, "grouped (generate_groups)")
+        _no_guidance(generate_kwargs, "grouped (generate_groups)")
         kw = dict(generate_kwargs)
         gkw = None
         if group_kwargs is not None:
@@ -718,6 +819,7 @@ class GPT(nn.Module):
         _no_beams(generate_kwargs, "rolling (generate_rolling)")
         _no_contrastive(generate_kwargs, "rolling (generate_rolling)")
         _single_return(generate_kwargs, "rolling (generate_rolling)")
+        _no_guidance(generate_kwargs, "rolling (generate_rolling)")
         kw = dict(generate_kwargs)
         jkw = None
         if job_kwargs is not None:
@@ -867,6 +969,7 @@ class GPT(nn.Module):
         _no_beams(generate_kwargs, "streaming (get_generator)")
         _no_contrastive(generate_kwargs, "streaming (get_generator)")
         _single_return(generate_kwargs, "streaming (get_generator)")
+        _no_guidance(generate_kwargs, "streaming (get_generator)")
         self._need_engine()
         group = generate_kwargs.pop("stream_group", 8)
         B = int(fake_inputs.shape[0])

@@ -499,6 +499,37 @@ int gvc_gpt_generate_warp(gvc_gpt* ctx, const int32_t* slots, int32_t B, int32_t
                           int32_t max_keys, int32_t* tokens_out, int32_t tok_stride, float* latents_out, int32_t lat_stride,
                           gvc_stream s);
 
+/* ------------------------------------------------------------------------------------------
+ * Classifier-free guidance (HF guidance_scale; transformers generation/logits_process.py,
+ * UnbatchedClassifierFreeGuidanceLogitsProcessor.__call__):
+ *     scores = log_softmax(scores, dim=-1)
+ *     unconditional_logits = log_softmax(logits[:, -1], dim=-1)
+ *     scores_processed = guidance_scale * (scores - unconditional_logits) + unconditional_logits
+ * HF puts this processor first in the list (generation/utils.py, _get_logits_processor), so every other processor, the warpers and
+ * the draw see scores_processed in the place of the raw logits.  The model's prompt is an embedded prefix, so the unconditional
+ * pass is a second prefilled KV slot per item (another conditioning, e.g. the source speaker) that is fed the item's tokens.
+ *
+ * gvc_cfg_guide: out[b][v] from logits_cond[b] and logits_uncond[b] ([B][vocab] device rows, vocab <= 2048), fp32, in the operation
+ * order above; the row maximum comes off before exp, so finite inputs of any range give finite outputs.
+ * gvc_gpt_generate_cfg: gvc_gpt_generate_warp over B items (2B <= max_slots, 2B <= 64).  slots[b] is item b's conditional slot,
+ * uncond_slots[b] its unconditional one (device arrays; both prefilled).  One step = [guide; sample over B rows on the guided
+ * scores with ids / processors / keys of the conditional rows; token b to both rows; one decode step over the 2B rows -- the
+ * one-launch rows step for 2..16 rows where it applies, never the one-stream step].  latents_out are the conditional rows'.
+ * The next-step logits and latents of all 2B slots are parked between calls, so a generation split into calls (i0 > 0) continues
+ * exactly; pending deferred tokens of the slots are flushed first.  scale must be finite (scale == 1 computes log_softmax(cond):
+ * callers that want the unguided path call gvc_gpt_generate_warp).  The graphs are captured on first use or by gvc_gpt_warmup_cfg,
+ * after which a call of that shape neither allocates nor synchronises.
+ * ------------------------------------------------------------------------------------------ */
+int gvc_cfg_guide(const float* logits_cond, const float* logits_uncond, int32_t B, int32_t vocab, float scale, float* out, gvc_stream s);
+int gvc_gpt_generate_cfg(gvc_gpt* ctx, const int32_t* slots, const int32_t* uncond_slots, int32_t B, float scale, int32_t* ids,
+                         int32_t ids_stride, int32_t* ids_len, int32_t* finished, const gvc_sample_params* p,
+                         const gvc_row_sampling* rows, const gvc_logits_processors* sets, const gvc_logits_warpers* warps,
+                         int32_t n_sets, const int32_t* set_of_row, int32_t i0, int32_t n_steps, int32_t max_keys, int32_t* tokens_out,
+                         int32_t tok_stride, float* latents_out, int32_t lat_stride, gvc_stream s);
+/* gvc_gpt_warmup for gvc_gpt_generate_cfg over B items with this top_k: the guided step graphs of every context class up to max_keys
+ * cached positions (and everything gvc_gpt_warmup(2B) prepares).  Afterwards such calls neither allocate nor synchronise */
+int gvc_gpt_warmup_cfg(gvc_gpt* ctx, int32_t B, int32_t max_keys, int32_t top_k);
+
 /* Which decode step the last gvc_gpt_generate call replayed (diagnostic): 0 none yet, 1 launch-per-phase with split-key attention,
  * 2 launch-per-phase with the fused short-context attention launch, 3 the one-launch step (one stream), 4 the MFMA rows path
  * (launch per phase: 17+ streams, or shapes the one-launch rows step does not serve), 5 the one-launch rows step (2..16 streams,

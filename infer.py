@@ -51,7 +51,23 @@ if __name__ == "__main__":
     parser.add_argument("--typical_p", type=float, default=None, help="typical sampling mass in (0, 1] (1: off)")
     parser.add_argument("--epsilon_cutoff", type=float, default=None, help="epsilon sampling cut-off in [0, 1) (0: off)")
     parser.add_argument("--eta_cutoff", type=float, default=None, help="eta sampling cut-off in [0, 1) (0: off)")
+    parser.add_argument("--guidance_scale", type=float, default=None,
+                        help="non-streaming only: classifier-free guidance strength (HF guidance_scale; 1 or absent: off): every segment "
+                             "decodes under the reference speaker and under a negative speaker and extrapolates away from the negative")
+    parser.add_argument("--negative_ref_audio", type=str, default=None,
+                        help="with --guidance_scale: the negative speaker's audio (default: the source utterance, whose timbre leaks)")
     args = parser.parse_args()
+    if args.guidance_scale is not None:
+        g = args.guidance_scale
+        if g != g or g in (float("inf"), float("-inf")):
+            raise SystemExit("--guidance_scale must be finite")
+        if g != 1.0 and args.streaming:
+            raise SystemExit("--guidance_scale is not on the streaming path (--streaming): classifier-free guidance decodes two KV slots per "
+                             "segment, which GPT.generate serves")
+        if g != 1.0 and (args.num_beams != 1 or args.penalty_alpha is not None or args.num_return_sequences != 1):
+            raise SystemExit("--guidance_scale does not combine with --num_beams, --penalty_alpha or --num_return_sequences")
+    if args.negative_ref_audio is not None and (args.guidance_scale is None or args.guidance_scale == 1.0):
+        raise SystemExit("--negative_ref_audio needs --guidance_scale (other than 1)")
     if args.num_beams < 1 or (args.streaming and args.num_beams != 1):
         raise SystemExit("--num_beams must be >= 1, and 1 with --streaming")
     if args.num_return_sequences < 1 or (args.num_return_sequences > 1 and (args.streaming or args.penalty_alpha is not None)):
@@ -108,6 +124,16 @@ if __name__ == "__main__":
     ref_audio = load_audio(args.ref_audio, model.config.audio.sample_rate, device=args.device)
     if src_wav is None or ref_audio is None:
         raise SystemExit("could not load the input audio")
+    guide_kw = {}
+    if args.guidance_scale is not None and args.guidance_scale != 1.0:
+        guide_kw["guidance_scale"] = args.guidance_scale
+        if args.negative_ref_audio is not None:
+            neg = load_audio(args.negative_ref_audio, model.config.audio.sample_rate, device=args.device)
+            if neg is None:
+                raise SystemExit("could not load the negative reference audio")
+            guide_kw["negative_ref_audio"] = (neg, model.config.audio.sample_rate)
+        if model.gpt.max_slots < 2:                    # two KV slots per segment
+            model.gpt.init_gpt_for_inference(max_slots=2, weight_dtype=args.weights)
 
     if args.num_return_sequences > 1:
         outs = synthesize_utt(model, src_wav, ref_audio, seg_len=args.seg_len, return_details=True, num_beams=args.num_beams,
@@ -132,7 +158,7 @@ if __name__ == "__main__":
             lat = torch.cat(out["latents"], 1)
         else:
             out = synthesize_utt(model, src_wav, ref_audio, seg_len=args.seg_len, return_details=True, num_beams=args.num_beams,
-                                 generate_kwargs=gen_kw or None)
+                                 generate_kwargs=gen_kw or None, **guide_kw)
             toks = torch.cat(out["codes"]).unsqueeze(0)
             lat = out["latents"]
         print(f"generated {toks.shape[-1]} codec tokens, latents {tuple(lat.shape)}")
