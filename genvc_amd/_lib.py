@@ -143,6 +143,10 @@ _SIGNATURES = {
                                        C.POINTER(RowSampling), C.POINTER(LogitsProcessors), C.POINTER(LogitsWarpers), C.c_int32, c_i32p,
                                        C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_int32, _P]),
     "gvc_gpt_warmup_cfg": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32]),
+    "gvc_gpt_generate_scores": (C.c_int, [_P, _P, _P, C.c_int32, C.c_float, _P, C.c_int32, _P, _P, C.POINTER(SampleParams),
+                                          C.POINTER(RowSampling), C.POINTER(LogitsProcessors), C.POINTER(LogitsWarpers), C.c_int32, c_i32p,
+                                          C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_int32, _P, _P, C.c_int32, C.c_int32, _P]),
+    "gvc_transition_scores": (C.c_int, [_P, C.c_int64, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "gvc_gpt_decode_variant": (C.c_int, [_P]),
     "gvc_gpt_rows_step_launches": (C.c_longlong, [_P]),
     "gvc_gpt_one_stream_steps": (C.c_longlong, [_P]),

@@ -1868,6 +1868,14 @@ extern "C" int gvc_gpt_rearm(gvc_gpt* c) {
     return GVC_OK;
 }
 
+// the per-step score / logit buffers of a gvc_gpt_generate_scores call (SampleCall::scores_out); all null: none
+struct StepOutputs {
+    float* scores = nullptr;
+    float* logits = nullptr;
+    int stride = 0;
+    int do_sample = 1;
+};
+
 // rows: null (gvc_gpt_generate: p's settings for every row) or B host entries (gvc_gpt_generate_rows).  proc: null or the call's
 // processors (gvc_gpt_generate_proc); set_of_row: null or B host indices into the n_sets host sets (gvc_gpt_generate_proc_sets, proc null)
 // and, when warps is set (gvc_gpt_generate_warp), into the n_sets host warpers too; sets is then nullable.  uslots: null, or the B
@@ -1877,10 +1885,12 @@ static int generate_impl(gvc_gpt* c, const int32_t* slots, int32_t B, int32_t* i
                          const gvc_logits_processors* sets, const gvc_logits_warpers* warps, int32_t n_sets, const int32_t* set_of_row,
                          int32_t i0,
                          int32_t n_steps, int32_t max_keys, int32_t* tokens_out, int32_t tok_stride, float* latents_out, int32_t lat_stride,
-                         gvc_stream sv, const int32_t* uslots = nullptr, float scale = 1.f) {
+                         gvc_stream sv, const int32_t* uslots = nullptr, float scale = 1.f, const StepOutputs& so = StepOutputs()) {
     int rc = check_ready(c);
     if (rc) return rc;
     GVC_REQUIRE(B >= 1 && B <= c->dm.max_slots && p && n_steps >= 0 && max_keys >= 0, GVC_ERR_ARG, "generate: bad argument");
+    GVC_REQUIRE((!so.scores && !so.logits) || (i0 >= 0 && i0 + n_steps <= so.stride), GVC_ERR_ARG,
+                "generate_scores: steps [%d, %d) do not fit the %d steps of a row of the output buffers", i0, i0 + n_steps, so.stride);
     GVC_REQUIRE(!uslots || 2 * B <= c->dm.max_slots, GVC_ERR_ARG, "generate_cfg: 2 * %d rows exceed the context's %d KV slots", B,
                 c->dm.max_slots);
     const int Brows = uslots ? 2 * B : B;      // rows of the decode step
@@ -1920,6 +1930,10 @@ static int generate_impl(gvc_gpt* c, const int32_t* slots, int32_t B, int32_t* i
     sc.finished = finished; sc.p = *p; sc.step = 0; sc.step_ptr = c->step_ctr; sc.tok_out = c->tok_buf;
     sc.tokens_out = tokens_out; sc.tok_stride = tok_stride; sc.i0 = i0; sc.latent_src = c->latent;
     sc.latents_out = latents_out; sc.lat_stride = lat_stride; sc.d = c->dm.d_model;
+    // per-step outputs (gvc_gpt_generate_scores): they travel in the call state the step graphs read, so the graphs are the same.  The
+    // sampler of a guided call reads the guided scores as its logits: its raw rows are the conditional rows of the decode step
+    sc.scores_out = so.scores; sc.logits_out = so.logits; sc.out_stride = so.stride; sc.scores_warped = so.do_sample;
+    sc.logits_src = uslots && so.logits ? c->logits : nullptr;
     if (set_of_row) {
         // each set some row uses travels by value into the device-resident call state, ahead of the begin launch, which carries the
         // rows' indices (and row entries): nothing to allocate, no staging buffer, and the caller's arrays are free on return
@@ -2057,6 +2071,31 @@ extern "C" int gvc_gpt_generate_cfg(gvc_gpt* c, const int32_t* slots, const int3
     return generate_impl(c, slots, B, ids, ids_stride, ids_len, finished, p, rows, nullptr, any ? sets : nullptr, any ? warps : nullptr,
                          any ? n_sets : 0, any ? (set_of_row ? set_of_row : zeros) : nullptr, i0, n_steps, max_keys, tokens_out, tok_stride,
                          latents_out, lat_stride, sv, uncond_slots, scale);
+}
+
+// gvc_gpt_generate_warp (uncond_slots null) or gvc_gpt_generate_cfg that also stores, per row and step, the scores the draw was taken
+// from and / or the raw logits ([B][out_stride][vocab] fp32, either nullable).  do_sample: HF's flag, which only decides what the
+// scores hold (SampleCall::scores_warped); the tokens are those of the call without the buffers, bit for bit
+extern "C" int gvc_gpt_generate_scores(gvc_gpt* c, const int32_t* slots, const int32_t* uncond_slots, int32_t B, float scale, int32_t* ids,
+                                       int32_t ids_stride, int32_t* ids_len, int32_t* finished, const gvc_sample_params* p,
+                                       const gvc_row_sampling* rows, const gvc_logits_processors* sets, const gvc_logits_warpers* warps,
+                                       int32_t n_sets, const int32_t* set_of_row, int32_t i0, int32_t n_steps, int32_t max_keys,
+                                       int32_t* tokens_out, int32_t tok_stride, float* latents_out, int32_t lat_stride, float* scores_out,
+                                       float* logits_out, int32_t out_stride, int32_t do_sample, gvc_stream sv) {
+    GVC_REQUIRE(c && slots, GVC_ERR_ARG, "generate_scores: null argument");
+    GVC_REQUIRE(B >= 1 && (uncond_slots ? 2 : 1) * B <= kMaxSampleRows, GVC_ERR_ARG, "generate_scores: need 1..%d rows, got %d",
+                kMaxSampleRows / (uncond_slots ? 2 : 1), B);
+    GVC_REQUIRE(!uncond_slots || (scale == scale && fabsf(scale) <= 3.0e38f), GVC_ERR_ARG, "generate_scores: the guidance scale is not finite");
+    GVC_REQUIRE(!uncond_slots || c->dm.vocab <= kCfgMaxVocab, GVC_ERR_UNSUPPORTED, "generate_scores: vocab %d above %d", c->dm.vocab,
+                kCfgMaxVocab);
+    GVC_REQUIRE((!scores_out && !logits_out) || out_stride >= 1, GVC_ERR_ARG, "generate_scores: output buffers without a stride");
+    int32_t zeros[kMaxSampleRows] = {};
+    const bool any = warps || sets;
+    StepOutputs so;
+    so.scores = scores_out; so.logits = logits_out; so.stride = out_stride; so.do_sample = do_sample != 0;
+    return generate_impl(c, slots, B, ids, ids_stride, ids_len, finished, p, rows, nullptr, any ? sets : nullptr, any ? warps : nullptr,
+                         any ? n_sets : 0, any ? (set_of_row ? set_of_row : zeros) : nullptr, i0, n_steps, max_keys, tokens_out, tok_stride,
+                         latents_out, lat_stride, sv, uncond_slots, scale, so);
 }
 
 // gvc_gpt_warmup for gvc_gpt_generate_cfg over B items: everything gvc_gpt_warmup(2B) prepares, and the guided step graphs of every

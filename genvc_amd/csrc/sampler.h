@@ -44,7 +44,24 @@ struct SampleCall {
     // it behind every sample -- tok_out now holds a token the next decode launch must run -- and advances *step_ptr itself, which the
     // decode step does in the eager order.  One row only
     int32_t* run_flag;
+    // nullable: per-step outputs of a gvc_gpt_generate_scores call, [B][out_stride][vocab] fp32 each, written at i0 + step as tokens_out
+    // is.  scores_out: the row the draw is taken from, as HF's `scores` holds it -- behind the repetition penalty, the processors and
+    // (scores_warped) Temperature and every warper, dropped entries -inf.  logits_out: the raw head output of the step, read from
+    // logits_src when that is set (a guided call: the conditional rows; `logits` then holds the guided scores).  Null: none, and the
+    // kernels compute exactly what they compute without these fields
+    float* scores_out;
+    float* logits_out;
+    const float* logits_src;
+    int out_stride;
+    // HF's do_sample of the call (read only with scores_out): 1 = the scores carry Temperature and the warpers (TopK(1)'s row when
+    // top_k == 1), 0 = greedy search: the full processed row, no temperature
+    int scores_warped;
 };
+
+// row b's entry of a per-step output buffer at this step (see SampleCall::scores_out)
+__device__ __forceinline__ float* step_row(float* out, const SampleCall& C, int b, int step) {
+    return out + ((size_t)b * C.out_stride + C.i0 + step) * (size_t)C.p.vocab;
+}
 
 // the processors of row b (uniform over the row's workgroup)
 __device__ __forceinline__ const gvc_logits_processors* row_procs(const SampleCall& C, int b) {

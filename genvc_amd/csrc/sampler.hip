@@ -209,6 +209,22 @@ __global__ __launch_bounds__(kSampThreads) void k_sample(SampleCall cv, const Sa
         }
         __syncthreads();
         tok = s_tok;
+        if (C.scores_out) {
+            float* so = step_row(C.scores_out, C, b, step);
+            if (C.scores_warped) {
+                // TopK(1): the entries that equal the maximum stay (HF keeps ties), at their temperature-scaled score
+                const float top = sc[tok];
+                for (int i = tid; i < V; i += kSampThreads) so[i] = sc[i] >= top ? sc[i] : -INFINITY;
+            } else {
+                // greedy search has no Temperature: the row as it stood before the division above
+                for (int i = tid; i < V; i += kSampThreads) {
+                    float v = lg[i];
+                    if (seen[i]) v = v < 0.f ? v * rep_pen : v / rep_pen;
+                    if (P) v = proc_score(v, i, C.p.eos_token, ps, kill);
+                    so[i] = v;
+                }
+            }
+        }
     } else {
         // bitonic sort, descending.  Thread t keeps elements t and t + 1024 in registers; a partner at distance j < 64 is a
         // lane of the same wave (shuffle, no barrier), j = 1024 is the thread's own second element, and only the 14 stages
@@ -291,6 +307,17 @@ __global__ __launch_bounds__(kSampThreads) void k_sample(SampleCall cv, const Sa
             const gvc_logits_warpers* W = row_warps(C, b);
             if (W && (W->typical_p > 0.f || W->epsilon_cutoff > 0.f || W->eta_cutoff > 0.f))
                 dmx = apply_warpers(*W, i0v < V ? sc[i0v] : -INFINITY, i1v < V ? sc[i1v] : -INFINITY, k0, k1, mx, wscr);
+            if (C.scores_out) {
+                // what survives the last warper keeps its temperature-scaled score, not renormalised; thread t stores its pair
+                float* so = step_row(C.scores_out, C, b, step);
+                const float o0 = k0 ? sc[i0v] : -INFINITY, o1 = k1 ? sc[i1v] : -INFINITY;
+                if (i1v < V && (reinterpret_cast<uintptr_t>(so) & 7) == 0) {
+                    *reinterpret_cast<float2*>(so + i0v) = make_float2(o0, o1);
+                } else {
+                    if (i0v < V) so[i0v] = o0;
+                    if (i1v < V) so[i1v] = o1;
+                }
+            }
             const double w0 = k0 ? (double)expf(sc[i0v] - dmx) : 0.0, w1 = k1 ? (double)expf(sc[i1v] - dmx) : 0.0;
             double total;
             const double ex = block_scan_excl<double>(w0 + w1, dscr, &total);
@@ -329,6 +356,11 @@ __global__ __launch_bounds__(kSampThreads) void k_sample(SampleCall cv, const Sa
         float* dst = C.latents_out + ((size_t)b * C.lat_stride + C.i0 + step) * C.d;
         for (int k = tid; k < C.d; k += kSampThreads) dst[k] = src[k];
     }
+    if (C.logits_out) {
+        const float* raw = C.logits_src ? C.logits_src + (size_t)b * V : lg;
+        float* lo = step_row(C.logits_out, C, b, step);
+        for (int i = tid; i < V; i += kSampThreads) lo[i] = raw[i];
+    }
 }
 
 // top_k = 1 (the configuration of every BASELINE workload that fixes top_k: TopK(1) leaves one candidate, so top-p and the draw are
@@ -340,6 +372,7 @@ __global__ __launch_bounds__(kGreedyThreads) void k_sample_greedy(SampleCall cv,
     __shared__ float red_v[kGreedyThreads / 64];
     __shared__ int red_i[kGreedyThreads / 64];
     __shared__ int s_tok;
+    __shared__ float s_top;
     __shared__ uint32_t kill[kProcWords];
     unsigned char* seen = reinterpret_cast<unsigned char*>(seen_w);
     const SampleCall& C = cp ? *cp : cv;
@@ -367,6 +400,8 @@ __global__ __launch_bounds__(kGreedyThreads) void k_sample_greedy(SampleCall cv,
     }
     if (P) proc_ngram(ids, len, P->no_repeat_ngram_size, V, kill, tid, kGreedyThreads);
     __syncthreads();
+    // per-step scores of a gvc_gpt_generate_scores call (SampleCall::scores_out): the loop below stores the row of a greedy search
+    float* so = C.scores_out && !C.scores_warped ? step_row(C.scores_out, C, b, step) : nullptr;
     float bv = -INFINITY; int bi = 0x7fffffff;
 #pragma unroll
     for (int u = 0; u < PER; ++u) {
@@ -375,6 +410,7 @@ __global__ __launch_bounds__(kGreedyThreads) void k_sample_greedy(SampleCall cv,
             float x = v[u];
             if (seen[i]) x = x < 0.f ? x * rep_pen : x / rep_pen;
             if (P) x = proc_score(x, i, C.p.eos_token, ps, kill);
+            if (so) so[i] = x;                // greedy search: the processed row, no Temperature
             x = x / temp;
             if (x > bv || (x == bv && i < bi)) { bv = x; bi = i; }
         }
@@ -390,6 +426,7 @@ __global__ __launch_bounds__(kGreedyThreads) void k_sample_greedy(SampleCall cv,
         for (int w = 1; w < kGreedyThreads / 64; ++w)
             if (red_v[w] > bv || (red_v[w] == bv && red_i[w] < bi)) { bv = red_v[w]; bi = red_i[w]; }
         int tok = bi < V ? bi : 0;            // (all scores NaN -- the step before produced garbage: any valid id, never an out-of-range one)
+        s_top = bv;
         // finished rows emit the pad (= eos) token; a row whose ids buffer is full is finished too (see k_sample)
         if (C.finished[b] || len >= C.ids_stride) tok = C.p.eos_token;
         if (len < C.ids_stride) { ids[len] = tok; C.ids_len[b] = len + 1; }
@@ -402,6 +439,32 @@ __global__ __launch_bounds__(kGreedyThreads) void k_sample_greedy(SampleCall cv,
         const float* src = C.latent_src + (size_t)b * C.d;
         float* dst = C.latents_out + ((size_t)b * C.lat_stride + C.i0 + step) * C.d;
         for (int k = tid * 4; k < C.d; k += kGreedyThreads * 4) *reinterpret_cast<float4*>(dst + k) = *reinterpret_cast<const float4*>(src + k);
+    }
+    if (C.scores_out && C.scores_warped) {
+        // sampling with top_k == 1: Temperature, then TopK(1) keeps the entries that equal the maximum (ties stay, as in HF)
+        __syncthreads();
+        const float top = s_top;
+        float* sw = step_row(C.scores_out, C, b, step);
+#pragma unroll
+        for (int u = 0; u < PER; ++u) {
+            const int i = tid + u * kGreedyThreads;
+            if (i < V) {
+                float x = v[u];
+                if (seen[i]) x = x < 0.f ? x * rep_pen : x / rep_pen;
+                if (P) x = proc_score(x, i, C.p.eos_token, ps, kill);
+                x = x / temp;
+                sw[i] = x >= top ? x : -INFINITY;
+            }
+        }
+    }
+    if (C.logits_out) {
+        const float* raw = C.logits_src ? C.logits_src + (size_t)b * V : lg;
+        float* lo = step_row(C.logits_out, C, b, step);
+#pragma unroll
+        for (int u = 0; u < PER; ++u) {
+            const int i = tid + u * kGreedyThreads;
+            if (i < V) lo[i] = C.logits_src ? raw[i] : v[u];
+        }
     }
 }
 __global__ void k_stage_rows(gvc_row_sampling* dst, SampleRows src, int B) {

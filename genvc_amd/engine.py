@@ -826,6 +826,59 @@ class GptEngine:
                                          int(i0), int(n_steps), int(max_keys), ptr(tokens_out), tokens_out.stride(0), ptr(latents_out),
                                          lat_stride, stream()), "generate_cfg")
 
+    def generate_scores(self, slots, uncond_slots, scale, ids, ids_len, finished, params, sets, i0, n_steps, tokens_out, latents_out,
+                        scores_out=None, logits_out=None, do_sample=True, max_keys=0, rows=None):
+        """generate_warp() (uncond_slots None) or generate_cfg() that also stores what every step decoded from (include/genvc_hip.h:
+        gvc_gpt_generate_scores): scores_out / logits_out fp32 [B, >= i0 + n_steps, V], dense, either may be None; step i of the call
+        lands at [:, i0 + i].  do_sample is HF's flag and decides only what the scores hold: with it the warped row (dropped entries
+        -inf), without it the full processed row before any temperature.  sets: a WarperSets over the B rows, or None."""
+        self._join_side()
+        B = slots.shape[0]
+        if uncond_slots is not None and uncond_slots.shape[0] != B:
+            raise ValueError(f"{uncond_slots.shape[0]} unconditional slots for {B} items")
+        if sets is not None and len(sets) != B:
+            raise ValueError(f"{len(sets)} set indices for {B} rows")
+        arr = _rows_arg(rows, B) if rows is not None else None
+        assert tokens_out.is_cuda and tokens_out.dtype == torch.int32 and tokens_out.stride(1) == 1
+        lat_stride = 0
+        if latents_out is not None:
+            assert latents_out.is_cuda and latents_out.dtype == torch.float32 and latents_out.stride(2) == 1
+            assert latents_out.stride(1) == self.d and latents_out.stride(0) % self.d == 0
+            lat_stride = latents_out.stride(0) // self.d
+        out_stride = 0
+        for buf in (scores_out, logits_out):
+            if buf is not None:
+                if tuple(buf.shape[::2]) != (B, self.V) or (out_stride and buf.shape[1] != out_stride):
+                    raise ValueError(f"generate_scores: an output buffer of shape {tuple(buf.shape)} for {B} rows of {self.V} scores")
+                _f32(buf)
+                out_stride = int(buf.shape[1])
+        if rows is not None:
+            params = sample_params(dict(repetition_penalty=1.0, temperature=1.0, top_p=1.0, top_k=0), self.V, self.dims["stop_audio_token"])
+        check(lib().gvc_gpt_generate_scores(self._h, ptr(_i32(slots)), None if uncond_slots is None else ptr(_i32(uncond_slots)), B,
+                                            float(scale), ptr(_i32(ids)), ids.shape[1], ptr(_i32(ids_len)), ptr(_i32(finished)),
+                                            C.byref(params), arr, sets.sets if sets is not None else None,
+                                            sets.warps if sets is not None else None, sets.n_sets if sets is not None else 0,
+                                            sets.set_of_row if sets is not None else None, int(i0), int(n_steps), int(max_keys),
+                                            ptr(tokens_out), tokens_out.stride(0), ptr(latents_out), lat_stride, ptr(scores_out),
+                                            ptr(logits_out), out_stride, int(bool(do_sample)), stream()), "generate_scores")
+
+    def transition_scores(self, scores, tokens, normalize=False):
+        """HF's compute_transition_scores without beams on the device (include/genvc_hip.h: gvc_transition_scores): scores fp32
+        [R, n, V] (its rows dense, the stride between rows free: a column slice of a generate_scores buffer goes in as it is), tokens
+        int32 [R, n] -> fp32 [R, n]: scores[r, t, tokens[r, t]], behind a log_softmax over the vocabulary when normalize"""
+        assert scores.is_cuda and scores.dtype == torch.float32 and scores.ndim == 3
+        R, n, V = scores.shape
+        if tuple(tokens.shape) != (R, n):
+            raise ValueError(f"transition_scores: tokens {tuple(tokens.shape)} do not go with scores {tuple(scores.shape)}")
+        if n == 0 or R == 0:
+            return torch.empty(R, n, device=scores.device, dtype=torch.float32)
+        if scores.stride(2) != 1 or scores.stride(1) != V or (R > 1 and scores.stride(0) < n * V):
+            scores = scores.contiguous()
+        out = torch.empty(R, n, device=scores.device, dtype=torch.float32)
+        check(lib().gvc_transition_scores(ptr(scores), int(scores.stride(0)) if R > 1 else n * V, ptr(_i32(tokens.contiguous())), R, n, V,
+                                          int(bool(normalize)), ptr(out), stream()), "transition_scores")
+        return out
+
     def warmup_cfg(self, B, max_keys=0, top_k=1):
         """warmup() for generate_cfg over B items (include/genvc_hip.h: gvc_gpt_warmup_cfg)"""
         check(lib().gvc_gpt_warmup_cfg(self._h, int(B), int(max_keys), int(top_k)), "warmup_cfg")

@@ -108,7 +108,7 @@ def _segment_latents(m, cond_latent, codes, gen, repass_latents, row=0):
 @torch.inference_mode()
 def synthesize_utt(genVC_mdl, src_wav, tgt_audio, seg_len=6.0, return_details=False, repass_latents=False, num_beams=1,
                    generate_kwargs=None, num_return_sequences=None, num_beam_groups=None, diversity_penalty=None, guidance_scale=None,
-                   negative_ref_audio=None):
+                   negative_ref_audio=None, token_scores=False):
     """non-streaming conversion, latent-level concatenation (reference :23-89).  num_beams = K > 1: every segment decodes with
     deterministic beam search (GPT.generate(num_beams=K, do_sample=False)); its latents come from the re-pass.
     generate_kwargs: more GPT.generate kwargs (the logits processors: min_new_tokens, no_repeat_ngram_size, ...; the
@@ -121,9 +121,15 @@ def synthesize_utt(genVC_mdl, src_wav, tgt_audio, seg_len=6.0, return_details=Fa
     every segment decodes with group (diverse) beam search, whose N best hypotheses start from different groups.
     guidance_scale = s != 1 (the keyword, or in generate_kwargs): classifier-free guidance (GPT.generate(guidance_scale=s)): every segment
     decodes under the target reference and under a negative speaker, negative_ref_audio = (wav, sample rate), default the source
-    utterance itself; its conditioning latents are computed once for the utterance."""
+    utterance itself; its conditioning latents are computed once for the utterance.
+    token_scores=True with return_details: the dict also carries "token_logprobs", one fp32 [n] tensor per segment beside "codes": the
+    log-probability of every token under the distribution it was decoded from (GPT.generate(output_scores=True) and
+    compute_transition_scores(normalize_logits=True): processors, warpers and guidance included).  Not with num_return_sequences > 1;
+    beams and contrastive search raise NotImplementedError (GPT.generate)."""
     m = genVC_mdl
     from genvc_amd.layers.gpt import _num_return
+    if token_scores and not return_details:
+        raise ValueError("token_scores=True needs return_details=True (the scores come back in the details dict)")
     gkw = dict(generate_kwargs or {})
     if num_return_sequences is not None:
         gkw["num_return_sequences"] = num_return_sequences
@@ -132,30 +138,40 @@ def synthesize_utt(genVC_mdl, src_wav, tgt_audio, seg_len=6.0, return_details=Fa
     if diversity_penalty is not None:
         gkw["diversity_penalty"] = diversity_penalty
     gkw = _guided_kwargs(m, gkw, guidance_scale, negative_ref_audio, src_wav)
+    if token_scores and _num_return(gkw) > 1:
+        raise NotImplementedError("token_scores=True with num_return_sequences > 1 is not implemented: the candidates carry "
+                                  "their sequence scores")
+    if token_scores:
+        gkw.update(return_dict_in_generate=True, output_scores=True)
     if _num_return(gkw) > 1:
         return _synthesize_candidates(m, src_wav, tgt_audio, seg_len, return_details, repass_latents, num_beams, gkw)
     min_len = int(0.32 * m.content_sample_rate)
     src_wav = src_wav.to(m.device)
     seg = int(seg_len * m.content_sample_rate)
     cond_latent = m.get_gpt_cond_latents(tgt_audio.to(m.device), m.config.audio.sample_rate)
-    final_latents, all_codes = [], []
+    final_latents, all_codes, all_logprobs = [], [], []
+    more = {"token_logprobs": all_logprobs} if token_scores else {}
     for src_seg in segments(src_wav, seg, min_len):
         feat = m.content_extractor.extract_content_features(src_seg)
         codes = m.content_dvae.get_codebook_indices(feat.transpose(1, 2))
         kw = _sampling_kwargs(m) if num_beams == 1 else dict(_sampling_kwargs(m), do_sample=False, num_beams=int(num_beams))
-        gen = m.gpt.generate(cond_latent, codes, output_attentions=False, **dict(kw, **gkw))[0]
-        gen = gen[gen != m.gpt.stop_audio_token]                        # reference :68 (0-d collapse guarded)
+        res = m.gpt.generate(cond_latent, codes, output_attentions=False, **dict(kw, **gkw))
+        gen = getattr(res, "sequences", res)[0]          # (a caller's own return_dict_in_generate in generate_kwargs: the tokens of the result)
+        keep = gen != m.gpt.stop_audio_token
+        gen = gen[keep]                                                 # reference :68 (0-d collapse guarded)
         if gen.numel() == 0:
             continue
         final_latents.append(_segment_latents(m, cond_latent, codes, gen, repass_latents))
         all_codes.append(gen)
+        if token_scores:
+            all_logprobs.append(m.gpt.compute_transition_scores(res.sequences, res.scores, normalize_logits=True)[0][keep])
     if not final_latents:                    # every segment ended on its first token: nothing to vocode
         empty = torch.zeros(0, device=m.device)
-        return dict(latents=None, codes=[], wav=empty) if return_details else empty
+        return dict(latents=None, codes=[], wav=empty, **more) if return_details else empty
     latents = torch.cat(final_latents, dim=1)
     wav = _vocode(m, latents)
     if return_details or wav is None:
-        return dict(latents=latents, codes=all_codes, wav=None if wav is None else wav[0].squeeze())
+        return dict(latents=latents, codes=all_codes, wav=None if wav is None else wav[0].squeeze(), **more)
     return wav[0].squeeze()
 
 
@@ -172,6 +188,7 @@ def _synthesize_candidates(m, src_wav, tgt_audio, seg_len, return_details, repas
         feat = m.content_extractor.extract_content_features(src_seg)
         codes = m.content_dvae.get_codebook_indices(feat.transpose(1, 2))
         rows = m.gpt.generate(cond_latent, codes, output_attentions=False, **dict(kw, **gkw))
+        rows = getattr(rows, "sequences", rows)
         sc = m.gpt.last_sequence_logprobs if m.gpt.last_latents is not None else m.gpt.last_beam_scores
         for j in range(N):
             score[j] += float(sc[j])

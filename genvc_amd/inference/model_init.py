@@ -182,7 +182,8 @@ class GenVCModel(nn.Module):
         from genvc_amd.layers.gpt import _num_return
         if _num_return(kw) > 1:
             return self._inference_candidates(cond_latent, codes, kw, repass_latents)
-        gen = self.gpt.generate(cond_latent, codes, **kw)[0]
+        gen = self.gpt.generate(cond_latent, codes, **kw)
+        gen = getattr(gen, "sequences", gen)[0]
         gen = gen[gen != self.gpt.stop_audio_token]
         if gen.numel() == 0:
             return torch.zeros(1, 1, 0, device=self.device)

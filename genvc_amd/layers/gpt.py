@@ -188,6 +188,51 @@ def _no_contrastive(kw, where):
                                   "harness always samples, inference_utils.py:178)")
 
 
+OUTPUT_KWARGS = ("return_dict_in_generate", "output_scores", "output_logits")
+
+
+class GenerateOutput(dict):
+    """what GPT.generate(return_dict_in_generate=True) returns, read as attributes or by key (HF's ModelOutput habit):
+    sequences  int64 [rows, n]: what the call returns without the kwarg
+    scores     output_scores=True: a tuple of n fp32 [rows, V] views into one device tensor, scores[t] the row step t decoded from as
+               transformers' logits processors (and, when sampling, warpers) leave it; else None
+    logits     output_logits=True: likewise the raw head output of every step (under guidance the conditional row); else None
+    latents    `last_latents` of the call
+    sequences_scores  beam search: `last_beam_scores`; else None"""
+
+    def __getattr__(self, name):
+        try:
+            return self[name]
+        except KeyError:
+            raise AttributeError(name) from None
+
+
+def _output_kwargs(kw):
+    """(return_dict_in_generate, output_scores, output_logits) of the call as HF reads them: without return_dict_in_generate the
+    call returns the bare tensor and the other two are ignored"""
+    rd = bool(kw.get("return_dict_in_generate"))
+    return rd, rd and bool(kw.get("output_scores")), rd and bool(kw.get("output_logits"))
+
+
+def _no_outputs(kw, where):
+    """the paths that return bare tokens: return_dict_in_generate / output_scores / output_logits raise, naming the path"""
+    for k in OUTPUT_KWARGS:
+        if kw.get(k):
+            raise NotImplementedError(f"{k}={kw.get(k)!r} is not on the {where} path: GPT.generate serves it (one result object per "
+                                      "call, per-step scores of the sampler paths)")
+
+
+def _no_step_outputs(kw, mode):
+    """the modes of GPT.generate without per-step scores: output_scores / output_logits raise, naming the mode (return_dict_in_generate
+    alone is served)"""
+    _, sc, lg = _output_kwargs(kw)
+    if sc or lg:
+        which = "output_scores" if sc else "output_logits"
+        raise NotImplementedError(f"{which}=True with {mode} is not implemented: HF's scores of that mode are not the sampler's rows "
+                                  "(beam scores add the running beam score and need beam_indices); return_dict_in_generate=True alone is "
+                                  "served")
+
+
 def _any_proc(kw):
     """a processor kwarg is given (engine.logits_processors may still find every one at its default)"""
     return any(kw.get(k) is not None for k in PROC_KWARGS)
@@ -416,7 +461,14 @@ class GPT(nn.Module):
         if n > 0:
             # the cache holds n0 positions after the prefill and one more per step: the library picks its decode kernels for the
             # context length this call reaches (not for the 602-token cap the ids rows are sized for)
-            if st.get("uncond_slots") is not None:
+            if st.get("scores") is not None or st.get("raw_logits") is not None:
+                # output_scores / output_logits: the same steps, the call state also naming the buffers the sampler stores its rows in
+                sets = st["warp"] if st["warp"] is not None else (None if st["proc"] is None else WarperSets.one(st["proc"], None, st["B"]))
+                self.engine.generate_scores(st["slots"], st.get("uncond_slots"), st.get("guidance_scale", 1.0), st["ids"], st["ids_len"],
+                                            st["finished"], st["params"], sets, st["done"], n, st["toks"], st["lats"],
+                                            scores_out=st.get("scores"), logits_out=st.get("raw_logits"), do_sample=st["do_sample"],
+                                            max_keys=max(st["n0"], st.get("n0_uncond", 0)) + st["done"] + n)
+            elif st.get("uncond_slots") is not None:
                 # classifier-free guidance: the unconditional slots decode the same tokens; the longer of the two contexts bounds the keys
                 sets = st["warp"] if st["warp"] is not None else (None if st["proc"] is None else WarperSets.one(st["proc"], None, st["B"]))
                 self.engine.generate_cfg(st["slots"], st["uncond_slots"], st["guidance_scale"], st["ids"], st["ids_len"], st["finished"],
@@ -433,6 +485,49 @@ class GPT(nn.Module):
         self.engine.health()          # (the .item() above synchronised: a hand-off timeout of these steps surfaces here, not a call later)
         return end
 
+    def _step_outputs(self, st, kw):
+        """the per-step buffers of a call with output_scores / output_logits, allocated only when asked for ([rows, max_new, V] fp32
+        each) and filled by _advance"""
+        _, want_scores, want_logits = _output_kwargs(kw)
+        shape = (st["B"], st["max_new"], self.num_audio_tokens)
+        dev = st["ids"].device
+        st["scores"] = torch.empty(shape, device=dev, dtype=torch.float32) if want_scores else None
+        st["raw_logits"] = torch.empty(shape, device=dev, dtype=torch.float32) if want_logits else None
+        st["do_sample"] = bool(kw.get("do_sample", True))
+
+    def _result(self, ids, kw, st=None, n=0, beams=False):
+        """what generate() returns: the tokens, or with return_dict_in_generate=True a GenerateOutput around them"""
+        if not _output_kwargs(kw)[0]:
+            return ids
+
+        def steps(buf):
+            return None if buf is None else tuple(buf[:, t] for t in range(n))
+        return GenerateOutput(sequences=ids, scores=steps(st.get("scores")) if st else None,
+                              logits=steps(st.get("raw_logits")) if st else None, latents=self.last_latents,
+                              sequences_scores=self.last_beam_scores if beams else None)
+
+    @torch.inference_mode()
+    def compute_transition_scores(self, sequences, scores, normalize_logits=False):
+        """transformers' GenerationMixin.compute_transition_scores without beams, on the device (include/genvc_hip.h:
+        gvc_transition_scores): sequences int64 [rows, n] and scores (a GenerateOutput's `scores` or `logits`: n rows of [rows, V]) ->
+        fp32 [rows, n], the score of every generated token, behind a log_softmax over the vocabulary with normalize_logits=True.
+        Longer sequences are read from their last n columns, as HF cuts the prompt away."""
+        self._need_engine()
+        scores = tuple(scores)
+        n = len(scores)
+        V = self.num_audio_tokens
+        if n == 0:
+            return torch.empty(int(sequences.shape[0]), 0, device=sequences.device, dtype=torch.float32)
+        s0 = scores[0]
+        # the views generate() hands out share one [rows, max_new, V] tensor: read in place
+        if all(s.shape == s0.shape and s.stride() == s0.stride() and s.data_ptr() == s0.data_ptr() + 4 * V * t
+               for t, s in enumerate(scores)) and s0.ndim == 2 and s0.stride(1) == 1 and (s0.shape[0] == 1 or s0.stride(0) >= n * V):
+            stacked = torch.as_strided(s0, (s0.shape[0], n, V), (s0.stride(0) if s0.shape[0] > 1 else n * V, V, 1))
+        else:
+            stacked = torch.stack([s.to(torch.float32) for s in scores], 1).contiguous()
+        toks = sequences[:, -n:].to(device=stacked.device, dtype=torch.int32).contiguous()
+        return self.engine.transition_scores(stacked, toks, normalize=normalize_logits)
+
     @torch.inference_mode()
     def generate(self, cond_latents, text_inputs, **generate_kwargs):
         """reference gpt.py:594-609 -> int64 [B, n_generated]; finished rows are padded with the stop token.
@@ -446,15 +541,23 @@ class GPT(nn.Module):
         then decode together.  `last_latents` is [B*N, n, d]; `last_sequence_logprobs` / `last_sequence_lengths` hold
         sequence_logprobs() of the candidates (an extension: a score to rank them by).  Greedy decoding with N > 1 raises ValueError.
         guidance_scale = s != 1 with negative_cond_latents: classifier-free guidance on the device (_generate_guided), checked before
-        the other modes; None or 1 is exactly the call without it (negative_* are then ignored, as HF ignores negative_prompt_ids)."""
+        the other modes; None or 1 is exactly the call without it (negative_* are then ignored, as HF ignores negative_prompt_ids).
+        return_dict_in_generate=True: a GenerateOutput (sequences = the tensor above, latents, sequences_scores for beams) instead
+        of the tensor; with it output_scores=True / output_logits=True add `scores` / `logits`, tuples of n fp32 [rows, V] rows, as
+        transformers' _sample fills them -- on the sampler paths (greedy, sampling, every processor and warper,
+        num_return_sequences, guidance_scale); with beams, beam groups or contrastive search they raise NotImplementedError.  The
+        tokens are those of the call without the kwargs, bit for bit.  Without return_dict_in_generate the other two are ignored."""
         _num_return(generate_kwargs)
         scale = _guidance_scale(generate_kwargs)
         if scale is not None:
             return self._generate_guided(cond_latents, text_inputs, scale, generate_kwargs)
         if _contrastive_kwargs(generate_kwargs) is not None:
-            return self._generate_contrastive(cond_latents, text_inputs, generate_kwargs)
+            _no_step_outputs(generate_kwargs, f"contrastive search (penalty_alpha={generate_kwargs.get('penalty_alpha')})")
+            return self._result(self._generate_contrastive(cond_latents, text_inputs, generate_kwargs), generate_kwargs)
         if int(generate_kwargs.get("num_beams", 1) or 1) > 1 or _grouped(generate_kwargs):
-            return self._generate_beams(cond_latents, text_inputs, generate_kwargs)
+            _no_step_outputs(generate_kwargs, "beam groups (num_beam_groups / diversity_penalty)" if _grouped(generate_kwargs)
+                             else f"beam search (num_beams={generate_kwargs.get('num_beams')})")
+            return self._result(self._generate_beams(cond_latents, text_inputs, generate_kwargs), generate_kwargs, beams=True)
         N = _sample_return_kwargs(generate_kwargs, int(text_inputs.shape[0]), self.max_slots)
         fake = self.compute_embeddings(cond_latents, text_inputs)
         if N > 1:
@@ -467,6 +570,7 @@ class GPT(nn.Module):
             # (a retry after a hand-off time-out prefills in full: the reset slots have lost any cached conditioning rows)
             st = self._start(fake, dict(generate_kwargs, cached_cond_rows=0) if attempt else generate_kwargs, fan=N)
             attempt.append(1)
+            self._step_outputs(st, generate_kwargs)
             while not self._advance(st, group):
                 pass
             return st
@@ -478,7 +582,7 @@ class GPT(nn.Module):
         self.last_sequence_logprobs = self.last_sequence_lengths = None
         if N > 1:
             self.last_sequence_logprobs, self.last_sequence_lengths = self.sequence_logprobs(toks[:, :n], self.last_latents)
-        return toks[:, :n]
+        return self._result(toks[:, :n], generate_kwargs, st, n)
 
     def _generate_guided(self, cond_latents, text_inputs, scale, generate_kwargs):
         """HF generate(guidance_scale=s, negative_prompt_ids=...) semantics on a prefix-embedded model (include/genvc_hip.h:
@@ -533,6 +637,7 @@ class GPT(nn.Module):
             st["guidance_scale"] = scale
             st["n0_uncond"] = int(uprefix.shape[1]) + 1
             self.engine.prefill(st["uncond_slots"], uprefix, want_outputs=False)      # (always in full: no cached rows on these slots)
+            self._step_outputs(st, kw)
             while not self._advance(st, group):
                 pass
             return st
@@ -541,7 +646,7 @@ class GPT(nn.Module):
         n = self._stop_len(toks)
         self.last_latents = st["lats"][:, :n]
         self.last_sequence_logprobs = self.last_sequence_lengths = None
-        return toks[:, :n]
+        return self._result(toks[:, :n], kw, st, n)
 
     @torch.inference_mode()
     def sequence_logprobs(self, tokens, latents):
@@ -669,6 +774,7 @@ class GPT(nn.Module):
         _no_contrastive(generate_kwargs, "grouped (generate_groups)")
         _single_return(generate_kwargs, "grouped (generate_groups)")
         _no_guidance(generate_kwargs, "grouped (generate_groups)")
+        _no_outputs(generate_kwargs, "grouped (generate_groups)")
         kw = dict(generate_kwargs)
         gkw = None
         if group_kwargs is not None:
@@ -820,6 +926,7 @@ class GPT(nn.Module):
         _no_contrastive(generate_kwargs, "rolling (generate_rolling)")
         _single_return(generate_kwargs, "rolling (generate_rolling)")
         _no_guidance(generate_kwargs, "rolling (generate_rolling)")
+        _no_outputs(generate_kwargs, "rolling (generate_rolling)")
         kw = dict(generate_kwargs)
         jkw = None
         if job_kwargs is not None:
@@ -970,6 +1077,7 @@ class GPT(nn.Module):
         _no_contrastive(generate_kwargs, "streaming (get_generator)")
         _single_return(generate_kwargs, "streaming (get_generator)")
         _no_guidance(generate_kwargs, "streaming (get_generator)")
+        _no_outputs(generate_kwargs, "streaming (get_generator)")
         self._need_engine()
         group = generate_kwargs.pop("stream_group", 8)
         B = int(fake_inputs.shape[0])

@@ -526,6 +526,34 @@ int gvc_gpt_generate_cfg(gvc_gpt* ctx, const int32_t* slots, const int32_t* unco
                          const gvc_row_sampling* rows, const gvc_logits_processors* sets, const gvc_logits_warpers* warps,
                          int32_t n_sets, const int32_t* set_of_row, int32_t i0, int32_t n_steps, int32_t max_keys, int32_t* tokens_out,
                          int32_t tok_stride, float* latents_out, int32_t lat_stride, gvc_stream s);
+/* ------------------------------------------------------------------------------------------
+ * Per-step scores and logits (HF return_dict_in_generate with output_scores / output_logits; transformers
+ * generation/utils.py, GenerationMixin._sample and compute_transition_scores).
+ *
+ * gvc_gpt_generate_scores: gvc_gpt_generate_warp (uncond_slots null; scale is then ignored) or gvc_gpt_generate_cfg (uncond_slots set)
+ * that also stores what each step decoded from.  scores_out / logits_out: device buffers [B][out_stride][vocab] fp32, either may be
+ * null; step i of the call lands at [b][i0 + i], as in tokens_out, and i0 + n_steps <= out_stride.
+ *   scores_out  the row logits_processor(input_ids, logits) returns in HF: behind the guidance, the repetition penalty and the
+ *               processors.  do_sample != 0: also behind Temperature and every warper (TopK, TopP, MinP, Typical, Epsilon, Eta), dropped
+ *               entries -inf, kept ones at their temperature-scaled score, not renormalised; top_k == 1 gives TopK's row at k = 1
+ *               (ties with the maximum kept).  do_sample == 0 (greedy search, top_k == 1): the full processed row, no temperature.
+ *   logits_out  the raw head output of the step; under guidance the conditional row.
+ * Rows that have stopped keep decoding the stop token and keep storing rows.  do_sample decides nothing else: the tokens, ids and
+ * latents are those of the call without the buffers, bit for bit, and the same captured step graphs serve both.
+ *
+ * gvc_transition_scores: out[r][t] = scores[r][t][tokens[r][t]] (normalize 0) or log_softmax(scores[r][t])[tokens[r][t]] (normalize 1:
+ * the maximum comes off before exp, -inf entries add nothing, the sum runs in a fixed order).  scores: row r starts row_stride floats
+ * after row r - 1 and holds n dense [V] rows (row_stride >= n * V: a scores_out buffer's out_stride * vocab); tokens int32 [R][n] and
+ * out fp32 [R][n] are dense.  A token outside [0, V) gives NaN.
+ * ------------------------------------------------------------------------------------------ */
+int gvc_gpt_generate_scores(gvc_gpt* ctx, const int32_t* slots, const int32_t* uncond_slots, int32_t B, float scale, int32_t* ids,
+                            int32_t ids_stride, int32_t* ids_len, int32_t* finished, const gvc_sample_params* p,
+                            const gvc_row_sampling* rows, const gvc_logits_processors* sets, const gvc_logits_warpers* warps,
+                            int32_t n_sets, const int32_t* set_of_row, int32_t i0, int32_t n_steps, int32_t max_keys, int32_t* tokens_out,
+                            int32_t tok_stride, float* latents_out, int32_t lat_stride, float* scores_out, float* logits_out,
+                            int32_t out_stride, int32_t do_sample, gvc_stream s);
+int gvc_transition_scores(const float* scores, int64_t row_stride, const int32_t* tokens, int32_t R, int32_t n, int32_t V,
+                          int32_t normalize, float* out, gvc_stream s);
 /* gvc_gpt_warmup for gvc_gpt_generate_cfg over B items with this top_k: the guided step graphs of every context class up to max_keys
  * cached positions (and everything gvc_gpt_warmup(2B) prepares).  Afterwards such calls neither allocate nor synchronise */
 int gvc_gpt_warmup_cfg(gvc_gpt* ctx, int32_t B, int32_t max_keys, int32_t top_k);

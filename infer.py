@@ -2,7 +2,7 @@
 
 Flags and defaults are the reference's; added: --seg_len (the reference hard-codes 6.0; the README's
 "1-second chunk" numbers correspond to --seg_len 1.0), --stream_chunk_size, --synthetic (no checkpoint
-ships with the reference: run the same pipeline on deterministic synthetic weights) and --save_tokens.
+ships with the reference: run the same pipeline on deterministic synthetic weights), --save_tokens and --token_scores.
 The waveform is written like the reference does (24 kHz PCM16); --save_tokens also stores the codec tokens/latents.
 """
 import argparse
@@ -56,7 +56,15 @@ if __name__ == "__main__":
                              "decodes under the reference speaker and under a negative speaker and extrapolates away from the negative")
     parser.add_argument("--negative_ref_audio", type=str, default=None,
                         help="with --guidance_scale: the negative speaker's audio (default: the source utterance, whose timbre leaks)")
+    parser.add_argument("--token_scores", type=str, default=None, metavar="PATH.npz",
+                        help="non-streaming only: write, per segment, the codec tokens and the log-probability of each under the "
+                             "distribution it was decoded from (processors, warpers and guidance included)")
     args = parser.parse_args()
+    if args.token_scores is not None:
+        if args.streaming:
+            raise SystemExit("--token_scores is not on the streaming path (--streaming): GPT.generate serves the per-step scores")
+        if args.num_beams != 1 or args.penalty_alpha is not None or args.num_return_sequences != 1:
+            raise SystemExit("--token_scores does not combine with --num_beams, --penalty_alpha or --num_return_sequences")
     if args.guidance_scale is not None:
         g = args.guidance_scale
         if g != g or g in (float("inf"), float("-inf")):
@@ -158,9 +166,15 @@ if __name__ == "__main__":
             lat = torch.cat(out["latents"], 1)
         else:
             out = synthesize_utt(model, src_wav, ref_audio, seg_len=args.seg_len, return_details=True, num_beams=args.num_beams,
-                                 generate_kwargs=gen_kw or None, **guide_kw)
+                                 generate_kwargs=gen_kw or None, token_scores=args.token_scores is not None, **guide_kw)
             toks = torch.cat(out["codes"]).unsqueeze(0)
             lat = out["latents"]
+            if args.token_scores is not None:
+                import numpy as np
+                np.savez(args.token_scores, n_segments=len(out["codes"]),
+                         **{f"tokens_{i}": c.cpu().numpy() for i, c in enumerate(out["codes"])},
+                         **{f"logprobs_{i}": lp.cpu().numpy() for i, lp in enumerate(out["token_logprobs"])})
+                print(f"{args.token_scores}: tokens and log-probabilities of {len(out['codes'])} segments")
         print(f"generated {toks.shape[-1]} codec tokens, latents {tuple(lat.shape)}")
         if out["wav"] is not None:
             save_wav(args.output_path, out["wav"], config.audio.sample_rate)
