@@ -61,6 +61,18 @@ class LogitsWarpers(C.Structure):
     _fields_ = [("typical_p", C.c_float), ("epsilon_cutoff", C.c_float), ("eta_cutoff", C.c_float), ("reserved", C.c_int32)]
 
 
+BIAS_MAX_SEQS = 32     # GVC_BIAS_MAX_SEQS
+BIAS_MAX_LEN = 8       # GVC_BIAS_MAX_LEN
+
+
+class LogitsBias(C.Structure):
+    """gvc_logits_bias (include/genvc_hip.h): one call's sequence bias, bad words, forced EOS and renormalize flag (1312 bytes); all
+    zero = off"""
+    _fields_ = [(n, C.c_int32) for n in ("n_bias", "n_ban", "force_eos_at", "renormalize", "prompt_len")] + \
+        [("reserved", C.c_int32 * 3), ("len", C.c_int32 * BIAS_MAX_SEQS), ("bias", C.c_float * BIAS_MAX_SEQS),
+         ("ids", (C.c_int32 * BIAS_MAX_LEN) * BIAS_MAX_SEQS)]
+
+
 class PerceiverDims(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("dim", "depth", "dim_context", "num_latents", "dim_head", "heads",
                                          "ff_mult", "max_batch", "max_frames")]
@@ -146,6 +158,13 @@ _SIGNATURES = {
     "gvc_gpt_generate_scores": (C.c_int, [_P, _P, _P, C.c_int32, C.c_float, _P, C.c_int32, _P, _P, C.POINTER(SampleParams),
                                           C.POINTER(RowSampling), C.POINTER(LogitsProcessors), C.POINTER(LogitsWarpers), C.c_int32, c_i32p,
                                           C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_int32, _P, _P, C.c_int32, C.c_int32, _P]),
+    "gvc_sample_bias": (C.c_int, [_P, C.c_int32, _P, C.c_int32, _P, _P, C.POINTER(SampleParams), C.POINTER(RowSampling),
+                                  C.POINTER(LogitsProcessors), C.POINTER(LogitsWarpers), C.c_int32, c_i32p, C.POINTER(LogitsBias), C.c_int32,
+                                  _P, _P]),
+    "gvc_gpt_generate_bias": (C.c_int, [_P, _P, _P, C.c_int32, C.c_float, _P, C.c_int32, _P, _P, C.POINTER(SampleParams),
+                                        C.POINTER(RowSampling), C.POINTER(LogitsProcessors), C.POINTER(LogitsWarpers), C.c_int32, c_i32p,
+                                        C.POINTER(LogitsBias), C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_int32, _P, _P,
+                                        C.c_int32, C.c_int32, _P]),
     "gvc_transition_scores": (C.c_int, [_P, C.c_int64, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "gvc_gpt_decode_variant": (C.c_int, [_P]),
     "gvc_gpt_rows_step_launches": (C.c_longlong, [_P]),

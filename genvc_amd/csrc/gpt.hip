@@ -189,6 +189,7 @@ struct GenCall {
     int32_t set_of_row[kMaxSampleRows];      // ... and each row's index into them, -1: none (sc.set_of_row points here)
     gvc_logits_warpers warps[kMaxSampleRows];     // warpers of a gvc_gpt_generate_warp call, one per set (sc.warps points here)
     float cfg_scale;                         // guidance scale of a gvc_gpt_generate_cfg call (k_cfg_guide reads it here)
+    gvc_logits_bias bias;                    // sequence bias / bad words / forced EOS of a gvc_gpt_generate_bias call (sc.bias points here)
 };
 
 // Start / end of a gvc_gpt_generate call in ONE launch each (they used to be a memset, k_set_gen_call and two k_stage_rows before the
@@ -1885,7 +1886,8 @@ static int generate_impl(gvc_gpt* c, const int32_t* slots, int32_t B, int32_t* i
                          const gvc_logits_processors* sets, const gvc_logits_warpers* warps, int32_t n_sets, const int32_t* set_of_row,
                          int32_t i0,
                          int32_t n_steps, int32_t max_keys, int32_t* tokens_out, int32_t tok_stride, float* latents_out, int32_t lat_stride,
-                         gvc_stream sv, const int32_t* uslots = nullptr, float scale = 1.f, const StepOutputs& so = StepOutputs()) {
+                         gvc_stream sv, const int32_t* uslots = nullptr, float scale = 1.f, const StepOutputs& so = StepOutputs(),
+                         const gvc_logits_bias* bias = nullptr) {
     int rc = check_ready(c);
     if (rc) return rc;
     GVC_REQUIRE(B >= 1 && B <= c->dm.max_slots && p && n_steps >= 0 && max_keys >= 0, GVC_ERR_ARG, "generate: bad argument");
@@ -1897,6 +1899,7 @@ static int generate_impl(gvc_gpt* c, const int32_t* slots, int32_t B, int32_t* i
     bool rows_greedy = false;
     if (rows && (rc = check_sample_rows(rows, B, c->dm.vocab, &rows_greedy))) return rc;
     if (proc && (rc = check_procs(*proc, c->dm.vocab))) return rc;
+    if (bias && (rc = check_bias(*bias, c->dm.vocab))) return rc;
     if (warps) {
         if ((rc = check_warp_sets(sets, warps, n_sets, set_of_row, B, c->dm.vocab))) return rc;
     } else if (set_of_row && (rc = check_proc_sets(sets, n_sets, set_of_row, B, c->dm.vocab))) {
@@ -1934,6 +1937,12 @@ static int generate_impl(gvc_gpt* c, const int32_t* slots, int32_t B, int32_t* i
     // sampler of a guided call reads the guided scores as its logits: its raw rows are the conditional rows of the decode step
     sc.scores_out = so.scores; sc.logits_out = so.logits; sc.out_stride = so.stride; sc.scores_warped = so.do_sample;
     sc.logits_src = uslots && so.logits ? c->logits : nullptr;
+    if (bias) {
+        // gvc_gpt_generate_bias: the struct travels by value into the device-resident call state in a launch of its own, ahead of the
+        // begin launch (as the warpers do): nothing to allocate, and the caller's struct is free on return
+        if ((rc = launch_stage_bias(&c->gen_call->bias, bias, s))) return rc;
+        sc.bias = &c->gen_call->bias;
+    }
     if (set_of_row) {
         // each set some row uses travels by value into the device-resident call state, ahead of the begin launch, which carries the
         // rows' indices (and row entries): nothing to allocate, no staging buffer, and the caller's arrays are free on return
@@ -2096,6 +2105,34 @@ extern "C" int gvc_gpt_generate_scores(gvc_gpt* c, const int32_t* slots, const i
     return generate_impl(c, slots, B, ids, ids_stride, ids_len, finished, p, rows, nullptr, any ? sets : nullptr, any ? warps : nullptr,
                          any ? n_sets : 0, any ? (set_of_row ? set_of_row : zeros) : nullptr, i0, n_steps, max_keys, tokens_out, tok_stride,
                          latents_out, lat_stride, sv, uncond_slots, scale, so);
+}
+
+// gvc_gpt_generate_scores with the call's sequence bias / bad words / forced EOS / renormalised scores (include/genvc_hip.h:
+// gvc_logits_bias, HOST, nullable: null is exactly gvc_gpt_generate_scores)
+extern "C" int gvc_gpt_generate_bias(gvc_gpt* c, const int32_t* slots, const int32_t* uncond_slots, int32_t B, float scale, int32_t* ids,
+                                     int32_t ids_stride, int32_t* ids_len, int32_t* finished, const gvc_sample_params* p,
+                                     const gvc_row_sampling* rows, const gvc_logits_processors* sets, const gvc_logits_warpers* warps,
+                                     int32_t n_sets, const int32_t* set_of_row, const gvc_logits_bias* bias, int32_t i0, int32_t n_steps,
+                                     int32_t max_keys, int32_t* tokens_out, int32_t tok_stride, float* latents_out, int32_t lat_stride,
+                                     float* scores_out, float* logits_out, int32_t out_stride, int32_t do_sample, gvc_stream sv) {
+    if (!bias)
+        return gvc_gpt_generate_scores(c, slots, uncond_slots, B, scale, ids, ids_stride, ids_len, finished, p, rows, sets, warps, n_sets,
+                                       set_of_row, i0, n_steps, max_keys, tokens_out, tok_stride, latents_out, lat_stride, scores_out,
+                                       logits_out, out_stride, do_sample, sv);
+    GVC_REQUIRE(c && slots, GVC_ERR_ARG, "generate_bias: null argument");
+    GVC_REQUIRE(B >= 1 && (uncond_slots ? 2 : 1) * B <= kMaxSampleRows, GVC_ERR_ARG, "generate_bias: need 1..%d rows, got %d",
+                kMaxSampleRows / (uncond_slots ? 2 : 1), B);
+    GVC_REQUIRE(!uncond_slots || (scale == scale && fabsf(scale) <= 3.0e38f), GVC_ERR_ARG, "generate_bias: the guidance scale is not finite");
+    GVC_REQUIRE(!uncond_slots || c->dm.vocab <= kCfgMaxVocab, GVC_ERR_UNSUPPORTED, "generate_bias: vocab %d above %d", c->dm.vocab,
+                kCfgMaxVocab);
+    GVC_REQUIRE((!scores_out && !logits_out) || out_stride >= 1, GVC_ERR_ARG, "generate_bias: output buffers without a stride");
+    int32_t zeros[kMaxSampleRows] = {};
+    const bool any = warps || sets;
+    StepOutputs so;
+    so.scores = scores_out; so.logits = logits_out; so.stride = out_stride; so.do_sample = do_sample != 0;
+    return generate_impl(c, slots, B, ids, ids_stride, ids_len, finished, p, rows, nullptr, any ? sets : nullptr, any ? warps : nullptr,
+                         any ? n_sets : 0, any ? (set_of_row ? set_of_row : zeros) : nullptr, i0, n_steps, max_keys, tokens_out, tok_stride,
+                         latents_out, lat_stride, sv, uncond_slots, scale, so, bias);
 }
 
 // gvc_gpt_warmup for gvc_gpt_generate_cfg over B items: everything gvc_gpt_warmup(2B) prepares, and the guided step graphs of every

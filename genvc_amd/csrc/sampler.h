@@ -56,6 +56,10 @@ struct SampleCall {
     // HF's do_sample of the call (read only with scores_out): 1 = the scores carry Temperature and the warpers (TopK(1)'s row when
     // top_k == 1), 0 = greedy search: the full processed row, no temperature
     int scores_warped;
+    // nullable: the call's sequence bias / bad words / forced EOS / renormalised scores (gvc_*_bias calls: gvc_logits_bias, device
+    // memory), call-wide: independent of rows, proc_sets and warps.  Null: none, and the kernels compute exactly what they compute
+    // without this field
+    const gvc_logits_bias* bias;
 };
 
 // row b's entry of a per-step output buffer at this step (see SampleCall::scores_out)
@@ -121,5 +125,7 @@ int check_warp_sets(const gvc_logits_processors* sets, const gvc_logits_warpers*
                     int vocab);
 // warps[0..n_sets) -> dst[0..n_sets) on stream s (one small launch)
 int launch_stage_warps(gvc_logits_warpers* dst, const gvc_logits_warpers* warps, int n_sets, hipStream_t s);
+// *bias -> *dst on stream s, BY VALUE in one small launch (1.3 KB of kernel argument); check_bias (logits_proc.h) comes first
+int launch_stage_bias(gvc_logits_bias* dst, const gvc_logits_bias* bias, hipStream_t s);
 
 }  // namespace gvc

@@ -46,6 +46,7 @@ __device__ __forceinline__ T block_scan_excl(T v, T* scr /*[17]*/, T* total) {
 // sum of (a, b) over the workgroup, the same bits in every thread and on every run: the xor butterfly gives all 64 lanes of a wave one
 // value (each pairing adds x + y and y + x, which round alike), and every thread adds the 16 wave sums in wave order.  scr: [32] floats
 // that no thread reads past the leading barrier
+template <int NT = kSampThreads>
 __device__ __forceinline__ void block_sum2(float& a, float& b, float* scr) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
@@ -55,9 +56,10 @@ __device__ __forceinline__ void block_sum2(float& a, float& b, float* scr) {
     __syncthreads();
     a = 0.f; b = 0.f;
 #pragma unroll
-    for (int w = 0; w < kSampThreads / 64; ++w) { a += scr[w]; b += scr[16 + w]; }
+    for (int w = 0; w < NT / 64; ++w) { a += scr[w]; b += scr[16 + w]; }
 }
 
+template <int NT = kSampThreads>
 __device__ __forceinline__ float block_max(float v, float* scr) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
@@ -67,8 +69,30 @@ __device__ __forceinline__ float block_max(float v, float* scr) {
     __syncthreads();
     v = -INFINITY;
 #pragma unroll
-    for (int w = 0; w < kSampThreads / 64; ++w) v = fmaxf(v, scr[w]);
+    for (int w = 0; w < NT / 64; ++w) v = fmaxf(v, scr[w]);
     return v;
+}
+
+// LogitNormalization (gvc_logits_bias::renormalize) of the scores row a step has just stored: so[i] <- log_softmax(so)[i], in place,
+// by the whole workgroup of NT threads.  The maximum comes off before exp, -inf entries stay and add nothing, and the sum is the
+// fixed-order workgroup sum.  Nothing else reads the row: the tokens do not move.  scr: [32] floats
+template <int NT>
+__device__ void renorm_row(float* so, int V, float* scr) {
+    __syncthreads();                         // the row as the other threads stored it
+    float m = -INFINITY;
+    for (int i = threadIdx.x; i < V; i += NT) m = fmaxf(m, so[i]);
+    m = block_max<NT>(m, scr);
+    float z = 0.f, unused = 0.f;
+    for (int i = threadIdx.x; i < V; i += NT) {
+        const float x = so[i];
+        if (x > -INFINITY) z += expf(x - m);
+    }
+    block_sum2<NT>(z, unused, scr);
+    const float lz = logf(z);
+    for (int i = threadIdx.x; i < V; i += NT) {
+        const float x = so[i];
+        if (x > -INFINITY) so[i] = (x - m) - lz;
+    }
 }
 
 // softmax mass (.x) and entropy (.y) of the survivors (k0, k1) of this thread's pair (s0, s1); m = the largest surviving score.
@@ -150,6 +174,7 @@ __global__ __launch_bounds__(kSampThreads) void k_sample(SampleCall cv, const Sa
     __shared__ double dscr[17];
     __shared__ float wscr[32];
     __shared__ uint32_t kill[kProcWords];
+    __shared__ BiasHits bh;
     const SampleCall& C = cp ? *cp : cv;
     const int b = blockIdx.x, tid = threadIdx.x;
     const int V = C.p.vocab;
@@ -165,23 +190,33 @@ __global__ __launch_bounds__(kSampThreads) void k_sample(SampleCall cv, const Sa
     const int top_k = R ? R->top_k : C.p.top_k;
     const gvc_logits_processors* P = row_procs(C, b);
 
+    // sequence bias / bad words / forced EOS of the call (null: none of the lines that read Z runs)
+    const gvc_logits_bias* Z = C.bias;
+    const bool force = Z && Z->force_eos_at > 0 && len - Z->prompt_len == Z->force_eos_at - 1;
+    const bool pr = P || Z;                   // a kill bitmap and a ProcStep exist
+
     for (int i = tid; i < kSortN; i += kSampThreads) seen[i] = 0;
-    ProcStep ps{false, 0.f};
-    if (P) ps = proc_row_begin(*P, len, P->prompt_lens ? P->prompt_lens[b] : P->prompt_len, C.p.eos_token, kill, tid);
+    ProcStep ps{false, 0.f, force};
+    if (P) ps = proc_row_begin(*P, len, P->prompt_lens ? P->prompt_lens[b] : P->prompt_len, C.p.eos_token, kill, tid, force);
+    else if (Z && tid < kProcWords) kill[tid] = 0u;
+    if (Z && tid < 64) bias_match(*Z, ids, len, &bh, tid);
     __syncthreads();
     for (int i = tid; i < len; i += kSampThreads) {
         const int id = ids[i];
         if (id >= 0 && id < V) seen[id] = 1;
     }
-    if (P) proc_ngram(ids, len, P->no_repeat_ngram_size, V, kill, tid, kSampThreads);
+    // (a forced EOS overrides the bans of the processors ahead of it in HF's list: n-gram and bad words)
+    if (P && !force) proc_ngram(ids, len, P->no_repeat_ngram_size, V, kill, tid, kSampThreads);
+    if (Z && !force) bias_bans(*Z, bh, V, kill, tid);
+    const uint32_t hits = Z ? bh.hit & (uint32_t)((1ull << Z->n_bias) - 1ull) : 0u;
     __syncthreads();
-    // RepetitionPenalty (every id of input_ids incl. the fake prefix, once), the processors, then Temperature
+    // SequenceBias, RepetitionPenalty (every id of input_ids incl. the fake prefix, once), the processors, then Temperature
     for (int i = tid; i < kSortN; i += kSampThreads) {
         float v = -INFINITY;
         if (i < V) {
-            v = lg[i];
+            v = bias_logit(lg[i], i, hits, bh);
             if (seen[i]) v = v < 0.f ? v * rep_pen : v / rep_pen;
-            if (P) v = proc_score(v, i, C.p.eos_token, ps, kill);
+            if (pr) v = proc_score(v, i, C.p.eos_token, ps, kill);
             v = v / temp;
         }
         sc[i] = v;
@@ -218,9 +253,9 @@ __global__ __launch_bounds__(kSampThreads) void k_sample(SampleCall cv, const Sa
             } else {
                 // greedy search has no Temperature: the row as it stood before the division above
                 for (int i = tid; i < V; i += kSampThreads) {
-                    float v = lg[i];
+                    float v = bias_logit(lg[i], i, hits, bh);
                     if (seen[i]) v = v < 0.f ? v * rep_pen : v / rep_pen;
-                    if (P) v = proc_score(v, i, C.p.eos_token, ps, kill);
+                    if (pr) v = proc_score(v, i, C.p.eos_token, ps, kill);
                     so[i] = v;
                 }
             }
@@ -361,6 +396,7 @@ __global__ __launch_bounds__(kSampThreads) void k_sample(SampleCall cv, const Sa
         float* lo = step_row(C.logits_out, C, b, step);
         for (int i = tid; i < V; i += kSampThreads) lo[i] = raw[i];
     }
+    if (Z && Z->renormalize && C.scores_out) renorm_row<kSampThreads>(step_row(C.scores_out, C, b, step), V, wscr);
 }
 
 // top_k = 1 (the configuration of every BASELINE workload that fixes top_k: TopK(1) leaves one candidate, so top-p and the draw are
@@ -374,6 +410,8 @@ __global__ __launch_bounds__(kGreedyThreads) void k_sample_greedy(SampleCall cv,
     __shared__ int s_tok;
     __shared__ float s_top;
     __shared__ uint32_t kill[kProcWords];
+    __shared__ BiasHits bh;
+    __shared__ float rscr[32];
     unsigned char* seen = reinterpret_cast<unsigned char*>(seen_w);
     const SampleCall& C = cp ? *cp : cv;
     const int b = blockIdx.x, tid = threadIdx.x;
@@ -391,14 +429,22 @@ __global__ __launch_bounds__(kGreedyThreads) void k_sample_greedy(SampleCall cv,
     for (int u = 0; u < PER; ++u) { const int i = tid + u * kGreedyThreads; v[u] = i < V ? lg[i] : -INFINITY; }
     for (int i = tid; i < kSortN / 4; i += kGreedyThreads) seen_w[i] = 0u;
     const gvc_logits_processors* P = row_procs(C, b);
-    ProcStep ps{false, 0.f};
-    if (P) ps = proc_row_begin(*P, len, P->prompt_lens ? P->prompt_lens[b] : P->prompt_len, C.p.eos_token, kill, tid);
+    // sequence bias / bad words / forced EOS of the call, as in k_sample
+    const gvc_logits_bias* Z = C.bias;
+    const bool force = Z && Z->force_eos_at > 0 && len - Z->prompt_len == Z->force_eos_at - 1;
+    const bool pr = P || Z;
+    ProcStep ps{false, 0.f, force};
+    if (P) ps = proc_row_begin(*P, len, P->prompt_lens ? P->prompt_lens[b] : P->prompt_len, C.p.eos_token, kill, tid, force);
+    else if (Z && tid < kProcWords) kill[tid] = 0u;
+    if (Z && tid < 64) bias_match(*Z, ids, len, &bh, tid);
     __syncthreads();
     for (int i = tid; i < len; i += kGreedyThreads) {
         const int id = ids[i];
         if (id >= 0 && id < V) seen[id] = 1;
     }
-    if (P) proc_ngram(ids, len, P->no_repeat_ngram_size, V, kill, tid, kGreedyThreads);
+    if (P && !force) proc_ngram(ids, len, P->no_repeat_ngram_size, V, kill, tid, kGreedyThreads);
+    if (Z && !force) bias_bans(*Z, bh, V, kill, tid);
+    const uint32_t hits = Z ? bh.hit & (uint32_t)((1ull << Z->n_bias) - 1ull) : 0u;
     __syncthreads();
     // per-step scores of a gvc_gpt_generate_scores call (SampleCall::scores_out): the loop below stores the row of a greedy search
     float* so = C.scores_out && !C.scores_warped ? step_row(C.scores_out, C, b, step) : nullptr;
@@ -407,9 +453,9 @@ __global__ __launch_bounds__(kGreedyThreads) void k_sample_greedy(SampleCall cv,
     for (int u = 0; u < PER; ++u) {
         const int i = tid + u * kGreedyThreads;
         if (i < V) {
-            float x = v[u];
+            float x = bias_logit(v[u], i, hits, bh);
             if (seen[i]) x = x < 0.f ? x * rep_pen : x / rep_pen;
-            if (P) x = proc_score(x, i, C.p.eos_token, ps, kill);
+            if (pr) x = proc_score(x, i, C.p.eos_token, ps, kill);
             if (so) so[i] = x;                // greedy search: the processed row, no Temperature
             x = x / temp;
             if (x > bv || (x == bv && i < bi)) { bv = x; bi = i; }
@@ -449,9 +495,9 @@ __global__ __launch_bounds__(kGreedyThreads) void k_sample_greedy(SampleCall cv,
         for (int u = 0; u < PER; ++u) {
             const int i = tid + u * kGreedyThreads;
             if (i < V) {
-                float x = v[u];
+                float x = bias_logit(v[u], i, hits, bh);
                 if (seen[i]) x = x < 0.f ? x * rep_pen : x / rep_pen;
-                if (P) x = proc_score(x, i, C.p.eos_token, ps, kill);
+                if (pr) x = proc_score(x, i, C.p.eos_token, ps, kill);
                 x = x / temp;
                 sw[i] = x >= top ? x : -INFINITY;
             }
@@ -466,6 +512,7 @@ __global__ __launch_bounds__(kGreedyThreads) void k_sample_greedy(SampleCall cv,
             if (i < V) lo[i] = C.logits_src ? raw[i] : v[u];
         }
     }
+    if (Z && Z->renormalize && C.scores_out) renorm_row<kGreedyThreads>(step_row(C.scores_out, C, b, step), V, rscr);
 }
 __global__ void k_stage_rows(gvc_row_sampling* dst, SampleRows src, int B) {
     if ((int)threadIdx.x < B) dst[threadIdx.x] = src.r[threadIdx.x];
@@ -491,6 +538,39 @@ __global__ void k_stage_set_index(int32_t* dst, SetIndex src, int B) {
 
 __global__ void k_stage_warps(gvc_logits_warpers* dst, WarpTable t) {
     if ((int)threadIdx.x < t.n) dst[threadIdx.x] = t.w[threadIdx.x];
+}
+
+__global__ void k_stage_bias(gvc_logits_bias* dst, gvc_logits_bias src) {
+    int32_t* d = reinterpret_cast<int32_t*>(dst);
+    const int32_t* w = reinterpret_cast<const int32_t*>(&src);
+    for (int i = threadIdx.x; i < (int)(sizeof(gvc_logits_bias) / sizeof(int32_t)); i += blockDim.x) d[i] = w[i];
+}
+
+int check_bias(const gvc_logits_bias& Z, int vocab) {
+    GVC_REQUIRE(vocab <= 32 * kProcWords, GVC_ERR_UNSUPPORTED, "bias: vocab %d > %d", vocab, 32 * kProcWords);
+    GVC_REQUIRE(Z.n_bias >= 0 && Z.n_ban >= 0 && Z.n_bias <= GVC_BIAS_MAX_SEQS && Z.n_ban <= GVC_BIAS_MAX_SEQS &&
+                    Z.n_bias + Z.n_ban <= GVC_BIAS_MAX_SEQS,
+                GVC_ERR_ARG, "bias: %d sequence_bias + %d bad-word entries outside [0, %d]", Z.n_bias, Z.n_ban, GVC_BIAS_MAX_SEQS);
+    GVC_REQUIRE(Z.force_eos_at >= 0 && Z.prompt_len >= 0 && (Z.renormalize == 0 || Z.renormalize == 1), GVC_ERR_ARG,
+                "bias: force_eos_at %d / prompt_len %d negative, or renormalize %d not 0 / 1", Z.force_eos_at, Z.prompt_len, Z.renormalize);
+    GVC_REQUIRE(Z.reserved[0] == 0 && Z.reserved[1] == 0 && Z.reserved[2] == 0, GVC_ERR_ARG, "bias: reserved fields must be 0");
+    for (int e = 0; e < Z.n_bias + Z.n_ban; ++e) {
+        GVC_REQUIRE(Z.len[e] >= 1 && Z.len[e] <= GVC_BIAS_MAX_LEN, GVC_ERR_ARG, "bias: entry %d has length %d outside [1, %d]", e, Z.len[e],
+                    GVC_BIAS_MAX_LEN);
+        for (int q = 0; q < Z.len[e]; ++q)
+            GVC_REQUIRE(Z.ids[e][q] >= 0 && Z.ids[e][q] < vocab, GVC_ERR_ARG, "bias: entry %d holds id %d outside [0, %d)", e, Z.ids[e][q],
+                        vocab);
+        // finite or -inf (a ban): NaN and +inf would poison the row
+        GVC_REQUIRE(e >= Z.n_bias || (Z.bias[e] == Z.bias[e] && Z.bias[e] <= 3.4028234664e38f), GVC_ERR_ARG,
+                    "bias: entry %d has bias %g (finite or -inf)", e, (double)Z.bias[e]);
+    }
+    return GVC_OK;
+}
+
+int launch_stage_bias(gvc_logits_bias* dst, const gvc_logits_bias* bias, hipStream_t s) {
+    hipLaunchKernelGGL(k_stage_bias, dim3(1), dim3(64), 0, s, dst, *bias);
+    GVC_LAUNCH_CHECK();
+    return GVC_OK;
 }
 
 int check_procs(const gvc_logits_processors& P, int vocab) {
@@ -773,6 +853,54 @@ extern "C" int gvc_sample_warp(const float* logits, int32_t B, int32_t* ids, int
         sc.logits = logits; sc.B = B; sc.ids = ids; sc.ids_stride = ids_stride; sc.ids_len = ids_len;
         sc.finished = finished; sc.p = *p; sc.step = step; sc.tok_out = tok_out; sc.rows = d_rows;
         sc.proc_sets = d_sets; sc.set_of_row = d_sor; sc.warps = d_warps;
+        if (rows) sc.p.top_k = greedy ? 1 : 0;          // (kernel choice only: every row's settings come from d_rows)
+        rc = gvc::launch_sample(sc, s);
+    }
+    const hipError_t e = hipFreeAsync(d, s);
+    if (rc) return rc;
+    GVC_CHECK_HIP(e);
+    return GVC_OK;
+}
+
+extern "C" int gvc_sample_bias(const float* logits, int32_t B, int32_t* ids, int32_t ids_stride, int32_t* ids_len, int32_t* finished,
+                               const gvc_sample_params* p, const gvc_row_sampling* rows, const gvc_logits_processors* sets,
+                               const gvc_logits_warpers* warps, int32_t n_sets, const int32_t* set_of_row, const gvc_logits_bias* bias,
+                               int32_t step, int32_t* tok_out, gvc_stream sv) {
+    GVC_REQUIRE(logits && ids && ids_len && finished && p && tok_out && B >= 1, GVC_ERR_ARG, "gvc_sample_bias: bad argument");
+    const bool any = sets || warps;
+    if (!bias && any) return gvc_sample_warp(logits, B, ids, ids_stride, ids_len, finished, p, rows, sets, warps, n_sets, set_of_row, step, tok_out, sv);
+    GVC_REQUIRE(B <= gvc::kMaxSampleRows, GVC_ERR_ARG, "gvc_sample_bias: need 1..%d rows, got %d", gvc::kMaxSampleRows, B);
+    int rc = GVC_OK;
+    if (bias && (rc = gvc::check_bias(*bias, p->vocab))) return rc;
+    if (any && (rc = gvc::check_warp_sets(sets, warps, n_sets, set_of_row, B, p->vocab))) return rc;
+    bool greedy = p->top_k == 1;
+    if (rows && (rc = gvc::check_sample_rows(rows, B, p->vocab, &greedy))) return rc;
+    int32_t zeros[gvc::kMaxSampleRows] = {};
+    const int32_t* sor = set_of_row ? set_of_row : zeros;             // (null: every row uses entry 0)
+    hipStream_t s = (hipStream_t)sv;
+    // everything needs device memory for the duration of this call only: stream-ordered, freed behind the sampler launch
+    const size_t bias_bytes = bias ? sizeof(gvc_logits_bias) : 0;
+    const size_t set_bytes = sets ? (size_t)n_sets * sizeof(gvc_logits_processors) : 0;
+    const size_t warp_bytes = warps ? (size_t)n_sets * sizeof(gvc_logits_warpers) : 0;
+    const size_t row_bytes = rows ? (size_t)B * sizeof(gvc_row_sampling) : 0;
+    char* d = nullptr;
+    GVC_CHECK_HIP(hipMallocAsync((void**)&d, bias_bytes + set_bytes + warp_bytes + row_bytes + (size_t)B * sizeof(int32_t), s));
+    gvc_logits_bias* d_bias = reinterpret_cast<gvc_logits_bias*>(d);
+    gvc_logits_processors* d_sets = sets ? reinterpret_cast<gvc_logits_processors*>(d + bias_bytes) : nullptr;
+    gvc_logits_warpers* d_warps = warps ? reinterpret_cast<gvc_logits_warpers*>(d + bias_bytes + set_bytes) : nullptr;
+    gvc_row_sampling* d_rows = rows ? reinterpret_cast<gvc_row_sampling*>(d + bias_bytes + set_bytes + warp_bytes) : nullptr;
+    int32_t* d_sor = reinterpret_cast<int32_t*>(d + bias_bytes + set_bytes + warp_bytes + row_bytes);
+    if (bias) rc = gvc::launch_stage_bias(d_bias, bias, s);
+    if (rc == GVC_OK && sets) rc = gvc::launch_stage_proc_sets(d_sets, sets, n_sets, sor, B, s);
+    if (rc == GVC_OK && warps) rc = gvc::launch_stage_warps(d_warps, warps, n_sets, s);
+    if (rc == GVC_OK && any) rc = gvc::launch_stage_set_index(d_sor, sor, B, s);
+    if (rc == GVC_OK && rows) rc = gvc::launch_stage_rows(d_rows, rows, B, s);
+    if (rc == GVC_OK) {
+        gvc::SampleCall sc;
+        memset(&sc, 0, sizeof(sc));
+        sc.logits = logits; sc.B = B; sc.ids = ids; sc.ids_stride = ids_stride; sc.ids_len = ids_len;
+        sc.finished = finished; sc.p = *p; sc.step = step; sc.tok_out = tok_out; sc.rows = d_rows;
+        sc.proc_sets = d_sets; sc.set_of_row = any ? d_sor : nullptr; sc.warps = d_warps; sc.bias = bias ? d_bias : nullptr;
         if (rows) sc.p.top_k = greedy ? 1 : 0;          // (kernel choice only: every row's settings come from d_rows)
         rc = gvc::launch_sample(sc, s);
     }

@@ -160,6 +160,109 @@ def logits_warpers(kw, sampling=True):
     return w
 
 
+# HF generate kwargs of the call-wide sequence bias / bad words / forced EOS / renormalised scores (include/genvc_hip.h: gvc_logits_bias)
+BIAS_KWARGS = ("sequence_bias", "bad_words_ids", "forced_eos_token_id", "forced_bos_token_id", "renormalize_logits")
+BIAS_MAX_SEQS = _lib.BIAS_MAX_SEQS      # entries of sequence_bias and bad_words_ids together
+BIAS_MAX_LEN = _lib.BIAS_MAX_LEN        # ids of one entry
+
+
+def _bias_ids(name, seq, vocab):
+    """one id sequence of sequence_bias / bad_words_ids -> a tuple of ints in [0, vocab), 1..BIAS_MAX_LEN of them"""
+    if isinstance(seq, (str, bytes)) or not hasattr(seq, "__iter__"):
+        raise ValueError(f"{name}: an entry must be a sequence of token ids, not {seq!r}")
+    seq = tuple(seq)
+    if not 1 <= len(seq) <= BIAS_MAX_LEN:
+        raise ValueError(f"{name}: an entry holds {len(seq)} ids; the device matches 1..{BIAS_MAX_LEN}")
+    for x in seq:
+        if isinstance(x, bool) or int(x) != x or not 0 <= int(x) < vocab:
+            raise ValueError(f"{name}: token {x!r} outside [0, {vocab})")
+    return tuple(int(x) for x in seq)
+
+
+def _sequence_bias(value, vocab):
+    """sequence_bias in either HF form -- {tuple(ids): float} or [[ids, float], ...] -> [(ids, float)] in HF's order of application:
+    the length-1 entries, then the longer ones in dict order (the list form becomes a dict first, as in HF: a repeated sequence keeps
+    its first place and its last value)"""
+    if value is None:
+        return []
+    if isinstance(value, dict):
+        items = list(value.items())
+    elif isinstance(value, (list, tuple)):
+        items = []
+        for e in value:
+            if not isinstance(e, (list, tuple)) or len(e) != 2:
+                raise ValueError(f"sequence_bias: a list entry must be [ids, bias], not {e!r}")
+            items.append((e[0], e[1]))
+    else:
+        raise ValueError(f"sequence_bias must be a dict {{tuple(ids): float}} or a list [[ids, float], ...], not {type(value).__name__}")
+    merged = {}
+    for seq, v in items:
+        if isinstance(v, bool) or not isinstance(v, (int, float)):
+            raise ValueError(f"sequence_bias: the bias of {seq!r} must be a number, not {v!r}")
+        v = float(v)
+        if v != v or v == float("inf"):
+            raise ValueError(f"sequence_bias: the bias of {seq!r} must be finite or -inf, not {v!r}")
+        merged[_bias_ids("sequence_bias", seq, vocab)] = v
+    out = [(k, v) for k, v in merged.items() if len(k) == 1]
+    return out + [(k, v) for k, v in merged.items() if len(k) > 1]
+
+
+def logits_bias(kw, prompt_len, max_new, vocab, eos):
+    """the BIAS_KWARGS of one call (HF semantics, transformers 5.x SequenceBiasLogitsProcessor / NoBadWordsLogitsProcessor /
+    ForcedEOSTokenLogitsProcessor / LogitNormalization) -> a gvc_logits_bias, or None when every one is off: None, {} / [], False, and
+    bad_words_ids == [[eos]] (HF drops a bare [eos]).  prompt_len: the prompt length of every row (fake ids included); max_new: the
+    call's max_new_tokens (the forced EOS fires at the step that writes token max_new - 1).  Ids lie in [0, vocab) in both forms of
+    sequence_bias (HF's list form refuses 0: the one deviation).  forced_eos_token_id must be `eos` -- the loop knows one stop token --
+    and the stop token must not be suppressed with it (the row would be all -inf).  forced_bos_token_id is accepted and does nothing:
+    HF's processor fires at cur_len == 1, and no prompt of this model is that short.  Malformed settings raise ValueError."""
+    seqs = _sequence_bias(kw.get("sequence_bias"), vocab)
+    bad = kw.get("bad_words_ids")
+    bans = []
+    if bad is not None:
+        if isinstance(bad, (str, bytes, dict)) or not hasattr(bad, "__iter__"):
+            raise ValueError(f"bad_words_ids must be a list of lists of token ids, not {bad!r}")
+        for seq in bad:
+            ids = _bias_ids("bad_words_ids", seq, vocab)
+            if ids != (int(eos),) and ids not in bans:
+                bans.append(ids)
+    if len(seqs) + len(bans) > BIAS_MAX_SEQS:
+        raise ValueError(f"sequence_bias ({len(seqs)}) and bad_words_ids ({len(bans)}) hold {len(seqs) + len(bans)} entries together; the "
+                         f"device matches {BIAS_MAX_SEQS} per step")
+    force = kw.get("forced_eos_token_id")
+    if force is not None:
+        if isinstance(force, (list, tuple)) and len(force) == 1:
+            force = force[0]
+        if isinstance(force, bool) or not isinstance(force, int) or force != int(eos):
+            raise ValueError(f"forced_eos_token_id={kw.get('forced_eos_token_id')!r} must be the model's stop token {int(eos)}: the "
+                             "generation loop knows one EOS")
+        sup = list(kw.get("suppress_tokens") or ())
+        if int(max_new) == 1:
+            sup += list(kw.get("begin_suppress_tokens") or ())
+        if int(eos) in [int(x) for x in sup]:
+            raise ValueError(f"forced_eos_token_id={int(eos)} with the stop token suppressed leaves the last step no token at all")
+        if int(max_new) < 1:
+            raise ValueError(f"forced_eos_token_id needs max_new_tokens >= 1, not {max_new}")
+    bos = kw.get("forced_bos_token_id")
+    if bos is not None and (isinstance(bos, bool) or not isinstance(bos, int) or not 0 <= bos < vocab):
+        raise ValueError(f"forced_bos_token_id: token {bos!r} outside [0, {vocab})")
+    renorm = kw.get("renormalize_logits")
+    if renorm is not None and not isinstance(renorm, bool):
+        raise ValueError(f"renormalize_logits must be a bool, not {renorm!r}")
+    if not (seqs or bans or force is not None or renorm):
+        return None
+    z = _lib.LogitsBias()
+    z.n_bias, z.n_ban = len(seqs), len(bans)
+    z.force_eos_at = int(max_new) if force is not None else 0
+    z.renormalize = 1 if renorm else 0
+    z.prompt_len = int(prompt_len)
+    for e, (ids, v) in enumerate(seqs + [(b, float("-inf")) for b in bans]):
+        z.len[e] = len(ids)
+        z.bias[e] = v
+        for q, x in enumerate(ids):
+            z.ids[e][q] = x
+    return z
+
+
 def check_proc_kwargs(kw, where):
     """a per-row / per-group / per-job / per-session processor dict may hold PROC_KWARGS and WARP_KWARGS only: anything else raises
     ValueError naming the key and `where` it came from"""
@@ -861,6 +964,57 @@ class GptEngine:
                                             sets.set_of_row if sets is not None else None, int(i0), int(n_steps), int(max_keys),
                                             ptr(tokens_out), tokens_out.stride(0), ptr(latents_out), lat_stride, ptr(scores_out),
                                             ptr(logits_out), out_stride, int(bool(do_sample)), stream()), "generate_scores")
+
+    def sample_bias(self, logits, ids, ids_len, finished, params, bias, step, sets=None, rows=None):
+        """sample_warp() with the call's sequence bias / bad words / forced EOS (a _lib.LogitsBias from logits_bias(), or None;
+        include/genvc_hip.h: gvc_sample_bias).  sets: a WarperSets / ProcessorSets over the B rows, or None for no processors"""
+        B = logits.shape[0]
+        if sets is not None and len(sets) != B:
+            raise ValueError(f"{len(sets)} set indices for {B} rows")
+        arr = _rows_arg(rows, B) if rows is not None else None
+        tok = torch.empty(B, device=logits.device, dtype=torch.int32)
+        check(lib().gvc_sample_bias(ptr(_f32(logits)), B, ptr(_i32(ids)), ids.shape[1], ptr(_i32(ids_len)), ptr(_i32(finished)),
+                                    C.byref(params), arr, sets.sets if sets is not None else None,
+                                    getattr(sets, "warps", None) if sets is not None else None, sets.n_sets if sets is not None else 0,
+                                    sets.set_of_row if sets is not None else None, None if bias is None else C.byref(bias), int(step),
+                                    ptr(tok), stream()), "sample_bias")
+        return tok
+
+    def generate_bias(self, slots, uncond_slots, scale, ids, ids_len, finished, params, sets, bias, i0, n_steps, tokens_out, latents_out,
+                      scores_out=None, logits_out=None, do_sample=True, max_keys=0, rows=None):
+        """generate_scores() with the call's sequence bias / bad words / forced EOS / renormalised scores (a _lib.LogitsBias from
+        logits_bias(); include/genvc_hip.h: gvc_gpt_generate_bias).  The struct travels with the call in one staging launch: the step
+        graphs are generate()'s, and nothing is allocated or captured once warm.  bias None is generate_scores()."""
+        self._join_side()
+        B = slots.shape[0]
+        if uncond_slots is not None and uncond_slots.shape[0] != B:
+            raise ValueError(f"{uncond_slots.shape[0]} unconditional slots for {B} items")
+        if sets is not None and len(sets) != B:
+            raise ValueError(f"{len(sets)} set indices for {B} rows")
+        arr = _rows_arg(rows, B) if rows is not None else None
+        assert tokens_out.is_cuda and tokens_out.dtype == torch.int32 and tokens_out.stride(1) == 1
+        lat_stride = 0
+        if latents_out is not None:
+            assert latents_out.is_cuda and latents_out.dtype == torch.float32 and latents_out.stride(2) == 1
+            assert latents_out.stride(1) == self.d and latents_out.stride(0) % self.d == 0
+            lat_stride = latents_out.stride(0) // self.d
+        out_stride = 0
+        for buf in (scores_out, logits_out):
+            if buf is not None:
+                if tuple(buf.shape[::2]) != (B, self.V) or (out_stride and buf.shape[1] != out_stride):
+                    raise ValueError(f"generate_bias: an output buffer of shape {tuple(buf.shape)} for {B} rows of {self.V} scores")
+                _f32(buf)
+                out_stride = int(buf.shape[1])
+        if rows is not None:
+            params = sample_params(dict(repetition_penalty=1.0, temperature=1.0, top_p=1.0, top_k=0), self.V, self.dims["stop_audio_token"])
+        check(lib().gvc_gpt_generate_bias(self._h, ptr(_i32(slots)), None if uncond_slots is None else ptr(_i32(uncond_slots)), B,
+                                          float(scale), ptr(_i32(ids)), ids.shape[1], ptr(_i32(ids_len)), ptr(_i32(finished)),
+                                          C.byref(params), arr, sets.sets if sets is not None else None,
+                                          getattr(sets, "warps", None) if sets is not None else None,
+                                          sets.n_sets if sets is not None else 0, sets.set_of_row if sets is not None else None,
+                                          None if bias is None else C.byref(bias), int(i0), int(n_steps), int(max_keys),
+                                          ptr(tokens_out), tokens_out.stride(0), ptr(latents_out), lat_stride, ptr(scores_out),
+                                          ptr(logits_out), out_stride, int(bool(do_sample)), stream()), "generate_bias")
 
     def transition_scores(self, scores, tokens, normalize=False):
         """HF's compute_transition_scores without beams on the device (include/genvc_hip.h: gvc_transition_scores): scores fp32

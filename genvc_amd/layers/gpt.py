@@ -12,7 +12,7 @@ from torch import nn
 
 from .._lib import GenvcHipError
 from ..engine import (BEAM_LENGTH_MODES, beam_early_stopping, check_beam_groups, GroupBeamSearch, MAX_CONTRASTIVE_K, PROC_KWARGS, WARP_KWARGS, BeamSearch, ContrastiveSearch, GptEngine, WarperSets,
-                      check_proc_kwargs, logits_processors, logits_sets, logits_warpers, sample_params)
+                      check_proc_kwargs, logits_bias, logits_processors, logits_sets, logits_warpers, sample_params)
 from .perceiver_encoder import PerceiverResampler
 
 
@@ -233,6 +233,21 @@ def _no_step_outputs(kw, mode):
                                   "served")
 
 
+# the BIAS_KWARGS (engine.logits_bias) that change a call; forced_bos_token_id never does (see GPT.generate)
+_BIAS_ON = ("sequence_bias", "bad_words_ids", "forced_eos_token_id", "renormalize_logits")
+
+
+def _no_bias(kw, where):
+    """the modes and paths the call-wide sequence bias does not serve: sequence_bias / bad_words_ids / forced_eos_token_id /
+    renormalize_logits at anything but an off spelling (None, {}, [], False) raise, naming the kwarg and the mode or path"""
+    for k in _BIAS_ON:
+        v = kw.get(k)
+        if v is None or v is False or (isinstance(v, (dict, list, tuple)) and len(v) == 0):
+            continue
+        raise NotImplementedError(f"{k}={v!r} is not served with {where}: GPT.generate serves it on the sampler paths (greedy, sampling, "
+                                  "num_return_sequences, guidance_scale), one call-wide set per call")
+
+
 def _any_proc(kw):
     """a processor kwarg is given (engine.logits_processors may still find every one at its default)"""
     return any(kw.get(k) is not None for k in PROC_KWARGS)
@@ -445,6 +460,8 @@ class GPT(nn.Module):
         # typical / epsilon / eta warpers (engine.WARP_KWARGS): with any on, the call carries them with its processors as one entry
         warp = logits_warpers(kw, sampling=kw.get("do_sample", True))
         st["warp"] = None if warp is None else WarperSets.one(st["proc"], warp, B)
+        # sequence bias / bad words / forced EOS / renormalised scores (engine.BIAS_KWARGS): one call-wide struct, None when all are off
+        st["bias"] = logits_bias(kw, n0, max_new, self.num_audio_tokens, self.stop_audio_token)
         # `cached_cond_rows` (extension): the leading rows of the prefix -- the conditioning latents, identical for every
         # segment of an utterance -- are still in the KV cache from the previous segment's prefill of these slots
         if fan > 1:
@@ -461,7 +478,15 @@ class GPT(nn.Module):
         if n > 0:
             # the cache holds n0 positions after the prefill and one more per step: the library picks its decode kernels for the
             # context length this call reaches (not for the 602-token cap the ids rows are sized for)
-            if st.get("scores") is not None or st.get("raw_logits") is not None:
+            if st.get("bias") is not None:
+                # sequence_bias / bad_words_ids / forced_eos_token_id / renormalize_logits: the same steps, the call state also carrying
+                # the bias struct (and the buffers of output_scores / output_logits, and the unconditional slots, when the call has them)
+                sets = st["warp"] if st["warp"] is not None else (None if st["proc"] is None else WarperSets.one(st["proc"], None, st["B"]))
+                self.engine.generate_bias(st["slots"], st.get("uncond_slots"), st.get("guidance_scale", 1.0), st["ids"], st["ids_len"],
+                                          st["finished"], st["params"], sets, st["bias"], st["done"], n, st["toks"], st["lats"],
+                                          scores_out=st.get("scores"), logits_out=st.get("raw_logits"), do_sample=st.get("do_sample", True),
+                                          max_keys=max(st["n0"], st.get("n0_uncond", 0)) + st["done"] + n)
+            elif st.get("scores") is not None or st.get("raw_logits") is not None:
                 # output_scores / output_logits: the same steps, the call state also naming the buffers the sampler stores its rows in
                 sets = st["warp"] if st["warp"] is not None else (None if st["proc"] is None else WarperSets.one(st["proc"], None, st["B"]))
                 self.engine.generate_scores(st["slots"], st.get("uncond_slots"), st.get("guidance_scale", 1.0), st["ids"], st["ids_len"],
@@ -546,15 +571,26 @@ class GPT(nn.Module):
         of the tensor; with it output_scores=True / output_logits=True add `scores` / `logits`, tuples of n fp32 [rows, V] rows, as
         transformers' _sample fills them -- on the sampler paths (greedy, sampling, every processor and warper,
         num_return_sequences, guidance_scale); with beams, beam groups or contrastive search they raise NotImplementedError.  The
-        tokens are those of the call without the kwargs, bit for bit.  Without return_dict_in_generate the other two are ignored."""
+        tokens are those of the call without the kwargs, bit for bit.  Without return_dict_in_generate the other two are ignored.
+        sequence_bias / bad_words_ids / forced_eos_token_id / renormalize_logits (engine.logits_bias; include/genvc_hip.h:
+        gvc_logits_bias): transformers' SequenceBias, NoBadWords, ForcedEOSToken and LogitNormalization processors at
+        their places in HF's list, on the same sampler paths (under guidance on the guided row).  sequence_bias ids may be 0 in both of
+        its forms (HF's list form refuses 0); forced_eos_token_id must be the stop token and fires at the step that writes token
+        max_new_tokens - 1; renormalize_logits makes the stored `scores` log-probabilities and leaves the tokens those of the call
+        without it, bit for bit (no effect without output_scores).  forced_bos_token_id is accepted and does nothing: HF's processor
+        fires at cur_len == 1, and no prompt of this model is that short.  Beams, beam groups and contrastive search raise
+        NotImplementedError for them, as the grouped, rolling, session and streaming paths do."""
         _num_return(generate_kwargs)
         scale = _guidance_scale(generate_kwargs)
         if scale is not None:
             return self._generate_guided(cond_latents, text_inputs, scale, generate_kwargs)
         if _contrastive_kwargs(generate_kwargs) is not None:
+            _no_bias(generate_kwargs, f"contrastive search (penalty_alpha={generate_kwargs.get('penalty_alpha')})")
             _no_step_outputs(generate_kwargs, f"contrastive search (penalty_alpha={generate_kwargs.get('penalty_alpha')})")
             return self._result(self._generate_contrastive(cond_latents, text_inputs, generate_kwargs), generate_kwargs)
         if int(generate_kwargs.get("num_beams", 1) or 1) > 1 or _grouped(generate_kwargs):
+            _no_bias(generate_kwargs, "beam groups (num_beam_groups / diversity_penalty)" if _grouped(generate_kwargs)
+                     else f"beam search (num_beams={generate_kwargs.get('num_beams')})")
             _no_step_outputs(generate_kwargs, "beam groups (num_beam_groups / diversity_penalty)" if _grouped(generate_kwargs)
                              else f"beam search (num_beams={generate_kwargs.get('num_beams')})")
             return self._result(self._generate_beams(cond_latents, text_inputs, generate_kwargs), generate_kwargs, beams=True)
@@ -775,6 +811,7 @@ class GPT(nn.Module):
         _single_return(generate_kwargs, "grouped (generate_groups)")
         _no_guidance(generate_kwargs, "grouped (generate_groups)")
         _no_outputs(generate_kwargs, "grouped (generate_groups)")
+        _no_bias(generate_kwargs, "the grouped (generate_groups) path")
         kw = dict(generate_kwargs)
         gkw = None
         if group_kwargs is not None:
@@ -927,6 +964,7 @@ class GPT(nn.Module):
         _single_return(generate_kwargs, "rolling (generate_rolling)")
         _no_guidance(generate_kwargs, "rolling (generate_rolling)")
         _no_outputs(generate_kwargs, "rolling (generate_rolling)")
+        _no_bias(generate_kwargs, "the rolling (generate_rolling) path")
         kw = dict(generate_kwargs)
         jkw = None
         if job_kwargs is not None:
@@ -1078,6 +1116,7 @@ class GPT(nn.Module):
         _single_return(generate_kwargs, "streaming (get_generator)")
         _no_guidance(generate_kwargs, "streaming (get_generator)")
         _no_outputs(generate_kwargs, "streaming (get_generator)")
+        _no_bias(generate_kwargs, "the streaming (get_generator) path")
         self._need_engine()
         group = generate_kwargs.pop("stream_group", 8)
         B = int(fake_inputs.shape[0])

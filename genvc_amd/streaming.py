@@ -43,7 +43,7 @@ import torch
 
 from .inference.inference_utils import _sampling_kwargs, _vocode, handle_chunks
 from .engine import check_proc_kwargs, logits_processors, logits_sets, logits_warpers, sample_params
-from .layers.gpt import _no_contrastive, _no_guidance, _no_outputs, _single_return
+from .layers.gpt import _no_bias, _no_contrastive, _no_guidance, _no_outputs, _single_return
 from ._lib import GenvcHipError
 
 
@@ -108,6 +108,7 @@ class StreamSessions:
         _single_return(kw or {}, f"session (StreamSessions, {where})")
         _no_guidance(kw or {}, f"session (StreamSessions, {where})")
         _no_outputs(kw or {}, f"session (StreamSessions, {where})")
+        _no_bias(kw or {}, f"the session (StreamSessions, {where}) path")
         check_proc_kwargs(kw, where)
         m = dict(base, **{k: v for k, v in (kw or {}).items() if v is not None})
         try:

@@ -554,6 +554,59 @@ int gvc_gpt_generate_scores(gvc_gpt* ctx, const int32_t* slots, const int32_t* u
                             int32_t out_stride, int32_t do_sample, gvc_stream s);
 int gvc_transition_scores(const float* scores, int64_t row_stride, const int32_t* tokens, int32_t R, int32_t n, int32_t V,
                           int32_t normalize, float* out, gvc_stream s);
+/* ------------------------------------------------------------------------------------------
+ * Sequence bias, bad words, forced EOS and renormalised scores (HF sequence_bias, bad_words_ids, forced_eos_token_id,
+ * renormalize_logits; transformers generation/logits_process.py: SequenceBiasLogitsProcessor, NoBadWordsLogitsProcessor,
+ * ForcedEOSTokenLogitsProcessor, LogitNormalization), on the sampler kernels.  One call-wide struct; HF's order
+ * (generation/utils.py, _get_logits_processor) is
+ *   guidance -> SEQUENCE BIAS -> repetition penalty -> no_repeat_ngram -> BAD WORDS -> min_length -> min_new_tokens -> FORCED EOS ->
+ *   exponential decay -> suppress -> begin_suppress -> [sampling: temperature, top_k, top_p, min_p, typical, epsilon, eta] ->
+ *   LOGIT NORMALIZATION.
+ * Entry e is the id sequence ids[e][0 .. len[e]) with the value bias[e]; it HITS a row when its first len - 1 ids equal the row's
+ * last len - 1 input ids (the fake prompt ids count; len == 1 always hits; an entry longer than the row never hits).
+ *   sequence bias  entries [0, n_bias), length-1 entries first, then the caller's order: x = logit + (0 + bias of every hit entry
+ *                  that ends in this id, added in entry order), one fp32 add per term, ahead of the repetition penalty.
+ *   bad words      entries [n_bias, n_bias + n_ban): the last id of every hit entry is -inf (their bias field is not read).
+ *   forced EOS     force_eos_at = N > 0: at the step where the row holds N - 1 new tokens (len - prompt_len == N - 1) every score is
+ *                  -inf and the stop token's is 0.0, whatever the bans above say; the decay, suppress, the temperature and the
+ *                  warpers then run as ever.  N is the call's max_new_tokens.
+ *   renormalize    the scores_out row of a step is log_softmax of the row stored without it: the maximum comes off before exp, -inf
+ *                  entries stay -inf and add nothing, the sum runs in a fixed order.  Read only where a scores row is stored.  THE
+ *                  TOKENS ARE THOSE OF THE CALL WITHOUT IT, BIT FOR BIT: the draw and the argmax read the un-normalised row (in HF
+ *                  the draw reads the normalised one; the two distributions differ by rounding only).
+ * Ids lie in [0, vocab) -- HF's list form of sequence_bias refuses id 0 and its dict form does not; 0 is accepted here in both, the
+ * one deviation.  Values are finite or -inf.  The all-zero struct is "off" and computes exactly what the call without it computes.
+ * ------------------------------------------------------------------------------------------ */
+#define GVC_BIAS_MAX_SEQS 32
+#define GVC_BIAS_MAX_LEN 8
+typedef struct gvc_logits_bias {
+    int32_t n_bias;                     /* entries [0, n_bias): sequence_bias, length-1 entries first, then dict order */
+    int32_t n_ban;                      /* entries [n_bias, n_bias + n_ban): bad words; n_bias + n_ban <= GVC_BIAS_MAX_SEQS */
+    int32_t force_eos_at;               /* 0 off, else max_new_tokens: the stop token is forced at len - prompt_len == force_eos_at - 1 */
+    int32_t renormalize;                /* 0 / 1; read only where a scores row is stored */
+    int32_t prompt_len;                 /* prompt length of every row (read with force_eos_at) */
+    int32_t reserved[3];                /* 0 */
+    int32_t len[GVC_BIAS_MAX_SEQS];     /* 1..GVC_BIAS_MAX_LEN */
+    float bias[GVC_BIAS_MAX_SEQS];      /* finite or -inf */
+    int32_t ids[GVC_BIAS_MAX_SEQS][GVC_BIAS_MAX_LEN];
+} gvc_logits_bias;
+
+/* gvc_sample_bias: gvc_sample_warp with the struct above (HOST, nullable: null is gvc_sample_warp; sets / warps / set_of_row all null
+ * then mean no processors, n_sets is ignored).  gvc_gpt_generate_bias: gvc_gpt_generate_scores with it; bias null is exactly
+ * gvc_gpt_generate_scores.  The struct travels into the device-resident call state in one staging launch of its own (1.3 KB of kernel
+ * argument) ahead of the call's first launch: the same captured step graphs, no allocation and no synchronisation per call.
+ * GVC_ERR_ARG: counts outside the caps, a len outside 1..8, an id outside the vocabulary, a NaN or +inf bias, force_eos_at or
+ * prompt_len < 0, renormalize other than 0 / 1, reserved != 0.  Not on the beam or contrastive paths. */
+int gvc_sample_bias(const float* logits, int32_t B, int32_t* ids, int32_t ids_stride, int32_t* ids_len, int32_t* finished,
+                    const gvc_sample_params* p, const gvc_row_sampling* rows, const gvc_logits_processors* sets,
+                    const gvc_logits_warpers* warps, int32_t n_sets, const int32_t* set_of_row, const gvc_logits_bias* bias, int32_t step,
+                    int32_t* tok_out, gvc_stream s);
+int gvc_gpt_generate_bias(gvc_gpt* ctx, const int32_t* slots, const int32_t* uncond_slots, int32_t B, float scale, int32_t* ids,
+                          int32_t ids_stride, int32_t* ids_len, int32_t* finished, const gvc_sample_params* p,
+                          const gvc_row_sampling* rows, const gvc_logits_processors* sets, const gvc_logits_warpers* warps,
+                          int32_t n_sets, const int32_t* set_of_row, const gvc_logits_bias* bias, int32_t i0, int32_t n_steps,
+                          int32_t max_keys, int32_t* tokens_out, int32_t tok_stride, float* latents_out, int32_t lat_stride,
+                          float* scores_out, float* logits_out, int32_t out_stride, int32_t do_sample, gvc_stream s);
 /* gvc_gpt_warmup for gvc_gpt_generate_cfg over B items with this top_k: the guided step graphs of every context class up to max_keys
  * cached positions (and everything gvc_gpt_warmup(2B) prepares).  Afterwards such calls neither allocate nor synchronise */
 int gvc_gpt_warmup_cfg(gvc_gpt* ctx, int32_t B, int32_t max_keys, int32_t top_k);

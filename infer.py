@@ -51,6 +51,13 @@ if __name__ == "__main__":
     parser.add_argument("--typical_p", type=float, default=None, help="typical sampling mass in (0, 1] (1: off)")
     parser.add_argument("--epsilon_cutoff", type=float, default=None, help="epsilon sampling cut-off in [0, 1) (0: off)")
     parser.add_argument("--eta_cutoff", type=float, default=None, help="eta sampling cut-off in [0, 1) (0: off)")
+    parser.add_argument("--sequence_bias", action="append", default=None, metavar="IDS=VALUE",
+                        help="non-streaming only, repeatable: add VALUE to the score of the last of the comma-separated codec ids when the "
+                             "ids before it were just generated (HF sequence_bias), e.g. 1025=-2.0 makes every segment stop later")
+    parser.add_argument("--bad_words_ids", action="append", default=None, metavar="IDS",
+                        help="non-streaming only, repeatable: never generate this comma-separated id sequence (HF bad_words_ids)")
+    parser.add_argument("--forced_eos", action="store_true",
+                        help="non-streaming only: a segment that reaches its token budget ends with the stop code (HF forced_eos_token_id)")
     parser.add_argument("--guidance_scale", type=float, default=None,
                         help="non-streaming only: classifier-free guidance strength (HF guidance_scale; 1 or absent: off): every segment "
                              "decodes under the reference speaker and under a negative speaker and extrapolates away from the negative")
@@ -108,10 +115,25 @@ if __name__ == "__main__":
         gen_kw[k] = v
     if args.num_beam_groups > 1:
         gen_kw.update(num_beam_groups=args.num_beam_groups, diversity_penalty=args.diversity_penalty)
+    if args.sequence_bias or args.bad_words_ids or args.forced_eos:
+        if args.streaming or args.num_beams != 1 or args.penalty_alpha is not None:
+            raise SystemExit("--sequence_bias, --bad_words_ids and --forced_eos are not on the streaming path (--streaming) and do not combine "
+                             "with --num_beams or --penalty_alpha: the sampler paths of GPT.generate serve them")
+        try:
+            if args.sequence_bias:
+                gen_kw["sequence_bias"] = {tuple(int(x) for x in ent.rpartition("=")[0].split(",")): float(ent.rpartition("=")[2])
+                                           for ent in args.sequence_bias}
+            if args.bad_words_ids:
+                gen_kw["bad_words_ids"] = [[int(x) for x in ent.split(",")] for ent in args.bad_words_ids]
+        except ValueError:
+            raise SystemExit("--sequence_bias takes IDS=VALUE and --bad_words_ids takes IDS, IDS a comma-separated list of codec ids")
+        if args.forced_eos:
+            gen_kw["forced_eos_token_id"] = 1025
     try:
-        from genvc_amd.engine import logits_processors, logits_warpers
+        from genvc_amd.engine import logits_bias, logits_processors, logits_warpers
         logits_processors(gen_kw, 0, 1026)
         logits_warpers(gen_kw)
+        logits_bias(gen_kw, 0, 600, 1026, 1025)      # (any budget above 1: a first-step-only rule must not refuse here)
     except ValueError as e:
         raise SystemExit(f"bad processor flag: {e}")
 
@@ -121,6 +143,8 @@ if __name__ == "__main__":
     else:
         model, config = model_init(args.model_path, args.device, weight_dtype=args.weights)
     model.config.top_k = args.top_k
+    if args.forced_eos:
+        gen_kw["forced_eos_token_id"] = model.gpt.stop_audio_token      # (the flags were validated above against the default vocabulary)
     if args.penalty_alpha is not None:
         gen_kw.update(do_sample=False, penalty_alpha=args.penalty_alpha, top_k=args.top_k)
         if model.gpt.max_slots < args.top_k:           # one KV slot per candidate
