@@ -1869,30 +1869,56 @@ extern "C" int gvc_gpt_rearm(gvc_gpt* c) {
     return GVC_OK;
 }
 
-// the per-step score / logit buffers of a gvc_gpt_generate_scores call (SampleCall::scores_out); all null: none
-struct StepOutputs {
-    float* scores = nullptr;
-    float* logits = nullptr;
-    int stride = 0;
+// What a generation call may carry beyond gvc_gpt_generate's arguments; everything null: that plain call.  Each gvc_gpt_generate* entry
+// fills the members its signature has and generate_impl does the rest, so an option is handled in exactly one place.
+struct GenOptions {
+    const gvc_row_sampling* rows = nullptr;        // B host entries (gvc_gpt_generate_rows): the rows' own settings and keys, else p's for all
+    const gvc_logits_processors* proc = nullptr;   // the call's one processor set (gvc_gpt_generate_proc)
+    const gvc_logits_processors* sets = nullptr;   // n_sets host processor sets (gvc_gpt_generate_proc_sets) ...
+    const gvc_logits_warpers* warps = nullptr;     // ... and / or n_sets host warpers (gvc_gpt_generate_warp), both indexed through
+    int n_sets = 0;
+    const int32_t* set_of_row = nullptr;           // B host indices (null: every row uses entry 0); ignored without sets and warps
+    const int32_t* uslots = nullptr;               // the B unconditional slots of a guided call (gvc_gpt_generate_cfg) ...
+    float scale = 1.f;                             // ... and its guidance scale
+    float* scores_out = nullptr;                   // per-step score / logit buffers (gvc_gpt_generate_scores, SampleCall::scores_out)
+    float* logits_out = nullptr;
+    int out_stride = 0;
     int do_sample = 1;
+    const gvc_logits_bias* bias = nullptr;         // the call's sequence bias (gvc_gpt_generate_bias)
 };
 
-// rows: null (gvc_gpt_generate: p's settings for every row) or B host entries (gvc_gpt_generate_rows).  proc: null or the call's
-// processors (gvc_gpt_generate_proc); set_of_row: null or B host indices into the n_sets host sets (gvc_gpt_generate_proc_sets, proc null)
-// and, when warps is set (gvc_gpt_generate_warp), into the n_sets host warpers too; sets is then nullable.  uslots: null, or the B
-// unconditional slots of a guided call (gvc_gpt_generate_cfg) with guidance scale `scale`
+// the guards gvc_gpt_generate_cfg / _scores / _bias share, under the entry's name (a guided entry counts items, the others rows)
+static int check_guided(const char* name, const gvc_gpt* c, const int32_t* slots, int B, bool need_uslots, const GenOptions& o) {
+    const int per = o.uslots ? 2 : 1;
+    GVC_REQUIRE(c && slots && (o.uslots || !need_uslots), GVC_ERR_ARG, "%s: null argument", name);
+    GVC_REQUIRE(B >= 1 && per * B <= kMaxSampleRows, GVC_ERR_ARG, "%s: need 1..%d %s, got %d", name, kMaxSampleRows / per,
+                need_uslots ? "items" : "rows", B);
+    GVC_REQUIRE(!o.uslots || (o.scale == o.scale && fabsf(o.scale) <= 3.0e38f), GVC_ERR_ARG, "%s: the guidance scale is not finite", name);
+    GVC_REQUIRE(!o.uslots || c->dm.vocab <= kCfgMaxVocab, GVC_ERR_UNSUPPORTED, "%s: vocab %d above %d", name, c->dm.vocab, kCfgMaxVocab);
+    GVC_REQUIRE((!o.scores_out && !o.logits_out) || o.out_stride >= 1, GVC_ERR_ARG, "%s: output buffers without a stride", name);
+    return GVC_OK;
+}
+
 static int generate_impl(gvc_gpt* c, const int32_t* slots, int32_t B, int32_t* ids, int32_t ids_stride, int32_t* ids_len, int32_t* finished,
-                         const gvc_sample_params* p, const gvc_row_sampling* rows, const gvc_logits_processors* proc,
-                         const gvc_logits_processors* sets, const gvc_logits_warpers* warps, int32_t n_sets, const int32_t* set_of_row,
-                         int32_t i0,
-                         int32_t n_steps, int32_t max_keys, int32_t* tokens_out, int32_t tok_stride, float* latents_out, int32_t lat_stride,
-                         gvc_stream sv, const int32_t* uslots = nullptr, float scale = 1.f, const StepOutputs& so = StepOutputs(),
-                         const gvc_logits_bias* bias = nullptr) {
+                         const gvc_sample_params* p, int32_t i0, int32_t n_steps, int32_t max_keys, int32_t* tokens_out,
+                         int32_t tok_stride, float* latents_out, int32_t lat_stride, gvc_stream sv, const GenOptions& o = GenOptions()) {
+    const gvc_row_sampling* rows = o.rows;
+    const gvc_logits_processors* proc = o.proc;
+    const gvc_logits_bias* bias = o.bias;
+    const int32_t* uslots = o.uslots;
+    // without sets and warpers there is nothing to index; with either, a null index means entry 0 for every row (the entries that allow
+    // a null index have bounded B by kMaxSampleRows)
+    const bool any = o.sets || o.warps;
+    const gvc_logits_processors* sets = o.sets;
+    const gvc_logits_warpers* warps = o.warps;
+    const int n_sets = any ? o.n_sets : 0;
+    static const int32_t zeros[kMaxSampleRows] = {};
+    const int32_t* set_of_row = any ? (o.set_of_row ? o.set_of_row : zeros) : nullptr;
     int rc = check_ready(c);
     if (rc) return rc;
     GVC_REQUIRE(B >= 1 && B <= c->dm.max_slots && p && n_steps >= 0 && max_keys >= 0, GVC_ERR_ARG, "generate: bad argument");
-    GVC_REQUIRE((!so.scores && !so.logits) || (i0 >= 0 && i0 + n_steps <= so.stride), GVC_ERR_ARG,
-                "generate_scores: steps [%d, %d) do not fit the %d steps of a row of the output buffers", i0, i0 + n_steps, so.stride);
+    GVC_REQUIRE((!o.scores_out && !o.logits_out) || (i0 >= 0 && i0 + n_steps <= o.out_stride), GVC_ERR_ARG,
+                "generate_scores: steps [%d, %d) do not fit the %d steps of a row of the output buffers", i0, i0 + n_steps, o.out_stride);
     GVC_REQUIRE(!uslots || 2 * B <= c->dm.max_slots, GVC_ERR_ARG, "generate_cfg: 2 * %d rows exceed the context's %d KV slots", B,
                 c->dm.max_slots);
     const int Brows = uslots ? 2 * B : B;      // rows of the decode step
@@ -1935,8 +1961,8 @@ static int generate_impl(gvc_gpt* c, const int32_t* slots, int32_t B, int32_t* i
     sc.latents_out = latents_out; sc.lat_stride = lat_stride; sc.d = c->dm.d_model;
     // per-step outputs (gvc_gpt_generate_scores): they travel in the call state the step graphs read, so the graphs are the same.  The
     // sampler of a guided call reads the guided scores as its logits: its raw rows are the conditional rows of the decode step
-    sc.scores_out = so.scores; sc.logits_out = so.logits; sc.out_stride = so.stride; sc.scores_warped = so.do_sample;
-    sc.logits_src = uslots && so.logits ? c->logits : nullptr;
+    sc.scores_out = o.scores_out; sc.logits_out = o.logits_out; sc.out_stride = o.out_stride; sc.scores_warped = o.do_sample;
+    sc.logits_src = uslots && o.logits_out ? c->logits : nullptr;
     if (bias) {
         // gvc_gpt_generate_bias: the struct travels by value into the device-resident call state in a launch of its own, ahead of the
         // begin launch (as the warpers do): nothing to allocate, and the caller's struct is free on return
@@ -1996,7 +2022,7 @@ static int generate_impl(gvc_gpt* c, const int32_t* slots, int32_t B, int32_t* i
     if (uslots) {
         // the unconditional rows behind the conditional ones: slot table, parked logits and latents, and the scale
         const int V = c->dm.vocab, d = c->dm.d_model;
-        if ((rc = launch_cfg_begin(c->gen_call->slots, uslots, B, scale, &c->gen_call->cfg_scale, c->logits, c->slot_logits, V, c->latent,
+        if ((rc = launch_cfg_begin(c->gen_call->slots, uslots, B, o.scale, &c->gen_call->cfg_scale, c->logits, c->slot_logits, V, c->latent,
                                    c->slot_latent, d, s)))
             return rc;
         if ((rc = replay_steps(n_steps, s, [&](int unroll, hipGraphExec_t* ge) { return cfg_graph(c, B, pl, unroll, ge); }))) return rc;
@@ -2020,8 +2046,8 @@ extern "C" int gvc_gpt_generate(gvc_gpt* c, const int32_t* slots, int32_t B, int
                                 int32_t* ids_len, int32_t* finished, const gvc_sample_params* p, int32_t i0,
                                 int32_t n_steps, int32_t max_keys, int32_t* tokens_out, int32_t tok_stride, float* latents_out,
                                 int32_t lat_stride, gvc_stream sv) {
-    return generate_impl(c, slots, B, ids, ids_stride, ids_len, finished, p, nullptr, nullptr, nullptr, nullptr, 0, nullptr, i0, n_steps, max_keys,
-                         tokens_out, tok_stride, latents_out, lat_stride, sv);
+    return generate_impl(c, slots, B, ids, ids_stride, ids_len, finished, p, i0, n_steps, max_keys, tokens_out, tok_stride, latents_out,
+                         lat_stride, sv);
 }
 
 extern "C" int gvc_gpt_generate_rows(gvc_gpt* c, const int32_t* slots, int32_t B, int32_t* ids, int32_t ids_stride, int32_t* ids_len,
@@ -2029,16 +2055,20 @@ extern "C" int gvc_gpt_generate_rows(gvc_gpt* c, const int32_t* slots, int32_t B
                                      int32_t n_steps, int32_t max_keys, int32_t* tokens_out, int32_t tok_stride, float* latents_out,
                                      int32_t lat_stride, gvc_stream sv) {
     GVC_REQUIRE(rows, GVC_ERR_ARG, "generate_rows: null rows");
-    return generate_impl(c, slots, B, ids, ids_stride, ids_len, finished, common, rows, nullptr, nullptr, nullptr, 0, nullptr, i0, n_steps, max_keys,
-                         tokens_out, tok_stride, latents_out, lat_stride, sv);
+    GenOptions o;
+    o.rows = rows;
+    return generate_impl(c, slots, B, ids, ids_stride, ids_len, finished, common, i0, n_steps, max_keys, tokens_out, tok_stride,
+                         latents_out, lat_stride, sv, o);
 }
 
 extern "C" int gvc_gpt_generate_proc(gvc_gpt* c, const int32_t* slots, int32_t B, int32_t* ids, int32_t ids_stride, int32_t* ids_len,
                                      int32_t* finished, const gvc_sample_params* p, const gvc_row_sampling* rows,
                                      const gvc_logits_processors* proc, int32_t i0, int32_t n_steps, int32_t max_keys, int32_t* tokens_out,
                                      int32_t tok_stride, float* latents_out, int32_t lat_stride, gvc_stream sv) {
-    return generate_impl(c, slots, B, ids, ids_stride, ids_len, finished, p, rows, proc, nullptr, nullptr, 0, nullptr, i0, n_steps, max_keys,
-                         tokens_out, tok_stride, latents_out, lat_stride, sv);
+    GenOptions o;
+    o.rows = rows; o.proc = proc;
+    return generate_impl(c, slots, B, ids, ids_stride, ids_len, finished, p, i0, n_steps, max_keys, tokens_out, tok_stride, latents_out,
+                         lat_stride, sv, o);
 }
 
 extern "C" int gvc_gpt_generate_proc_sets(gvc_gpt* c, const int32_t* slots, int32_t B, int32_t* ids, int32_t ids_stride, int32_t* ids_len,
@@ -2047,22 +2077,23 @@ extern "C" int gvc_gpt_generate_proc_sets(gvc_gpt* c, const int32_t* slots, int3
                                           int32_t n_steps, int32_t max_keys, int32_t* tokens_out, int32_t tok_stride, float* latents_out,
                                           int32_t lat_stride, gvc_stream sv) {
     GVC_REQUIRE(sets && set_of_row, GVC_ERR_ARG, "generate_proc_sets: null sets or set_of_row");
-    return generate_impl(c, slots, B, ids, ids_stride, ids_len, finished, p, rows, nullptr, sets, nullptr, n_sets, set_of_row, i0, n_steps, max_keys,
-                         tokens_out, tok_stride, latents_out, lat_stride, sv);
+    GenOptions o;
+    o.rows = rows; o.sets = sets; o.n_sets = n_sets; o.set_of_row = set_of_row;
+    return generate_impl(c, slots, B, ids, ids_stride, ids_len, finished, p, i0, n_steps, max_keys, tokens_out, tok_stride, latents_out,
+                         lat_stride, sv, o);
 }
 
+// (neither sets nor warpers: the call without processors)
 extern "C" int gvc_gpt_generate_warp(gvc_gpt* c, const int32_t* slots, int32_t B, int32_t* ids, int32_t ids_stride, int32_t* ids_len,
                                      int32_t* finished, const gvc_sample_params* p, const gvc_row_sampling* rows,
                                      const gvc_logits_processors* sets, const gvc_logits_warpers* warps, int32_t n_sets,
                                      const int32_t* set_of_row, int32_t i0, int32_t n_steps, int32_t max_keys, int32_t* tokens_out,
                                      int32_t tok_stride, float* latents_out, int32_t lat_stride, gvc_stream sv) {
     GVC_REQUIRE(B >= 1 && B <= kMaxSampleRows, GVC_ERR_ARG, "generate_warp: need 1..%d rows, got %d", kMaxSampleRows, B);
-    if (!warps && !sets)           // neither: the call without processors
-        return generate_impl(c, slots, B, ids, ids_stride, ids_len, finished, p, rows, nullptr, nullptr, nullptr, 0, nullptr, i0, n_steps,
-                             max_keys, tokens_out, tok_stride, latents_out, lat_stride, sv);
-    int32_t zeros[kMaxSampleRows] = {};
-    return generate_impl(c, slots, B, ids, ids_stride, ids_len, finished, p, rows, nullptr, sets, warps, n_sets,
-                         set_of_row ? set_of_row : zeros, i0, n_steps, max_keys, tokens_out, tok_stride, latents_out, lat_stride, sv);
+    GenOptions o;
+    o.rows = rows; o.sets = sets; o.warps = warps; o.n_sets = n_sets; o.set_of_row = set_of_row;
+    return generate_impl(c, slots, B, ids, ids_stride, ids_len, finished, p, i0, n_steps, max_keys, tokens_out, tok_stride, latents_out,
+                         lat_stride, sv, o);
 }
 
 // Guided generation (classifier-free guidance, HF guidance_scale): gvc_gpt_generate_warp's call over B items of two KV slots each
@@ -2071,68 +2102,43 @@ extern "C" int gvc_gpt_generate_cfg(gvc_gpt* c, const int32_t* slots, const int3
                                     const gvc_row_sampling* rows, const gvc_logits_processors* sets, const gvc_logits_warpers* warps,
                                     int32_t n_sets, const int32_t* set_of_row, int32_t i0, int32_t n_steps, int32_t max_keys,
                                     int32_t* tokens_out, int32_t tok_stride, float* latents_out, int32_t lat_stride, gvc_stream sv) {
-    GVC_REQUIRE(c && slots && uncond_slots, GVC_ERR_ARG, "generate_cfg: null argument");
-    GVC_REQUIRE(B >= 1 && 2 * B <= kMaxSampleRows, GVC_ERR_ARG, "generate_cfg: need 1..%d items, got %d", kMaxSampleRows / 2, B);
-    GVC_REQUIRE(scale == scale && fabsf(scale) <= 3.0e38f, GVC_ERR_ARG, "generate_cfg: the guidance scale is not finite");
-    GVC_REQUIRE(c->dm.vocab <= kCfgMaxVocab, GVC_ERR_UNSUPPORTED, "generate_cfg: vocab %d above %d", c->dm.vocab, kCfgMaxVocab);
-    int32_t zeros[kMaxSampleRows] = {};
-    const bool any = warps || sets;
-    return generate_impl(c, slots, B, ids, ids_stride, ids_len, finished, p, rows, nullptr, any ? sets : nullptr, any ? warps : nullptr,
-                         any ? n_sets : 0, any ? (set_of_row ? set_of_row : zeros) : nullptr, i0, n_steps, max_keys, tokens_out, tok_stride,
-                         latents_out, lat_stride, sv, uncond_slots, scale);
+    GenOptions o;
+    o.rows = rows; o.sets = sets; o.warps = warps; o.n_sets = n_sets; o.set_of_row = set_of_row;
+    o.uslots = uncond_slots; o.scale = scale;
+    const int rc = check_guided("generate_cfg", c, slots, B, true, o);
+    return rc ? rc : generate_impl(c, slots, B, ids, ids_stride, ids_len, finished, p, i0, n_steps, max_keys, tokens_out, tok_stride,
+                                   latents_out, lat_stride, sv, o);
 }
 
-// gvc_gpt_generate_warp (uncond_slots null) or gvc_gpt_generate_cfg that also stores, per row and step, the scores the draw was taken
-// from and / or the raw logits ([B][out_stride][vocab] fp32, either nullable).  do_sample: HF's flag, which only decides what the
-// scores hold (SampleCall::scores_warped); the tokens are those of the call without the buffers, bit for bit
-extern "C" int gvc_gpt_generate_scores(gvc_gpt* c, const int32_t* slots, const int32_t* uncond_slots, int32_t B, float scale, int32_t* ids,
-                                       int32_t ids_stride, int32_t* ids_len, int32_t* finished, const gvc_sample_params* p,
-                                       const gvc_row_sampling* rows, const gvc_logits_processors* sets, const gvc_logits_warpers* warps,
-                                       int32_t n_sets, const int32_t* set_of_row, int32_t i0, int32_t n_steps, int32_t max_keys,
-                                       int32_t* tokens_out, int32_t tok_stride, float* latents_out, int32_t lat_stride, float* scores_out,
-                                       float* logits_out, int32_t out_stride, int32_t do_sample, gvc_stream sv) {
-    GVC_REQUIRE(c && slots, GVC_ERR_ARG, "generate_scores: null argument");
-    GVC_REQUIRE(B >= 1 && (uncond_slots ? 2 : 1) * B <= kMaxSampleRows, GVC_ERR_ARG, "generate_scores: need 1..%d rows, got %d",
-                kMaxSampleRows / (uncond_slots ? 2 : 1), B);
-    GVC_REQUIRE(!uncond_slots || (scale == scale && fabsf(scale) <= 3.0e38f), GVC_ERR_ARG, "generate_scores: the guidance scale is not finite");
-    GVC_REQUIRE(!uncond_slots || c->dm.vocab <= kCfgMaxVocab, GVC_ERR_UNSUPPORTED, "generate_scores: vocab %d above %d", c->dm.vocab,
-                kCfgMaxVocab);
-    GVC_REQUIRE((!scores_out && !logits_out) || out_stride >= 1, GVC_ERR_ARG, "generate_scores: output buffers without a stride");
-    int32_t zeros[kMaxSampleRows] = {};
-    const bool any = warps || sets;
-    StepOutputs so;
-    so.scores = scores_out; so.logits = logits_out; so.stride = out_stride; so.do_sample = do_sample != 0;
-    return generate_impl(c, slots, B, ids, ids_stride, ids_len, finished, p, rows, nullptr, any ? sets : nullptr, any ? warps : nullptr,
-                         any ? n_sets : 0, any ? (set_of_row ? set_of_row : zeros) : nullptr, i0, n_steps, max_keys, tokens_out, tok_stride,
-                         latents_out, lat_stride, sv, uncond_slots, scale, so);
-}
-
-// gvc_gpt_generate_scores with the call's sequence bias / bad words / forced EOS / renormalised scores (include/genvc_hip.h:
-// gvc_logits_bias, HOST, nullable: null is exactly gvc_gpt_generate_scores)
+// gvc_gpt_generate_scores (bias null; uncond_slots null: gvc_gpt_generate_warp's call, else gvc_gpt_generate_cfg's) also stores, per row
+// and step, the scores the draw was taken from and / or the raw logits ([B][out_stride][vocab] fp32, either nullable).  do_sample: HF's
+// flag, which only decides what the scores hold (SampleCall::scores_warped); the tokens are those of the call without the buffers, bit
+// for bit.  gvc_gpt_generate_bias adds the call's sequence bias / bad words / forced EOS / renormalised scores (include/genvc_hip.h:
+// gvc_logits_bias, HOST, nullable: null is exactly gvc_gpt_generate_scores, under its name)
 extern "C" int gvc_gpt_generate_bias(gvc_gpt* c, const int32_t* slots, const int32_t* uncond_slots, int32_t B, float scale, int32_t* ids,
                                      int32_t ids_stride, int32_t* ids_len, int32_t* finished, const gvc_sample_params* p,
                                      const gvc_row_sampling* rows, const gvc_logits_processors* sets, const gvc_logits_warpers* warps,
                                      int32_t n_sets, const int32_t* set_of_row, const gvc_logits_bias* bias, int32_t i0, int32_t n_steps,
                                      int32_t max_keys, int32_t* tokens_out, int32_t tok_stride, float* latents_out, int32_t lat_stride,
                                      float* scores_out, float* logits_out, int32_t out_stride, int32_t do_sample, gvc_stream sv) {
-    if (!bias)
-        return gvc_gpt_generate_scores(c, slots, uncond_slots, B, scale, ids, ids_stride, ids_len, finished, p, rows, sets, warps, n_sets,
-                                       set_of_row, i0, n_steps, max_keys, tokens_out, tok_stride, latents_out, lat_stride, scores_out,
-                                       logits_out, out_stride, do_sample, sv);
-    GVC_REQUIRE(c && slots, GVC_ERR_ARG, "generate_bias: null argument");
-    GVC_REQUIRE(B >= 1 && (uncond_slots ? 2 : 1) * B <= kMaxSampleRows, GVC_ERR_ARG, "generate_bias: need 1..%d rows, got %d",
-                kMaxSampleRows / (uncond_slots ? 2 : 1), B);
-    GVC_REQUIRE(!uncond_slots || (scale == scale && fabsf(scale) <= 3.0e38f), GVC_ERR_ARG, "generate_bias: the guidance scale is not finite");
-    GVC_REQUIRE(!uncond_slots || c->dm.vocab <= kCfgMaxVocab, GVC_ERR_UNSUPPORTED, "generate_bias: vocab %d above %d", c->dm.vocab,
-                kCfgMaxVocab);
-    GVC_REQUIRE((!scores_out && !logits_out) || out_stride >= 1, GVC_ERR_ARG, "generate_bias: output buffers without a stride");
-    int32_t zeros[kMaxSampleRows] = {};
-    const bool any = warps || sets;
-    StepOutputs so;
-    so.scores = scores_out; so.logits = logits_out; so.stride = out_stride; so.do_sample = do_sample != 0;
-    return generate_impl(c, slots, B, ids, ids_stride, ids_len, finished, p, rows, nullptr, any ? sets : nullptr, any ? warps : nullptr,
-                         any ? n_sets : 0, any ? (set_of_row ? set_of_row : zeros) : nullptr, i0, n_steps, max_keys, tokens_out, tok_stride,
-                         latents_out, lat_stride, sv, uncond_slots, scale, so, bias);
+    GenOptions o;
+    o.rows = rows; o.sets = sets; o.warps = warps; o.n_sets = n_sets; o.set_of_row = set_of_row;
+    o.uslots = uncond_slots; o.scale = scale; o.bias = bias;
+    o.scores_out = scores_out; o.logits_out = logits_out; o.out_stride = out_stride; o.do_sample = do_sample != 0;
+    const int rc = check_guided(bias ? "generate_bias" : "generate_scores", c, slots, B, false, o);
+    return rc ? rc : generate_impl(c, slots, B, ids, ids_stride, ids_len, finished, p, i0, n_steps, max_keys, tokens_out, tok_stride,
+                                   latents_out, lat_stride, sv, o);
+}
+
+extern "C" int gvc_gpt_generate_scores(gvc_gpt* c, const int32_t* slots, const int32_t* uncond_slots, int32_t B, float scale, int32_t* ids,
+                                       int32_t ids_stride, int32_t* ids_len, int32_t* finished, const gvc_sample_params* p,
+                                       const gvc_row_sampling* rows, const gvc_logits_processors* sets, const gvc_logits_warpers* warps,
+                                       int32_t n_sets, const int32_t* set_of_row, int32_t i0, int32_t n_steps, int32_t max_keys,
+                                       int32_t* tokens_out, int32_t tok_stride, float* latents_out, int32_t lat_stride, float* scores_out,
+                                       float* logits_out, int32_t out_stride, int32_t do_sample, gvc_stream sv) {
+    return gvc_gpt_generate_bias(c, slots, uncond_slots, B, scale, ids, ids_stride, ids_len, finished, p, rows, sets, warps, n_sets,
+                                 set_of_row, nullptr, i0, n_steps, max_keys, tokens_out, tok_stride, latents_out, lat_stride, scores_out,
+                                 logits_out, out_stride, do_sample, sv);
 }
 
 // gvc_gpt_warmup for gvc_gpt_generate_cfg over B items: everything gvc_gpt_warmup(2B) prepares, and the guided step graphs of every

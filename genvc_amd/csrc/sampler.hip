@@ -685,6 +685,12 @@ int check_warp_sets(const gvc_logits_processors* sets, const gvc_logits_warpers*
     return GVC_OK;
 }
 
+static int launch_stage_proc(gvc_logits_processors* dst, const gvc_logits_processors* proc, hipStream_t s) {
+    hipLaunchKernelGGL(k_stage_proc, dim3(1), dim3(64), 0, s, dst, *proc);
+    GVC_LAUNCH_CHECK();
+    return GVC_OK;
+}
+
 int launch_stage_warps(gvc_logits_warpers* dst, const gvc_logits_warpers* warps, int n_sets, hipStream_t s) {
     WarpTable t;
     memset(&t, 0, sizeof(t));
@@ -712,6 +718,66 @@ int launch_sample_indirect(const SampleCall* sc_dev, int B, bool greedy, hipStre
     return GVC_OK;
 }
 
+// The one path behind gvc_sample_rows / _proc / _proc_sets / _warp / _bias.  Each entry checks its own arguments and passes what it has;
+// everything null here is simply absent from the launch.  What is present needs device memory for the duration of this call only: one
+// stream-ordered allocation, carved up, staged by value, and freed behind the sampler launch (no synchronisation; these context-free
+// entries serve tests and callers that sample themselves, not the generation loop).  `greedy` is what check_sample_rows found when rows
+// are given.  `proc` is the single by-value set of gvc_sample_proc; `sets` / `warps` are tables of n_sets indexed through set_of_row
+// (null: every row uses entry 0).
+struct SampleOptions {
+    const gvc_row_sampling* rows = nullptr;
+    bool greedy = false;
+    const gvc_logits_processors* proc = nullptr;
+    const gvc_logits_processors* sets = nullptr;
+    const gvc_logits_warpers* warps = nullptr;
+    int n_sets = 0;
+    const int32_t* set_of_row = nullptr;
+    const gvc_logits_bias* bias = nullptr;
+    bool index = false;          // stage set_of_row and hand it to the kernel (the entries that take sets or warpers)
+};
+
+static int sample_once(const float* logits, int B, int32_t* ids, int ids_stride, int32_t* ids_len, int32_t* finished,
+                       const gvc_sample_params& p, int step, int32_t* tok_out, const SampleOptions& o, hipStream_t s) {
+    static const int32_t zeros[kMaxSampleRows] = {};
+    const int32_t* sor = o.set_of_row ? o.set_of_row : zeros;
+    const size_t bias_bytes = o.bias ? sizeof(gvc_logits_bias) : 0;
+    const size_t proc_bytes = o.proc ? sizeof(gvc_logits_processors) : 0;
+    const size_t set_bytes = o.sets ? (size_t)o.n_sets * sizeof(gvc_logits_processors) : 0;
+    const size_t warp_bytes = o.warps ? (size_t)o.n_sets * sizeof(gvc_logits_warpers) : 0;
+    const size_t row_bytes = o.rows ? (size_t)B * sizeof(gvc_row_sampling) : 0;
+    const size_t sor_bytes = (size_t)B * sizeof(int32_t);          // (always there: the allocation is never empty)
+    char* d = nullptr;
+    GVC_CHECK_HIP(hipMallocAsync((void**)&d, bias_bytes + proc_bytes + set_bytes + warp_bytes + row_bytes + sor_bytes, s));
+    char* at = d;
+    auto carve = [&at](size_t bytes) { char* q = bytes ? at : nullptr; at += bytes; return q; };
+    gvc_logits_bias* d_bias = reinterpret_cast<gvc_logits_bias*>(carve(bias_bytes));
+    gvc_logits_processors* d_proc = reinterpret_cast<gvc_logits_processors*>(carve(proc_bytes));
+    gvc_logits_processors* d_sets = reinterpret_cast<gvc_logits_processors*>(carve(set_bytes));
+    gvc_logits_warpers* d_warps = reinterpret_cast<gvc_logits_warpers*>(carve(warp_bytes));
+    gvc_row_sampling* d_rows = reinterpret_cast<gvc_row_sampling*>(carve(row_bytes));
+    int32_t* d_sor = reinterpret_cast<int32_t*>(carve(sor_bytes));
+    int rc = GVC_OK;
+    if (o.bias) rc = launch_stage_bias(d_bias, o.bias, s);
+    if (rc == GVC_OK && o.proc) rc = launch_stage_proc(d_proc, o.proc, s);
+    if (rc == GVC_OK && o.sets) rc = launch_stage_proc_sets(d_sets, o.sets, o.n_sets, sor, B, s);
+    if (rc == GVC_OK && o.warps) rc = launch_stage_warps(d_warps, o.warps, o.n_sets, s);
+    if (rc == GVC_OK && o.index) rc = launch_stage_set_index(d_sor, sor, B, s);
+    if (rc == GVC_OK && o.rows) rc = launch_stage_rows(d_rows, o.rows, B, s);
+    if (rc == GVC_OK) {
+        SampleCall sc;
+        memset(&sc, 0, sizeof(sc));
+        sc.logits = logits; sc.B = B; sc.ids = ids; sc.ids_stride = ids_stride; sc.ids_len = ids_len;
+        sc.finished = finished; sc.p = p; sc.step = step; sc.tok_out = tok_out; sc.rows = d_rows; sc.proc = d_proc;
+        sc.proc_sets = d_sets; sc.set_of_row = o.index ? d_sor : nullptr; sc.warps = d_warps; sc.bias = d_bias;
+        if (o.rows) sc.p.top_k = o.greedy ? 1 : 0;          // (kernel choice only: every row's settings come from d_rows)
+        rc = launch_sample(sc, s);
+    }
+    const hipError_t e = hipFreeAsync(d, s);
+    if (rc) return rc;
+    GVC_CHECK_HIP(e);
+    return GVC_OK;
+}
+
 }  // namespace gvc
 
 extern "C" int gvc_sample(const float* logits, int32_t B, int32_t* ids, int32_t ids_stride, int32_t* ids_len,
@@ -729,27 +795,11 @@ extern "C" int gvc_sample_rows(const float* logits, int32_t B, int32_t* ids, int
                                int32_t* finished, const gvc_sample_params* common, const gvc_row_sampling* rows, int32_t step,
                                int32_t* tok_out, gvc_stream sv) {
     GVC_REQUIRE(logits && ids && ids_len && finished && common && tok_out && B >= 1, GVC_ERR_ARG, "gvc_sample_rows: bad argument");
-    bool greedy = false;
-    int rc = gvc::check_sample_rows(rows, B, common->vocab, &greedy);
+    gvc::SampleOptions o;
+    o.rows = rows;
+    const int rc = gvc::check_sample_rows(rows, B, common->vocab, &o.greedy);
     if (rc) return rc;
-    hipStream_t s = (hipStream_t)sv;
-    // the rows need device memory for the duration of this call only: a stream-ordered allocation, freed behind the sampler launch
-    // (no synchronisation; this context-free entry point serves tests and callers that sample themselves, not the generation loop)
-    gvc_row_sampling* d_rows = nullptr;
-    GVC_CHECK_HIP(hipMallocAsync((void**)&d_rows, (size_t)B * sizeof(gvc_row_sampling), s));
-    rc = gvc::launch_stage_rows(d_rows, rows, B, s);
-    if (rc == GVC_OK) {
-        gvc::SampleCall sc;
-        memset(&sc, 0, sizeof(sc));
-        sc.logits = logits; sc.B = B; sc.ids = ids; sc.ids_stride = ids_stride; sc.ids_len = ids_len;
-        sc.finished = finished; sc.p = *common; sc.step = step; sc.tok_out = tok_out; sc.rows = d_rows;
-        sc.p.top_k = greedy ? 1 : 0;          // (kernel choice only: every row's settings come from d_rows)
-        rc = gvc::launch_sample(sc, s);
-    }
-    const hipError_t e = hipFreeAsync(d_rows, s);
-    if (rc) return rc;
-    GVC_CHECK_HIP(e);
-    return GVC_OK;
+    return gvc::sample_once(logits, B, ids, ids_stride, ids_len, finished, *common, step, tok_out, o, (hipStream_t)sv);
 }
 
 extern "C" int gvc_sample_proc(const float* logits, int32_t B, int32_t* ids, int32_t ids_stride, int32_t* ids_len, int32_t* finished,
@@ -758,32 +808,10 @@ extern "C" int gvc_sample_proc(const float* logits, int32_t B, int32_t* ids, int
     GVC_REQUIRE(logits && ids && ids_len && finished && p && proc && tok_out && B >= 1, GVC_ERR_ARG, "gvc_sample_proc: bad argument");
     int rc = gvc::check_procs(*proc, p->vocab);
     if (rc) return rc;
-    bool greedy = p->top_k == 1;
-    if (rows && (rc = gvc::check_sample_rows(rows, B, p->vocab, &greedy))) return rc;
-    hipStream_t s = (hipStream_t)sv;
-    // the processors (and rows) need device memory for the duration of this call only: stream-ordered, freed behind the sampler launch
-    const size_t bytes = sizeof(gvc_logits_processors) + (rows ? (size_t)B * sizeof(gvc_row_sampling) : 0);
-    char* d = nullptr;
-    GVC_CHECK_HIP(hipMallocAsync((void**)&d, bytes, s));
-    gvc_logits_processors* d_proc = reinterpret_cast<gvc_logits_processors*>(d);
-    gvc_row_sampling* d_rows = rows ? reinterpret_cast<gvc_row_sampling*>(d + sizeof(gvc_logits_processors)) : nullptr;
-    hipLaunchKernelGGL(gvc::k_stage_proc, dim3(1), dim3(64), 0, s, d_proc, *proc);
-    hipError_t e = hipGetLastError();
-    rc = e == hipSuccess ? GVC_OK : GVC_ERR_HIP;
-    if (rc == GVC_OK && rows) rc = gvc::launch_stage_rows(d_rows, rows, B, s);
-    if (rc == GVC_OK) {
-        gvc::SampleCall sc;
-        memset(&sc, 0, sizeof(sc));
-        sc.logits = logits; sc.B = B; sc.ids = ids; sc.ids_stride = ids_stride; sc.ids_len = ids_len;
-        sc.finished = finished; sc.p = *p; sc.step = step; sc.tok_out = tok_out; sc.rows = d_rows; sc.proc = d_proc;
-        if (rows) sc.p.top_k = greedy ? 1 : 0;          // (kernel choice only: every row's settings come from d_rows)
-        rc = gvc::launch_sample(sc, s);
-    }
-    const hipError_t e2 = hipFreeAsync(d, s);
-    if (e != hipSuccess) gvc::set_error("gvc_sample_proc: staging launch failed: %s", hipGetErrorString(e));
-    if (rc) return rc;
-    GVC_CHECK_HIP(e2);
-    return GVC_OK;
+    gvc::SampleOptions o;
+    o.rows = rows; o.proc = proc;
+    if (rows && (rc = gvc::check_sample_rows(rows, B, p->vocab, &o.greedy))) return rc;
+    return gvc::sample_once(logits, B, ids, ids_stride, ids_len, finished, *p, step, tok_out, o, (hipStream_t)sv);
 }
 
 extern "C" int gvc_sample_proc_sets(const float* logits, int32_t B, int32_t* ids, int32_t ids_stride, int32_t* ids_len, int32_t* finished,
@@ -792,33 +820,10 @@ extern "C" int gvc_sample_proc_sets(const float* logits, int32_t B, int32_t* ids
     GVC_REQUIRE(logits && ids && ids_len && finished && p && tok_out && B >= 1, GVC_ERR_ARG, "gvc_sample_proc_sets: bad argument");
     int rc = gvc::check_proc_sets(sets, n_sets, set_of_row, B, p->vocab);
     if (rc) return rc;
-    bool greedy = p->top_k == 1;
-    if (rows && (rc = gvc::check_sample_rows(rows, B, p->vocab, &greedy))) return rc;
-    hipStream_t s = (hipStream_t)sv;
-    // sets, rows and indices need device memory for the duration of this call only: stream-ordered, freed behind the sampler launch
-    const size_t set_bytes = (size_t)n_sets * sizeof(gvc_logits_processors);
-    const size_t row_bytes = rows ? (size_t)B * sizeof(gvc_row_sampling) : 0;
-    char* d = nullptr;
-    GVC_CHECK_HIP(hipMallocAsync((void**)&d, set_bytes + row_bytes + (size_t)B * sizeof(int32_t), s));
-    gvc_logits_processors* d_sets = reinterpret_cast<gvc_logits_processors*>(d);
-    gvc_row_sampling* d_rows = rows ? reinterpret_cast<gvc_row_sampling*>(d + set_bytes) : nullptr;
-    int32_t* d_sor = reinterpret_cast<int32_t*>(d + set_bytes + row_bytes);
-    rc = gvc::launch_stage_proc_sets(d_sets, sets, n_sets, set_of_row, B, s);
-    if (rc == GVC_OK) rc = gvc::launch_stage_set_index(d_sor, set_of_row, B, s);
-    if (rc == GVC_OK && rows) rc = gvc::launch_stage_rows(d_rows, rows, B, s);
-    if (rc == GVC_OK) {
-        gvc::SampleCall sc;
-        memset(&sc, 0, sizeof(sc));
-        sc.logits = logits; sc.B = B; sc.ids = ids; sc.ids_stride = ids_stride; sc.ids_len = ids_len;
-        sc.finished = finished; sc.p = *p; sc.step = step; sc.tok_out = tok_out; sc.rows = d_rows;
-        sc.proc_sets = d_sets; sc.set_of_row = d_sor;
-        if (rows) sc.p.top_k = greedy ? 1 : 0;          // (kernel choice only: every row's settings come from d_rows)
-        rc = gvc::launch_sample(sc, s);
-    }
-    const hipError_t e = hipFreeAsync(d, s);
-    if (rc) return rc;
-    GVC_CHECK_HIP(e);
-    return GVC_OK;
+    gvc::SampleOptions o;
+    o.rows = rows; o.sets = sets; o.n_sets = n_sets; o.set_of_row = set_of_row; o.index = true;
+    if (rows && (rc = gvc::check_sample_rows(rows, B, p->vocab, &o.greedy))) return rc;
+    return gvc::sample_once(logits, B, ids, ids_stride, ids_len, finished, *p, step, tok_out, o, (hipStream_t)sv);
 }
 
 extern "C" int gvc_sample_warp(const float* logits, int32_t B, int32_t* ids, int32_t ids_stride, int32_t* ids_len, int32_t* finished,
@@ -828,38 +833,10 @@ extern "C" int gvc_sample_warp(const float* logits, int32_t B, int32_t* ids, int
     GVC_REQUIRE(logits && ids && ids_len && finished && p && tok_out && B >= 1, GVC_ERR_ARG, "gvc_sample_warp: bad argument");
     int rc = gvc::check_warp_sets(sets, warps, n_sets, set_of_row, B, p->vocab);
     if (rc) return rc;
-    bool greedy = p->top_k == 1;
-    if (rows && (rc = gvc::check_sample_rows(rows, B, p->vocab, &greedy))) return rc;
-    int32_t zeros[gvc::kMaxSampleRows] = {};
-    const int32_t* sor = set_of_row ? set_of_row : zeros;             // (null: every row uses entry 0)
-    hipStream_t s = (hipStream_t)sv;
-    // sets, warpers, rows and indices need device memory for the duration of this call only: stream-ordered, freed behind the launch
-    const size_t set_bytes = sets ? (size_t)n_sets * sizeof(gvc_logits_processors) : 0;
-    const size_t warp_bytes = warps ? (size_t)n_sets * sizeof(gvc_logits_warpers) : 0;
-    const size_t row_bytes = rows ? (size_t)B * sizeof(gvc_row_sampling) : 0;
-    char* d = nullptr;
-    GVC_CHECK_HIP(hipMallocAsync((void**)&d, set_bytes + warp_bytes + row_bytes + (size_t)B * sizeof(int32_t), s));
-    gvc_logits_processors* d_sets = sets ? reinterpret_cast<gvc_logits_processors*>(d) : nullptr;
-    gvc_logits_warpers* d_warps = warps ? reinterpret_cast<gvc_logits_warpers*>(d + set_bytes) : nullptr;
-    gvc_row_sampling* d_rows = rows ? reinterpret_cast<gvc_row_sampling*>(d + set_bytes + warp_bytes) : nullptr;
-    int32_t* d_sor = reinterpret_cast<int32_t*>(d + set_bytes + warp_bytes + row_bytes);
-    if (sets) rc = gvc::launch_stage_proc_sets(d_sets, sets, n_sets, sor, B, s);
-    if (rc == GVC_OK && warps) rc = gvc::launch_stage_warps(d_warps, warps, n_sets, s);
-    if (rc == GVC_OK) rc = gvc::launch_stage_set_index(d_sor, sor, B, s);
-    if (rc == GVC_OK && rows) rc = gvc::launch_stage_rows(d_rows, rows, B, s);
-    if (rc == GVC_OK) {
-        gvc::SampleCall sc;
-        memset(&sc, 0, sizeof(sc));
-        sc.logits = logits; sc.B = B; sc.ids = ids; sc.ids_stride = ids_stride; sc.ids_len = ids_len;
-        sc.finished = finished; sc.p = *p; sc.step = step; sc.tok_out = tok_out; sc.rows = d_rows;
-        sc.proc_sets = d_sets; sc.set_of_row = d_sor; sc.warps = d_warps;
-        if (rows) sc.p.top_k = greedy ? 1 : 0;          // (kernel choice only: every row's settings come from d_rows)
-        rc = gvc::launch_sample(sc, s);
-    }
-    const hipError_t e = hipFreeAsync(d, s);
-    if (rc) return rc;
-    GVC_CHECK_HIP(e);
-    return GVC_OK;
+    gvc::SampleOptions o;
+    o.rows = rows; o.sets = sets; o.warps = warps; o.n_sets = n_sets; o.set_of_row = set_of_row; o.index = true;
+    if (rows && (rc = gvc::check_sample_rows(rows, B, p->vocab, &o.greedy))) return rc;
+    return gvc::sample_once(logits, B, ids, ids_stride, ids_len, finished, *p, step, tok_out, o, (hipStream_t)sv);
 }
 
 extern "C" int gvc_sample_bias(const float* logits, int32_t B, int32_t* ids, int32_t ids_stride, int32_t* ids_len, int32_t* finished,
@@ -873,39 +850,8 @@ extern "C" int gvc_sample_bias(const float* logits, int32_t B, int32_t* ids, int
     int rc = GVC_OK;
     if (bias && (rc = gvc::check_bias(*bias, p->vocab))) return rc;
     if (any && (rc = gvc::check_warp_sets(sets, warps, n_sets, set_of_row, B, p->vocab))) return rc;
-    bool greedy = p->top_k == 1;
-    if (rows && (rc = gvc::check_sample_rows(rows, B, p->vocab, &greedy))) return rc;
-    int32_t zeros[gvc::kMaxSampleRows] = {};
-    const int32_t* sor = set_of_row ? set_of_row : zeros;             // (null: every row uses entry 0)
-    hipStream_t s = (hipStream_t)sv;
-    // everything needs device memory for the duration of this call only: stream-ordered, freed behind the sampler launch
-    const size_t bias_bytes = bias ? sizeof(gvc_logits_bias) : 0;
-    const size_t set_bytes = sets ? (size_t)n_sets * sizeof(gvc_logits_processors) : 0;
-    const size_t warp_bytes = warps ? (size_t)n_sets * sizeof(gvc_logits_warpers) : 0;
-    const size_t row_bytes = rows ? (size_t)B * sizeof(gvc_row_sampling) : 0;
-    char* d = nullptr;
-    GVC_CHECK_HIP(hipMallocAsync((void**)&d, bias_bytes + set_bytes + warp_bytes + row_bytes + (size_t)B * sizeof(int32_t), s));
-    gvc_logits_bias* d_bias = reinterpret_cast<gvc_logits_bias*>(d);
-    gvc_logits_processors* d_sets = sets ? reinterpret_cast<gvc_logits_processors*>(d + bias_bytes) : nullptr;
-    gvc_logits_warpers* d_warps = warps ? reinterpret_cast<gvc_logits_warpers*>(d + bias_bytes + set_bytes) : nullptr;
-    gvc_row_sampling* d_rows = rows ? reinterpret_cast<gvc_row_sampling*>(d + bias_bytes + set_bytes + warp_bytes) : nullptr;
-    int32_t* d_sor = reinterpret_cast<int32_t*>(d + bias_bytes + set_bytes + warp_bytes + row_bytes);
-    if (bias) rc = gvc::launch_stage_bias(d_bias, bias, s);
-    if (rc == GVC_OK && sets) rc = gvc::launch_stage_proc_sets(d_sets, sets, n_sets, sor, B, s);
-    if (rc == GVC_OK && warps) rc = gvc::launch_stage_warps(d_warps, warps, n_sets, s);
-    if (rc == GVC_OK && any) rc = gvc::launch_stage_set_index(d_sor, sor, B, s);
-    if (rc == GVC_OK && rows) rc = gvc::launch_stage_rows(d_rows, rows, B, s);
-    if (rc == GVC_OK) {
-        gvc::SampleCall sc;
-        memset(&sc, 0, sizeof(sc));
-        sc.logits = logits; sc.B = B; sc.ids = ids; sc.ids_stride = ids_stride; sc.ids_len = ids_len;
-        sc.finished = finished; sc.p = *p; sc.step = step; sc.tok_out = tok_out; sc.rows = d_rows;
-        sc.proc_sets = d_sets; sc.set_of_row = any ? d_sor : nullptr; sc.warps = d_warps; sc.bias = bias ? d_bias : nullptr;
-        if (rows) sc.p.top_k = greedy ? 1 : 0;          // (kernel choice only: every row's settings come from d_rows)
-        rc = gvc::launch_sample(sc, s);
-    }
-    const hipError_t e = hipFreeAsync(d, s);
-    if (rc) return rc;
-    GVC_CHECK_HIP(e);
-    return GVC_OK;
+    gvc::SampleOptions o;
+    o.rows = rows; o.sets = sets; o.warps = warps; o.n_sets = n_sets; o.set_of_row = set_of_row; o.bias = bias; o.index = any;
+    if (rows && (rc = gvc::check_sample_rows(rows, B, p->vocab, &o.greedy))) return rc;
+    return gvc::sample_once(logits, B, ids, ids_stride, ids_len, finished, *p, step, tok_out, o, (hipStream_t)sv);
 }

@@ -742,6 +742,76 @@ class GptEngine:
                                     stream()), "latents")
         return out
 
+    # ---- the sampler and generation entry points: families of C entries (include/genvc_hip.h), one marshalling path each ----------------
+    def _neutral_params(self):
+        """the common params of a call whose rows carry their own settings: eos and vocab, everything else neutral"""
+        return sample_params(dict(repetition_penalty=1.0, temperature=1.0, top_p=1.0, top_k=0), self.V, self.dims["stop_audio_token"])
+
+    def _lat_stride(self, tokens_out, latents_out):
+        """checks the output buffers of a generation call -> the row stride of latents_out in rows of d (0 without latents)"""
+        assert tokens_out.is_cuda and tokens_out.dtype == torch.int32 and tokens_out.stride(1) == 1
+        if latents_out is None:
+            return 0
+        assert latents_out.is_cuda and latents_out.dtype == torch.float32 and latents_out.stride(2) == 1
+        assert latents_out.stride(1) == self.d and latents_out.stride(0) % self.d == 0
+        return latents_out.stride(0) // self.d
+
+    _NO_SETS = object()          # (an entry without sets arguments; None is an entry called without sets)
+
+    def _sets_args(self, sets, B, warps=True):
+        """[sets, warps, n_sets, set_of_row] of a ProcessorSets / WarperSets over B rows, all null for None; warps=False: without them"""
+        if sets is not None and len(sets) != B:
+            raise ValueError(f"{len(sets)} set indices for {B} rows")
+        a = [None, None, 0, None] if sets is None else [sets.sets, getattr(sets, "warps", None), sets.n_sets, sets.set_of_row]
+        return a if warps else a[:1] + a[2:]
+
+    def _sample(self, name, logits, ids, ids_len, finished, params, step, rows, extra=(), sets=_NO_SETS, warps=True, need_rows=False):
+        """gvc_<name>(logits ... params, rows, *sets arguments, *extra, step, tok, stream) -> the tokens.  sets: the ProcessorSets /
+        WarperSets (or None) of the entries that take one, warps=False: of the entry without warpers; need_rows: rows are not optional"""
+        B = logits.shape[0]
+        if sets is not self._NO_SETS:
+            extra = self._sets_args(sets, B, warps) + list(extra)
+        tok = torch.empty(B, device=logits.device, dtype=torch.int32)
+        arr = _rows_arg(rows, B) if rows is not None or need_rows else None
+        check(getattr(lib(), "gvc_" + name)(ptr(_f32(logits)), B, ptr(_i32(ids)), ids.shape[1], ptr(_i32(ids_len)), ptr(_i32(finished)),
+                                            C.byref(params), arr, *extra, int(step), ptr(tok), stream()), name)
+        return tok
+
+    def _generate(self, name, label, slots, ids, ids_len, finished, params, i0, n_steps, tokens_out, latents_out, max_keys, rows,
+                  extra=(), sets=_NO_SETS, warps=True, need_rows=False, guided=None, outputs=None):
+        """gvc_gpt_<name>(ctx, slots, [uncond_slots,] B, [scale,] ids ... params, rows, *sets arguments, *extra, i0 ... lat_stride,
+        [outputs,] stream).  sets, warps, need_rows: as in _sample.
+        guided: (uncond_slots or None, scale) of the entries that take them; outputs: (scores_out, logits_out, do_sample) likewise.
+        With rows the common params are neutral, whatever the caller passed."""
+        self._join_side()
+        B = slots.shape[0]
+        head = [B]
+        if guided is not None:
+            uslots, scale = guided
+            if uslots is not None and uslots.shape[0] != B:
+                raise ValueError(f"{uslots.shape[0]} unconditional slots for {B} items")
+            head = [None if uslots is None else ptr(_i32(uslots)), B, float(scale)]
+        if sets is not self._NO_SETS:
+            extra = self._sets_args(sets, B, warps) + list(extra)
+        arr = _rows_arg(rows, B) if rows is not None or need_rows else None
+        lat_stride = self._lat_stride(tokens_out, latents_out)
+        tail = []
+        if outputs is not None:
+            out_stride = 0
+            for buf in outputs[:2]:
+                if buf is not None:
+                    if tuple(buf.shape[::2]) != (B, self.V) or (out_stride and buf.shape[1] != out_stride):
+                        raise ValueError(f"{name}: an output buffer of shape {tuple(buf.shape)} for {B} rows of {self.V} scores")
+                    _f32(buf)
+                    out_stride = int(buf.shape[1])
+            tail = [ptr(outputs[0]), ptr(outputs[1]), out_stride, int(bool(outputs[2]))]
+        if rows is not None:
+            params = self._neutral_params()
+        check(getattr(lib(), "gvc_gpt_" + name)(self._h, ptr(_i32(slots)), *head, ptr(_i32(ids)), ids.shape[1], ptr(_i32(ids_len)),
+                                                ptr(_i32(finished)), C.byref(params), arr, *extra, int(i0), int(n_steps), int(max_keys),
+                                                ptr(tokens_out), tokens_out.stride(0), ptr(latents_out), lat_stride, *tail, stream()),
+              label)
+
     def sample(self, logits, ids, ids_len, finished, params, step):
         B = logits.shape[0]
         tok = torch.empty(B, device=logits.device, dtype=torch.int32)
@@ -751,86 +821,44 @@ class GptEngine:
 
     def sample_proc(self, logits, ids, ids_len, finished, params, proc, step, rows=None):
         """sample() (rows None) or sample_rows() with the processors `proc` (logits_processors(); include/genvc_hip.h: gvc_sample_proc)"""
-        B = logits.shape[0]
-        arr = _rows_arg(rows, B) if rows is not None else None
-        tok = torch.empty(B, device=logits.device, dtype=torch.int32)
-        check(lib().gvc_sample_proc(ptr(_f32(logits)), B, ptr(_i32(ids)), ids.shape[1], ptr(_i32(ids_len)), ptr(_i32(finished)),
-                                    C.byref(params), arr, C.byref(proc), int(step), ptr(tok), stream()), "sample_proc")
-        return tok
+        return self._sample("sample_proc", logits, ids, ids_len, finished, params, step, rows, [C.byref(proc)])
 
     def generate(self, slots, ids, ids_len, finished, params, i0, n_steps, tokens_out, latents_out, max_keys=0, proc=None):
         """tokens_out [B, >= i0+n_steps] int32 and latents_out [B, >= i0+n_steps, d] may be column slices of larger
         buffers (row strides are passed on); step i of this call lands in column i0 + i.  max_keys: cached positions of the
         longest stream after the call (0: unknown, the width of `ids` is taken).  proc: the call's processors (logits_processors(),
         include/genvc_hip.h: gvc_gpt_generate_proc) or None."""
-        self._join_side()
-        B = slots.shape[0]
-        assert tokens_out.is_cuda and tokens_out.dtype == torch.int32 and tokens_out.stride(1) == 1
-        lat_stride = 0
-        if latents_out is not None:
-            assert latents_out.is_cuda and latents_out.dtype == torch.float32 and latents_out.stride(2) == 1
-            assert latents_out.stride(1) == self.d and latents_out.stride(0) % self.d == 0
-            lat_stride = latents_out.stride(0) // self.d
         if proc is not None:
-            check(lib().gvc_gpt_generate_proc(self._h, ptr(_i32(slots)), B, ptr(_i32(ids)), ids.shape[1], ptr(_i32(ids_len)),
-                                              ptr(_i32(finished)), C.byref(params), None, C.byref(proc), i0, n_steps, int(max_keys),
-                                              ptr(tokens_out), tokens_out.stride(0), ptr(latents_out), lat_stride, stream()),
-                  "generate_proc")
-            return
-        check(lib().gvc_gpt_generate(self._h, ptr(_i32(slots)), B, ptr(_i32(ids)), ids.shape[1], ptr(_i32(ids_len)),
+            return self._generate("generate_proc", "generate_proc", slots, ids, ids_len, finished, params, i0, n_steps, tokens_out,
+                                  latents_out, max_keys, None, [C.byref(proc)])
+        # (the plain call stays spelled out: it is the flagship loop's, once per group of steps)
+        self._join_side()
+        lat_stride = self._lat_stride(tokens_out, latents_out)
+        check(lib().gvc_gpt_generate(self._h, ptr(_i32(slots)), slots.shape[0], ptr(_i32(ids)), ids.shape[1], ptr(_i32(ids_len)),
                                      ptr(_i32(finished)), C.byref(params), i0, n_steps, int(max_keys), ptr(tokens_out),
                                      tokens_out.stride(0), ptr(latents_out), lat_stride, stream()), "generate")
 
     def sample_rows(self, logits, ids, ids_len, finished, rows, step):
         """sample() with per-row settings and RNG keys (include/genvc_hip.h: gvc_sample_rows): row b draws
         rng_uniform(seed_b, rng_step0_b + step, rng_row_b).  rows: see row_sampling()"""
-        B = logits.shape[0]
-        arr = _rows_arg(rows, B)
-        common = sample_params(dict(repetition_penalty=1.0, temperature=1.0, top_p=1.0, top_k=0), self.V, self.dims["stop_audio_token"])
-        tok = torch.empty(B, device=logits.device, dtype=torch.int32)
-        check(lib().gvc_sample_rows(ptr(_f32(logits)), B, ptr(_i32(ids)), ids.shape[1], ptr(_i32(ids_len)), ptr(_i32(finished)),
-                                    C.byref(common), arr, int(step), ptr(tok), stream()), "sample_rows")
-        return tok
+        return self._sample("sample_rows", logits, ids, ids_len, finished, self._neutral_params(), step, rows, need_rows=True)
 
     def generate_rows(self, slots, ids, ids_len, finished, rows, i0, n_steps, tokens_out, latents_out, max_keys=0, proc=None):
         """generate() with per-row settings and RNG keys (include/genvc_hip.h: gvc_gpt_generate_rows): tokens and latents of step i
         land in column i0 + i as in generate(); row b draws rng_uniform(seed_b, rng_step0_b + i, rng_row_b), so its tokens do not
         depend on which rows share the call.  rows: see row_sampling() (B entries, or a prepared gvc_row_sampling array)"""
-        self._join_side()
-        B = slots.shape[0]
-        arr = _rows_arg(rows, B)
-        assert tokens_out.is_cuda and tokens_out.dtype == torch.int32 and tokens_out.stride(1) == 1
-        lat_stride = 0
-        if latents_out is not None:
-            assert latents_out.is_cuda and latents_out.dtype == torch.float32 and latents_out.stride(2) == 1
-            assert latents_out.stride(1) == self.d and latents_out.stride(0) % self.d == 0
-            lat_stride = latents_out.stride(0) // self.d
-        common = sample_params(dict(repetition_penalty=1.0, temperature=1.0, top_p=1.0, top_k=0), self.V, self.dims["stop_audio_token"])
         if proc is not None:
-            check(lib().gvc_gpt_generate_proc(self._h, ptr(_i32(slots)), B, ptr(_i32(ids)), ids.shape[1], ptr(_i32(ids_len)),
-                                              ptr(_i32(finished)), C.byref(common), arr, C.byref(proc), int(i0), int(n_steps),
-                                              int(max_keys), ptr(tokens_out), tokens_out.stride(0), ptr(latents_out), lat_stride,
-                                              stream()), "generate_rows_proc")
-            return
-        check(lib().gvc_gpt_generate_rows(self._h, ptr(_i32(slots)), B, ptr(_i32(ids)), ids.shape[1], ptr(_i32(ids_len)),
-                                          ptr(_i32(finished)), C.byref(common), arr, int(i0), int(n_steps), int(max_keys),
-                                          ptr(tokens_out), tokens_out.stride(0), ptr(latents_out), lat_stride, stream()),
-              "generate_rows")
+            return self._generate("generate_proc", "generate_rows_proc", slots, ids, ids_len, finished, None, i0, n_steps, tokens_out,
+                                  latents_out, max_keys, rows, [C.byref(proc)], need_rows=True)
+        return self._generate("generate_rows", "generate_rows", slots, ids, ids_len, finished, None, i0, n_steps, tokens_out, latents_out,
+                              max_keys, rows, need_rows=True)
 
     def sample_proc_sets(self, logits, ids, ids_len, finished, params, sets, step, rows=None):
         """sample_proc() with per-row processor sets (logits_processor_sets(); include/genvc_hip.h: gvc_sample_proc_sets): row b uses
         sets.sets[sets.set_of_row[b]], none for -1.  rows: as in sample_proc (then params carries eos / vocab only)"""
         if isinstance(sets, WarperSets):
             return self.sample_warp(logits, ids, ids_len, finished, params, sets, step, rows=rows)
-        B = logits.shape[0]
-        if len(sets) != B:
-            raise ValueError(f"{len(sets)} set indices for {B} rows")
-        arr = _rows_arg(rows, B) if rows is not None else None
-        tok = torch.empty(B, device=logits.device, dtype=torch.int32)
-        check(lib().gvc_sample_proc_sets(ptr(_f32(logits)), B, ptr(_i32(ids)), ids.shape[1], ptr(_i32(ids_len)), ptr(_i32(finished)),
-                                         C.byref(params), arr, sets.sets, sets.n_sets, sets.set_of_row, int(step), ptr(tok), stream()),
-              "sample_proc_sets")
-        return tok
+        return self._sample("sample_proc_sets", logits, ids, ids_len, finished, params, step, rows, sets=sets, warps=False)
 
     def generate_proc_sets(self, slots, ids, ids_len, finished, params, sets, i0, n_steps, tokens_out, latents_out, max_keys=0, rows=None):
         """generate() (rows None: params for every row) or generate_rows() (rows set: params may be None) with per-row processor sets
@@ -840,57 +868,19 @@ class GptEngine:
         if isinstance(sets, WarperSets):
             return self.generate_warp(slots, ids, ids_len, finished, params, sets, i0, n_steps, tokens_out, latents_out, max_keys=max_keys,
                                       rows=rows)
-        self._join_side()
-        B = slots.shape[0]
-        if len(sets) != B:
-            raise ValueError(f"{len(sets)} set indices for {B} rows")
-        arr = _rows_arg(rows, B) if rows is not None else None
-        assert tokens_out.is_cuda and tokens_out.dtype == torch.int32 and tokens_out.stride(1) == 1
-        lat_stride = 0
-        if latents_out is not None:
-            assert latents_out.is_cuda and latents_out.dtype == torch.float32 and latents_out.stride(2) == 1
-            assert latents_out.stride(1) == self.d and latents_out.stride(0) % self.d == 0
-            lat_stride = latents_out.stride(0) // self.d
-        if rows is not None:
-            params = sample_params(dict(repetition_penalty=1.0, temperature=1.0, top_p=1.0, top_k=0), self.V, self.dims["stop_audio_token"])
-        check(lib().gvc_gpt_generate_proc_sets(self._h, ptr(_i32(slots)), B, ptr(_i32(ids)), ids.shape[1], ptr(_i32(ids_len)),
-                                               ptr(_i32(finished)), C.byref(params), arr, sets.sets, sets.n_sets, sets.set_of_row,
-                                               int(i0), int(n_steps), int(max_keys), ptr(tokens_out), tokens_out.stride(0),
-                                               ptr(latents_out), lat_stride, stream()), "generate_proc_sets")
+        return self._generate("generate_proc_sets", "generate_proc_sets", slots, ids, ids_len, finished, params, i0, n_steps, tokens_out,
+                              latents_out, max_keys, rows, sets=sets, warps=False)
 
     def sample_warp(self, logits, ids, ids_len, finished, params, sets, step, rows=None):
         """sample_proc_sets() with the typical / epsilon / eta warpers of a WarperSets (include/genvc_hip.h: gvc_sample_warp)"""
-        B = logits.shape[0]
-        if len(sets) != B:
-            raise ValueError(f"{len(sets)} set indices for {B} rows")
-        arr = _rows_arg(rows, B) if rows is not None else None
-        tok = torch.empty(B, device=logits.device, dtype=torch.int32)
-        check(lib().gvc_sample_warp(ptr(_f32(logits)), B, ptr(_i32(ids)), ids.shape[1], ptr(_i32(ids_len)), ptr(_i32(finished)),
-                                    C.byref(params), arr, sets.sets, sets.warps, sets.n_sets, sets.set_of_row, int(step), ptr(tok),
-                                    stream()), "sample_warp")
-        return tok
+        return self._sample("sample_warp", logits, ids, ids_len, finished, params, step, rows, sets=sets)
 
     def generate_warp(self, slots, ids, ids_len, finished, params, sets, i0, n_steps, tokens_out, latents_out, max_keys=0, rows=None):
         """generate_proc_sets() with the warpers of a WarperSets (logits_sets() / WarperSets.one(); include/genvc_hip.h:
         gvc_gpt_generate_warp): row b uses entry sets.set_of_row[b], none for -1.  The warpers travel with the call in one staging
         launch: the step graphs are generate()'s, and nothing is allocated or captured once warm."""
-        self._join_side()
-        B = slots.shape[0]
-        if len(sets) != B:
-            raise ValueError(f"{len(sets)} set indices for {B} rows")
-        arr = _rows_arg(rows, B) if rows is not None else None
-        assert tokens_out.is_cuda and tokens_out.dtype == torch.int32 and tokens_out.stride(1) == 1
-        lat_stride = 0
-        if latents_out is not None:
-            assert latents_out.is_cuda and latents_out.dtype == torch.float32 and latents_out.stride(2) == 1
-            assert latents_out.stride(1) == self.d and latents_out.stride(0) % self.d == 0
-            lat_stride = latents_out.stride(0) // self.d
-        if rows is not None:
-            params = sample_params(dict(repetition_penalty=1.0, temperature=1.0, top_p=1.0, top_k=0), self.V, self.dims["stop_audio_token"])
-        check(lib().gvc_gpt_generate_warp(self._h, ptr(_i32(slots)), B, ptr(_i32(ids)), ids.shape[1], ptr(_i32(ids_len)),
-                                          ptr(_i32(finished)), C.byref(params), arr, sets.sets, sets.warps, sets.n_sets, sets.set_of_row,
-                                          int(i0), int(n_steps), int(max_keys), ptr(tokens_out), tokens_out.stride(0), ptr(latents_out),
-                                          lat_stride, stream()), "generate_warp")
+        return self._generate("generate_warp", "generate_warp", slots, ids, ids_len, finished, params, i0, n_steps, tokens_out, latents_out,
+                              max_keys, rows, sets=sets)
 
     def cfg_guide(self, logits_cond, logits_uncond, scale):
         """HF's classifier-free guidance combine on [B, V] rows (include/genvc_hip.h: gvc_cfg_guide):
@@ -907,27 +897,8 @@ class GptEngine:
         (conditional prompt) and uncond_slots[b] (unconditional prompt), both prefilled; every step samples item b from
         scale * (lsm(cond) - lsm(uncond)) + lsm(uncond) and feeds the token to both slots.  sets: a WarperSets over the B items, or
         None.  ids / rows / tokens_out / latents_out have B rows: the conditional ones."""
-        self._join_side()
-        B = slots.shape[0]
-        if uncond_slots.shape[0] != B:
-            raise ValueError(f"{uncond_slots.shape[0]} unconditional slots for {B} items")
-        if sets is not None and len(sets) != B:
-            raise ValueError(f"{len(sets)} set indices for {B} rows")
-        arr = _rows_arg(rows, B) if rows is not None else None
-        assert tokens_out.is_cuda and tokens_out.dtype == torch.int32 and tokens_out.stride(1) == 1
-        lat_stride = 0
-        if latents_out is not None:
-            assert latents_out.is_cuda and latents_out.dtype == torch.float32 and latents_out.stride(2) == 1
-            assert latents_out.stride(1) == self.d and latents_out.stride(0) % self.d == 0
-            lat_stride = latents_out.stride(0) // self.d
-        if rows is not None:
-            params = sample_params(dict(repetition_penalty=1.0, temperature=1.0, top_p=1.0, top_k=0), self.V, self.dims["stop_audio_token"])
-        check(lib().gvc_gpt_generate_cfg(self._h, ptr(_i32(slots)), ptr(_i32(uncond_slots)), B, float(scale), ptr(_i32(ids)), ids.shape[1],
-                                         ptr(_i32(ids_len)), ptr(_i32(finished)), C.byref(params), arr,
-                                         sets.sets if sets is not None else None, sets.warps if sets is not None else None,
-                                         sets.n_sets if sets is not None else 0, sets.set_of_row if sets is not None else None,
-                                         int(i0), int(n_steps), int(max_keys), ptr(tokens_out), tokens_out.stride(0), ptr(latents_out),
-                                         lat_stride, stream()), "generate_cfg")
+        return self._generate("generate_cfg", "generate_cfg", slots, ids, ids_len, finished, params, i0, n_steps, tokens_out, latents_out,
+                              max_keys, rows, sets=sets, guided=(uncond_slots, scale))
 
     def generate_scores(self, slots, uncond_slots, scale, ids, ids_len, finished, params, sets, i0, n_steps, tokens_out, latents_out,
                         scores_out=None, logits_out=None, do_sample=True, max_keys=0, rows=None):
@@ -935,86 +906,54 @@ class GptEngine:
         gvc_gpt_generate_scores): scores_out / logits_out fp32 [B, >= i0 + n_steps, V], dense, either may be None; step i of the call
         lands at [:, i0 + i].  do_sample is HF's flag and decides only what the scores hold: with it the warped row (dropped entries
         -inf), without it the full processed row before any temperature.  sets: a WarperSets over the B rows, or None."""
-        self._join_side()
-        B = slots.shape[0]
-        if uncond_slots is not None and uncond_slots.shape[0] != B:
-            raise ValueError(f"{uncond_slots.shape[0]} unconditional slots for {B} items")
-        if sets is not None and len(sets) != B:
-            raise ValueError(f"{len(sets)} set indices for {B} rows")
-        arr = _rows_arg(rows, B) if rows is not None else None
-        assert tokens_out.is_cuda and tokens_out.dtype == torch.int32 and tokens_out.stride(1) == 1
-        lat_stride = 0
-        if latents_out is not None:
-            assert latents_out.is_cuda and latents_out.dtype == torch.float32 and latents_out.stride(2) == 1
-            assert latents_out.stride(1) == self.d and latents_out.stride(0) % self.d == 0
-            lat_stride = latents_out.stride(0) // self.d
-        out_stride = 0
-        for buf in (scores_out, logits_out):
-            if buf is not None:
-                if tuple(buf.shape[::2]) != (B, self.V) or (out_stride and buf.shape[1] != out_stride):
-                    raise ValueError(f"generate_scores: an output buffer of shape {tuple(buf.shape)} for {B} rows of {self.V} scores")
-                _f32(buf)
-                out_stride = int(buf.shape[1])
-        if rows is not None:
-            params = sample_params(dict(repetition_penalty=1.0, temperature=1.0, top_p=1.0, top_k=0), self.V, self.dims["stop_audio_token"])
-        check(lib().gvc_gpt_generate_scores(self._h, ptr(_i32(slots)), None if uncond_slots is None else ptr(_i32(uncond_slots)), B,
-                                            float(scale), ptr(_i32(ids)), ids.shape[1], ptr(_i32(ids_len)), ptr(_i32(finished)),
-                                            C.byref(params), arr, sets.sets if sets is not None else None,
-                                            sets.warps if sets is not None else None, sets.n_sets if sets is not None else 0,
-                                            sets.set_of_row if sets is not None else None, int(i0), int(n_steps), int(max_keys),
-                                            ptr(tokens_out), tokens_out.stride(0), ptr(latents_out), lat_stride, ptr(scores_out),
-                                            ptr(logits_out), out_stride, int(bool(do_sample)), stream()), "generate_scores")
+        return self._generate("generate_scores", "generate_scores", slots, ids, ids_len, finished, params, i0, n_steps, tokens_out,
+                              latents_out, max_keys, rows, sets=sets, guided=(uncond_slots, scale),
+                              outputs=(scores_out, logits_out, do_sample))
 
     def sample_bias(self, logits, ids, ids_len, finished, params, bias, step, sets=None, rows=None):
         """sample_warp() with the call's sequence bias / bad words / forced EOS (a _lib.LogitsBias from logits_bias(), or None;
         include/genvc_hip.h: gvc_sample_bias).  sets: a WarperSets / ProcessorSets over the B rows, or None for no processors"""
-        B = logits.shape[0]
-        if sets is not None and len(sets) != B:
-            raise ValueError(f"{len(sets)} set indices for {B} rows")
-        arr = _rows_arg(rows, B) if rows is not None else None
-        tok = torch.empty(B, device=logits.device, dtype=torch.int32)
-        check(lib().gvc_sample_bias(ptr(_f32(logits)), B, ptr(_i32(ids)), ids.shape[1], ptr(_i32(ids_len)), ptr(_i32(finished)),
-                                    C.byref(params), arr, sets.sets if sets is not None else None,
-                                    getattr(sets, "warps", None) if sets is not None else None, sets.n_sets if sets is not None else 0,
-                                    sets.set_of_row if sets is not None else None, None if bias is None else C.byref(bias), int(step),
-                                    ptr(tok), stream()), "sample_bias")
-        return tok
+        return self._sample("sample_bias", logits, ids, ids_len, finished, params, step, rows,
+                            [None if bias is None else C.byref(bias)], sets=sets)
 
     def generate_bias(self, slots, uncond_slots, scale, ids, ids_len, finished, params, sets, bias, i0, n_steps, tokens_out, latents_out,
                       scores_out=None, logits_out=None, do_sample=True, max_keys=0, rows=None):
         """generate_scores() with the call's sequence bias / bad words / forced EOS / renormalised scores (a _lib.LogitsBias from
         logits_bias(); include/genvc_hip.h: gvc_gpt_generate_bias).  The struct travels with the call in one staging launch: the step
         graphs are generate()'s, and nothing is allocated or captured once warm.  bias None is generate_scores()."""
-        self._join_side()
-        B = slots.shape[0]
-        if uncond_slots is not None and uncond_slots.shape[0] != B:
-            raise ValueError(f"{uncond_slots.shape[0]} unconditional slots for {B} items")
-        if sets is not None and len(sets) != B:
-            raise ValueError(f"{len(sets)} set indices for {B} rows")
-        arr = _rows_arg(rows, B) if rows is not None else None
-        assert tokens_out.is_cuda and tokens_out.dtype == torch.int32 and tokens_out.stride(1) == 1
-        lat_stride = 0
-        if latents_out is not None:
-            assert latents_out.is_cuda and latents_out.dtype == torch.float32 and latents_out.stride(2) == 1
-            assert latents_out.stride(1) == self.d and latents_out.stride(0) % self.d == 0
-            lat_stride = latents_out.stride(0) // self.d
-        out_stride = 0
-        for buf in (scores_out, logits_out):
-            if buf is not None:
-                if tuple(buf.shape[::2]) != (B, self.V) or (out_stride and buf.shape[1] != out_stride):
-                    raise ValueError(f"generate_bias: an output buffer of shape {tuple(buf.shape)} for {B} rows of {self.V} scores")
-                _f32(buf)
-                out_stride = int(buf.shape[1])
+        return self._generate("generate_bias", "generate_bias", slots, ids, ids_len, finished, params, i0, n_steps, tokens_out, latents_out,
+                              max_keys, rows, [None if bias is None else C.byref(bias)], sets=sets,
+                              guided=(uncond_slots, scale), outputs=(scores_out, logits_out, do_sample))
+
+    def generate_call(self, slots, ids, ids_len, finished, params, i0, n_steps, tokens_out, latents_out, max_keys=0, rows=None, proc=None,
+                      sets=None, bias=None, uncond_slots=None, scale=1.0, scores_out=None, logits_out=None, do_sample=True):
+        """The generation call for whatever options a loop has, through the narrowest entry that carries them: generate_bias (bias),
+        generate_scores (score / logit buffers), generate_cfg (uncond_slots), generate_proc_sets / generate_warp (sets), generate_rows
+        (rows), else generate.  proc: the call-wide processors; sets (a ProcessorSets / WarperSets) supersedes it, and the entries
+        without a `proc` argument take it as one call-wide entry.  A loop makes this one call instead of choosing.  It goes through
+        the public methods, so a patched or overridden entry still sees its calls, and an engine stand-in that has no generate_call
+        of its own (layers.gpt._generate_call) needs only the entries its options reach."""
+        wide = bias is not None or scores_out is not None or logits_out is not None or uncond_slots is not None
+        if wide and sets is None and proc is not None:
+            sets = WarperSets.one(proc, None, slots.shape[0])
+        pk = {} if proc is None or sets is not None else {"proc": proc}
+        if bias is not None:
+            return self.generate_bias(slots, uncond_slots, scale, ids, ids_len, finished, params, sets, bias, i0, n_steps, tokens_out,
+                                      latents_out, scores_out=scores_out, logits_out=logits_out, do_sample=do_sample, max_keys=max_keys,
+                                      rows=rows)
+        if scores_out is not None or logits_out is not None:
+            return self.generate_scores(slots, uncond_slots, scale, ids, ids_len, finished, params, sets, i0, n_steps, tokens_out,
+                                        latents_out, scores_out=scores_out, logits_out=logits_out, do_sample=do_sample, max_keys=max_keys,
+                                        rows=rows)
+        if uncond_slots is not None:
+            return self.generate_cfg(slots, uncond_slots, scale, ids, ids_len, finished, params, sets, i0, n_steps, tokens_out, latents_out,
+                                     max_keys=max_keys, rows=rows)
+        if sets is not None:
+            return self.generate_proc_sets(slots, ids, ids_len, finished, params, sets, i0, n_steps, tokens_out, latents_out,
+                                           max_keys=max_keys, rows=rows)
         if rows is not None:
-            params = sample_params(dict(repetition_penalty=1.0, temperature=1.0, top_p=1.0, top_k=0), self.V, self.dims["stop_audio_token"])
-        check(lib().gvc_gpt_generate_bias(self._h, ptr(_i32(slots)), None if uncond_slots is None else ptr(_i32(uncond_slots)), B,
-                                          float(scale), ptr(_i32(ids)), ids.shape[1], ptr(_i32(ids_len)), ptr(_i32(finished)),
-                                          C.byref(params), arr, sets.sets if sets is not None else None,
-                                          getattr(sets, "warps", None) if sets is not None else None,
-                                          sets.n_sets if sets is not None else 0, sets.set_of_row if sets is not None else None,
-                                          None if bias is None else C.byref(bias), int(i0), int(n_steps), int(max_keys),
-                                          ptr(tokens_out), tokens_out.stride(0), ptr(latents_out), lat_stride, ptr(scores_out),
-                                          ptr(logits_out), out_stride, int(bool(do_sample)), stream()), "generate_bias")
+            return self.generate_rows(slots, ids, ids_len, finished, rows, i0, n_steps, tokens_out, latents_out, max_keys=max_keys, **pk)
+        return self.generate(slots, ids, ids_len, finished, params, i0, n_steps, tokens_out, latents_out, max_keys=max_keys, **pk)
 
     def transition_scores(self, scores, tokens, normalize=False):
         """HF's compute_transition_scores without beams on the device (include/genvc_hip.h: gvc_transition_scores): scores fp32

@@ -248,6 +248,24 @@ def _no_bias(kw, where):
                                   "num_return_sequences, guidance_scale), one call-wide set per call")
 
 
+def _plain_rows_only(kw, where, beams=True):
+    """the paths that decode one sampled or greedy row per stream and return bare tokens (grouped, rolling, streaming, sessions):
+    every mode only GPT.generate serves raises, naming the path `where`.  beams=False: the caller has no num_beams to refuse"""
+    if beams:
+        _no_beams(kw, where)
+    _no_contrastive(kw, where)
+    _single_return(kw, where)
+    _no_guidance(kw, where)
+    _no_outputs(kw, where)
+    _no_bias(kw, f"the {where} path")
+
+
+def _generate_call(eng, *args, **kw):
+    """eng.generate_call(...); an engine stand-in without one gets GptEngine's, over the entries it does have"""
+    fn = getattr(eng, "generate_call", None)
+    return fn(*args, **kw) if fn is not None else GptEngine.generate_call(eng, *args, **kw)
+
+
 def _any_proc(kw):
     """a processor kwarg is given (engine.logits_processors may still find every one at its default)"""
     return any(kw.get(k) is not None for k in PROC_KWARGS)
@@ -477,34 +495,14 @@ class GPT(nn.Module):
         n = min(n, st["max_new"] - st["done"])
         if n > 0:
             # the cache holds n0 positions after the prefill and one more per step: the library picks its decode kernels for the
-            # context length this call reaches (not for the 602-token cap the ids rows are sized for)
-            if st.get("bias") is not None:
-                # sequence_bias / bad_words_ids / forced_eos_token_id / renormalize_logits: the same steps, the call state also carrying
-                # the bias struct (and the buffers of output_scores / output_logits, and the unconditional slots, when the call has them)
-                sets = st["warp"] if st["warp"] is not None else (None if st["proc"] is None else WarperSets.one(st["proc"], None, st["B"]))
-                self.engine.generate_bias(st["slots"], st.get("uncond_slots"), st.get("guidance_scale", 1.0), st["ids"], st["ids_len"],
-                                          st["finished"], st["params"], sets, st["bias"], st["done"], n, st["toks"], st["lats"],
-                                          scores_out=st.get("scores"), logits_out=st.get("raw_logits"), do_sample=st.get("do_sample", True),
-                                          max_keys=max(st["n0"], st.get("n0_uncond", 0)) + st["done"] + n)
-            elif st.get("scores") is not None or st.get("raw_logits") is not None:
-                # output_scores / output_logits: the same steps, the call state also naming the buffers the sampler stores its rows in
-                sets = st["warp"] if st["warp"] is not None else (None if st["proc"] is None else WarperSets.one(st["proc"], None, st["B"]))
-                self.engine.generate_scores(st["slots"], st.get("uncond_slots"), st.get("guidance_scale", 1.0), st["ids"], st["ids_len"],
-                                            st["finished"], st["params"], sets, st["done"], n, st["toks"], st["lats"],
-                                            scores_out=st.get("scores"), logits_out=st.get("raw_logits"), do_sample=st["do_sample"],
-                                            max_keys=max(st["n0"], st.get("n0_uncond", 0)) + st["done"] + n)
-            elif st.get("uncond_slots") is not None:
-                # classifier-free guidance: the unconditional slots decode the same tokens; the longer of the two contexts bounds the keys
-                sets = st["warp"] if st["warp"] is not None else (None if st["proc"] is None else WarperSets.one(st["proc"], None, st["B"]))
-                self.engine.generate_cfg(st["slots"], st["uncond_slots"], st["guidance_scale"], st["ids"], st["ids_len"], st["finished"],
-                                         st["params"], sets, st["done"], n, st["toks"], st["lats"],
-                                         max_keys=max(st["n0"], st["n0_uncond"]) + st["done"] + n)
-            elif st["warp"] is not None:
-                self.engine.generate_warp(st["slots"], st["ids"], st["ids_len"], st["finished"], st["params"], st["warp"], st["done"], n,
-                                          st["toks"], st["lats"], max_keys=st["n0"] + st["done"] + n)
-            else:
-                self.engine.generate(st["slots"], st["ids"], st["ids_len"], st["finished"], st["params"], st["done"], n,
-                                     st["toks"], st["lats"], max_keys=st["n0"] + st["done"] + n, **_proc_arg(st["proc"]))
+            # context length this call reaches (not for the 602-token cap the ids rows are sized for); under guidance the longer of the
+            # two contexts bounds the keys.  One call whatever the loop state holds (processors, warpers, sequence bias, the buffers of
+            # output_scores / output_logits, unconditional slots): generate_call picks the entry, on the engine or a stand-in for it
+            _generate_call(self.engine, st["slots"], st["ids"], st["ids_len"], st["finished"], st["params"], st["done"], n, st["toks"],
+                           st["lats"], max_keys=max(st["n0"], st.get("n0_uncond", 0)) + st["done"] + n, proc=st["proc"],
+                           sets=st["warp"], bias=st.get("bias"), uncond_slots=st.get("uncond_slots"),
+                           scale=st.get("guidance_scale", 1.0), scores_out=st.get("scores"), logits_out=st.get("raw_logits"),
+                           do_sample=st.get("do_sample", True))
             st["done"] += n
         end = bool(st["finished"].all().item()) or st["done"] >= st["max_new"]
         self.engine.health()          # (the .item() above synchronised: a hand-off timeout of these steps surfaces here, not a call later)
@@ -610,15 +608,17 @@ class GPT(nn.Module):
             while not self._advance(st, group):
                 pass
             return st
-        st = self._recovering(int(fake.shape[0]), run)
-        # the reference loop stops at the step where the last row emits 1025
+        return self._finish(self._recovering(int(fake.shape[0]), run), generate_kwargs, N)
+
+    def _finish(self, st, kw, N=1):
+        """what a finished sampler loop returns: the reference loop stops at the step where the last row emits 1025"""
         toks = st["toks"][:, :st["done"]].long()
         n = self._stop_len(toks)
         self.last_latents = st["lats"][:, :n]
         self.last_sequence_logprobs = self.last_sequence_lengths = None
         if N > 1:
             self.last_sequence_logprobs, self.last_sequence_lengths = self.sequence_logprobs(toks[:, :n], self.last_latents)
-        return self._result(toks[:, :n], generate_kwargs, st, n)
+        return self._result(toks[:, :n], kw, st, n)
 
     def _generate_guided(self, cond_latents, text_inputs, scale, generate_kwargs):
         """HF generate(guidance_scale=s, negative_prompt_ids=...) semantics on a prefix-embedded model (include/genvc_hip.h:
@@ -677,12 +677,7 @@ class GPT(nn.Module):
             while not self._advance(st, group):
                 pass
             return st
-        st = self._recovering(2 * B, run)
-        toks = st["toks"][:, :st["done"]].long()
-        n = self._stop_len(toks)
-        self.last_latents = st["lats"][:, :n]
-        self.last_sequence_logprobs = self.last_sequence_lengths = None
-        return self._result(toks[:, :n], kw, st, n)
+        return self._finish(self._recovering(2 * B, run), kw)
 
     @torch.inference_mode()
     def sequence_logprobs(self, tokens, latents):
@@ -806,12 +801,7 @@ class GPT(nn.Module):
         gets what generate(**its merged kwargs) returns for it, the joint decode giving every row its group's set
         (gvc_gpt_generate_proc_sets, or gvc_gpt_generate_warp when a warper is on).
         Returns a list of int64 [B_i, n_i] (reference gpt.py:594-609 per group)."""
-        _no_beams(generate_kwargs, "grouped (generate_groups)")
-        _no_contrastive(generate_kwargs, "grouped (generate_groups)")
-        _single_return(generate_kwargs, "grouped (generate_groups)")
-        _no_guidance(generate_kwargs, "grouped (generate_groups)")
-        _no_outputs(generate_kwargs, "grouped (generate_groups)")
-        _no_bias(generate_kwargs, "the grouped (generate_groups) path")
+        _plain_rows_only(generate_kwargs, "grouped (generate_groups)")
         kw = dict(generate_kwargs)
         gkw = None
         if group_kwargs is not None:
@@ -912,21 +902,12 @@ class GPT(nn.Module):
                 sets = logits_sets([gkw[g] for g in live_groups for _ in range(spans[g][1] - spans[g][0])],
                                    [n0s[g] for g in live_groups for _ in range(spans[g][1] - spans[g][0])],
                                    self.num_audio_tokens, sampling=seeds is not None)
-            if sets is not None:
-                rows = None
-                if seeds is not None:
-                    rows = [dict(rs, seed=seeds[g], rng_row=r, rng_step0=done) for g in live_groups
-                            for r in range(spans[g][1] - spans[g][0])]
-                self.engine.generate_proc_sets(slots[:live], ids[:live], ids_len[:live], finished[:live], params, sets, done, n, toks[:live],
-                                               lats[:live], max_keys=mk, rows=rows)
-            elif seeds is None:
-                self.engine.generate(slots[:live], ids[:live], ids_len[:live], finished[:live], params, done, n, toks[:live], lats[:live],
-                                     max_keys=mk, **_proc_arg(proc))
-            else:
-                # sampling: row r of class g is keyed (class seed, r, done) -- what generate(seed=class seed) draws for it
+            # sampling: row r of class g is keyed (class seed, r, done) -- what generate(seed=class seed) draws for it
+            rows = None
+            if seeds is not None:
                 rows = [dict(rs, seed=seeds[g], rng_row=r, rng_step0=done) for g in live_groups for r in range(spans[g][1] - spans[g][0])]
-                self.engine.generate_rows(slots[:live], ids[:live], ids_len[:live], finished[:live], rows, done, n, toks[:live], lats[:live],
-                                          max_keys=mk, **_proc_arg(proc))
+            _generate_call(self.engine, slots[:live], ids[:live], ids_len[:live], finished[:live], params, done, n, toks[:live], lats[:live],
+                           max_keys=mk, rows=rows, proc=proc, sets=sets)
             done += n
             stop = bool(finished[:live].all().item())
             self.engine.health()
@@ -959,12 +940,7 @@ class GPT(nn.Module):
         `job_kwargs` (one dict or None per job): each job's own logits processors and warpers (PROC_KWARGS, WARP_KWARGS), merged over
         the call-wide ones; job j then gets what generate(c_j, t_j, **its merged kwargs) returns (seed=job_seeds[j] when sampling), each
         row of a decode call carrying its job's set (gvc_gpt_generate_proc_sets, or gvc_gpt_generate_warp when a warper is on)."""
-        _no_beams(generate_kwargs, "rolling (generate_rolling)")
-        _no_contrastive(generate_kwargs, "rolling (generate_rolling)")
-        _single_return(generate_kwargs, "rolling (generate_rolling)")
-        _no_guidance(generate_kwargs, "rolling (generate_rolling)")
-        _no_outputs(generate_kwargs, "rolling (generate_rolling)")
-        _no_bias(generate_kwargs, "the rolling (generate_rolling) path")
+        _plain_rows_only(generate_kwargs, "rolling (generate_rolling)")
         kw = dict(generate_kwargs)
         jkw = None
         if job_kwargs is not None:
@@ -1051,17 +1027,11 @@ class GPT(nn.Module):
             elif _any_proc(kw):
                 plens = torch.tensor([j["n0"] for j in live for _ in j["alive"]], dtype=torch.int32).to(dev)
                 proc = logits_processors(kw, 0, self.num_audio_tokens, sampling=seeds is not None, prompt_lens=plens)
-            if sets is not None:
-                keys = None
-                if seeds is not None:
-                    keys = [dict(rs, seed=seeds[j["job"]], rng_row=r, rng_step0=j["done"]) for j in live for r in j["alive"]]
-                eng.generate_proc_sets(rows, ids, ids_len, fin, params, sets, 0, n, toks, None, max_keys=W - 8, rows=keys)
-            elif seeds is None:
-                eng.generate(rows, ids, ids_len, fin, params, 0, n, toks, None, max_keys=W - 8, **_proc_arg(proc))
-            else:
-                # row r of job j keyed (job seed, r, tokens the job has drawn): the key generate(seed=job_seeds[j]) gives that row
+            # row r of job j keyed (job seed, r, tokens the job has drawn): the key generate(seed=job_seeds[j]) gives that row
+            keys = None
+            if seeds is not None:
                 keys = [dict(rs, seed=seeds[j["job"]], rng_row=r, rng_step0=j["done"]) for j in live for r in j["alive"]]
-                eng.generate_rows(rows, ids, ids_len, fin, keys, 0, n, toks, None, max_keys=W - 8, **_proc_arg(proc))
+            _generate_call(eng, rows, ids, ids_len, fin, params, 0, n, toks, None, max_keys=W - 8, rows=keys, proc=proc, sets=sets)
             ids_all[idx, :W] = ids
             len_all[idx] = ids_len
             fin_all[idx] = fin
@@ -1111,12 +1081,7 @@ class GPT(nn.Module):
         """reference gpt.py:612-621 + stream_generator.py:865: yields (tokens int64[B], latent float[B,d]) per step,
         the EOS step included.  Steps run in groups of `stream_group` (default 8, the vocoder chunk of
         inference_utils.py:195) with one host check of the finished flags per group."""
-        _no_beams(generate_kwargs, "streaming (get_generator)")
-        _no_contrastive(generate_kwargs, "streaming (get_generator)")
-        _single_return(generate_kwargs, "streaming (get_generator)")
-        _no_guidance(generate_kwargs, "streaming (get_generator)")
-        _no_outputs(generate_kwargs, "streaming (get_generator)")
-        _no_bias(generate_kwargs, "the streaming (get_generator) path")
+        _plain_rows_only(generate_kwargs, "streaming (get_generator)")
         self._need_engine()
         group = generate_kwargs.pop("stream_group", 8)
         B = int(fake_inputs.shape[0])

@@ -43,7 +43,7 @@ import torch
 
 from .inference.inference_utils import _sampling_kwargs, _vocode, handle_chunks
 from .engine import check_proc_kwargs, logits_processors, logits_sets, logits_warpers, sample_params
-from .layers.gpt import _no_bias, _no_contrastive, _no_guidance, _no_outputs, _single_return
+from .layers.gpt import _generate_call, _plain_rows_only
 from ._lib import GenvcHipError
 
 
@@ -104,11 +104,7 @@ class StreamSessions:
     def _procs(self, kw, base, where):
         """a processor dict (PROC_KWARGS and WARP_KWARGS only) merged over `base`, validated -> the merged dict, or None when it is
         empty.  The contrastive-search kwargs raise NotImplementedError (sessions decode one row per stream)"""
-        _no_contrastive(kw or {}, f"session (StreamSessions, {where})")
-        _single_return(kw or {}, f"session (StreamSessions, {where})")
-        _no_guidance(kw or {}, f"session (StreamSessions, {where})")
-        _no_outputs(kw or {}, f"session (StreamSessions, {where})")
-        _no_bias(kw or {}, f"the session (StreamSessions, {where}) path")
+        _plain_rows_only(kw or {}, f"session (StreamSessions, {where})", beams=False)
         check_proc_kwargs(kw, where)
         m = dict(base, **{k: v for k, v in (kw or {}).items() if v is not None})
         try:
@@ -312,19 +308,14 @@ class StreamSessions:
         sets = None
         if any(s.procs for _, s in act):
             sets = logits_sets([s.procs for _, s in act], [s.p1 for _, s in act], m.gpt.num_audio_tokens)
+        rows = None
         if self.per_session_sampling:
             # each session's row keyed by its own stream: (its seed, row 0 of a lone stream, tokens of this segment drawn so far)
             rows = [dict(s.sampling, seed=s.seed, rng_row=0, rng_step0=s.done) for _, s in act]
-            if sets is not None:
-                eng.generate_proc_sets(slots, ids, ids_len, fin, None, sets, 0, n, toks, lats, max_keys=W - 8, rows=rows)
-            else:
-                eng.generate_rows(slots, ids, ids_len, fin, rows, 0, n, toks, lats, max_keys=W - 8)
-        elif sets is not None:
-            self.params.seed = self.calls - 1
-            eng.generate_proc_sets(slots, ids, ids_len, fin, self.params, sets, 0, n, toks, lats, max_keys=W - 8)
         else:
             self.params.seed = self.calls - 1      # a fresh counter-RNG stream per call (only matters for top_k > 1)
-            eng.generate(slots, ids, ids_len, fin, self.params, 0, n, toks, lats, max_keys=W - 8)
+        _generate_call(eng, slots, ids, ids_len, fin, None if rows is not None else self.params, 0, n, toks, lats, max_keys=W - 8, rows=rows,
+                       sets=sets)
         th = toks.cpu()                                           # (synchronises: the steps above have run)
         # a hand-off of the one-launch step that timed out (not all workgroups resident, e.g. another context on the GPU) raises here:
         # these tokens and latents are garbage and so are the K/V rows the steps appended.  Nothing of this call is kept or vocoded
