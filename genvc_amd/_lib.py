@@ -73,6 +73,13 @@ class LogitsBias(C.Structure):
          ("ids", (C.c_int32 * BIAS_MAX_LEN) * BIAS_MAX_SEQS)]
 
 
+class SpecState(C.Structure):
+    """gvc_spec_state (include/genvc_hip.h): sizes and the device arrays of one assisted (speculative) generation"""
+    _fields_ = [(n, C.c_int32) for n in ("B", "ids_stride", "max_new", "tok_stride", "lat_stride", "d")] + \
+        [(n, C.c_void_p) for n in ("ids", "ids_len", "finished", "emitted", "pending", "toks", "lats", "drop_target", "drop_assistant",
+                                   "rounds", "drafted", "accepted", "v_toks", "v_logits", "v_latents", "d_ids_len", "d_finished")]
+
+
 class PerceiverDims(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("dim", "depth", "dim_context", "num_latents", "dim_head", "heads",
                                          "ff_mult", "max_batch", "max_frames")]
@@ -166,6 +173,12 @@ _SIGNATURES = {
                                         C.POINTER(LogitsBias), C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_int32, _P, _P,
                                         C.c_int32, C.c_int32, _P]),
     "gvc_transition_scores": (C.c_int, [_P, C.c_int64, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
+    "gvc_gpt_verify": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, _P, _P, _P]),
+    "gvc_gpt_truncate": (C.c_int, [_P, _P, C.c_int32, _P, _P]),
+    "gvc_spec_accept": (C.c_int, [C.POINTER(SpecState), C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, C.POINTER(SampleParams),
+                                  C.POINTER(LogitsProcessors), _P]),
+    "gvc_gpt_generate_assisted": (C.c_int, [_P, _P, _P, _P, C.POINTER(SpecState), C.POINTER(SampleParams), C.POINTER(LogitsProcessors),
+                                            C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
     "gvc_gpt_decode_variant": (C.c_int, [_P]),
     "gvc_gpt_rows_step_launches": (C.c_longlong, [_P]),
     "gvc_gpt_one_stream_steps": (C.c_longlong, [_P]),

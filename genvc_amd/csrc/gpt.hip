@@ -19,6 +19,7 @@
 #include "contrastive.h"
 #include "sampler.h"
 #include "seqscore.h"
+#include "spec.h"
 
 namespace gvc {
 
@@ -356,6 +357,7 @@ struct gvc_gpt {
     float *logits = nullptr, *latent = nullptr;             // staging of the generation loop, indexed by position in the call
     float *slot_logits = nullptr, *slot_latent = nullptr;   // ... parked per slot between calls   // generate(): [slots][V], [slots][d]
     float* guided = nullptr;          // [slots / 2][V] guided scores of a gvc_gpt_generate_cfg step (what its sampler reads as logits)
+    int32_t* spec_base = nullptr;     // [slots] cache position of the first row of a slot's verification pass (gvc_gpt_verify)
     int32_t* state = nullptr;         // seq_len[slots], mel_pos[slots], tok[slots], step
     GptState st;
     int32_t *tok_buf = nullptr, *step_ctr = nullptr;
@@ -514,6 +516,8 @@ extern "C" int gvc_gpt_create(const gvc_gpt_dims* dims, gvc_gpt** out) {
     c->flush_slot = c->state + 6 * D.max_slots + 5;
     GVC_CHECK_HIP(hipMemset(c->st.pending, 0xff, (size_t)D.max_slots * sizeof(int32_t)));      // -1: nothing pending
     GVC_CHECK_HIP(hipMalloc((void**)&c->exec_ctr, sizeof(long long)));
+    GVC_CHECK_HIP(hipMalloc((void**)&c->spec_base, (size_t)D.max_slots * sizeof(int32_t)));
+    GVC_CHECK_HIP(hipMemset(c->spec_base, 0, (size_t)D.max_slots * sizeof(int32_t)));
     GVC_CHECK_HIP(hipMemset(c->exec_ctr, 0, sizeof(long long)));
     GVC_CHECK_HIP(hipDeviceSynchronize());      // (the memsets went to the legacy default stream; callers may use non-blocking ones)
     if (getenv("GVC_DEFER_DECODE")) c->defer = atoi(getenv("GVC_DEFER_DECODE")) != 0;
@@ -553,7 +557,7 @@ extern "C" int gvc_gpt_destroy(gvc_gpt* c) {
         if (p) hipFree(p);
     for (void* p : {(void*)c->wbase, (void*)c->wfm, (void*)c->wh, (void*)c->kv, (void*)c->x, (void*)c->a, (void*)c->q, (void*)c->h,
                     (void*)c->part, (void*)c->work, (void*)c->logits, (void*)c->latent, (void*)c->slot_logits, (void*)c->slot_latent, (void*)c->state, (void*)c->x2, (void*)c->part2,
-                    (void*)c->gen_call, (void*)c->beam_call, (void*)c->cs_call, (void*)c->exec_ctr, (void*)c->guided})
+                    (void*)c->gen_call, (void*)c->beam_call, (void*)c->cs_call, (void*)c->exec_ctr, (void*)c->guided, (void*)c->spec_base})
         if (p) hipFree(p);
     cs_free(&c->cs);
     delete c;
@@ -2155,6 +2159,132 @@ extern "C" int gvc_gpt_warmup_cfg(gvc_gpt* c, int32_t B, int32_t max_keys, int32
                       [&](const GenPlan& pl, int unroll, hipGraphExec_t* ge) { return cfg_graph(c, B, pl, unroll, ge); });
     if (rc) return rc;
     GVC_CHECK_HIP(hipDeviceSynchronize());
+    return GVC_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// assisted (speculative) greedy decoding (include/genvc_hip.h; kernels in spec.hip)
+// ---------------------------------------------------------------------------------------------
+// One verification pass over the T new rows of each of B slots, enqueued on s: input rows, the block stack through run_rows at the
+// slots' cached lengths (the one-launch rows step for <= 16 rows where it applies, else the skinny path), the head over all B * T
+// rows, and the lengths.  The caller has checked the arguments, prepared the rows step and settled deferred tokens.
+static int verify_rows(gvc_gpt* c, const int32_t* slots, int B, const int32_t* toks, int T, float* logits_out, float* latent_out,
+                       hipStream_t s) {
+    const int d = c->dm.d_model, V = c->dm.vocab, rows = B * T;
+    int rc;
+    if ((rc = launch_spec_embed(c->x, toks, slots, B, T, c->st.seq_len, c->st.mel_pos, c->mel_emb, c->mel_pos, d, V, c->dm.max_seq,
+                                c->dm.max_mel_pos, c->spec_base, c->seam_err_dev, s)))
+        return rc;
+    c->last_variant = c->r_ready == 1 && rows_persist_ok(c, rows, c->spec_base) ? 5 : 4;
+    if ((rc = run_rows(c, slots, B, T, s, c->spec_base))) return rc;
+    if (d <= 1024) {
+        // the GEMV head takes 8 rows per launch and reads no slot when it does not advance them
+        for (int g = 0; g < rows && rc == GVC_OK; g += 8)
+            rc = launch_head(c, slots, rows - g < 8 ? rows - g : 8, 0, c->x + (size_t)g * d, 1, 0, logits_out + (size_t)g * V,
+                             latent_out + (size_t)g * d, 0, nullptr, s);
+    } else {
+        rc = launch_head(c, slots, rows, 0, c->x, 1, 0, logits_out, latent_out, 0, nullptr, s);
+    }
+    if (rc) return rc;
+    return launch_spec_advance(c->st.seq_len, c->st.mel_pos, slots, B, T, c->dm.max_seq, c->dm.max_mel_pos, s);
+}
+
+static int check_verify(const gvc_gpt* c, int B, int T) {
+    GVC_REQUIRE(B >= 1 && B <= c->dm.max_slots && T >= 1, GVC_ERR_ARG, "verify: B=%d outside [1,%d] or T=%d below 1", B, c->dm.max_slots, T);
+    GVC_REQUIRE(B * T <= kSpecMaxRows && B * T <= c->dm.max_rows, GVC_ERR_ARG, "verify: %d x %d rows exceed %d rows (max_rows %d)", B, T,
+                kSpecMaxRows, c->dm.max_rows);
+    GVC_REQUIRE(T < c->dm.max_seq - 1 && T < c->dm.max_mel_pos - 1, GVC_ERR_ARG, "verify: T=%d does not fit max_seq %d / max_mel_pos %d", T,
+                c->dm.max_seq, c->dm.max_mel_pos);
+    // the skinny path is the only other one that takes rows at per-slot lengths
+    GVC_REQUIRE(rows_persist_ok(c, B * T, c->st.seq_len) ||
+                    (c->skinny_prefill && c->wfm && (long long)4 * B * T * c->dm.d_model <= c->work_cap / 2),
+                GVC_ERR_UNSUPPORTED, "verify: no rows path for %d rows of d_model %d", B * T, c->dm.d_model);
+    return GVC_OK;
+}
+
+extern "C" int gvc_gpt_verify(gvc_gpt* c, const int32_t* slots, int32_t B, const int32_t* toks, int32_t T, float* logits_out,
+                              float* latent_out, gvc_stream sv) {
+    int rc = check_ready(c);
+    if (rc) return rc;
+    GVC_REQUIRE(slots && toks && logits_out && latent_out, GVC_ERR_ARG, "verify: null argument");
+    if ((rc = check_verify(c, B, T))) return rc;
+    hipStream_t s = (hipStream_t)sv;
+    if (rows_persist_ok(c, B * T, c->st.seq_len) && (rc = rows_persist_prepare(c))) return rc;
+    c->rows_keys_hint = c->dm.max_seq;            // (no bound from the caller: the key split for the longest possible context)
+    if ((rc = flush_pending(c, slots, B, s))) return rc;
+    return verify_rows(c, slots, B, toks, T, logits_out, latent_out, s);
+}
+
+extern "C" int gvc_gpt_truncate(gvc_gpt* c, const int32_t* slots, int32_t B, const int32_t* drop, gvc_stream sv) {
+    GVC_REQUIRE(c && slots && drop && B >= 1 && B <= c->dm.max_slots, GVC_ERR_ARG, "truncate: bad argument");
+    hipStream_t s = (hipStream_t)sv;
+    // (a deferred token sits behind the slot's length: it is decoded before the length moves)
+    int rc = flush_pending(c, slots, B, s);
+    if (rc) return rc;
+    return launch_spec_truncate(c->st.seq_len, c->st.mel_pos, slots, B, drop, s);
+}
+
+extern "C" int gvc_gpt_generate_assisted(gvc_gpt* c, gvc_gpt* a, const int32_t* slots, const int32_t* aslots, const gvc_spec_state* st,
+                                         const gvc_sample_params* p, const gvc_logits_processors* proc, int32_t first, int32_t n_rounds,
+                                         int32_t k, int32_t max_keys, int32_t a_max_keys, gvc_stream sv) {
+    int rc = check_ready(c);
+    if (rc) return rc;
+    if ((rc = check_ready(a))) return rc;
+    GVC_REQUIRE(c != a && slots && aslots, GVC_ERR_ARG, "generate_assisted: the target and the assistant are two contexts with a slot list each");
+    if ((rc = check_spec_state(st, k, p, proc, true))) return rc;
+    const gvc_spec_state& S = *st;
+    const int B = S.B, V = c->dm.vocab, d = c->dm.d_model;
+    GVC_REQUIRE(k >= 1 && n_rounds >= 0, GVC_ERR_ARG, "generate_assisted: k=%d below 1 or n_rounds=%d below 0", k, n_rounds);
+    GVC_REQUIRE(p->vocab == V && a->dm.vocab == V, GVC_ERR_ARG, "generate_assisted: vocab mismatch (call %d, target %d, assistant %d)",
+                p->vocab, V, a->dm.vocab);
+    GVC_REQUIRE(B <= a->dm.max_slots && (!S.lats || S.d == d), GVC_ERR_ARG, "generate_assisted: %d streams / latent width %d do not fit", B, S.d);
+    if ((rc = check_verify(c, B, k + 1))) return rc;
+    GVC_REQUIRE(max_keys > 0 && max_keys < c->dm.max_seq - 1 && a_max_keys > 0 && a_max_keys < a->dm.max_seq - 1, GVC_ERR_STATE,
+                "generate_assisted: %d / %d cached positions would overflow a KV cache (max_seq %d / %d)", max_keys, a_max_keys,
+                c->dm.max_seq, a->dm.max_seq);
+    hipStream_t s = (hipStream_t)sv;
+    if (rows_persist_ok(c, B * (k + 1), c->st.seq_len) && (rc = rows_persist_prepare(c))) return rc;
+    c->rows_keys_hint = max_keys;
+    GenPlan apl;
+    if ((rc = plan_generate(a, B, a_max_keys, 1, &apl))) return rc;
+    a->last_variant = apl.variant;
+    if ((rc = flush_pending(c, slots, B, s)) || (rc = flush_pending(a, aslots, B, s))) return rc;
+    gvc_sample_params gp = *p;
+    gp.top_k = 1;
+    if (first) {
+        // token 0 of every row: the target's greedy choice from the logits and latent its prefill parked
+        hipLaunchKernelGGL(k_stage_rows, dim3(B), dim3(256), 0, s, S.v_logits, c->slot_logits, slots, V, 0);
+        hipLaunchKernelGGL(k_stage_rows, dim3(B), dim3(256), 0, s, S.v_latents, c->slot_latent, slots, d, 0);
+        GVC_LAUNCH_CHECK();
+        if ((rc = launch_spec_accept(S, 0, 0, S.v_logits, S.v_latents, nullptr, 0, gp, proc, s))) return rc;
+    }
+    // the draft sampler: the sampler's greedy kernel on the assistant's logits, with the call's settings, on the rows' own ids (it
+    // writes d_j where the accept step writes it again) but lengths and finished flags of its own; d_j lands in row j of v_toks
+    SampleCall dsc;
+    memset(&dsc, 0, sizeof(dsc));
+    dsc.logits = a->logits; dsc.B = B; dsc.ids = S.ids; dsc.ids_stride = S.ids_stride; dsc.ids_len = S.d_ids_len;
+    dsc.finished = S.d_finished; dsc.p = gp; dsc.step_ptr = a->step_ctr; dsc.tok_out = a->tok_buf;
+    dsc.tokens_out = S.v_toks; dsc.tok_stride = k + 1; dsc.i0 = 1; dsc.d = a->dm.d_model;
+    if (proc) {
+        static const int32_t zeros[kMaxSampleRows] = {};
+        GVC_REQUIRE(B <= kMaxSampleRows, GVC_ERR_ARG, "generate_assisted: processors serve up to %d streams", kMaxSampleRows);
+        if ((rc = launch_stage_proc_sets(&a->gen_call->proc, proc, 1, zeros, B, s))) return rc;
+        dsc.proc = &a->gen_call->proc;
+    }
+    for (int r = 0; r < n_rounds; ++r) {
+        // 1. k + 1 decode steps of the assistant: the pending token, then [sample d_j, decode d_j] for j = 1..k
+        if ((rc = launch_spec_round_begin(S, k + 1, a->step_ctr, s))) return rc;
+        if ((rc = decode_step(a, aslots, B, S.pending, a->logits, a->latent, nullptr, s, apl.fused, apl.key_chunks))) return rc;
+        for (int j = 0; j < k; ++j) {
+            if ((rc = launch_sample(dsc, s))) return rc;
+            if ((rc = decode_step(a, aslots, B, a->tok_buf, a->logits, a->latent, a->step_ctr, s, apl.fused, apl.key_chunks))) return rc;
+        }
+        // 2. - 4. one pass of the target over [pending, d_1..d_k], the accept step, and both caches rolled back
+        if ((rc = verify_rows(c, slots, B, S.v_toks, k + 1, S.v_logits, S.v_latents, s))) return rc;
+        if ((rc = launch_spec_accept(S, k, k + 1, S.v_logits, S.v_latents, S.v_toks + 1, k + 1, gp, proc, s))) return rc;
+        if ((rc = launch_spec_truncate(c->st.seq_len, c->st.mel_pos, slots, B, S.drop_target, s))) return rc;
+        if ((rc = launch_spec_truncate(a->st.seq_len, a->st.mel_pos, aslots, B, S.drop_assistant, s))) return rc;
+    }
     return GVC_OK;
 }
 

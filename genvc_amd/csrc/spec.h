@@ -1,0 +1,35 @@
+// Assisted (speculative) greedy decoding on the device (include/genvc_hip.h: gvc_gpt_verify, gvc_gpt_truncate, gvc_spec_accept,
+// gvc_gpt_generate_assisted): the input rows and length bookkeeping of a multi-row verification pass, the rollback of a slot, and the
+// accept step.  The block stack and the head of the verification are the context's own (gpt.hip: run_rows, launch_head); the round
+// loop that chains them with the draft context's decode steps lives there too.
+#pragma once
+#include "common.h"
+
+namespace gvc {
+
+constexpr int kSpecThreads = 256;
+constexpr int kSpecMaxVocab = 2048;     // one byte per vocabulary entry in LDS (the sampler's bound)
+constexpr int kSpecMaxDrafts = 15;      // k: a round verifies k + 1 <= 16 rows per stream
+constexpr int kSpecMaxRows = 128;       // rows of one verification pass (the skinny GEMMs' bound)
+
+// Row (b, t) of a verification pass: x[b * T + t] = mel_emb[toks[b][t]] + mel_pos[mel_pos_idx[slot b] + t], the token clamped into the
+// vocabulary and the position into the table.  base_out[slot b] = the cache position of row (b, 0): seq_len[slot], or the last one at
+// which T rows still end below max_seq - 1 (then *err = 950; a mel position past the table sets 951): see gvc_gpt_verify
+int launch_spec_embed(float* x, const int32_t* toks, const int32_t* slots, int B, int T, const int32_t* seq_len, const int32_t* mel_pos_idx,
+                      const float* mel_emb, const float* mel_pos, int d, int vocab, int max_seq, int max_mel_pos, int32_t* base_out,
+                      int* err, hipStream_t s);
+// behind the pass: length and mel position of every slot grow by T (a slot the embed launch flagged stays where it is)
+int launch_spec_advance(int32_t* seq_len, int32_t* mel_pos_idx, const int32_t* slots, int B, int T, int max_seq, int max_mel_pos,
+                        hipStream_t s);
+// length and mel position of slot b go down by max(drop[b], 0), not below 0
+int launch_spec_truncate(int32_t* seq_len, int32_t* mel_pos_idx, const int32_t* slots, int B, const int32_t* drop, hipStream_t s);
+// start of a round on the draft side: the draft sampler's own row lengths and finished flags start from the target's, its step
+// counter from 0, and row 0 of every stream's verification tokens is the pending token
+int launch_spec_round_begin(const gvc_spec_state& st, int k1, int32_t* step_ctr, hipStream_t s);
+// the accept step (include/genvc_hip.h: gvc_spec_accept); the arguments are checked by the callers
+int launch_spec_accept(const gvc_spec_state& st, int k, int appended, const float* logits, const float* latents, const int32_t* drafts,
+                       int draft_stride, const gvc_sample_params& p, const gvc_logits_processors* proc, hipStream_t s);
+// host-side checks of a state and a call's k
+int check_spec_state(const gvc_spec_state* st, int k, const gvc_sample_params* p, const gvc_logits_processors* proc, bool workspace);
+
+}  // namespace gvc

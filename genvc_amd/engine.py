@@ -606,6 +606,62 @@ class ContrastiveSearch:
         self.proc = proc          # gvc_logits_processors (logits_processors()) or None
 
 
+MAX_ASSISTANT_TOKENS = 15    # kSpecMaxDrafts (csrc/spec.h): drafts per round of an assisted generation
+MAX_VERIFY_ROWS = 128        # kSpecMaxRows: rows of one verification pass, B * (k + 1)
+
+
+class AssistedState:
+    """device-side state of one assisted (speculative) greedy generation over B streams (include/genvc_hip.h: gvc_spec_state): the
+    ids rows, per-row lengths, emitted counts, finished flags and pending tokens, the result buffers, the counters and the workspace
+    of the rounds.  `fake` int [B, n0]: the prompt's fake ids; k: drafts per round"""
+
+    def __init__(self, fake, k, max_new, eos, vocab, d, latents=True):
+        B, n0 = fake.shape
+        dev = fake.device
+        if isinstance(k, bool) or int(k) != k or not 0 <= int(k) <= MAX_ASSISTANT_TOKENS:
+            raise ValueError(f"an assisted round drafts 0..{MAX_ASSISTANT_TOKENS} tokens, not {k!r}")
+        k = int(k)
+        if B * (k + 1) > MAX_VERIFY_ROWS:
+            raise ValueError(f"{B} streams x {k + 1} rows exceed the {MAX_VERIFY_ROWS} rows of one verification pass")
+
+        def i32(*shape, fill=0):
+            return torch.full(shape, fill, device=dev, dtype=torch.int32)
+        self.B, self.k, self.n0, self.max_new, self.eos, self.vocab, self.d = B, k, n0, int(max_new), int(eos), int(vocab), int(d)
+        self.ids = i32(B, n0 + self.max_new + MAX_ASSISTANT_TOKENS + 1)
+        self.ids[:, :n0] = fake.to(torch.int32)
+        self.ids_len = i32(B, fill=n0)
+        self.finished, self.emitted, self.pending = i32(B), i32(B), i32(B, fill=-1)
+        self.toks = i32(B, self.max_new, fill=self.eos)
+        self.lats = torch.zeros(B, self.max_new, self.d, device=dev, dtype=torch.float32) if latents else None
+        self.drop_target, self.drop_assistant = i32(B), i32(B)
+        self.rounds, self.drafted, self.accepted = i32(B), i32(B), i32(B)
+        self.v_toks = i32(B, MAX_ASSISTANT_TOKENS + 1)
+        self.v_logits = torch.zeros(B, MAX_ASSISTANT_TOKENS + 1, self.vocab, device=dev, dtype=torch.float32)
+        self.v_latents = torch.zeros(B, MAX_ASSISTANT_TOKENS + 1, self.d, device=dev, dtype=torch.float32)
+        self.d_ids_len, self.d_finished = i32(B), i32(B)
+        self.opened = False          # the opening step (token 0 from the prefill's parked logits) has run
+        self.rounds_done = 0         # rounds enqueued so far (every live row emits at least one token per round)
+        p = (lambda t: None if t is None else t.data_ptr())
+        self.c = _lib.SpecState(B, self.ids.shape[1], self.max_new, self.toks.stride(0), self.max_new, self.d, p(self.ids),
+                                p(self.ids_len), p(self.finished), p(self.emitted), p(self.pending), p(self.toks), p(self.lats),
+                                p(self.drop_target), p(self.drop_assistant), p(self.rounds), p(self.drafted), p(self.accepted),
+                                p(self.v_toks), p(self.v_logits), p(self.v_latents), p(self.d_ids_len), p(self.d_finished))
+
+    def stats(self):
+        """the device counters as int64 [B] tensors: rounds run, drafts compared and drafts accepted per row"""
+        return dict(rounds=self.rounds.long(), drafted=self.drafted.long(), accepted=self.accepted.long())
+
+
+def spec_accept(state, k, appended, logits, latents, drafts, params, proc=None):
+    """the accept step of an assisted round on `state` (include/genvc_hip.h: gvc_spec_accept): logits fp32 [B, k + 1, V], latents fp32
+    [B, k + 1, d] or None, drafts int32 [B, >= k] or None for k = 0; appended: rows both caches gained (k + 1, or 0 for an opening step)"""
+    B = state.B
+    assert tuple(logits.shape) == (B, k + 1, state.vocab) and (latents is None or tuple(latents.shape) == (B, k + 1, state.d))
+    check(lib().gvc_spec_accept(C.byref(state.c), int(k), int(appended), ptr(_f32(logits)), ptr(None if latents is None else _f32(latents)),
+                                ptr(None if drafts is None else _i32(drafts)), 0 if drafts is None else drafts.shape[1], C.byref(params),
+                                None if proc is None else C.byref(proc), stream()), "spec_accept")
+
+
 class GptEngine:
     """KV-cached GPT-2 stack of GenVC (reference layers/gpt.py + layers/gpt_inference.py)."""
 
@@ -975,6 +1031,45 @@ class GptEngine:
     def warmup_cfg(self, B, max_keys=0, top_k=1):
         """warmup() for generate_cfg over B items (include/genvc_hip.h: gvc_gpt_warmup_cfg)"""
         check(lib().gvc_gpt_warmup_cfg(self._h, int(B), int(max_keys), int(top_k)), "warmup_cfg")
+
+    def verify(self, slots, toks, logits=None, latent=None):
+        """T = toks.shape[1] new rows per slot in one pass (include/genvc_hip.h: gvc_gpt_verify): toks int32 [B, T] ->
+        (logits [B, T, V], latent [B, T, d]) of every row; the slots' lengths and mel positions grow by T"""
+        self._join_side()
+        B, T = toks.shape
+        if slots.shape[0] != B:
+            raise ValueError(f"{slots.shape[0]} slots for {B} rows of tokens")
+        if logits is None:
+            logits = torch.empty(B, T, self.V, device=toks.device, dtype=torch.float32)
+            latent = torch.empty(B, T, self.d, device=toks.device, dtype=torch.float32)
+        check(lib().gvc_gpt_verify(self._h, ptr(_i32(slots)), B, ptr(_i32(toks)), T, ptr(_f32(logits)), ptr(_f32(latent)), stream()),
+              "verify")
+        return logits, latent
+
+    def truncate(self, slots, drop):
+        """roll the slots back by drop[b] positions (device int32 [B]; include/genvc_hip.h: gvc_gpt_truncate); no synchronisation"""
+        if drop.shape[0] != slots.shape[0]:
+            raise ValueError(f"{drop.shape[0]} drop counts for {slots.shape[0]} slots")
+        check(lib().gvc_gpt_truncate(self._h, ptr(_i32(slots)), slots.shape[0], ptr(_i32(drop)), stream()), "truncate")
+
+    def generate_assisted(self, assistant, slots, assistant_slots, state, params, n_rounds, max_keys, assistant_max_keys, proc=None,
+                          k=None):
+        """n_rounds rounds of assisted greedy decoding of `state` (an AssistedState) with this engine as the target and `assistant`
+        (another GptEngine) drafting k (default state.k; never more) tokens per round (include/genvc_hip.h:
+        gvc_gpt_generate_assisted).  The first call of a state also runs its opening step.  max_keys / assistant_max_keys: cached positions the longest stream reaches inside the call"""
+        self._join_side()
+        assistant._join_side()
+        if slots.shape[0] != state.B or assistant_slots.shape[0] != state.B:
+            raise ValueError(f"{slots.shape[0]} / {assistant_slots.shape[0]} slots for {state.B} streams")
+        k = state.k if k is None else int(k)
+        if not 1 <= k <= state.k:
+            raise ValueError(f"{k} drafts per round outside [1, {state.k}]")
+        check(lib().gvc_gpt_generate_assisted(self._h, assistant._h, ptr(_i32(slots)), ptr(_i32(assistant_slots)), C.byref(state.c),
+                                              C.byref(params), None if proc is None else C.byref(proc), int(not state.opened),
+                                              int(n_rounds), k, int(max_keys), int(assistant_max_keys), stream()),
+              "generate_assisted")
+        state.opened = True
+        state.rounds_done += int(n_rounds)
 
     def beam_generate(self, slots, beam, n_steps, max_keys=0):
         """n_steps steps of `beam` (a BeamSearch) on the device, continuing at beam.steps (include/genvc_hip.h: gvc_gpt_beam_generate):

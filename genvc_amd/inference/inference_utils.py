@@ -244,9 +244,11 @@ def synthesize_utt_streaming(genVC_mdl, src_wav, tgt_audio, seg_len=6.0, stream_
                              return_details=False, generate_kwargs=None):
     """streaming conversion (reference :135-217); the clock starts before the host->device copies (:148).  generate_kwargs: more
     GPT.get_generator kwargs (the logits processors), merged into every segment's call.  sequence_bias / bad_words_ids /
-    forced_eos_token_id / renormalize_logits raise NotImplementedError here (infer.py --streaming): synthesize_utt serves them"""
-    from genvc_amd.layers.gpt import _no_bias
+    forced_eos_token_id / renormalize_logits and assistant_model raise NotImplementedError here (infer.py --streaming): synthesize_utt
+    serves them"""
+    from genvc_amd.layers.gpt import _no_assistant, _no_bias
     _no_bias(generate_kwargs or {}, "the streaming (synthesize_utt_streaming, infer.py --streaming) path")
+    _no_assistant(generate_kwargs or {}, "streaming (synthesize_utt_streaming, infer.py --streaming)")
     m = genVC_mdl
     wav_gen_prev, wav_overlap = None, None
     total = src_wav.shape[-1]

@@ -302,6 +302,25 @@ def model_init_synthetic(config=None, seed=1, device="cuda", max_slots=8, weight
     return model, config
 
 
+@torch.inference_mode()
+def synthetic_assistant(config, layers, seed=2, device="cuda", max_slots=8, weight_dtype="fp32"):
+    """A draft GPT for GPT.generate(assistant_model=...): the architecture of config.model_args with `layers` layers, deterministic
+    synthetic weights of its own (a demonstration of the mode: such a draft agrees with the target about as often as chance)."""
+    from .. import synth
+    from ..layers.gpt import GPT
+    a = gcfg.to_attr(dict(config.model_args, gpt_layers=int(layers)))
+    g = GPT(layers=a.gpt_layers, model_dim=a.gpt_n_model_channels, heads=a.gpt_n_heads,
+            max_text_tokens=a.gpt_max_text_tokens, max_mel_tokens=a.gpt_max_audio_tokens,
+            max_prompt_tokens=a.gpt_max_prompt_tokens, number_text_tokens=a.gpt_number_text_tokens,
+            start_text_token=a.gpt_start_text_token, stop_text_token=a.gpt_stop_text_token,
+            num_audio_tokens=a.gpt_num_audio_tokens, start_audio_token=a.gpt_start_audio_token,
+            stop_audio_token=a.gpt_stop_audio_token, code_stride_len=a.gpt_code_stride_len)
+    g.load_state_dict(synth.make_weights(seed, synth.gpt_weight_spec(gcfg.gpt_dims(a)), device=device), strict=False)
+    g.eval()
+    g.to(device)
+    return g.init_gpt_for_inference(max_slots=max_slots, weight_dtype=weight_dtype)
+
+
 _REQUIRED_PREFIXES = ("gpt.", "content_dvae.", "hifigan.", "content_extractor.model.")
 
 

@@ -11,7 +11,7 @@ import torch
 from torch import nn
 
 from .._lib import GenvcHipError
-from ..engine import (BEAM_LENGTH_MODES, beam_early_stopping, check_beam_groups, GroupBeamSearch, MAX_CONTRASTIVE_K, PROC_KWARGS, WARP_KWARGS, BeamSearch, ContrastiveSearch, GptEngine, WarperSets,
+from ..engine import (MAX_ASSISTANT_TOKENS, MAX_VERIFY_ROWS, AssistedState, BEAM_LENGTH_MODES, beam_early_stopping, check_beam_groups, GroupBeamSearch, MAX_CONTRASTIVE_K, PROC_KWARGS, WARP_KWARGS, BeamSearch, ContrastiveSearch, GptEngine, WarperSets,
                       check_proc_kwargs, logits_bias, logits_processors, logits_sets, logits_warpers, sample_params)
 from .perceiver_encoder import PerceiverResampler
 
@@ -248,6 +248,52 @@ def _no_bias(kw, where):
                                   "num_return_sequences, guidance_scale), one call-wide set per call")
 
 
+ASSIST_KWARGS = ("assistant_model", "num_assistant_tokens", "num_assistant_tokens_schedule", "assistant_cond_latents")
+
+
+def _no_assistant(kw, where):
+    """the paths without a draft model: assistant_model raises, naming the path"""
+    if kw.get("assistant_model") is not None:
+        raise NotImplementedError(f"assisted decoding (assistant_model) is not on the {where} path: GPT.generate serves it (greedy, "
+                                  "one draft context next to the target's)")
+
+
+def _assisted_kwargs(kw, B):
+    """the kwargs of GPT.generate(assistant_model=...) validated -> k, the drafts per round.  Assisted decoding is greedy: every
+    other mode of generate raises NotImplementedError naming the combination; a k outside [1, 15], more than 128 verification rows
+    and a schedule other than "constant" raise ValueError"""
+    mode = "assisted decoding (assistant_model)"
+    if _guidance_scale(kw) is not None:
+        raise NotImplementedError(f"guidance_scale={kw.get('guidance_scale')} with {mode} is not implemented")
+    if _contrastive_mode(kw) is not None:
+        raise NotImplementedError(f"contrastive search (penalty_alpha={kw.get('penalty_alpha')}) with {mode} is not implemented")
+    if _grouped(kw):
+        raise NotImplementedError(f"beam groups (num_beam_groups / diversity_penalty) with {mode} are not implemented")
+    if int(kw.get("num_beams", 1) or 1) != 1:
+        raise NotImplementedError(f"beam search (num_beams={kw.get('num_beams')}) with {mode} is not implemented")
+    if _num_return(kw) != 1:
+        raise NotImplementedError(f"num_return_sequences={kw.get('num_return_sequences')} with {mode} is not implemented")
+    if kw.get("do_sample", True) and kw.get("top_k", 0) != 1:
+        raise NotImplementedError(f"sampling (do_sample=True, top_k={kw.get('top_k', 0)}) with {mode} is not implemented: speculative "
+                                  "sampling needs the draft's warped rows; pass do_sample=False or top_k=1")
+    _no_step_outputs(kw, mode)
+    _no_bias(kw, mode)
+    if logits_warpers(kw, sampling=False) is not None:
+        raise NotImplementedError(f"typical_p / epsilon_cutoff / eta_cutoff with {mode} are not implemented")
+    sched = kw.get("num_assistant_tokens_schedule", "constant")
+    if sched is not None and sched != "constant":
+        raise ValueError(f"num_assistant_tokens_schedule={sched!r} with {mode}: only \"constant\" is served (a heuristic schedule needs "
+                         "a host round trip per round)")
+    k = kw.get("num_assistant_tokens")
+    k = 5 if k is None else k
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= MAX_ASSISTANT_TOKENS:
+        raise ValueError(f"num_assistant_tokens must be an int in [1, {MAX_ASSISTANT_TOKENS}] for {mode}, not {k!r}")
+    if B * (k + 1) > MAX_VERIFY_ROWS:
+        raise ValueError(f"{mode}: {B} items x (num_assistant_tokens + 1 = {k + 1}) rows exceed the {MAX_VERIFY_ROWS} rows of one "
+                         "verification pass")
+    return k
+
+
 def _plain_rows_only(kw, where, beams=True):
     """the paths that decode one sampled or greedy row per stream and return bare tokens (grouped, rolling, streaming, sessions):
     every mode only GPT.generate serves raises, naming the path `where`.  beams=False: the caller has no num_beams to refuse"""
@@ -258,6 +304,7 @@ def _plain_rows_only(kw, where, beams=True):
     _no_guidance(kw, where)
     _no_outputs(kw, where)
     _no_bias(kw, f"the {where} path")
+    _no_assistant(kw, where)
 
 
 def _generate_call(eng, *args, **kw):
@@ -577,8 +624,12 @@ class GPT(nn.Module):
         max_new_tokens - 1; renormalize_logits makes the stored `scores` log-probabilities and leaves the tokens those of the call
         without it, bit for bit (no effect without output_scores).  forced_bos_token_id is accepted and does nothing: HF's processor
         fires at cur_len == 1, and no prompt of this model is that short.  Beams, beam groups and contrastive search raise
-        NotImplementedError for them, as the grouped, rolling, session and streaming paths do."""
+        NotImplementedError for them, as the grouped, rolling, session and streaming paths do.
+        assistant_model = another initialised GPT: assisted (speculative) greedy decoding (_generate_assisted), checked
+        before every other mode; the tokens are those of the call without it.  None is exactly that call."""
         _num_return(generate_kwargs)
+        if generate_kwargs.get("assistant_model") is not None:
+            return self._generate_assisted(cond_latents, text_inputs, generate_kwargs)
         scale = _guidance_scale(generate_kwargs)
         if scale is not None:
             return self._generate_guided(cond_latents, text_inputs, scale, generate_kwargs)
@@ -678,6 +729,102 @@ class GPT(nn.Module):
                 pass
             return st
         return self._finish(self._recovering(2 * B, run), kw)
+
+    def _generate_assisted(self, cond_latents, text_inputs, generate_kwargs):
+        """HF generate(assistant_model=draft, do_sample=False) semantics on the device (include/genvc_hip.h: gvc_gpt_generate_assisted):
+        `assistant_model` is a GPT after init_gpt_for_inference with this model's num_audio_tokens, start and stop audio tokens; it
+        builds its own prefix from `assistant_cond_latents` (required when its model_dim differs, else cond_latents is reused) and
+        the same text_inputs, and prefills its own KV slots.  Every round the assistant drafts k = num_assistant_tokens (1..15,
+        default 5, the choice of profiles/assisted_decoding.md) tokens greedily, this model scores [pending token, d_1..d_k] in one
+        multi-row pass, the device accepts the longest agreeing prefix plus one token of this model per row, and both caches roll
+        back; near the end of the position tables a call drafts fewer tokens.  Greedy only (do_sample=False or top_k=1), with
+        repetition_penalty, temperature and the processor kwargs (engine.PROC_KWARGS) on both models; every other mode raises
+        NotImplementedError.  The host reads the finished flags once per max(1, group // (k + 1)) rounds.  Token 0 of a row comes from
+        the prefill's logits (the opening step: no round is counted for it), so a row of n tokens whose drafts were all accepted ran
+        ceil((n - 1) / (k + 1)) rounds.  Returns what the call without the assistant returns (tokens bit for bit; `last_latents`
+        from the verification rows) and sets `last_assist_stats`: dict(rounds, drafted, accepted), int64 [B] each."""
+        kw = dict(generate_kwargs)
+        asst = kw.pop("assistant_model")
+        acond = kw.pop("assistant_cond_latents", None)
+        B = int(text_inputs.shape[0])
+        k = _assisted_kwargs(kw, B)
+        for name in ASSIST_KWARGS[1:3]:
+            kw.pop(name, None)
+        mode = "assisted decoding (assistant_model)"
+        if not isinstance(asst, GPT) or asst is self:
+            raise ValueError(f"{mode}: assistant_model must be another GPT, not {type(asst).__name__ if asst is not self else 'the target itself'}")
+        if asst.engine is None:
+            raise ValueError(f"{mode}: the assistant is not initialised (call its init_gpt_for_inference() first)")
+        for name in ("num_audio_tokens", "start_audio_token", "stop_audio_token"):
+            if getattr(asst, name) != getattr(self, name):
+                raise ValueError(f"{mode}: the assistant's {name} is {getattr(asst, name)}, the target's {getattr(self, name)}")
+        if acond is None:
+            if asst.model_dim != self.model_dim:
+                raise ValueError(f"{mode}: assistant_cond_latents is required: the assistant's model_dim {asst.model_dim} differs from "
+                                 f"the target's {self.model_dim}")
+            acond = cond_latents
+        if B > self.max_slots or B > asst.max_slots:
+            raise ValueError(f"{mode}: {B} items need {B} KV slots in both contexts (target {self.max_slots}, assistant {asst.max_slots})")
+        self._need_engine()
+        group = int(kw.pop("group", 16))
+        fake = self.compute_embeddings(cond_latents, text_inputs)
+        afake = asst.compute_embeddings(acond, text_inputs)
+        n0, a_n0 = int(fake.shape[1]), int(afake.shape[1])
+        dev = fake.device
+        max_new = int(kw.get("max_new_tokens") or self.max_gen_mel_tokens)
+
+        # drafts that fit the position tables of both contexts when the furthest live row has emitted ub tokens: a round appends
+        # k + 1 rows at cache length n0 + ub - 1 and mel position ub, and both must end below the last table entry
+        def fit(ub):
+            f = []
+            for m, p0 in ((self, n0), (asst, a_n0)):
+                f += [m.engine.dims["max_mel_pos"] - 2 - ub, m.engine.dims["max_seq"] - 2 - p0 - ub]
+            return min(f)
+        if max_new > 1 and fit(max_new - 1) < 1:
+            raise ValueError(f"{mode}: max_new_tokens={max_new} leaves no room for a draft in the position tables; lower it")
+        samp = dict(repetition_penalty=kw.get("repetition_penalty", 1.0), temperature=kw.get("temperature", 1.0), top_p=1.0, top_k=1)
+        params = sample_params(samp, self.num_audio_tokens, self.stop_audio_token, kw.get("seed", 0))
+        proc = logits_processors(kw, n0, self.num_audio_tokens, sampling=False)
+        per_check = max(1, group // (k + 1))
+
+        def run():
+            slots = torch.arange(B, device=dev, dtype=torch.int32)
+            self.engine.prefill(slots, self._prefix, want_outputs=False)
+            asst.engine.prefill(slots, asst._prefix, want_outputs=False)
+            st = AssistedState(fake, k, max_new, self.stop_audio_token, self.num_audio_tokens, self.model_dim)
+            ub = 1          # tokens the furthest live row can have emitted (the opening step emits one)
+            while True:
+                # the rounds of one call draft the same count: as many rounds as that count fits (fit() only shrinks as rows advance)
+                kc = min(k, fit(ub)) if max_new > 1 else 1
+                n, u, reach = 0, ub, ub
+                while max_new > 1 and n < per_check and min(k, fit(u)) >= kc:
+                    reach = u + kc          # cached positions behind the prompt at the end of this round's verification
+                    n, u = n + 1, min(max_new - 1, u + kc + 1)
+                self.engine.generate_assisted(asst.engine, slots, slots, st, params, n, n0 + reach, a_n0 + reach, proc=proc, k=kc)
+                ub = u
+                end = bool(st.finished.all().item())
+                self.engine.health()          # (the .item() above synchronised)
+                asst.engine.health()
+                if end:
+                    return st
+        try:
+            st = run()
+        except GenvcHipError as e:
+            if not e.is_handoff_timeout:
+                raise
+            # a hand-off time-out in either context (_recovering): both have switched paths where needed; reset and repeat in full
+            self.recoveries = getattr(self, "recoveries", 0) + 1
+            torch.cuda.synchronize()
+            slots = torch.arange(B, device=dev, dtype=torch.int32)
+            self.engine.reset(slots)
+            asst.engine.reset(slots)
+            st = run()
+        toks = st.toks.long()
+        n = self._stop_len(toks)
+        self.last_latents = st.lats[:, :n]
+        self.last_sequence_logprobs = self.last_sequence_lengths = None
+        self.last_assist_stats = st.stats()
+        return self._result(toks[:, :n], kw)
 
     @torch.inference_mode()
     def sequence_logprobs(self, tokens, latents):

@@ -611,10 +611,90 @@ int gvc_gpt_generate_bias(gvc_gpt* ctx, const int32_t* slots, const int32_t* unc
  * cached positions (and everything gvc_gpt_warmup(2B) prepares).  Afterwards such calls neither allocate nor synchronise */
 int gvc_gpt_warmup_cfg(gvc_gpt* ctx, int32_t B, int32_t max_keys, int32_t top_k);
 
+/* ------------------------------------------------------------------------------------------
+ * Assisted (speculative) greedy decoding (HF generate(assistant_model=...), transformers generation/utils.py _assisted_decoding
+ * with do_sample=False): a small draft context proposes k tokens per stream, the target scores [pending token, d_1..d_k] in ONE
+ * multi-row pass, the longest prefix of drafts that equals the target's own greedy choices is accepted together with one target
+ * token, and both KV caches roll back.  The emitted tokens are those of the plain greedy call.
+ *
+ * gvc_gpt_verify: appends T rows to each of the B slots (B * T <= 128, B * T <= max_rows): row t of stream b enters as
+ * mel_embedding[toks[b][t]] + mel_pos[mel_pos(slot) + t] at cache position len(slot) + t, attends causally over [0, len + t], writes
+ * its K/V, and its final_norm(ln_f(h)) / mel_head land in latent_out[b][t] / logits_out[b][t]; length and mel position advance by T.
+ * d_model 1024 with B * T <= 16 runs the block stack in one launch (csrc/persist_rows.h), otherwise the skinny MFMA rows path.  More
+ * than 128 rows is GVC_ERR_ARG.  A pending deferred token of a slot is decoded first.  A slot whose length + T would pass max_seq - 1
+ * is computed at the last positions that fit and a mel position past the table reads its last row: nothing is indexed out of
+ * bounds, the slot does not advance, its outputs are invalid and the next call reports GVC_ERR_STATE as after a full decode step.
+ * gvc_gpt_truncate: length and mel position of slot b go down by drop[b] (DEVICE int32 [B], negative counts as 0), not below 0;
+ * no synchronisation.  K/V behind the new length is overwritten by later rows.
+ * ------------------------------------------------------------------------------------------ */
+int gvc_gpt_verify(gvc_gpt* ctx, const int32_t* slots, int32_t B, const int32_t* toks, int32_t T, float* logits_out, float* latent_out,
+                   gvc_stream s);
+int gvc_gpt_truncate(gvc_gpt* ctx, const int32_t* slots, int32_t B, const int32_t* drop, gvc_stream s);
+
+/* State of an assisted generation: DEVICE arrays owned by the caller.  ids / ids_len / finished as in gvc_sample; ids_stride must
+ * hold prompt + max_new + 16 ids.  emitted[b]: tokens row b has emitted; toks / lats receive token j of row b at column j (the
+ * caller fills toks with the stop token first).  pending[b]: the row's last emitted token, which is in neither KV cache yet and
+ * opens the next round.  rounds / drafted / accepted (nullable): counters, bumped once per round and live row.
+ * The rest is workspace of gvc_gpt_generate_assisted (unused by gvc_spec_accept): v_toks [B][16], v_logits [B][16][vocab],
+ * v_latents [B][16][d], d_ids_len / d_finished [B]. */
+typedef struct gvc_spec_state {
+    int32_t B, ids_stride, max_new, tok_stride, lat_stride, d;
+    int32_t* ids;
+    int32_t* ids_len;
+    int32_t* finished;
+    int32_t* emitted;
+    int32_t* pending;
+    int32_t* toks;
+    float* lats;                        /* nullable */
+    int32_t* drop_target;               /* [B] rows the target / the assistant drop after this round */
+    int32_t* drop_assistant;
+    int32_t* rounds;
+    int32_t* drafted;
+    int32_t* accepted;
+    int32_t* v_toks;
+    float* v_logits;
+    float* v_latents;
+    int32_t* d_ids_len;
+    int32_t* d_finished;
+} gvc_spec_state;
+
+/* The accept step, one workgroup per stream.  logits [B][k + 1][vocab] and latents [B][k + 1][d] are the target's rows for the inputs
+ * [pending, d_1..d_k]; drafts [B][draft_stride] holds d_1..d_k (0 <= k <= 15; k = 0: the opening step of a generation, one row per
+ * stream and no draft).  `appended`: rows both caches gained this round (k + 1; 0 for the opening step).  A live row with r =
+ * max_new - emitted tokens to go compares k' = min(k, r - 1) drafts (HF clamps the draft length the same way): for i = 0..k' in
+ * order, draft i - 1 goes into the ids row, the greedy chain of gvc_sample at top_k = 1 (repetition penalty, the processors `proc`
+ * at length ids_len + i, temperature, argmax with the lower index winning a tie) runs on logits row i, the token is emitted with
+ * latent row i, and the row goes on while i < k' and the token equals draft i and is not the stop token.  Then ids_len and emitted
+ * grow by the m emitted tokens, pending is the last of them, finished is set at the stop token or when emitted reaches max_new,
+ * both drops are appended - m (0 for the opening step), and rounds += 1, drafted += k', accepted += the agreeing drafts (not for
+ * the opening step).  A finished row emits nothing and drops `appended`.  p: eos_token, vocab (<= 2048), repetition_penalty and
+ * temperature are read.  proc: nullable HOST struct, free when the call returns. */
+int gvc_spec_accept(const gvc_spec_state* st, int32_t k, int32_t appended, const float* logits, const float* latents,
+                    const int32_t* drafts, int32_t draft_stride, const gvc_sample_params* p, const gvc_logits_processors* proc,
+                    gvc_stream s);
+
+/* n_rounds rounds of assisted greedy decoding over st->B streams (B * (k + 1) <= 128, 1 <= k <= 15) with no host synchronisation
+ * inside or between them.  target / assistant: two contexts with the same vocabulary whose slots[b] / assistant_slots[b] (device
+ * arrays) hold the same stream, both prefilled.  first != 0 opens the generation: token 0 of every row is the target's greedy
+ * choice from the logits its prefill parked (gvc_spec_accept with k = 0) and becomes the pending token.  One round:
+ *   1. the assistant decodes the pending token, then k x [greedy sample -> decode step] with the call's settings on its own
+ *      logits; the last of those decodes consumes d_k, so that a round in which every draft is accepted leaves the assistant
+ *      complete (k + 1 decode steps per round; both caches then hold the same k + 1 new positions and roll back by the same count);
+ *   2. gvc_gpt_verify of [pending, d_1..d_k] on the target: exactly one block-stack pass per round;
+ *   3. gvc_spec_accept;  4. gvc_gpt_truncate on both contexts.
+ * Rows accept different counts: all loop state is per row on the device.  The caller reads st->finished between calls.  max_keys /
+ * assistant_max_keys: cached positions the longest stream can reach inside this call, rolled-back rows included (GVC_ERR_STATE
+ * when that passes max_seq - 1: refused before anything runs).  The rounds are launched directly, not captured.  Pending deferred
+ * tokens of the slots are decoded first; the slots end the call with nothing deferred and their parked logits stale. */
+int gvc_gpt_generate_assisted(gvc_gpt* target, gvc_gpt* assistant, const int32_t* slots, const int32_t* assistant_slots,
+                              const gvc_spec_state* st, const gvc_sample_params* p, const gvc_logits_processors* proc, int32_t first,
+                              int32_t n_rounds, int32_t k, int32_t max_keys, int32_t assistant_max_keys, gvc_stream s);
+
 /* Which decode step the last gvc_gpt_generate call replayed (diagnostic): 0 none yet, 1 launch-per-phase with split-key attention,
  * 2 launch-per-phase with the fused short-context attention launch, 3 the one-launch step (one stream), 4 the MFMA rows path
  * (launch per phase: 17+ streams, or shapes the one-launch rows step does not serve), 5 the one-launch rows step (2..16 streams,
- * csrc/persist_rows.h). */
+ * csrc/persist_rows.h).  gvc_gpt_verify and the rounds of gvc_gpt_generate_assisted report 5 or 4 for their verification pass (on the
+ * assistant: the variant of its draft steps). */
 int gvc_gpt_decode_variant(gvc_gpt* ctx);
 /* Diagnostic: how many one-launch rows steps (csrc/persist_rows.h: 2..16 rows that continue cached sequences -- batched decode
  * steps, the uncached rows of a streaming chunk's prefill) this context has issued; a step captured into the generation loop's

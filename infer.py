@@ -66,7 +66,27 @@ if __name__ == "__main__":
     parser.add_argument("--token_scores", type=str, default=None, metavar="PATH.npz",
                         help="non-streaming only: write, per segment, the codec tokens and the log-probability of each under the "
                              "distribution it was decoded from (processors, warpers and guidance included)")
+    parser.add_argument("--assistant_layers", type=int, default=None, metavar="N",
+                        help="with --synthetic, non-streaming: assisted (speculative) greedy decoding with a synthetic N-layer draft model "
+                             "of the same width (GPT.generate(assistant_model=...)); a demonstration of the mode, not of an acceptance rate")
+    parser.add_argument("--num_assistant_tokens", type=int, default=None, metavar="K",
+                        help="with --assistant_layers: tokens drafted per round, 1..15 (default 5)")
     args = parser.parse_args()
+    if args.num_assistant_tokens is not None and args.assistant_layers is None:
+        raise SystemExit("--num_assistant_tokens needs --assistant_layers")
+    if args.assistant_layers is not None:
+        if not args.synthetic:
+            raise SystemExit("--assistant_layers needs --synthetic: no draft checkpoint ships with the reference")
+        if args.streaming:
+            raise SystemExit("--assistant_layers is not on the streaming path (--streaming): GPT.generate serves assisted decoding")
+        if args.assistant_layers < 1 or not 1 <= (5 if args.num_assistant_tokens is None else args.num_assistant_tokens) <= 15:
+            raise SystemExit("--assistant_layers must be >= 1 and --num_assistant_tokens in [1, 15]")
+        if (args.num_beams != 1 or args.penalty_alpha is not None or args.num_return_sequences != 1 or args.token_scores is not None
+                or (args.guidance_scale is not None and args.guidance_scale != 1.0) or args.sequence_bias or args.bad_words_ids
+                or args.forced_eos or args.typical_p is not None or args.epsilon_cutoff is not None or args.eta_cutoff is not None):
+            raise SystemExit("--assistant_layers decodes greedily: it does not combine with --num_beams, --penalty_alpha, "
+                             "--num_return_sequences, --guidance_scale, --token_scores, the warper flags, --sequence_bias, --bad_words_ids "
+                             "or --forced_eos")
     if args.token_scores is not None:
         if args.streaming:
             raise SystemExit("--token_scores is not on the streaming path (--streaming): GPT.generate serves the per-step scores")
@@ -152,6 +172,11 @@ if __name__ == "__main__":
     if args.num_beams == 1 and model.gpt.max_slots < args.num_return_sequences:     # sampling: one KV slot per candidate
         model.gpt.init_gpt_for_inference(max_slots=args.num_return_sequences, max_rows=max(4096, 128 * args.num_return_sequences),
                                          weight_dtype=args.weights)
+    if args.assistant_layers is not None:
+        from genvc_amd.inference.model_init import synthetic_assistant
+        gen_kw.update(do_sample=False, num_assistant_tokens=5 if args.num_assistant_tokens is None else args.num_assistant_tokens,
+                      assistant_model=synthetic_assistant(model.config, args.assistant_layers, device=args.device,
+                                                          max_slots=model.gpt.max_slots, weight_dtype=args.weights))
     src_wav = load_audio(args.src_wav, model.content_sample_rate, device=args.device)
     ref_audio = load_audio(args.ref_audio, model.config.audio.sample_rate, device=args.device)
     if src_wav is None or ref_audio is None:
@@ -200,6 +225,10 @@ if __name__ == "__main__":
                          **{f"logprobs_{i}": lp.cpu().numpy() for i, lp in enumerate(out["token_logprobs"])})
                 print(f"{args.token_scores}: tokens and log-probabilities of {len(out['codes'])} segments")
         print(f"generated {toks.shape[-1]} codec tokens, latents {tuple(lat.shape)}")
+        if args.assistant_layers is not None:
+            st = model.gpt.last_assist_stats
+            print(f"assisted decoding, last segment: {int(st['rounds'].sum())} rounds, {int(st['accepted'].sum())} of "
+                  f"{int(st['drafted'].sum())} drafts accepted (synthetic weights: chance level)")
         if out["wav"] is not None:
             save_wav(args.output_path, out["wav"], config.audio.sample_rate)
         else:

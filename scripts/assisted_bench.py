@@ -1,0 +1,240 @@
+"""Cost of one round of assisted (speculative) greedy decoding on one MI355X: full size (GenVC_small dims: 30 layers,
+d_model 1024, synthetic weights, fp32), ONE stream behind a 48-row prompt.
+
+    python scripts/assisted_bench.py [--out profiles/assisted_decoding.md] [--json profiles/assisted_decoding.json] [--reps 5] [--render]
+
+A round is k + 1 decode steps of the assistant (the pending token and the k drafts) plus one k + 1-row verification pass of the target,
+the accept step and two rollbacks.  Its work does not depend on what is accepted, so one timing per (assistant layers, k) gives both
+extremes: at acceptance 0 a round emits one token, at full acceptance k + 1.  Timed with device events around ONE engine call of
+ROUNDS rounds that ends in a synchronise, after an untimed call of the same shape, REPS times per cell with the cells interleaved;
+the cell's figure is the median and `spread` the largest relative distance of one timing from it.  The assistants are 2, 4 and 8 layer
+models of the target's width with weights of their own (a truncated target is no valid draft, and is not what is timed here); with
+synthetic weights they agree with the target about as often as chance, which is what makes every timed round emit exactly one token
+-- the script asserts the count from the device counters -- and says NOTHING about the acceptance a trained draft model reaches.
+The other extreme is run and reported, not timed: an assistant with the target's own weights (k + 1 tokens per round).
+Next to the rounds, in the same process and interleaved with them: the plain one-stream greedy step of the same target
+(engine.generate, 200 steps per call; DESIGN.md 4.1 has 513 us for it).
+Break-even: a round must emit t_round / t_step tokens to match the plain loop.  With an independent per-draft acceptance probability
+a, a round emits (1 - a^(k+1)) / (1 - a) tokens; the table gives the a at which that equals t_round / t_step ("never" when k + 1
+tokens per round are not enough)."""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+LAYERS = (2, 4, 8)
+KS = (3, 5, 7)
+ROUNDS = 40
+STEPS = 200
+MAX_NEW = 400
+
+
+def med(xs):
+    return sorted(xs)[len(xs) // 2]
+
+
+def build(layers, seed, weights=None):
+    from genvc_amd import config as gcfg
+    from genvc_amd import synth
+    from genvc_amd.layers.gpt import GPT
+    a = dict(gcfg.DEFAULT_MODEL_ARGS, gpt_layers=layers)
+    g = GPT(layers=a["gpt_layers"], model_dim=a["gpt_n_model_channels"], heads=a["gpt_n_heads"],
+            max_text_tokens=a["gpt_max_text_tokens"], max_mel_tokens=a["gpt_max_audio_tokens"],
+            max_prompt_tokens=a["gpt_max_prompt_tokens"], number_text_tokens=a["gpt_number_text_tokens"],
+            start_text_token=a["gpt_start_text_token"], stop_text_token=a["gpt_stop_text_token"],
+            num_audio_tokens=a["gpt_num_audio_tokens"], start_audio_token=a["gpt_start_audio_token"],
+            stop_audio_token=a["gpt_stop_audio_token"], code_stride_len=a["gpt_code_stride_len"])
+    if weights is None:
+        weights = synth.make_weights(seed, synth.gpt_weight_spec(gcfg.gpt_dims(a)))
+        weights["mel_head.bias"][1025] = -30.0          # the stop token is biased away: every run takes all its rounds
+    g.load_state_dict(weights, strict=False)
+    g.to("cuda")
+    g.init_gpt_for_inference(max_slots=2)
+    return g, weights
+
+
+def break_even(tokens_needed, k):
+    """the per-draft acceptance probability a with (1 - a^(k+1)) / (1 - a) = tokens_needed, None when k + 1 tokens are not enough"""
+    if tokens_needed <= 1.0:
+        return 0.0
+    if tokens_needed >= k + 1:
+        return None
+    lo, hi = 0.0, 1.0
+    for _ in range(60):
+        a = 0.5 * (lo + hi)
+        e = sum(a ** i for i in range(k + 1))
+        lo, hi = (a, hi) if e < tokens_needed else (lo, a)
+    return 0.5 * (lo + hi)
+
+
+def measure(args):
+    import torch
+    from genvc_amd import synth
+    from genvc_amd.engine import AssistedState, sample_params
+    assert torch.cuda.is_available(), "this measurement needs the GPU"
+    target, w30 = build(30, 1)
+    twin, _ = build(30, 1, weights=w30)
+    assistants = {n: build(n, 7)[0] for n in LAYERS}
+    d = target.model_dim
+    cond = synth.uniform(300, "cond_latents", (1, 32, d), 1.0).cuda()
+    codes = synth.integers(300, "content_codes", (1, 13), 256).cuda()
+    fake = target.compute_embeddings(cond, codes)
+    for g in [twin] + list(assistants.values()):
+        g.compute_embeddings(cond, codes)
+    n0 = int(fake.shape[1])
+    assert n0 == 48
+    slots = torch.zeros(1, device="cuda", dtype=torch.int32)
+    params = sample_params(dict(repetition_penalty=1.0, temperature=1.0, top_p=1.0, top_k=1), 1026, 1025)
+    teng = target.engine
+
+    def rounds(asst, k, n_rounds):
+        """prefill both (untimed), then the opening step and n_rounds rounds in one timed call -> (us per round, state)"""
+        teng.prefill(slots, target._prefix, want_outputs=False)
+        asst.engine.prefill(slots, asst._prefix, want_outputs=False)
+        st = AssistedState(fake, k, MAX_NEW, 1025, 1026, d)
+        reach = 1 + n_rounds * (k + 1) + k
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        teng.generate_assisted(asst.engine, slots, slots, st, params, n_rounds, n0 + reach, n0 + reach)
+        e1.record()
+        torch.cuda.synchronize()
+        teng.health()
+        asst.engine.health()
+        return e0.elapsed_time(e1) * 1000.0 / n_rounds, st
+
+    def plain():
+        teng.prefill(slots, target._prefix, want_outputs=False)
+        ids = torch.ones(1, n0 + STEPS + 8, device="cuda", dtype=torch.int32)
+        ids[:, n0 - 1] = 1024
+        ids_len = torch.full((1,), n0, device="cuda", dtype=torch.int32)
+        fin = torch.zeros(1, device="cuda", dtype=torch.int32)
+        toks = torch.zeros(1, STEPS, device="cuda", dtype=torch.int32)
+        lats = torch.zeros(1, STEPS, d, device="cuda")
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        teng.generate(slots, ids, ids_len, fin, params, 0, STEPS, toks, lats, max_keys=n0 + STEPS)
+        e1.record()
+        torch.cuda.synchronize()
+        teng.health()
+        return e0.elapsed_time(e1) * 1000.0 / STEPS, toks
+
+    # the other extreme, checked and reported (not timed): the target's own weights as the assistant
+    plain_toks = plain()[1][0, :40].tolist()
+    plain_variant = teng.decode_variant()
+    twin_rows = []
+    for k in KS:
+        _, st = rounds(twin, k, 3)
+        s = st.stats()
+        n = int(st.emitted[0])
+        twin_rows.append(dict(k=k, rounds=3, drafted=int(s["drafted"][0]), accepted=int(s["accepted"][0]), emitted=n,
+                              tokens_equal_plain=st.toks[0, :n].tolist() == plain_toks[:n]))
+    cells = {(n, k): [] for n in LAYERS for k in KS}
+    steps = []
+    for n, k in cells:          # untimed: every shape once
+        rounds(assistants[n], k, ROUNDS)
+    plain()
+    accepted = {}
+    for _ in range(args.reps):
+        steps.append(plain()[0])
+        for (n, k), xs in cells.items():
+            us, st = rounds(assistants[n], k, ROUNDS)
+            xs.append(us)
+            accepted[(n, k)] = int(st.stats()["accepted"][0])
+            assert int(st.emitted[0]) == 1 + ROUNDS + accepted[(n, k)] and int(st.stats()["rounds"][0]) == ROUNDS
+    t_step = med(steps)
+    res = dict(device=torch.cuda.get_device_name(0), n0=n0, rounds_per_call=ROUNDS, steps_per_plain_call=STEPS, reps=args.reps,
+               plain_us_per_step=t_step, plain_runs=steps, plain_spread=max(abs(x - t_step) / t_step for x in steps),
+               plain_variant=plain_variant, own_weights_assistant=twin_rows, cells=[])
+    for (n, k), xs in cells.items():
+        t = med(xs)
+        res["cells"].append(dict(assistant_layers=n, k=k, us_per_round=t, spread=max(abs(x - t) / t for x in xs), runs=xs,
+                                 us_per_token_acceptance_0=t, us_per_token_full_acceptance=t / (k + 1),
+                                 tokens_per_round_to_break_even=t / t_step, break_even_acceptance=break_even(t / t_step, k),
+                                 accepted_in_last_timed_call=accepted[(n, k)]))
+    return res
+
+
+RATES = (0.5, 0.6, 0.7, 0.8, 0.9)
+
+
+def render(res):
+    """the markdown report of a measurement (every figure in it is computed from `res`)"""
+    t_step = res["plain_us_per_step"]
+    lines = ["# Assisted (speculative) greedy decoding: the cost of a round", "",
+             f"`scripts/assisted_bench.py` on one MI355X (device name as the runtime reports it: {res['device']}): 30 layers, d_model 1024, "
+             f"fp32, one stream, a {res['n0']}-row prompt; {res['rounds_per_call']} rounds per timed call, {res['reps']} timed calls per "
+             "cell (median; `spread` is the largest relative distance of one call from it), cells interleaved with the plain loop in one "
+             "process.", "",
+             f"Plain one-stream greedy step of the same target, same run: **{t_step:.1f} us** per token over "
+             f"{res['steps_per_plain_call']} steps, sampler included (spread {res['plain_spread']:.2%}; DESIGN.md 4.1 has 513 us for the "
+             "decode step alone at the headline workload's context lengths).", "",
+             "A round = k + 1 assistant decode steps + one (k + 1)-row verification pass + accept + two rollbacks, launched directly "
+             "(no graph).  Its work is the same whatever is accepted: at acceptance 0 it emits 1 token, at full acceptance k + 1.", "",
+             "| assistant layers | k | us / round | spread | us / token, acceptance 0 | us / token, full acceptance | tokens / round to "
+             "break even | break-even per-draft acceptance |", "|---|---|---|---|---|---|---|---|"]
+    for c in res["cells"]:
+        t, k, a = c["us_per_round"], c["k"], c["break_even_acceptance"]
+        lines.append(f"| {c['assistant_layers']} | {k} | {t:.0f} | {c['spread']:.2%} | {t:.0f} | {t / (k + 1):.0f} | {t / t_step:.2f} | "
+                     f"{'never' if a is None else f'{a:.2f}'} |")
+    lines += ["", "Break-even: a round has to emit (us / round) / (plain us / token) tokens; the last column is the independent per-draft "
+              "acceptance probability a at which (1 - a^(k+1)) / (1 - a) reaches that.", "",
+              "Expected us per token, (us / round) / ((1 - a^(k+1)) / (1 - a)), at a per-draft acceptance a (computed from the table above; "
+              f"the plain loop is {t_step:.0f}):", "", "| assistant layers | k | " + " | ".join(f"a = {a}" for a in RATES) + " |",
+              "|---|---|" + "---|" * len(RATES)]
+    for c in res["cells"]:
+        k = c["k"]
+        lines.append(f"| {c['assistant_layers']} | {k} | " +
+                     " | ".join(f"{c['us_per_round'] / sum(a ** i for i in range(k + 1)):.0f}" for a in RATES) + " |")
+    acc = sorted({c["accepted_in_last_timed_call"] for c in res["cells"]})
+    # the default k: the one whose expected cost is never far from the best of the measured three, over every (size, a) at which
+    # assisted decoding beats the plain loop at all
+    exp = {(c["assistant_layers"], c["k"], a): c["us_per_round"] / sum(a ** i for i in range(c["k"] + 1)) for c in res["cells"] for a in RATES}
+    sizes, ks = sorted({c["assistant_layers"] for c in res["cells"]}), sorted({c["k"] for c in res["cells"]})
+    regret = {k: 0.0 for k in ks}
+    for n in sizes:
+        for a in RATES:
+            best = min(exp[(n, k, a)] for k in ks)
+            if best < t_step:
+                for k in ks:
+                    regret[k] = max(regret[k], exp[(n, k, a)] / best - 1.0)
+    pick = min(ks, key=lambda k: regret[k])
+    lines += ["", "Reading for the default `num_assistant_tokens`: over every (assistant size, a) above at which some k beats the plain "
+              "loop, the worst excess of a k over the best of the three is " + ", ".join(f"k = {k}: +{regret[k]:.0%}" for k in ks) +
+              f".  k = {pick} is never far from the best; small k wins at low acceptance, large k at high.  GPT.generate's default is 5.",
+              "", "The weights are synthetic.  The unrelated assistants agree with the target about as often as chance (the timed calls "
+              f"accepted {acc} drafts in {res['rounds_per_call']} rounds), and an assistant with the target's own weights gave " +
+              "; ".join(f"k = {r['k']}: {r['accepted']} of {r['drafted']} drafts accepted, {r['emitted']} tokens in {r['rounds']} rounds, "
+                        f"tokens {'equal to' if r['tokens_equal_plain'] else 'DIFFERENT from'} the plain loop's"
+                        for r in res["own_weights_assistant"]) +
+              ".  These pin the two ends of the range and say nothing about the acceptance rate a trained draft model would reach."]
+    return "\n".join(lines) + "\n"
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "assisted_decoding.md"))
+    ap.add_argument("--json", default=os.path.join(ROOT, "profiles", "assisted_decoding.json"))
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--render", action="store_true", help="no measurement: write --out again from the figures in --json")
+    args = ap.parse_args()
+    if args.render:
+        with open(args.json) as f:
+            res = json.load(f)
+    else:
+        res = measure(args)
+        with open(args.json, "w") as f:
+            json.dump(res, f, indent=1)
+    text = render(res)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write(text)
+    print(text)
+
+
+if __name__ == "__main__":
+    main()
