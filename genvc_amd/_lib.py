@@ -80,6 +80,11 @@ class SpecState(C.Structure):
                                    "rounds", "drafted", "accepted", "v_toks", "v_logits", "v_latents", "d_ids_len", "d_finished")]
 
 
+class SpecSampling(C.Structure):
+    """gvc_spec_sampling (include/genvc_hip.h): the device workspaces of a sampled assisted generation (24 bytes)"""
+    _fields_ = [(n, C.c_void_p) for n in ("q_scores", "p_scores", "rows")]
+
+
 class PerceiverDims(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("dim", "depth", "dim_context", "num_latents", "dim_head", "heads",
                                          "ff_mult", "max_batch", "max_frames")]
@@ -179,6 +184,11 @@ _SIGNATURES = {
                                   C.POINTER(LogitsProcessors), _P]),
     "gvc_gpt_generate_assisted": (C.c_int, [_P, _P, _P, _P, C.POINTER(SpecState), C.POINTER(SampleParams), C.POINTER(LogitsProcessors),
                                             C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
+    "gvc_spec_accept_sample": (C.c_int, [C.POINTER(SpecState), C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, _P, _P,
+                                         C.POINTER(SampleParams), C.POINTER(LogitsProcessors), _P]),
+    "gvc_gpt_generate_assisted_sample": (C.c_int, [_P, _P, _P, _P, C.POINTER(SpecState), C.POINTER(SpecSampling), C.POINTER(SampleParams),
+                                                   C.POINTER(LogitsProcessors), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                   _P]),
     "gvc_gpt_decode_variant": (C.c_int, [_P]),
     "gvc_gpt_rows_step_launches": (C.c_longlong, [_P]),
     "gvc_gpt_one_stream_steps": (C.c_longlong, [_P]),

@@ -2224,14 +2224,18 @@ extern "C" int gvc_gpt_truncate(gvc_gpt* c, const int32_t* slots, int32_t B, con
     return launch_spec_truncate(c->st.seq_len, c->st.mel_pos, slots, B, drop, s);
 }
 
-extern "C" int gvc_gpt_generate_assisted(gvc_gpt* c, gvc_gpt* a, const int32_t* slots, const int32_t* aslots, const gvc_spec_state* st,
-                                         const gvc_sample_params* p, const gvc_logits_processors* proc, int32_t first, int32_t n_rounds,
-                                         int32_t k, int32_t max_keys, int32_t a_max_keys, gvc_stream sv) {
+// The round loop behind gvc_gpt_generate_assisted (ss null: greedy) and gvc_gpt_generate_assisted_sample (ss: the workspaces of
+// speculative sampling; the draft steps run the full sampler on keyed rows and store their warped rows, the accept step is
+// launch_spec_accept_sample)
+static int assisted_rounds(gvc_gpt* c, gvc_gpt* a, const int32_t* slots, const int32_t* aslots, const gvc_spec_state* st,
+                           const gvc_spec_sampling* ss, const gvc_sample_params* p, const gvc_logits_processors* proc, int32_t first,
+                           int32_t n_rounds, int32_t k, int32_t max_keys, int32_t a_max_keys, gvc_stream sv) {
     int rc = check_ready(c);
     if (rc) return rc;
     if ((rc = check_ready(a))) return rc;
     GVC_REQUIRE(c != a && slots && aslots, GVC_ERR_ARG, "generate_assisted: the target and the assistant are two contexts with a slot list each");
     if ((rc = check_spec_state(st, k, p, proc, true))) return rc;
+    if (ss && (rc = check_spec_sampling(ss->q_scores, ss->p_scores, ss->rows, true, p))) return rc;
     const gvc_spec_state& S = *st;
     const int B = S.B, V = c->dm.vocab, d = c->dm.d_model;
     GVC_REQUIRE(k >= 1 && n_rounds >= 0, GVC_ERR_ARG, "generate_assisted: k=%d below 1 or n_rounds=%d below 0", k, n_rounds);
@@ -2246,17 +2250,19 @@ extern "C" int gvc_gpt_generate_assisted(gvc_gpt* c, gvc_gpt* a, const int32_t* 
     if (rows_persist_ok(c, B * (k + 1), c->st.seq_len) && (rc = rows_persist_prepare(c))) return rc;
     c->rows_keys_hint = max_keys;
     GenPlan apl;
-    if ((rc = plan_generate(a, B, a_max_keys, 1, &apl))) return rc;
+    if ((rc = plan_generate(a, B, a_max_keys, ss ? p->top_k : 1, &apl))) return rc;
     a->last_variant = apl.variant;
     if ((rc = flush_pending(c, slots, B, s)) || (rc = flush_pending(a, aslots, B, s))) return rc;
     gvc_sample_params gp = *p;
-    gp.top_k = 1;
+    if (!ss) gp.top_k = 1;
     if (first) {
-        // token 0 of every row: the target's greedy choice from the logits and latent its prefill parked
+        // token 0 of every row: the target's choice (greedy, or drawn with u_res(0)) from the logits and latent its prefill parked
         hipLaunchKernelGGL(k_stage_rows, dim3(B), dim3(256), 0, s, S.v_logits, c->slot_logits, slots, V, 0);
         hipLaunchKernelGGL(k_stage_rows, dim3(B), dim3(256), 0, s, S.v_latents, c->slot_latent, slots, d, 0);
         GVC_LAUNCH_CHECK();
-        if ((rc = launch_spec_accept(S, 0, 0, S.v_logits, S.v_latents, nullptr, 0, gp, proc, s))) return rc;
+        if (ss) rc = launch_spec_accept_sample(S, 0, 0, S.v_logits, S.v_latents, nullptr, 0, false, nullptr, ss->p_scores, gp, proc, s);
+        else rc = launch_spec_accept(S, 0, 0, S.v_logits, S.v_latents, nullptr, 0, gp, proc, s);
+        if (rc) return rc;
     }
     // the draft sampler: the sampler's greedy kernel on the assistant's logits, with the call's settings, on the rows' own ids (it
     // writes d_j where the accept step writes it again) but lengths and finished flags of its own; d_j lands in row j of v_toks
@@ -2265,6 +2271,11 @@ extern "C" int gvc_gpt_generate_assisted(gvc_gpt* c, gvc_gpt* a, const int32_t* 
     dsc.logits = a->logits; dsc.B = B; dsc.ids = S.ids; dsc.ids_stride = S.ids_stride; dsc.ids_len = S.d_ids_len;
     dsc.finished = S.d_finished; dsc.p = gp; dsc.step_ptr = a->step_ctr; dsc.tok_out = a->tok_buf;
     dsc.tokens_out = S.v_toks; dsc.tok_stride = k + 1; dsc.i0 = 1; dsc.d = a->dm.d_model;
+    if (ss) {
+        // the full sampler on device-resident keyed rows (the round-begin launch writes them); the row d_j is drawn from lands in row
+        // j of q_scores, as d_j lands in column j of v_toks
+        dsc.rows = ss->rows; dsc.scores_out = ss->q_scores; dsc.scores_warped = 1; dsc.out_stride = k + 1;
+    }
     if (proc) {
         static const int32_t zeros[kMaxSampleRows] = {};
         GVC_REQUIRE(B <= kMaxSampleRows, GVC_ERR_ARG, "generate_assisted: processors serve up to %d streams", kMaxSampleRows);
@@ -2273,7 +2284,7 @@ extern "C" int gvc_gpt_generate_assisted(gvc_gpt* c, gvc_gpt* a, const int32_t* 
     }
     for (int r = 0; r < n_rounds; ++r) {
         // 1. k + 1 decode steps of the assistant: the pending token, then [sample d_j, decode d_j] for j = 1..k
-        if ((rc = launch_spec_round_begin(S, k + 1, a->step_ctr, s))) return rc;
+        if ((rc = launch_spec_round_begin(S, k + 1, a->step_ctr, ss ? ss->rows : nullptr, gp, s))) return rc;
         if ((rc = decode_step(a, aslots, B, S.pending, a->logits, a->latent, nullptr, s, apl.fused, apl.key_chunks))) return rc;
         for (int j = 0; j < k; ++j) {
             if ((rc = launch_sample(dsc, s))) return rc;
@@ -2281,11 +2292,29 @@ extern "C" int gvc_gpt_generate_assisted(gvc_gpt* c, gvc_gpt* a, const int32_t* 
         }
         // 2. - 4. one pass of the target over [pending, d_1..d_k], the accept step, and both caches rolled back
         if ((rc = verify_rows(c, slots, B, S.v_toks, k + 1, S.v_logits, S.v_latents, s))) return rc;
-        if ((rc = launch_spec_accept(S, k, k + 1, S.v_logits, S.v_latents, S.v_toks + 1, k + 1, gp, proc, s))) return rc;
+        if (ss) rc = launch_spec_accept_sample(S, k, k + 1, S.v_logits, S.v_latents, S.v_toks + 1, k + 1, false, ss->q_scores, ss->p_scores,
+                                               gp, proc, s);
+        else rc = launch_spec_accept(S, k, k + 1, S.v_logits, S.v_latents, S.v_toks + 1, k + 1, gp, proc, s);
+        if (rc) return rc;
         if ((rc = launch_spec_truncate(c->st.seq_len, c->st.mel_pos, slots, B, S.drop_target, s))) return rc;
         if ((rc = launch_spec_truncate(a->st.seq_len, a->st.mel_pos, aslots, B, S.drop_assistant, s))) return rc;
     }
     return GVC_OK;
+}
+
+extern "C" int gvc_gpt_generate_assisted(gvc_gpt* c, gvc_gpt* a, const int32_t* slots, const int32_t* aslots, const gvc_spec_state* st,
+                                         const gvc_sample_params* p, const gvc_logits_processors* proc, int32_t first, int32_t n_rounds,
+                                         int32_t k, int32_t max_keys, int32_t a_max_keys, gvc_stream sv) {
+    return assisted_rounds(c, a, slots, aslots, st, nullptr, p, proc, first, n_rounds, k, max_keys, a_max_keys, sv);
+}
+
+extern "C" int gvc_gpt_generate_assisted_sample(gvc_gpt* c, gvc_gpt* a, const int32_t* slots, const int32_t* aslots,
+                                                const gvc_spec_state* st, const gvc_spec_sampling* ss, const gvc_sample_params* p,
+                                                const gvc_logits_processors* proc, int32_t first, int32_t n_rounds, int32_t k,
+                                                int32_t max_keys, int32_t a_max_keys, gvc_stream sv) {
+    GVC_REQUIRE(ss, GVC_ERR_ARG, "generate_assisted_sample: null sampling workspaces");
+    GVC_REQUIRE(p && p->top_k != 1, GVC_ERR_ARG, "generate_assisted_sample: top_k == 1 is the greedy call (gvc_gpt_generate_assisted)");
+    return assisted_rounds(c, a, slots, aslots, st, ss, p, proc, first, n_rounds, k, max_keys, a_max_keys, sv);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -1,7 +1,13 @@
-// Assisted (speculative) greedy decoding on the device (include/genvc_hip.h: gvc_gpt_verify, gvc_gpt_truncate, gvc_spec_accept,
-// gvc_gpt_generate_assisted): the input rows and length bookkeeping of a multi-row verification pass, the rollback of a slot, and the
-// accept step.  The block stack and the head of the verification are the context's own (gpt.hip: run_rows, launch_head); the round
-// loop that chains them with the draft context's decode steps lives there too.
+// Assisted (speculative) decoding on the device, greedy and sampled (include/genvc_hip.h: gvc_gpt_verify, gvc_gpt_truncate,
+// gvc_spec_accept, gvc_spec_accept_sample, gvc_gpt_generate_assisted, gvc_gpt_generate_assisted_sample): the input rows and length
+// bookkeeping of a multi-row verification pass, the rollback of a slot, and the accept steps.  The block stack and the head of the
+// verification are the context's own (gpt.hip: run_rows, launch_head); the round loop that chains them with the draft context's decode
+// steps lives there too.
+//
+// Speculative sampling draws with counters keyed by POSITION, not by round: row b deciding token t (0-based within the generation) uses
+// u_draft(t) = rng_uniform(seed, t, 3b), u_acc(t) = rng_uniform(seed, t, 3b + 1), u_res(t) = rng_uniform(seed, t, 3b + 2), so a result does
+// not depend on how rounds are grouped into calls.  The uniforms of a position that was drafted behind a rejection are reused when
+// that position is drafted again: they were never looked at by anything that was kept, so the draws stay independent.
 #pragma once
 #include "common.h"
 
@@ -25,10 +31,20 @@ int launch_spec_advance(int32_t* seq_len, int32_t* mel_pos_idx, const int32_t* s
 int launch_spec_truncate(int32_t* seq_len, int32_t* mel_pos_idx, const int32_t* slots, int B, const int32_t* drop, hipStream_t s);
 // start of a round on the draft side: the draft sampler's own row lengths and finished flags start from the target's, its step
 // counter from 0, and row 0 of every stream's verification tokens is the pending token
-int launch_spec_round_begin(const gvc_spec_state& st, int k1, int32_t* step_ctr, hipStream_t s);
+// rows (nullable; a sampled generation): the draft sampler's keyed row of every stream as well -- the call's settings p, p.seed,
+// rng_row = 3 b, rng_step0 = emitted[b]
+int launch_spec_round_begin(const gvc_spec_state& st, int k1, int32_t* step_ctr, gvc_row_sampling* rows, const gvc_sample_params& p,
+                            hipStream_t s);
 // the accept step (include/genvc_hip.h: gvc_spec_accept); the arguments are checked by the callers
 int launch_spec_accept(const gvc_spec_state& st, int k, int appended, const float* logits, const float* latents, const int32_t* drafts,
                        int draft_stride, const gvc_sample_params& p, const gvc_logits_processors* proc, hipStream_t s);
+// the accept step of speculative sampling (include/genvc_hip.h: gvc_spec_accept_sample): [d_1..d_k' behind the rows' ids when
+// put_drafts,] k_spec_warp of the B * (k + 1) logits rows into p_rows, then k_spec_accept_sample; the arguments are checked by the callers
+int launch_spec_accept_sample(const gvc_spec_state& st, int k, int appended, const float* logits, const float* latents,
+                              const int32_t* drafts, int draft_stride, bool put_drafts, const float* q, float* p_rows,
+                              const gvc_sample_params& p, const gvc_logits_processors* proc, hipStream_t s);
+// host-side checks of a sampled call: the workspaces (rows only when need_rows), top_k <= vocab, temperature and repetition penalty > 0
+int check_spec_sampling(const float* q, const float* p_rows, const gvc_row_sampling* rows, bool need_rows, const gvc_sample_params* p);
 // host-side checks of a state and a call's k
 int check_spec_state(const gvc_spec_state* st, int k, const gvc_sample_params* p, const gvc_logits_processors* proc, bool workspace);
 

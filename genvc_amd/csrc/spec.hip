@@ -1,9 +1,20 @@
-// Assisted (speculative) greedy decoding: the kernels around a verification pass and the accept step (spec.h).  The accept step
+// Assisted (speculative) decoding: the kernels around a verification pass and the accept steps (spec.h).  The greedy accept step
 // restates nothing of the sampler: the repetition penalty is k_sample_greedy's expression and the processors are logits_proc.h's
-// device functions, run once per verified position at the length the row has there.
+// device functions, run once per verified position at the length the row has there.  Speculative sampling restates nothing either:
+// k_spec_warp IS the sampler's chain (sample_body.h: sample_row<true>) on the k + 1 verification rows, and the draft's rows come
+// from k_sample itself (SampleCall::scores_out).  k_spec_accept_sample only compares and draws.
+//
+// RNG of a sampled generation: counters are keyed by POSITION, not by round.  Deciding token t (0-based index within the generation)
+// of row b uses  u_draft(t) = rng_uniform(seed, t, 3b)  for the draft's draw,  u_acc(t) = rng_uniform(seed, t, 3b + 1)  for the accept
+// test and  u_res(t) = rng_uniform(seed, t, 3b + 2)  for the residual / bonus / opening draw, so a result does not depend on how rounds
+// are grouped into calls.  A position that was drafted BEHIND a rejection is drafted again in a later round with the same u_draft,
+// u_acc and u_res: none of them was ever looked at by a decision that was kept (the draft tokens behind a rejection are discarded
+// unread, and the accept loop stops at the rejection), so every uniform that reaches an emitted token is used for exactly one
+// decision and the draws stay independent.
 #include "spec.h"
 
 #include "logits_proc.h"
+#include "sample_body.h"
 
 namespace gvc {
 
@@ -46,13 +57,20 @@ __global__ void k_spec_truncate(int32_t* seq_len, int32_t* mel_pos_idx, const in
     mel_pos_idx[slot] = max(mel_pos_idx[slot] - n, 0);
 }
 
-__global__ void k_spec_round_begin(gvc_spec_state S, int k1, int32_t* step_ctr) {
+__global__ void k_spec_round_begin(gvc_spec_state S, int k1, int32_t* step_ctr, gvc_row_sampling* rows, gvc_sample_params p) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b == 0) *step_ctr = 0;
     if (b >= S.B) return;
     S.d_ids_len[b] = S.ids_len[b];
     S.d_finished[b] = S.finished[b];
     S.v_toks[(size_t)b * k1] = S.pending[b];
+    if (rows) {
+        // the draft sampler's keyed row: the call's settings, and u_draft of the position its first draft decides
+        gvc_row_sampling r;
+        r.repetition_penalty = p.repetition_penalty; r.temperature = p.temperature; r.top_p = p.top_p; r.top_k = p.top_k;
+        r.seed = p.seed; r.rng_row = 3 * b; r.rng_step0 = S.emitted[b];
+        rows[b] = r;
+    }
 }
 
 // the call's processors BY VALUE as a kernel argument (the caller's struct is free when the launch is enqueued)
@@ -166,6 +184,225 @@ __global__ __launch_bounds__(kSpecThreads) void k_spec_accept(gvc_spec_state S, 
     }
 }
 
+// ---- speculative sampling ---------------------------------------------------------------------------------------------------------
+// d_1..d_k' behind the ids of every live row (the draft sampler has put them there in a generation; gvc_spec_accept_sample alone has
+// only the draft array)
+__global__ void k_spec_put_drafts(gvc_spec_state S, int k, const int32_t* drafts, int draft_stride) {
+    const int b = blockIdx.x, em0 = S.emitted[b];
+    if (S.finished[b] || em0 >= S.max_new) return;
+    const int kk = min(k, S.max_new - em0 - 1), len0 = S.ids_len[b];
+    for (int j = threadIdx.x; j < kk; j += blockDim.x)
+        if (len0 + j < S.ids_stride) S.ids[(size_t)b * S.ids_stride + len0 + j] = drafts[(size_t)b * draft_stride + j];
+}
+
+// p_i of verification row (b, i): the sampler's chain at ids length ids_len[b] + i, stored as the sampler stores scores_out.  One
+// workgroup per row, so the sorts of a stream run side by side.  Rows of finished streams and rows behind the k' drafts the accept
+// step compares return at once
+__global__ __launch_bounds__(kSampThreads) void k_spec_warp(gvc_spec_state S, int k, const float* logits, float* p_out, gvc_sample_params p,
+                                                            SpecProc pr) {
+    const int r = blockIdx.x, b = r / (k + 1), i = r - b * (k + 1);
+    const int em0 = S.emitted[b];
+    if (S.finished[b] || em0 >= S.max_new || i > min(k, S.max_new - em0 - 1)) return;          // (uniform over the workgroup)
+    SampleCall C = {};
+    C.p = p;
+    C.scores_warped = 1;
+    sample_row<true>(C, b, logits + (size_t)r * p.vocab, S.ids + (size_t)b * S.ids_stride, min(S.ids_len[b] + i, S.ids_stride),
+                     pr.on ? &pr.P : nullptr, p_out + (size_t)r * p.vocab, 0);
+}
+
+constexpr int kSpecPer = kSpecMaxVocab / kSpecThreads;          // 8 consecutive vocabulary entries per thread
+
+// entries [8 tid, 8 tid + 8) of a scores row, -inf past the vocabulary; vector loads where the row's alignment allows
+__device__ __forceinline__ void spec_load8(const float* row, int V, int tid, float* s) {
+    const int i0 = tid * kSpecPer;
+    const uintptr_t a = reinterpret_cast<uintptr_t>(row);
+    if (i0 + kSpecPer <= V && (a & 15) == 0) {
+        const float4 x = *reinterpret_cast<const float4*>(row + i0), y = *reinterpret_cast<const float4*>(row + i0 + 4);
+        s[0] = x.x; s[1] = x.y; s[2] = x.z; s[3] = x.w; s[4] = y.x; s[5] = y.y; s[6] = y.z; s[7] = y.w;
+    } else if (i0 + kSpecPer <= V && (a & 7) == 0) {
+#pragma unroll
+        for (int u = 0; u < kSpecPer; u += 2) {
+            const float2 x = *reinterpret_cast<const float2*>(row + i0 + u);
+            s[u] = x.x; s[u + 1] = x.y;
+        }
+    } else {
+#pragma unroll
+        for (int u = 0; u < kSpecPer; ++u) s[u] = i0 + u < V ? row[i0 + u] : -INFINITY;
+    }
+}
+
+// maxima of (a, b) over the workgroup of kSpecThreads; scr: [8] floats
+__device__ __forceinline__ void spec_max2(float& a, float& b, float* scr) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) { a = fmaxf(a, __shfl_xor(a, off)); b = fmaxf(b, __shfl_xor(b, off)); }
+    __syncthreads();                         // scr may still be read from the row before
+    if (lane == 0) { scr[wave] = a; scr[4 + wave] = b; }
+    __syncthreads();
+    a = fmaxf(fmaxf(scr[0], scr[1]), fmaxf(scr[2], scr[3]));
+    b = fmaxf(fmaxf(scr[4], scr[5]), fmaxf(scr[6], scr[7]));
+}
+
+// exclusive prefix sums of (a, b) per thread over the workgroup of kSpecThreads in thread order (= vocabulary order); the totals in
+// ta / tb.  scr: [8] doubles
+__device__ __forceinline__ void spec_scan2(double& a, double& b, double* scr, double* ta, double* tb) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    double ia = a, ib = b;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const double oa = __shfl_up(ia, off), ob = __shfl_up(ib, off);
+        if (lane >= off) { ia += oa; ib += ob; }
+    }
+    __syncthreads();                         // scr may still be read from the scan before
+    if (lane == 63) { scr[wave] = ia; scr[4 + wave] = ib; }
+    __syncthreads();
+    double ba = 0.0, bb = 0.0, sa = 0.0, sb = 0.0;
+#pragma unroll
+    for (int w = 0; w < kSpecThreads / 64; ++w) {
+        if (w < wave) { ba += scr[w]; bb += scr[4 + w]; }
+        sa += scr[w]; sb += scr[4 + w];
+    }
+    a = ba + ia - a; b = bb + ib - b;
+    *ta = sa; *tb = sb;
+}
+
+// The accept rule of speculative sampling (include/genvc_hip.h: gvc_spec_accept_sample), one workgroup per stream.  q / p: the warped
+// rows [B][k + 1][vocab] of the draft (row j: what d_j was drawn from) and of the target (row i: verification row i).  Only the rows up
+// to the first rejection are read.  The bookkeeping is k_spec_accept's, field for field
+__global__ __launch_bounds__(kSpecThreads) void k_spec_accept_sample(gvc_spec_state S, int k, int appended, const float* latents,
+                                                                     const int32_t* drafts, int draft_stride, const float* q,
+                                                                     const float* p, gvc_sample_params sp) {
+    __shared__ double dscr[8];
+    __shared__ float fscr[8];
+    __shared__ int s_pick, s_last, s_acc;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int V = sp.vocab, eos = sp.eos_token;
+    const int len0 = S.ids_len[b], em0 = S.emitted[b];
+    // (uniform over the workgroup: a finished row leaves before the first barrier)
+    if (S.finished[b] || em0 >= S.max_new) {
+        if (tid == 0) {
+            S.finished[b] = 1;
+            S.drop_target[b] = appended;
+            S.drop_assistant[b] = appended;
+        }
+        return;
+    }
+    int32_t* ids = S.ids + (size_t)b * S.ids_stride;
+    const int32_t* dr = drafts ? drafts + (size_t)b * draft_stride : nullptr;
+    const int kk = dr ? min(k, S.max_new - em0 - 1) : 0;
+    const int i0 = tid * kSpecPer;
+    int m = 0, acc = 0, last = eos;
+    bool fin = false;
+    for (int i = 0; i <= kk; ++i) {
+        const size_t r = (size_t)b * (k + 1) + i;
+        const bool hasq = i < kk;
+        float ps[kSpecPer], qs[kSpecPer];
+        spec_load8(p + r * V, V, tid, ps);
+        if (hasq) spec_load8(q + (r + 1) * V, V, tid, qs);
+        else {
+#pragma unroll
+            for (int u = 0; u < kSpecPer; ++u) qs[u] = -INFINITY;
+        }
+        float pm = -INFINITY, qm = -INFINITY;
+#pragma unroll
+        for (int u = 0; u < kSpecPer; ++u) { pm = fmaxf(pm, ps[u]); qm = fmaxf(qm, qs[u]); }
+        spec_max2(pm, qm, fscr);
+        // the sampler's weights: expf(s - max) in fp32 for kept entries, summed in double in vocabulary order
+        float wp[kSpecPer], wq[kSpecPer];
+        double exP = 0.0, exQ = 0.0, totP, totQ;
+#pragma unroll
+        for (int u = 0; u < kSpecPer; ++u) {
+            wp[u] = ps[u] > -INFINITY ? expf(ps[u] - pm) : 0.f;
+            wq[u] = qs[u] > -INFINITY ? expf(qs[u] - qm) : 0.f;
+            exP += (double)wp[u]; exQ += (double)wq[u];
+        }
+        spec_scan2(exP, exQ, dscr, &totP, &totQ);
+        const int x = hasq ? dr[i] : -1;
+        bool ok = false;
+        if (hasq) {
+            if (tid == 0) s_acc = 0;          // (a draft outside the vocabulary is rejected)
+            __syncthreads();
+            if (x >= 0 && x < V && (x >> 3) == tid) {
+                double px = 0.0, qx = 0.0;
+#pragma unroll
+                for (int u = 0; u < kSpecPer; ++u)
+                    if (u == (x & 7)) { px = (double)wp[u] / totP; qx = (double)wq[u] / totQ; }
+                const double rr = (double)rng_uniform(sp.seed, (uint64_t)(em0 + i), (uint64_t)(3 * b + 1));
+                s_acc = rr * qx <= px ? 1 : 0;          // no division by q: q(x) == 0 accepts
+            }
+            __syncthreads();
+            ok = s_acc != 0;
+        }
+        int tok = x;
+        if (!ok) {
+            // one token from max(p - q, 0) behind a rejection (from p when that is empty), from p behind k' accepted drafts
+            double w[kSpecPer], ex = 0.0, tot = 0.0, unused_a = 0.0, unused_t;
+            bool resid = false;
+            if (hasq) {
+#pragma unroll
+                for (int u = 0; u < kSpecPer; ++u) {
+                    w[u] = fmax((double)wp[u] / totP - (double)wq[u] / totQ, 0.0);
+                    ex += w[u];
+                }
+                spec_scan2(ex, unused_a, dscr, &tot, &unused_t);
+                resid = tot > 0.0;          // (uniform: every thread holds the same total)
+            }
+            if (!resid) {
+#pragma unroll
+                for (int u = 0; u < kSpecPer; ++u) w[u] = (double)wp[u];
+                ex = exP; tot = totP;
+            }
+            const double target = (double)rng_uniform(sp.seed, (uint64_t)(em0 + i), (uint64_t)(3 * b + 2)) * tot;
+            // the sampler's inverse-CDF rule: the first kept index whose running mass reaches the target, else the last kept index
+            int pick = 0x7fffffff, lastk = -1;
+            double a = ex;
+#pragma unroll
+            for (int u = 0; u < kSpecPer; ++u) {
+                a += w[u];
+                const bool kept = resid ? w[u] > 0.0 : ps[u] > -INFINITY;
+                if (kept) { lastk = i0 + u; if (a >= target && pick == 0x7fffffff) pick = i0 + u; }
+            }
+            if (tid == 0) { s_pick = 0x7fffffff; s_last = -1; }
+            __syncthreads();
+            if (pick != 0x7fffffff) atomicMin(&s_pick, pick);
+            if (lastk >= 0) atomicMax(&s_last, lastk);
+            __syncthreads();
+            tok = s_pick != 0x7fffffff ? s_pick : (s_last >= 0 ? s_last : 0);
+        }
+        if (tid == 0) {
+            S.toks[(size_t)b * S.tok_stride + em0 + m] = tok;
+            if (len0 + i < S.ids_stride) ids[len0 + i] = tok;
+        }
+        last = tok;
+        ++m;
+        if (last == eos) { fin = true; break; }
+        if (ok) ++acc;
+        else break;
+    }
+    if (tid == 0) {
+        S.ids_len[b] = min(len0 + m, S.ids_stride);
+        S.emitted[b] = em0 + m;
+        S.pending[b] = last;
+        S.finished[b] = (fin || em0 + m >= S.max_new) ? 1 : 0;
+        const int drop = appended > 0 ? appended - m : 0;
+        S.drop_target[b] = drop;
+        S.drop_assistant[b] = drop;
+        if (appended > 0) {
+            if (S.rounds) S.rounds[b] += 1;
+            if (S.drafted) S.drafted[b] += kk;
+            if (S.accepted) S.accepted[b] += acc;
+        }
+    }
+    if (S.lats && latents) {
+        for (int j = 0; j < m; ++j) {
+            const float* src = latents + ((size_t)b * (k + 1) + j) * S.d;
+            float* dst = S.lats + ((size_t)b * S.lat_stride + em0 + j) * S.d;
+            for (int c = tid * 4; c < S.d; c += kSpecThreads * 4)
+                *reinterpret_cast<float4*>(dst + c) = *reinterpret_cast<const float4*>(src + c);
+        }
+    }
+}
+
 int launch_spec_embed(float* x, const int32_t* toks, const int32_t* slots, int B, int T, const int32_t* seq_len, const int32_t* mel_pos_idx,
                       const float* mel_emb, const float* mel_pos, int d, int vocab, int max_seq, int max_mel_pos, int32_t* base_out,
                       int* err, hipStream_t s) {
@@ -188,8 +425,9 @@ int launch_spec_truncate(int32_t* seq_len, int32_t* mel_pos_idx, const int32_t* 
     return GVC_OK;
 }
 
-int launch_spec_round_begin(const gvc_spec_state& st, int k1, int32_t* step_ctr, hipStream_t s) {
-    hipLaunchKernelGGL(k_spec_round_begin, dim3(cdiv(st.B, 64)), dim3(64), 0, s, st, k1, step_ctr);
+int launch_spec_round_begin(const gvc_spec_state& st, int k1, int32_t* step_ctr, gvc_row_sampling* rows, const gvc_sample_params& p,
+                            hipStream_t s) {
+    hipLaunchKernelGGL(k_spec_round_begin, dim3(cdiv(st.B, 64)), dim3(64), 0, s, st, k1, step_ctr, rows, p);
     GVC_LAUNCH_CHECK();
     return GVC_OK;
 }
@@ -201,6 +439,29 @@ int launch_spec_accept(const gvc_spec_state& st, int k, int appended, const floa
     if (proc) { pr.on = 1; pr.P = *proc; }
     hipLaunchKernelGGL(k_spec_accept, dim3(st.B), dim3(kSpecThreads), 0, s, st, k, appended, logits, latents, drafts, draft_stride, p, pr);
     GVC_LAUNCH_CHECK();
+    return GVC_OK;
+}
+
+int launch_spec_accept_sample(const gvc_spec_state& st, int k, int appended, const float* logits, const float* latents,
+                              const int32_t* drafts, int draft_stride, bool put_drafts, const float* q, float* p_rows,
+                              const gvc_sample_params& p, const gvc_logits_processors* proc, hipStream_t s) {
+    SpecProc pr;
+    memset(&pr, 0, sizeof(pr));
+    if (proc) { pr.on = 1; pr.P = *proc; }
+    if (put_drafts && drafts && k > 0) hipLaunchKernelGGL(k_spec_put_drafts, dim3(st.B), dim3(64), 0, s, st, k, drafts, draft_stride);
+    hipLaunchKernelGGL(k_spec_warp, dim3(st.B * (k + 1)), dim3(kSampThreads), 0, s, st, k, logits, p_rows, p, pr);
+    hipLaunchKernelGGL(k_spec_accept_sample, dim3(st.B), dim3(kSpecThreads), 0, s, st, k, appended, latents, drafts, draft_stride, q,
+                       (const float*)p_rows, p);
+    GVC_LAUNCH_CHECK();
+    return GVC_OK;
+}
+
+int check_spec_sampling(const float* q, const float* p_rows, const gvc_row_sampling* rows, bool need_rows, const gvc_sample_params* p) {
+    GVC_REQUIRE(p, GVC_ERR_ARG, "spec sampling: null argument");
+    GVC_REQUIRE(q && p_rows && (rows || !need_rows), GVC_ERR_ARG, "spec sampling: a null workspace array");
+    GVC_REQUIRE(p->temperature > 0.f && p->top_k <= p->vocab && p->repetition_penalty > 0.f, GVC_ERR_ARG,
+                "spec sampling: temperature %g, top_k %d (vocab %d), repetition_penalty %g", (double)p->temperature, p->top_k, p->vocab,
+                (double)p->repetition_penalty);
     return GVC_OK;
 }
 
@@ -236,4 +497,17 @@ extern "C" int gvc_spec_accept(const gvc_spec_state* st, int32_t k, int32_t appe
                 "gvc_spec_accept: bad argument (k %d, appended %d, draft_stride %d)", k, appended, draft_stride);
     GVC_REQUIRE(!st->lats || latents, GVC_ERR_ARG, "gvc_spec_accept: a latent buffer without latent rows");
     return launch_spec_accept(*st, k, appended, logits, latents, k > 0 ? drafts : nullptr, draft_stride, *p, proc, (hipStream_t)sv);
+}
+
+extern "C" int gvc_spec_accept_sample(const gvc_spec_state* st, int32_t k, int32_t appended, const float* logits, const float* latents,
+                                      const int32_t* drafts, int32_t draft_stride, const float* q_scores, float* p_scores,
+                                      const gvc_sample_params* p, const gvc_logits_processors* proc, gvc_stream sv) {
+    int rc = check_spec_state(st, k, p, proc, false);
+    if (rc) return rc;
+    if ((rc = check_spec_sampling(k > 0 ? q_scores : p_scores, p_scores, nullptr, false, p))) return rc;
+    GVC_REQUIRE(logits && (k == 0 || (drafts && draft_stride >= k)) && (appended == 0 || appended == k + 1), GVC_ERR_ARG,
+                "gvc_spec_accept_sample: bad argument (k %d, appended %d, draft_stride %d)", k, appended, draft_stride);
+    GVC_REQUIRE(!st->lats || latents, GVC_ERR_ARG, "gvc_spec_accept_sample: a latent buffer without latent rows");
+    return launch_spec_accept_sample(*st, k, appended, logits, latents, k > 0 ? drafts : nullptr, draft_stride, true, q_scores, p_scores, *p,
+                                     proc, (hipStream_t)sv);
 }

@@ -647,6 +647,17 @@ class AssistedState:
                                 p(self.drop_target), p(self.drop_assistant), p(self.rounds), p(self.drafted), p(self.accepted),
                                 p(self.v_toks), p(self.v_logits), p(self.v_latents), p(self.d_ids_len), p(self.d_finished))
 
+    def sampling(self):
+        """the workspaces of speculative sampling (include/genvc_hip.h: gvc_spec_sampling), allocated on first use: the draft's and
+        the target's warped rows fp32 [B, 16, V] and the draft sampler's keyed rows (32 bytes per stream)"""
+        if getattr(self, "_sampling", None) is None:
+            dev = self.ids.device
+            self.q_scores = torch.zeros(self.B, MAX_ASSISTANT_TOKENS + 1, self.vocab, device=dev, dtype=torch.float32)
+            self.p_scores = torch.zeros(self.B, MAX_ASSISTANT_TOKENS + 1, self.vocab, device=dev, dtype=torch.float32)
+            self.key_rows = torch.zeros(self.B, C.sizeof(_lib.RowSampling), device=dev, dtype=torch.uint8)
+            self._sampling = _lib.SpecSampling(self.q_scores.data_ptr(), self.p_scores.data_ptr(), self.key_rows.data_ptr())
+        return self._sampling
+
     def stats(self):
         """the device counters as int64 [B] tensors: rounds run, drafts compared and drafts accepted per row"""
         return dict(rounds=self.rounds.long(), drafted=self.drafted.long(), accepted=self.accepted.long())
@@ -660,6 +671,22 @@ def spec_accept(state, k, appended, logits, latents, drafts, params, proc=None):
     check(lib().gvc_spec_accept(C.byref(state.c), int(k), int(appended), ptr(_f32(logits)), ptr(None if latents is None else _f32(latents)),
                                 ptr(None if drafts is None else _i32(drafts)), 0 if drafts is None else drafts.shape[1], C.byref(params),
                                 None if proc is None else C.byref(proc), stream()), "spec_accept")
+
+
+def spec_accept_sample(state, k, appended, logits, latents, drafts, q_scores, params, proc=None):
+    """the accept step of speculative sampling on `state`, warping included (include/genvc_hip.h: gvc_spec_accept_sample): arguments as
+    spec_accept, plus q_scores fp32 [B, k + 1, V] (row j: the warped row draft j was drawn from; None for k = 0) and every sampling
+    field of `params`.  Returns the target's warped rows fp32 [B, k + 1, V] (rows the step did not need are left as they were)"""
+    B = state.B
+    assert tuple(logits.shape) == (B, k + 1, state.vocab) and (latents is None or tuple(latents.shape) == (B, k + 1, state.d))
+    assert q_scores is None or tuple(q_scores.shape) == (B, k + 1, state.vocab)
+    p_rows = torch.zeros(B, k + 1, state.vocab, device=logits.device, dtype=torch.float32)
+    check(lib().gvc_spec_accept_sample(C.byref(state.c), int(k), int(appended), ptr(_f32(logits)),
+                                       ptr(None if latents is None else _f32(latents)), ptr(None if drafts is None else _i32(drafts)),
+                                       0 if drafts is None else drafts.shape[1], ptr(None if q_scores is None else _f32(q_scores)),
+                                       ptr(p_rows), C.byref(params), None if proc is None else C.byref(proc), stream()),
+          "spec_accept_sample")
+    return p_rows
 
 
 class GptEngine:
@@ -1053,10 +1080,12 @@ class GptEngine:
         check(lib().gvc_gpt_truncate(self._h, ptr(_i32(slots)), slots.shape[0], ptr(_i32(drop)), stream()), "truncate")
 
     def generate_assisted(self, assistant, slots, assistant_slots, state, params, n_rounds, max_keys, assistant_max_keys, proc=None,
-                          k=None):
+                          k=None, sampling=False):
         """n_rounds rounds of assisted greedy decoding of `state` (an AssistedState) with this engine as the target and `assistant`
         (another GptEngine) drafting k (default state.k; never more) tokens per round (include/genvc_hip.h:
-        gvc_gpt_generate_assisted).  The first call of a state also runs its opening step.  max_keys / assistant_max_keys: cached positions the longest stream reaches inside the call"""
+        gvc_gpt_generate_assisted).  The first call of a state also runs its opening step.  max_keys / assistant_max_keys: cached positions the longest stream reaches inside the call.
+        sampling=True: speculative sampling with every sampling field of `params` (gvc_gpt_generate_assisted_sample; top_k != 1); the
+        state gets its sampling workspaces on the first such call"""
         self._join_side()
         assistant._join_side()
         if slots.shape[0] != state.B or assistant_slots.shape[0] != state.B:
@@ -1064,10 +1093,17 @@ class GptEngine:
         k = state.k if k is None else int(k)
         if not 1 <= k <= state.k:
             raise ValueError(f"{k} drafts per round outside [1, {state.k}]")
-        check(lib().gvc_gpt_generate_assisted(self._h, assistant._h, ptr(_i32(slots)), ptr(_i32(assistant_slots)), C.byref(state.c),
-                                              C.byref(params), None if proc is None else C.byref(proc), int(not state.opened),
-                                              int(n_rounds), k, int(max_keys), int(assistant_max_keys), stream()),
-              "generate_assisted")
+        if sampling:
+            check(lib().gvc_gpt_generate_assisted_sample(self._h, assistant._h, ptr(_i32(slots)), ptr(_i32(assistant_slots)),
+                                                         C.byref(state.c), C.byref(state.sampling()), C.byref(params),
+                                                         None if proc is None else C.byref(proc), int(not state.opened), int(n_rounds), k,
+                                                         int(max_keys), int(assistant_max_keys), stream()),
+                  "generate_assisted_sample")
+        else:
+            check(lib().gvc_gpt_generate_assisted(self._h, assistant._h, ptr(_i32(slots)), ptr(_i32(assistant_slots)), C.byref(state.c),
+                                                  C.byref(params), None if proc is None else C.byref(proc), int(not state.opened),
+                                                  int(n_rounds), k, int(max_keys), int(assistant_max_keys), stream()),
+                  "generate_assisted")
         state.opened = True
         state.rounds_done += int(n_rounds)
 

@@ -248,7 +248,8 @@ def _no_bias(kw, where):
                                   "num_return_sequences, guidance_scale), one call-wide set per call")
 
 
-ASSIST_KWARGS = ("assistant_model", "num_assistant_tokens", "num_assistant_tokens_schedule", "assistant_cond_latents")
+ASSIST_KWARGS = ("assistant_model", "num_assistant_tokens", "num_assistant_tokens_schedule", "assistant_cond_latents",
+                 "speculative_sampling")
 
 
 def _no_assistant(kw, where):
@@ -258,11 +259,21 @@ def _no_assistant(kw, where):
                                   "one draft context next to the target's)")
 
 
+def _speculative(kw):
+    """an assisted call that samples: the opt-in kwarg, do_sample (default True) and a top_k that leaves a choice.  do_sample=False or
+    top_k=1 with the kwarg is the greedy mode"""
+    return bool(kw.get("speculative_sampling")) and bool(kw.get("do_sample", True)) and kw.get("top_k", 0) != 1
+
+
 def _assisted_kwargs(kw, B):
-    """the kwargs of GPT.generate(assistant_model=...) validated -> k, the drafts per round.  Assisted decoding is greedy: every
-    other mode of generate raises NotImplementedError naming the combination; a k outside [1, 15], more than 128 verification rows
-    and a schedule other than "constant" raise ValueError"""
+    """the kwargs of GPT.generate(assistant_model=...) validated -> k, the drafts per round.  Assisted decoding is greedy, or -- with
+    the opt-in speculative_sampling=True -- sampled (do_sample, top_k != 1: _speculative(kw)): every other mode of generate raises
+    NotImplementedError naming the combination; a k outside [1, 15], more than 128 verification rows and a schedule other than
+    "constant" raise ValueError"""
     mode = "assisted decoding (assistant_model)"
+    spec = kw.get("speculative_sampling")
+    if spec is not None and not isinstance(spec, bool):
+        raise ValueError(f"speculative_sampling must be True, False or None, not {spec!r}")
     if _guidance_scale(kw) is not None:
         raise NotImplementedError(f"guidance_scale={kw.get('guidance_scale')} with {mode} is not implemented")
     if _contrastive_mode(kw) is not None:
@@ -273,12 +284,13 @@ def _assisted_kwargs(kw, B):
         raise NotImplementedError(f"beam search (num_beams={kw.get('num_beams')}) with {mode} is not implemented")
     if _num_return(kw) != 1:
         raise NotImplementedError(f"num_return_sequences={kw.get('num_return_sequences')} with {mode} is not implemented")
-    if kw.get("do_sample", True) and kw.get("top_k", 0) != 1:
+    if kw.get("do_sample", True) and kw.get("top_k", 0) != 1 and not spec:
         raise NotImplementedError(f"sampling (do_sample=True, top_k={kw.get('top_k', 0)}) with {mode} is not implemented: speculative "
-                                  "sampling needs the draft's warped rows; pass do_sample=False or top_k=1")
+                                  "sampling needs the draft's warped rows; pass do_sample=False or top_k=1 (or opt in with "
+                                  "speculative_sampling=True)")
     _no_step_outputs(kw, mode)
     _no_bias(kw, mode)
-    if logits_warpers(kw, sampling=False) is not None:
+    if logits_warpers(kw, sampling=_speculative(kw)) is not None:
         raise NotImplementedError(f"typical_p / epsilon_cutoff / eta_cutoff with {mode} are not implemented")
     sched = kw.get("num_assistant_tokens_schedule", "constant")
     if sched is not None and sched != "constant":
@@ -626,7 +638,9 @@ class GPT(nn.Module):
         fires at cur_len == 1, and no prompt of this model is that short.  Beams, beam groups and contrastive search raise
         NotImplementedError for them, as the grouped, rolling, session and streaming paths do.
         assistant_model = another initialised GPT: assisted (speculative) greedy decoding (_generate_assisted), checked
-        before every other mode; the tokens are those of the call without it.  None is exactly that call."""
+        before every other mode; the tokens are those of the call without it.  None is exactly that call.  With
+        speculative_sampling=True a sampled call is served too (speculative sampling: same distribution per token, other tokens than
+        the plain call with that seed; _generate_assisted)."""
         _num_return(generate_kwargs)
         if generate_kwargs.get("assistant_model") is not None:
             return self._generate_assisted(cond_latents, text_inputs, generate_kwargs)
@@ -737,9 +751,17 @@ class GPT(nn.Module):
         the same text_inputs, and prefills its own KV slots.  Every round the assistant drafts k = num_assistant_tokens (1..15,
         default 5, the choice of profiles/assisted_decoding.md) tokens greedily, this model scores [pending token, d_1..d_k] in one
         multi-row pass, the device accepts the longest agreeing prefix plus one token of this model per row, and both caches roll
-        back; near the end of the position tables a call drafts fewer tokens.  Greedy only (do_sample=False or top_k=1), with
+        back; near the end of the position tables a call drafts fewer tokens.  Greedy (do_sample=False or top_k=1), with
         repetition_penalty, temperature and the processor kwargs (engine.PROC_KWARGS) on both models; every other mode raises
-        NotImplementedError.  The host reads the finished flags once per max(1, group // (k + 1)) rounds.  Token 0 of a row comes from
+        NotImplementedError.
+        speculative_sampling=True (opt-in; without it a sampled call is refused as before) with do_sample (default True) and
+        top_k != 1: speculative sampling (Leviathan et al.; include/genvc_hip.h: gvc_gpt_generate_assisted_sample).
+        The draft SAMPLES its k tokens with the call's top_k / top_p / temperature / repetition_penalty / processors (min_p included),
+        draft d is accepted with probability min(1, p(d) / q(d)) under the two models' warped rows, and the token behind the accepted
+        prefix is drawn from max(p - q, 0) (from p behind k accepted drafts).  Each emitted token is distributed as a plain sampled
+        token of this model under the same warpers; the tokens are NOT those of the plain call with the same `seed` -- the uniforms
+        are keyed by (seed, position in the generation, 3 * row + {0: draft, 1: accept, 2: residual}), so they do not depend on
+        `group` either.  do_sample=False or top_k=1 with the kwarg is the greedy mode above.  The host reads the finished flags once per max(1, group // (k + 1)) rounds.  Token 0 of a row comes from
         the prefill's logits (the opening step: no round is counted for it), so a row of n tokens whose drafts were all accepted ran
         ceil((n - 1) / (k + 1)) rounds.  Returns what the call without the assistant returns (tokens bit for bit; `last_latents`
         from the verification rows) and sets `last_assist_stats`: dict(rounds, drafted, accepted), int64 [B] each."""
@@ -748,7 +770,8 @@ class GPT(nn.Module):
         acond = kw.pop("assistant_cond_latents", None)
         B = int(text_inputs.shape[0])
         k = _assisted_kwargs(kw, B)
-        for name in ASSIST_KWARGS[1:3]:
+        spec = _speculative(kw)
+        for name in ASSIST_KWARGS[1:3] + ASSIST_KWARGS[4:]:
             kw.pop(name, None)
         mode = "assisted decoding (assistant_model)"
         if not isinstance(asst, GPT) or asst is self:
@@ -782,10 +805,16 @@ class GPT(nn.Module):
             return min(f)
         if max_new > 1 and fit(max_new - 1) < 1:
             raise ValueError(f"{mode}: max_new_tokens={max_new} leaves no room for a draft in the position tables; lower it")
-        samp = dict(repetition_penalty=kw.get("repetition_penalty", 1.0), temperature=kw.get("temperature", 1.0), top_p=1.0, top_k=1)
+        samp = dict(repetition_penalty=kw.get("repetition_penalty", 1.0), temperature=kw.get("temperature", 1.0),
+                    top_p=kw.get("top_p", 1.0) if spec else 1.0, top_k=kw.get("top_k", 0) if spec else 1)
+        if spec and not int(samp["top_k"]) <= self.num_audio_tokens:
+            raise ValueError(f"{mode}: top_k={samp['top_k']} is above the vocabulary ({self.num_audio_tokens})")
+        if spec and not float(samp["temperature"]) > 0.0:
+            raise ValueError(f"{mode}: temperature={samp['temperature']} must be > 0")
         params = sample_params(samp, self.num_audio_tokens, self.stop_audio_token, kw.get("seed", 0))
-        proc = logits_processors(kw, n0, self.num_audio_tokens, sampling=False)
+        proc = logits_processors(kw, n0, self.num_audio_tokens, sampling=spec)
         per_check = max(1, group // (k + 1))
+        more = dict(sampling=True) if spec else {}          # (the greedy mode makes exactly the call it made before)
 
         def run():
             slots = torch.arange(B, device=dev, dtype=torch.int32)
@@ -800,7 +829,7 @@ class GPT(nn.Module):
                 while max_new > 1 and n < per_check and min(k, fit(u)) >= kc:
                     reach = u + kc          # cached positions behind the prompt at the end of this round's verification
                     n, u = n + 1, min(max_new - 1, u + kc + 1)
-                self.engine.generate_assisted(asst.engine, slots, slots, st, params, n, n0 + reach, a_n0 + reach, proc=proc, k=kc)
+                self.engine.generate_assisted(asst.engine, slots, slots, st, params, n, n0 + reach, a_n0 + reach, proc=proc, k=kc, **more)
                 ub = u
                 end = bool(st.finished.all().item())
                 self.engine.health()          # (the .item() above synchronised)

@@ -690,6 +690,50 @@ int gvc_gpt_generate_assisted(gvc_gpt* target, gvc_gpt* assistant, const int32_t
                               const gvc_spec_state* st, const gvc_sample_params* p, const gvc_logits_processors* proc, int32_t first,
                               int32_t n_rounds, int32_t k, int32_t max_keys, int32_t assistant_max_keys, gvc_stream s);
 
+/* ------------------------------------------------------------------------------------------
+ * Speculative SAMPLING for assisted decoding (Leviathan et al. 2023; transformers generation/utils.py _speculative_sampling).  The
+ * draft draws d_{i+1} from q_i, its own warped row; the target's verification row i is warped into p_i -- "warped" is what gvc_sample
+ * draws from: repetition penalty over the ids the row has at that position (accepted drafts included), the processors `proc` (min_p
+ * included) at length ids_len + i, Temperature, TopK, TopP, MinP; kept entries weigh expf(s - max) in fp32, sums and CDFs are double
+ * in vocabulary order, a probability is weight / total.  For one stream with e tokens emitted and k' = min(k, max_new - e - 1), for
+ * i = 0, 1, ..: draft x = d_{i+1} is accepted iff (double)u_acc(e + i) * q_i(x) <= p_i(x) (no division: q_i(x) == 0 accepts) and is
+ * emitted with latent row i; the stop token ends the row.  At the first rejection one token is drawn from max(p_i - q_i, 0) by the
+ * sampler's inverse-CDF rule (first kept index whose running mass reaches u * total, else the last kept index) with u = u_res(e + i)
+ * -- from p_i with the same u when the residual is empty (p_i == q_i); behind k' accepted drafts one token is drawn from p_k' with
+ * u_res(e + k').  The opening step (k = 0) draws token 0 from p_0 with u_res(0).  Bookkeeping is gvc_spec_accept's, field for field.
+ * RNG counters are keyed by position, so a result does not depend on how rounds are grouped into calls; row b deciding token t uses
+ *     u_draft(t) = rng_uniform(seed, t, 3b)     u_acc(t) = rng_uniform(seed, t, 3b + 1)     u_res(t) = rng_uniform(seed, t, 3b + 2)
+ * and a position drafted behind a rejection reuses its uniforms when it is drafted again (they were never looked at).
+ * Each emitted token is distributed as a plain sampled token of the target under the same warpers; the tokens themselves are NOT those
+ * of gvc_gpt_generate with the same seed.
+ * ------------------------------------------------------------------------------------------ */
+/* Device workspaces of a sampled assisted generation, owned by the caller: q_scores / p_scores fp32 [B][16][vocab] (used as
+ * [B][k + 1][vocab]: row j of q is the warped row d_j was drawn from, row 0 unused; row i of p is p_i), rows [B] the draft sampler's
+ * keyed rows (written at the start of every round: the call's settings, seed, rng_row = 3b, rng_step0 = emitted[b]). */
+typedef struct gvc_spec_sampling {
+    float* q_scores;
+    float* p_scores;
+    gvc_row_sampling* rows;
+} gvc_spec_sampling;
+
+/* The accept step of speculative sampling alone, warping included; needs no context.  Arguments as gvc_spec_accept, plus q_scores
+ * [B][k + 1][vocab] (read; null allowed for k = 0) and p_scores [B][k + 1][vocab] (written: the warped target rows up to k').  d_1..d_k'
+ * are written behind the live rows' ids first, then one workgroup per verification row warps it and one per stream applies the rule;
+ * only the rows up to the first rejection are read.  p: every field is read (top_k == 1 is served too: one-hot rows).  A null
+ * workspace, top_k > vocab or temperature <= 0 is GVC_ERR_ARG before anything is launched. */
+int gvc_spec_accept_sample(const gvc_spec_state* st, int32_t k, int32_t appended, const float* logits, const float* latents,
+                           const int32_t* drafts, int32_t draft_stride, const float* q_scores, float* p_scores,
+                           const gvc_sample_params* p, const gvc_logits_processors* proc, gvc_stream s);
+
+/* gvc_gpt_generate_assisted with speculative sampling: the same contract (first, n_rounds, k, both max_keys, no host synchronisation
+ * inside, rounds launched directly), the sampling settings taken from p (top_k != 1; top_k == 1 is gvc_gpt_generate_assisted).  The
+ * draft's steps run gvc_sample's full kernel on the keyed rows `ss->rows` and store their warped rows in ss->q_scores; step 3 of a
+ * round is gvc_spec_accept_sample.  ss: HOST struct of device pointers, free when the call returns. */
+int gvc_gpt_generate_assisted_sample(gvc_gpt* target, gvc_gpt* assistant, const int32_t* slots, const int32_t* assistant_slots,
+                                     const gvc_spec_state* st, const gvc_spec_sampling* ss, const gvc_sample_params* p,
+                                     const gvc_logits_processors* proc, int32_t first, int32_t n_rounds, int32_t k, int32_t max_keys,
+                                     int32_t assistant_max_keys, gvc_stream s);
+
 /* Which decode step the last gvc_gpt_generate call replayed (diagnostic): 0 none yet, 1 launch-per-phase with split-key attention,
  * 2 launch-per-phase with the fused short-context attention launch, 3 the one-launch step (one stream), 4 the MFMA rows path
  * (launch per phase: 17+ streams, or shapes the one-launch rows step does not serve), 5 the one-launch rows step (2..16 streams,

@@ -71,9 +71,15 @@ if __name__ == "__main__":
                              "of the same width (GPT.generate(assistant_model=...)); a demonstration of the mode, not of an acceptance rate")
     parser.add_argument("--num_assistant_tokens", type=int, default=None, metavar="K",
                         help="with --assistant_layers: tokens drafted per round, 1..15 (default 5)")
+    parser.add_argument("--assistant_sampling", action="store_true",
+                        help="with --assistant_layers: speculative sampling (GPT.generate(speculative_sampling=True)) -- the draft samples "
+                             "and the sampling flags (--top_k, config top_p / temperature) apply; without it --assistant_layers decodes "
+                             "greedily")
     args = parser.parse_args()
     if args.num_assistant_tokens is not None and args.assistant_layers is None:
         raise SystemExit("--num_assistant_tokens needs --assistant_layers")
+    if args.assistant_sampling and args.assistant_layers is None:
+        raise SystemExit("--assistant_sampling needs --assistant_layers")
     if args.assistant_layers is not None:
         if not args.synthetic:
             raise SystemExit("--assistant_layers needs --synthetic: no draft checkpoint ships with the reference")
@@ -174,7 +180,8 @@ if __name__ == "__main__":
                                          weight_dtype=args.weights)
     if args.assistant_layers is not None:
         from genvc_amd.inference.model_init import synthetic_assistant
-        gen_kw.update(do_sample=False, num_assistant_tokens=5 if args.num_assistant_tokens is None else args.num_assistant_tokens,
+        gen_kw.update(dict(speculative_sampling=True) if args.assistant_sampling else dict(do_sample=False))
+        gen_kw.update(num_assistant_tokens=5 if args.num_assistant_tokens is None else args.num_assistant_tokens,
                       assistant_model=synthetic_assistant(model.config, args.assistant_layers, device=args.device,
                                                           max_slots=model.gpt.max_slots, weight_dtype=args.weights))
     src_wav = load_audio(args.src_wav, model.content_sample_rate, device=args.device)

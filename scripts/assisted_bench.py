@@ -16,7 +16,14 @@ Next to the rounds, in the same process and interleaved with them: the plain one
 (engine.generate, 200 steps per call; DESIGN.md 4.1 has 513 us for it).
 Break-even: a round must emit t_round / t_step tokens to match the plain loop.  With an independent per-draft acceptance probability
 a, a round emits (1 - a^(k+1)) / (1 - a) tokens; the table gives the a at which that equals t_round / t_step ("never" when k + 1
-tokens per round are not enough)."""
+tokens per round are not enough).
+
+    python scripts/assisted_bench.py --sample [--sample_json profiles/assisted_sampling.json]
+
+measures the round of speculative SAMPLING (GPT.generate(speculative_sampling=True), DESIGN.md 4.17: k full-sampler draft steps that
+store their warped rows, one warp launch over the k + 1 verification rows, the accept kernel) at top_k = 15, top_p = 0.85, temperature
+0.85 on the same cells, interleaved in one process with the greedy round of the same cell and with the plain SAMPLED step of the
+target at the same settings, and adds its section to --out behind the greedy report (rendered from --json as it stands)."""
 import argparse
 import json
 import os
@@ -159,6 +166,123 @@ def measure(args):
     return res
 
 
+SAMPLING = dict(repetition_penalty=1.0, temperature=0.85, top_p=0.85, top_k=15)
+
+
+def measure_sample(args):
+    """the sampled round against the greedy round of the same cell and the plain sampled step, one process, interleaved"""
+    import torch
+    from genvc_amd import synth
+    from genvc_amd.engine import AssistedState, sample_params
+    assert torch.cuda.is_available(), "this measurement needs the GPU"
+    target, _ = build(30, 1)
+    assistants = {n: build(n, 7)[0] for n in LAYERS}
+    d = target.model_dim
+    cond = synth.uniform(300, "cond_latents", (1, 32, d), 1.0).cuda()
+    codes = synth.integers(300, "content_codes", (1, 13), 256).cuda()
+    fake = target.compute_embeddings(cond, codes)
+    for g in assistants.values():
+        g.compute_embeddings(cond, codes)
+    n0 = int(fake.shape[1])
+    slots = torch.zeros(1, device="cuda", dtype=torch.int32)
+    greedy = sample_params(dict(repetition_penalty=1.0, temperature=1.0, top_p=1.0, top_k=1), 1026, 1025)
+    sampled = sample_params(SAMPLING, 1026, 1025, 17)
+    teng = target.engine
+
+    def rounds(asst, k, sample):
+        teng.prefill(slots, target._prefix, want_outputs=False)
+        asst.engine.prefill(slots, asst._prefix, want_outputs=False)
+        st = AssistedState(fake, k, MAX_NEW, 1025, 1026, d)
+        reach = 1 + ROUNDS * (k + 1) + k
+        more = dict(sampling=True) if sample else {}
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        teng.generate_assisted(asst.engine, slots, slots, st, sampled if sample else greedy, ROUNDS, n0 + reach, n0 + reach, **more)
+        e1.record()
+        torch.cuda.synchronize()
+        teng.health()
+        asst.engine.health()
+        s = st.stats()
+        assert int(s["rounds"][0]) == ROUNDS and int(st.emitted[0]) == 1 + ROUNDS + int(s["accepted"][0])
+        return e0.elapsed_time(e1) * 1000.0 / ROUNDS, int(s["accepted"][0]), int(s["drafted"][0])
+
+    def plain(params):
+        teng.prefill(slots, target._prefix, want_outputs=False)
+        ids = torch.ones(1, n0 + STEPS + 8, device="cuda", dtype=torch.int32)
+        ids[:, n0 - 1] = 1024
+        ids_len = torch.full((1,), n0, device="cuda", dtype=torch.int32)
+        fin = torch.zeros(1, device="cuda", dtype=torch.int32)
+        toks = torch.zeros(1, STEPS, device="cuda", dtype=torch.int32)
+        lats = torch.zeros(1, STEPS, d, device="cuda")
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        teng.generate(slots, ids, ids_len, fin, params, 0, STEPS, toks, lats, max_keys=n0 + STEPS)
+        e1.record()
+        torch.cuda.synchronize()
+        teng.health()
+        return e0.elapsed_time(e1) * 1000.0 / STEPS
+
+    cells = {(n, k): dict(sampled=[], greedy=[]) for n in LAYERS for k in KS}
+    for n, k in cells:          # untimed: every shape once in both modes
+        rounds(assistants[n], k, True)
+        rounds(assistants[n], k, False)
+    plain(sampled)
+    plain(greedy)
+    steps, gsteps, acc = [], [], {}
+    for _ in range(args.reps):
+        steps.append(plain(sampled))
+        gsteps.append(plain(greedy))
+        for (n, k), xs in cells.items():
+            us, a, dr = rounds(assistants[n], k, True)
+            xs["sampled"].append(us)
+            acc[(n, k)] = (a, dr)
+            xs["greedy"].append(rounds(assistants[n], k, False)[0])
+    t_step, g_step = med(steps), med(gsteps)
+    res = dict(device=torch.cuda.get_device_name(0), n0=n0, rounds_per_call=ROUNDS, steps_per_plain_call=STEPS, reps=args.reps,
+               sampling=SAMPLING, plain_sampled_us_per_step=t_step, plain_sampled_runs=steps,
+               plain_sampled_spread=max(abs(x - t_step) / t_step for x in steps), plain_greedy_us_per_step=g_step,
+               plain_greedy_runs=gsteps, cells=[])
+    for (n, k), xs in cells.items():
+        ts, tg = med(xs["sampled"]), med(xs["greedy"])
+        res["cells"].append(dict(assistant_layers=n, k=k, sampled_us_per_round=ts, greedy_us_per_round=tg,
+                                 sampled_spread=max(abs(x - ts) / ts for x in xs["sampled"]),
+                                 greedy_spread=max(abs(x - tg) / tg for x in xs["greedy"]), sampled_runs=xs["sampled"],
+                                 greedy_runs=xs["greedy"], tokens_per_round_to_break_even=ts / t_step,
+                                 break_even_acceptance=break_even(ts / t_step, k), accepted_in_last_timed_call=acc[(n, k)][0],
+                                 drafted_in_last_timed_call=acc[(n, k)][1]))
+    return res
+
+
+def render_sample(res):
+    """the section on speculative sampling (every figure in it is computed from `res`)"""
+    t_step, s = res["plain_sampled_us_per_step"], res["sampling"]
+    lines = ["", "## Speculative sampling: the cost of a sampled round", "",
+             f"`scripts/assisted_bench.py --sample` on one MI355X ({res['device']}): the same target, assistants, prompt and cells; "
+             f"top_k = {s['top_k']}, top_p = {s['top_p']}, temperature = {s['temperature']}; {res['rounds_per_call']} rounds per timed call, "
+             f"{res['reps']} timed calls per cell and mode (median; spread as above), the sampled round, the greedy round of the same "
+             "cell and the plain loops interleaved in one process.  Timed with device events around one engine call that ends in a "
+             "synchronise, after an untimed call of every shape.", "",
+             f"Plain one-stream SAMPLED step of the same target at these settings, same run: **{t_step:.1f} us** per token over "
+             f"{res['steps_per_plain_call']} steps (spread {res['plain_sampled_spread']:.2%}); the plain greedy step in this run: "
+             f"{res['plain_greedy_us_per_step']:.1f} us.", "",
+             "A sampled round = a greedy round with k full-sampler draft steps that also store their warped row (instead of k argmax "
+             "steps), one warp launch of k + 1 workgroups and the accept kernel (instead of the greedy accept kernel).  Break-even is "
+             "against the plain SAMPLED step.", "",
+             "| assistant layers | k | sampled us / round | spread | greedy us / round | spread | sampled - greedy | tokens / round to break "
+             "even | break-even per-draft acceptance |", "|---|---|---|---|---|---|---|---|---|"]
+    for c in res["cells"]:
+        ts, tg, a = c["sampled_us_per_round"], c["greedy_us_per_round"], c["break_even_acceptance"]
+        lines.append(f"| {c['assistant_layers']} | {c['k']} | {ts:.0f} | {c['sampled_spread']:.2%} | {tg:.0f} | {c['greedy_spread']:.2%} | "
+                     f"{ts - tg:+.0f} | {ts / t_step:.2f} | {'never' if a is None else f'{a:.2f}'} |")
+    acc = ", ".join(f"{c['accepted_in_last_timed_call']} of {c['drafted_in_last_timed_call']}" for c in res["cells"])
+    lines += ["", "The acceptance of a sampled round is min(1, p / q) per draft, not agreement of two argmaxes; with synthetic weights the "
+              f"unrelated assistants had {acc} drafts accepted in the last timed call of each cell, which says nothing about a trained "
+              "draft model.  What was measured is the cost of a round; no threshold was set for it in advance."]
+    return "\n".join(lines) + "\n"
+
+
 RATES = (0.5, 0.6, 0.7, 0.8, 0.9)
 
 
@@ -221,8 +345,15 @@ def main():
     ap.add_argument("--json", default=os.path.join(ROOT, "profiles", "assisted_decoding.json"))
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--render", action="store_true", help="no measurement: write --out again from the figures in --json")
+    ap.add_argument("--sample", action="store_true", help="measure the round of speculative sampling (into --sample_json); the greedy "
+                                                          "report is rendered from --json as it stands")
+    ap.add_argument("--sample_json", default=os.path.join(ROOT, "profiles", "assisted_sampling.json"))
     args = ap.parse_args()
-    if args.render:
+    if args.sample:
+        sres = measure_sample(args)
+        with open(args.sample_json, "w") as f:
+            json.dump(sres, f, indent=1)
+    if args.render or args.sample:
         with open(args.json) as f:
             res = json.load(f)
     else:
@@ -230,6 +361,9 @@ def main():
         with open(args.json, "w") as f:
             json.dump(res, f, indent=1)
     text = render(res)
+    if os.path.exists(args.sample_json):
+        with open(args.sample_json) as f:
+            text += render_sample(json.load(f))
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
         f.write(text)
