@@ -189,6 +189,14 @@ _SIGNATURES = {
     "gvc_gpt_generate_assisted_sample": (C.c_int, [_P, _P, _P, _P, C.POINTER(SpecState), C.POINTER(SpecSampling), C.POINTER(SampleParams),
                                                    C.POINTER(LogitsProcessors), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                                    _P]),
+    "gvc_spec_lookup": (C.c_int, [C.POINTER(SpecState), C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32, _P]),
+    "gvc_spec_accept_len": (C.c_int, [C.POINTER(SpecState), C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, _P, C.POINTER(SampleParams),
+                                      C.POINTER(LogitsProcessors), _P]),
+    "gvc_spec_accept_sample_len": (C.c_int, [C.POINTER(SpecState), C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, _P, _P, _P,
+                                             C.POINTER(SampleParams), C.POINTER(LogitsProcessors), _P]),
+    "gvc_gpt_generate_lookup": (C.c_int, [_P, _P, C.POINTER(SpecState), C.POINTER(SpecSampling), C.POINTER(SampleParams),
+                                          C.POINTER(LogitsProcessors), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P,
+                                          C.c_int32, _P]),
     "gvc_gpt_decode_variant": (C.c_int, [_P]),
     "gvc_gpt_rows_step_launches": (C.c_longlong, [_P]),
     "gvc_gpt_one_stream_steps": (C.c_longlong, [_P]),

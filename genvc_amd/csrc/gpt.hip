@@ -2224,35 +2224,50 @@ extern "C" int gvc_gpt_truncate(gvc_gpt* c, const int32_t* slots, int32_t B, con
     return launch_spec_truncate(c->st.seq_len, c->st.mel_pos, slots, B, drop, s);
 }
 
-// The round loop behind gvc_gpt_generate_assisted (ss null: greedy) and gvc_gpt_generate_assisted_sample (ss: the workspaces of
+// where a round's drafts come from when there is no assistant: prompt lookup in the row's own history (spec.h: launch_spec_lookup)
+struct LookupDrafts {
+    int max_ngram, from;
+    int32_t* draft_len;
+};
+
+// The round loop behind gvc_gpt_generate_assisted (ss null: greedy), gvc_gpt_generate_assisted_sample (ss: the workspaces of
 // speculative sampling; the draft steps run the full sampler on keyed rows and store their warped rows, the accept step is
-// launch_spec_accept_sample)
+// launch_spec_accept_sample) and gvc_gpt_generate_lookup (lk: no assistant -- a is null -- and the draft side of a round is one
+// launch_spec_lookup, which hands the accept step a draft count per row and, when ss is given, the drafts' one-hot rows)
 static int assisted_rounds(gvc_gpt* c, gvc_gpt* a, const int32_t* slots, const int32_t* aslots, const gvc_spec_state* st,
                            const gvc_spec_sampling* ss, const gvc_sample_params* p, const gvc_logits_processors* proc, int32_t first,
-                           int32_t n_rounds, int32_t k, int32_t max_keys, int32_t a_max_keys, gvc_stream sv) {
+                           int32_t n_rounds, int32_t k, int32_t max_keys, int32_t a_max_keys, const LookupDrafts* lk, gvc_stream sv) {
+    const char* who = lk ? "generate_lookup" : "generate_assisted";
     int rc = check_ready(c);
     if (rc) return rc;
-    if ((rc = check_ready(a))) return rc;
-    GVC_REQUIRE(c != a && slots && aslots, GVC_ERR_ARG, "generate_assisted: the target and the assistant are two contexts with a slot list each");
+    if (lk) {
+        GVC_REQUIRE(slots, GVC_ERR_ARG, "%s: null slot list", who);
+    } else {
+        if ((rc = check_ready(a))) return rc;
+        GVC_REQUIRE(c != a && slots && aslots, GVC_ERR_ARG, "%s: the target and the assistant are two contexts with a slot list each", who);
+    }
     if ((rc = check_spec_state(st, k, p, proc, true))) return rc;
-    if (ss && (rc = check_spec_sampling(ss->q_scores, ss->p_scores, ss->rows, true, p))) return rc;
+    if (ss && (rc = check_spec_sampling(ss->q_scores, ss->p_scores, ss->rows, !lk, p))) return rc;
     const gvc_spec_state& S = *st;
     const int B = S.B, V = c->dm.vocab, d = c->dm.d_model;
-    GVC_REQUIRE(k >= 1 && n_rounds >= 0, GVC_ERR_ARG, "generate_assisted: k=%d below 1 or n_rounds=%d below 0", k, n_rounds);
-    GVC_REQUIRE(p->vocab == V && a->dm.vocab == V, GVC_ERR_ARG, "generate_assisted: vocab mismatch (call %d, target %d, assistant %d)",
-                p->vocab, V, a->dm.vocab);
-    GVC_REQUIRE(B <= a->dm.max_slots && (!S.lats || S.d == d), GVC_ERR_ARG, "generate_assisted: %d streams / latent width %d do not fit", B, S.d);
+    GVC_REQUIRE(k >= 1 && n_rounds >= 0, GVC_ERR_ARG, "%s: k=%d below 1 or n_rounds=%d below 0", who, k, n_rounds);
+    GVC_REQUIRE(p->vocab == V && (lk || a->dm.vocab == V), GVC_ERR_ARG, "%s: vocab mismatch (call %d, target %d, assistant %d)", who,
+                p->vocab, V, lk ? V : a->dm.vocab);
+    GVC_REQUIRE((lk || B <= a->dm.max_slots) && (!S.lats || S.d == d), GVC_ERR_ARG, "%s: %d streams / latent width %d do not fit", who, B, S.d);
+    if (lk && (rc = check_spec_lookup(st, k, lk->max_ngram, lk->from, lk->draft_len, V))) return rc;
     if ((rc = check_verify(c, B, k + 1))) return rc;
-    GVC_REQUIRE(max_keys > 0 && max_keys < c->dm.max_seq - 1 && a_max_keys > 0 && a_max_keys < a->dm.max_seq - 1, GVC_ERR_STATE,
-                "generate_assisted: %d / %d cached positions would overflow a KV cache (max_seq %d / %d)", max_keys, a_max_keys,
-                c->dm.max_seq, a->dm.max_seq);
+    GVC_REQUIRE(max_keys > 0 && max_keys < c->dm.max_seq - 1 && (lk || (a_max_keys > 0 && a_max_keys < a->dm.max_seq - 1)), GVC_ERR_STATE,
+                "%s: %d / %d cached positions would overflow a KV cache (max_seq %d / %d)", who, max_keys, a_max_keys, c->dm.max_seq,
+                lk ? 0 : a->dm.max_seq);
     hipStream_t s = (hipStream_t)sv;
     if (rows_persist_ok(c, B * (k + 1), c->st.seq_len) && (rc = rows_persist_prepare(c))) return rc;
     c->rows_keys_hint = max_keys;
-    GenPlan apl;
-    if ((rc = plan_generate(a, B, a_max_keys, ss ? p->top_k : 1, &apl))) return rc;
-    a->last_variant = apl.variant;
-    if ((rc = flush_pending(c, slots, B, s)) || (rc = flush_pending(a, aslots, B, s))) return rc;
+    GenPlan apl = {};
+    if (!lk) {
+        if ((rc = plan_generate(a, B, a_max_keys, ss ? p->top_k : 1, &apl))) return rc;
+        a->last_variant = apl.variant;
+    }
+    if ((rc = flush_pending(c, slots, B, s)) || (!lk && (rc = flush_pending(a, aslots, B, s)))) return rc;
     gvc_sample_params gp = *p;
     if (!ss) gp.top_k = 1;
     if (first) {
@@ -2260,44 +2275,53 @@ static int assisted_rounds(gvc_gpt* c, gvc_gpt* a, const int32_t* slots, const i
         hipLaunchKernelGGL(k_stage_rows, dim3(B), dim3(256), 0, s, S.v_logits, c->slot_logits, slots, V, 0);
         hipLaunchKernelGGL(k_stage_rows, dim3(B), dim3(256), 0, s, S.v_latents, c->slot_latent, slots, d, 0);
         GVC_LAUNCH_CHECK();
-        if (ss) rc = launch_spec_accept_sample(S, 0, 0, S.v_logits, S.v_latents, nullptr, 0, false, nullptr, ss->p_scores, gp, proc, s);
-        else rc = launch_spec_accept(S, 0, 0, S.v_logits, S.v_latents, nullptr, 0, gp, proc, s);
+        if (ss) rc = launch_spec_accept_sample(S, 0, 0, S.v_logits, S.v_latents, nullptr, 0, nullptr, false, nullptr, ss->p_scores, gp, proc, s);
+        else rc = launch_spec_accept(S, 0, 0, S.v_logits, S.v_latents, nullptr, 0, nullptr, gp, proc, s);
         if (rc) return rc;
     }
     // the draft sampler: the sampler's greedy kernel on the assistant's logits, with the call's settings, on the rows' own ids (it
     // writes d_j where the accept step writes it again) but lengths and finished flags of its own; d_j lands in row j of v_toks
     SampleCall dsc;
     memset(&dsc, 0, sizeof(dsc));
-    dsc.logits = a->logits; dsc.B = B; dsc.ids = S.ids; dsc.ids_stride = S.ids_stride; dsc.ids_len = S.d_ids_len;
-    dsc.finished = S.d_finished; dsc.p = gp; dsc.step_ptr = a->step_ctr; dsc.tok_out = a->tok_buf;
-    dsc.tokens_out = S.v_toks; dsc.tok_stride = k + 1; dsc.i0 = 1; dsc.d = a->dm.d_model;
-    if (ss) {
-        // the full sampler on device-resident keyed rows (the round-begin launch writes them); the row d_j is drawn from lands in row
-        // j of q_scores, as d_j lands in column j of v_toks
-        dsc.rows = ss->rows; dsc.scores_out = ss->q_scores; dsc.scores_warped = 1; dsc.out_stride = k + 1;
-    }
-    if (proc) {
-        static const int32_t zeros[kMaxSampleRows] = {};
-        GVC_REQUIRE(B <= kMaxSampleRows, GVC_ERR_ARG, "generate_assisted: processors serve up to %d streams", kMaxSampleRows);
-        if ((rc = launch_stage_proc_sets(&a->gen_call->proc, proc, 1, zeros, B, s))) return rc;
-        dsc.proc = &a->gen_call->proc;
-    }
-    for (int r = 0; r < n_rounds; ++r) {
-        // 1. k + 1 decode steps of the assistant: the pending token, then [sample d_j, decode d_j] for j = 1..k
-        if ((rc = launch_spec_round_begin(S, k + 1, a->step_ctr, ss ? ss->rows : nullptr, gp, s))) return rc;
-        if ((rc = decode_step(a, aslots, B, S.pending, a->logits, a->latent, nullptr, s, apl.fused, apl.key_chunks))) return rc;
-        for (int j = 0; j < k; ++j) {
-            if ((rc = launch_sample(dsc, s))) return rc;
-            if ((rc = decode_step(a, aslots, B, a->tok_buf, a->logits, a->latent, a->step_ctr, s, apl.fused, apl.key_chunks))) return rc;
+    if (!lk) {
+        dsc.logits = a->logits; dsc.B = B; dsc.ids = S.ids; dsc.ids_stride = S.ids_stride; dsc.ids_len = S.d_ids_len;
+        dsc.finished = S.d_finished; dsc.p = gp; dsc.step_ptr = a->step_ctr; dsc.tok_out = a->tok_buf;
+        dsc.tokens_out = S.v_toks; dsc.tok_stride = k + 1; dsc.i0 = 1; dsc.d = a->dm.d_model;
+        if (ss) {
+            // the full sampler on device-resident keyed rows (the round-begin launch writes them); the row d_j is drawn from lands in
+            // row j of q_scores, as d_j lands in column j of v_toks
+            dsc.rows = ss->rows; dsc.scores_out = ss->q_scores; dsc.scores_warped = 1; dsc.out_stride = k + 1;
         }
-        // 2. - 4. one pass of the target over [pending, d_1..d_k], the accept step, and both caches rolled back
+        if (proc) {
+            static const int32_t zeros[kMaxSampleRows] = {};
+            GVC_REQUIRE(B <= kMaxSampleRows, GVC_ERR_ARG, "%s: processors serve up to %d streams", who, kMaxSampleRows);
+            if ((rc = launch_stage_proc_sets(&a->gen_call->proc, proc, 1, zeros, B, s))) return rc;
+            dsc.proc = &a->gen_call->proc;
+        }
+    }
+    const int32_t* dlen = lk ? lk->draft_len : nullptr;
+    for (int r = 0; r < n_rounds; ++r) {
+        if (lk) {
+            // 1. the drafts of every row from its own history: one launch, which is the round's begin as well
+            if ((rc = launch_spec_lookup(S, k, lk->max_ngram, lk->from, lk->draft_len, ss ? ss->q_scores : nullptr, V, s))) return rc;
+        } else {
+            // 1. k + 1 decode steps of the assistant: the pending token, then [sample d_j, decode d_j] for j = 1..k
+            if ((rc = launch_spec_round_begin(S, k + 1, a->step_ctr, ss ? ss->rows : nullptr, gp, s))) return rc;
+            if ((rc = decode_step(a, aslots, B, S.pending, a->logits, a->latent, nullptr, s, apl.fused, apl.key_chunks))) return rc;
+            for (int j = 0; j < k; ++j) {
+                if ((rc = launch_sample(dsc, s))) return rc;
+                if ((rc = decode_step(a, aslots, B, a->tok_buf, a->logits, a->latent, a->step_ctr, s, apl.fused, apl.key_chunks))) return rc;
+            }
+        }
+        // 2. - 4. one pass of the target over [pending, d_1..d_k], the accept step, and the caches rolled back (the looked-up drafts
+        // are in no ids row yet: the sampled accept step puts them there before it warps)
         if ((rc = verify_rows(c, slots, B, S.v_toks, k + 1, S.v_logits, S.v_latents, s))) return rc;
-        if (ss) rc = launch_spec_accept_sample(S, k, k + 1, S.v_logits, S.v_latents, S.v_toks + 1, k + 1, false, ss->q_scores, ss->p_scores,
-                                               gp, proc, s);
-        else rc = launch_spec_accept(S, k, k + 1, S.v_logits, S.v_latents, S.v_toks + 1, k + 1, gp, proc, s);
+        if (ss) rc = launch_spec_accept_sample(S, k, k + 1, S.v_logits, S.v_latents, S.v_toks + 1, k + 1, dlen, lk != nullptr, ss->q_scores,
+                                               ss->p_scores, gp, proc, s);
+        else rc = launch_spec_accept(S, k, k + 1, S.v_logits, S.v_latents, S.v_toks + 1, k + 1, dlen, gp, proc, s);
         if (rc) return rc;
         if ((rc = launch_spec_truncate(c->st.seq_len, c->st.mel_pos, slots, B, S.drop_target, s))) return rc;
-        if ((rc = launch_spec_truncate(a->st.seq_len, a->st.mel_pos, aslots, B, S.drop_assistant, s))) return rc;
+        if (!lk && (rc = launch_spec_truncate(a->st.seq_len, a->st.mel_pos, aslots, B, S.drop_assistant, s))) return rc;
     }
     return GVC_OK;
 }
@@ -2305,7 +2329,7 @@ static int assisted_rounds(gvc_gpt* c, gvc_gpt* a, const int32_t* slots, const i
 extern "C" int gvc_gpt_generate_assisted(gvc_gpt* c, gvc_gpt* a, const int32_t* slots, const int32_t* aslots, const gvc_spec_state* st,
                                          const gvc_sample_params* p, const gvc_logits_processors* proc, int32_t first, int32_t n_rounds,
                                          int32_t k, int32_t max_keys, int32_t a_max_keys, gvc_stream sv) {
-    return assisted_rounds(c, a, slots, aslots, st, nullptr, p, proc, first, n_rounds, k, max_keys, a_max_keys, sv);
+    return assisted_rounds(c, a, slots, aslots, st, nullptr, p, proc, first, n_rounds, k, max_keys, a_max_keys, nullptr, sv);
 }
 
 extern "C" int gvc_gpt_generate_assisted_sample(gvc_gpt* c, gvc_gpt* a, const int32_t* slots, const int32_t* aslots,
@@ -2314,7 +2338,15 @@ extern "C" int gvc_gpt_generate_assisted_sample(gvc_gpt* c, gvc_gpt* a, const in
                                                 int32_t max_keys, int32_t a_max_keys, gvc_stream sv) {
     GVC_REQUIRE(ss, GVC_ERR_ARG, "generate_assisted_sample: null sampling workspaces");
     GVC_REQUIRE(p && p->top_k != 1, GVC_ERR_ARG, "generate_assisted_sample: top_k == 1 is the greedy call (gvc_gpt_generate_assisted)");
-    return assisted_rounds(c, a, slots, aslots, st, ss, p, proc, first, n_rounds, k, max_keys, a_max_keys, sv);
+    return assisted_rounds(c, a, slots, aslots, st, ss, p, proc, first, n_rounds, k, max_keys, a_max_keys, nullptr, sv);
+}
+
+extern "C" int gvc_gpt_generate_lookup(gvc_gpt* c, const int32_t* slots, const gvc_spec_state* st, const gvc_spec_sampling* ss,
+                                       const gvc_sample_params* p, const gvc_logits_processors* proc, int32_t first, int32_t n_rounds,
+                                       int32_t k, int32_t max_ngram, int32_t from, int32_t* draft_len, int32_t max_keys, gvc_stream sv) {
+    GVC_REQUIRE(!ss || (p && p->top_k != 1), GVC_ERR_ARG, "generate_lookup: top_k == 1 is the greedy call (pass no sampling workspaces)");
+    const LookupDrafts lk = {max_ngram, from, draft_len};
+    return assisted_rounds(c, nullptr, slots, nullptr, st, ss, p, proc, first, n_rounds, k, max_keys, 0, &lk, sv);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -1,5 +1,6 @@
 // Assisted (speculative) decoding on the device, greedy and sampled (include/genvc_hip.h: gvc_gpt_verify, gvc_gpt_truncate,
-// gvc_spec_accept, gvc_spec_accept_sample, gvc_gpt_generate_assisted, gvc_gpt_generate_assisted_sample): the input rows and length
+// gvc_spec_accept[_len], gvc_spec_accept_sample[_len], gvc_spec_lookup, gvc_gpt_generate_assisted, gvc_gpt_generate_assisted_sample,
+// gvc_gpt_generate_lookup): the input rows and length
 // bookkeeping of a multi-row verification pass, the rollback of a slot, and the accept steps.  The block stack and the head of the
 // verification are the context's own (gpt.hip: run_rows, launch_head); the round loop that chains them with the draft context's decode
 // steps lives there too.
@@ -17,6 +18,8 @@ constexpr int kSpecThreads = 256;
 constexpr int kSpecMaxVocab = 2048;     // one byte per vocabulary entry in LDS (the sampler's bound)
 constexpr int kSpecMaxDrafts = 15;      // k: a round verifies k + 1 <= 16 rows per stream
 constexpr int kSpecMaxRows = 128;       // rows of one verification pass (the skinny GEMMs' bound)
+constexpr int kSpecMaxNgram = 8;        // prompt lookup: the longest suffix searched for
+constexpr int kSpecMaxHistory = 2048;   // prompt lookup: ids of one row's history staged in LDS (8 KB)
 
 // Row (b, t) of a verification pass: x[b * T + t] = mel_emb[toks[b][t]] + mel_pos[mel_pos_idx[slot b] + t], the token clamped into the
 // vocabulary and the position into the table.  base_out[slot b] = the cache position of row (b, 0): seq_len[slot], or the last one at
@@ -35,14 +38,22 @@ int launch_spec_truncate(int32_t* seq_len, int32_t* mel_pos_idx, const int32_t* 
 // rng_row = 3 b, rng_step0 = emitted[b]
 int launch_spec_round_begin(const gvc_spec_state& st, int k1, int32_t* step_ctr, gvc_row_sampling* rows, const gvc_sample_params& p,
                             hipStream_t s);
-// the accept step (include/genvc_hip.h: gvc_spec_accept); the arguments are checked by the callers
+// start of a round whose drafts come from prompt lookup (include/genvc_hip.h: gvc_spec_lookup): per stream, row 0 of the verification
+// tokens is the pending token, rows 1..draft_len[b] the ids that followed the earliest earlier occurrence of the longest suffix (up to
+// max_ngram ids) of ids[from .. ids_len), the rest the pending token again; q (nullable) [B][k + 1][vocab] gets the drafts' one-hot rows
+int launch_spec_lookup(const gvc_spec_state& st, int k, int max_ngram, int from, int32_t* draft_len, float* q, int vocab, hipStream_t s);
+int check_spec_lookup(const gvc_spec_state* st, int k, int max_ngram, int from, const int32_t* draft_len, int vocab);
+// the accept step (include/genvc_hip.h: gvc_spec_accept_len); the arguments are checked by the callers.  draft_len (nullable, device
+// [B]): drafts row b has; null: every row has k
 int launch_spec_accept(const gvc_spec_state& st, int k, int appended, const float* logits, const float* latents, const int32_t* drafts,
-                       int draft_stride, const gvc_sample_params& p, const gvc_logits_processors* proc, hipStream_t s);
-// the accept step of speculative sampling (include/genvc_hip.h: gvc_spec_accept_sample): [d_1..d_k' behind the rows' ids when
-// put_drafts,] k_spec_warp of the B * (k + 1) logits rows into p_rows, then k_spec_accept_sample; the arguments are checked by the callers
+                       int draft_stride, const int32_t* draft_len, const gvc_sample_params& p, const gvc_logits_processors* proc,
+                       hipStream_t s);
+// the accept step of speculative sampling (include/genvc_hip.h: gvc_spec_accept_sample_len): [d_1..d_k' behind the rows' ids when
+// put_drafts,] k_spec_warp of the B * (k + 1) logits rows into p_rows, then k_spec_accept_sample; the arguments are checked by the
+// callers.  draft_len as in launch_spec_accept
 int launch_spec_accept_sample(const gvc_spec_state& st, int k, int appended, const float* logits, const float* latents,
-                              const int32_t* drafts, int draft_stride, bool put_drafts, const float* q, float* p_rows,
-                              const gvc_sample_params& p, const gvc_logits_processors* proc, hipStream_t s);
+                              const int32_t* drafts, int draft_stride, const int32_t* draft_len, bool put_drafts, const float* q,
+                              float* p_rows, const gvc_sample_params& p, const gvc_logits_processors* proc, hipStream_t s);
 // host-side checks of a sampled call: the workspaces (rows only when need_rows), top_k <= vocab, temperature and repetition penalty > 0
 int check_spec_sampling(const float* q, const float* p_rows, const gvc_row_sampling* rows, bool need_rows, const gvc_sample_params* p);
 // host-side checks of a state and a call's k

@@ -73,6 +73,65 @@ __global__ void k_spec_round_begin(gvc_spec_state S, int k1, int32_t* step_ctr, 
     }
 }
 
+// Prompt lookup (spec.h: launch_spec_lookup): the draft side of a round without a draft model, and the round's begin.  One workgroup
+// per stream.  The history h = ids[from .. ids_len) is staged in LDS; for n = min(max_ngram, len - 1) down to 1 thread t tests the start
+// indices t, t + 256, .. (ascending, so its first hit is its lowest), the lowest hit of the workgroup is found by a wave reduction and
+// four LDS words, and the loop leaves at the first n with a hit: len, n and the reduced index are the same in every thread, so every
+// barrier is reached by all of them.  Plain stores only
+__global__ __launch_bounds__(kSpecThreads) void k_spec_lookup(gvc_spec_state S, int k, int max_ngram, int from, int32_t* draft_len,
+                                                              float* q, int V) {
+    __shared__ int32_t h[kSpecMaxHistory];
+    __shared__ int red[kSpecThreads / 64];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int pend = S.pending[b];
+    int32_t* vt = S.v_toks + (size_t)b * (k + 1);
+    // (uniform over the workgroup: a finished row leaves before the first barrier)
+    if (S.finished[b]) {
+        if (tid <= k) vt[tid] = pend;
+        if (tid == 0) draft_len[b] = 0;
+        return;
+    }
+    const int32_t* ids = S.ids + (size_t)b * S.ids_stride + from;
+    const int len = min(max(min(S.ids_len[b], S.ids_stride) - from, 0), kSpecMaxHistory);
+    for (int i = tid; i < len; i += kSpecThreads) h[i] = ids[i];
+    __syncthreads();
+    int start = -1;          // index of the first draft in h
+    for (int n = min(max_ngram, len - 1); n >= 1; --n) {
+        const int32_t* suf = h + len - n;
+        int best = 0x7fffffff;
+        for (int i = tid; i + n < len; i += kSpecThreads) {
+            bool eq = true;
+            for (int j = 0; j < n; ++j) eq = eq && h[i + j] == suf[j];
+            if (eq) { best = i; break; }
+        }
+        for (int off = 32; off > 0; off >>= 1) best = min(best, __shfl_xor(best, off));
+        if ((tid & 63) == 0) red[tid >> 6] = best;
+        __syncthreads();
+        best = min(min(red[0], red[1]), min(red[2], red[3]));
+        __syncthreads();          // red is written again for the next n
+        if (best != 0x7fffffff) { start = best + n; break; }
+    }
+    const int cnt = start >= 0 ? min(k, len - start) : 0;
+    // column 0: the pending token; columns 1..cnt: the drafts; the rest: the pending token again, a valid id nobody compares
+    if (tid <= k) vt[tid] = tid >= 1 && tid <= cnt ? h[start + tid - 1] : pend;
+    if (tid == 0) draft_len[b] = cnt;
+    if (q) {
+        // the one-hot row of draft j in the form the accept step reads (warped scores): 0 at the token and -inf elsewhere, which
+        // weighs expf(0) = 1 there and nothing elsewhere -- probability exactly 1.0 at v_toks[b][j] and 0 at every other id
+        for (int j = 1; j <= k; ++j) {
+            const int tok = j <= cnt ? h[start + j - 1] : pend;
+            float* row = q + ((size_t)b * (k + 1) + j) * V;
+            for (int v = tid; v < V; v += kSpecThreads) row[v] = v == tok ? 0.f : -INFINITY;
+        }
+    }
+}
+
+// k' of a live row: min(k, budget[, draft_len[b]]) -- draft_len null is the count every row had before there was one
+__device__ __forceinline__ int spec_drafts(int k, int budget, const int32_t* draft_len, int b) {
+    const int kk = min(k, budget);
+    return draft_len ? min(kk, max(draft_len[b], 0)) : kk;
+}
+
 // the call's processors BY VALUE as a kernel argument (the caller's struct is free when the launch is enqueued)
 struct SpecProc {
     int on;
@@ -81,7 +140,7 @@ struct SpecProc {
 
 __global__ __launch_bounds__(kSpecThreads) void k_spec_accept(gvc_spec_state S, int k, int appended, const float* logits,
                                                               const float* latents, const int32_t* drafts, int draft_stride,
-                                                              gvc_sample_params p, SpecProc pr) {
+                                                              const int32_t* draft_len, gvc_sample_params p, SpecProc pr) {
     __shared__ unsigned seen_w[kSpecMaxVocab / 4];          // one byte per vocabulary entry
     __shared__ float red_v[kSpecThreads / 64];
     __shared__ int red_i[kSpecThreads / 64];
@@ -102,7 +161,8 @@ __global__ __launch_bounds__(kSpecThreads) void k_spec_accept(gvc_spec_state S, 
     }
     int32_t* ids = S.ids + (size_t)b * S.ids_stride;
     const int32_t* dr = drafts ? drafts + (size_t)b * draft_stride : nullptr;
-    const int kk = dr ? min(k, S.max_new - em0 - 1) : 0;          // drafts compared: HF's clamp of the draft length to the budget
+    // drafts compared: HF's clamp of the draft length to the budget, and the row's own count where the draft source gives one
+    const int kk = dr ? spec_drafts(k, S.max_new - em0 - 1, draft_len, b) : 0;
     const float rep_pen = p.repetition_penalty, temp = p.temperature;
     for (int i = tid; i < kSpecMaxVocab / 4; i += kSpecThreads) seen_w[i] = 0u;
     __syncthreads();
@@ -187,10 +247,10 @@ __global__ __launch_bounds__(kSpecThreads) void k_spec_accept(gvc_spec_state S, 
 // ---- speculative sampling ---------------------------------------------------------------------------------------------------------
 // d_1..d_k' behind the ids of every live row (the draft sampler has put them there in a generation; gvc_spec_accept_sample alone has
 // only the draft array)
-__global__ void k_spec_put_drafts(gvc_spec_state S, int k, const int32_t* drafts, int draft_stride) {
+__global__ void k_spec_put_drafts(gvc_spec_state S, int k, const int32_t* drafts, int draft_stride, const int32_t* draft_len) {
     const int b = blockIdx.x, em0 = S.emitted[b];
     if (S.finished[b] || em0 >= S.max_new) return;
-    const int kk = min(k, S.max_new - em0 - 1), len0 = S.ids_len[b];
+    const int kk = spec_drafts(k, S.max_new - em0 - 1, draft_len, b), len0 = S.ids_len[b];
     for (int j = threadIdx.x; j < kk; j += blockDim.x)
         if (len0 + j < S.ids_stride) S.ids[(size_t)b * S.ids_stride + len0 + j] = drafts[(size_t)b * draft_stride + j];
 }
@@ -198,11 +258,12 @@ __global__ void k_spec_put_drafts(gvc_spec_state S, int k, const int32_t* drafts
 // p_i of verification row (b, i): the sampler's chain at ids length ids_len[b] + i, stored as the sampler stores scores_out.  One
 // workgroup per row, so the sorts of a stream run side by side.  Rows of finished streams and rows behind the k' drafts the accept
 // step compares return at once
-__global__ __launch_bounds__(kSampThreads) void k_spec_warp(gvc_spec_state S, int k, const float* logits, float* p_out, gvc_sample_params p,
-                                                            SpecProc pr) {
+__global__ __launch_bounds__(kSampThreads) void k_spec_warp(gvc_spec_state S, int k, const float* logits, float* p_out,
+                                                            const int32_t* draft_len, gvc_sample_params p, SpecProc pr) {
     const int r = blockIdx.x, b = r / (k + 1), i = r - b * (k + 1);
     const int em0 = S.emitted[b];
-    if (S.finished[b] || em0 >= S.max_new || i > min(k, S.max_new - em0 - 1)) return;          // (uniform over the workgroup)
+    // (uniform over the workgroup)
+    if (S.finished[b] || em0 >= S.max_new || i > spec_drafts(k, S.max_new - em0 - 1, draft_len, b)) return;
     SampleCall C = {};
     C.p = p;
     C.scores_warped = 1;
@@ -270,8 +331,9 @@ __device__ __forceinline__ void spec_scan2(double& a, double& b, double* scr, do
 // rows [B][k + 1][vocab] of the draft (row j: what d_j was drawn from) and of the target (row i: verification row i).  Only the rows up
 // to the first rejection are read.  The bookkeeping is k_spec_accept's, field for field
 __global__ __launch_bounds__(kSpecThreads) void k_spec_accept_sample(gvc_spec_state S, int k, int appended, const float* latents,
-                                                                     const int32_t* drafts, int draft_stride, const float* q,
-                                                                     const float* p, gvc_sample_params sp) {
+                                                                     const int32_t* drafts, int draft_stride,
+                                                                     const int32_t* draft_len, const float* q, const float* p,
+                                                                     gvc_sample_params sp) {
     __shared__ double dscr[8];
     __shared__ float fscr[8];
     __shared__ int s_pick, s_last, s_acc;
@@ -289,7 +351,7 @@ __global__ __launch_bounds__(kSpecThreads) void k_spec_accept_sample(gvc_spec_st
     }
     int32_t* ids = S.ids + (size_t)b * S.ids_stride;
     const int32_t* dr = drafts ? drafts + (size_t)b * draft_stride : nullptr;
-    const int kk = dr ? min(k, S.max_new - em0 - 1) : 0;
+    const int kk = dr ? spec_drafts(k, S.max_new - em0 - 1, draft_len, b) : 0;
     const int i0 = tid * kSpecPer;
     int m = 0, acc = 0, last = eos;
     bool fin = false;
@@ -432,26 +494,35 @@ int launch_spec_round_begin(const gvc_spec_state& st, int k1, int32_t* step_ctr,
     return GVC_OK;
 }
 
+int launch_spec_lookup(const gvc_spec_state& st, int k, int max_ngram, int from, int32_t* draft_len, float* q, int vocab, hipStream_t s) {
+    hipLaunchKernelGGL(k_spec_lookup, dim3(st.B), dim3(kSpecThreads), 0, s, st, k, max_ngram, from, draft_len, q, vocab);
+    GVC_LAUNCH_CHECK();
+    return GVC_OK;
+}
+
 int launch_spec_accept(const gvc_spec_state& st, int k, int appended, const float* logits, const float* latents, const int32_t* drafts,
-                       int draft_stride, const gvc_sample_params& p, const gvc_logits_processors* proc, hipStream_t s) {
+                       int draft_stride, const int32_t* draft_len, const gvc_sample_params& p, const gvc_logits_processors* proc,
+                       hipStream_t s) {
     SpecProc pr;
     memset(&pr, 0, sizeof(pr));
     if (proc) { pr.on = 1; pr.P = *proc; }
-    hipLaunchKernelGGL(k_spec_accept, dim3(st.B), dim3(kSpecThreads), 0, s, st, k, appended, logits, latents, drafts, draft_stride, p, pr);
+    hipLaunchKernelGGL(k_spec_accept, dim3(st.B), dim3(kSpecThreads), 0, s, st, k, appended, logits, latents, drafts, draft_stride,
+                       draft_len, p, pr);
     GVC_LAUNCH_CHECK();
     return GVC_OK;
 }
 
 int launch_spec_accept_sample(const gvc_spec_state& st, int k, int appended, const float* logits, const float* latents,
-                              const int32_t* drafts, int draft_stride, bool put_drafts, const float* q, float* p_rows,
-                              const gvc_sample_params& p, const gvc_logits_processors* proc, hipStream_t s) {
+                              const int32_t* drafts, int draft_stride, const int32_t* draft_len, bool put_drafts, const float* q,
+                              float* p_rows, const gvc_sample_params& p, const gvc_logits_processors* proc, hipStream_t s) {
     SpecProc pr;
     memset(&pr, 0, sizeof(pr));
     if (proc) { pr.on = 1; pr.P = *proc; }
-    if (put_drafts && drafts && k > 0) hipLaunchKernelGGL(k_spec_put_drafts, dim3(st.B), dim3(64), 0, s, st, k, drafts, draft_stride);
-    hipLaunchKernelGGL(k_spec_warp, dim3(st.B * (k + 1)), dim3(kSampThreads), 0, s, st, k, logits, p_rows, p, pr);
-    hipLaunchKernelGGL(k_spec_accept_sample, dim3(st.B), dim3(kSpecThreads), 0, s, st, k, appended, latents, drafts, draft_stride, q,
-                       (const float*)p_rows, p);
+    if (put_drafts && drafts && k > 0)
+        hipLaunchKernelGGL(k_spec_put_drafts, dim3(st.B), dim3(64), 0, s, st, k, drafts, draft_stride, draft_len);
+    hipLaunchKernelGGL(k_spec_warp, dim3(st.B * (k + 1)), dim3(kSampThreads), 0, s, st, k, logits, p_rows, draft_len, p, pr);
+    hipLaunchKernelGGL(k_spec_accept_sample, dim3(st.B), dim3(kSpecThreads), 0, s, st, k, appended, latents, drafts, draft_stride,
+                       draft_len, q, (const float*)p_rows, p);
     GVC_LAUNCH_CHECK();
     return GVC_OK;
 }
@@ -484,30 +555,62 @@ int check_spec_state(const gvc_spec_state* st, int k, const gvc_sample_params* p
     return GVC_OK;
 }
 
+int check_spec_lookup(const gvc_spec_state* st, int k, int max_ngram, int from, const int32_t* draft_len, int vocab) {
+    GVC_REQUIRE(st && draft_len, GVC_ERR_ARG, "spec lookup: null argument");
+    GVC_REQUIRE(k >= 1 && k <= kSpecMaxDrafts, GVC_ERR_ARG, "spec lookup: %d draft tokens outside [1, %d]", k, kSpecMaxDrafts);
+    GVC_REQUIRE(max_ngram >= 1 && max_ngram <= kSpecMaxNgram, GVC_ERR_ARG, "spec lookup: max_ngram %d outside [1, %d]", max_ngram,
+                kSpecMaxNgram);
+    GVC_REQUIRE(st->B >= 1 && st->ids_stride >= 1 && from >= 0 && vocab >= 1, GVC_ERR_ARG, "spec lookup: B %d, ids_stride %d, from %d, vocab %d",
+                st->B, st->ids_stride, from, vocab);
+    GVC_REQUIRE(st->ids && st->ids_len && st->finished && st->pending && st->v_toks, GVC_ERR_ARG, "spec lookup: a null state array");
+    GVC_REQUIRE(st->ids_stride - from <= kSpecMaxHistory, GVC_ERR_ARG, "spec lookup: a history of up to %d ids (ids_stride %d - from %d) exceeds %d",
+                st->ids_stride - from, st->ids_stride, from, kSpecMaxHistory);
+    return GVC_OK;
+}
+
 }  // namespace gvc
 
 using namespace gvc;
 
-extern "C" int gvc_spec_accept(const gvc_spec_state* st, int32_t k, int32_t appended, const float* logits, const float* latents,
-                               const int32_t* drafts, int32_t draft_stride, const gvc_sample_params* p, const gvc_logits_processors* proc,
-                               gvc_stream sv) {
+extern "C" int gvc_spec_lookup(const gvc_spec_state* st, int32_t k, int32_t max_ngram, int32_t from, int32_t* draft_len, float* q_scores,
+                               int32_t vocab, gvc_stream sv) {
+    int rc = check_spec_lookup(st, k, max_ngram, from, draft_len, vocab);
+    if (rc) return rc;
+    return launch_spec_lookup(*st, k, max_ngram, from, draft_len, q_scores, vocab, (hipStream_t)sv);
+}
+
+extern "C" int gvc_spec_accept_len(const gvc_spec_state* st, int32_t k, int32_t appended, const float* logits, const float* latents,
+                                   const int32_t* drafts, int32_t draft_stride, const int32_t* draft_len, const gvc_sample_params* p,
+                                   const gvc_logits_processors* proc, gvc_stream sv) {
     int rc = check_spec_state(st, k, p, proc, false);
     if (rc) return rc;
     GVC_REQUIRE(logits && (k == 0 || (drafts && draft_stride >= k)) && (appended == 0 || appended == k + 1), GVC_ERR_ARG,
                 "gvc_spec_accept: bad argument (k %d, appended %d, draft_stride %d)", k, appended, draft_stride);
     GVC_REQUIRE(!st->lats || latents, GVC_ERR_ARG, "gvc_spec_accept: a latent buffer without latent rows");
-    return launch_spec_accept(*st, k, appended, logits, latents, k > 0 ? drafts : nullptr, draft_stride, *p, proc, (hipStream_t)sv);
+    return launch_spec_accept(*st, k, appended, logits, latents, k > 0 ? drafts : nullptr, draft_stride, draft_len, *p, proc, (hipStream_t)sv);
 }
 
-extern "C" int gvc_spec_accept_sample(const gvc_spec_state* st, int32_t k, int32_t appended, const float* logits, const float* latents,
-                                      const int32_t* drafts, int32_t draft_stride, const float* q_scores, float* p_scores,
-                                      const gvc_sample_params* p, const gvc_logits_processors* proc, gvc_stream sv) {
+extern "C" int gvc_spec_accept(const gvc_spec_state* st, int32_t k, int32_t appended, const float* logits, const float* latents,
+                               const int32_t* drafts, int32_t draft_stride, const gvc_sample_params* p, const gvc_logits_processors* proc,
+                               gvc_stream sv) {
+    return gvc_spec_accept_len(st, k, appended, logits, latents, drafts, draft_stride, nullptr, p, proc, sv);
+}
+
+extern "C" int gvc_spec_accept_sample_len(const gvc_spec_state* st, int32_t k, int32_t appended, const float* logits, const float* latents,
+                                          const int32_t* drafts, int32_t draft_stride, const int32_t* draft_len, const float* q_scores,
+                                          float* p_scores, const gvc_sample_params* p, const gvc_logits_processors* proc, gvc_stream sv) {
     int rc = check_spec_state(st, k, p, proc, false);
     if (rc) return rc;
     if ((rc = check_spec_sampling(k > 0 ? q_scores : p_scores, p_scores, nullptr, false, p))) return rc;
     GVC_REQUIRE(logits && (k == 0 || (drafts && draft_stride >= k)) && (appended == 0 || appended == k + 1), GVC_ERR_ARG,
                 "gvc_spec_accept_sample: bad argument (k %d, appended %d, draft_stride %d)", k, appended, draft_stride);
     GVC_REQUIRE(!st->lats || latents, GVC_ERR_ARG, "gvc_spec_accept_sample: a latent buffer without latent rows");
-    return launch_spec_accept_sample(*st, k, appended, logits, latents, k > 0 ? drafts : nullptr, draft_stride, true, q_scores, p_scores, *p,
-                                     proc, (hipStream_t)sv);
+    return launch_spec_accept_sample(*st, k, appended, logits, latents, k > 0 ? drafts : nullptr, draft_stride, draft_len, true, q_scores,
+                                     p_scores, *p, proc, (hipStream_t)sv);
+}
+
+extern "C" int gvc_spec_accept_sample(const gvc_spec_state* st, int32_t k, int32_t appended, const float* logits, const float* latents,
+                                      const int32_t* drafts, int32_t draft_stride, const float* q_scores, float* p_scores,
+                                      const gvc_sample_params* p, const gvc_logits_processors* proc, gvc_stream sv) {
+    return gvc_spec_accept_sample_len(st, k, appended, logits, latents, drafts, draft_stride, nullptr, q_scores, p_scores, p, proc, sv);
 }

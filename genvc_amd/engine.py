@@ -608,6 +608,8 @@ class ContrastiveSearch:
 
 MAX_ASSISTANT_TOKENS = 15    # kSpecMaxDrafts (csrc/spec.h): drafts per round of an assisted generation
 MAX_VERIFY_ROWS = 128        # kSpecMaxRows: rows of one verification pass, B * (k + 1)
+MAX_LOOKUP_NGRAM = 8         # kSpecMaxNgram: the longest suffix a prompt lookup searches for
+MAX_LOOKUP_HISTORY = 2048    # kSpecMaxHistory: ids of one row's history a prompt lookup stages (the ids row behind `from`)
 
 
 class AssistedState:
@@ -639,6 +641,7 @@ class AssistedState:
         self.v_logits = torch.zeros(B, MAX_ASSISTANT_TOKENS + 1, self.vocab, device=dev, dtype=torch.float32)
         self.v_latents = torch.zeros(B, MAX_ASSISTANT_TOKENS + 1, self.d, device=dev, dtype=torch.float32)
         self.d_ids_len, self.d_finished = i32(B), i32(B)
+        self.draft_len = i32(B)      # drafts per row of a prompt-lookup round (gvc_spec_lookup writes it, the accept step reads it)
         self.opened = False          # the opening step (token 0 from the prefill's parked logits) has run
         self.rounds_done = 0         # rounds enqueued so far (every live row emits at least one token per round)
         p = (lambda t: None if t is None else t.data_ptr())
@@ -663,24 +666,51 @@ class AssistedState:
         return dict(rounds=self.rounds.long(), drafted=self.drafted.long(), accepted=self.accepted.long())
 
 
-def spec_accept(state, k, appended, logits, latents, drafts, params, proc=None):
+def spec_lookup(state, k, max_ngram, start, q_scores=None):
+    """the prompt lookup of one round on `state` (include/genvc_hip.h: gvc_spec_lookup): k drafts per row from the longest suffix (up
+    to max_ngram ids) of ids[start .. ids_len) that occurs earlier in it.  Fills state.v_toks (as [B, k + 1]) and state.draft_len;
+    q_scores fp32 [B, k + 1, V] (optional) gets the drafts' one-hot rows as warped scores (0 at the token, -inf elsewhere)"""
+    assert q_scores is None or (tuple(q_scores.shape) == (state.B, k + 1, state.vocab) and q_scores.is_contiguous())
+    check(lib().gvc_spec_lookup(C.byref(state.c), int(k), int(max_ngram), int(start), ptr(state.draft_len),
+                                ptr(None if q_scores is None else _f32(q_scores)), state.vocab, stream()), "spec_lookup")
+
+
+def spec_accept(state, k, appended, logits, latents, drafts, params, proc=None, draft_len=None):
     """the accept step of an assisted round on `state` (include/genvc_hip.h: gvc_spec_accept): logits fp32 [B, k + 1, V], latents fp32
-    [B, k + 1, d] or None, drafts int32 [B, >= k] or None for k = 0; appended: rows both caches gained (k + 1, or 0 for an opening step)"""
+    [B, k + 1, d] or None, drafts int32 [B, >= k] or None for k = 0; appended: rows both caches gained (k + 1, or 0 for an opening step).
+    draft_len int32 [B] (optional; gvc_spec_accept_len): the drafts each row has, fewer than k where its source found fewer"""
     B = state.B
     assert tuple(logits.shape) == (B, k + 1, state.vocab) and (latents is None or tuple(latents.shape) == (B, k + 1, state.d))
+    if draft_len is not None:
+        assert tuple(draft_len.shape) == (B,)
+        check(lib().gvc_spec_accept_len(C.byref(state.c), int(k), int(appended), ptr(_f32(logits)),
+                                        ptr(None if latents is None else _f32(latents)), ptr(None if drafts is None else _i32(drafts)),
+                                        0 if drafts is None else drafts.shape[1], ptr(_i32(draft_len)), C.byref(params),
+                                        None if proc is None else C.byref(proc), stream()), "spec_accept_len")
+        return
     check(lib().gvc_spec_accept(C.byref(state.c), int(k), int(appended), ptr(_f32(logits)), ptr(None if latents is None else _f32(latents)),
                                 ptr(None if drafts is None else _i32(drafts)), 0 if drafts is None else drafts.shape[1], C.byref(params),
                                 None if proc is None else C.byref(proc), stream()), "spec_accept")
 
 
-def spec_accept_sample(state, k, appended, logits, latents, drafts, q_scores, params, proc=None):
+def spec_accept_sample(state, k, appended, logits, latents, drafts, q_scores, params, proc=None, draft_len=None):
     """the accept step of speculative sampling on `state`, warping included (include/genvc_hip.h: gvc_spec_accept_sample): arguments as
     spec_accept, plus q_scores fp32 [B, k + 1, V] (row j: the warped row draft j was drawn from; None for k = 0) and every sampling
-    field of `params`.  Returns the target's warped rows fp32 [B, k + 1, V] (rows the step did not need are left as they were)"""
+    field of `params`.  Returns the target's warped rows fp32 [B, k + 1, V] (rows the step did not need are left as they were).
+    draft_len int32 [B] (optional; gvc_spec_accept_sample_len): as in spec_accept"""
     B = state.B
     assert tuple(logits.shape) == (B, k + 1, state.vocab) and (latents is None or tuple(latents.shape) == (B, k + 1, state.d))
     assert q_scores is None or tuple(q_scores.shape) == (B, k + 1, state.vocab)
     p_rows = torch.zeros(B, k + 1, state.vocab, device=logits.device, dtype=torch.float32)
+    if draft_len is not None:
+        assert tuple(draft_len.shape) == (B,)
+        check(lib().gvc_spec_accept_sample_len(C.byref(state.c), int(k), int(appended), ptr(_f32(logits)),
+                                               ptr(None if latents is None else _f32(latents)),
+                                               ptr(None if drafts is None else _i32(drafts)), 0 if drafts is None else drafts.shape[1],
+                                               ptr(_i32(draft_len)), ptr(None if q_scores is None else _f32(q_scores)), ptr(p_rows),
+                                               C.byref(params), None if proc is None else C.byref(proc), stream()),
+              "spec_accept_sample_len")
+        return p_rows
     check(lib().gvc_spec_accept_sample(C.byref(state.c), int(k), int(appended), ptr(_f32(logits)),
                                        ptr(None if latents is None else _f32(latents)), ptr(None if drafts is None else _i32(drafts)),
                                        0 if drafts is None else drafts.shape[1], ptr(None if q_scores is None else _f32(q_scores)),
@@ -1104,6 +1134,25 @@ class GptEngine:
                                                   C.byref(params), None if proc is None else C.byref(proc), int(not state.opened),
                                                   int(n_rounds), k, int(max_keys), int(assistant_max_keys), stream()),
                   "generate_assisted")
+        state.opened = True
+        state.rounds_done += int(n_rounds)
+
+    def generate_lookup(self, slots, state, params, n_rounds, max_keys, max_ngram, proc=None, k=None, sampling=False):
+        """n_rounds rounds of prompt-lookup assisted decoding of `state` (an AssistedState) on this engine alone (include/genvc_hip.h:
+        gvc_gpt_generate_lookup): every round drafts up to k (default state.k; never more) tokens per row from the row's own generated
+        ids -- the longest suffix of up to max_ngram ids that occurs earlier in ids[state.n0 ..] -- and otherwise runs as a round of
+        generate_assisted.  The first call of a state also runs its opening step.  sampling=True: speculative sampling with one-hot
+        draft rows and every sampling field of `params` (top_k != 1)"""
+        self._join_side()
+        if slots.shape[0] != state.B:
+            raise ValueError(f"{slots.shape[0]} slots for {state.B} streams")
+        k = state.k if k is None else int(k)
+        if not 1 <= k <= state.k:
+            raise ValueError(f"{k} drafts per round outside [1, {state.k}]")
+        check(lib().gvc_gpt_generate_lookup(self._h, ptr(_i32(slots)), C.byref(state.c), C.byref(state.sampling()) if sampling else None,
+                                            C.byref(params), None if proc is None else C.byref(proc), int(not state.opened),
+                                            int(n_rounds), k, int(max_ngram), state.n0, ptr(state.draft_len), int(max_keys), stream()),
+              "generate_lookup")
         state.opened = True
         state.rounds_done += int(n_rounds)
 

@@ -11,7 +11,7 @@ import torch
 from torch import nn
 
 from .._lib import GenvcHipError
-from ..engine import (MAX_ASSISTANT_TOKENS, MAX_VERIFY_ROWS, AssistedState, BEAM_LENGTH_MODES, beam_early_stopping, check_beam_groups, GroupBeamSearch, MAX_CONTRASTIVE_K, PROC_KWARGS, WARP_KWARGS, BeamSearch, ContrastiveSearch, GptEngine, WarperSets,
+from ..engine import (MAX_ASSISTANT_TOKENS, MAX_LOOKUP_HISTORY, MAX_LOOKUP_NGRAM, MAX_VERIFY_ROWS, AssistedState, BEAM_LENGTH_MODES, beam_early_stopping, check_beam_groups, GroupBeamSearch, MAX_CONTRASTIVE_K, PROC_KWARGS, WARP_KWARGS, BeamSearch, ContrastiveSearch, GptEngine, WarperSets,
                       check_proc_kwargs, logits_bias, logits_processors, logits_sets, logits_warpers, sample_params)
 from .perceiver_encoder import PerceiverResampler
 
@@ -252,11 +252,30 @@ ASSIST_KWARGS = ("assistant_model", "num_assistant_tokens", "num_assistant_token
                  "speculative_sampling")
 
 
+LOOKUP_KWARGS = ("prompt_lookup_num_tokens", "max_matching_ngram_size")
+_LOOKUP_MODE = "prompt-lookup decoding (prompt_lookup_num_tokens)"
+
+
 def _no_assistant(kw, where):
-    """the paths without a draft model: assistant_model raises, naming the path"""
+    """the paths without assisted decoding: assistant_model and prompt_lookup_num_tokens raise, naming the path"""
     if kw.get("assistant_model") is not None:
         raise NotImplementedError(f"assisted decoding (assistant_model) is not on the {where} path: GPT.generate serves it (greedy, "
                                   "one draft context next to the target's)")
+    if kw.get("prompt_lookup_num_tokens") is not None or kw.get("max_matching_ngram_size") is not None:
+        raise NotImplementedError(f"{_LOOKUP_MODE} is not on the {where} path: GPT.generate serves it (rounds of one verification "
+                                  "pass over the call's own rows)")
+
+
+def _lookup(kw):
+    """the call asks for prompt-lookup decoding.  ValueError: the kwarg next to assistant_model (two draft sources), and
+    max_matching_ngram_size without it (HF ignores the orphan; here a typo in the other kwarg would silently decode plainly)"""
+    if kw.get("prompt_lookup_num_tokens") is None:
+        if kw.get("max_matching_ngram_size") is not None:
+            raise ValueError(f"max_matching_ngram_size={kw.get('max_matching_ngram_size')!r} needs prompt_lookup_num_tokens")
+        return False
+    if kw.get("assistant_model") is not None:
+        raise ValueError("prompt_lookup_num_tokens and assistant_model are two draft sources: pass one of them")
+    return True
 
 
 def _speculative(kw):
@@ -265,12 +284,14 @@ def _speculative(kw):
     return bool(kw.get("speculative_sampling")) and bool(kw.get("do_sample", True)) and kw.get("top_k", 0) != 1
 
 
-def _assisted_kwargs(kw, B):
+def _assisted_kwargs(kw, B, lookup=False):
     """the kwargs of GPT.generate(assistant_model=...) validated -> k, the drafts per round.  Assisted decoding is greedy, or -- with
     the opt-in speculative_sampling=True -- sampled (do_sample, top_k != 1: _speculative(kw)): every other mode of generate raises
     NotImplementedError naming the combination; a k outside [1, 15], more than 128 verification rows and a schedule other than
-    "constant" raise ValueError"""
-    mode = "assisted decoding (assistant_model)"
+    "constant" raise ValueError.
+    lookup: the kwargs of GPT.generate(prompt_lookup_num_tokens=k, max_matching_ngram_size=N) instead -> (k, N): the same refusals
+    under that mode's name, k required in [1, 15], N in [1, 8] (default 2, HF's)"""
+    mode = _LOOKUP_MODE if lookup else "assisted decoding (assistant_model)"
     spec = kw.get("speculative_sampling")
     if spec is not None and not isinstance(spec, bool):
         raise ValueError(f"speculative_sampling must be True, False or None, not {spec!r}")
@@ -296,14 +317,21 @@ def _assisted_kwargs(kw, B):
     if sched is not None and sched != "constant":
         raise ValueError(f"num_assistant_tokens_schedule={sched!r} with {mode}: only \"constant\" is served (a heuristic schedule needs "
                          "a host round trip per round)")
-    k = kw.get("num_assistant_tokens")
-    k = 5 if k is None else k
+    name = "prompt_lookup_num_tokens" if lookup else "num_assistant_tokens"
+    k = kw.get(name)
+    k = 5 if k is None else k          # (a lookup call always names its k: _lookup)
     if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= MAX_ASSISTANT_TOKENS:
-        raise ValueError(f"num_assistant_tokens must be an int in [1, {MAX_ASSISTANT_TOKENS}] for {mode}, not {k!r}")
+        raise ValueError(f"{name} must be an int in [1, {MAX_ASSISTANT_TOKENS}] for {mode}, not {k!r}")
     if B * (k + 1) > MAX_VERIFY_ROWS:
-        raise ValueError(f"{mode}: {B} items x (num_assistant_tokens + 1 = {k + 1}) rows exceed the {MAX_VERIFY_ROWS} rows of one "
+        raise ValueError(f"{mode}: {B} items x ({name} + 1 = {k + 1}) rows exceed the {MAX_VERIFY_ROWS} rows of one "
                          "verification pass")
-    return k
+    if not lookup:
+        return k
+    N = kw.get("max_matching_ngram_size")
+    N = 2 if N is None else N
+    if isinstance(N, bool) or not isinstance(N, int) or not 1 <= N <= MAX_LOOKUP_NGRAM:
+        raise ValueError(f"max_matching_ngram_size must be an int in [1, {MAX_LOOKUP_NGRAM}] for {mode}, not {N!r}")
+    return k, N
 
 
 def _plain_rows_only(kw, where, beams=True):
@@ -640,9 +668,13 @@ class GPT(nn.Module):
         assistant_model = another initialised GPT: assisted (speculative) greedy decoding (_generate_assisted), checked
         before every other mode; the tokens are those of the call without it.  None is exactly that call.  With
         speculative_sampling=True a sampled call is served too (speculative sampling: same distribution per token, other tokens than
-        the plain call with that seed; _generate_assisted)."""
+        the plain call with that seed; _generate_assisted).
+        prompt_lookup_num_tokens = k (1..15) [, max_matching_ngram_size = N (1..8, default 2)]: assisted decoding without a draft
+        model (_generate_assisted) -- the drafts of a round are the k ids that followed the earliest earlier
+        occurrence of the row's last up-to-N generated ids.  Greedy (the tokens of the call without it), or sampled with
+        speculative_sampling=True.  With assistant_model, or max_matching_ngram_size alone: ValueError."""
         _num_return(generate_kwargs)
-        if generate_kwargs.get("assistant_model") is not None:
+        if _lookup(generate_kwargs) or generate_kwargs.get("assistant_model") is not None:
             return self._generate_assisted(cond_latents, text_inputs, generate_kwargs)
         scale = _guidance_scale(generate_kwargs)
         if scale is not None:
@@ -761,46 +793,61 @@ class GPT(nn.Module):
         prefix is drawn from max(p - q, 0) (from p behind k accepted drafts).  Each emitted token is distributed as a plain sampled
         token of this model under the same warpers; the tokens are NOT those of the plain call with the same `seed` -- the uniforms
         are keyed by (seed, position in the generation, 3 * row + {0: draft, 1: accept, 2: residual}), so they do not depend on
-        `group` either.  do_sample=False or top_k=1 with the kwarg is the greedy mode above.  The host reads the finished flags once per max(1, group // (k + 1)) rounds.  Token 0 of a row comes from
+        `group` either.  do_sample=False or top_k=1 with the kwarg is the greedy mode above.
+        prompt_lookup_num_tokens=k [, max_matching_ngram_size=N] instead of assistant_model (HF's PromptLookupCandidateGenerator;
+        include/genvc_hip.h: gvc_gpt_generate_lookup): no draft model -- a round's drafts are the up to k ids that
+        followed the earliest earlier occurrence of the row's last n <= N GENERATED ids, the longest n with a hit; the prompt's
+        placeholder ids are never searched.  A row without a hit still pays the round's (k + 1)-row pass and emits one token.  Same
+        modes, refusals, returns and stats; sampled, the draft rows are one-hot (accept d iff u_acc <= p(d)).  The host reads the finished flags once per max(1, group // (k + 1)) rounds.  Token 0 of a row comes from
         the prefill's logits (the opening step: no round is counted for it), so a row of n tokens whose drafts were all accepted ran
         ceil((n - 1) / (k + 1)) rounds.  Returns what the call without the assistant returns (tokens bit for bit; `last_latents`
         from the verification rows) and sets `last_assist_stats`: dict(rounds, drafted, accepted), int64 [B] each."""
         kw = dict(generate_kwargs)
-        asst = kw.pop("assistant_model")
+        asst = kw.pop("assistant_model", None)
         acond = kw.pop("assistant_cond_latents", None)
         B = int(text_inputs.shape[0])
-        k = _assisted_kwargs(kw, B)
+        lookup = asst is None          # (generate() sends a call here for an assistant or for prompt_lookup_num_tokens, never both)
+        if lookup:
+            k, ngram = _assisted_kwargs(kw, B, lookup=True)
+        else:
+            k = _assisted_kwargs(kw, B)
         spec = _speculative(kw)
-        for name in ASSIST_KWARGS[1:3] + ASSIST_KWARGS[4:]:
+        for name in ASSIST_KWARGS[1:3] + ASSIST_KWARGS[4:] + LOOKUP_KWARGS:
             kw.pop(name, None)
-        mode = "assisted decoding (assistant_model)"
-        if not isinstance(asst, GPT) or asst is self:
-            raise ValueError(f"{mode}: assistant_model must be another GPT, not {type(asst).__name__ if asst is not self else 'the target itself'}")
-        if asst.engine is None:
-            raise ValueError(f"{mode}: the assistant is not initialised (call its init_gpt_for_inference() first)")
-        for name in ("num_audio_tokens", "start_audio_token", "stop_audio_token"):
-            if getattr(asst, name) != getattr(self, name):
-                raise ValueError(f"{mode}: the assistant's {name} is {getattr(asst, name)}, the target's {getattr(self, name)}")
-        if acond is None:
-            if asst.model_dim != self.model_dim:
-                raise ValueError(f"{mode}: assistant_cond_latents is required: the assistant's model_dim {asst.model_dim} differs from "
-                                 f"the target's {self.model_dim}")
-            acond = cond_latents
-        if B > self.max_slots or B > asst.max_slots:
-            raise ValueError(f"{mode}: {B} items need {B} KV slots in both contexts (target {self.max_slots}, assistant {asst.max_slots})")
+        mode = _LOOKUP_MODE if lookup else "assisted decoding (assistant_model)"
+        if not lookup:
+            if not isinstance(asst, GPT) or asst is self:
+                raise ValueError(f"{mode}: assistant_model must be another GPT, not {type(asst).__name__ if asst is not self else 'the target itself'}")
+            if asst.engine is None:
+                raise ValueError(f"{mode}: the assistant is not initialised (call its init_gpt_for_inference() first)")
+            for name in ("num_audio_tokens", "start_audio_token", "stop_audio_token"):
+                if getattr(asst, name) != getattr(self, name):
+                    raise ValueError(f"{mode}: the assistant's {name} is {getattr(asst, name)}, the target's {getattr(self, name)}")
+            if acond is None:
+                if asst.model_dim != self.model_dim:
+                    raise ValueError(f"{mode}: assistant_cond_latents is required: the assistant's model_dim {asst.model_dim} differs "
+                                     f"from the target's {self.model_dim}")
+                acond = cond_latents
+            if B > self.max_slots or B > asst.max_slots:
+                raise ValueError(f"{mode}: {B} items need {B} KV slots in both contexts (target {self.max_slots}, assistant {asst.max_slots})")
+        elif B > self.max_slots:
+            raise ValueError(f"{mode}: {B} items need {B} KV slots (the context has {self.max_slots})")
         self._need_engine()
         group = int(kw.pop("group", 16))
         fake = self.compute_embeddings(cond_latents, text_inputs)
-        afake = asst.compute_embeddings(acond, text_inputs)
-        n0, a_n0 = int(fake.shape[1]), int(afake.shape[1])
+        n0 = int(fake.shape[1])
+        a_n0 = n0 if lookup else int(asst.compute_embeddings(acond, text_inputs).shape[1])
         dev = fake.device
         max_new = int(kw.get("max_new_tokens") or self.max_gen_mel_tokens)
+        if lookup and max_new + MAX_ASSISTANT_TOKENS + 1 > MAX_LOOKUP_HISTORY:
+            raise ValueError(f"{mode}: max_new_tokens={max_new} is above the {MAX_LOOKUP_HISTORY - MAX_ASSISTANT_TOKENS - 1} generated "
+                             "ids a lookup searches")
 
-        # drafts that fit the position tables of both contexts when the furthest live row has emitted ub tokens: a round appends
-        # k + 1 rows at cache length n0 + ub - 1 and mel position ub, and both must end below the last table entry
+        # drafts that fit the position tables of both contexts (of this one, for a lookup) when the furthest live row has emitted ub
+        # tokens: a round appends k + 1 rows at cache length n0 + ub - 1 and mel position ub, and both must end below the last table entry
         def fit(ub):
             f = []
-            for m, p0 in ((self, n0), (asst, a_n0)):
+            for m, p0 in ((self, n0),) if lookup else ((self, n0), (asst, a_n0)):
                 f += [m.engine.dims["max_mel_pos"] - 2 - ub, m.engine.dims["max_seq"] - 2 - p0 - ub]
             return min(f)
         if max_new > 1 and fit(max_new - 1) < 1:
@@ -819,7 +866,8 @@ class GPT(nn.Module):
         def run():
             slots = torch.arange(B, device=dev, dtype=torch.int32)
             self.engine.prefill(slots, self._prefix, want_outputs=False)
-            asst.engine.prefill(slots, asst._prefix, want_outputs=False)
+            if not lookup:
+                asst.engine.prefill(slots, asst._prefix, want_outputs=False)
             st = AssistedState(fake, k, max_new, self.stop_audio_token, self.num_audio_tokens, self.model_dim)
             ub = 1          # tokens the furthest live row can have emitted (the opening step emits one)
             while True:
@@ -829,11 +877,15 @@ class GPT(nn.Module):
                 while max_new > 1 and n < per_check and min(k, fit(u)) >= kc:
                     reach = u + kc          # cached positions behind the prompt at the end of this round's verification
                     n, u = n + 1, min(max_new - 1, u + kc + 1)
-                self.engine.generate_assisted(asst.engine, slots, slots, st, params, n, n0 + reach, a_n0 + reach, proc=proc, k=kc, **more)
+                if lookup:
+                    self.engine.generate_lookup(slots, st, params, n, n0 + reach, ngram, proc=proc, k=kc, **more)
+                else:
+                    self.engine.generate_assisted(asst.engine, slots, slots, st, params, n, n0 + reach, a_n0 + reach, proc=proc, k=kc, **more)
                 ub = u
                 end = bool(st.finished.all().item())
                 self.engine.health()          # (the .item() above synchronised)
-                asst.engine.health()
+                if not lookup:
+                    asst.engine.health()
                 if end:
                     return st
         try:
@@ -846,7 +898,8 @@ class GPT(nn.Module):
             torch.cuda.synchronize()
             slots = torch.arange(B, device=dev, dtype=torch.int32)
             self.engine.reset(slots)
-            asst.engine.reset(slots)
+            if not lookup:
+                asst.engine.reset(slots)
             st = run()
         toks = st.toks.long()
         n = self._stop_len(toks)

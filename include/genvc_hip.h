@@ -734,6 +734,47 @@ int gvc_gpt_generate_assisted_sample(gvc_gpt* target, gvc_gpt* assistant, const 
                                      const gvc_logits_processors* proc, int32_t first, int32_t n_rounds, int32_t k, int32_t max_keys,
                                      int32_t assistant_max_keys, gvc_stream s);
 
+/* ------------------------------------------------------------------------------------------
+ * Prompt-lookup assisted decoding (HF generate(prompt_lookup_num_tokens=k, max_matching_ngram_size=N), transformers
+ * generation/candidate_generator.py PromptLookupCandidateGenerator): the drafts of a round come from the row's own history instead of
+ * a draft model.  For a live row with history h = ids[from .. ids_len) (the generated codes; the last entry is the pending token), for
+ * n = min(N, len(h) - 1) down to 1: the lowest index i with h[i .. i + n) == h[len - n ..) and i + n < len (the suffix's own position
+ * never counts, so the continuation is not empty); the first n with a hit wins, and the drafts are h[i + n .. min(i + n + k, len)) -- they
+ * may overlap the suffix.  `from` is the prompt length: the placeholder ids of the prefix and the start token are no codes and are never
+ * searched (HF would match inside them).
+ *
+ * gvc_spec_lookup: the kernel alone, one workgroup per stream, no context needed.  Reads st->ids / ids_stride / ids_len / finished /
+ * pending; writes st->v_toks as [B][k + 1]: column 0 the pending token (the call is the round's begin), columns 1..draft_len[b] the
+ * drafts, the remaining columns the pending token again (a valid id that is never compared); draft_len DEVICE int32 [B] gets the
+ * count, 0..k, and 0 for a finished row.  q_scores (nullable) fp32 [B][k + 1][vocab]: row j = 1..k of a live stream becomes the
+ * one-hot row of v_toks[b][j] in the form gvc_spec_accept_sample reads, a warped scores row -- 0 at the token and -inf at every other
+ * id, i.e. probability exactly 1 at the token and 0 elsewhere.  GVC_ERR_ARG for k outside [1, 15], max_ngram outside [1, 8], negative
+ * `from`, a null array, or ids_stride - from above 2048 (the history is staged in LDS); nothing is launched then.
+ *
+ * gvc_spec_accept_len / gvc_spec_accept_sample_len: gvc_spec_accept / gvc_spec_accept_sample with a draft count per row, draft_len
+ * DEVICE int32 [B] (nullable): k' = min(k, max_new - emitted - 1, draft_len[b]), and drafted += k'.  Null is the entry without it,
+ * bit for bit.
+ *
+ * gvc_gpt_generate_lookup: gvc_gpt_generate_assisted without an assistant; the same contract for `first`, no host synchronisation
+ * inside or between rounds, the checks of gvc_gpt_verify, GVC_ERR_STATE before anything runs when max_keys would pass max_seq - 1, and
+ * pending deferred tokens decoded first.  One round: gvc_spec_lookup -> gvc_gpt_verify of [pending, d_1..d_k] -> gvc_spec_accept_len
+ * (ss null) or gvc_spec_accept_sample_len (ss given; p->top_k != 1) -> gvc_gpt_truncate of the target by drop_target.  Every stream
+ * pays the full (k + 1)-row pass, whatever its draft_len.  Sampled, this is speculative sampling with q = one-hot: draft x at position
+ * e + i is accepted iff u_acc(e + i) <= p_i(x), the residual is p_i with x removed, u_draft is not consumed, and u_acc / u_res stay
+ * keyed by position as above.  ss->rows is not used and may be null.  draft_len: DEVICE int32 [B] workspace owned by the caller.
+ * ------------------------------------------------------------------------------------------ */
+int gvc_spec_lookup(const gvc_spec_state* st, int32_t k, int32_t max_ngram, int32_t from, int32_t* draft_len, float* q_scores,
+                    int32_t vocab, gvc_stream s);
+int gvc_spec_accept_len(const gvc_spec_state* st, int32_t k, int32_t appended, const float* logits, const float* latents,
+                        const int32_t* drafts, int32_t draft_stride, const int32_t* draft_len, const gvc_sample_params* p,
+                        const gvc_logits_processors* proc, gvc_stream s);
+int gvc_spec_accept_sample_len(const gvc_spec_state* st, int32_t k, int32_t appended, const float* logits, const float* latents,
+                               const int32_t* drafts, int32_t draft_stride, const int32_t* draft_len, const float* q_scores,
+                               float* p_scores, const gvc_sample_params* p, const gvc_logits_processors* proc, gvc_stream s);
+int gvc_gpt_generate_lookup(gvc_gpt* target, const int32_t* slots, const gvc_spec_state* st, const gvc_spec_sampling* ss,
+                            const gvc_sample_params* p, const gvc_logits_processors* proc, int32_t first, int32_t n_rounds, int32_t k,
+                            int32_t max_ngram, int32_t from, int32_t* draft_len, int32_t max_keys, gvc_stream s);
+
 /* Which decode step the last gvc_gpt_generate call replayed (diagnostic): 0 none yet, 1 launch-per-phase with split-key attention,
  * 2 launch-per-phase with the fused short-context attention launch, 3 the one-launch step (one stream), 4 the MFMA rows path
  * (launch per phase: 17+ streams, or shapes the one-launch rows step does not serve), 5 the one-launch rows step (2..16 streams,

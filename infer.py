@@ -72,14 +72,36 @@ if __name__ == "__main__":
     parser.add_argument("--num_assistant_tokens", type=int, default=None, metavar="K",
                         help="with --assistant_layers: tokens drafted per round, 1..15 (default 5)")
     parser.add_argument("--assistant_sampling", action="store_true",
-                        help="with --assistant_layers: speculative sampling (GPT.generate(speculative_sampling=True)) -- the draft samples "
+                        help="with --assistant_layers or --prompt_lookup_num_tokens: speculative sampling (GPT.generate(speculative_sampling=True)) -- the draft samples "
                              "and the sampling flags (--top_k, config top_p / temperature) apply; without it --assistant_layers decodes "
                              "greedily")
+    parser.add_argument("--prompt_lookup_num_tokens", type=int, default=None, metavar="K",
+                        help="non-streaming: prompt-lookup assisted decoding (GPT.generate(prompt_lookup_num_tokens=K)), K in 1..15 -- "
+                             "every round drafts the K codes that followed the earliest earlier occurrence of the segment's last codes; "
+                             "no draft model, so it runs on a real checkpoint; greedy, or sampled with --assistant_sampling")
+    parser.add_argument("--max_matching_ngram_size", type=int, default=None, metavar="N",
+                        help="with --prompt_lookup_num_tokens: the longest run of last codes searched for, 1..8 (default 2)")
     args = parser.parse_args()
+    if args.max_matching_ngram_size is not None and args.prompt_lookup_num_tokens is None:
+        raise SystemExit("--max_matching_ngram_size needs --prompt_lookup_num_tokens")
+    if args.prompt_lookup_num_tokens is not None:
+        if args.streaming:
+            raise SystemExit("--prompt_lookup_num_tokens is not on the streaming path (--streaming): GPT.generate serves prompt-lookup "
+                             "decoding")
+        if args.assistant_layers is not None:
+            raise SystemExit("--prompt_lookup_num_tokens and --assistant_layers are two draft sources: pass one of them")
+        if not 1 <= args.prompt_lookup_num_tokens <= 15 or not 1 <= (2 if args.max_matching_ngram_size is None
+                                                                     else args.max_matching_ngram_size) <= 8:
+            raise SystemExit("--prompt_lookup_num_tokens must be in [1, 15] and --max_matching_ngram_size in [1, 8]")
+        if (args.num_beams != 1 or args.penalty_alpha is not None or args.num_return_sequences != 1 or args.token_scores is not None
+                or (args.guidance_scale is not None and args.guidance_scale != 1.0) or args.sequence_bias or args.bad_words_ids
+                or args.forced_eos or args.typical_p is not None or args.epsilon_cutoff is not None or args.eta_cutoff is not None):
+            raise SystemExit("--prompt_lookup_num_tokens does not combine with --num_beams, --penalty_alpha, --num_return_sequences, "
+                             "--guidance_scale, --token_scores, the warper flags, --sequence_bias, --bad_words_ids or --forced_eos")
     if args.num_assistant_tokens is not None and args.assistant_layers is None:
         raise SystemExit("--num_assistant_tokens needs --assistant_layers")
-    if args.assistant_sampling and args.assistant_layers is None:
-        raise SystemExit("--assistant_sampling needs --assistant_layers")
+    if args.assistant_sampling and args.assistant_layers is None and args.prompt_lookup_num_tokens is None:
+        raise SystemExit("--assistant_sampling needs --assistant_layers or --prompt_lookup_num_tokens")
     if args.assistant_layers is not None:
         if not args.synthetic:
             raise SystemExit("--assistant_layers needs --synthetic: no draft checkpoint ships with the reference")
@@ -184,6 +206,11 @@ if __name__ == "__main__":
         gen_kw.update(num_assistant_tokens=5 if args.num_assistant_tokens is None else args.num_assistant_tokens,
                       assistant_model=synthetic_assistant(model.config, args.assistant_layers, device=args.device,
                                                           max_slots=model.gpt.max_slots, weight_dtype=args.weights))
+    if args.prompt_lookup_num_tokens is not None:
+        gen_kw.update(dict(speculative_sampling=True) if args.assistant_sampling else dict(do_sample=False))
+        gen_kw.update(prompt_lookup_num_tokens=args.prompt_lookup_num_tokens)
+        if args.max_matching_ngram_size is not None:
+            gen_kw.update(max_matching_ngram_size=args.max_matching_ngram_size)
     src_wav = load_audio(args.src_wav, model.content_sample_rate, device=args.device)
     ref_audio = load_audio(args.ref_audio, model.config.audio.sample_rate, device=args.device)
     if src_wav is None or ref_audio is None:
@@ -236,6 +263,10 @@ if __name__ == "__main__":
             st = model.gpt.last_assist_stats
             print(f"assisted decoding, last segment: {int(st['rounds'].sum())} rounds, {int(st['accepted'].sum())} of "
                   f"{int(st['drafted'].sum())} drafts accepted (synthetic weights: chance level)")
+        if args.prompt_lookup_num_tokens is not None:
+            st = model.gpt.last_assist_stats
+            print(f"prompt-lookup decoding, last segment: {int(st['rounds'].sum())} rounds, {int(st['accepted'].sum())} of "
+                  f"{int(st['drafted'].sum())} drafts accepted")
         if out["wav"] is not None:
             save_wav(args.output_path, out["wav"], config.audio.sample_rate)
         else:

@@ -23,7 +23,16 @@ tokens per round are not enough).
 measures the round of speculative SAMPLING (GPT.generate(speculative_sampling=True), DESIGN.md 4.17: k full-sampler draft steps that
 store their warped rows, one warp launch over the k + 1 verification rows, the accept kernel) at top_k = 15, top_p = 0.85, temperature
 0.85 on the same cells, interleaved in one process with the greedy round of the same cell and with the plain SAMPLED step of the
-target at the same settings, and adds its section to --out behind the greedy report (rendered from --json as it stands)."""
+target at the same settings, and adds its section to --out behind the greedy report (rendered from --json as it stands).
+
+    python scripts/assisted_bench.py --lookup [--lookup_json profiles/assisted_lookup.json]
+
+measures the round of PROMPT-LOOKUP decoding (GPT.generate(prompt_lookup_num_tokens=k), DESIGN.md 4.18: one lookup launch, the
+(k + 1)-row verification pass, accept, one rollback; no assistant) at max_matching_ngram_size = 2 for k = 3 / 5 / 7, greedy and
+sampled (the settings of --sample), twice per cell: as the call runs on this model (the drafted and accepted counts are reported), and
+with the lookup's `from` moved behind the ids row so that no round finds a match (every round emits exactly one token, asserted) --
+the price every stream pays whatever it drafts.  Interleaved in one process with the plain greedy and sampled steps; its section
+follows the others in --out."""
 import argparse
 import json
 import os
@@ -34,6 +43,7 @@ sys.path.insert(0, ROOT)
 
 LAYERS = (2, 4, 8)
 KS = (3, 5, 7)
+NGRAM = 2          # max_matching_ngram_size of the lookup cells (GPT.generate's default)
 ROUNDS = 40
 STEPS = 200
 MAX_NEW = 400
@@ -283,6 +293,133 @@ def render_sample(res):
     return "\n".join(lines) + "\n"
 
 
+def measure_lookup(args):
+    """the lookup round, greedy and sampled, natural and without any match, against the plain steps: one process, interleaved"""
+    import torch
+    from genvc_amd import synth
+    from genvc_amd.engine import AssistedState, sample_params
+    assert torch.cuda.is_available(), "this measurement needs the GPU"
+    target, _ = build(30, 1)
+    d = target.model_dim
+    cond = synth.uniform(300, "cond_latents", (1, 32, d), 1.0).cuda()
+    codes = synth.integers(300, "content_codes", (1, 13), 256).cuda()
+    fake = target.compute_embeddings(cond, codes)
+    n0 = int(fake.shape[1])
+    slots = torch.zeros(1, device="cuda", dtype=torch.int32)
+    greedy = sample_params(dict(repetition_penalty=1.0, temperature=1.0, top_p=1.0, top_k=1), 1026, 1025)
+    sampled = sample_params(SAMPLING, 1026, 1025, 17)
+    teng = target.engine
+
+    def rounds(k, sample, match):
+        teng.prefill(slots, target._prefix, want_outputs=False)
+        st = AssistedState(fake, k, MAX_NEW, 1025, 1026, d)
+        if not match:
+            st.n0 = int(st.ids.shape[1])          # the lookup's `from` behind the ids row: an empty history, draft_len 0 in every round
+        reach = 1 + ROUNDS * (k + 1) + k
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        teng.generate_lookup(slots, st, sampled if sample else greedy, ROUNDS, n0 + reach, NGRAM, k=k, sampling=sample)
+        e1.record()
+        torch.cuda.synchronize()
+        teng.health()
+        s = st.stats()
+        assert int(s["rounds"][0]) == ROUNDS and int(st.emitted[0]) == 1 + ROUNDS + int(s["accepted"][0])
+        assert match or (int(s["drafted"][0]) == 0 and int(st.emitted[0]) == 1 + ROUNDS)
+        return e0.elapsed_time(e1) * 1000.0 / ROUNDS, int(s["accepted"][0]), int(s["drafted"][0]), int(st.emitted[0])
+
+    def plain(params):
+        teng.prefill(slots, target._prefix, want_outputs=False)
+        ids = torch.ones(1, n0 + STEPS + 8, device="cuda", dtype=torch.int32)
+        ids[:, n0 - 1] = 1024
+        ids_len = torch.full((1,), n0, device="cuda", dtype=torch.int32)
+        fin = torch.zeros(1, device="cuda", dtype=torch.int32)
+        toks = torch.zeros(1, STEPS, device="cuda", dtype=torch.int32)
+        lats = torch.zeros(1, STEPS, d, device="cuda")
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        teng.generate(slots, ids, ids_len, fin, params, 0, STEPS, toks, lats, max_keys=n0 + STEPS)
+        e1.record()
+        torch.cuda.synchronize()
+        teng.health()
+        return e0.elapsed_time(e1) * 1000.0 / STEPS
+
+    cells = {(k, sample, match): [] for k in KS for sample in (False, True) for match in (True, False)}
+    for c in cells:          # untimed: every shape once
+        rounds(*c)
+    plain(greedy)
+    plain(sampled)
+    gsteps, ssteps, seen = [], [], {}
+    for _ in range(args.reps):
+        gsteps.append(plain(greedy))
+        ssteps.append(plain(sampled))
+        for c, xs in cells.items():
+            us, acc, dr, em = rounds(*c)
+            xs.append(us)
+            seen[c] = (acc, dr, em)
+    g_step, s_step = med(gsteps), med(ssteps)
+    res = dict(device=torch.cuda.get_device_name(0), n0=n0, rounds_per_call=ROUNDS, steps_per_plain_call=STEPS, reps=args.reps,
+               max_matching_ngram_size=NGRAM, sampling=SAMPLING, plain_greedy_us_per_step=g_step, plain_greedy_runs=gsteps,
+               plain_greedy_spread=max(abs(x - g_step) / g_step for x in gsteps), plain_sampled_us_per_step=s_step,
+               plain_sampled_runs=ssteps, plain_sampled_spread=max(abs(x - s_step) / s_step for x in ssteps), cells=[])
+    for (k, sample, match), xs in cells.items():
+        t, step = med(xs), s_step if sample else g_step
+        res["cells"].append(dict(k=k, sampled=sample, lookups_match=match, us_per_round=t, spread=max(abs(x - t) / t for x in xs), runs=xs,
+                                 plain_us_per_step=step, tokens_per_round_to_break_even=t / step,
+                                 accepted_in_last_timed_call=seen[(k, sample, match)][0],
+                                 drafted_in_last_timed_call=seen[(k, sample, match)][1],
+                                 emitted_in_last_timed_call=seen[(k, sample, match)][2]))
+    return res
+
+
+def render_lookup(res):
+    """the section on prompt-lookup decoding (every figure in it is computed from `res`)"""
+    g, s = res["plain_greedy_us_per_step"], res["plain_sampled_us_per_step"]
+    sm = res["sampling"]
+    lines = ["", "## Prompt lookup: the cost of a round without a draft model", "",
+             f"`scripts/assisted_bench.py --lookup` on one MI355X ({res['device']}): the same target and prompt, no assistant; "
+             f"max_matching_ngram_size = {res['max_matching_ngram_size']}; sampled cells at top_k = {sm['top_k']}, top_p = {sm['top_p']}, "
+             f"temperature = {sm['temperature']}; {res['rounds_per_call']} rounds per timed call, {res['reps']} timed calls per cell (median; "
+             "spread as above), all cells and the plain loops interleaved in one process.  Timed with device events around one engine "
+             "call that ends in a synchronise, after an untimed call of every shape.", "",
+             f"Plain one-stream steps of the same target, same run: greedy **{g:.1f} us** per token (spread "
+             f"{res['plain_greedy_spread']:.2%}), sampled **{s:.1f} us** (spread {res['plain_sampled_spread']:.2%}), over "
+             f"{res['steps_per_plain_call']} steps each.", "",
+             "A lookup round = one lookup launch + one (k + 1)-row verification pass + accept (sampled: put-drafts, warp and accept "
+             "launches) + one rollback, launched directly (no graph).  \"no match\" rows: the same call with the lookup's `from` moved "
+             "behind the ids row, so every round has draft_len = 0 and emits exactly one token (asserted) -- the verification pass "
+             "still runs all k + 1 rows.  Tokens / round to break even = (us / round) / (plain us / token of the same mode).", "",
+             "| mode | k | lookups | us / round | spread | plain us / token | round - plain step | tokens / round to break even | drafted | "
+             "accepted | tokens emitted |", "|---|---|---|---|---|---|---|---|---|---|---|"]
+    for c in res["cells"]:
+        t, p = c["us_per_round"], c["plain_us_per_step"]
+        lines.append(f"| {'sampled' if c['sampled'] else 'greedy'} | {c['k']} | {'as they fall' if c['lookups_match'] else 'no match'} | "
+                     f"{t:.0f} | {c['spread']:.2%} | {p:.1f} | {t - p:+.0f} ({(t - p) / p:+.1%}) | {t / p:.2f} | "
+                     f"{c['drafted_in_last_timed_call']} | {c['accepted_in_last_timed_call']} | {c['emitted_in_last_timed_call']} |")
+    nm = [c for c in res["cells"] if not c["lookups_match"]]
+    worse = [c for c in nm if c["us_per_round"] > c["plain_us_per_step"]]
+    lines += ["", ("A round without any match costs MORE than a plain step in " + ("every" if len(worse) == len(nm) else f"{len(worse)} of "
+               f"{len(nm)}") + " measured cells: " if worse else "A round without any match costs no more than a plain step: ") +
+              "; ".join(f"{'sampled' if c['sampled'] else 'greedy'} k = {c['k']}: {c['us_per_round'] - c['plain_us_per_step']:+.0f} us "
+                        f"({(c['us_per_round'] - c['plain_us_per_step']) / c['plain_us_per_step']:+.1%})" for c in nm) +
+              ".  That is what a stream that never repeats itself pays per token for the mode; a stream gains as soon as its rounds emit "
+              "more tokens on average than the break-even column says.", "",
+              "The drafted / accepted / emitted columns of the \"as they fall\" rows are what this SYNTHETIC model did in the last timed "
+              f"call ({res['rounds_per_call']} rounds): they show the mode at work and say nothing about a trained checkpoint, whose code "
+              "streams repeat where speech pauses or sustains, not where random weights happen to loop.  No threshold was set for these "
+              "figures in advance."]
+    return "\n".join(lines) + "\n"
+
+
+LOOKUP_PENDING = ("\n## Prompt lookup: the cost of a round without a draft model\n\nNot measured yet: `scripts/assisted_bench.py --lookup` has not "
+                  "run on a GPU, so no figure is given here.  It times the lookup round (one lookup launch, the (k + 1)-row verification pass, "
+                  "accept, one rollback; max_matching_ngram_size = 2) at k = 3 / 5 / 7, greedy and sampled, as the call runs on the synthetic "
+                  "model and with every lookup forced to find no match, beside the plain greedy and sampled steps in the same process; it "
+                  "writes `profiles/assisted_lookup.json` and replaces this section with the table, the tokens per round that break even, "
+                  "the drafted and accepted counts on the synthetic model, and by how much a round without any match exceeds a plain "
+                  "step.\n")
+
 RATES = (0.5, 0.6, 0.7, 0.8, 0.9)
 
 
@@ -348,12 +485,19 @@ def main():
     ap.add_argument("--sample", action="store_true", help="measure the round of speculative sampling (into --sample_json); the greedy "
                                                           "report is rendered from --json as it stands")
     ap.add_argument("--sample_json", default=os.path.join(ROOT, "profiles", "assisted_sampling.json"))
+    ap.add_argument("--lookup", action="store_true", help="measure the round of prompt-lookup decoding (into --lookup_json); the other "
+                                                          "reports are rendered from their json files as they stand")
+    ap.add_argument("--lookup_json", default=os.path.join(ROOT, "profiles", "assisted_lookup.json"))
     args = ap.parse_args()
+    if args.lookup:
+        lres = measure_lookup(args)
+        with open(args.lookup_json, "w") as f:
+            json.dump(lres, f, indent=1)
     if args.sample:
         sres = measure_sample(args)
         with open(args.sample_json, "w") as f:
             json.dump(sres, f, indent=1)
-    if args.render or args.sample:
+    if args.render or args.sample or args.lookup:
         with open(args.json) as f:
             res = json.load(f)
     else:
@@ -364,6 +508,11 @@ def main():
     if os.path.exists(args.sample_json):
         with open(args.sample_json) as f:
             text += render_sample(json.load(f))
+    if os.path.exists(args.lookup_json):
+        with open(args.lookup_json) as f:
+            text += render_lookup(json.load(f))
+    else:
+        text += LOOKUP_PENDING
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
         f.write(text)
