@@ -199,6 +199,7 @@ _SIGNATURES = {
                                           C.c_int32, _P]),
     "gvc_gpt_decode_variant": (C.c_int, [_P]),
     "gvc_gpt_rows_step_launches": (C.c_longlong, [_P]),
+    "gvc_gpt_bf16_gemm_launches": (C.c_longlong, [_P]),
     "gvc_gpt_one_stream_steps": (C.c_longlong, [_P]),
     "gvc_gpt_health": (C.c_int, [_P]),
     "gvc_gpt_warmup": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32]),
@@ -206,6 +207,7 @@ _SIGNATURES = {
     "gvc_gpt_lazy_inits": (C.c_longlong, [_P]),
     "gvc_gpt_rearm": (C.c_int, [_P]),
     "gvc_gpt_time_kernel": (C.c_int, [_P, C.c_int32, _P, C.c_int32, _P, C.c_int32, c_f32p, c_i32p, _P]),
+    "gvc_fb16_index": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     "gvc_gemm_probe": (C.c_int, [C.c_int32, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_f32p, _P]),
     "gvc_perceiver_create": (C.c_int, [C.POINTER(PerceiverDims), C.POINTER(_P)]),
     "gvc_perceiver_destroy": (C.c_int, [_P]),

@@ -1,5 +1,6 @@
 // fp32 MFMA GEMM (see gemm.h)
 #include "gemm.h"
+#include "gemm_b16.h"
 #include <algorithm>
 
 namespace gvc {
@@ -520,6 +521,56 @@ int launch_ln_sum_rows(const float* x_in, float* x_out, float* a, const float* p
     return GVC_OK;
 }
 
+// the bf16 matrix-core mode's row kernel (gemm_b16.h): the same row completion, then the row ROUNDED to bf16 in the FB16 layout and
+// the (mean, rstd) of the rounded row -- the LayerNorm itself is folded into the GEMM that consumes the row
+template <int NV>
+__global__ __launch_bounds__(64) void k_ln_sum_rows_b16_t(const float* x_in, float* x_out, unsigned short* a_b16, float* stats, const float* part,
+                                                           int SK, const float* bias, int rows) {
+    constexpr int d = 256 * NV;
+    constexpr float inv_d = 1.0f / (float)d;
+    const int lane = threadIdx.x, row = blockIdx.x;
+    float4 v[NV];
+    row_sum<NV>(x_in + (size_t)row * d, part, (size_t)row * d, (size_t)rows * d, SK, bias, lane, v);
+#pragma unroll
+    for (int i = 0; i < NV; ++i) *reinterpret_cast<float4*>(x_out + (size_t)row * d + (i * 64 + lane) * 4) = v[i];
+    if (!a_b16) return;
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        ushort4 o;
+        o.x = f32_to_bf16(v[i].x); o.y = f32_to_bf16(v[i].y); o.z = f32_to_bf16(v[i].z); o.w = f32_to_bf16(v[i].w);
+        *reinterpret_cast<ushort4*>(a_b16 + fb16_index(row, (i * 64 + lane) * 4, d)) = o;
+        v[i] = make_float4(__uint_as_float((unsigned)o.x << 16), __uint_as_float((unsigned)o.y << 16), __uint_as_float((unsigned)o.z << 16),
+                           __uint_as_float((unsigned)o.w << 16));
+        s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
+    }
+    const float mean = wave_sum(s) * inv_d;
+    float q = 0.f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const float a0 = v[i].x - mean, a1 = v[i].y - mean, a2 = v[i].z - mean, a3 = v[i].w - mean;
+        q += (a0 * a0 + a1 * a1) + (a2 * a2 + a3 * a3);
+    }
+    const float rstd = 1.0f / sqrtf(wave_sum(q) * inv_d + 1e-5f);
+    if (lane == 0) *reinterpret_cast<float2*>(stats + 2 * (size_t)row) = make_float2(mean, rstd);
+}
+
+int launch_ln_sum_rows_b16(const float* x_in, float* x_out, unsigned short* a_b16, float* stats, const float* part, int SK, const float* bias,
+                           int rows, int d, hipStream_t s) {
+    GVC_REQUIRE(d % 256 == 0 && d >= 256 && d <= 2048 && SK >= 0 && SK <= 8 && (!a_b16 || stats), GVC_ERR_UNSUPPORTED,
+                "ln_sum_rows_b16: d=%d SK=%d unsupported", d, SK);
+#define GVC_LN_SUM_B16(nv)                                                                                                              \
+    case nv:                                                                                                                            \
+        hipLaunchKernelGGL(k_ln_sum_rows_b16_t<nv>, dim3(rows), dim3(64), 0, s, x_in, x_out, a_b16, stats, part, SK, bias, rows);        \
+        break;
+    switch (d / 256) {
+        GVC_LN_SUM_B16(1) GVC_LN_SUM_B16(2) GVC_LN_SUM_B16(3) GVC_LN_SUM_B16(4) GVC_LN_SUM_B16(5) GVC_LN_SUM_B16(6) GVC_LN_SUM_B16(7) GVC_LN_SUM_B16(8)
+    }
+#undef GVC_LN_SUM_B16
+    GVC_LAUNCH_CHECK();
+    return GVC_OK;
+}
+
 // ---- skinny GEMM for <= 16 rows with the row completion + LayerNorm in its prologue (K = d) ----
 // A = LayerNorm(x_in + bias + sum part) is built by the workgroup itself (wave w: rows w and w + 8) and staged in LDS in
 // the FM16 fragment order; workgroup 0 also writes the completed rows to x_out (a buffer other than x_in: the other
@@ -898,11 +949,12 @@ void gemm_init_attributes() {
 extern "C" int gvc_gemm_probe(int32_t variant, const float* A, const float* W, const float* bias, float* C, int32_t M, int32_t N,
                               int32_t K, int32_t sk_max, int32_t iters, float* avg_us, gvc_stream sv) {
     using namespace gvc;
-    GVC_REQUIRE(A && W && C && M >= 1 && N >= 16 && K >= 16 && K % 16 == 0 && N % 16 == 0 && variant >= 0 && variant <= 2, GVC_ERR_ARG,
+    GVC_REQUIRE(A && W && C && M >= 1 && N >= 16 && K >= 16 && K % 16 == 0 && N % 16 == 0 && variant >= 0 && variant <= 3, GVC_ERR_ARG,
                 "gemm_probe: bad argument");
+    GVC_REQUIRE(variant != 3 || (K % 32 == 0 && N % 64 == 0), GVC_ERR_ARG, "gemm_probe: the bf16 strip kernel needs K %% 32 == 0 and N %% 64 == 0 (N=%d K=%d)", N, K);
     hipStream_t s = (hipStream_t)sv;
     static bool attrs = false;
-    if (!attrs) { gemm_init_attributes(); attrs = true; }
+    if (!attrs) { gemm_init_attributes(); gemm_b16_init_attributes(); attrs = true; }
     const int Mp = (M + 15) & ~15;
     float *Af = nullptr, *Wf = nullptr, *work = nullptr;
     const long long work_cap = (long long)8 * M * N;
@@ -916,6 +968,13 @@ extern "C" int gvc_gemm_probe(int32_t variant, const float* A, const float* W, c
     G.C = C; G.ldc = N; G.M = M; G.N = N; G.K = K; G.work = work; G.e.bias = bias;
     if (variant == 0) {
         G.A = A; G.lda = K; G.Wt = W; G.ldw = K;
+    } else if (variant == 3) {      // the operands rounded to bf16 (nearest even) in the FB16 layout; A's rows padded to 16 with zeros
+        GVC_CHECK_HIP(hipMalloc((void**)&Af, (size_t)Mp * K * sizeof(unsigned short)));
+        GVC_CHECK_HIP(hipMalloc((void**)&Wf, (size_t)N * K * sizeof(unsigned short)));
+        int rc3 = launch_to_fb16(A, reinterpret_cast<unsigned short*>(Af), M, K, nullptr, s);
+        if (rc3 == GVC_OK) rc3 = launch_to_fb16(W, reinterpret_cast<unsigned short*>(Wf), N, K, nullptr, s);
+        if (rc3 != GVC_OK) return rc3;
+        G.A = Af; G.lda = K; G.Wt = Wf; G.ldw = K;
     } else {
         GVC_CHECK_HIP(hipMalloc((void**)&Af, (size_t)Mp * K * sizeof(float)));
         GVC_CHECK_HIP(hipMalloc((void**)&Wf, (size_t)N * K * sizeof(float)));
@@ -927,6 +986,7 @@ extern "C" int gvc_gemm_probe(int32_t variant, const float* A, const float* W, c
     auto once = [&]() -> int {
         if (variant == 0) return launch_gemm_cap(G, 1, work_cap, s);
         if (variant == 1) return launch_gemm_strip(G, sk_max, work_cap, 0, nullptr, s);
+        if (variant == 3) return launch_gemm_strip_b16(G, B16Epi{}, sk_max, work_cap, 0, nullptr, s);
         return launch_gemm_skinny(G, 1, work_cap, s);
     };
     int rc = once();

@@ -14,6 +14,7 @@
 #include "persist_kernel.h"
 #include "persist_rows.h"
 #include "persist_rows_b16.h"
+#include "gemm_b16.h"
 #include "beam.h"
 #include "cfg.h"
 #include "contrastive.h"
@@ -340,6 +341,14 @@ struct gvc_gpt {
     float* kv = nullptr;              // [L][2][slots][H][max_seq][hd], fp32 or (kv_bf16) bf16 elements
     int kv_bf16 = 0;
     int act_bf16 = 0;                 // weight_dtype 3: the one-launch rows step rounds the activations that cross its hand-offs (persist_rows_b16.h)
+    // weight_dtype 4: every multi-row pass that is not a one-launch step multiplies on bf16 matrix cores (gemm_b16.h, run_rows_b16)
+    int mfma_b16 = 0;
+    unsigned short* wb16 = nullptr;   // per layer, FB16: bf16(c_attn g1) [3d][d] | c_proj [d][d] | bf16(c_fc g2) [4d][d] | mlp c_proj [d][4d]
+    float* b16_fold = nullptr;        // per layer: S[3d] | C[3d] of LN1 -> c_attn and S[4d] | C[4d] of LN2 -> c_fc (k_rows_ln_fold_b16)
+    float* b16_stats = nullptr;       // [rows padded to 16][2] (mean, rstd) of the bf16 rows the folded GEMM consumes
+    std::vector<char> b16_dirty;      // per layer: a matrix or LayerNorm parameter was (re)bound -> repack before the next call (b16_prepare)
+    int b16_any_dirty = 0;
+    long long b16_launches = 0;       // bf16 strip GEMMs issued (gvc_gpt_bf16_gemm_launches; graph replays count once per capture)
     size_t kv_layer_stride = 0;       // floats per (layer, k|v)
     float *x = nullptr, *a = nullptr, *q = nullptr, *h = nullptr, *part = nullptr, *work = nullptr;
     long long work_cap = 0;
@@ -467,9 +476,27 @@ extern "C" int gvc_gpt_create(const gvc_gpt_dims* dims, gvc_gpt** out) {
     if (getenv("GVC_ROWS_DECODE_MIN")) c->rows_decode_min = atoi(getenv("GVC_ROWS_DECODE_MIN"));
     c->bf16 = D.weight_dtype >= 1;
     c->kv_bf16 = D.weight_dtype >= 2;
-    c->act_bf16 = D.weight_dtype == 3;
-    GVC_REQUIRE(D.weight_dtype >= 0 && D.weight_dtype <= 3, GVC_ERR_ARG,
-                "weight_dtype must be 0 (fp32), 1 (bf16 weights), 2 (bf16 weights + KV cache) or 3 (2 + bf16 activations on the one-launch rows step)");
+    c->act_bf16 = D.weight_dtype >= 3;
+    c->mfma_b16 = D.weight_dtype == 4;
+    GVC_REQUIRE(D.weight_dtype >= 0 && D.weight_dtype <= 4, GVC_ERR_ARG,
+                "weight_dtype must be 0 (fp32), 1 (bf16 weights), 2 (bf16 weights + KV cache), 3 (2 + bf16 activations on the one-launch rows step) "
+                "or 4 (3 + bf16 matrix cores on every other multi-row pass)");
+    if (c->mfma_b16) {
+        if (!(d % 256 == 0 && d <= 2048 && hd % 4 == 0)) {
+            gvc_gpt_destroy(c);
+            GVC_REQUIRE(false, GVC_ERR_UNSUPPORTED, "weight_dtype 4: the bf16 matrix-core kernels need d_model %% 256 == 0, d_model <= 2048 (got %d)", (int)d);
+        }
+        gemm_b16_init_attributes();
+        if (hipMalloc((void**)&c->wb16, (size_t)L * 12 * d * d * sizeof(unsigned short)) != hipSuccess ||
+            hipMalloc((void**)&c->b16_fold, (size_t)L * 14 * d * sizeof(float)) != hipSuccess ||
+            hipMalloc((void**)&c->b16_stats, (((size_t)D.max_rows + 15) & ~(size_t)15) * 2 * sizeof(float)) != hipSuccess) {
+            (void)hipGetLastError();
+            gvc_gpt_destroy(c);
+            GVC_REQUIRE(false, GVC_ERR_HIP, "weight_dtype 4: no memory for the bf16 fragment-major weight copies (%.0f MB)", L * 12.0 * d * d * 2 / 1e6);
+        }
+        c->b16_dirty.assign(L, 1);
+        c->b16_any_dirty = 1;
+    }
     if (c->bf16) {
         GVC_CHECK_HIP(hipMalloc((void**)&c->wh, (L * 12 * d * d + V * d + 64) * sizeof(unsigned short)));
         unsigned short* hq = c->wh;
@@ -492,6 +519,9 @@ extern "C" int gvc_gpt_create(const gvc_gpt_dims* dims, gvc_gpt** out) {
     c->kv_layer_stride = (size_t)D.max_slots * D.n_head * D.max_seq * hd;
     const size_t rows = ((size_t)D.max_rows + 15) & ~(size_t)15;       // fragment-major activations come in 16-row tiles
     c->work_cap = 8ll << 20;
+    // weight_dtype 4: the N = d projections of EVERY multi-row pass leave K-split partials (there is no tiled-GEMM path behind the bf16
+    // one), so the two halves of the scratch each hold max_rows x d floats whatever max_rows is
+    if (c->mfma_b16 && (long long)2 * rows * d > c->work_cap) c->work_cap = (long long)2 * rows * d;
     if ((rc = alloc_f(&c->kv, (c->kv_bf16 ? 1 : 2) * L * c->kv_layer_stride)) || (rc = alloc_f(&c->x, rows * d)) ||
         (rc = alloc_f(&c->a, rows * d)) || (rc = alloc_f(&c->q, rows * d)) || (rc = alloc_f(&c->h, rows * 4 * d)) ||
         (rc = alloc_f(&c->part, (size_t)D.max_slots * D.n_head * kAttnChunks * (hd + 4))) ||
@@ -553,7 +583,7 @@ extern "C" int gvc_gpt_destroy(gvc_gpt* c) {
     if (c->xalt) hipFree(c->xalt);
     if (c->seam_err_host) hipHostFree(c->seam_err_host);
     for (void* p : {(void*)c->p_layers, (void*)c->p_gran, (void*)c->p_epoch, (void*)c->p_dbg, (void*)c->r_layers, (void*)c->r_wpack,
-                    (void*)c->r_bufs, (void*)c->r_dbg, (void*)c->r_lnfold})
+                    (void*)c->r_bufs, (void*)c->r_dbg, (void*)c->r_lnfold, (void*)c->wb16, (void*)c->b16_fold, (void*)c->b16_stats})
         if (p) hipFree(p);
     for (void* p : {(void*)c->wbase, (void*)c->wfm, (void*)c->wh, (void*)c->kv, (void*)c->x, (void*)c->a, (void*)c->q, (void*)c->h,
                     (void*)c->part, (void*)c->work, (void*)c->logits, (void*)c->latent, (void*)c->slot_logits, (void*)c->slot_latent, (void*)c->state, (void*)c->x2, (void*)c->part2,
@@ -644,6 +674,7 @@ extern "C" int gvc_gpt_bind_weight(gvc_gpt* c, const char* name, const float* sr
 // a block matrix of layer li was (re)bound: the one-launch rows step's packed copy of that layer must be rebuilt before its next use
 static void mark_rows_pack_dirty(gvc_gpt* c, int li) {
     if (c->r_ready == 1 && li < (int)c->r_dirty.size()) c->r_dirty[li] = 1;
+    if (c->mfma_b16 && li < (int)c->b16_dirty.size()) { c->b16_dirty[li] = 1; c->b16_any_dirty = 1; }     // (the bf16 matrix-core copies too)
 }
 
 extern "C" int gvc_gpt_missing_weights(gvc_gpt* c) {
@@ -1269,6 +1300,7 @@ static int launch_head(gvc_gpt* c, const int32_t* slots, int B, int row0, const 
 // appended at each slot's cached length.
 static bool rows_decode_ok(const gvc_gpt* c, int B) {
     if (c->r_ready >= 0 && rows_persist_ok(c, B, c->st.seq_len)) return true;       // served by the one-launch rows step (from 2 streams)
+    if (c->mfma_b16 && B >= 2 && B <= c->dm.max_rows) return true;                   // weight_dtype 4: every multi-row pass, the same rounding points
     const bool wide = c->dm.d_model > 1024;       // no GEMV path above 1024: every batch decodes as rows
     return (wide || (c->rows_decode_min > 0 && B >= c->rows_decode_min)) && B <= 128 && c->skinny_prefill && c->wfm &&
            c->dm.d_model % 256 == 0 && (long long)4 * B * c->dm.d_model <= c->work_cap / 2 && B <= c->dm.max_rows;
@@ -1335,6 +1367,38 @@ static void settle_pending(gvc_gpt* c) {
     (void)hipGetLastError();
 }
 
+// weight_dtype 4: the FB16 bf16 copies of the four matrices of every layer bound since the last call, with the LayerNorm gains folded
+// into c_attn / c_fc, and the fold constants.  Outside stream capture (every entry point passes here before it enqueues anything):
+// waits for the bind stream, packs, waits again.  After a bind + gvc_gpt_warmup no data-path call packs, allocates or synchronises.
+static unsigned short* b16_w(const gvc_gpt* c, int l, int which) {
+    const size_t d = c->dm.d_model, off[4] = {0, 3 * d * d, 4 * d * d, 8 * d * d};
+    return c->wb16 + (size_t)l * 12 * d * d + off[which];
+}
+static int b16_prepare(gvc_gpt* c) {
+    if (!c->mfma_b16 || !c->b16_any_dirty) return GVC_OK;
+    note_lazy(c);
+    const int d = c->dm.d_model;
+    GVC_CHECK_HIP(hipDeviceSynchronize());
+    int rc;
+    for (int l = 0; l < c->dm.n_layer; ++l) {
+        if (!c->b16_dirty[l]) continue;
+        const GptLayer& ly = c->layers[l];
+        float* f = c->b16_fold + (size_t)l * 14 * d;
+        if ((rc = launch_to_fb16(ly.qkv_w, b16_w(c, l, 0), 3 * d, d, ly.ln1_w, 0)) || (rc = launch_to_fb16(ly.proj_w, b16_w(c, l, 1), d, d, nullptr, 0)) ||
+            (rc = launch_to_fb16(ly.fc_w, b16_w(c, l, 2), 4 * d, d, ly.ln2_w, 0)) || (rc = launch_to_fb16(ly.p2_w, b16_w(c, l, 3), d, 4 * d, nullptr, 0)))
+            return rc;
+        hipLaunchKernelGGL(k_rows_ln_fold_b16, dim3(3 * d / 4), dim3(256), 0, 0, f, f + 3 * d, (const float*)ly.qkv_w, (const float*)ly.ln1_w,
+                           (const float*)ly.ln1_b, (const float*)ly.qkv_b, 3 * d, d);
+        hipLaunchKernelGGL(k_rows_ln_fold_b16, dim3(4 * d / 4), dim3(256), 0, 0, f + 6 * d, f + 10 * d, (const float*)ly.fc_w, (const float*)ly.ln2_w,
+                           (const float*)ly.ln2_b, (const float*)ly.fc_b, 4 * d, d);
+        GVC_LAUNCH_CHECK();
+    }
+    GVC_CHECK_HIP(hipDeviceSynchronize());
+    std::fill(c->b16_dirty.begin(), c->b16_dirty.end(), 0);
+    c->b16_any_dirty = 0;
+    return GVC_OK;
+}
+
 static int check_ready(gvc_gpt* c) {
     GVC_REQUIRE(c, GVC_ERR_ARG, "null context");
     const int dev_err = c->seam_err_host ? *(volatile int*)c->seam_err_host : 0;
@@ -1360,7 +1424,7 @@ static int check_ready(gvc_gpt* c) {
     }
     GVC_REQUIRE(gvc_gpt_missing_weights(c) == 0, GVC_ERR_STATE, "%d GPT weight tensors are not bound",
                 gvc_gpt_missing_weights(c));
-    return GVC_OK;
+    return b16_prepare(c);
 }
 
 // One decode step over the B rows of a slot table, eager or under capture: the one-stream one-launch step, else the rows path, else
@@ -1441,12 +1505,75 @@ extern "C" int gvc_gpt_prefix_embeddings(gvc_gpt* c, const float* cond, int32_t 
 // rows <= 128 (a streaming prefill): skinny MFMA GEMMs; the N = d projections are K-split over 4 workgroup
 // rows and their raw partial sums are folded into the NEXT LayerNorm launch (k_ln_sum_rows), so a layer is
 // 7 launches.  Larger row counts (batched offline prefill, latent re-pass) use the tiled GEMM.
+// weight_dtype 4: the block stack of run_rows with the four projections of every layer on bf16 matrix cores and the rounding points of
+// the one-launch bf16 rows step (oracle: gpt_blocks(act_bf16, kv_bf16)): the residual stream stays fp32 in c->x; the row kernel
+// completes it and publishes x~ = bf16(x) (FB16, in c->a) with the (mean, rstd) of x~; c_attn / c_fc consume x~ against bf16(W g) and
+// apply the folded LayerNorm in their epilogue; the attention output (fp32 rows, in c->h) is rounded into c->a by a convert launch;
+// c_fc stores bf16(gelu_new(.)) in FB16 (in c->h); the N = d projections leave raw K-split partials for the next row kernel.
+// 8 launches per layer (the fp32 path: 7).  The attention runs with ONE key chunk per (row, head): run_rows' 2 / 4-way key split of a batched decode
+// step over long contexts merges its partials inside the fp32 skinny c_proj GEMM, which this path does not use.
+static int run_rows_b16(gvc_gpt* c, const int32_t* slots, int B, int T, hipStream_t s, const int32_t* base_len) {
+    const int d = c->dm.d_model, rows = B * T, L = c->dm.n_layer;
+    GVC_REQUIRE((long long)rows * d <= c->work_cap / 2, GVC_ERR_STATE, "weight_dtype 4: %d rows exceed the split-K scratch", rows);   // (sized for max_rows at create)
+    int rc;
+    float* part_proj = c->work;
+    float* part_p2 = c->work + c->work_cap / 2;
+    unsigned short* a16 = reinterpret_cast<unsigned short*>(c->a);
+    unsigned short* h16 = reinterpret_cast<unsigned short*>(c->h);
+    int sk_p2 = 0, sk_proj = 0;
+    for (int l = 0; l < L; ++l) {
+        const GptLayer& ly = c->layers[l];
+        const float* f = c->b16_fold + (size_t)l * 14 * d;
+        if ((rc = launch_ln_sum_rows_b16(c->x, c->x, a16, c->b16_stats, l > 0 ? part_p2 : nullptr, sk_p2, l > 0 ? c->layers[l - 1].p2_b : nullptr,
+                                         rows, d, s)))
+            return rc;
+        GemmArgs G;
+        B16Epi F;
+        memset(&G, 0, sizeof(G));
+        memset(&F, 0, sizeof(F));
+        G.A = c->a; G.lda = d; G.Wt = reinterpret_cast<const float*>(b16_w(c, l, 0)); G.ldw = d; G.C = c->q; G.ldc = d; G.M = rows; G.N = 3 * d; G.K = d;
+        G.e.qkv = 1; G.e.d = d; G.e.n_head = c->dm.n_head; G.e.head_dim = c->hd; G.e.max_seq = c->dm.max_seq; G.e.T = T; G.e.slots = slots;
+        G.e.base_len = base_len; G.e.kcache = kv_layer(c, l, 0); G.e.vcache = kv_layer(c, l, 1); G.e.kv_bf16 = c->kv_bf16;
+        F.stats = c->b16_stats; F.S = f; F.Cc = f + 3 * d;
+        if ((rc = launch_gemm_strip_b16(G, F, 1, c->work_cap, 0, nullptr, s))) return rc;
+
+        AttnArgs At = gpt_attn_args(c, l, slots);
+        At.q = c->q; At.T = T; At.base_len = base_len;
+        At.out = c->h; At.out_stride = d; At.out_fm16 = 0;
+        if ((rc = launch_attention(c, At, 1, rows, true, s, base_len && T == 1))) return rc;
+        if ((rc = launch_to_fb16(c->h, a16, rows, d, nullptr, s))) return rc;
+
+        memset(&G, 0, sizeof(G));
+        memset(&F, 0, sizeof(F));
+        G.A = c->a; G.lda = d; G.Wt = reinterpret_cast<const float*>(b16_w(c, l, 1)); G.ldw = d; G.C = c->x; G.ldc = d; G.M = rows; G.N = d; G.K = d;
+        G.work = part_proj;
+        if ((rc = launch_gemm_strip_b16(G, F, 8, c->work_cap / 2, 1, &sk_proj, s))) return rc;
+        if ((rc = launch_ln_sum_rows_b16(c->x, c->x, a16, c->b16_stats, part_proj, sk_proj, ly.proj_b, rows, d, s))) return rc;
+
+        memset(&G, 0, sizeof(G));
+        G.A = c->a; G.lda = d; G.Wt = reinterpret_cast<const float*>(b16_w(c, l, 2)); G.ldw = d; G.C = c->h; G.ldc = 4 * d; G.M = rows; G.N = 4 * d; G.K = d;
+        G.e.act = ACT_GELU_NEW;
+        F.stats = c->b16_stats; F.S = f + 6 * d; F.Cc = f + 10 * d; F.c_b16 = h16;
+        if ((rc = launch_gemm_strip_b16(G, F, 1, c->work_cap, 0, nullptr, s))) return rc;
+
+        memset(&G, 0, sizeof(G));
+        memset(&F, 0, sizeof(F));
+        G.A = c->h; G.lda = 4 * d; G.Wt = reinterpret_cast<const float*>(b16_w(c, l, 3)); G.ldw = 4 * d; G.C = c->x; G.ldc = d; G.M = rows; G.N = d; G.K = 4 * d;
+        G.work = part_p2;
+        if ((rc = launch_gemm_strip_b16(G, F, 8, c->work_cap / 2, 1, &sk_p2, s))) return rc;
+        c->b16_launches += 4;
+    }
+    // fold the last layer's mlp partials into the residual stream (what the head reads)
+    return launch_ln_sum_rows_b16(c->x, c->x, nullptr, nullptr, part_p2, sk_p2, c->layers[L - 1].p2_b, rows, d, s);
+}
+
 static int run_rows(gvc_gpt* c, const int32_t* slots, int B, int T, hipStream_t s, const int32_t* base_len, int key_chunks) {
     const int d = c->dm.d_model, rows = B * T;
     int rc;
     // 2..16 rows that continue cached sequences (a batched decode step, the uncached rows of a streaming chunk): ONE launch
     if (c->r_ready == 1 && rows_persist_ok(c, rows, base_len))
         return launch_rows_persist(c, slots, rows, T, base_len, rows_persist_chunks(c, rows, c->rows_keys_hint), s);
+    if (c->mfma_b16 && rows > 1) return run_rows_b16(c, slots, B, T, s, base_len);
     const bool skinny = c->skinny_prefill && c->wfm && rows <= 128 && d % 256 == 0 && (long long)4 * rows * d <= c->work_cap / 2;
     const int SKP = 4;
     float* part_proj = c->work;                                    // [SKP][rows][d]
@@ -1827,8 +1954,12 @@ static int warmup_sweep(int lo, int hi, Plan&& plan, Graph&& graph) {
 // B streams reaching `max_keys` cached positions with this top_k.  Synchronous; call it after the weights are bound, once per shape a
 // deployment uses.  After it, data-path calls of that shape neither allocate nor synchronise the device (gvc_gpt_lazy_inits stays put).
 extern "C" int gvc_gpt_warmup(gvc_gpt* c, int32_t B, int32_t max_keys, int32_t top_k) {
-    int rc = check_ready(c);
-    if (rc) return rc;
+    int rc;
+    if (c && c->mfma_b16 && gvc_gpt_missing_weights(c) == 0) {       // (the pack is warm-up work, not a lazy initialisation)
+        WarmupScope warm(c);
+        if ((rc = b16_prepare(c))) return rc;
+    }
+    if ((rc = check_ready(c))) return rc;
     GVC_REQUIRE(B >= 1 && B <= c->dm.max_slots && max_keys >= 0 && max_keys < c->dm.max_seq, GVC_ERR_ARG, "warmup: bad argument");
     WarmupScope warm(c);
     // the rows step also serves the <= 16 uncached rows of a cached chunk prefill, whatever B
@@ -2646,6 +2777,7 @@ extern "C" int gvc_gpt_time_kernel(gvc_gpt* c, int32_t which, const int32_t* slo
 
 extern "C" int gvc_gpt_decode_variant(gvc_gpt* c) { return c ? c->last_variant : 0; }
 extern "C" long long gvc_gpt_rows_step_launches(gvc_gpt* c) { return c ? c->r_launches : 0; }
+extern "C" long long gvc_gpt_bf16_gemm_launches(gvc_gpt* c) { return c ? c->b16_launches : 0; }
 
 // one-stream one-launch steps that RAN so far (generation loops, flushes, decode_step; launches that left at the run flag are not
 // counted).  Synchronises the device.

@@ -719,6 +719,10 @@ def spec_accept_sample(state, k, appended, logits, latents, drafts, q_scores, pa
     return p_rows
 
 
+# host names of gvc_gpt_dims.weight_dtype (include/genvc_hip.h)
+WEIGHT_DTYPES = {"fp32": 0, "bf16": 1, "bf16_kv": 2, "bf16_act": 3, "bf16_mfma": 4}
+
+
 class GptEngine:
     """KV-cached GPT-2 stack of GenVC (reference layers/gpt.py + layers/gpt_inference.py)."""
 
@@ -730,7 +734,7 @@ class GptEngine:
         max_seq = max_seq or ((dims["max_seq"] + 63) // 64) * 64
         cd = _lib.GptDims(dims["n_layer"], dims["d_model"], dims["n_head"], dims["num_audio_tokens"],
                           dims["max_mel_pos"], dims["max_text_pos"], dims["number_text_tokens"], max_seq,
-                          max_slots, max_rows, {"fp32": 0, "bf16": 1, "bf16_kv": 2, "bf16_act": 3}[weight_dtype])
+                          max_slots, max_rows, WEIGHT_DTYPES[weight_dtype])
         self._h = C.c_void_p()
         self._pending_side = None     # end-of-work event of another stream of this process (watch_stream)
         self.side_joins = 0
@@ -1245,6 +1249,10 @@ class GptEngine:
     def rows_step_launches(self):
         """one-launch rows steps issued so far (include/genvc_hip.h: gvc_gpt_rows_step_launches)"""
         return int(lib().gvc_gpt_rows_step_launches(self._h))
+
+    def bf16_gemm_launches(self):
+        """bf16 matrix-core strip GEMMs issued so far: the multi-row passes of a "bf16_mfma" context (gvc_gpt_bf16_gemm_launches)"""
+        return int(lib().gvc_gpt_bf16_gemm_launches(self._h))
 
     def time_kernel(self, which, slots, tok, n_steps):
         """(mean us per launch, launches) of one kernel class of the decode step, launched back to back"""

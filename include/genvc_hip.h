@@ -94,7 +94,18 @@ typedef struct gvc_gpt_dims {
                              attention output, x' into LN2, the gelu output -- to bf16 where they are published and multiplies on bf16 MFMAs with
                              fp32 accumulation (LayerNorm gain folded into the packed bf16 weights); residual stream, softmax, statistics and q stay
                              fp32.  The other paths of such a context (one stream, full prefills, 17+ streams) compute as mode 2.  Not bit-exact
-                             against any reference by construction: oracle rounding points `dims["act_bf16"]` */
+                             against any reference by construction: oracle rounding points `dims["act_bf16"]`.
+                             4 ("bf16_mfma"): as 3, and every other pass over MORE THAN ONE row -- full prefills, cached chunk prefills, the
+                             latent re-pass, verification rows of assisted decoding, 17+ streams, and 2..16 rows whenever the one-launch rows
+                             step is switched off or has timed out -- runs its four projections per layer on bf16 matrix cores
+                             (v_mfma_f32_16x16x32_bf16, csrc/gemm_b16.hip) with the rounding points of the rows step, so they are the same on
+                             every multi-row path: x~ = bf16(x) into c_attn / c_fc with the LayerNorm statistics taken over x~ in fp32 and the
+                             gain folded into bf16(W g); the attention output and gelu_new(.) rounded to bf16 where they are stored;
+                             residual stream, q, softmax, k / v (bf16 into the cache as in 2), every accumulation and the head stay fp32.  One
+                             row (the one-stream decode step, the fused skinny path) computes as mode 2, as in mode 3.  Costs a second bf16 copy of
+                             the four block matrices in MFMA fragment order: 12 d^2 x 2 bytes per layer (755 MB at d = 1024, L = 30), packed
+                             outside the data path (first call after a bind, or gvc_gpt_warmup).  Needs d_model % 256 == 0, d_model <= 2048.
+                             Oracle: gpt_blocks(act_bf16, kv_bf16), gpt_prefill(act_bf16_prefill) */
 } gvc_gpt_dims;
 
 int gvc_gpt_create(const gvc_gpt_dims* dims, gvc_gpt** out);
@@ -785,6 +796,9 @@ int gvc_gpt_decode_variant(gvc_gpt* ctx);
  * steps, the uncached rows of a streaming chunk's prefill) this context has issued; a step captured into the generation loop's
  * graph counts once.  Tests use it to prove which path served a call. */
 long long gvc_gpt_rows_step_launches(gvc_gpt* ctx);
+/* bf16 matrix-core strip GEMMs issued so far by the multi-row passes of a weight_dtype-4 context (four per layer and pass; a captured
+ * graph counts once per capture); 0 in every other mode. */
+long long gvc_gpt_bf16_gemm_launches(gvc_gpt* ctx);
 /* Diagnostic: how many one-stream one-launch decode steps (csrc/persist_kernel.h) have RUN in this context -- generation loops,
  * gvc_gpt_decode_step, flushes of deferred decodes.  A launch that left at its run flag (the first step of a deferring call with
  * nothing pending, a flush row with nothing pending) is not counted: a prefill followed by 24 generated tokens counts 23, and 24
@@ -837,11 +851,18 @@ int gvc_gpt_time_kernel(gvc_gpt* ctx, int32_t which, const int32_t* slots, int32
 
 /* Measurement / test hook for the fp32 MFMA GEMMs under the prefill (not a reference interface): C[M][N] = A[M][K] W[N][K]^T
  * (+ bias[N], nullable), all row-major device buffers, through one kernel: variant 0 the 64x64x32 tiled kernel, 1 the strip
- * kernel (operands converted to the fragment-major layout first; K split up to sk_max), 2 the skinny kernel (M <= 128).  With
+ * kernel (operands converted to the fragment-major layout first; K split up to sk_max), 2 the skinny kernel (M <= 128), 3 the bf16
+ * matrix-core strip kernel (csrc/gemm_b16.hip: both operands rounded to bf16, nearest even, by the probe; K split up to sk_max; needs
+ * K % 32 == 0 and N % 64 == 0).  With
  * iters > 0 the GEMM is then launched iters more times between two hipEvents and *avg_us is the mean microseconds per GEMM
  * (split-K epilogue included).  Synchronises the stream. */
 int gvc_gemm_probe(int32_t variant, const float* A, const float* W, const float* bias, float* C, int32_t M, int32_t N, int32_t K,
                    int32_t sk_max, int32_t iters, float* avg_us, gvc_stream s);
+
+/* Element index of (row m, column k) of an [M][K] bf16 matrix in the fragment-major layout of the bf16 matrix-core GEMMs
+ * (csrc/gemm_b16.h: fb16_index; M % 16 == 0, K % 32 == 0): each (16 rows x 32 k) block is 64 fragments of 8 consecutive k, fragment
+ * (m % 16) + 16 * ((k % 32) / 8) -- the lane of v_mfma_f32_16x16x32_bf16 that holds them.  Host arithmetic only. */
+int64_t gvc_fb16_index(int32_t m, int32_t k, int32_t K);
 
 /* ------------------------------------------------------------------------------------------
  * Perceiver resampler.  Replaces layers/perceiver_encoder.py:PerceiverResampler.forward (:265-276)

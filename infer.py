@@ -28,7 +28,7 @@ if __name__ == "__main__":
     parser.add_argument("--synthetic", action="store_true", help="deterministic synthetic weights instead of --model_path")
     parser.add_argument("--tiny", action="store_true", help="with --synthetic: the 2-layer test architecture")
     parser.add_argument("--save_tokens", type=str, default=None)
-    parser.add_argument("--weights", type=str, default="fp32", choices=["fp32", "bf16", "bf16_kv", "bf16_act"],
+    parser.add_argument("--weights", type=str, default="fp32", choices=["fp32", "bf16", "bf16_kv", "bf16_act", "bf16_mfma"],
                         help="GPT weight / KV-cache storage on the GPU (fp32 = the reference's numerics)")
     parser.add_argument("--num_beams", type=int, default=1,
                         help="non-streaming only: > 1 decodes with deterministic beam search (do_sample=False) of this width")
