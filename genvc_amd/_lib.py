@@ -125,6 +125,8 @@ _SIGNATURES = {
     "gvc_gpt_kv_fanout": (C.c_int, [_P, _P, _P, C.c_int32, _P]),
     "gvc_gpt_sequence_logprobs": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "gvc_gpt_latents": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
+    "gvc_gpt_forward_rows": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, _P, C.c_int32, _P, C.c_int32, _P, _P, _P]),
+    "gvc_gpt_head_xent": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_float, C.c_int32, _P, _P, _P, _P]),
     "gvc_sample": (C.c_int, [_P, C.c_int32, _P, C.c_int32, _P, _P, C.POINTER(SampleParams), C.c_int32, _P, _P]),
     "gvc_gpt_generate": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, _P, _P, C.POINTER(SampleParams), C.c_int32,
                                    C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_int32, _P]),
@@ -214,6 +216,7 @@ _SIGNATURES = {
     "gvc_perceiver_bind_weight": (C.c_int, [_P, C.c_char_p, _P, C.c_int64, _P]),
     "gvc_perceiver_missing_weights": (C.c_int, [_P]),
     "gvc_perceiver_forward": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P]),
+    "gvc_perceiver_forward_masked": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P]),
     "gvc_mel_create": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_int32,
                                  c_f32p, C.POINTER(_P)]),
     "gvc_mel_destroy": (C.c_int, [_P]),

@@ -18,6 +18,7 @@
 #include "beam.h"
 #include "cfg.h"
 #include "contrastive.h"
+#include "forward_eval.h"
 #include "sampler.h"
 #include "seqscore.h"
 #include "spec.h"
@@ -335,6 +336,10 @@ struct gvc_gpt {
     unsigned short* head_h = nullptr;
     int bf16 = 0;
     float *mel_emb, *mel_pos, *text_emb, *text_pos, *lnf_w, *lnf_b, *fn_w, *fn_b, *head_w, *head_b;
+    float* thead = nullptr;           // text_head.weight [n_text][d] | text_head.bias [n_text]: optional (gvc_gpt_head_xent, head 0), an allocation of its own
+    int thead_bound = 0;              // bit 0: weight, bit 1: bias
+    const uint8_t* eval_mask = nullptr;   // key-padding mask [B][eval_mask_stride] of the running gvc_gpt_forward_rows call (null outside it)
+    int eval_mask_stride = 0;
     std::vector<GptLayer> layers;
     std::map<std::string, int> bound;  // name -> 1 once bound
     int n_expected = 0;
@@ -581,6 +586,7 @@ extern "C" int gvc_gpt_destroy(gvc_gpt* c) {
     drop_graphs(c);
     if (c->cap_stream) hipStreamDestroy(c->cap_stream);
     if (c->xalt) hipFree(c->xalt);
+    if (c->thead) hipFree(c->thead);
     if (c->seam_err_host) hipHostFree(c->seam_err_host);
     for (void* p : {(void*)c->p_layers, (void*)c->p_gran, (void*)c->p_epoch, (void*)c->p_dbg, (void*)c->r_layers, (void*)c->r_wpack,
                     (void*)c->r_bufs, (void*)c->r_dbg, (void*)c->r_lnfold, (void*)c->wb16, (void*)c->b16_fold, (void*)c->b16_stats})
@@ -644,6 +650,15 @@ extern "C" int gvc_gpt_bind_weight(gvc_gpt* c, const char* name, const float* sr
         }
     }
     else if (n == "mel_head.bias") rc = copy_w(c->head_b, src, numel, V, name, s);
+    else if (n == "text_head.weight" || n == "text_head.bias") {
+        // the evaluation pass alone reads it (gvc_gpt_head_xent): not among the expected tensors, so an inference-only bind stays complete
+        const int64_t nt = c->dm.n_text, nt4 = (nt * d + 3) & ~(int64_t)3;
+        if (!c->thead) GVC_CHECK_HIP(hipMalloc((void**)&c->thead, (size_t)(nt4 + nt) * sizeof(float)));
+        const bool w = n == "text_head.weight";
+        rc = copy_w(w ? c->thead : c->thead + nt4, src, numel, w ? nt * d : nt, name, s);
+        if (rc == GVC_OK) c->thead_bound |= w ? 1 : 2;
+        return rc;
+    }
     else if (n.rfind("gpt.h.", 0) == 0) {
         const size_t dot = n.find('.', 6);
         GVC_REQUIRE(dot != std::string::npos, GVC_ERR_ARG, "malformed weight name %s", name);
@@ -798,6 +813,12 @@ static GemvArgs base_args(gvc_gpt* c, const int32_t* slots, int row0) {
 static int launch_attention(gvc_gpt* c, AttnArgs T, int chunks, int rows, bool direct, hipStream_t s, bool wide = false) {
     // prefill-shaped calls (>= 16 rows per stream): 16-row query tiles on the matrix cores
     int rc = GVC_OK;
+    if (c->eval_mask) {            // the evaluation pass: key-padding mask inside the tile kernels, whatever the tile count
+        GVC_REQUIRE(direct && chunks == 1 && !wide && !c->kv_bf16 && rows % T.T == 0, GVC_ERR_STATE, "masked attention outside a whole-sequence fp32 pass");
+        T.key_mask = c->eval_mask;
+        T.mask_stride = c->eval_mask_stride;
+        return launch_attention_tile_masked(c->hd, c->dm.n_head, T, rows / T.T, T.T, s);
+    }
     if (direct && chunks == 1 && !wide && T.T >= 16 && rows % T.T == 0 &&
         launch_attention_tile(c->hd, c->dm.n_head, T, rows / T.T, T.base_len ? c->dm.max_seq : T.T, s, c->kv_bf16 != 0, &rc))
         return rc;
@@ -1814,6 +1835,68 @@ extern "C" int gvc_gpt_latents(gvc_gpt* c, const int32_t* slots, int32_t B, cons
     hipLaunchKernelGGL(k_set_state, dim3(cdiv(B, 64)), dim3(64), 0, s, c->st, slots, B, 0, 0);
     GVC_LAUNCH_CHECK();
     return GVC_OK;
+}
+
+// The block stack over a padded batch with all its text and code rows (GPT.forward's default call, gpt.py:476-506 and get_logits
+// :275-304): rows = [cond (n_cond) | text rows (Lt) | code rows (Lm)] per item, causal attention with the nullable key-padding mask,
+// final_norm(ln_f(h)) of the Lt + Lm rows behind the conditioning ones.  Reference numerics only (weight_dtype 0).
+extern "C" int gvc_gpt_forward_rows(gvc_gpt* c, const int32_t* slots, int32_t B, const float* cond, int32_t n_cond, const int32_t* text_ids,
+                                    int32_t Lt, const int32_t* code_ids, int32_t Lm, const uint8_t* key_mask, float* latents_out,
+                                    gvc_stream sv) {
+    int rc = check_ready(c);
+    if (rc) return rc;
+    GVC_REQUIRE(c->dm.weight_dtype == 0, GVC_ERR_UNSUPPORTED,
+                "forward_rows: the evaluation pass is a reference-numerics pass: fp32 contexts only (weight_dtype %d)", c->dm.weight_dtype);
+    GVC_REQUIRE(slots && cond && text_ids && code_ids && latents_out, GVC_ERR_ARG, "forward_rows: null argument");
+    GVC_REQUIRE(B >= 1 && B <= c->dm.max_slots, GVC_ERR_ARG, "forward_rows: B=%d outside [1,%d]", B, c->dm.max_slots);
+    GVC_REQUIRE(n_cond >= 0 && Lt >= 1 && Lm >= 1, GVC_ERR_ARG, "forward_rows: bad row counts (n_cond %d, Lt %d, Lm %d)", n_cond, Lt, Lm);
+    GVC_REQUIRE(Lt <= c->dm.max_text_pos && Lm <= c->dm.max_mel_pos, GVC_ERR_ARG,
+                "forward_rows: %d text rows / %d code rows exceed the position tables (%d, %d)", Lt, Lm, c->dm.max_text_pos, c->dm.max_mel_pos);
+    const long long T = (long long)n_cond + Lt + Lm;
+    const int d = c->dm.d_model;
+    GVC_REQUIRE(T <= c->dm.max_seq, GVC_ERR_ARG, "forward_rows: %lld rows per item exceed max_seq %d", T, c->dm.max_seq);
+    GVC_REQUIRE(B * T <= c->dm.max_rows, GVC_ERR_ARG, "forward_rows: %lld rows exceed max_rows %d", B * T, c->dm.max_rows);
+    hipStream_t s = (hipStream_t)sv;
+    if ((rc = launch_eval_embed(c->x, cond, n_cond, text_ids, Lt, code_ids, Lm, B, d, c->text_emb, c->text_pos, c->dm.n_text, c->mel_emb,
+                                c->mel_pos, c->dm.vocab, s)))
+        return rc;
+    c->rows_keys_hint = (int)T;
+    c->eval_mask = key_mask;
+    c->eval_mask_stride = (int)T;
+    rc = run_rows(c, slots, B, (int)T, s);
+    c->eval_mask = nullptr;
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_ln_rows, dim3(cdiv(B * (int)T, 4)), dim3(256), 0, s, c->x, c->a, B * (int)T, d, c->lnf_w, c->lnf_b, c->fn_w, c->fn_b, 0);
+    GVC_LAUNCH_CHECK();
+    if ((rc = launch_eval_gather(c->a, latents_out, B, (int)T, n_cond, Lt + Lm, d, s))) return rc;
+    hipLaunchKernelGGL(k_set_state, dim3(cdiv(B, 64)), dim3(64), 0, s, c->st, slots, B, 0, 0);
+    GVC_LAUNCH_CHECK();
+    return GVC_OK;
+}
+
+// One head over R latent rows and its loss terms (gpt.py:306-312, 526-535): logits_out [R][V] = head(latents), then launch_head_xent
+// (forward_eval.h).  head 0: text_head (V = n_text), 1: mel_head (V = vocab)
+extern "C" int gvc_gpt_head_xent(gvc_gpt* c, const float* latents, int32_t R, int32_t head, const int32_t* targets, float label_smoothing,
+                                 int32_t top_k, float* logits_out, float* row_terms, double* sums, gvc_stream sv) {
+    int rc = check_ready(c);
+    if (rc) return rc;
+    GVC_REQUIRE(c->dm.weight_dtype == 0, GVC_ERR_UNSUPPORTED,
+                "head_xent: the evaluation pass is a reference-numerics pass: fp32 contexts only (weight_dtype %d)", c->dm.weight_dtype);
+    GVC_REQUIRE(latents && targets && logits_out && row_terms && sums, GVC_ERR_ARG, "head_xent: null argument");
+    GVC_REQUIRE(head == 0 || head == 1, GVC_ERR_ARG, "head_xent: head %d (0 text_head, 1 mel_head)", head);
+    GVC_REQUIRE(R >= 1 && R <= c->dm.max_rows, GVC_ERR_ARG, "head_xent: %d rows outside [1, max_rows %d]", R, c->dm.max_rows);
+    GVC_REQUIRE(label_smoothing >= 0.f && label_smoothing <= 1.f && top_k >= 1, GVC_ERR_ARG, "head_xent: label_smoothing %g outside [0,1] or top_k %d < 1",
+                (double)label_smoothing, top_k);
+    GVC_REQUIRE(head == 1 || c->thead_bound == 3, GVC_ERR_STATE, "head_xent: text_head.weight / text_head.bias are not bound");
+    const int d = c->dm.d_model, V = head ? c->dm.vocab : c->dm.n_text;
+    const long long nt4 = ((long long)c->dm.n_text * d + 3) & ~3ll;
+    hipStream_t s = (hipStream_t)sv;
+    GemmArgs G;
+    memset(&G, 0, sizeof(G));
+    G.A = latents; G.lda = d; G.Wt = head ? c->head_w : c->thead; G.ldw = d; G.C = logits_out; G.ldc = V; G.M = R; G.N = V; G.K = d;
+    G.work = c->work; G.e.bias = head ? c->head_b : c->thead + nt4;
+    if ((rc = launch_gemm_cap(G, 1, c->work_cap, s))) return rc;
+    return launch_head_xent(logits_out, V, targets, R, V, label_smoothing, top_k, row_terms, sums, s);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -440,6 +440,10 @@ struct AttnArgs {
     float* out;                // DIRECT: [rows][out_stride] ; else partials [rows][heads][chunks][HD+4]
     int out_stride;
     int out_fm16;              // DIRECT: write `out` in the FM16 layout of gemm.h (row length out_stride)
+    // key-padding mask of the tile kernels' MASK instantiations (forward_eval.hip; null everywhere else): key_mask[b * mask_stride + k]
+    // == 0 excludes key k of batch element b for every query row, on top of the causal limit
+    const uint8_t* key_mask;
+    int mask_stride;
 };
 
 // NW = waves that share the keys of one (chunk, head, row): 4, or 16 for the batched decode rows (one new row over a
@@ -671,7 +675,10 @@ __global__ __launch_bounds__(512, 2) void k_attn_proj(const AttnProjArgs A) {
 
 typedef float at_f32x4 __attribute__((ext_vector_type(4)));
 
-template <int HD, int KVB, int VC>          // VC: keys per V chunk
+// MASK (the evaluation pass, reference gpt.py:446-474): a key with key_mask == 0 gets weight exactly 0 -- it is left out of the row
+// maximum and of the sum, as in k_attn64_mfma, never pushed down by a large negative number; a 16-key tile (or a whole row) of masked
+// keys contributes zeros.  The unmasked instantiations compile to what they were.
+template <int HD, int KVB, int VC, bool MASK = false>          // VC: keys per V chunk
 __global__ __launch_bounds__(512) void k_attention_tile(const AttnArgs A, int nkp) {
     constexpr int KB = HD / 16;                    // 16-dim blocks of a head
     constexpr int NTW = KB >= 8 ? KB / 8 : 1;      // output column tiles per wave
@@ -748,17 +755,19 @@ __global__ __launch_bounds__(512) void k_attention_tile(const AttnArgs A, int nk
         const int r = 2 * wave + rr;
         const int lim = A.causal ? min(base + t0 + r + 1, nk) : nk;
         float* sr = S + r * lds_s;
+        const uint8_t* km = MASK ? A.key_mask + (size_t)b * A.mask_stride : nullptr;
+        auto seen = [&](int k) { return k < lim && (!MASK || km[k] != 0); };
         float mx = -INFINITY;
-        for (int k = lane; k < nkt * 16; k += 64) mx = fmaxf(mx, k < lim ? sr[k] : -INFINITY);
+        for (int k = lane; k < nkt * 16; k += 64) mx = fmaxf(mx, seen(k) ? sr[k] : -INFINITY);
         mx = wave_max(mx);
         float sum = 0.f;
         for (int k = lane; k < nkt * 16; k += 64) {
-            const float pr = k < lim ? __expf(sr[k] - mx) : 0.f;
+            const float pr = seen(k) ? __expf(sr[k] - mx) : 0.f;
             sr[k] = pr;
             sum += pr;
         }
         sum = wave_sum(sum);
-        if (lane == 0) linv[r] = 1.0f / sum;
+        if (lane == 0) linv[r] = (MASK && sum == 0.f) ? 0.f : 1.0f / sum;        // (a row with every key masked: zeros, not NaN)
     }
 
     // ---- 3. O = P V ----
@@ -822,7 +831,7 @@ __global__ __launch_bounds__(512) void k_attention_tile(const AttnArgs A, int nk
 // whole K and the whole V of the head are requested up front with coalesced row loads (one memory round trip for the kernel),
 // K and V take turns in one LDS buffer, and every fragment comes from LDS.  One key tile per wave in phase 1; the P V loop has
 // no tail case (S is zero-filled up to 128 keys).
-template <int HD, int KVB>
+template <int HD, int KVB, bool MASK = false>          // MASK: as k_attention_tile
 __global__ __launch_bounds__(512) void k_attention_tile_short(const AttnArgs A) {
     constexpr int KB = HD / 16, NTW = KB >= 8 ? KB / 8 : 1, LDV = HD + 4, ES = KVB ? 2 : 4;
     constexpr int NKP = 128, LDS_S = NKP + 4;
@@ -908,13 +917,15 @@ __global__ __launch_bounds__(512) void k_attention_tile_short(const AttnArgs A) 
         const int r = 2 * wave + rr;
         const int lim = A.causal ? min(base + t0 + r + 1, nk) : nk;
         float* sr = S + r * LDS_S;
-        const float s0 = lane < lim ? sr[lane] : -INFINITY, s1 = lane + 64 < lim ? sr[lane + 64] : -INFINITY;
+        const uint8_t* km = MASK ? A.key_mask + (size_t)b * A.mask_stride : nullptr;
+        const bool ok0 = lane < lim && (!MASK || km[lane] != 0), ok1 = lane + 64 < lim && (!MASK || km[lane + 64] != 0);
+        const float s0 = ok0 ? sr[lane] : -INFINITY, s1 = ok1 ? sr[lane + 64] : -INFINITY;
         const float mx = wave_max(fmaxf(s0, s1));
-        const float p0 = lane < lim ? __expf(s0 - mx) : 0.f, p1 = lane + 64 < lim ? __expf(s1 - mx) : 0.f;
+        const float p0 = ok0 ? __expf(s0 - mx) : 0.f, p1 = ok1 ? __expf(s1 - mx) : 0.f;
         sr[lane] = p0;
         sr[lane + 64] = p1;
         const float sum = wave_sum(p0 + p1);
-        if (lane == 0) linv[r] = 1.0f / sum;
+        if (lane == 0) linv[r] = (MASK && sum == 0.f) ? 0.f : 1.0f / sum;
     }
     __syncthreads();
 

@@ -17,6 +17,7 @@
 
 #include "gemm.h"
 #include "attn64.h"
+#include "forward_eval.h"
 
 namespace gvc {
 
@@ -92,6 +93,7 @@ struct gvc_perceiver {
     unsigned long long tick = 0;
     hipStream_t cap_stream = nullptr;
     int use_graph = 1;               // GVC_PERCEIVER_GRAPH=0: eager launches
+    int32_t* fmask = nullptr;        // [max_batch][num_latents + max_frames] excluded-key flags of a masked forward (allocated by the first one)
 };
 
 extern "C" int gvc_perceiver_create(const gvc_perceiver_dims* dims, gvc_perceiver** out) {
@@ -156,7 +158,7 @@ extern "C" int gvc_perceiver_destroy(gvc_perceiver* c) {
     for (auto& kvp : c->graphs) (void)hipGraphExecDestroy(kvp.second);
     if (c->cap_stream) (void)hipStreamDestroy(c->cap_stream);
     for (void* p : {(void*)c->wbase, (void*)c->C, (void*)c->X, (void*)c->kv, (void*)c->o, (void*)c->g, (void*)c->xp, (void*)c->work,
-                    (void*)c->tmp})
+                    (void*)c->tmp, (void*)c->fmask})
         if (p) hipFree(p);
     delete c;
     return GVC_OK;
@@ -259,7 +261,8 @@ static int perc_stage_in(gvc_perceiver* c, const float* x, int B, int F, hipStre
 }
 
 // `side`: a second stream of the same capture (null: everything in order on s)
-static int perc_launch(gvc_perceiver* c, int B, int F, hipStream_t s) {
+// fmask (nullable): [B][num_latents + F], nonzero = key excluded (gvc_perceiver_forward_masked)
+static int perc_launch(gvc_perceiver* c, int B, int F, hipStream_t s, const int32_t* fmask = nullptr) {
     const int d = c->dm.dim, in = c->inner, NL = c->dm.num_latents, R = NL + F, depth = c->dm.depth, fp = c->ffi_p;
     const int ldkv = depth * 3 * in;                  // floats per row of KV: [depth][q | k | v]
     int rc;
@@ -309,6 +312,10 @@ static int perc_launch(gvc_perceiver* c, int B, int F, hipStream_t s) {
         // cross-attention of the 32 latent queries over latents + context, output fragment-major [B * 32][inner]
         {
             const float* qb = c->kv + (size_t)l * 3 * in;
+            if (fmask)
+                hipLaunchKernelGGL((k_attn64_mfma<true, 16>), dim3(NL / 16, c->dm.heads, B), dim3(1024), 0, s, qb, qb + in, qb + 2 * in, (long long)ldkv,
+                                   (long long)R * ldkv, NL, R, c->o, NL, in, 1.0f / sqrtf((float)c->dm.dim_head), 1, fmask);
+            else
             hipLaunchKernelGGL((k_attn64_mfma<false, 16>), dim3(NL / 16, c->dm.heads, B), dim3(1024), 0, s, qb, qb + in, qb + 2 * in, (long long)ldkv,
                                (long long)R * ldkv, NL, R, c->o, NL, in, 1.0f / sqrtf((float)c->dm.dim_head), 1, (const int32_t*)nullptr);
             GVC_LAUNCH_CHECK();
@@ -369,6 +376,30 @@ extern "C" int gvc_perceiver_forward(gvc_perceiver* c, const float* x, int32_t B
         c->graph_used[key] = ++c->tick;
         GVC_CHECK_HIP(hipGraphLaunch(it->second, s));
     }
+    hipLaunchKernelGGL(k_rmsnorm_rows_fm16, dim3(cdiv(B * c->dm.num_latents, 4)), dim3(256), 0, s, c->X, out, B * c->dm.num_latents, c->dm.dim,
+                       c->gamma);
+    GVC_LAUNCH_CHECK();
+    return GVC_OK;
+}
+
+// The forward with a key-padding mask over [latents | frames] (PerceiverResampler.forward(mask=), perceiver_encoder.py:265-273 and
+// Attention.forward :305-316; the caller of gpt.py:362-369 builds it): every layer's cross-attention leaves out the keys with
+// key_mask == 0.  Uncaptured: the unmasked call and its graphs are untouched.
+extern "C" int gvc_perceiver_forward_masked(gvc_perceiver* c, const float* x, int32_t B, int32_t F, const uint8_t* key_mask, float* out,
+                                            gvc_stream sv) {
+    GVC_REQUIRE(c && x && out && key_mask, GVC_ERR_ARG, "gvc_perceiver_forward_masked: null argument");
+    GVC_REQUIRE(gvc_perceiver_missing_weights(c) == 0, GVC_ERR_STATE, "%d Perceiver weight tensors are not bound",
+                gvc_perceiver_missing_weights(c));
+    GVC_REQUIRE(B >= 1 && B <= c->dm.max_batch && F >= 1 && F <= c->dm.max_frames, GVC_ERR_ARG,
+                "perceiver: B=%d F=%d outside capacity (%d, %d)", B, F, c->dm.max_batch, c->dm.max_frames);
+    hipStream_t s = (hipStream_t)sv;
+    int rc;
+    if (!c->fmask)
+        GVC_CHECK_HIP(hipMalloc((void**)&c->fmask, (size_t)c->dm.max_batch * (c->dm.num_latents + c->dm.max_frames) * sizeof(int32_t)));
+    if ((rc = perc_prepare(c, s))) return rc;
+    if ((rc = perc_stage_in(c, x, B, F, s))) return rc;
+    if ((rc = launch_mask_excluded(key_mask, c->fmask, B * (c->dm.num_latents + F), s))) return rc;
+    if ((rc = perc_launch(c, B, F, s, c->fmask))) return rc;
     hipLaunchKernelGGL(k_rmsnorm_rows_fm16, dim3(cdiv(B * c->dm.num_latents, 4)), dim3(256), 0, s, c->X, out, B * c->dm.num_latents, c->dm.dim,
                        c->gamma);
     GVC_LAUNCH_CHECK();

@@ -731,6 +731,8 @@ class GptEngine:
         self.d = dims["d_model"]
         self.V = dims["num_audio_tokens"]
         self.max_slots = max_slots
+        self.max_rows = max_rows
+        self.weight_dtype = weight_dtype
         max_seq = max_seq or ((dims["max_seq"] + 63) // 64) * 64
         cd = _lib.GptDims(dims["n_layer"], dims["d_model"], dims["n_head"], dims["num_audio_tokens"],
                           dims["max_mel_pos"], dims["max_text_pos"], dims["number_text_tokens"], max_seq,
@@ -858,6 +860,52 @@ class GptEngine:
                                     self.dims["start_audio_token"], self.dims["stop_audio_token"], ptr(out),
                                     stream()), "latents")
         return out
+
+    def _eval_check(self, rc, what):
+        """status of an evaluation-pass entry: argument errors as ValueError, a bf16 context as NotImplementedError naming its mode"""
+        if rc == -4:
+            raise NotImplementedError(f"{what}: the evaluation pass runs in reference numerics only -- this context was created with "
+                                      f"weight_dtype=\"{self.weight_dtype}\" ({lib().gvc_last_error().decode(errors='replace')})")
+        if rc == -1:
+            raise ValueError(f"{what}: {lib().gvc_last_error().decode(errors='replace')}")
+        check(rc, what)
+
+    def forward_rows(self, slots, cond_latents, text_ids, code_ids, key_mask=None):
+        """cond_latents fp32 [B, n_cond, d], text_ids int32 [B, Lt], code_ids int32 [B, Lm], key_mask uint8 / bool [B, n_cond + Lt + Lm]
+        (nonzero = attend; None: no mask) -> final_norm(ln_f(h)) of the Lt + Lm rows behind the conditioning ones, fp32 [B, Lt + Lm, d]
+        (include/genvc_hip.h: gvc_gpt_forward_rows)"""
+        self._join_side()
+        cond_latents = _f32(cond_latents.contiguous())
+        text_ids, code_ids = _i32(text_ids.contiguous()), _i32(code_ids.contiguous())
+        B, n_cond, d = cond_latents.shape
+        Lt, Lm = int(text_ids.shape[1]), int(code_ids.shape[1])
+        if d != self.d or text_ids.shape[0] != B or code_ids.shape[0] != B or slots.shape[0] != B:
+            raise ValueError(f"forward_rows: cond {tuple(cond_latents.shape)}, text ids {tuple(text_ids.shape)}, code ids "
+                             f"{tuple(code_ids.shape)} and {int(slots.shape[0])} slots do not go together (d_model {self.d})")
+        if key_mask is not None:
+            if tuple(key_mask.shape) != (B, n_cond + Lt + Lm):
+                raise ValueError(f"forward_rows: key mask {tuple(key_mask.shape)} for {B} x {n_cond + Lt + Lm} rows")
+            key_mask = key_mask.to(torch.uint8).contiguous()
+        out = torch.empty(B, Lt + Lm, self.d, device=cond_latents.device, dtype=torch.float32)
+        self._eval_check(lib().gvc_gpt_forward_rows(self._h, ptr(_i32(slots)), B, ptr(cond_latents), n_cond, ptr(text_ids), Lt,
+                                                    ptr(code_ids), Lm, ptr(key_mask), ptr(out), stream()), "forward_rows")
+        return out
+
+    def head_xent(self, latents, head, targets, label_smoothing=0.0, top_k=10):
+        """latents fp32 [R, d], head "text" / "mel", targets int32 [R] (-1 = ignored) -> (logits fp32 [R, V], row_terms fp32 [R, 3] =
+        (nll, smoothing term, top-k hit), sums float64 [4] = (loss, hits, count, mean nll))   (include/genvc_hip.h: gvc_gpt_head_xent)"""
+        latents = _f32(latents.contiguous())
+        targets = _i32(targets.contiguous())
+        R = int(latents.shape[0])
+        if latents.ndim != 2 or latents.shape[1] != self.d or tuple(targets.shape) != (R,):
+            raise ValueError(f"head_xent: latents {tuple(latents.shape)} / targets {tuple(targets.shape)} (d_model {self.d})")
+        V = {"text": self.dims["number_text_tokens"], "mel": self.V}[head]
+        logits = torch.empty(R, V, device=latents.device, dtype=torch.float32)
+        terms = torch.empty(R, 3, device=latents.device, dtype=torch.float32)
+        sums = torch.empty(4, device=latents.device, dtype=torch.float64)
+        self._eval_check(lib().gvc_gpt_head_xent(self._h, ptr(latents), R, 1 if head == "mel" else 0, ptr(targets), float(label_smoothing),
+                                                 int(top_k), ptr(logits), ptr(terms), ptr(sums), stream()), "head_xent")
+        return logits, terms, sums
 
     # ---- the sampler and generation entry points: families of C entries (include/genvc_hip.h), one marshalling path each ----------------
     def _neutral_params(self):
@@ -1295,6 +1343,17 @@ class PerceiverEngine:
         missing = lib().gvc_perceiver_missing_weights(self._h)
         if missing:
             raise _lib.GenvcHipError(f"{missing} Perceiver weight tensors missing after bind")
+
+    def forward_masked(self, x, key_mask):
+        """x [B, F, dim_context], key_mask uint8 / bool [B, num_latents + F] over the keys [latents | frames] (nonzero = attend)
+        (include/genvc_hip.h: gvc_perceiver_forward_masked)"""
+        B, F, _ = x.shape
+        if tuple(key_mask.shape) != (B, self.num_latents + F):
+            raise ValueError(f"perceiver: mask {tuple(key_mask.shape)} for {B} x ({self.num_latents} latents + {F} frames)")
+        key_mask = key_mask.to(device=x.device, dtype=torch.uint8).contiguous()
+        out = torch.empty(B, self.num_latents, self.dim, device=x.device, dtype=torch.float32)
+        check(lib().gvc_perceiver_forward_masked(self._h, ptr(_f32(x)), B, F, ptr(key_mask), ptr(out), stream()), "perceiver_forward_masked")
+        return out
 
     def forward(self, x):
         """x [B,F,dim_context] -> [B,num_latents,dim]"""

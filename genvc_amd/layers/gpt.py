@@ -3,12 +3,14 @@
 (same names and shapes as the reference state dict, so `load_state_dict(ckpt['model'])` works) and
 drives libgenvc_hip through `GptEngine`; there is no PyTorch arithmetic fallback.
 
-Mapped entry points: init_gpt_for_inference (:197), get_style_emb (:351), forward(return_latent=True)
-(:375-508), compute_embeddings (:572), generate (:594), get_generator (:612), inference (:569).
-Training-only paths (losses, masks, eval_sample) raise NotImplementedError: out of scope.
+Mapped entry points: init_gpt_for_inference (:197), get_style_emb (:351, seq_lens included), forward (:375-537: the evaluation pass --
+losses, top-10 accuracy, mel logits of a ragged batch -- and return_latent=True), compute_embeddings (:572), generate (:594),
+get_generator (:612), inference (:569).
+Training mode, return_attentions and eval_sample raise NotImplementedError: out of scope.
 """
 import torch
 from torch import nn
+from torch.nn import functional as F
 
 from .._lib import GenvcHipError
 from ..engine import (MAX_ASSISTANT_TOKENS, MAX_LOOKUP_HISTORY, MAX_LOOKUP_NGRAM, MAX_VERIFY_ROWS, AssistedState, BEAM_LENGTH_MODES, beam_early_stopping, check_beam_groups, GroupBeamSearch, MAX_CONTRASTIVE_K, PROC_KWARGS, WARP_KWARGS, BeamSearch, ContrastiveSearch, GptEngine, WarperSets,
@@ -417,6 +419,72 @@ def _ln(d):
     return m
 
 
+def perceiver_key_mask(seq_lens, n_frames, num_latents=32):
+    """the Perceiver mask of reference gpt.py:362-367, bool [B, n_frames + num_latents]: cat([frame j < seq_lens[b], ones(num_latents)]).
+    The reference's Attention lays its keys out as cat([latents, frames]) (perceiver_encoder.py:310-311), so entry j of this mask meets
+    key j of [latents | frames]: the masked keys are those with index in [len, n_frames) -- frames len - num_latents .. n_frames -
+    num_latents - 1, and latents len .. num_latents - 1 when len < num_latents -- and the last num_latents frames are always attended.
+    That misalignment is the reference's behaviour and is reproduced, not repaired."""
+    seq_lens = torch.as_tensor(seq_lens).to("cpu", torch.long).reshape(-1)
+    frames = torch.arange(int(n_frames)).unsqueeze(0) < seq_lens.unsqueeze(1)
+    return torch.cat([frames, torch.ones(seq_lens.shape[0], num_latents, dtype=torch.bool)], dim=-1)
+
+
+def forward_eval_prepare(text_inputs, text_lengths, audio_codes, wav_lengths, *, code_stride_len=1024, start_text_token=256,
+                         stop_text_token=257, start_audio_token=1024, stop_audio_token=1025, number_text_tokens=258,
+                         num_audio_tokens=1026, n_cond=32):
+    """The integer preparation of GPT.forward (reference gpt.py:404-474, 514-518) on the host, as CPU int64 / bool tensors:
+      text_ids [B, Lt]      = start | text[:max(text_lengths)] with stop from each row's length on | stop          (Lt = max len + 2)
+      code_ids [B, Lm]      = start | codes zero-padded to max(code_lengths) with stop from each row's real length on | stop
+                              (code_lengths = ceil(wav_lengths / code_stride_len) + 3, Lm = max(code_lengths) + 2)
+      text_targets / mel_targets = the same rows without the start token and with one more stop, -1 from position l + 1 on
+                              (l = the row's text length / code length with its + 3)
+      key_mask [B, n_cond + Lt + Lm] = ones over the conditioning rows; text and code positions > l are 0 (the first stop token of a
+                              text row is itself a masked key)."""
+    text_inputs = torch.as_tensor(text_inputs).to("cpu", torch.long)
+    audio_codes = torch.as_tensor(audio_codes).to("cpu", torch.long)
+    text_lengths = torch.as_tensor(text_lengths).to("cpu", torch.long).reshape(-1)
+    wav_lengths = torch.as_tensor(wav_lengths).to("cpu").reshape(-1)
+    B = text_inputs.shape[0]
+    if text_inputs.ndim != 2 or audio_codes.ndim != 2 or audio_codes.shape[0] != B or text_lengths.shape[0] != B or wav_lengths.shape[0] != B:
+        raise ValueError(f"forward: text {tuple(text_inputs.shape)}, codes {tuple(audio_codes.shape)}, {text_lengths.shape[0]} text lengths "
+                         f"and {wav_lengths.shape[0]} wav lengths do not describe one batch")
+    if int(text_lengths.min()) < 0 or int(wav_lengths.min()) < 0:
+        raise ValueError("forward: negative length")
+    max_text_len = int(text_lengths.max())
+    code_lengths = torch.ceil(wav_lengths / code_stride_len).long() + 3                      # gpt.py:405
+    max_mel_len = int(code_lengths.max())
+    if max_mel_len > audio_codes.shape[-1]:
+        audio_codes = F.pad(audio_codes, (0, max_mel_len - audio_codes.shape[-1]))           # :413-414
+    if max_text_len > text_inputs.shape[-1]:
+        raise ValueError(f"forward: max(text_lengths) {max_text_len} > text_inputs.shape[-1] {text_inputs.shape[-1]}")      # :420-422
+    if text_inputs.numel() and (int(text_inputs.min()) < 0 or int(text_inputs.max()) >= number_text_tokens):
+        raise ValueError(f"forward: text ids outside [0, {number_text_tokens})")
+    if int(audio_codes.min()) < 0 or int(audio_codes.max()) >= num_audio_tokens:
+        raise ValueError(f"forward: audio codes outside [0, {num_audio_tokens})")
+    text = F.pad(text_inputs[:, :max_text_len], (0, 1), value=stop_text_token)               # :425
+    codes = F.pad(audio_codes[:, :max_mel_len], (0, 1), value=stop_audio_token)              # :430
+    for b in range(B):                                                                       # set_text_padding / set_mel_padding, :237-260
+        lt, lc = int(text_lengths[b]), int(code_lengths[b]) - 3
+        if lt < text.shape[-1]:
+            text[b, lt:] = stop_text_token
+        if lc < codes.shape[-1]:
+            codes[b, lc:] = stop_audio_token
+    text_ids, text_targets = F.pad(text, (1, 0), value=start_text_token), F.pad(text, (0, 1), value=stop_text_token)        # :232-235
+    code_ids, mel_targets = F.pad(codes, (1, 0), value=start_audio_token), F.pad(codes, (0, 1), value=stop_audio_token)
+    mask_text = torch.ones(text_ids.shape, dtype=torch.bool)
+    mask_mel = torch.ones(code_ids.shape, dtype=torch.bool)
+    for b in range(B):                                                                       # :470-474, 514-518
+        lt, lc = int(text_lengths[b]), int(code_lengths[b])
+        mask_text[b, lt + 1:] = False
+        mask_mel[b, lc + 1:] = False
+        text_targets[b, lt + 1:] = -1
+        mel_targets[b, lc + 1:] = -1
+    key_mask = torch.cat([torch.ones(B, n_cond, dtype=torch.bool), mask_text, mask_mel], dim=1)
+    return dict(text_ids=text_ids, text_targets=text_targets, code_ids=code_ids, mel_targets=mel_targets, key_mask=key_mask,
+                code_lengths=code_lengths)
+
+
 class GPT(nn.Module):
     rolling_samples = True          # generate_rolling samples with per-job keys (job_seeds): parallel_offline rolls sampled runs too
 
@@ -438,6 +506,10 @@ class GPT(nn.Module):
         self.max_text_tokens = max_text_tokens + 2                                         # :133
         self.max_prompt_tokens = max_prompt_tokens
         self.code_stride_len = code_stride_len
+        self.label_smoothing = label_smoothing
+        self.perceiver_cond_length_compression = perceiver_cond_length_compression
+        self.train_solo_embeddings = train_solo_embeddings
+        self.average_conditioning_embeddings = average_conditioning_embeddings
 
         d = model_dim
         self.text_embedding = _Holder(); self.text_embedding.weight = _p(number_text_tokens, d)
@@ -525,10 +597,11 @@ class GPT(nn.Module):
             return cond_input.unsqueeze(1)
         if cond_input.ndim == 4:
             cond_input = cond_input.squeeze(1)
-        if seq_lens is not None:
-            raise NotImplementedError("perceiver masks are a training-only path")
         x = frames_major if frames_major is not None else cond_input.permute(0, 2, 1).contiguous()
-        return self.conditioning_perceiver(x).transpose(1, 2)
+        mask = None
+        if seq_lens is not None:              # gpt.py:362-367 (seq_lens in frames)
+            mask = perceiver_key_mask(seq_lens, x.shape[1], self.conditioning_perceiver.cfg["num_latents"])
+        return self.conditioning_perceiver(x, mask=mask).transpose(1, 2)
 
     @torch.inference_mode()
     def compute_embeddings(self, cond_latents, text_inputs):
@@ -1358,15 +1431,55 @@ class GPT(nn.Module):
     @torch.inference_mode()
     def forward(self, text_inputs, text_lengths, audio_codes, wav_lengths, cond_mels=None, cond_lens=None,
                 cond_latents=None, return_attentions=False, return_latent=False):
-        """Inference use of reference gpt.py:375-508: `return_latent=True` with `cond_latents` given
-        (inference_utils.py:71-76) -> latents [B,n,d] of the n = ceil(wav_lengths/1024) codes."""
+        """reference gpt.py:375-537 in eval mode.
+        Default call: a padded batch with `text_lengths`, `wav_lengths` (samples) and `cond_mels` (b,1,80,s) + `cond_lens` (samples; or
+        `cond_latents` (b,32,d) alone) -> (loss_text, loss_mel, Top10Accuracy, mel_logits [B, V, Lm]): the evaluation pass
+        (forward_eval_prepare on the host, then gvc_gpt_forward_rows + gvc_gpt_head_xent).  Top10Accuracy follows the published
+        definition of torchmetrics MulticlassAccuracy(top_k=10, average="micro", ignore_index=-1).
+        `return_latent=True` with `cond_latents` (inference_utils.py:71-76) -> latents [B,n,d] of the n = max ceil(wav_lengths/1024) codes;
+        ragged lengths take the reference's padding and no attention mask (gpt.py:450)."""
         self._need_engine()
-        if not return_latent or cond_latents is None or return_attentions:
-            raise NotImplementedError("only forward(..., cond_latents=..., return_latent=True) is on the inference path")
-        B, n = audio_codes.shape
-        if int(text_lengths.min()) != text_inputs.shape[1] or int(torch.ceil(wav_lengths / self.code_stride_len).min()) != n:
-            raise NotImplementedError("ragged text/code lengths are a training-only path")
-        prefix = self.engine.prefix_embeddings(cond_latents.to(torch.float32).contiguous(),
-                                               text_inputs.to(torch.int32).contiguous())
-        slots = torch.arange(B, device=audio_codes.device, dtype=torch.int32)
-        return self.engine.latents(slots, prefix, audio_codes.to(torch.int32).contiguous())
+        if return_attentions:
+            raise NotImplementedError("return_attentions: the attention kernels do not keep their weights")
+        dev = audio_codes.device
+        if return_latent and cond_latents is not None:
+            B, n = audio_codes.shape
+            if int(text_lengths.min()) == text_inputs.shape[1] and int(torch.ceil(wav_lengths / self.code_stride_len).min()) == n:
+                prefix = self.engine.prefix_embeddings(cond_latents.to(torch.float32).contiguous(),
+                                                       text_inputs.to(torch.int32).contiguous())
+                slots = torch.arange(B, device=dev, dtype=torch.int32)
+                return self.engine.latents(slots, prefix, audio_codes.to(torch.int32).contiguous())
+        # everything below is new ground (the equal-length re-pass above serves a module in either mode, as it always has)
+        if self.training:
+            raise NotImplementedError("GPT.forward in training mode (dropout, gradients, [:, :-1] latents): call .eval() first")
+        if self.train_solo_embeddings or self.average_conditioning_embeddings:
+            raise NotImplementedError("train_solo_embeddings / average_conditioning_embeddings are not part of the evaluation pass")
+        if cond_latents is None and cond_mels is None:
+            raise ValueError("forward: cond_mels (with cond_lens) or cond_latents is needed")
+        if cond_latents is None:
+            cond_latents = self.get_style_emb(cond_mels, seq_lens=None if cond_lens is None else
+                                              torch.as_tensor(cond_lens).to("cpu") // self.perceiver_cond_length_compression)   # gpt.py:407-408, 486
+            cond_latents = cond_latents.transpose(1, 2)
+        cond_latents = cond_latents.to(device=dev, dtype=torch.float32).contiguous()
+        prep = forward_eval_prepare(text_inputs, text_lengths, audio_codes, wav_lengths, code_stride_len=self.code_stride_len,
+                                    start_text_token=self.start_text_token, stop_text_token=self.stop_text_token,
+                                    start_audio_token=self.start_audio_token, stop_audio_token=self.stop_audio_token,
+                                    number_text_tokens=self.number_text_tokens, num_audio_tokens=self.num_audio_tokens,
+                                    n_cond=cond_latents.shape[1])
+        B, Lt = prep["text_ids"].shape
+        Lm = prep["code_ids"].shape[1]
+        if B > self.max_slots:
+            raise ValueError(f"forward: {B} items exceed the context's {self.max_slots} slots (init_gpt_for_inference(max_slots=))")
+        slots = torch.arange(B, device=dev, dtype=torch.int32)
+        text_ids, code_ids = prep["text_ids"].to(dev, torch.int32), prep["code_ids"].to(dev, torch.int32)
+        key_mask = None if return_latent else prep["key_mask"].to(dev, torch.uint8)           # gpt.py:450
+        lat = self.engine.forward_rows(slots, cond_latents, text_ids, code_ids, key_mask)
+        if return_latent:
+            return lat[:, Lt:][:, :-5].contiguous()                                           # gpt.py:304, 491, 508
+        _, _, s_text = self.engine.head_xent(lat[:, :Lt].reshape(B * Lt, -1), "text", prep["text_targets"].reshape(-1).to(dev, torch.int32),
+                                             self.label_smoothing)
+        mel_logits, _, s_mel = self.engine.head_xent(lat[:, Lt:].reshape(B * Lm, -1), "mel",
+                                                     prep["mel_targets"].reshape(-1).to(dev, torch.int32), self.label_smoothing)
+        loss_text, loss_mel = s_text[0].to(torch.float32), s_mel[0].to(torch.float32)
+        acc = (s_mel[1] / s_mel[2]).to(torch.float32)
+        return loss_text, loss_mel, acc, mel_logits.view(B, Lm, -1).permute(0, 2, 1)

@@ -51,9 +51,10 @@ class PerceiverResampler(nn.Module):
 
     @torch.inference_mode()
     def forward(self, x, mask=None):
-        """x [B,F,dim_context] -> [B,num_latents,dim]"""
-        if mask is not None:
-            raise NotImplementedError("PerceiverResampler mask is a training-only path (reference gpt.py:362-367)")
+        """x [B,F,dim_context] -> [B,num_latents,dim].  mask (bool [B, F + num_latents], True = attend): the key-padding mask of every
+        layer's cross-attention, entry j for key j of cat([latents, x]) (reference perceiver_encoder.py:305-316)"""
         if self._engine is None:
             self.bind()
+        if mask is not None:
+            return self._engine.forward_masked(x.to(torch.float32).contiguous(), mask)
         return self._engine.forward(x.to(torch.float32).contiguous())

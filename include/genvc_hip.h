@@ -188,6 +188,30 @@ int gvc_gpt_latents(gvc_gpt* ctx, const int32_t* slots, int32_t B, const float* 
                     const int32_t* gen_codes, int32_t n, int32_t start_tok, int32_t stop_tok,
                     float* out, gvc_stream s);
 
+/* The evaluation pass, GPT.forward's default call (gpt.py:375-537; the reference trainer's eval step): a padded batch through the
+ * block stack with ALL its text and code rows, then both heads, the losses and the top-k accuracy.  The integer preparation
+ * (gpt.py:404-474, 514-518: padding, start / stop tokens, targets, masks) is the caller's (genvc_amd.layers.gpt.forward_eval_prepare).
+ *
+ * gvc_gpt_forward_rows: rows of item b = [cond[b] (n_cond) | text_emb[text_ids[b][i]] + text_pos[i] (Lt) | mel_emb[code_ids[b][i]] +
+ * mel_pos[i] (Lm)] (gpt.py:476-480, get_logits :275-280); causal attention combined with the key-padding mask key_mask uint8
+ * [B][n_cond + Lt + Lm] (nonzero = attend, device, nullable = no mask: gpt.py:446-474 -- the mask a return_latent call does not
+ * pass).  A masked key has weight exactly 0 for every query row; padded query rows are still computed.  latents_out [B][Lt + Lm][d] =
+ * final_norm(ln_f(h)) of the rows behind the conditioning ones (get_logits :300-301).  Uses slots[b] as K/V scratch, as gvc_gpt_latents.
+ * GVC_ERR_ARG: B > max_slots, B * (n_cond + Lt + Lm) > max_rows, Lt / Lm beyond the position tables, n_cond + Lt + Lm > max_seq.
+ * GVC_ERR_UNSUPPORTED: a context with weight_dtype != 0 (evaluation is a reference-numerics job).
+ *
+ * gvc_gpt_head_xent: logits_out [R][V] = head(latents [R][d]) (head 0: text_head, V = n_text, needs text_head.* bound, else
+ * GVC_ERR_STATE; head 1: mel_head, V = vocab), then per row r with target t = targets[r] (int32, -1 = ignored):
+ *   row_terms[r] = (lse - x[t],  lse - mean_c x[c],  #{c : x[c] > x[t]} < top_k)        fp32 [R][3], zeros for ignored rows
+ * and, summed over the rows in a fixed order in double (no atomics: the same input gives the same bits),
+ *   sums[0] = ((1 - ls) sum nll + ls sum smoothing) / count   = F.cross_entropy(ignore_index=-1, label_smoothing=ls) (gpt.py:526-531)
+ *   sums[1] = hits, sums[2] = count (hits / count = MulticlassAccuracy(top_k, average="micro", ignore_index=-1), gpt.py:166-172, 533),
+ *   sums[3] = sum nll / count.                                                          double [4], device */
+int gvc_gpt_forward_rows(gvc_gpt* ctx, const int32_t* slots, int32_t B, const float* cond, int32_t n_cond, const int32_t* text_ids,
+                         int32_t Lt, const int32_t* code_ids, int32_t Lm, const uint8_t* key_mask, float* latents_out, gvc_stream s);
+int gvc_gpt_head_xent(gvc_gpt* ctx, const float* latents, int32_t R, int32_t head, const int32_t* targets, float label_smoothing,
+                      int32_t top_k, float* logits_out, float* row_terms, double* sums, gvc_stream s);
+
 /* ------------------------------------------------------------------------------------------
  * Sampling.  Replaces the per-step body of NewGenerationMixin.sample_stream
  * (layers/stream_generator.py:834-874): RepetitionPenalty -> Temperature -> TopK -> TopP ->
@@ -884,6 +908,12 @@ int gvc_perceiver_missing_weights(gvc_perceiver* ctx);
 /* x: [B,F,dim_context] -> out [B,num_latents,dim] */
 int gvc_perceiver_forward(gvc_perceiver* ctx, const float* x, int32_t B, int32_t F, float* out,
                           gvc_stream s);
+
+/* PerceiverResampler.forward(x, mask=) (perceiver_encoder.py:265-273, Attention.forward :305-316, 130-134): key_mask uint8
+ * [B][num_latents + F] (device, nonzero = attend) over the keys [latents | frames] of every layer's cross-attention; a masked key has
+ * weight exactly 0.  The mask GPT.get_style_emb(seq_lens=) builds (gpt.py:362-367) is the caller's.  Runs uncaptured. */
+int gvc_perceiver_forward_masked(gvc_perceiver* ctx, const float* x, int32_t B, int32_t F, const uint8_t* key_mask, float* out,
+                                 gvc_stream s);
 
 /* ------------------------------------------------------------------------------------------
  * Log-mel front end.  Replaces utils.py:TorchMelSpectrogram.forward (:150-162) as instantiated at
