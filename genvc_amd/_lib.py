@@ -95,6 +95,9 @@ class DvaeDims(C.Structure):
                                          "codebook_dim", "num_tokens", "max_batch", "max_frames")]
 
 
+DVAE_DECODER = 1          # GVC_DVAE_DECODER (gvc_dvae_create_ex)
+
+
 class HifiganDims(C.Structure):
     _fields_ = [("in_dim", C.c_int32), ("up_init_ch", C.c_int32), ("n_ups", C.c_int32), ("up_rates", C.c_int32 * 4),
                 ("up_kernels", C.c_int32 * 4), ("n_kernels", C.c_int32), ("res_kernels", C.c_int32 * 4),
@@ -227,6 +230,10 @@ _SIGNATURES = {
     "gvc_dvae_missing_weights": (C.c_int, [_P]),
     "gvc_dvae_encode": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P]),
     "gvc_dvae_encode_frames": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P]),
+    "gvc_dvae_create_ex": (C.c_int, [C.POINTER(DvaeDims), C.c_int32, C.POINTER(_P)]),
+    "gvc_dvae_decode": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P]),
+    "gvc_dvae_code_error": (C.c_int, [_P, _P]),
+    "gvc_dvae_reconstruct": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "gvc_hubert_create": (C.c_int, [C.POINTER(HubertDims), C.POINTER(_P)]),
     "gvc_hubert_destroy": (C.c_int, [_P]),
     "gvc_hubert_bind_weight": (C.c_int, [_P, C.c_char_p, _P, C.c_int64, _P]),

@@ -18,6 +18,9 @@ DEFAULT_MODEL_ARGS = dict(
 # train_genVC.py:28-39
 DEFAULT_CONTENT_DVAE = dict(num_channels=256, num_tokens=256, codebook_dim=512, hidden_dim=512,
                             num_resnet_blocks=3, kernel_size=3, num_layers=2, dvae_sample_rate=16000)
+# train_genVC.py:14-25: the acoustic DVAE (mel <-> audio codes); opt-in (default_config(with_acoustic=True))
+DEFAULT_ACOUSTIC_DVAE = dict(num_channels=80, num_tokens=1024, codebook_dim=512, hidden_dim=512,
+                             num_resnet_blocks=3, kernel_size=3, num_layers=2, dvae_sample_rate=24000)
 # configs/genVC_train_configs.py:76-80
 DEFAULT_SAMPLING = dict(temperature=0.85, length_penalty=1.0, repetition_penalty=2.0, top_k=15, top_p=0.85)
 
@@ -35,6 +38,7 @@ TINY_HUBERT = dict(conv_layers=[(64, 10, 5)] + [(64, 3, 2)] * 4 + [(64, 2, 2)] *
 
 TINY_MODEL_ARGS = dict(DEFAULT_MODEL_ARGS, gpt_layers=2, gpt_n_model_channels=256, gpt_n_heads=4)
 TINY_CONTENT_DVAE = dict(DEFAULT_CONTENT_DVAE, codebook_dim=64, hidden_dim=32, num_resnet_blocks=1)
+TINY_ACOUSTIC_DVAE = dict(DEFAULT_ACOUSTIC_DVAE, codebook_dim=64, hidden_dim=32, num_resnet_blocks=1)
 
 
 def gpt_dims(model_args):
@@ -76,7 +80,9 @@ def to_attr(d):
     return d
 
 
-def default_config(tiny=False):
+def default_config(tiny=False, with_acoustic=False):
+    """with_acoustic=True adds `acoustic_dvae_config` (as a reference checkpoint's config has): GenVCModel then builds the acoustic
+    DVAE and its mel extractor (format_batch_on_device / evaluate / decode of generated codes)."""
     cfg = dict(
         model_args=copy.deepcopy(TINY_MODEL_ARGS if tiny else DEFAULT_MODEL_ARGS),
         content_dvae_config=copy.deepcopy(TINY_CONTENT_DVAE if tiny else DEFAULT_CONTENT_DVAE),
@@ -85,4 +91,6 @@ def default_config(tiny=False):
         audio=dict(sample_rate=24000),
         **DEFAULT_SAMPLING,
     )
+    if with_acoustic:
+        cfg["acoustic_dvae_config"] = copy.deepcopy(TINY_ACOUSTIC_DVAE if tiny else DEFAULT_ACOUSTIC_DVAE)
     return to_attr(cfg)

@@ -1397,14 +1397,19 @@ class MelEngine:
 
 
 class DvaeEngine:
-    """DiscreteVAE.get_codebook_indices (reference layers/dvae.py:324-331)."""
+    """DiscreteVAE.get_codebook_indices (reference layers/dvae.py:324-331); with_decoder=True: also decode (:333-352) and the
+    eval-mode forward (:363-381)."""
 
-    def __init__(self, cfg, max_batch=8, max_frames=1504):
+    def __init__(self, cfg, max_batch=8, max_frames=1504, with_decoder=False):
         self.cfg = dict(cfg)
+        self.with_decoder = bool(with_decoder)
         cd = _lib.DvaeDims(cfg["num_channels"], cfg["hidden_dim"], cfg["num_layers"], cfg["num_resnet_blocks"],
                            cfg["kernel_size"], cfg["codebook_dim"], cfg["num_tokens"], max_batch, max_frames)
         self._h = C.c_void_p()
-        check(lib().gvc_dvae_create(C.byref(cd), C.byref(self._h)), "gvc_dvae_create")
+        if self.with_decoder:
+            check(lib().gvc_dvae_create_ex(C.byref(cd), _lib.DVAE_DECODER, C.byref(self._h)), "gvc_dvae_create_ex")
+        else:
+            check(lib().gvc_dvae_create(C.byref(cd), C.byref(self._h)), "gvc_dvae_create")
 
     def close(self):
         if self._h:
@@ -1447,6 +1452,29 @@ class DvaeEngine:
         fn = lib().gvc_dvae_encode_frames if frames_major else lib().gvc_dvae_encode
         check(fn(self._h, ptr(_f32(feat)), B, T, ptr(codes), ptr(enc), stream()), "dvae_encode")
         return (codes, enc) if return_enc else codes
+
+    def decode(self, codes, return_pre=True):
+        """codes int32 [B,n] -> out [B,channels,n 2^L] (and the last layer's input [B,hidden,n 2^L]).  Synchronises to learn
+        whether a code was out of range (ValueError)."""
+        B, n = codes.shape
+        T = n << self.cfg["num_layers"]
+        codes = codes.to(torch.int32).contiguous()
+        out = torch.empty(B, self.cfg["num_channels"], T, device=codes.device, dtype=torch.float32)
+        pre = torch.empty(B, self.cfg["hidden_dim"], T, device=codes.device, dtype=torch.float32) if return_pre else None
+        check(lib().gvc_dvae_decode(self._h, ptr(codes), B, n, ptr(out), ptr(pre), stream()), "dvae_decode")
+        if lib().gvc_dvae_code_error(self._h, stream()) != 0:
+            raise ValueError(lib().gvc_last_error().decode(errors="replace"))
+        return (out, pre) if return_pre else out
+
+    def reconstruct(self, feat):
+        """feat [B,channels,T] -> (losses float32 [2] = (recon, commitment), out [B,channels,T], codes int32 [B,T / 2^L])"""
+        B, _, T = feat.shape
+        feat = _f32(feat)
+        out = torch.empty_like(feat)
+        codes = torch.empty(B, T >> self.cfg["num_layers"], device=feat.device, dtype=torch.int32)
+        losses = torch.empty(2, device=feat.device, dtype=torch.float32)
+        check(lib().gvc_dvae_reconstruct(self._h, ptr(feat), B, T, ptr(out), ptr(codes), ptr(losses), stream()), "dvae_reconstruct")
+        return losses, out, codes
 
 
 def vq_argmin(x, embed):

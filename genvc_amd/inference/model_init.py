@@ -8,6 +8,7 @@ import torch
 from torch import nn
 
 from .. import config as gcfg
+from ..engine import resample
 from ..layers.content_processor import ContentvecExtractor
 from ..layers.dvae import DiscreteVAE
 from ..layers.gpt import GPT
@@ -51,7 +52,64 @@ class GenVCModel(nn.Module):
             filter_length=2048, hop_length=256, win_length=1024, normalize=False,
             sampling_rate=config.audio.sample_rate, mel_fmin=0, mel_fmax=8000, n_mel_channels=80,
             mel_norm_file=a.get("mel_norm_file") or DEFAULT_MEL_NORM_FILE)
+        # the acoustic DVAE (trainers/gpt_trainer.py:73-99) only when the config carries one (a reference checkpoint's does;
+        # default_config(with_acoustic=True)).  Its engine is bound on first use: a model that never tokenises audio allocates nothing
+        ac = config.get("acoustic_dvae_config")
+        self.acoustic_dvae = None
+        if ac is not None:
+            self.acoustic_dvae = DiscreteVAE(channels=ac.num_channels, normalization=None, positional_dims=1, num_tokens=ac.num_tokens,
+                                             codebook_dim=ac.codebook_dim, hidden_dim=ac.hidden_dim,
+                                             num_resnet_blocks=ac.num_resnet_blocks, kernel_size=ac.kernel_size,
+                                             num_layers=ac.num_layers, use_transposed_convs=False, with_decoder=True)
+            self.acoustic_sample_rate = (ac.get("audio") or {}).get("dvae_sample_rate",
+                                                                     ac.get("dvae_sample_rate", config.audio.sample_rate))
+            self.torch_mel_spectrogram_dvae = TorchMelSpectrogram(                      # gpt_trainer.py:97-99: the class defaults
+                mel_norm_file=a.get("mel_norm_file") or DEFAULT_MEL_NORM_FILE, sampling_rate=self.acoustic_sample_rate)
         self._device = torch.device("cpu")
+
+    @torch.inference_mode()
+    def format_batch_on_device(self, batch):
+        """reference trainers/gpt_trainer.py:198-254: {"wav" [B,1,T] at config.audio.sample_rate, "wav_lengths", "conditioning"
+        [B,n_cond,1,Tc], "cond_lens", "text_lengths" (optional)} gains `cond_mels` [B,n_cond,80,.] (2048-point extractor),
+        `audio_codes` (1024-point mel -> acoustic DVAE) and `text_inputs` (resample to the content rate, right-pad
+        int(text_frame_rate * content_sample_rate) zero samples, ContentVec, content DVAE).  `text_lengths` defaults to the dataset's
+        rule (dataset.py:56,154)."""
+        if self.acoustic_dvae is None:
+            raise NotImplementedError("format_batch_on_device: the config has no acoustic_dvae_config (default_config(with_acoustic=True))")
+        sr = int(self.config.audio.sample_rate)
+        if int(self.acoustic_sample_rate) != sr:
+            raise NotImplementedError(f"format_batch_on_device: an acoustic DVAE at {self.acoustic_sample_rate} Hz for audio at {sr} Hz "
+                                      "needs the reference's Kaiser-window resampler, which is not implemented")
+        dev = self.device
+        tfr = float(self.config.get("text_frame_rate", 0.02))
+        cond = batch["conditioning"]
+        B, n_cond, C, Tc = cond.shape
+        mel = self.torch_mel_spectrogram_style_encoder(cond.reshape(B * n_cond, C, Tc).to(dev))
+        batch["cond_mels"] = mel.view(B, n_cond, mel.shape[1], mel.shape[2])
+        wav = batch["wav"].to(dev)
+        batch["audio_codes"] = self.acoustic_dvae.get_codebook_indices(self.torch_mel_spectrogram_dvae(wav))
+        content = wav.reshape(B, -1).to(torch.float32).contiguous()
+        if sr != int(self.content_sample_rate):
+            content = resample(content, sr, int(self.content_sample_rate))
+        content = torch.nn.functional.pad(content, (0, content_pad_samples(tfr, self.content_sample_rate)))
+        feat = self.content_extractor.extract_content_features(content)
+        batch["text_inputs"] = self.content_dvae.get_codebook_indices(feat.transpose(1, 2))
+        if batch.get("text_lengths") is None:
+            batch["text_lengths"] = default_text_lengths(batch["wav_lengths"], sr, tfr)
+        batch["text_lengths"] = torch.as_tensor(batch["text_lengths"]).to(torch.long)
+        return batch
+
+    @torch.inference_mode()
+    def evaluate(self, batch):
+        """the reference trainer's eval_step without its trainer (gpt_trainer.py:256-283): format_batch_on_device, then GPT.forward ->
+        {loss_text_ce, loss_mel_ce, top10acc, loss}"""
+        b = self.format_batch_on_device(batch)
+        loss_text, loss_mel, acc, _ = self.gpt(b["text_inputs"], b["text_lengths"], b["audio_codes"], b["wav_lengths"],
+                                               cond_mels=b["cond_mels"], cond_lens=b["cond_lens"])
+        a = self.config.model_args
+        # configs/genVC_configs.py:146-147
+        loss = float(a.get("gpt_loss_text_ce_weight", 0.01)) * loss_text + float(a.get("gpt_loss_mel_ce_weight", 1.0)) * loss_mel
+        return dict(loss_text_ce=loss_text, loss_mel_ce=loss_mel, top10acc=acc, loss=loss)
 
     @property
     def device(self):
@@ -216,6 +274,16 @@ class GenVCModel(nn.Module):
         return out
 
 
+def content_pad_samples(text_frame_rate, content_sample_rate):
+    """zero samples appended to the content waveform (gpt_trainer.py:240)"""
+    return int(text_frame_rate * content_sample_rate)
+
+
+def default_text_lengths(wav_lengths, sample_rate, text_frame_rate=0.02):
+    """dataset.py:56,154: wav_lengths // (int(text_frame_rate * sample_rate) * 4)"""
+    return torch.as_tensor(wav_lengths).to(torch.long) // (int(text_frame_rate * sample_rate) * 4)
+
+
 class _CondFuture:
     def __init__(self, model, audio, sr, length, chunk_length, after=None):
         if not audio.is_cuda:
@@ -273,22 +341,30 @@ def model_init(checkpoint_path, device, content_extractor=None, hifigan=None, we
     config = gcfg.default_config()
     _merge(config, ckpt["config"])
     model, finish = build_model(config, device, content_extractor, hifigan, weight_dtype=weight_dtype)
-    _load_checked(model, ckpt["model"])                                  # model_init.py:22 (strict=False)
+    model.missing_checkpoint_keys, _ = _load_checked(model, ckpt["model"])    # model_init.py:22 (strict=False)
     finish()
     print("Model initialized")
     return model, config
 
 
 @torch.inference_mode()
-def model_init_synthetic(config=None, seed=1, device="cuda", max_slots=8, weight_dtype="fp32"):
-    """No checkpoint ships with the reference: deterministic synthetic weights of the same architecture."""
+def model_init_synthetic(config=None, seed=1, device="cuda", max_slots=8, weight_dtype="fp32", with_acoustic=False):
+    """No checkpoint ships with the reference: deterministic synthetic weights of the same architecture.  with_acoustic=True (or a
+    config with `acoustic_dvae_config`): also the acoustic DVAE, its codebook at standard deviation 0.05 (at 1.0 the synthetic encoder
+    output lies far inside the codebook and a handful of codes is ever chosen)."""
     from .. import synth
-    config = config or gcfg.default_config()
+    config = config or gcfg.default_config(with_acoustic=with_acoustic)
+    if with_acoustic and config.get("acoustic_dvae_config") is None:
+        config["acoustic_dvae_config"] = gcfg.to_attr(dict(gcfg.DEFAULT_ACOUSTIC_DVAE))
     model, finish = build_model(config, device, max_slots=max_slots, weight_dtype=weight_dtype)
     dims = gcfg.gpt_dims(config.model_args)
     w = {"gpt." + k: v for k, v in synth.make_weights(seed, synth.gpt_weight_spec(dims), device=device).items()}
     w.update({"content_dvae." + k: v for k, v in
               synth.make_weights(seed, synth.dvae_weight_spec(config.content_dvae_config), device=device).items()})
+    if model.acoustic_dvae is not None:
+        w.update({"acoustic_dvae." + k: v for k, v in
+                  synth.make_weights(seed, synth.dvae_full_weight_spec(config.acoustic_dvae_config, codebook_scale=0.05),
+                                     device=device).items()})
     if model.hifigan is not None:
         w.update({"hifigan." + k: v for k, v in
                   synth.make_weights(seed, synth.hifigan_weight_spec(config.vocoder_config), device=device).items()})

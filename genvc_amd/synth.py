@@ -139,6 +139,34 @@ def dvae_weight_spec(cfg, prefix=""):
     return spec
 
 
+def dvae_full_weight_spec(cfg, prefix="", codebook_scale=1.0):
+    """The whole DiscreteVAE with use_transposed_convs=False (reference layers/dvae.py:252-295): encoder, codebook (standard
+    deviation `codebook_scale`) and decoder = 1x1 in (only with ResBlocks), ResBlocks, UpsampledConv stages, 1x1 out."""
+    spec = dvae_weight_spec(cfg, prefix)
+    spec[f"{prefix}codebook.embed"] = (spec[f"{prefix}codebook.embed"][0], ("codebook_scaled", float(codebook_scale)))
+    hid, nl, k, nr = cfg["hidden_dim"], cfg["num_layers"], cfg["kernel_size"], cfg["num_resnet_blocks"]
+    inner = hid * 2 ** (nl - 1)
+    idx, cin = 0, cfg["codebook_dim"]
+
+    def conv(name, cout, cin, kk):
+        spec[f"{prefix}decoder.{name}.weight"] = ((cout, cin, kk), "conv")
+        spec[f"{prefix}decoder.{name}.bias"] = ((cout,), "bias")
+
+    if nr > 0:
+        conv("0", inner, cin, 1)
+        idx, cin = 1, inner
+    for _ in range(nr):
+        for j, kk in ((0, 3), (2, 3), (4, 1)):
+            conv(f"{idx}.net.{j}", cin, cin, kk)
+        idx += 1
+    for i in range(nl):
+        cout = hid * 2 ** (nl - 1 - i)
+        conv(f"{idx}.0.conv", cout, cin, k)
+        idx, cin = idx + 1, cout
+    conv(str(idx), cfg["num_channels"], cin, 1)
+    return spec
+
+
 def hifigan_weight_spec(cfg, prefix=""):
     """HiFi-GAN generator with weight-norm parametrisation, named as the reference state dict
     (reference layers/hifigan.py:160-216): conv_pre, ups.{i}, resblocks.{i*nk+j}.convs.{0,1}, conv_post."""
@@ -199,6 +227,8 @@ def make_weights(seed, spec, device="cpu", head_scale=0.05):
     for name, (shape, kind) in spec.items():
         if isinstance(kind, tuple) and kind[0] == "wn_g":
             out[name] = uniform(seed, name, shape, 0.1 * kind[1], kind[1], device)
+        elif isinstance(kind, tuple) and kind[0] == "codebook_scaled":
+            out[name] = uniform(seed, name, shape, kind[1], 0.0, device)
         elif kind == "ln_w":
             out[name] = uniform(seed, name, shape, 0.1, 1.0, device)
         elif kind in ("ln_b", "bias"):

@@ -952,6 +952,24 @@ int gvc_dvae_encode(gvc_dvae* ctx, const float* feat, int32_t B, int32_t T, int3
  * `get_codebook_indices(content_feat.transpose(1, 2))` (inference/inference_utils.py:53,167) without the transpose */
 int gvc_dvae_encode_frames(gvc_dvae* ctx, const float* feat, int32_t B, int32_t T, int32_t* codes_out,
                            float* enc_out, gvc_stream s);
+/* The whole DiscreteVAE: a context created with GVC_DVAE_DECODER also binds the reference's `decoder.*` tensors
+ * ("decoder.0.weight", "decoder.1.net.0.weight", "decoder.4.0.conv.weight", "decoder.6.bias", ...: layers/dvae.py:252-292 with
+ * use_transposed_convs=False) and counts them in gvc_dvae_missing_weights; flags = 0 is gvc_dvae_create.  Each nearest-x2
+ * upsampling + Conv1d stage is folded at bind time into two polyphase weight sets applied at the input rate. */
+#define GVC_DVAE_DECODER 1
+int gvc_dvae_create_ex(const gvc_dvae_dims* dims, int32_t flags, gvc_dvae** out);
+/* DiscreteVAE.decode (:333-352): codes int32 [B,n] -> out [B,channels,n*2^num_layers]; pre_out (may be NULL) receives the last
+ * layer's input [B,hidden_dim,n*2^num_layers].  Asynchronous, no allocation.  A code outside [0, num_tokens) is replaced by code 0
+ * and remembered: the next gvc_dvae_code_error reports it. */
+int gvc_dvae_decode(gvc_dvae* ctx, const int32_t* codes, int32_t B, int32_t n, float* out, float* pre_out, gvc_stream s);
+/* synchronises the stream; GVC_ERR_ARG (and the mark is cleared) when a decode since the last call met a code out of range */
+int gvc_dvae_code_error(gvc_dvae* ctx, gvc_stream s);
+/* DiscreteVAE.forward in eval mode (:363-381): feat [B,channels,T], T a multiple of 2^num_layers -> out [B,channels,T],
+ * codes_out (may be NULL) int32 [B,T/2^num_layers], losses (device) float[2] = mse(feat, out), mean((embed_code(codes) -
+ * encoder(feat))^2).  Both sums are reduced in a fixed order (per-workgroup partials, then one workgroup in double): the same
+ * bits every call. */
+int gvc_dvae_reconstruct(gvc_dvae* ctx, const float* feat, int32_t B, int32_t T, float* out, int32_t* codes_out,
+                         float* losses, gvc_stream s);
 /* standalone VQ: x [N,dim], embed [dim,n_embed] (reference layout) -> idx int32 [N] */
 int gvc_vq_argmin(const float* x, const float* embed, int32_t N, int32_t dim, int32_t n_embed,
                   int32_t* idx, float* work /* N*n_embed floats */, gvc_stream s);

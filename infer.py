@@ -2,7 +2,8 @@
 
 Flags and defaults are the reference's; added: --seg_len (the reference hard-codes 6.0; the README's
 "1-second chunk" numbers correspond to --seg_len 1.0), --stream_chunk_size, --synthetic (no checkpoint
-ships with the reference: run the same pipeline on deterministic synthetic weights), --save_tokens and --token_scores.
+ships with the reference: run the same pipeline on deterministic synthetic weights), --save_tokens, --token_scores and
+--decode_codes_to_mel (the acoustic DVAE's mel of the generated codes).
 The waveform is written like the reference does (24 kHz PCM16); --save_tokens also stores the codec tokens/latents.
 """
 import argparse
@@ -81,7 +82,12 @@ if __name__ == "__main__":
                              "no draft model, so it runs on a real checkpoint; greedy, or sampled with --assistant_sampling")
     parser.add_argument("--max_matching_ngram_size", type=int, default=None, metavar="N",
                         help="with --prompt_lookup_num_tokens: the longest run of last codes searched for, 1..8 (default 2)")
+    parser.add_argument("--decode_codes_to_mel", type=str, default=None, metavar="PATH.npy",
+                        help="non-streaming only: write the acoustic DVAE's mel [80, 4 x codes] of the generated codes, the segments one after "
+                             "the other; needs a checkpoint with acoustic_dvae.* tensors (and an acoustic_dvae_config), or --synthetic")
     args = parser.parse_args()
+    if args.decode_codes_to_mel is not None and (args.streaming or args.num_return_sequences != 1):
+        raise SystemExit("--decode_codes_to_mel is not on the streaming path (--streaming) and does not combine with --num_return_sequences")
     if args.max_matching_ngram_size is not None and args.prompt_lookup_num_tokens is None:
         raise SystemExit("--max_matching_ngram_size needs --prompt_lookup_num_tokens")
     if args.prompt_lookup_num_tokens is not None:
@@ -187,9 +193,13 @@ if __name__ == "__main__":
 
     if args.synthetic:
         from genvc_amd import config as gcfg
-        model, config = model_init_synthetic(gcfg.default_config(tiny=args.tiny), device=args.device, weight_dtype=args.weights)
+        model, config = model_init_synthetic(gcfg.default_config(tiny=args.tiny, with_acoustic=args.decode_codes_to_mel is not None),
+                                             device=args.device, weight_dtype=args.weights)
     else:
         model, config = model_init(args.model_path, args.device, weight_dtype=args.weights)
+        if args.decode_codes_to_mel is not None and (model.acoustic_dvae is None or any(
+                k.startswith("acoustic_dvae.") for k in model.missing_checkpoint_keys)):
+            raise SystemExit("--decode_codes_to_mel: the checkpoint has no acoustic DVAE (acoustic_dvae_config and acoustic_dvae.* tensors)")
     model.config.top_k = args.top_k
     if args.forced_eos:
         gen_kw["forced_eos_token_id"] = model.gpt.stop_audio_token      # (the flags were validated above against the default vocabulary)
@@ -259,6 +269,15 @@ if __name__ == "__main__":
                          **{f"logprobs_{i}": lp.cpu().numpy() for i, lp in enumerate(out["token_logprobs"])})
                 print(f"{args.token_scores}: tokens and log-probabilities of {len(out['codes'])} segments")
         print(f"generated {toks.shape[-1]} codec tokens, latents {tuple(lat.shape)}")
+        if args.decode_codes_to_mel is not None:
+            import numpy as np
+            dv = model.acoustic_dvae
+            segs = [c[c < dv.num_tokens] for c in out["codes"]]
+            segs = [c for c in segs if c.numel()]
+            dv.bind(max_batch=1, max_frames=4 * max([int(c.numel()) for c in segs] + [1]))
+            mels = [dv.decode(c.unsqueeze(0))[0][0].cpu().numpy() for c in segs]
+            np.save(args.decode_codes_to_mel, np.concatenate(mels, axis=1) if mels else np.zeros((80, 0), np.float32))
+            print(f"{args.decode_codes_to_mel}: acoustic-DVAE mel, frames per segment {[m.shape[1] for m in mels]}")
         if args.assistant_layers is not None:
             st = model.gpt.last_assist_stats
             print(f"assisted decoding, last segment: {int(st['rounds'].sum())} rounds, {int(st['accepted'].sum())} of "
