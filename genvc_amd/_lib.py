@@ -98,6 +98,22 @@ class DvaeDims(C.Structure):
 DVAE_DECODER = 1          # GVC_DVAE_DECODER (gvc_dvae_create_ex)
 
 
+class DiscDims(C.Structure):
+    """gvc_disc_dims (include/genvc_hip.h): one waveform-domain discriminator (MSD or MPD)"""
+    _fields_ = [("kind", C.c_int32), ("n_sub", C.c_int32), ("periods", C.c_int32 * 8), ("channels", C.c_int32 * 5),
+                ("spectral_norm", C.c_int32), ("max_batch", C.c_int32), ("max_samples", C.c_int32)]
+
+
+DISC_MSD, DISC_MPD = 0, 1                                        # GVC_DISC_MSD, GVC_DISC_MPD
+MEL_SLANEY_SCALE, MEL_MAGNITUDE, MEL_PAD_HALF_OVERLAP = 1, 2, 4  # GVC_MEL_* (gvc_mel_create_ex)
+
+
+class MelOptions(C.Structure):
+    """gvc_mel_options (include/genvc_hip.h)"""
+    _fields_ = [(n, C.c_int32) for n in ("n_fft", "hop", "win", "sample_rate", "n_mels", "flags")] + \
+        [("f_min", C.c_float), ("f_max", C.c_float), ("mel_norms_host", C.POINTER(C.c_float))]
+
+
 class HifiganDims(C.Structure):
     _fields_ = [("in_dim", C.c_int32), ("up_init_ch", C.c_int32), ("n_ups", C.c_int32), ("up_rates", C.c_int32 * 4),
                 ("up_kernels", C.c_int32 * 4), ("n_kernels", C.c_int32), ("res_kernels", C.c_int32 * 4),
@@ -224,6 +240,20 @@ _SIGNATURES = {
                                  c_f32p, C.POINTER(_P)]),
     "gvc_mel_destroy": (C.c_int, [_P]),
     "gvc_mel_forward": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P]),
+    "gvc_mel_create_ex": (C.c_int, [C.POINTER(MelOptions), C.POINTER(_P)]),
+    "gvc_mel_frames": (C.c_int, [_P, C.c_int32]),
+    "gvc_disc_create": (C.c_int, [C.POINTER(DiscDims), C.POINTER(_P)]),
+    "gvc_disc_destroy": (C.c_int, [_P]),
+    "gvc_disc_bind_weight": (C.c_int, [_P, C.c_char_p, _P, C.c_int64, _P]),
+    "gvc_disc_missing_weights": (C.c_int, [_P]),
+    "gvc_disc_folded_weight": (C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_int64, _P]),
+    "gvc_disc_arena_floats": (C.c_int64, [_P]),
+    "gvc_disc_set_arena": (C.c_int, [_P, _P]),
+    "gvc_disc_layers": (C.c_int, [_P]),
+    "gvc_disc_layer": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64), c_i32p, c_i32p, c_i32p]),
+    "gvc_disc_forward": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P, _P]),
+    "gvc_disc_time_layer": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_f32p, _P]),
+    "gvc_l1_mean": (C.c_int, [_P, _P, C.c_int64, C.c_float, _P, _P, _P]),
     "gvc_dvae_create": (C.c_int, [C.POINTER(DvaeDims), C.POINTER(_P)]),
     "gvc_dvae_destroy": (C.c_int, [_P]),
     "gvc_dvae_bind_weight": (C.c_int, [_P, C.c_char_p, _P, C.c_int64, _P]),

@@ -24,11 +24,13 @@ DEFAULT_ACOUSTIC_DVAE = dict(num_channels=80, num_tokens=1024, codebook_dim=512,
 # configs/genVC_train_configs.py:76-80
 DEFAULT_SAMPLING = dict(temperature=0.85, length_penalty=1.0, repetition_penalty=2.0, top_k=15, top_p=0.85)
 
-# configs/vocoder_configs.py:7-20 (HiFi-GAN generator, ResBlock2)
+# configs/vocoder_configs.py:7-24 (HiFi-GAN generator, ResBlock2; the mel loss's extractor :8-14; the MPD :22-24)
 DEFAULT_VOCODER = dict(input_feat_dim=1024, upsample_initial_channel=256, resblock_kernel_sizes=[3, 5, 7],
                        resblock_dilation_sizes=[[1, 2], [2, 6], [3, 12]], upsample_rates=[8, 8, 4],
-                       upsample_kernel_sizes=[16, 16, 8], resblock_type="2", hop_length=256)
-TINY_VOCODER = dict(DEFAULT_VOCODER, input_feat_dim=256, upsample_initial_channel=64)
+                       upsample_kernel_sizes=[16, 16, 8], resblock_type="2", hop_length=256,
+                       sample_rate=24000, fft_size=1024, num_mels=100, mel_fmin=0, mel_fmax=12000, win_length=1024,
+                       mpd_reshapes=[2, 3, 5, 7, 11], mpd_discriminator_channel_mult_factor=1, mpd_use_spectral_norm=False)
+TINY_VOCODER = dict(DEFAULT_VOCODER, input_feat_dim=256, upsample_initial_channel=64, mpd_discriminator_channel_mult_factor=0.25)
 
 # HuBERT-base / ContentVec (fairseq HubertModel): conv extractor (dim, kernel, stride), post-LN encoder
 DEFAULT_HUBERT = dict(conv_layers=[(512, 10, 5)] + [(512, 3, 2)] * 4 + [(512, 2, 2)] * 2, embed_dim=768, layers=12, heads=12,

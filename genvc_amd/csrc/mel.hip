@@ -17,6 +17,7 @@ namespace gvc {
 
 struct MelDev {
     int n_fft, log2n, hop, win, n_mels, n_bins;
+    int pad, magnitude;       // reflect padding per side; 1: sqrt(|X|^2 + 1e-9) instead of |X|^2 (gvc_mel_create_ex)
     const float* window;      // [win]
     const float2* twiddle;    // [n_fft/2]  exp(-2 pi i k / n_fft)
     const int* fb_lo;         // [n_mels] first bin of the filter
@@ -33,7 +34,7 @@ __global__ __launch_bounds__(256) void k_mel(const MelDev M, const float* wav, i
     float* im = lds + M.n_fft;
     const int frame = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
     const float* x = wav + (size_t)b * T;
-    const int pad = M.n_fft / 2;
+    const int pad = M.pad;
     const int woff = (M.n_fft - M.win) / 2;
 
     // windowed, reflect-padded frame, stored at the bit-reversed index
@@ -73,7 +74,8 @@ __global__ __launch_bounds__(256) void k_mel(const MelDev M, const float* wav, i
     // power spectrum of the one-sided bins, in place (re[k] <- |X_k|^2)
     for (int k = tid; k < M.n_bins; k += 256) {
         const float a = re[k], c = im[k];
-        re[k] = a * a + c * c;
+        const float p = a * a + c * c;
+        re[k] = M.magnitude ? sqrtf(p + 1e-9f) : p;
     }
     __syncthreads();
     if (tid < M.n_mels) {
@@ -96,9 +98,8 @@ struct gvc_mel {
     void* blob = nullptr;
 };
 
-extern "C" int gvc_mel_create(int32_t n_fft, int32_t hop, int32_t win, int32_t sample_rate, float f_min, float f_max,
-                              int32_t n_mels, const float* mel_norms_host, gvc_mel** out) {
-    GVC_REQUIRE(out && mel_norms_host, GVC_ERR_ARG, "gvc_mel_create: null argument");
+static int mel_create(int32_t n_fft, int32_t hop, int32_t win, int32_t sample_rate, float f_min, float f_max, int32_t n_mels,
+                      const float* mel_norms_host, int32_t flags, gvc_mel** out) {
     int log2n = 0;
     while ((1 << log2n) < n_fft) ++log2n;
     GVC_REQUIRE((1 << log2n) == n_fft && n_fft >= 64 && n_fft <= 8192 && win <= n_fft && hop >= 1 && n_mels <= 256,
@@ -113,8 +114,17 @@ extern "C" int gvc_mel_create(int32_t n_fft, int32_t hop, int32_t win, int32_t s
         tw[2 * k + 1] = (float)sin(-2.0 * M_PI * k / n_fft);
     }
     // torchaudio.functional.melscale_fbanks(norm="slaney", mel_scale="htk")
-    auto hz2mel = [](double f) { return 2595.0 * log10(1.0 + f / 700.0); };
-    auto mel2hz = [](double m) { return 700.0 * (pow(10.0, m / 2595.0) - 1.0); };
+    // GVC_MEL_SLANEY_SCALE: librosa.filters.mel(htk=False), 200/3 Hz per mel below 1 kHz, log steps of ln(6.4)/27 above
+    const bool slaney = (flags & GVC_MEL_SLANEY_SCALE) != 0;
+    const double f_sp = 200.0 / 3.0, min_log_mel = 1000.0 / f_sp, logstep = log(6.4) / 27.0;
+    auto hz2mel = [=](double f) {
+        if (!slaney) return 2595.0 * log10(1.0 + f / 700.0);
+        return f >= 1000.0 ? min_log_mel + log(f / 1000.0) / logstep : f / f_sp;
+    };
+    auto mel2hz = [=](double m) {
+        if (!slaney) return 700.0 * (pow(10.0, m / 2595.0) - 1.0);
+        return m >= min_log_mel ? 1000.0 * exp(logstep * (m - min_log_mel)) : f_sp * m;
+    };
     std::vector<double> fpts(n_mels + 2);
     const double m_lo = hz2mel(f_min), m_hi = hz2mel(f_max);
     for (int i = 0; i < n_mels + 2; ++i) fpts[i] = mel2hz(m_lo + (m_hi - m_lo) * i / (n_mels + 1));
@@ -125,7 +135,7 @@ extern "C" int gvc_mel_create(int32_t n_fft, int32_t hop, int32_t win, int32_t s
         int first = -1, last = -1;
         std::vector<float> row(n_bins);
         for (int k = 0; k < n_bins; ++k) {
-            const double f = (double)(sample_rate / 2) * k / (n_bins - 1);
+            const double f = (slaney ? sample_rate / 2.0 : (double)(sample_rate / 2)) * k / (n_bins - 1);
             const double down = (f - fpts[m]) / (fpts[m + 1] - fpts[m]);
             const double up = (fpts[m + 2] - f) / (fpts[m + 2] - fpts[m + 1]);
             const double v = fmax(0.0, fmin(down, up)) * enorm;
@@ -149,13 +159,16 @@ extern "C" int gvc_mel_create(int32_t n_fft, int32_t hop, int32_t win, int32_t s
     memcpy(&host[o_len], len.data(), n_mels * 4);
     memcpy(&host[o_off], off.data(), n_mels * 4);
     memcpy(&host[o_w], wts.data(), wts.size() * 4);
-    memcpy(&host[o_nrm], mel_norms_host, n_mels * 4);
+    if (mel_norms_host) memcpy(&host[o_nrm], mel_norms_host, n_mels * 4);
+    else for (int m = 0; m < n_mels; ++m) reinterpret_cast<float*>(&host[o_nrm])[m] = 1.0f;     // (x / 1 is exact)
     auto* c = new gvc_mel();
     GVC_CHECK_HIP(hipMalloc(&c->blob, total));
     GVC_CHECK_HIP(hipMemcpy(c->blob, host.data(), total, hipMemcpyHostToDevice));
     char* base = (char*)c->blob;
     c->dev.n_fft = n_fft; c->dev.log2n = log2n; c->dev.hop = hop; c->dev.win = win; c->dev.n_mels = n_mels;
     c->dev.n_bins = n_bins;
+    c->dev.pad = (flags & GVC_MEL_PAD_HALF_OVERLAP) ? (n_fft - hop) / 2 : n_fft / 2;
+    c->dev.magnitude = (flags & GVC_MEL_MAGNITUDE) ? 1 : 0;
     c->dev.window = (const float*)(base + o_win); c->dev.twiddle = (const float2*)(base + o_tw);
     c->dev.fb_lo = (const int*)(base + o_lo); c->dev.fb_len = (const int*)(base + o_len);
     c->dev.fb_off = (const int*)(base + o_off); c->dev.fb_w = (const float*)(base + o_w);
@@ -163,6 +176,25 @@ extern "C" int gvc_mel_create(int32_t n_fft, int32_t hop, int32_t win, int32_t s
     *out = c;
     return GVC_OK;
 }
+
+extern "C" int gvc_mel_create(int32_t n_fft, int32_t hop, int32_t win, int32_t sample_rate, float f_min, float f_max,
+                              int32_t n_mels, const float* mel_norms_host, gvc_mel** out) {
+    GVC_REQUIRE(out && mel_norms_host, GVC_ERR_ARG, "gvc_mel_create: null argument");
+    return mel_create(n_fft, hop, win, sample_rate, f_min, f_max, n_mels, mel_norms_host, 0, out);
+}
+
+extern "C" int gvc_mel_create_ex(const gvc_mel_options* o, gvc_mel** out) {
+    GVC_REQUIRE(o && out, GVC_ERR_ARG, "gvc_mel_create_ex: null argument");
+    GVC_REQUIRE((o->flags & ~(GVC_MEL_SLANEY_SCALE | GVC_MEL_MAGNITUDE | GVC_MEL_PAD_HALF_OVERLAP)) == 0, GVC_ERR_ARG,
+                "gvc_mel_create_ex: unknown flags %d", o->flags);
+    GVC_REQUIRE(o->hop <= o->n_fft && o->n_mels >= 1 && o->f_max > o->f_min, GVC_ERR_ARG, "gvc_mel_create_ex: bad hop / n_mels / band");
+    return mel_create(o->n_fft, o->hop, o->win, o->sample_rate, o->f_min, o->f_max, o->n_mels, o->mel_norms_host, o->flags, out);
+}
+
+// frames of T samples: the padded signal has T + 2 pad samples, a frame every hop
+static int mel_frames(const gvc_mel* c, int T) { return T <= c->dev.pad ? 0 : 1 + (T + 2 * c->dev.pad - c->dev.n_fft) / c->dev.hop; }
+
+extern "C" int gvc_mel_frames(gvc_mel* c, int32_t T) { return c ? mel_frames(c, T) : -1; }
 
 extern "C" int gvc_mel_destroy(gvc_mel* c) {
     if (!c) return GVC_OK;
@@ -174,9 +206,8 @@ extern "C" int gvc_mel_destroy(gvc_mel* c) {
 extern "C" int gvc_mel_forward(gvc_mel* c, const float* wav, int32_t B, int32_t T, float* out, float* out_fm,
                                gvc_stream sv) {
     GVC_REQUIRE(c && wav && out && B >= 1, GVC_ERR_ARG, "gvc_mel_forward: bad argument");
-    GVC_REQUIRE(T > c->dev.n_fft / 2, GVC_ERR_ARG, "mel: %d samples are too few for reflect padding of %d", T,
-                c->dev.n_fft / 2);
-    const int n_frames = 1 + T / c->dev.hop;
+    GVC_REQUIRE(T > c->dev.pad, GVC_ERR_ARG, "mel: %d samples are too few for reflect padding of %d", T, c->dev.pad);
+    const int n_frames = mel_frames(c, T);
     const size_t lds = 2 * (size_t)c->dev.n_fft * sizeof(float);
     hipLaunchKernelGGL(k_mel, dim3(n_frames, B), dim3(256), lds, (hipStream_t)sv, c->dev, wav, T, n_frames, out, out_fm);
     GVC_LAUNCH_CHECK();

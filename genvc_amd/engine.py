@@ -1557,6 +1557,144 @@ class HifiganEngine:
         return wav
 
 
+def mpd_channels(mult):
+    """DiscriminatorP's channel widths (reference layers/hifigan.py:327-363: int(32 m), int(128 m), int(512 m), int(1024 m) twice)"""
+    return [int(32 * mult), int(128 * mult), int(512 * mult), int(1024 * mult), int(1024 * mult)]
+
+
+class DiscriminatorEngine:
+    """MultiScaleDiscriminator / MultiPeriodDiscriminator.forward in eval mode (reference layers/hifigan.py:281-314, :399-426) with
+    the reductions of the criteria (layers/hifigan_loss.py:78-123) in the same call.  fp32; the feature maps live in an arena
+    tensor this object owns and are overwritten by the next forward."""
+
+    def __init__(self, kind, periods=(), mult=1.0, spectral_norm=False, max_batch=2, max_samples=24000):
+        if kind not in ("MSD", "MPD"):
+            raise NotImplementedError(f"discriminator {kind!r} is not served (MSD and MPD are)")
+        d = _lib.DiscDims()
+        d.kind = _lib.DISC_MSD if kind == "MSD" else _lib.DISC_MPD
+        self.kind, self.periods = kind, [int(p) for p in periods]
+        if kind == "MPD":
+            if not 1 <= len(self.periods) <= 8:
+                raise ValueError(f"MPD: {len(self.periods)} periods (1..8 are supported)")
+            d.n_sub = len(self.periods)
+            for i, p in enumerate(self.periods):
+                d.periods[i] = p
+            for i, ch in enumerate(mpd_channels(mult)):
+                d.channels[i] = ch
+            d.spectral_norm = int(bool(spectral_norm))
+        else:
+            d.n_sub = 3
+        d.max_batch, d.max_samples = max_batch, max_samples
+        self.n_sub = d.n_sub
+        self.max_batch, self.max_samples = max_batch, max_samples
+        self._h = C.c_void_p()
+        self._arena = None
+        check(lib().gvc_disc_create(C.byref(d), C.byref(self._h)), "gvc_disc_create")
+        self.n_layers = lib().gvc_disc_layers(self._h)
+        self._arena = torch.empty(lib().gvc_disc_arena_floats(self._h), device="cuda", dtype=torch.float32)
+        check(lib().gvc_disc_set_arena(self._h, ptr(self._arena)), "gvc_disc_set_arena")
+
+    def close(self):
+        if self._h:
+            lib().gvc_disc_destroy(self._h)
+            self._h = C.c_void_p()
+        self._arena = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def bind(self, weights, prefix=""):
+        """weights: reference state dict (weight_g / weight_v / bias, or weight_orig / weight_u / weight_v / bias); both
+        parametrisations are folded by the library"""
+        for name, t in weights.items():
+            if not name.startswith(prefix) or not torch.is_tensor(t) or not t.is_floating_point():
+                continue
+            t = _f32(t.detach().to(torch.float32).contiguous())
+            check(lib().gvc_disc_bind_weight(self._h, name[len(prefix):].encode(), ptr(t), t.numel(), stream()), f"bind {name}")
+        torch.cuda.current_stream().synchronize()
+        missing = lib().gvc_disc_missing_weights(self._h)
+        if missing:
+            raise _lib.GenvcHipError(f"{missing} discriminator weight tensors missing after bind")
+
+    def folded_weight(self, sub, layer, shape):
+        out = torch.empty(*shape, device="cuda", dtype=torch.float32)
+        check(lib().gvc_disc_folded_weight(self._h, sub, layer, ptr(out), out.numel(), stream()), "disc_folded_weight")
+        return out
+
+    def layer(self, sub, layer, B, T):
+        """the feature map of one layer after a forward at (B, T): a view [2 B, C, H, W] of the arena"""
+        off, c, h, w = C.c_int64(), C.c_int32(), C.c_int32(), C.c_int32()
+        check(lib().gvc_disc_layer(self._h, sub, layer, B, T, C.byref(off), C.byref(c), C.byref(h), C.byref(w)), "disc_layer")
+        n = 2 * B * c.value * h.value * w.value
+        return self._arena[off.value:off.value + n].view(2 * B, c.value, h.value, w.value)
+
+    def forward(self, y, y_hat):
+        """y, y_hat [B,T] -> stats float32 [n_sub, 3 + n_layers]: mean((1 - d_r)^2), mean(d_g^2), mean((1 - d_g)^2), then
+        mean|f_r - f_g| per layer; the feature maps are read with layer()"""
+        B, T = y.shape
+        if tuple(y_hat.shape) != (B, T):
+            raise ValueError(f"discriminator: y {tuple(y.shape)} and y_hat {tuple(y_hat.shape)} differ in shape")
+        stats = torch.empty(self.n_sub, 3 + self.n_layers, device=y.device, dtype=torch.float32)
+        check(lib().gvc_disc_forward(self._h, ptr(_f32(y)), ptr(_f32(y_hat)), B, T, ptr(stats), stream()), "disc_forward")
+        return stats
+
+
+    def time_layer(self, sub, layer, B, T, iters=20):
+        """microseconds per launch of one layer alone (measurement; run a forward at (B, T) first)"""
+        us = C.c_float()
+        check(lib().gvc_disc_time_layer(self._h, sub, layer, B, T, iters, C.byref(us), stream()), "disc_time_layer")
+        return us.value
+
+
+def l1_mean(a, b, scale=1.0):
+    """scale * mean|a - b| as a 0-d device tensor, reduced in a fixed order (the same input gives the same bits)"""
+    if a.shape != b.shape:
+        raise ValueError(f"l1_mean: shapes {tuple(a.shape)} and {tuple(b.shape)} differ")
+    a, b = _f32(a), _f32(b)
+    out = torch.empty(1, device=a.device, dtype=torch.float32)
+    work = torch.empty(256, device=a.device, dtype=torch.float64)
+    check(lib().gvc_l1_mean(ptr(a), ptr(b), a.numel(), float(scale), ptr(out), ptr(work), stream()), "l1_mean")
+    return out[0]
+
+
+class MelLossEngine:
+    """extract_mel_features of the reference's layers/hifigan_loss.py:16-75: reflect padding of (fft_size - hop) / 2 with
+    center=False, magnitude sqrt(re^2 + im^2 + 1e-9), librosa's default (Slaney) filterbank, log(clamp(., 1e-5))."""
+
+    def __init__(self, sample_rate=24000, fft_size=1024, num_mels=100, mel_fmin=0, mel_fmax=12000, win_length=1024, hop_length=256):
+        o = _lib.MelOptions()
+        o.n_fft, o.hop, o.win, o.sample_rate, o.n_mels = fft_size, hop_length, win_length, sample_rate, num_mels
+        o.flags = _lib.MEL_SLANEY_SCALE | _lib.MEL_MAGNITUDE | _lib.MEL_PAD_HALF_OVERLAP
+        o.f_min, o.f_max = float(mel_fmin), float(mel_fmax if mel_fmax is not None else sample_rate / 2.0)
+        self.n_mels, self.pad = num_mels, (fft_size - hop_length) // 2
+        self._h = C.c_void_p()
+        check(lib().gvc_mel_create_ex(C.byref(o), C.byref(self._h)), "gvc_mel_create_ex")
+
+    def close(self):
+        if self._h:
+            lib().gvc_mel_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def forward(self, wav):
+        """wav [B,T] -> [B,n_mels,T // hop]; ValueError when T does not exceed the reflect padding"""
+        B, T = wav.shape
+        if T <= self.pad:
+            raise ValueError(f"mel loss: {T} samples are too few for reflect padding of {self.pad}")
+        nf = lib().gvc_mel_frames(self._h, T)
+        out = torch.empty(B, self.n_mels, nf, device=wav.device, dtype=torch.float32)
+        check(lib().gvc_mel_forward(self._h, ptr(_f32(wav)), B, T, ptr(out), None, stream()), "mel_forward")
+        return out
+
+
 class HubertEngine:
     """ContentVecExtractor.extract_content_features (reference layers/content_processor.py:17-31): HuBERT-base
     extract_features(output_layer=n_layers) + final_proj, weights under fairseq's names."""

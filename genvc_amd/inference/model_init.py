@@ -111,6 +111,78 @@ class GenVCModel(nn.Module):
         loss = float(a.get("gpt_loss_text_ce_weight", 0.01)) * loss_text + float(a.get("gpt_loss_mel_ce_weight", 1.0)) * loss_mel
         return dict(loss_text_ce=loss_text, loss_mel_ce=loss_mel, top10acc=acc, loss=loss)
 
+    @torch.inference_mode()
+    def format_vocoder_batch_on_device(self, batch):
+        """reference trainers/hifigan_trainer.py:268-344: format_batch_on_device, then `wav_lengths += gpt_code_stride_len // 2`,
+        `mel_latents` [B,n,d] = GPT.forward(..., return_latent=True) and `wav` zero-padded or cut to n_codes * gpt_code_stride_len;
+        the tensors only the GPT needed are dropped from the batch"""
+        b = self.format_batch_on_device(batch)
+        dev = self.device
+        stride = int(self.config.model_args.gpt_code_stride_len)
+        b["wav_lengths"] = torch.as_tensor(b["wav_lengths"]).to(dev) + stride // 2
+        b["mel_latents"] = self.gpt(b["text_inputs"], b["text_lengths"], b["audio_codes"], b["wav_lengths"], cond_mels=b["cond_mels"],
+                                    cond_lens=b["cond_lens"], return_latent=True)
+        want = int(b["audio_codes"].shape[1]) * stride
+        wav = b["wav"].to(dev)
+        b["wav"] = torch.nn.functional.pad(wav, (0, max(0, want - wav.shape[-1])))[:, :, :want].contiguous()
+        for k in ("cond_mels", "cond_lens", "audio_codes", "text_lengths", "text_inputs", "conditioning"):
+            b.pop(k, None)
+        return b
+
+    SERVED_DISCRIMINATORS = ("MSD", "MPD")
+
+    def _vocoder_discriminator(self, key):
+        """the discriminators of hifigan_trainer.py:57-71 that this build serves, created on first use (under the state-dict prefix
+        `hifigan_discriminator.{key}.`, as the trainer's ModuleDict names them) and put in eval mode"""
+        if key in ("MSTFT", "MSCQT"):
+            raise NotImplementedError(f"discriminator {key} is not served (MSD and MPD are): it needs a spectrogram / CQT front end "
+                                      "and 2-D convolutions")
+        if key not in self.SERVED_DISCRIMINATORS:
+            raise NotImplementedError(f"unknown discriminator {key!r} (MSD and MPD are served)")
+        if not hasattr(self, "hifigan_discriminator"):
+            self.hifigan_discriminator = nn.ModuleDict()
+        if key not in self.hifigan_discriminator:
+            from ..layers.hifigan import MultiPeriodDiscriminator, MultiScaleDiscriminator
+            v = self.config.get("vocoder_config") or {}
+            d = MultiScaleDiscriminator() if key == "MSD" else MultiPeriodDiscriminator(
+                v.get("mpd_reshapes", [2, 3, 5, 7, 11]), v.get("mpd_discriminator_channel_mult_factor", 1), v.get("mpd_use_spectral_norm", False))
+            self.hifigan_discriminator[key] = d.to(self.device).eval()
+        return self.hifigan_discriminator[key]
+
+    @torch.inference_mode()
+    def evaluate_vocoder(self, batch, discriminators=("MSD", "MPD"), return_audio=False):
+        """the vocoder trainer's eval_step without its trainer (hifigan_trainer.py:346-385): format_vocoder_batch_on_device, the latents
+        interpolated x hifigan_scale_factor, the generator, then per discriminator discriminator_criterion on (wav, generated) and the
+        mel loss -> {"loss_disc", "mel_loss", "{key}_Discriminator_loss" per discriminator, "discriminators"} as Python floats.
+        The reference's trainer sums FOUR discriminators into loss_disc (MSD, MPD, MSTFT, MSCQT); this build serves the two
+        waveform-domain ones, "discriminators" names what the sum covers, and asking for "MSTFT" / "MSCQT" raises.
+        return_audio=True adds "audio_gt" and "audio_pred" [B,1,T]."""
+        from ..layers.hifigan_loss import discriminator_criterion, mel_criterion
+        keys = tuple(discriminators)
+        models = [self._vocoder_discriminator(k) for k in keys]
+        if self.hifigan is None:
+            raise NotImplementedError("evaluate_vocoder: the config has no vocoder_config")
+        b = self.format_vocoder_batch_on_device(batch)
+        audio_gt = b["wav"].to(torch.float32)
+        audio_pred = self.hifigan.forward_latents(b["mel_latents"], int(self.hifigan_scale_factor))
+        if audio_pred.shape != audio_gt.shape:
+            raise ValueError(f"evaluate_vocoder: generated {tuple(audio_pred.shape)} against wav {tuple(audio_gt.shape)}")
+        crit = discriminator_criterion()
+        out, total = {}, 0.0
+        for key, d in zip(keys, models):
+            y_r, y_g, _, _ = d(audio_gt, audio_pred)
+            loss, _, _ = crit(y_r, y_g)
+            out[f"{key}_Discriminator_loss"] = float(loss)
+            total = total + loss.cpu()
+        if not hasattr(self, "_mel_criterion"):
+            self._mel_criterion = mel_criterion(self.config.get("vocoder_config") or {})
+        out["loss_disc"] = float(total)
+        out["mel_loss"] = float(self._mel_criterion(audio_gt, audio_pred))
+        out["discriminators"] = keys
+        if return_audio:
+            out["audio_gt"], out["audio_pred"] = audio_gt, audio_pred
+        return out
+
     @property
     def device(self):
         return self._device

@@ -190,6 +190,49 @@ def hifigan_weight_spec(cfg, prefix=""):
     return spec
 
 
+def _disc_conv(spec, name, shape, spectral, gain):
+    """one discriminator conv under weight norm (weight_g, weight_v) or spectral norm (weight_orig, weight_u, weight_v); `gain`
+    scales the folded weight against a unit-variance-preserving one, so that the logits of a stack stay O(1)"""
+    co, r = shape[0], 1
+    for d in shape[1:]:
+        r *= d
+    if spectral:
+        spec[name + ".weight_orig"] = (shape, "conv")
+        spec[name + ".weight_u"] = ((co,), ("sn_u", gain, name + ".weight_orig"))
+        spec[name + ".weight_v"] = ((r,), ("sn_v", name + ".weight_orig"))
+    else:
+        spec[name + ".weight_g"] = ((co,) + (1,) * (len(shape) - 1), ("wn_g", gain))
+        spec[name + ".weight_v"] = (shape, "conv")
+    spec[name + ".bias"] = ((co,), "bias")
+
+
+def msd_weight_spec(prefix=""):
+    """MultiScaleDiscriminator (reference layers/hifigan.py:247-314): 3 x DiscriminatorS, the first under spectral norm."""
+    spec = {}
+    convs = [(128, 1, 15), (128, 32, 41), (256, 8, 41), (512, 16, 41), (1024, 32, 41), (1024, 64, 41), (1024, 1024, 5)]
+    for i in range(3):
+        for j, shape in enumerate(convs):
+            _disc_conv(spec, f"{prefix}discriminators.{i}.convs.{j}", shape, i == 0, 1.6)
+        _disc_conv(spec, f"{prefix}discriminators.{i}.conv_post", (1, 1024, 3), i == 0, 1.6)
+    return spec
+
+
+def mpd_weight_spec(cfg, prefix=""):
+    """MultiPeriodDiscriminator (reference layers/hifigan.py:316-426) of a vocoder config: mpd_reshapes, the channel multiplier
+    and mpd_use_spectral_norm."""
+    spec = {}
+    m = cfg.get("mpd_discriminator_channel_mult_factor", 1)
+    sn = bool(cfg.get("mpd_use_spectral_norm", False))
+    ch = [int(32 * m), int(128 * m), int(512 * m), int(1024 * m), int(1024 * m)]
+    for i, _ in enumerate(cfg.get("mpd_reshapes", [2, 3, 5, 7, 11])):
+        cin = 1
+        for j, co in enumerate(ch):
+            _disc_conv(spec, f"{prefix}discriminators.{i}.convs.{j}", (co, cin, 5, 1), sn, 1.6)
+            cin = co
+        _disc_conv(spec, f"{prefix}discriminators.{i}.conv_post", (1, cin, 3, 1), sn, 1.6)
+    return spec
+
+
 def hubert_weight_spec(cfg, prefix=""):
     """fairseq HubertModel / ContentVec tensors used by extract_features + final_proj, named as in the checkpoint
     (keys under `content_extractor.model.` in a GenVC checkpoint; reference layers/content_processor.py:10-31)."""
@@ -227,6 +270,25 @@ def make_weights(seed, spec, device="cpu", head_scale=0.05):
     for name, (shape, kind) in spec.items():
         if isinstance(kind, tuple) and kind[0] == "wn_g":
             out[name] = uniform(seed, name, shape, 0.1 * kind[1], kind[1], device)
+        elif isinstance(kind, tuple) and kind[0] in ("sn_u", "sn_v"):
+            # stored spectral-norm vectors (eval mode uses sigma = u . (W_mat v) as stored).  No power iteration here: its bits would
+            # differ between devices.  Built from the SIGNS of weight_orig, which are exact everywhere, so that sigma is a sum of
+            # |w| terms (well away from zero) close to 1 / gain: C_out > 1: u = sign(W[:, 0]) c, v = e_0 + noise; C_out = 1:
+            # u = [c], v = sign(W[0, :])
+            w = out[kind[-1]]
+            co = w.shape[0]
+            wm = w.reshape(co, -1)
+            r = wm.shape[1]
+            mean_abs = (1.0 / math.sqrt(r)) * math.sqrt(3.0) / 2.0          # E|w| of the "conv" kind
+            if kind[0] == "sn_u":
+                c = 1.0 / (kind[1] * max(co, r if co == 1 else 0) * mean_abs)
+                out[name] = (torch.sign(wm[:, 0]) if co > 1 else torch.ones(1, device=w.device)) * c
+            elif co > 1:
+                v = uniform(seed, name, shape, 0.5 / math.sqrt(r), 0.0, device)
+                v[0] += 1.0
+                out[name] = v
+            else:
+                out[name] = torch.sign(wm[0]).clone()
         elif isinstance(kind, tuple) and kind[0] == "codebook_scaled":
             out[name] = uniform(seed, name, shape, kind[1], 0.0, device)
         elif kind == "ln_w":

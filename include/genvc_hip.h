@@ -1040,6 +1040,67 @@ int gvc_hubert_frames(gvc_hubert* ctx, int32_t n_samples);
 /* wav [B,T] (16 kHz) -> out [B, gvc_hubert_frames(T), final_dim] */
 int gvc_hubert_forward(gvc_hubert* ctx, const float* wav, int32_t B, int32_t T, float* out, gvc_stream s);
 
+/* ------------------------------------------------------------------------------------------
+ * Vocoder evaluation (trainers/hifigan_trainer.py:346-385): the waveform-domain discriminators of layers/hifigan.py
+ * (MultiScaleDiscriminator :247-314, MultiPeriodDiscriminator :316-426) in eval mode, the reductions behind the criteria of
+ * layers/hifigan_loss.py, and that file's mel extractor through gvc_mel_create_ex.  fp32 only, no gradients.
+ *
+ * One context is one of the two discriminators.  Weights are bound under the reference's state-dict names
+ * (discriminators.{i}.convs.{j}.weight_g / weight_v / bias, discriminators.{i}.conv_post.*; a spectral-normed conv:
+ * weight_orig, weight_u, weight_v, bias) and folded to a plain weight once a conv's tensors are all there: weight norm
+ * v * (g / |v|) per output channel, spectral norm weight_orig / (u . (W_mat v)) with the STORED u, v (eval mode).
+ * The real and the generated waveform run as one batch of 2 B.  Every feature map and logit row lives in an arena of
+ * gvc_disc_arena_floats floats that the caller owns (gvc_disc_set_arena) and may read after a forward: layer `layer` of
+ * sub-discriminator `sub` is [2 B][C][H][W] (MSD: W = 1) at the offset gvc_disc_layer reports, items [0, B) real and
+ * [B, 2 B) generated -- the reference's layouts, overwritten by the next forward.
+ * ------------------------------------------------------------------------------------------ */
+#define GVC_DISC_MSD 0
+#define GVC_DISC_MPD 1
+#define GVC_DISC_MAX_SUB 8
+typedef struct gvc_disc gvc_disc;
+typedef struct gvc_disc_dims {
+    int32_t kind;                        /* GVC_DISC_MSD (3 scales, the first spectral-normed) or GVC_DISC_MPD */
+    int32_t n_sub;                       /* MPD: number of periods (<= GVC_DISC_MAX_SUB); MSD: 3 */
+    int32_t periods[GVC_DISC_MAX_SUB];   /* MPD */
+    int32_t channels[5];                 /* MPD: int(32 m), int(128 m), int(512 m), int(1024 m), int(1024 m); multiples of 16 */
+    int32_t spectral_norm;               /* MPD: mpd_use_spectral_norm */
+    int32_t max_batch, max_samples;      /* B (not 2 B) and T */
+} gvc_disc_dims;
+int gvc_disc_create(const gvc_disc_dims* dims, gvc_disc** out);
+int gvc_disc_destroy(gvc_disc* ctx);
+int gvc_disc_bind_weight(gvc_disc* ctx, const char* name, const float* src, int64_t numel, gvc_stream s);
+int gvc_disc_missing_weights(gvc_disc* ctx);
+/* the folded weight of conv `layer` (n_layers - 1 = conv_post) of `sub` as [C_out][C_in / groups][k] -> out (numel floats) */
+int gvc_disc_folded_weight(gvc_disc* ctx, int32_t sub, int32_t layer, float* out, int64_t numel, gvc_stream s);
+int64_t gvc_disc_arena_floats(gvc_disc* ctx);
+int gvc_disc_set_arena(gvc_disc* ctx, float* arena);
+/* layers per sub-discriminator, conv_post included (MSD 8, MPD 6) */
+int gvc_disc_layers(gvc_disc* ctx);
+/* geometry of one feature map at (B, T): offset into the arena and C, H, W; the last layer is the logits [2 B][1][H][W] */
+int gvc_disc_layer(gvc_disc* ctx, int32_t sub, int32_t layer, int32_t B, int32_t T, int64_t* offset, int32_t* C, int32_t* H, int32_t* W);
+/* y, y_hat [B][T] -> feature maps and logits in the arena, and stats [n_sub][3 + gvc_disc_layers]: mean((1 - d_r)^2),
+ * mean(d_g^2), mean((1 - d_g)^2), then mean|f_r - f_g| per layer.  The reductions have a fixed partition and order and use no
+ * float atomics: the same input gives the same bits.  One captured graph per (B, T).  T must exceed every period. */
+int gvc_disc_forward(gvc_disc* ctx, const float* y, const float* y_hat, int32_t B, int32_t T, float* stats, gvc_stream s);
+/* measurement: layer `layer` of `sub` alone, `iters` back-to-back launches on the arena's current contents (after a forward at the
+ * same (B, T)) between two events -> microseconds per launch; synchronises */
+int gvc_disc_time_layer(gvc_disc* ctx, int32_t sub, int32_t layer, int32_t B, int32_t T, int32_t iters, float* avg_us, gvc_stream s);
+/* out[0] = scale * mean|a - b| over n floats, reduced in a fixed order; work: 512 floats, 8-byte aligned */
+int gvc_l1_mean(const float* a, const float* b, int64_t n, float scale, float* out, float* work, gvc_stream s);
+
+/* The mel extractor of layers/hifigan_loss.py:16-75 (and, with other options, any variant of the front end above). */
+#define GVC_MEL_SLANEY_SCALE 1           /* librosa's default mel scale (linear below 1 kHz, logarithmic above); 0: HTK */
+#define GVC_MEL_MAGNITUDE 2              /* sqrt(re^2 + im^2 + 1e-9); 0: power */
+#define GVC_MEL_PAD_HALF_OVERLAP 4       /* reflect (n_fft - hop) / 2 per side, center=False: T / hop frames; 0: n_fft / 2, 1 + T / hop */
+typedef struct gvc_mel_options {
+    int32_t n_fft, hop, win, sample_rate, n_mels, flags;
+    float f_min, f_max;
+    const float* mel_norms_host;         /* [n_mels] or NULL (no norms) */
+} gvc_mel_options;
+int gvc_mel_create_ex(const gvc_mel_options* opt, gvc_mel** out);
+/* frames gvc_mel_forward writes for T samples (<= 0: too short for the reflect padding) */
+int gvc_mel_frames(gvc_mel* ctx, int32_t T);
+
 #ifdef __cplusplus
 }
 #endif
