@@ -114,6 +114,12 @@ class MelOptions(C.Structure):
         [("f_min", C.c_float), ("f_max", C.c_float), ("mel_norms_host", C.POINTER(C.c_float))]
 
 
+class TraceOptions(C.Structure):
+    """gvc_trace_options (include/genvc_hip.h)"""
+    _fields_ = [(n, C.c_int32) for n in ("start_tok", "stop_tok", "content_off", "n_content")] + [("layer_mask", C.c_uint64)] + \
+        [(n, C.c_void_p) for n in ("probs", "hidden", "align", "scratch")]
+
+
 class HifiganDims(C.Structure):
     _fields_ = [("in_dim", C.c_int32), ("up_init_ch", C.c_int32), ("n_ups", C.c_int32), ("up_rates", C.c_int32 * 4),
                 ("up_kernels", C.c_int32 * 4), ("n_kernels", C.c_int32), ("res_kernels", C.c_int32 * 4),
@@ -144,6 +150,7 @@ _SIGNATURES = {
     "gvc_gpt_kv_fanout": (C.c_int, [_P, _P, _P, C.c_int32, _P]),
     "gvc_gpt_sequence_logprobs": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "gvc_gpt_latents": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
+    "gvc_gpt_trace": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, _P, C.c_int32, _P, _P, C.POINTER(TraceOptions), _P]),
     "gvc_gpt_forward_rows": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, _P, C.c_int32, _P, C.c_int32, _P, _P, _P]),
     "gvc_gpt_head_xent": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_float, C.c_int32, _P, _P, _P, _P]),
     "gvc_sample": (C.c_int, [_P, C.c_int32, _P, C.c_int32, _P, _P, C.POINTER(SampleParams), C.c_int32, _P, _P]),

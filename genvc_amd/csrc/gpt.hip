@@ -22,6 +22,7 @@
 #include "sampler.h"
 #include "seqscore.h"
 #include "spec.h"
+#include "trace.h"
 
 namespace gvc {
 
@@ -327,6 +328,18 @@ struct GraphKey {
     }
 };
 
+// what the running gvc_gpt_trace call taps between the phases of run_rows (all device pointers, each nullable)
+struct TraceCall {
+    float* probs;              // [L][B][H][T][T]
+    float* hidden;             // [L+1][B][T][d]
+    float* align;              // [B][n][Tc]
+    float* scratch;            // [B][H][T][T]: a layer's weights when probs is null
+    const int32_t* lens;       // [B]
+    int P, n, c0, Tc;
+    unsigned long long layers; // bit l: layer l counts in align
+    int n_chosen, last_chosen;
+};
+
 struct gvc_gpt {
     gvc_gpt_dims dm;
     int hd = 0, n_cu = 256;
@@ -340,6 +353,7 @@ struct gvc_gpt {
     int thead_bound = 0;              // bit 0: weight, bit 1: bias
     const uint8_t* eval_mask = nullptr;   // key-padding mask [B][eval_mask_stride] of the running gvc_gpt_forward_rows call (null outside it)
     int eval_mask_stride = 0;
+    const struct TraceCall* trace = nullptr;   // taps of the running gvc_gpt_trace call (null outside it): run_rows keeps to its launch-per-phase loop
     std::vector<GptLayer> layers;
     std::map<std::string, int> bound;  // name -> 1 once bound
     int n_expected = 0;
@@ -1588,6 +1602,32 @@ static int run_rows_b16(gvc_gpt* c, const int32_t* slots, int B, int T, hipStrea
     return launch_ln_sum_rows_b16(c->x, c->x, nullptr, nullptr, part_p2, sk_p2, c->layers[L - 1].p2_b, rows, d, s);
 }
 
+// The taps of a gvc_gpt_trace call in front of layer l's attention launch: hidden plane l (the embedded rows for l = 0, else the residual
+// after layer l - 1), the layer's attention weights (trace.h) and its share of the alignment map.
+static int trace_layer(gvc_gpt* c, int l, const AttnArgs& At, int B, hipStream_t s) {
+    const TraceCall& tr = *c->trace;
+    const int d = c->dm.d_model, T = At.T, H = c->dm.n_head;
+    int rc;
+    if (tr.hidden) {
+        hipLaunchKernelGGL(k_trace_hidden, dim3(cdiv(B * T, 4)), dim3(256), 0, s, c->x, tr.hidden + (size_t)l * B * T * d, B, T, d, tr.lens, tr.P,
+                           (const float*)nullptr, (const float*)nullptr);
+        GVC_LAUNCH_CHECK();
+    }
+    const bool chosen = tr.align && ((tr.layers >> l) & 1ull);
+    if (!tr.probs && !chosen) return GVC_OK;
+    float* pl = tr.probs ? tr.probs + (size_t)l * B * H * T * T : tr.scratch;
+    if ((rc = launch_attention_probs(c->hd, H, At, B, tr.lens, tr.P, pl, s))) return rc;
+    if (chosen) {
+        const int total = B * tr.n * tr.Tc;
+        int first = 1;
+        for (int k = 0; k < l; ++k) first &= !((tr.layers >> k) & 1ull);
+        hipLaunchKernelGGL(k_trace_align, dim3(cdiv(total, 256)), dim3(256), 0, s, pl, tr.align, B, H, T, tr.P, tr.n, tr.c0, tr.Tc, first,
+                           l == tr.last_chosen ? 1.0f / (float)(H * tr.n_chosen) : 0.f);
+        GVC_LAUNCH_CHECK();
+    }
+    return GVC_OK;
+}
+
 static int run_rows(gvc_gpt* c, const int32_t* slots, int B, int T, hipStream_t s, const int32_t* base_len, int key_chunks) {
     const int d = c->dm.d_model, rows = B * T;
     int rc;
@@ -1608,7 +1648,7 @@ static int run_rows(gvc_gpt* c, const int32_t* slots, int B, int T, hipStream_t 
     // workgroup -- costs more than the two launches it saves): the row completion + LayerNorm runs
     // in the prologue of the QKV / c_fc GEMMs (5 launches per layer instead of 7); the residual stream ping-pongs between
     // c->x and c->xalt because only workgroup 0 of a launch writes the completed rows while the others still read them
-    if (skinny && rows <= c->fuse_ln_rows && c->fuse_ln && d <= 1024) {
+    if (skinny && rows <= c->fuse_ln_rows && c->fuse_ln && d <= 1024 && !c->trace) {
         float* X[2] = {c->x, c->xalt};
         int cur = 0;
         for (int l = 0; l < c->dm.n_layer; ++l) {
@@ -1694,6 +1734,7 @@ static int run_rows(gvc_gpt* c, const int32_t* slots, int B, int T, hipStream_t 
         AttnArgs At = gpt_attn_args(c, l, slots);
         At.q = c->q; At.T = T; At.base_len = base_len;
         At.out = c->a; At.out_stride = d; At.out_fm16 = fm ? 1 : 0;
+        if (c->trace && (rc = trace_layer(c, l, At, B, s))) return rc;      // c->x: the residual in front of layer l; q and the K rows are in place
         // one new row per cached stream (batched decode): 16 waves share the keys of a (row, head)
         if (att_nc > 1) {
             At.out = c->part;
@@ -1730,6 +1771,11 @@ static int run_rows(gvc_gpt* c, const int32_t* slots, int B, int T, hipStream_t 
     }
     if (fm) {       // fold the last layer's mlp partials into the residual stream
         ln_sum_sk(part_p2, sk_p2, c->layers[c->dm.n_layer - 1].p2_b, nullptr, nullptr);
+        GVC_LAUNCH_CHECK();
+    }
+    if (c->trace && c->trace->hidden && ln_rc == GVC_OK) {      // the last plane: ln_f of the last residual
+        hipLaunchKernelGGL(k_trace_hidden, dim3(cdiv(rows, 4)), dim3(256), 0, s, c->x, c->trace->hidden + (size_t)c->dm.n_layer * rows * d, B, T, d,
+                           c->trace->lens, c->trace->P, (const float*)c->lnf_w, (const float*)c->lnf_b);
         GVC_LAUNCH_CHECK();
     }
     return ln_rc;
@@ -1832,6 +1878,53 @@ extern "C" int gvc_gpt_latents(gvc_gpt* c, const int32_t* slots, int32_t B, cons
     GVC_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_gather_rows, dim3(B * n), dim3(256), 0, s, c->a, out, B, T, P, n, d);
     GVC_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_set_state, dim3(cdiv(B, 64)), dim3(64), 0, s, c->st, slots, B, 0, 0);
+    GVC_LAUNCH_CHECK();
+    return GVC_OK;
+}
+
+// Teacher-forced trace pass (include/genvc_hip.h): the rows of gvc_gpt_latents without its four trailing stop rows, through run_rows'
+// launch-per-phase loop with the taps of trace_layer between the phases.
+extern "C" int gvc_gpt_trace(gvc_gpt* c, const int32_t* slots, int32_t B, const float* prefix_emb, int32_t P, const int32_t* gen_codes,
+                             int32_t n, const int32_t* lengths, const int32_t* lengths_host, const gvc_trace_options* opt, gvc_stream sv) {
+    int rc = check_ready(c);
+    if (rc) return rc;
+    GVC_REQUIRE(c->dm.weight_dtype == 0, GVC_ERR_UNSUPPORTED,
+                "trace: the trace pass is a reference-numerics pass: fp32 contexts only (weight_dtype %d)", c->dm.weight_dtype);
+    GVC_REQUIRE(slots && prefix_emb && gen_codes && lengths && lengths_host && opt, GVC_ERR_ARG, "trace: null argument");
+    GVC_REQUIRE(opt->probs || opt->hidden || opt->align, GVC_ERR_ARG, "trace: no output asked for (probs, hidden and align are all null)");
+    GVC_REQUIRE(B >= 1 && B <= c->dm.max_slots && n >= 1 && P >= 1, GVC_ERR_ARG, "trace: bad B=%d n=%d P=%d", B, n, P);
+    const long long T = (long long)P + n;
+    const int d = c->dm.d_model, L = c->dm.n_layer;
+    GVC_REQUIRE(B * T <= c->dm.max_rows, GVC_ERR_ARG, "trace: %lld rows exceed max_rows %d", B * T, c->dm.max_rows);
+    GVC_REQUIRE(T < c->dm.max_seq, GVC_ERR_ARG, "trace: %lld rows per item exceed max_seq %d", T, c->dm.max_seq);
+    GVC_REQUIRE(n <= c->dm.max_mel_pos - 5, GVC_ERR_ARG, "trace: %d codes exceed the position table (%d - 5)", n, c->dm.max_mel_pos);
+    for (int b = 0; b < B; ++b)
+        GVC_REQUIRE(lengths_host[b] >= 1 && lengths_host[b] <= n, GVC_ERR_ARG, "trace: length %d of item %d outside [1,%d]", lengths_host[b], b, n);
+    GVC_REQUIRE(L <= 64, GVC_ERR_ARG, "trace: %d layers exceed the 64 bits of the layer mask", L);
+    TraceCall tr;
+    memset(&tr, 0, sizeof(tr));
+    tr.probs = opt->probs; tr.hidden = opt->hidden; tr.align = opt->align; tr.lens = lengths; tr.P = P; tr.n = n;
+    if (opt->align) {
+        GVC_REQUIRE(opt->n_content >= 1 && opt->content_off >= 0 && opt->content_off + opt->n_content <= P, GVC_ERR_ARG,
+                    "trace: content rows [%d, %d) outside the %d prefix rows", opt->content_off, opt->content_off + opt->n_content, P);
+        GVC_REQUIRE(opt->probs || opt->scratch, GVC_ERR_ARG, "trace: align without probs needs the [B][H][T][T] scratch");
+        const unsigned long long all = L == 64 ? ~0ull : (1ull << L) - 1;
+        tr.layers = opt->layer_mask ? opt->layer_mask : all;
+        GVC_REQUIRE((tr.layers & ~all) == 0, GVC_ERR_ARG, "trace: layer mask 0x%llx names layers past the %d of the model", tr.layers, L);
+        for (int l = 0; l < L; ++l)
+            if ((tr.layers >> l) & 1ull) { tr.n_chosen += 1; tr.last_chosen = l; }
+        tr.scratch = opt->scratch; tr.c0 = opt->content_off; tr.Tc = opt->n_content;
+    }
+    hipStream_t s = (hipStream_t)sv;
+    hipLaunchKernelGGL(k_embed_rows, dim3(B * (int)T), dim3(256), 0, s, c->x, prefix_emb, B, (int)T, P, d, c->mel_emb, c->mel_pos,
+                       gen_codes, n, opt->start_tok, opt->stop_tok, 0);
+    GVC_LAUNCH_CHECK();
+    c->rows_keys_hint = (int)T;
+    c->trace = &tr;
+    rc = run_rows(c, slots, B, (int)T, s);
+    c->trace = nullptr;
+    if (rc) return rc;
     hipLaunchKernelGGL(k_set_state, dim3(cdiv(B, 64)), dim3(64), 0, s, c->st, slots, B, 0, 0);
     GVC_LAUNCH_CHECK();
     return GVC_OK;

@@ -861,6 +861,52 @@ class GptEngine:
                                     stream()), "latents")
         return out
 
+    def trace(self, slots, prefix_emb, gen_codes, lengths, n_cond, output_attentions=True, output_hidden_states=False, alignment=True,
+              alignment_layers=None):
+        """the trace pass (include/genvc_hip.h: gvc_gpt_trace) over prefix_emb fp32 [B, P, d] (of prefix_embeddings: n_cond conditioning
+        rows, text start, Tc content codes, text stop) and gen_codes int32 [B, n] with generated lengths `lengths` [B] (stop code counted)
+        -> (probs fp32 [L, B, H, T, T] or None, hidden fp32 [L + 1, B, T, d] or None, align fp32 [B, n, Tc] or None), T = P + n.
+        alignment_layers: the layers the alignment averages over (indices, negative from the end; None = all)."""
+        self._join_side()
+        prefix_emb, gen_codes = _f32(prefix_emb.contiguous()), _i32(gen_codes.contiguous())
+        B, P, _ = prefix_emb.shape
+        n = int(gen_codes.shape[1])
+        T, L, H = P + n, self.dims["n_layer"], self.dims["n_head"]
+        Tc = P - int(n_cond) - 2
+        if gen_codes.shape[0] != B or slots.shape[0] != B or Tc < 1:
+            raise ValueError(f"trace: prefix {tuple(prefix_emb.shape)} ({n_cond} conditioning rows), codes {tuple(gen_codes.shape)} and "
+                             f"{int(slots.shape[0])} slots do not go together")
+        lens_host = torch.as_tensor(lengths).to("cpu", torch.int32).contiguous()
+        if tuple(lens_host.shape) != (B,):
+            raise ValueError(f"trace: {tuple(lens_host.shape)} lengths for {B} items")
+        mask = 0
+        if alignment_layers is not None:
+            for l in alignment_layers:
+                if not -L <= int(l) < L:
+                    raise ValueError(f"trace: alignment layer {l} outside the model's {L} layers")
+                mask |= 1 << (int(l) % L)
+            if mask == 0:
+                raise ValueError("trace: alignment_layers is empty")
+        dev = prefix_emb.device
+        lens_dev = lens_host.to(dev)
+        probs = torch.empty(L, B, H, T, T, device=dev, dtype=torch.float32) if output_attentions else None
+        hidden = torch.empty(L + 1, B, T, self.d, device=dev, dtype=torch.float32) if output_hidden_states else None
+        align = torch.empty(B, n, Tc, device=dev, dtype=torch.float32) if alignment else None
+        scratch = torch.empty(B, H, T, T, device=dev, dtype=torch.float32) if alignment and probs is None else None
+        opt = _lib.TraceOptions(start_tok=self.dims["start_audio_token"], stop_tok=self.dims["stop_audio_token"], content_off=int(n_cond) + 1,
+                                n_content=Tc, layer_mask=mask, probs=None if probs is None else probs.data_ptr(),
+                                hidden=None if hidden is None else hidden.data_ptr(), align=None if align is None else align.data_ptr(),
+                                scratch=None if scratch is None else scratch.data_ptr())
+        rc = lib().gvc_gpt_trace(self._h, ptr(_i32(slots)), B, ptr(prefix_emb), P, ptr(gen_codes), n, ptr(lens_dev),
+                                 C.c_void_p(lens_host.data_ptr()), C.byref(opt), stream())
+        if rc == -4:
+            raise NotImplementedError(f"trace: attentions and hidden states come from a reference-numerics pass -- this context was created "
+                                      f"with weight_dtype=\"{self.weight_dtype}\" ({lib().gvc_last_error().decode(errors='replace')})")
+        if rc == -1:
+            raise ValueError(f"trace: {lib().gvc_last_error().decode(errors='replace')}")
+        check(rc, "trace")
+        return probs, hidden, align
+
     def _eval_check(self, rc, what):
         """status of an evaluation-pass entry: argument errors as ValueError, a bf16 context as NotImplementedError naming its mode"""
         if rc == -4:

@@ -108,7 +108,7 @@ def _segment_latents(m, cond_latent, codes, gen, repass_latents, row=0):
 @torch.inference_mode()
 def synthesize_utt(genVC_mdl, src_wav, tgt_audio, seg_len=6.0, return_details=False, repass_latents=False, num_beams=1,
                    generate_kwargs=None, num_return_sequences=None, num_beam_groups=None, diversity_penalty=None, guidance_scale=None,
-                   negative_ref_audio=None, token_scores=False):
+                   negative_ref_audio=None, token_scores=False, alignment=False):
     """non-streaming conversion, latent-level concatenation (reference :23-89).  num_beams = K > 1: every segment decodes with
     deterministic beam search (GPT.generate(num_beams=K, do_sample=False)); its latents come from the re-pass.
     generate_kwargs: more GPT.generate kwargs (the logits processors: min_new_tokens, no_repeat_ngram_size, ...; the
@@ -125,9 +125,14 @@ def synthesize_utt(genVC_mdl, src_wav, tgt_audio, seg_len=6.0, return_details=Fa
     token_scores=True with return_details: the dict also carries "token_logprobs", one fp32 [n] tensor per segment beside "codes": the
     log-probability of every token under the distribution it was decoded from (GPT.generate(output_scores=True) and
     compute_transition_scores(normalize_logits=True): processors, warpers and guidance included).  Not with num_return_sequences > 1;
-    beams and contrastive search raise NotImplementedError (GPT.generate)."""
+    beams and contrastive search raise NotImplementedError (GPT.generate).
+    alignment=True with return_details: the dict also carries "alignments", one fp32 [n, Tc] matrix per segment beside "codes": the
+    attention of each of the segment's n acoustic codes over its Tc content codes (GPT.trace(output_attentions=False): the head /
+    layer mean, one more teacher-forced pass per segment; a row sums to at most 1).  Not with num_return_sequences > 1."""
     m = genVC_mdl
     from genvc_amd.layers.gpt import _num_return
+    if alignment and not return_details:
+        raise ValueError("alignment=True needs return_details=True (the matrices come back in the details dict)")
     if token_scores and not return_details:
         raise ValueError("token_scores=True needs return_details=True (the scores come back in the details dict)")
     gkw = dict(generate_kwargs or {})
@@ -141,6 +146,8 @@ def synthesize_utt(genVC_mdl, src_wav, tgt_audio, seg_len=6.0, return_details=Fa
     if token_scores and _num_return(gkw) > 1:
         raise NotImplementedError("token_scores=True with num_return_sequences > 1 is not implemented: the candidates carry "
                                   "their sequence scores")
+    if alignment and _num_return(gkw) > 1:
+        raise NotImplementedError("alignment=True with num_return_sequences > 1 is not implemented: GPT.trace serves each candidate's codes")
     if token_scores:
         gkw.update(return_dict_in_generate=True, output_scores=True)
     if _num_return(gkw) > 1:
@@ -149,8 +156,10 @@ def synthesize_utt(genVC_mdl, src_wav, tgt_audio, seg_len=6.0, return_details=Fa
     src_wav = src_wav.to(m.device)
     seg = int(seg_len * m.content_sample_rate)
     cond_latent = m.get_gpt_cond_latents(tgt_audio.to(m.device), m.config.audio.sample_rate)
-    final_latents, all_codes, all_logprobs = [], [], []
+    final_latents, all_codes, all_logprobs, all_aligns = [], [], [], []
     more = {"token_logprobs": all_logprobs} if token_scores else {}
+    if alignment:
+        more["alignments"] = all_aligns
     for src_seg in segments(src_wav, seg, min_len):
         feat = m.content_extractor.extract_content_features(src_seg)
         codes = m.content_dvae.get_codebook_indices(feat.transpose(1, 2))
@@ -165,6 +174,8 @@ def synthesize_utt(genVC_mdl, src_wav, tgt_audio, seg_len=6.0, return_details=Fa
         all_codes.append(gen)
         if token_scores:
             all_logprobs.append(m.gpt.compute_transition_scores(res.sequences, res.scores, normalize_logits=True)[0][keep])
+        if alignment:
+            all_aligns.append(m.gpt.trace(cond_latent, codes, gen.unsqueeze(0), output_attentions=False).alignment[0])
     if not final_latents:                    # every segment ended on its first token: nothing to vocode
         empty = torch.zeros(0, device=m.device)
         return dict(latents=None, codes=[], wav=empty, **more) if return_details else empty

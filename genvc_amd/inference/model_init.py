@@ -280,7 +280,8 @@ class GenVCModel(nn.Module):
     @torch.no_grad()
     def inference(self, src_audio, cond_latent, do_sample=True, top_p=0.85, top_k=15, temperature=0.75, num_beams=1,
                   length_penalty=1.0, repetition_penalty=10.0, output_attentions=False, repass_latents=False, generate_kwargs=None,
-                  num_return_sequences=None, num_beam_groups=None, diversity_penalty=None, guidance_scale=None, negative_ref_audio=None):
+                  num_return_sequences=None, num_beam_groups=None, diversity_penalty=None, guidance_scale=None, negative_ref_audio=None,
+                  return_alignment=False):
         """reference trainers/hifigan_trainer.py:457-500: one source segment [1,T] + conditioning latents -> waveform
         [1,1,1024 n]: ContentVec -> content codes -> generate -> strip stop tokens -> latent re-pass -> x4 linear
         interpolation -> HiFi-GAN.  (The reference's 0-d collapse at exactly one non-stop token, SURVEY appendix B.9, is
@@ -295,7 +296,10 @@ class GenVCModel(nn.Module):
         num_return_sequences = N <= K the N waveforms are its N best hypotheses, `last_beam_scores` their scores.
         guidance_scale = s != 1 (the keyword, or in generate_kwargs): classifier-free guidance; the negative prompt's conditioning
         latents are generate_kwargs["negative_cond_latents"] when given (synthesize_utt_chunked computes them once per utterance),
-        else those of negative_ref_audio = (wav, sample rate), default this source segment."""
+        else those of negative_ref_audio = (wav, sample rate), default this source segment.
+        return_alignment=True: (waveform, alignment) -- alignment fp32 [n_codes, Tc], the attention of each generated acoustic code over
+        the Tc content codes of the segment (GPT.trace: the head / layer mean, one more teacher-forced pass; a row sums to at most 1).
+        Not with num_return_sequences > 1."""
         feat = self.content_extractor.extract_content_features(src_audio)
         codes = self.content_dvae.get_codebook_indices(feat.transpose(1, 2))
         kw = dict(do_sample=do_sample, top_p=top_p, top_k=top_k, temperature=temperature, num_beams=num_beams,
@@ -311,13 +315,20 @@ class GenVCModel(nn.Module):
         kw = _guided_kwargs(self, kw, guidance_scale, negative_ref_audio, src_audio)
         from genvc_amd.layers.gpt import _num_return
         if _num_return(kw) > 1:
+            if return_alignment:
+                raise NotImplementedError("return_alignment=True with num_return_sequences > 1 is not implemented: GPT.trace serves each "
+                                          "candidate's codes")
             return self._inference_candidates(cond_latent, codes, kw, repass_latents)
         gen = self.gpt.generate(cond_latent, codes, **kw)
         gen = getattr(gen, "sequences", gen)[0]
         gen = gen[gen != self.gpt.stop_audio_token]
         if gen.numel() == 0:
-            return torch.zeros(1, 1, 0, device=self.device)
-        return self._vocode_segment(cond_latent, codes, gen, repass_latents)
+            wav = torch.zeros(1, 1, 0, device=self.device)
+            return (wav, torch.zeros(0, codes.shape[-1], device=self.device)) if return_alignment else wav
+        wav = self._vocode_segment(cond_latent, codes, gen, repass_latents)
+        if return_alignment:
+            return wav, self.gpt.trace(cond_latent, codes, gen.unsqueeze(0), output_attentions=False).alignment[0]
+        return wav
 
     def _vocode_segment(self, cond_latent, codes, gen, repass_latents, row=0):
         """the stop-free tokens `gen` of row `row` of the last generate call -> waveform [1, 1, 1024 n] (latents, x4 linear

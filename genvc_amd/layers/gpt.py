@@ -190,7 +190,11 @@ def _no_contrastive(kw, where):
                                   "harness always samples, inference_utils.py:178)")
 
 
-OUTPUT_KWARGS = ("return_dict_in_generate", "output_scores", "output_logits")
+# refused by name on the paths that return bare tokens.  output_hidden_states is not among them: the reference's streaming harness passes
+# output_hidden_states=True to get_generator as its way of asking for the latents (inference_utils.py:178), which these paths yield
+# anyway; as a request for a result object's `hidden_states` it only means something with return_dict_in_generate, which is refused
+OUTPUT_KWARGS = ("return_dict_in_generate", "output_scores", "output_logits", "output_attentions")
+MAX_TRACE_BYTES = 2 << 30          # default of generate(max_trace_bytes=): the attentions tensor of one call
 
 
 class GenerateOutput(dict):
@@ -200,7 +204,15 @@ class GenerateOutput(dict):
                transformers' logits processors (and, when sampling, warpers) leave it; else None
     logits     output_logits=True: likewise the raw head output of every step (under guidance the conditional row); else None
     latents    `last_latents` of the call
-    sequences_scores  beam search: `last_beam_scores`; else None"""
+    sequences_scores  beam search: `last_beam_scores`; else None
+    attentions output_attentions=True: HF's form, a tuple over the n steps of tuples over the L layers of fp32 views into one device
+               tensor [L, rows, H, T, T] (T = P + n, P the prefix rows): step 0 [rows, H, P+1, P+1], step i [rows, H, 1, P+1+i]; else
+               None.  A step at or past a row's end (HF ran it on a pad token) is all zeros.
+    hidden_states  output_hidden_states=True: likewise L + 1 entries per step (the embeddings, each layer's output, ln_f of the last
+               one), views into [L+1, rows, T, D]: step 0 [rows, P+1, D], step i [rows, 1, D]; else None
+    Both keys exist only in the result of a call that asked for either (the other one is then None): a result without them reads as it
+    always has (AttributeError / KeyError).
+    GPT.trace fills the same object with the full tensors under `attentions` / `hidden_states` and `alignment` [B, n, Tc]."""
 
     def __getattr__(self, name):
         try:
@@ -217,11 +229,36 @@ def _output_kwargs(kw):
 
 
 def _no_outputs(kw, where):
-    """the paths that return bare tokens: return_dict_in_generate / output_scores / output_logits raise, naming the path"""
+    """the paths that return bare tokens: return_dict_in_generate / output_scores / output_logits / output_attentions raise, naming the
+    path (output_hidden_states alone keeps its old treatment, see OUTPUT_KWARGS)"""
     for k in OUTPUT_KWARGS:
         if kw.get(k):
             raise NotImplementedError(f"{k}={kw.get(k)!r} is not on the {where} path: GPT.generate serves it (one result object per "
-                                      "call, per-step scores of the sampler paths)")
+                                      "call, per-step scores, attentions and hidden states of the sampler paths)")
+
+
+def _trace_kwargs(kw):
+    """(output_attentions, output_hidden_states) of the call as HF reads them: ignored without return_dict_in_generate"""
+    rd = bool(kw.get("return_dict_in_generate"))
+    return rd and bool(kw.get("output_attentions")), rd and bool(kw.get("output_hidden_states"))
+
+
+def _no_trace(kw, mode):
+    """the modes of GPT.generate without the trace pass: output_attentions / output_hidden_states raise, naming the mode"""
+    at, hs = _trace_kwargs(kw)
+    if at or hs:
+        which = "output_attentions" if at else "output_hidden_states"
+        raise NotImplementedError(f"{which}=True with {mode} is not implemented: the trace pass follows one token row per prompt row "
+                                  "(greedy, sampling, num_return_sequences, guidance_scale); GPT.trace serves any finished ids")
+
+
+def _trace_bytes_check(L, rows, H, T, limit):
+    """the size guard of output_attentions: the [L, rows, H, T, T] fp32 tensor against max_trace_bytes"""
+    size = 4 * L * rows * H * T * T
+    if size > limit:
+        raise ValueError(f"output_attentions: {L} layers x {rows} rows x {H} heads x {T}^2 fp32 weights are {size} bytes "
+                         f"({size / 2 ** 30:.2f} GiB), above max_trace_bytes={limit}: raise it, or take "
+                         "GPT.trace(..., output_attentions=False) for the hidden states and the alignment (one layer's weights at a time)")
 
 
 def _no_step_outputs(kw, mode):
@@ -312,6 +349,7 @@ def _assisted_kwargs(kw, B, lookup=False):
                                   "sampling needs the draft's warped rows; pass do_sample=False or top_k=1 (or opt in with "
                                   "speculative_sampling=True)")
     _no_step_outputs(kw, mode)
+    _no_trace(kw, mode)
     _no_bias(kw, mode)
     if logits_warpers(kw, sampling=_speculative(kw)) is not None:
         raise NotImplementedError(f"typical_p / epsilon_cutoff / eta_cutoff with {mode} are not implemented")
@@ -347,6 +385,14 @@ def _plain_rows_only(kw, where, beams=True):
     _no_outputs(kw, where)
     _no_bias(kw, f"the {where} path")
     _no_assistant(kw, where)
+
+
+def _step_views(probs, hidden, P, n):
+    """the full tensors of a trace pass (probs [L, rows, H, T, T], hidden [L+1, rows, T, D], either None) cut into HF's per-step form:
+    tuples over the n steps of tuples over the layers of views -- step 0 the P + 1 prompt rows, step i the one row P + i"""
+    def cut(t, f):
+        return None if t is None else tuple(tuple(f(t[l], 0 if i == 0 else P + i, P + i + 1) for l in range(t.shape[0])) for i in range(n))
+    return cut(probs, lambda p, lo, hi: p[:, :, lo:hi, :hi]), cut(hidden, lambda h, lo, hi: h[:, lo:hi])
 
 
 def _generate_call(eng, *args, **kw):
@@ -609,6 +655,7 @@ class GPT(nn.Module):
         self._need_engine()
         self._prefix = self.engine.prefix_embeddings(cond_latents.to(torch.float32).contiguous(),
                                                      text_inputs.to(torch.int32).contiguous())
+        self._n_cond = int(cond_latents.shape[1])
         B, P, _ = self._prefix.shape
         ids = torch.full((B, P + 1), 1, dtype=torch.long, device=text_inputs.device)
         ids[:, -1] = self.start_audio_token
@@ -687,9 +734,78 @@ class GPT(nn.Module):
 
         def steps(buf):
             return None if buf is None else tuple(buf[:, t] for t in range(n))
-        return GenerateOutput(sequences=ids, scores=steps(st.get("scores")) if st else None,
-                              logits=steps(st.get("raw_logits")) if st else None, latents=self.last_latents,
-                              sequences_scores=self.last_beam_scores if beams else None)
+        out = GenerateOutput(sequences=ids, scores=steps(st.get("scores")) if st else None,
+                             logits=steps(st.get("raw_logits")) if st else None, latents=self.last_latents,
+                             sequences_scores=self.last_beam_scores if beams else None)
+        if st and any(_trace_kwargs(kw)):
+            out["attentions"], out["hidden_states"] = self._trace_steps(st, ids, kw)
+        return out
+
+    def _trace_ready(self, kw, rows):
+        """before a call with output_attentions / output_hidden_states spends its steps: the context's numerics and the smallest size
+        the attentions can have (the exact size is checked once the tokens are final)"""
+        at, hs = _trace_kwargs(kw)
+        if not (at or hs):
+            return
+        wd = getattr(self.engine, "weight_dtype", "fp32")
+        if wd != "fp32":
+            raise NotImplementedError(f"output_attentions / output_hidden_states with weight_dtype=\"{wd}\" are not implemented: the "
+                                      "trace pass is a reference-numerics pass (init_gpt_for_inference(weight_dtype=\"fp32\"))")
+        if at:
+            _trace_bytes_check(self.layers, rows, self.heads, int(self._prefix.shape[1]) + 1, int(kw.get("max_trace_bytes", MAX_TRACE_BYTES)))
+
+    def _trace_steps(self, st, ids, kw):
+        """the trace pass of a finished sampler call (engine.trace; include/genvc_hip.h: gvc_gpt_trace) on the call's slots, from its
+        prefix embeddings and its final ids [rows, n], cut into HF's per-step views -> (attentions, hidden_states)"""
+        at, hs = _trace_kwargs(kw)
+        rows, n = int(ids.shape[0]), int(ids.shape[1])
+        prefix = self._prefix
+        if int(prefix.shape[0]) != rows:                     # num_return_sequences: row b*N + j is candidate j of item b
+            prefix = prefix.repeat_interleave(rows // int(prefix.shape[0]), 0)
+        P = int(prefix.shape[1])
+        if at:
+            _trace_bytes_check(self.layers, rows, self.heads, P + n, int(kw.get("max_trace_bytes", MAX_TRACE_BYTES)))
+        probs, hidden, _ = self.engine.trace(st["slots"], prefix, ids.to(torch.int32), self._code_lengths(ids), self._n_cond,
+                                             output_attentions=at, output_hidden_states=hs, alignment=False)
+        return _step_views(probs, hidden, P, n)
+
+    def _code_lengths(self, toks):
+        """generated length per row, its stop code counted; n for a row that never stopped"""
+        is_stop = toks == self.stop_audio_token
+        first = is_stop.long().argmax(1) + 1
+        return torch.where(is_stop.any(1), first, torch.full_like(first, toks.shape[1])).to("cpu", torch.int32)
+
+    @torch.inference_mode()
+    def trace(self, cond_latents, text_inputs, codes, code_lengths=None, output_attentions=True, output_hidden_states=False,
+              alignment_layers=None, max_trace_bytes=MAX_TRACE_BYTES):
+        """Attention weights, hidden states and the content alignment of given acoustic codes [B, n] under the prompt (cond_latents,
+        text_inputs): one teacher-forced pass over [prefix | start, codes[:, :n-1]] (include/genvc_hip.h: gvc_gpt_trace; DESIGN.md
+        4.23), row P + i the query of the step that produced code i.  code_lengths [B]: each row's generated length, its stop code
+        counted (default: up to and including the row's first stop token, else n); steps at or past it are zeros -- HF's generate
+        returns the attention of the pad inputs it fed such rows, which means nothing.
+        -> GenerateOutput: sequences = codes; attentions fp32 [L, B, H, T, T] (T = P + n; zero above the diagonal) or None;
+        hidden_states fp32 [L+1, B, T, D] (embeddings, each layer's output, ln_f of the last) or None; alignment fp32 [B, n, Tc]: the
+        mean over the heads of `alignment_layers` (indices, negative from the end; default all) of the weight step i puts on the Tc
+        content codes.  Of the prefix rows [conditioning (32) | text start | content codes | text stop] (compute_embeddings, reference
+        gpt.py:572-592) only the content codes count: a row of `alignment` sums to at most 1, the rest of the mass sits on the
+        conditioning rows, the text start / stop rows and the acoustic codes in front.  fp32 contexts only."""
+        self._need_engine()
+        wd = getattr(self.engine, "weight_dtype", "fp32")
+        if wd != "fp32":
+            raise NotImplementedError(f"GPT.trace with weight_dtype=\"{wd}\" is not implemented: the trace pass is a reference-numerics "
+                                      "pass (init_gpt_for_inference(weight_dtype=\"fp32\"))")
+        prefix = self.engine.prefix_embeddings(cond_latents.to(torch.float32).contiguous(), text_inputs.to(torch.int32).contiguous())
+        B, P, _ = prefix.shape
+        n = int(codes.shape[1])
+        if output_attentions:
+            _trace_bytes_check(self.layers, B, self.heads, P + n, int(max_trace_bytes))
+        lengths = self._code_lengths(codes) if code_lengths is None else torch.as_tensor(code_lengths).to("cpu", torch.int32)
+        slots = torch.arange(B, device=prefix.device, dtype=torch.int32)
+        probs, hidden, align = self.engine.trace(slots, prefix, codes.to(device=prefix.device, dtype=torch.int32), lengths,
+                                                 int(cond_latents.shape[1]), output_attentions=output_attentions,
+                                                 output_hidden_states=output_hidden_states, alignment=True, alignment_layers=alignment_layers)
+        return GenerateOutput(sequences=codes, scores=None, logits=None, latents=None, sequences_scores=None, attentions=probs,
+                              hidden_states=hidden, alignment=align)
 
     @torch.inference_mode()
     def compute_transition_scores(self, sequences, scores, normalize_logits=False):
@@ -732,6 +848,12 @@ class GPT(nn.Module):
         transformers' _sample fills them -- on the sampler paths (greedy, sampling, every processor and warper,
         num_return_sequences, guidance_scale); with beams, beam groups or contrastive search they raise NotImplementedError.  The
         tokens are those of the call without the kwargs, bit for bit.  Without return_dict_in_generate the other two are ignored.
+        output_attentions=True / output_hidden_states=True (with return_dict_in_generate, else ignored as HF ignores them): `attentions`
+        / `hidden_states` in HF's per-step form (GenerateOutput), from one trace pass over the final ids after the
+        loop (gvc_gpt_trace) on the same sampler paths -- under guidance the conditional rows, which are what HF's model call sees.
+        Steps at or past a row's end are zeros (HF returns the attention of its pad inputs there).  Beams, beam groups, contrastive
+        search, assisted and prompt-lookup decoding raise NotImplementedError, as does a context whose weight_dtype is not "fp32";
+        attentions above max_trace_bytes (default 2 GiB) raise ValueError.  The tokens are those of the call without the kwargs.
         sequence_bias / bad_words_ids / forced_eos_token_id / renormalize_logits (engine.logits_bias; include/genvc_hip.h:
         gvc_logits_bias): transformers' SequenceBias, NoBadWords, ForcedEOSToken and LogitNormalization processors at
         their places in HF's list, on the same sampler paths (under guidance on the guided row).  sequence_bias ids may be 0 in both of
@@ -757,17 +879,21 @@ class GPT(nn.Module):
         if _contrastive_kwargs(generate_kwargs) is not None:
             _no_bias(generate_kwargs, f"contrastive search (penalty_alpha={generate_kwargs.get('penalty_alpha')})")
             _no_step_outputs(generate_kwargs, f"contrastive search (penalty_alpha={generate_kwargs.get('penalty_alpha')})")
+            _no_trace(generate_kwargs, f"contrastive search (penalty_alpha={generate_kwargs.get('penalty_alpha')})")
             return self._result(self._generate_contrastive(cond_latents, text_inputs, generate_kwargs), generate_kwargs)
         if int(generate_kwargs.get("num_beams", 1) or 1) > 1 or _grouped(generate_kwargs):
             _no_bias(generate_kwargs, "beam groups (num_beam_groups / diversity_penalty)" if _grouped(generate_kwargs)
                      else f"beam search (num_beams={generate_kwargs.get('num_beams')})")
             _no_step_outputs(generate_kwargs, "beam groups (num_beam_groups / diversity_penalty)" if _grouped(generate_kwargs)
                              else f"beam search (num_beams={generate_kwargs.get('num_beams')})")
+            _no_trace(generate_kwargs, "beam groups (num_beam_groups / diversity_penalty)" if _grouped(generate_kwargs)
+                      else f"beam search (num_beams={generate_kwargs.get('num_beams')})")
             return self._result(self._generate_beams(cond_latents, text_inputs, generate_kwargs), generate_kwargs, beams=True)
         N = _sample_return_kwargs(generate_kwargs, int(text_inputs.shape[0]), self.max_slots)
         fake = self.compute_embeddings(cond_latents, text_inputs)
         if N > 1:
             fake = fake.repeat_interleave(N, 0)
+        self._trace_ready(generate_kwargs, int(fake.shape[0]))
         group = generate_kwargs.pop("group", 16)
 
         attempt = []
@@ -836,6 +962,7 @@ class GPT(nn.Module):
         neg = neg.to(device=dev, dtype=torch.float32).expand(B, -1, -1).contiguous()
         neg_text = neg_text.to(device=dev, dtype=torch.int32).expand(B, -1).contiguous()
         uprefix = self.engine.prefix_embeddings(neg, neg_text)
+        self._trace_ready(kw, B)
         attempt = []
 
         def run():
@@ -1440,7 +1567,8 @@ class GPT(nn.Module):
         ragged lengths take the reference's padding and no attention mask (gpt.py:450)."""
         self._need_engine()
         if return_attentions:
-            raise NotImplementedError("return_attentions: the attention kernels do not keep their weights")
+            raise NotImplementedError("return_attentions: the attention kernels do not keep their weights (GPT.trace runs a pass "
+                                      "that does, for given codes)")
         dev = audio_codes.device
         if return_latent and cond_latents is not None:
             B, n = audio_codes.shape

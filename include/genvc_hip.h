@@ -188,6 +188,42 @@ int gvc_gpt_latents(gvc_gpt* ctx, const int32_t* slots, int32_t B, const float* 
                     const int32_t* gen_codes, int32_t n, int32_t start_tok, int32_t stop_tok,
                     float* out, gvc_stream s);
 
+/* Trace pass: the attention weights, hidden states and content alignment of a generated sequence, by one teacher-forced pass over
+ * rows = [prefix_emb (P) | start, codes 0 .. n-2] of B items (T = P + n rows per item, embedded as gvc_gpt_latents embeds them; row
+ * P + i is the query of generation step i, the one that produced code i).  A full pass without a cache reproduces the per-step rows
+ * of HF's cached loop (output_attentions / output_hidden_states of transformers' generate with eager attention) to fp32 rounding.
+ * Always the launch-per-phase layer loop, with taps between its phases; fp32 contexts only (GVC_ERR_UNSUPPORTED otherwise).
+ *
+ * lengths int32 [B] (device) and lengths_host (the same values, host: the argument check reads them without a synchronisation):
+ * item b's generated length, its stop code counted, in [1, n].  Steps i >= lengths[b] of a finished item fed HF's model a pad
+ * token; their rows mean nothing and are written as zeros here (a deviation from HF, which returns them).
+ *
+ * Outputs (device, each nullable, at least one set; every element is written, no memset needed):
+ *   probs  fp32 [L][B][H][T][T]: (l, b, h, t, k) = softmax weight of query row t on key k in layer l; exactly 0 for k > t; rows
+ *          t >= P + lengths[b] all zeros.
+ *   hidden fp32 [L+1][B][T][D]: plane 0 the embedded rows, plane l (0 < l < L) the residual after layer l, plane L ln_f of the last
+ *          residual -- HF GPT-2's hidden_states (not final_norm(ln_f(.)), which is `latents`); rows t >= P + lengths[b] zeros.
+ *   align  fp32 [B][n][n_content]: the mean over the heads of the chosen layers (layer_mask bit l; 0 = all layers) of the weight step
+ *          i's query (row P + i) puts on the key rows content_off .. content_off + n_content - 1 of the prefix.  For a prefix of
+ *          gvc_gpt_prefix_embeddings = [cond (n_cond) | start text | Tc content codes | stop text] the content rows are
+ *          content_off = n_cond + 1, n_content = Tc: the conditioning rows and the text start / stop rows are not content.  Summed in
+ *          a fixed order (heads inside a layer, layers in order), no atomics: the same input gives the same bits.  Computed layer by
+ *          layer from probs' plane, or with probs null from `scratch` fp32 [B][H][T][T] (required then).
+ * Uses slots[b] as K/V scratch and leaves the slots as gvc_gpt_latents leaves them (length 0).
+ * GVC_ERR_ARG: B > max_slots, B * T > max_rows, T >= max_seq, n > max_mel_pos - 5, a length outside [1, n], content rows outside the
+ * prefix, a layer mask naming a layer the model does not have, no output set. */
+typedef struct gvc_trace_options {
+    int32_t start_tok, stop_tok;          /* start / stop audio token (the stop token embeds nothing here: n - 1 codes are read) */
+    int32_t content_off, n_content;       /* align: the content key rows of the prefix */
+    uint64_t layer_mask;                  /* align: bit l = layer l counts; 0 = every layer */
+    float* probs;
+    float* hidden;
+    float* align;
+    float* scratch;
+} gvc_trace_options;
+int gvc_gpt_trace(gvc_gpt* ctx, const int32_t* slots, int32_t B, const float* prefix_emb, int32_t P, const int32_t* gen_codes, int32_t n,
+                  const int32_t* lengths, const int32_t* lengths_host, const gvc_trace_options* opt, gvc_stream s);
+
 /* The evaluation pass, GPT.forward's default call (gpt.py:375-537; the reference trainer's eval step): a padded batch through the
  * block stack with ALL its text and code rows, then both heads, the losses and the top-k accuracy.  The integer preparation
  * (gpt.py:404-474, 514-518: padding, start / stop tokens, targets, masks) is the caller's (genvc_amd.layers.gpt.forward_eval_prepare).

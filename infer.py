@@ -67,6 +67,9 @@ if __name__ == "__main__":
     parser.add_argument("--token_scores", type=str, default=None, metavar="PATH.npz",
                         help="non-streaming only: write, per segment, the codec tokens and the log-probability of each under the "
                              "distribution it was decoded from (processors, warpers and guidance included)")
+    parser.add_argument("--alignment", type=str, default=None, metavar="PATH.npz",
+                        help="non-streaming only: write, per segment, the attention of every generated acoustic code over the segment's "
+                             "content codes (head / layer mean, GPT.trace), its argmax content position and its attention mass on content")
     parser.add_argument("--assistant_layers", type=int, default=None, metavar="N",
                         help="with --synthetic, non-streaming: assisted (speculative) greedy decoding with a synthetic N-layer draft model "
                              "of the same width (GPT.generate(assistant_model=...)); a demonstration of the mode, not of an acceptance rate")
@@ -126,6 +129,13 @@ if __name__ == "__main__":
             raise SystemExit("--token_scores is not on the streaming path (--streaming): GPT.generate serves the per-step scores")
         if args.num_beams != 1 or args.penalty_alpha is not None or args.num_return_sequences != 1:
             raise SystemExit("--token_scores does not combine with --num_beams, --penalty_alpha or --num_return_sequences")
+    if args.alignment is not None:
+        if args.streaming:
+            raise SystemExit("--alignment is not on the streaming path (--streaming): GPT.trace serves the alignment of finished codes")
+        if args.num_return_sequences != 1:
+            raise SystemExit("--alignment does not combine with --num_return_sequences")
+        if args.weights != "fp32":
+            raise SystemExit(f"--alignment needs --weights fp32 (the trace pass is a reference-numerics pass), not {args.weights}")
     if args.guidance_scale is not None:
         g = args.guidance_scale
         if g != g or g in (float("inf"), float("-inf")):
@@ -259,7 +269,8 @@ if __name__ == "__main__":
             lat = torch.cat(out["latents"], 1)
         else:
             out = synthesize_utt(model, src_wav, ref_audio, seg_len=args.seg_len, return_details=True, num_beams=args.num_beams,
-                                 generate_kwargs=gen_kw or None, token_scores=args.token_scores is not None, **guide_kw)
+                                 generate_kwargs=gen_kw or None, token_scores=args.token_scores is not None,
+                                 alignment=args.alignment is not None, **guide_kw)
             toks = torch.cat(out["codes"]).unsqueeze(0)
             lat = out["latents"]
             if args.token_scores is not None:
@@ -268,6 +279,12 @@ if __name__ == "__main__":
                          **{f"tokens_{i}": c.cpu().numpy() for i, c in enumerate(out["codes"])},
                          **{f"logprobs_{i}": lp.cpu().numpy() for i, lp in enumerate(out["token_logprobs"])})
                 print(f"{args.token_scores}: tokens and log-probabilities of {len(out['codes'])} segments")
+            if args.alignment is not None:
+                import numpy as np
+                al = [a.cpu().numpy() for a in out["alignments"]]
+                np.savez(args.alignment, n_segments=len(al), **{f"alignment_{i}": a for i, a in enumerate(al)},
+                         **{f"argmax_{i}": a.argmax(1) for i, a in enumerate(al)}, **{f"mass_{i}": a.sum(1) for i, a in enumerate(al)})
+                print(f"{args.alignment}: alignment of {len(al)} segments, shapes {[a.shape for a in al]}")
         print(f"generated {toks.shape[-1]} codec tokens, latents {tuple(lat.shape)}")
         if args.decode_codes_to_mel is not None:
             import numpy as np
