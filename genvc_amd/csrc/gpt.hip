@@ -880,19 +880,27 @@ static int persist_test_grid() {
 // the instantiation that serves this context: d_model / 256, bf16 weight storage, bf16 KV cache (bf16 rows are streamed in whole
 // KiB per workgroup and phase, which needs an even d_model / 256)
 typedef void (*persist_fn)(const PersistArgs);
-static persist_fn persist_kernel(const gvc_gpt* c) {
-    const int nd = c->dm.d_model / 256;
+// d_model 1024: the stamping variant (STAMPS = true) only when the stamp buffer exists (GVC_PERSIST_STAMPS; persist_prepare allocates
+// it for d_model 1024 alone), the production variant otherwise
+template <bool STAMPS>
+static persist_fn persist_kernel_1024(const gvc_gpt* c) {
     // p_xl = 0 (GVC_PERSIST_XCD=0, or a device that does not deal 8 XCDs x 32 workgroups: persist_prepare's probe): d_model 1024 keeps the
     // device-wide hand-off of the hidden units (the round-3 kernel)
-    if (nd == 4 && c->p_xl) {
-        if (c->kv_bf16) return (persist_fn)k_decode_persist<4, 1, 1, 1>;
-        if (c->bf16) return (persist_fn)k_decode_persist<4, 1, 0, 1>;
-        return (persist_fn)k_decode_persist<4, 0, 0, 1>;
+    if (c->p_xl) {
+        if (c->kv_bf16) return (persist_fn)k_decode_persist<4, 1, 1, 1, STAMPS>;
+        if (c->bf16) return (persist_fn)k_decode_persist<4, 1, 0, 1, STAMPS>;
+        return (persist_fn)k_decode_persist<4, 0, 0, 1, STAMPS>;
     }
-    if (c->kv_bf16) return nd == 4 ? (persist_fn)k_decode_persist<4, 1, 1> : (persist_fn)k_decode_persist<2, 1, 1>;
-    if (c->bf16) return nd == 4 ? (persist_fn)k_decode_persist<4, 1, 0> : (persist_fn)k_decode_persist<2, 1, 0>;
-    return nd == 4 ? (persist_fn)k_decode_persist<4> : nd == 3 ? (persist_fn)k_decode_persist<3> : nd == 2 ? (persist_fn)k_decode_persist<2>
-                                                                                                              : (persist_fn)k_decode_persist<1>;
+    if (c->kv_bf16) return (persist_fn)k_decode_persist<4, 1, 1, 0, STAMPS>;
+    if (c->bf16) return (persist_fn)k_decode_persist<4, 1, 0, 0, STAMPS>;
+    return (persist_fn)k_decode_persist<4, 0, 0, 0, STAMPS>;
+}
+static persist_fn persist_kernel(const gvc_gpt* c) {
+    const int nd = c->dm.d_model / 256;
+    if (nd == 4) return c->p_dbg ? persist_kernel_1024<true>(c) : persist_kernel_1024<false>(c);
+    if (c->kv_bf16) return (persist_fn)k_decode_persist<2, 1, 1>;
+    if (c->bf16) return (persist_fn)k_decode_persist<2, 1, 0>;
+    return nd == 3 ? (persist_fn)k_decode_persist<3> : nd == 2 ? (persist_fn)k_decode_persist<2> : (persist_fn)k_decode_persist<1>;
 }
 
 // one stream, fp32 weights and cache, a full MI355X (one workgroup per CU)
@@ -973,7 +981,7 @@ static int persist_prepare(gvc_gpt* c) {
     if (hipMalloc((void**)&c->p_gran, ngran * sizeof(pu64)) != hipSuccess || hipMemset(c->p_gran, 0, ngran * sizeof(pu64)) != hipSuccess ||
         hipMalloc((void**)&c->p_epoch, 16 * sizeof(unsigned)) != hipSuccess || hipMemset(c->p_epoch, 0, 16 * sizeof(unsigned)) != hipSuccess)
         return unavailable();
-    if (getenv("GVC_PERSIST_STAMPS")) {
+    if (getenv("GVC_PERSIST_STAMPS") && d == 1024) {        // (the stamping variant is instantiated for d_model 1024: persist_kernel)
         const size_t nb = (size_t)(20 * (L + 2) + 2 * 5 * kPG + 8 * kPG) * sizeof(unsigned long long);
         if (hipMalloc((void**)&c->p_dbg, nb) != hipSuccess || hipMemset(c->p_dbg, 0, nb) != hipSuccess) return unavailable();
     }
@@ -2969,6 +2977,35 @@ extern "C" long long gvc_gpt_one_stream_steps(gvc_gpt* c) {
 // cleanly; otherwise the state error of check_ready (a timed-out hand-off has switched the context to the launch-per-phase paths,
 // a full KV cache / position table).  Without it such an error surfaces on the next library call.
 extern "C" int gvc_gpt_health(gvc_gpt* c) { return check_ready(c); }
+
+// debug / tests: the cached K and V rows of ONE position of one slot, every layer, to the host: host_out[layer][k | v][head][head_dim] in the
+// cache's element type (fp32, or bf16 for a bf16 cache).  Returns the bytes written, or a negative error.  Synchronises the device.
+extern "C" long long gvc_gpt_debug_kv_row(gvc_gpt* c, int32_t slot, int32_t pos, void* host_out) {
+    if (!c || !c->kv || !host_out || slot < 0 || slot >= c->dm.max_slots || pos < 0 || pos >= c->dm.max_seq) return GVC_ERR_ARG;
+    if (hipDeviceSynchronize() != hipSuccess) return GVC_ERR_HIP;
+    const size_t esz = c->kv_bf16 ? 2 : 4, row = (size_t)c->hd * esz;
+    const int H = c->dm.n_head;
+    char* out = static_cast<char*>(host_out);
+    for (int l = 0; l < c->dm.n_layer; ++l)
+        for (int which = 0; which < 2; ++which)
+            for (int h = 0; h < H; ++h) {       // cache layout: [slot][head][max_seq][head_dim] per (layer, k | v)
+                const char* src = reinterpret_cast<const char*>(kv_layer(c, l, which)) + (((size_t)slot * H + h) * c->dm.max_seq + pos) * row;
+                if (hipMemcpy(out, src, row, hipMemcpyDeviceToHost) != hipSuccess) return GVC_ERR_HIP;
+                out += row;
+            }
+    return (long long)(out - static_cast<char*>(host_out));
+}
+
+// debug / tests: the logits [vocab] and latent [d_model] parked for one slot between calls, to the host.  Synchronises the device.
+extern "C" int gvc_gpt_debug_parked(gvc_gpt* c, int32_t slot, float* logits_host, float* latent_host) {
+    if (!c || !c->slot_logits || !c->slot_latent || !logits_host || !latent_host || slot < 0 || slot >= c->dm.max_slots) return GVC_ERR_ARG;
+    if (hipDeviceSynchronize() != hipSuccess) return GVC_ERR_HIP;
+    const size_t V = (size_t)c->dm.vocab, d = (size_t)c->dm.d_model;
+    if (hipMemcpy(logits_host, c->slot_logits + slot * V, V * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(latent_host, c->slot_latent + slot * d, d * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
+        return GVC_ERR_HIP;
+    return GVC_OK;
+}
 
 // debug: copy the in-kernel timestamps of the GEMV launches since the last call (GVC_DEBUG_STAMPS=1)
 extern "C" int gvc_gpt_debug_stamps(gvc_gpt* c, unsigned long long* host_out, int32_t max_launches) {

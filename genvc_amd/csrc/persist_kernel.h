@@ -108,6 +108,60 @@ struct PCtx {
     bool dead;
 };
 
+// Scalar live ranges of the one-stream kernel.  PersistArgs arrives by value: the compiler loads the kernel arguments at entry, keeps all
+// of them alive across the layer loop, runs out of scalar registers and parks the rest in VGPR lanes, so that every use inside the loop is
+// a lane read (profiles/decode_scalar_spills.md).  The kernel therefore reads its arguments where it needs them, through the
+// kernel-argument segment (PersistArgs is the only argument: it sits at offset 0; scalar loads, at the kernel's entry and in the head
+// only), and a layer's pointers phase by phase.  The empty asm makes each pointer a new value for the compiler: loads through it can
+// neither be hoisted above that point nor merged with the loads of another phase, so a value lives from there to its last use.
+// The layer table is read with VECTOR loads, as before, NOT through the constant address space: scalar loads share their counter with
+// the LDS reads, so every LDS wait of the phase also waits for the table's line to come from L2, and 120 of them per step made the step
+// 6-15 us SLOWER than the parent where vector loads make it 18 us faster (measured, same note).
+#define GVC_CONSTANT_AS __attribute__((address_space(4)))
+typedef const GVC_CONSTANT_AS PersistArgs* PArgsK;
+typedef const PersistLayer* PLayerK;
+#undef GVC_CONSTANT_AS
+__device__ __forceinline__ PArgsK persist_args() {
+    PArgsK p = (PArgsK)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return p;
+}
+__device__ __forceinline__ PLayerK persist_layer(const PersistLayer* layers, int l) {
+    PLayerK p = (PLayerK)(layers + l);
+    asm volatile("" : "+s"(p));
+    return p;
+}
+// what the consumer waves need of a layer's table entry (the weight matrices are the loader wave's business)
+struct PLayerPtrs {
+    const float *ln1_w, *ln1_b, *qkv_b, *proj_b, *ln2_w, *ln2_b, *fc_b, *p2_b;
+    float *kcache, *vcache;
+};
+// phase A's part of it (read in phase E of the layer before; the other phases' parts are single lines in the kernel)
+__device__ __forceinline__ void persist_layer_ptrs_a(PLayerPtrs& r, const PersistLayer* layers, int l) {
+    const PLayerK p = persist_layer(layers, l);
+    r.ln1_w = p->ln1_w; r.ln1_b = p->ln1_b; r.qkv_b = p->qkv_b; r.kcache = p->kcache; r.vcache = p->vcache;
+}
+// a wave-uniform value as a new one for the compiler: what is computed from it stays where it is computed
+__device__ __forceinline__ int fresh_uniform(int v) {
+    v = __builtin_amdgcn_readfirstlane(v);      // (a value the compiler cannot prove uniform, such as one loaded through a pointer)
+    asm volatile("" : "+s"(v));
+    return v;
+}
+
+// key chunks of the unfused attention phases B and C (contexts of more than kPUF * kPCW keys), computed inside those phases
+struct PChunks {
+    int lpk, kpw;                   // lanes per key row, keys per wave-instruction
+    int pass_keys, kc, nchunks;
+};
+__device__ __forceinline__ PChunks persist_chunks(int hd, int n_keys) {
+    PChunks k;
+    k.lpk = hd >> 2; k.kpw = 64 / k.lpk;
+    k.pass_keys = kPU * kPCW * k.kpw;
+    k.kc = max(k.pass_keys, (n_keys + kPMaxChunks - 1) / kPMaxChunks);
+    k.nchunks = (n_keys + k.kc - 1) / k.kc;
+    return k;
+}
+
 __device__ __forceinline__ unsigned lds_ld(const unsigned* p) {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
@@ -182,8 +236,9 @@ __device__ __forceinline__ void publish_local(__amdgpu_buffer_rsrc_t rs, int ind
 // j * 128 kPCW, j < NJ.  Sweeps of more than two loads per lane poll a sentinel first (load j = 0 of the last plane) and issue
 // the other loads when its tags have arrived (everything is re-issued if a tag is still old); one- and two-load sweeps re-read
 // everything in every poll pass, which saves a round trip (measured: 612 vs 630 us per step at 110-250 keys).  n is a multiple of 128.
-// gd (diagnostics, GVC_PERSIST_STAMPS): [0] entry, [1] sentinel seen, [2] done (wall clock), [3] sentinel polls, [4] sweep passes
-template <int NJ, int NP>
+// GD (diagnostics, the stamping variant of the kernel only): gd[0] entry, [1] sentinel seen, [2] done (wall clock), [3] sentinel polls,
+// [4] sweep passes; without GD the sweep carries neither the pointer nor the counters
+template <int NJ, int NP, bool GD = false>
 __device__ __forceinline__ void gather(PCtx& c, __amdgpu_buffer_rsrc_t rs, int base, int n, unsigned tag, float* dst, int code, int sleep = 3,
                                        unsigned long long* gd = nullptr) {
     if (c.dead || c.wave * 128 >= n) return;         // a wave is all in or all out
@@ -194,17 +249,17 @@ __device__ __forceinline__ void gather(PCtx& c, __amdgpu_buffer_rsrc_t rs, int b
     pu32x4 v[NJ][NP];
     constexpr bool kSentinel = NJ > 1 || NP > 2;      // one load per lane on <= 2 planes: every poll pass reads everything (one round trip less)
     unsigned npoll = 0, npass = 0;
-    if (gd) gd[0] = wall_clock64();
+    if constexpr (GD) { if (gd) gd[0] = wall_clock64(); }
     while (kSentinel) {
         v[0][NP - 1] = __builtin_amdgcn_raw_buffer_load_b128(rs, voff, (NP - 1) * n * 8, 16);
-        ++npoll;
+        if constexpr (GD) ++npoll;
         if (__all(v[0][NP - 1].y == tag && v[0][NP - 1].w == tag)) break;
         if (spin_fail(c, spins, code, 3)) return;
     }
-    if (gd) { gd[1] = wall_clock64(); gd[3] = npoll; }
+    if constexpr (GD) { if (gd) { gd[1] = wall_clock64(); gd[3] = npoll; } }
     while (true) {
         unsigned bad = 0;
-        ++npass;
+        if constexpr (GD) ++npass;
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
             if (j == 0 || c.wave * 128 + j * JT < n) {
@@ -223,7 +278,7 @@ __device__ __forceinline__ void gather(PCtx& c, __amdgpu_buffer_rsrc_t rs, int b
         if (!__any(bad != 0u)) break;
         if (spin_fail(c, spins, code, sleep)) return;
     }
-    if (gd) { gd[2] = wall_clock64(); gd[4] = npass; }
+    if constexpr (GD) { if (gd) { gd[2] = wall_clock64(); gd[4] = npass; } }
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
         if (j == 0 || c.wave * 128 + j * JT < n) {
@@ -371,25 +426,25 @@ __device__ __forceinline__ void persist_loader(const PersistArgs& A, PCtx& c, ch
         bool rowpair = false;                        // a row piece is TWO consecutive KiB (kib_stride then counts rows)
         auto wptr = [&](const float* w, size_t elems) { return reinterpret_cast<const char*>(w) + ((elems * 4) >> WB); };
         if (sgi < 4 * A.n_layer) {
-            const PersistLayer& Ly = A.layers[sgi >> 2];
+            const PLayerK Ly = persist_layer(A.layers, sgi >> 2);
             const int ph = sgi & 3;
-            if (ph == 0) { base = wptr(Ly.qkv_w, (size_t)c.wg * (3 * ND) * D); bytes = (3 * ND * D * 4) >> WB; }
+            if (ph == 0) { base = wptr(Ly->qkv_w, (size_t)c.wg * (3 * ND) * D); bytes = (3 * ND * D * 4) >> WB; }
             else if (ph == 1 && fused) {             // rows [i RF, (i+1) RF) x the 256-element K-slice of head h
                 const int h = c.wg % A.n_head, i = c.wg / A.n_head, RF = ND * A.n_head;
-                base = wptr(Ly.proj_w, (size_t)i * RF * D + h * 256); bytes = (RF * 1024) >> WB; kib_stride = D * 4;
+                base = wptr(Ly->proj_w, (size_t)i * RF * D + h * 256); bytes = (RF * 1024) >> WB; kib_stride = D * 4;
                 // fp32: one KiB per row; bf16: a KiB of the segment is TWO rows' 512-byte slices (lanes 32.. take the second)
                 if (WB) lane_off = (c.lane >> 5) * (D * 2) + (c.lane & 31) * 16;
             }
-            else if (ph == 1) { base = wptr(Ly.proj_w, (size_t)c.wg * ND * D); bytes = (ND * D * 4) >> WB; }
+            else if (ph == 1) { base = wptr(Ly->proj_w, (size_t)c.wg * ND * D); bytes = (ND * D * 4) >> WB; }
             else if (ph == 2) {
                 const int dwg = XL ? xx * 32 + jj : c.wg;          // XL: the XCD's workgroups own 512 consecutive hidden units
-                base = wptr(Ly.fc_w, (size_t)dwg * (4 * ND) * D); bytes = (4 * ND * D * 4) >> WB;
+                base = wptr(Ly->fc_w, (size_t)dwg * (4 * ND) * D); bytes = (4 * ND * D * 4) >> WB;
             }
             else if (XL) {       // rows [32 j, +32) x the XCD's K-slice [512 x, +512) of mlp c_proj: 2 KiB (bf16: 1 KiB) per row
-                base = wptr(Ly.p2_w, (size_t)(32 * jj) * (4 * D) + 512 * xx); bytes = (32 * 2048) >> WB;
+                base = wptr(Ly->p2_w, (size_t)(32 * jj) * (4 * D) + 512 * xx); bytes = (32 * 2048) >> WB;
                 kib_stride = (4 * D * 4) >> WB; rowpair = !WB;
             }
-            else { base = wptr(Ly.p2_w, (size_t)c.wg * ND * (4 * D)); bytes = (ND * 4 * D * 4) >> WB; }
+            else { base = wptr(Ly->p2_w, (size_t)c.wg * ND * (4 * D)); bytes = (ND * 4 * D * 4) >> WB; }
         } else if (sgi == 4 * A.n_layer) {
             base = wptr(A.head_w, (size_t)c.wg * rm * D); bytes = (rm * D * 4) >> WB;
         } else {
@@ -452,7 +507,9 @@ __device__ __forceinline__ void persist_loader(const PersistArgs& A, PCtx& c, ch
 }
 
 // ---- decode-step kernel --------------------------------------------------------------------------------------
-template <int ND, int WB = 0, int KVB = 0, int XL = 0>      // d_model = 256 * ND; bf16 weight storage; bf16 KV cache; XCD-local MLP hand-off
+// d_model = 256 * ND; bf16 weight storage; bf16 KV cache; XCD-local MLP hand-off; STAMPS: the diagnostics variant (GVC_PERSIST_STAMPS,
+// PersistArgs::dbg allocated) -- the production variant holds no timestamp read, no stamp test and none of the scalars they keep alive
+template <int ND, int WB = 0, int KVB = 0, int XL = 0, bool STAMPS = false>
 __global__ __launch_bounds__(kPThreads) void k_decode_persist(const PersistArgs A) {
     static_assert(!XL || ND == 4, "the XCD-local MLP hand-off is laid out for d_model 1024 (8 XCDs x 32 workgroups)");
     constexpr int D = 256 * ND;
@@ -461,13 +518,15 @@ __global__ __launch_bounds__(kPThreads) void k_decode_persist(const PersistArgs 
     constexpr int KSE = 2;                       // K-split of an mlp c_proj row (planes of X1)
     constexpr int NJX = (D + kPCW * 128 - 1) / (kPCW * 128);        // 16-byte loads per lane and plane in a sweep over a d-vector
     extern __shared__ __attribute__((aligned(16))) float smem[];      // (same declaration as k_gemv's)
+    (void)A;                                     // read through persist_args() where a phase needs it (see there)
+    const PArgsK K0 = persist_args();
     char* ring = reinterpret_cast<char*>(smem);
-    float* hvec = reinterpret_cast<float*>(ring + (size_t)A.ring_slots * kPSlot);      // [4D] mlp hidden units
+    float* hvec = reinterpret_cast<float*>(ring + (size_t)K0->ring_slots * kPSlot);      // [4D] mlp hidden units
     float* ovec = hvec;                          // [D] merged attention output: hvec is idle between E of a layer and E of the next
     float* o_s = hvec + D;                       // attention lane-group states [NG][hd] (phase B; same idle window)
-    float* xvec = hvec + A.hvec_floats;          // [D] phase input (x / x')
+    float* xvec = hvec + K0->hvec_floats;         // [D] phase input (x / x')
     float* ascr = xvec + D;                      // attention: q_h | k_h | v_h of this step, then m_s, l_s
-    unsigned* ctl = reinterpret_cast<unsigned*>(ascr + A.ascr_floats);
+    unsigned* ctl = reinterpret_cast<unsigned*>(ascr + K0->ascr_floats);
     if (threadIdx.x < kCtlWords) ctl[threadIdx.x] = 0u;
     // Deferred decode (gpt.hip: the generation loop runs [decode the pending token, sample]): the launch is in the captured graph whether
     // or not a token is pending; the run flag says which.  Nothing writes the flag while this grid runs (the begin kernel of the call / the
@@ -477,23 +536,23 @@ __global__ __launch_bounds__(kPThreads) void k_decode_persist(const PersistArgs 
     // arrival counter and the per-XCD rank counters at zero (the last workgroup to arrive stores zeros, as after a full step; the ranks
     // were never raised), and that no granule carries the tag of a LATER step.  The epoch is bumped as after a full step, so the next step
     // expects tags (epoch + 2, ...) that no launch has written yet; an early exit writes no granule at all.
-    const bool run = !A.run || __hip_atomic_load(A.run, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
+    const bool run = !K0->run || __hip_atomic_load(K0->run, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
     // XL: this workgroup's XCD and its rank among the XCD's workgroups (requested here, used after the barrier)
     unsigned xcc = 0, xrank = 0;
     if (XL && run && threadIdx.x == kPCW * 64) {
         asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
         xcc &= 7u;
-        xrank = __hip_atomic_fetch_add(A.epoch + 4 + xcc, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        xrank = __hip_atomic_fetch_add(K0->epoch + 4 + xcc, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         // more than 32 workgroups of this grid on one XCD (CU masking, another partition mode, an uneven deal): the XCD-local layout does
         // not hold.  Reported like a hand-off time-out (the ranks that are missing elsewhere time out anyway): the host drops the call
-        if (xrank >= 32u) __hip_atomic_store(A.err, 961, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        if (xrank >= 32u) __hip_atomic_store(K0->err, 961, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
     __syncthreads();
 
     PCtx c;
     c.lane = threadIdx.x & 63; c.wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); c.wg = blockIdx.x;
-    c.ctl = ctl; c.err = A.err; c.bar_target = 0; c.filled_seen = 0; c.dead = false;
-    const unsigned epoch = __hip_atomic_load(A.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    c.ctl = ctl; c.err = K0->err; c.bar_target = 0; c.filled_seen = 0; c.dead = false;
+    const unsigned epoch = __hip_atomic_load(K0->epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 
     if (c.wave == kPCW) {
         int xx = 0, jj = 0;
@@ -505,29 +564,35 @@ __global__ __launch_bounds__(kPThreads) void k_decode_persist(const PersistArgs 
         if (run) persist_loader<ND, WB, XL>(A, c, ring, xx, jj);
     } else if (run) {
         // `lane` is re-defined through an empty asm at every phase: without it the compiler hoists the per-lane addresses of all
-        // phases out of the layer loop and spills them to scratch (vector memory behind the loader's DMA queue)
+        // phases out of the layer loop and spills them to scratch (vector memory behind the loader's DMA queue).  The same holds for what
+        // is wave-uniform: hoisted out of the loop, the row numbers, offsets and LDS addresses that every phase derives from the wave, the
+        // workgroup and the LDS layout are a few hundred scalars, kept in VGPR lanes and read back one by one inside the phases.  So the
+        // wave, the workgroup and the LDS offsets are re-defined too, and a phase derives its LDS pointers from them (a few scalar
+        // additions per phase)
         int& lane = c.lane;
-        const int wave = c.wave, wg = c.wg;
-#define GVC_PHASE_BEGIN() asm volatile("" : "+v"(c.lane))
-        const unsigned rmask = A.ring_slots - 1;
-        const int H = A.n_head, hd = A.head_dim;
-        const int slot = A.slots[0];
-        const int S = A.st.seq_len[slot];                // cached positions; this step's key goes to index S
-        float* const logits_out = A.per_slot ? A.logits_out + (size_t)slot * A.vocab : A.logits_out;
-        float* const latent_out = A.per_slot ? A.latent_out + (size_t)slot * D : A.latent_out;
+        int &wave = c.wave, &wg = c.wg;
+        int o_hvec = (int)(reinterpret_cast<float*>(hvec) - smem), o_xvec = (int)(xvec - smem), o_ctl = (int)(reinterpret_cast<float*>(ctl) - smem);
+#define GVC_PHASE_BEGIN()                                                                                                       \
+        asm volatile("" : "+v"(c.lane));     /* (an asm of its own: scalar outputs beside a vector one did not compile at d_model 768) */ \
+        asm volatile("" : "+s"(c.wave), "+s"(c.wg), "+s"(o_hvec), "+s"(o_xvec), "+s"(o_ctl));                                     \
+        float* const hvec = smem + o_hvec; float* const ovec = hvec; float* const o_s = hvec + D;                                 \
+        float* const xvec = smem + o_xvec; float* const ascr = xvec + D;                                                          \
+        c.ctl = reinterpret_cast<unsigned*>(smem + o_ctl);                                                                        \
+        (void)ovec; (void)o_s; (void)ascr
+        // what the layer loop needs of the arguments; the embedding's and the head's are read there
+        const PArgsK K = persist_args();
+        const unsigned rmask = K->ring_slots - 1;
+        const int H = K->n_head, hd = K->head_dim, n_layer = K->n_layer, max_seq = K->max_seq;
+        const PersistLayer* const layers = K->layers;
+        const int slot = K->slots[0];
+        const int S = K->st.seq_len[slot];               // cached positions; this step's key goes to index S
         const int n_keys = S + 1;
-        const int lpk = hd >> 2, kpw = 64 / lpk;         // lanes per key row, keys per wave-instruction
-        const int pass_keys = kPU * kPCW * kpw;
-        const int kc = max(pass_keys, (n_keys + kPMaxChunks - 1) / kPMaxChunks);
-        const int nchunks = (n_keys + kc - 1) / kc;
         const bool fused = persist_fused_attn(H, hd, n_keys);
-        const bool is_attn = !fused && wg < H * nchunks;
-        const int ah = wg / nchunks, ac = wg - ah * nchunks;
         const float scale = 1.0f / sqrtf((float)hd);
         const int PS = D + 2 * H;                        // granules per key chunk: o[D] | {m, l}[H]
         // granule indices of the five hand-off buffers inside the allocation
         const int iQ = 0, iP = 3 * D, iX0 = iP + kPMaxChunks * PS, iH = iX0 + 4 * D, iX1 = iH + 4 * D;
-        const __amdgpu_buffer_rsrc_t grs = make_rsrc(A.gran, (unsigned)(iX1 + 8 * D) * 8u);
+        const __amdgpu_buffer_rsrc_t grs = make_rsrc(K->gran, (unsigned)(iX1 + 8 * D) * 8u);
         int xx = 0, jj = 0;              // XL: XCD and rank inside it (the loader wave publishes them through LDS)
         auto need_xcd = [&]() {
             if (!XL || xx >= 0x100) return;
@@ -541,11 +606,15 @@ __global__ __launch_bounds__(kPThreads) void k_decode_persist(const PersistArgs 
         auto tag_of = [&](int l, int p) { return tbase | (unsigned)(l * 8 + p + 1); };
         // stamps (GVC_PERSIST_STAMPS): workgroup 0, every layer: [(l * 5 + p) * 4 + k], k = 0 input ready, 1 output published,
         // 2 / 3 extra; every workgroup, layer 2: [base2 + (wg * 5 + p) * 2 + k]
-        const bool stamp0 = A.dbg && wave == 0 && lane == 0;
-        const int base2 = 4 * 5 * (A.n_layer + 2);
+        unsigned long long* dbg = nullptr;
+        if constexpr (STAMPS) dbg = K->dbg;
+        const bool stamp0 = STAMPS && dbg && wave == 0 && lane == 0;
+        const int base2 = 4 * 5 * (n_layer + 2);
         auto stamp_at = [&](int l, int p, int k) {
-            if (stamp0 && wg == 0) A.dbg[(l * 5 + p) * 4 + k] = wall_clock64();
-            if (stamp0 && l == kPStampLayer && k < 2) A.dbg[base2 + (wg * 5 + p) * 2 + k] = wall_clock64();
+            if constexpr (STAMPS) {
+                if (stamp0 && wg == 0) dbg[(l * 5 + p) * 4 + k] = wall_clock64();
+                if (stamp0 && l == kPStampLayer && k < 2) dbg[base2 + (wg * 5 + p) * 2 + k] = wall_clock64();
+            }
         };
         unsigned fs = 0;                                 // first fill of the current weight segment
         constexpr unsigned nfA = (((3 * ND * D * 4) >> WB) + kPSlot - 1) / kPSlot, nfC = (((ND * D * 4) >> WB) + kPSlot - 1) / kPSlot,
@@ -555,25 +624,34 @@ __global__ __launch_bounds__(kPThreads) void k_decode_persist(const PersistArgs 
 
         // ---- x = mel_embedding[tok] + mel_pos_embedding[pos]  (gpt_inference.py:92-96), by every workgroup ----
         if (wave < ND) {
-            const float* e = A.mel_emb + (size_t)min(max(A.tok_in[0], 0), A.vocab - 1) * D + wave * 256 + lane * 4;
-            const float* p = A.mel_pos + (size_t)A.st.mel_pos[slot] * D + wave * 256 + lane * 4;
+            const float* e = K->mel_emb + (size_t)min(max(K->tok_in[0], 0), K->vocab - 1) * D + wave * 256 + lane * 4;
+            const float* p = K->mel_pos + (size_t)K->st.mel_pos[slot] * D + wave * 256 + lane * 4;
             const float4 ev = *reinterpret_cast<const float4*>(e), pv = *reinterpret_cast<const float4*>(p);
             *reinterpret_cast<float4*>(xvec + wave * 256 + lane * 4) = make_float4(ev.x + pv.x, ev.y + pv.y, ev.z + pv.z, ev.w + pv.w);
         }
-        if (stamp0 && wg == 0) A.dbg[4 * 5 * (A.n_layer + 1)] = wall_clock64();      // kernel entry
+        if constexpr (STAMPS) {
+            if (stamp0 && wg == 0) dbg[4 * 5 * (n_layer + 1)] = wall_clock64();      // kernel entry
+        }
 
-        for (int l = 0; l < A.n_layer; ++l) {
-            const PersistLayer& Ly = A.layers[l];
+        // A phase's pointers are read ONE PHASE AHEAD, at the start of the phase before (phase A's in phase E of the layer before): a
+        // load at the start of the phase that uses them sits in front of that phase's own loads, on the path of the workgroup the others
+        // wait for; a whole layer's pointers read at once are sixteen more scalars alive across every phase
+        PLayerPtrs Ly = {};
+        if (n_layer > 0) persist_layer_ptrs_a(Ly, layers, 0);
+        for (int l = 0; l < n_layer; ++l) {
             // =================== A: LN1 -> c_attn rows -> q | k | v ===================
             // row (wave + 8 i) of the workgroup's 3 ND rows belongs to wave `wave`
             {
                 GVC_PHASE_BEGIN();
                 float4 g[ND], b[ND], xv[ND];
+                Ly.proj_b = persist_layer(layers, l)->proj_b;        // (for B / BC / C)
                 load_gb<ND>(Ly.ln1_w, Ly.ln1_b, lane, g, b);
                 constexpr int RA = 3 * ND, UPW = (RA + kPCW - 1) / kPCW;
                 const int nmy = wave < RA ? (RA - wave + kPCW - 1) / kPCW : 0;
                 const int row_g = wg * RA + wave + kPCW * lane;
                 const float bias = lane < nmy ? Ly.qkv_b[row_g] : 0.f;
+                float* const kcache = Ly.kcache;
+                float* const vcache = Ly.vcache;
                 if (l > 0) gather<NJX, NPX>(c, grs, iX1, D, tag_of(l - 1, 4), xvec, 100 + l, 3, nullptr);
                 cbar(c);
                 stamp_at(l, 0, 0);
@@ -601,8 +679,8 @@ __global__ __launch_bounds__(kPThreads) void k_decode_persist(const PersistArgs 
                     if (row_g >= D) {            // append k / v of this position to the cache (read by later steps)
                         const int which = row_g / D, ci = row_g - which * D;
                         const int h = ci / hd, j = ci - h * hd;
-                        float* cache = which == 1 ? Ly.kcache : Ly.vcache;
-                        const size_t e = (((size_t)slot * H + h) * A.max_seq + S) * hd + j;
+                        float* cache = which == 1 ? kcache : vcache;
+                        const size_t e = (((size_t)slot * H + h) * max_seq + S) * hd + j;
                         if (KVB) reinterpret_cast<unsigned short*>(cache)[e] = (unsigned short)(__float_as_uint(val) >> 16);
                         else cache[e] = val;
                     }
@@ -612,14 +690,27 @@ __global__ __launch_bounds__(kPThreads) void k_decode_persist(const PersistArgs 
                 stamp_at(l, 0, 1);
             }
             // =================== B: attention over one key chunk of one head (a few workgroups) ===================
+            // (B and C are off the short contexts' path: their chunk arithmetic is done inside them, layer by layer, so that nothing of
+            // it lives across the loop)
+            bool is_attn = false;
+            PChunks ckB = {};
+            int hd_l = hd, H_l = H;
+            if (!fused) {
+                hd_l = fresh_uniform(hd); H_l = fresh_uniform(H);
+                ckB = persist_chunks(hd_l, fresh_uniform(n_keys));
+                is_attn = wg < H_l * ckB.nchunks;
+            }
             if (is_attn) {
+                const int hd = hd_l, H = H_l;
                 GVC_PHASE_BEGIN();
+                const int lpk = ckB.lpk, kpw = ckB.kpw, pass_keys = ckB.pass_keys, kc = ckB.kc, nchunks = ckB.nchunks;
+                const int ah = wg / nchunks, ac = wg - ah * nchunks;
                 const int kl = lane / lpk, dl = (lane - kl * lpk) * 4;
                 const int k0 = ac * kc, k1 = min(S, k0 + kc);            // cached keys of this chunk
                 // this head's rows of the layer's K / V cache as buffers: one per-lane offset serves every key of a pass
                 constexpr int ESZ = KVB ? 2 : 4;                             // bytes per cache element
-                const unsigned head_bytes = (unsigned)A.max_seq * hd * ESZ;
-                const size_t head_off = ((size_t)slot * H + ah) * A.max_seq * hd * ESZ;
+                const unsigned head_bytes = (unsigned)max_seq * hd * ESZ;
+                const size_t head_off = ((size_t)slot * H + ah) * max_seq * hd * ESZ;
                 const __amdgpu_buffer_rsrc_t krs = make_rsrc(reinterpret_cast<const char*>(Ly.kcache) + head_off, head_bytes);
                 const __amdgpu_buffer_rsrc_t vrs = make_rsrc(reinterpret_cast<const char*>(Ly.vcache) + head_off, head_bytes);
                 const int kv_step = kPCW * kpw * hd * ESZ;                   // bytes between the keys u and u + 1 of a lane
@@ -748,10 +839,14 @@ __global__ __launch_bounds__(kPThreads) void k_decode_persist(const PersistArgs 
             // =================== BC (short contexts): attention of head h + its K-slice of attn c_proj, every workgroup ===================
             if (fused) {
                 GVC_PHASE_BEGIN();
+                {       // (for D)
+                    const PLayerK T = persist_layer(layers, l);
+                    Ly.ln2_w = T->ln2_w; Ly.ln2_b = T->ln2_b; Ly.fc_b = T->fc_b;
+                }
                 const int fh = wg % H, fi = wg / H, RF = ND * H;        // head, row block, rows of the block
                 constexpr int ESZ = KVB ? 2 : 4;
-                const unsigned head_bytes = (unsigned)A.max_seq * 256u * ESZ;
-                const size_t head_off = ((size_t)slot * H + fh) * A.max_seq * 256 * ESZ;
+                const unsigned head_bytes = (unsigned)max_seq * 256u * ESZ;
+                const size_t head_off = ((size_t)slot * H + fh) * max_seq * 256 * ESZ;
                 const __amdgpu_buffer_rsrc_t krs = make_rsrc(reinterpret_cast<const char*>(Ly.kcache) + head_off, head_bytes);
                 const __amdgpu_buffer_rsrc_t vrs = make_rsrc(reinterpret_cast<const char*>(Ly.vcache) + head_off, head_bytes);
                 float4 kr[kPUF], vr[kPUF];
@@ -870,12 +965,18 @@ __global__ __launch_bounds__(kPThreads) void k_decode_persist(const PersistArgs 
             // =================== C: merge chunk partials -> attn c_proj (row, K-half) units -> x' = x + ... ===================
             {
                 GVC_PHASE_BEGIN();
+                {       // (for D)
+                    const PLayerK T = persist_layer(layers, l);
+                    Ly.ln2_w = T->ln2_w; Ly.ln2_b = T->ln2_b; Ly.fc_b = T->fc_b;
+                }
+                const int hdC = fresh_uniform(hd), PS = D + 2 * fresh_uniform(H);
+                const int nchunks = persist_chunks(hdC, fresh_uniform(n_keys)).nchunks;
                 constexpr int VN = ND / KSC;             // KiB of a row per unit
                 const int crow = wave / KSC, cks = wave - crow * KSC;
                 const bool unit = wave < ND * KSC;
                 const float bias = unit && cks == 0 ? Ly.proj_b[wg * ND + crow] : 0.f;
                 if (wave < ND && !c.dead) {
-                    const int e = wave * 256 + lane * 4, h = e / hd;
+                    const int e = wave * 256 + lane * 4, h = e / hdC;
                     const unsigned tg = tag_of(l, 1);
                     float4 o;
                     if (nchunks <= 2) o = merge_chunks<2>(c, grs, iP, PS, D, nchunks, e, h, tg, 300 + l);
@@ -902,6 +1003,7 @@ __global__ __launch_bounds__(kPThreads) void k_decode_persist(const PersistArgs 
             {
                 GVC_PHASE_BEGIN();
                 float4 g[ND], b[ND], xv[ND];
+                Ly.p2_b = persist_layer(layers, l)->p2_b;            // (for E)
                 load_gb<ND>(Ly.ln2_w, Ly.ln2_b, lane, g, b);
                 constexpr int RD = 4 * ND, UPW = (RD + kPCW - 1) / kPCW;
                 const int nmy = wave < RD ? (RD - wave + kPCW - 1) / kPCW : 0;
@@ -910,10 +1012,13 @@ __global__ __launch_bounds__(kPThreads) void k_decode_persist(const PersistArgs 
                 const int row_g = dwg * RD + wave + kPCW * lane;
                 const float bias = lane < nmy ? Ly.fc_b[row_g] : 0.f;
                 // (diagnostics: wave 0's gather of layer 2 in every workgroup -> [base3 + wg * 8 + ..], and the workgroup's XCD / rank)
-                unsigned long long* gdD = (A.dbg && l == kPStampLayer && wave == 0) ? A.dbg + base2 + 2 * 5 * kPG + wg * 8 : nullptr;
-                if (gdD && lane == 0) gdD[5] = XL ? (unsigned long long)(((xx & 7) << 8) | jj) : 0xffffull;
+                unsigned long long* gdD = nullptr;
+                if constexpr (STAMPS) {
+                    if (dbg && l == kPStampLayer && wave == 0) gdD = dbg + base2 + 2 * 5 * kPG + wg * 8;
+                    if (gdD && lane == 0) gdD[5] = XL ? (unsigned long long)(((xx & 7) << 8) | jj) : 0xffffull;
+                }
                 if (!fused) gather<NJX, KSC>(c, grs, iX0, D, tag_of(l, 2), xvec, 400 + l);
-                else if (H == 4) gather<NJX, 4>(c, grs, iX0, D, tag_of(l, 2), xvec, 400 + l, 3, gdD);
+                else if (H == 4) gather<NJX, 4, STAMPS>(c, grs, iX0, D, tag_of(l, 2), xvec, 400 + l, 3, gdD);
                 else if (H == 2) gather<NJX, 2>(c, grs, iX0, D, tag_of(l, 2), xvec, 400 + l);
                 else gather<NJX, 1>(c, grs, iX0, D, tag_of(l, 2), xvec, 400 + l);
                 cbar(c);
@@ -944,6 +1049,7 @@ __global__ __launch_bounds__(kPThreads) void k_decode_persist(const PersistArgs 
             // =================== E (XL): the XCD's 512 hidden units x its K-slice of mlp c_proj, 32 output rows -> plane x of X1 ===================
             if constexpr (XL != 0) {
                 GVC_PHASE_BEGIN();
+                persist_layer_ptrs_a(Ly, layers, min(l + 1, n_layer - 1));      // (for A of the next layer)
                 const int x8 = xx & 7;
                 const int orow = 32 * jj + 4 * wave + lane;                  // (lanes 0..3: the wave's four rows)
                 const float bias = x8 == 0 && lane < 4 ? Ly.p2_b[orow] : 0.f;
@@ -973,6 +1079,7 @@ __global__ __launch_bounds__(kPThreads) void k_decode_persist(const PersistArgs 
             // =================== E: mlp c_proj (row, K-half) units -> x = x' + ... ===================
             {
                 GVC_PHASE_BEGIN();
+                persist_layer_ptrs_a(Ly, layers, min(l + 1, n_layer - 1));      // (for A of the next layer)
                 constexpr int VN = 4 * ND / KSE;         // KiB of a row per unit
                 const int erow = wave / KSE, eks = wave - erow * KSE;
                 const bool unit = wave < ND * KSE;
@@ -997,16 +1104,19 @@ __global__ __launch_bounds__(kPThreads) void k_decode_persist(const PersistArgs 
         // =================== head: ln_f -> final_norm -> latent -> mel_head rows ===================
         {
             GVC_PHASE_BEGIN();
-            const int L = A.n_layer;
+            const PArgsK Kh = persist_args();    // the head's arguments: read here, behind the layer loop
+            const int L = n_layer;
+            float* const logits_out = Kh->per_slot ? Kh->logits_out + (size_t)slot * Kh->vocab : Kh->logits_out;
+            float* const latent_out = Kh->per_slot ? Kh->latent_out + (size_t)slot * D : Kh->latent_out;
             float4 g[ND], b[ND], g2[ND], b2[ND], xv[ND];
-            load_gb<ND>(A.lnf_w, A.lnf_b, lane, g, b);
-            load_gb<ND>(A.fn_w, A.fn_b, lane, g2, b2);
-            const int rm = A.vocab / kPG, rem = A.vocab - rm * kPG;
+            load_gb<ND>(Kh->lnf_w, Kh->lnf_b, lane, g, b);
+            load_gb<ND>(Kh->fn_w, Kh->fn_b, lane, g2, b2);
+            const int rm = Kh->vocab / kPG, rem = Kh->vocab - rm * kPG;
             const int nmy = wave < rm ? (rm - wave + kPCW - 1) / kPCW : 0;
             const int row_g = wg * rm + wave + kPCW * lane;
-            const float bias = lane < nmy ? A.head_b[row_g] : 0.f;
+            const float bias = lane < nmy ? Kh->head_b[row_g] : 0.f;
             const bool tail = wave == kPCW - 1 && wg < rem;
-            const float tbias = tail ? A.head_b[rm * kPG + wg] : 0.f;
+            const float tbias = tail ? Kh->head_b[rm * kPG + wg] : 0.f;
             gather<NJX, NPX>(c, grs, iX1, D, tag_of(L - 1, 4), xvec, 600);
             cbar(c);
             stamp_at(L, 0, 0);
@@ -1035,14 +1145,14 @@ __global__ __launch_bounds__(kPThreads) void k_decode_persist(const PersistArgs 
             phase_done();
             stamp_at(L, 0, 1);
             if (wg == 0 && wave == 0 && lane == 0) {
-                if (A.advance) {
-                    if (A.st.seq_len[slot] < A.max_seq - 1) A.st.seq_len[slot] += 1;
-                    else *A.err = 950;           // KV cache full: GVC_ERR_STATE on the host's next call
-                    if (A.st.mel_pos[slot] < A.max_mel_pos - 1) A.st.mel_pos[slot] += 1;
-                    else *A.err = 951;
+                if (Kh->advance) {
+                    if (Kh->st.seq_len[slot] < max_seq - 1) Kh->st.seq_len[slot] += 1;
+                    else *Kh->err = 950;         // KV cache full: GVC_ERR_STATE on the host's next call
+                    if (Kh->st.mel_pos[slot] < Kh->max_mel_pos - 1) Kh->st.mel_pos[slot] += 1;
+                    else *Kh->err = 951;
                 }
-                if (A.step_ctr) *A.step_ctr += 1;
-                if (A.exec_ctr) *A.exec_ctr += 1;
+                if (Kh->step_ctr) *Kh->step_ctr += 1;
+                if (Kh->exec_ctr) *Kh->exec_ctr += 1;
             }
         }
 #undef GVC_PHASE_BEGIN
@@ -1051,16 +1161,17 @@ __global__ __launch_bounds__(kPThreads) void k_decode_persist(const PersistArgs 
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     __syncthreads();
     if (threadIdx.x == 0) {
-        const unsigned prev = __hip_atomic_fetch_add(A.epoch + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        unsigned* const ep = persist_args()->epoch;
+        const unsigned prev = __hip_atomic_fetch_add(ep + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (prev == gridDim.x - 1) {
-            __hip_atomic_store(A.epoch + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(ep + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             // the per-XCD rank counters start every launch at zero: a workgroup's rank is its arrival order inside THIS grid, whatever
             // earlier launches (other grid sizes, an uneven deal) left behind
             if (XL) {
 #pragma unroll
-                for (int x = 0; x < 8; ++x) __hip_atomic_store(A.epoch + 4 + x, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                for (int x = 0; x < 8; ++x) __hip_atomic_store(ep + 4 + x, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
-            __hip_atomic_store(A.epoch, epoch + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(ep, epoch + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
 }

@@ -31,7 +31,9 @@
  *                            decode of a call's last token to the next call that continues the slot (read at gvc_gpt_create; for A/B
  *                            runs and the tests that compare the two orders)
  *   GVC_PERSIST_TEST_GRID=n  test hook: launch the one-launch steps with n < 256 workgroups (every hand-off then times out)
- *   GVC_PERSIST_STAMPS=1     in-kernel wall-clock stamps of the one-launch steps (scripts/stamps_persist.py, scripts/stamps_rows.py)
+ *   GVC_PERSIST_STAMPS=1     in-kernel wall-clock stamps of the one-launch steps (scripts/stamps_persist.py, scripts/stamps_rows.py).  The
+ *                            one-stream step stamps in a kernel variant of its own, chosen when the context prepares that step and
+ *                            instantiated for d_model 1024 only: at other widths the switch leaves the one-stream step as it is
  *   GVC_DEBUG_STAMPS=1       in-kernel stamps of the launch-per-phase decode kernels (scripts/stamps.py)
  *   GVC_ROWS_DECODE_MIN=n    smallest batch that decodes on the MFMA rows path when the one-launch rows step does not serve it
  *                            (default 5; 0: never -- the 8-stream GEMV groups; tests use it to reach both paths)
