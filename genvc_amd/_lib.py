@@ -114,6 +114,12 @@ class MelOptions(C.Structure):
         [("f_min", C.c_float), ("f_max", C.c_float), ("mel_norms_host", C.POINTER(C.c_float))]
 
 
+class GlOptions(C.Structure):
+    """gvc_gl_options (include/genvc_hip.h)"""
+    _fields_ = [(n, C.c_int32) for n in ("n_fft", "hop", "win", "sample_rate", "n_mels", "max_batch", "max_frames")] + \
+        [("f_min", C.c_float), ("f_max", C.c_float)]
+
+
 class TraceOptions(C.Structure):
     """gvc_trace_options (include/genvc_hip.h)"""
     _fields_ = [(n, C.c_int32) for n in ("start_tok", "stop_tok", "content_off", "n_content")] + [("layer_mask", C.c_uint64)] + \
@@ -286,6 +292,13 @@ _SIGNATURES = {
     "gvc_resample_length": (C.c_int, [C.c_int32, C.c_int32, C.c_int32]),
     "gvc_resample": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "gvc_vq_argmin": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
+    "gvc_gl_create": (C.c_int, [C.POINTER(GlOptions), c_f32p, C.POINTER(_P)]),
+    "gvc_gl_destroy": (C.c_int, [_P]),
+    "gvc_gl_inverse_matrix": (C.c_int, [_P, c_f32p]),
+    "gvc_gl_inverse_mel": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P]),
+    "gvc_gl_init_angles": (C.c_int, [_P, C.c_uint64, C.c_int32, C.c_int32, _P, _P]),
+    "gvc_gl_run": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_float, _P, _P]),
+    "gvc_gl_launches": (C.c_longlong, [_P]),
 }
 
 _lib = None

@@ -1442,6 +1442,75 @@ class MelEngine:
         return (out, fm) if frames_major else out
 
 
+class GriffinLimEngine:
+    """TorchMelSpectrogram.invert (reference utils.py:164-172) in its parts: the inverse mel scale (torchaudio's InverseMelScale: the
+    minimum-norm least-squares inverse of the filterbank, relu'd) and librosa.griffinlim (csrc/griffinlim.hip).  `max_batch` and
+    `max_frames` bound griffinlim(); a filterbank without an inverse raises ValueError naming the filter."""
+
+    def __init__(self, mel_norms=None, n_fft=1024, hop=256, win=1024, sample_rate=22050, f_min=0.0, f_max=8000.0, n_mels=80,
+                 max_batch=1, max_frames=1024):
+        import numpy as np
+        norms = None
+        if mel_norms is not None:
+            norms = np.ascontiguousarray(np.asarray(mel_norms, dtype=np.float32))
+            assert norms.shape == (n_mels,)
+        o = _lib.GlOptions()
+        o.n_fft, o.hop, o.win, o.sample_rate, o.n_mels = n_fft, hop, win, sample_rate, n_mels
+        o.max_batch, o.max_frames = max_batch, max_frames
+        o.f_min, o.f_max = float(f_min), float(f_max)
+        self.n_fft, self.hop, self.win, self.n_mels, self.n_freq = n_fft, hop, win, n_mels, n_fft // 2 + 1
+        self.max_batch, self.max_frames = max_batch, max_frames
+        self._h = C.c_void_p()
+        rc = lib().gvc_gl_create(C.byref(o), None if norms is None else norms.ctypes.data_as(_lib.c_f32p), C.byref(self._h))
+        if rc == -1:        # GVC_ERR_ARG: an unsupported configuration, or a filterbank without an inverse (the message names the filter)
+            raise ValueError(lib().gvc_last_error().decode(errors="replace"))
+        check(rc, "gvc_gl_create")
+
+    def close(self):
+        if self._h:
+            lib().gvc_gl_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def inverse_matrix(self):
+        """W float32 [n_freq, n_mels] = fb (fb^T fb)^-1 (a host tensor)"""
+        w = torch.empty(self.n_freq, self.n_mels, dtype=torch.float32)
+        check(lib().gvc_gl_inverse_matrix(self._h, C.cast(w.data_ptr(), _lib.c_f32p)), "gl_inverse_matrix")
+        return w
+
+    def inverse_mel(self, mel):
+        """mel [B,n_mels,F] (normalised log power mel) -> S [B,n_freq,F] = relu(W exp(mel * norms))"""
+        B, _, F = mel.shape
+        out = torch.empty(B, self.n_freq, F, device=mel.device, dtype=torch.float32)
+        check(lib().gvc_gl_inverse_mel(self._h, ptr(_f32(mel)), B, F, ptr(out), stream()), "gl_inverse_mel")
+        return out
+
+    def init_angles(self, seed, B, F):
+        """complex64 [B,n_freq,F] unit phasors exp(2 pi i u), u from the sampler's counter-based generator keyed by (seed, item, bin, frame)"""
+        out = torch.empty(B, self.n_freq, F, device="cuda", dtype=torch.complex64)
+        check(lib().gvc_gl_init_angles(self._h, int(seed) & 0xFFFFFFFFFFFFFFFF, B, F, ptr(out), stream()), "gl_init_angles")
+        return out
+
+    def griffinlim(self, S, init_angles=None, seed=0, n_iter=64, momentum=0.99):
+        """S [B,n_freq,F] -> wav [B, hop (F - 1)] after n_iter iterations from init_angles (or the seeded start)"""
+        B, _, F = S.shape
+        if init_angles is None:
+            init_angles = self.init_angles(seed, B, F)
+        S, init_angles = _f32(S), init_angles.contiguous()
+        wav = torch.empty(B, self.hop * (F - 1), device=S.device, dtype=torch.float32)
+        check(lib().gvc_gl_run(self._h, ptr(S), ptr(init_angles), B, F, int(n_iter), float(momentum), ptr(wav), stream()), "gl_run")
+        return wav
+
+    def launches(self):
+        """kernel launches enqueued so far (measurement)"""
+        return int(lib().gvc_gl_launches(self._h))
+
+
 class DvaeEngine:
     """DiscreteVAE.get_codebook_indices (reference layers/dvae.py:324-331); with_decoder=True: also decode (:333-352) and the
     eval-mode forward (:363-381)."""

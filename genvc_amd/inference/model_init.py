@@ -100,6 +100,16 @@ class GenVCModel(nn.Module):
         return batch
 
     @torch.inference_mode()
+    def audition_codes(self, audio_codes, n_iter=64, seed=0):
+        """audio codes [B,n] -> waveform [B, hop (F - 1)] at the acoustic DVAE's rate, without the vocoder: the DVAE's decoded mel
+        through TorchMelSpectrogram.invert (inverse mel scale, then Griffin-Lim from the seeded start).  Tells "the codes are bad" from
+        "the vocoder is bad"."""
+        if self.acoustic_dvae is None:
+            raise NotImplementedError("audition_codes: the config has no acoustic_dvae_config (default_config(with_acoustic=True))")
+        mel = self.acoustic_dvae.decode(audio_codes)[0]
+        return self.torch_mel_spectrogram_dvae.invert(mel, n_iter=n_iter, seed=seed)
+
+    @torch.inference_mode()
     def evaluate(self, batch):
         """the reference trainer's eval_step without its trainer (gpt_trainer.py:256-283): format_batch_on_device, then GPT.forward ->
         {loss_text_ce, loss_mel_ce, top10acc, loss}"""

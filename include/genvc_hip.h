@@ -1139,6 +1139,39 @@ int gvc_mel_create_ex(const gvc_mel_options* opt, gvc_mel** out);
 /* frames gvc_mel_forward writes for T samples (<= 0: too short for the reflect padding) */
 int gvc_mel_frames(gvc_mel* ctx, int32_t T);
 
+/* ------------------------------------------------------------------------------------------
+ * Mel inversion and Griffin-Lim.  Replaces utils.py:TorchMelSpectrogram.invert (:164-172): exp(mel * norms), then
+ * torchaudio.transforms.InverseMelScale (the minimum-norm least-squares inverse of the HTK / Slaney-normalised filterbank, relu'd), then
+ * librosa.griffinlim (zero-padded centred STFT, periodic Hann, momentum) on the result AS A MAGNITUDE, as the reference passes it.
+ *
+ * The inverse matrix W [n_freq][n_mels] = fb (fb^T fb)^-1 is built at creation on the host in double (Cholesky of the Gram matrix) and
+ * stored as fp32; a filterbank without an inverse (a filter with no bin) is GVC_ERR_ARG and the message names the filter.
+ * Supported: n_fft a power of two in [512, 2048], win <= n_fft, hop divides win, win / hop >= 2; anything else is GVC_ERR_ARG.
+ * B > max_batch or F > max_frames in gvc_gl_run is GVC_ERR_ARG (capacity, as for the other engines): create a larger context.
+ * No atomics, fixed summation orders: the same input gives the same bits.  gvc_gl_run enqueues n_iter + 2 launches.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct gvc_gl gvc_gl;
+typedef struct gvc_gl_options {
+    int32_t n_fft, hop, win, sample_rate, n_mels;
+    int32_t max_batch, max_frames;       /* capacity of gvc_gl_run */
+    float f_min, f_max;
+} gvc_gl_options;
+int gvc_gl_create(const gvc_gl_options* opt, const float* mel_norms_host_or_null, gvc_gl** out);
+int gvc_gl_destroy(gvc_gl* ctx);
+/* W [n_freq][n_mels] -> HOST memory */
+int gvc_gl_inverse_matrix(gvc_gl* ctx, float* W);
+/* mel [B][n_mels][F] (normalised log power mel) -> spec [B][n_freq][F] = relu(W exp(mel * norms)) */
+int gvc_gl_inverse_mel(gvc_gl* ctx, const float* mel, int32_t B, int32_t F, float* spec, gvc_stream s);
+/* angles [B][n_freq][F] complex64 (interleaved re, im) = exp(2 pi i u), u from the sampler's counter-based generator keyed by
+ * (seed, item, bin, frame): independent of the launch geometry and of B, F of other entries */
+int gvc_gl_init_angles(gvc_gl* ctx, uint64_t seed, int32_t B, int32_t F, void* angles, gvc_stream s);
+/* spec [B][n_freq][F], init_angles [B][n_freq][F] complex64 -> wav [B][hop (F - 1)] after n_iter >= 0 iterations with momentum in
+ * [0, 1) (librosa's alpha = momentum / (1 + momentum)); n_iter = 0 is istft(spec * init_angles).  F >= 2. */
+int gvc_gl_run(gvc_gl* ctx, const float* spec, const void* init_angles, int32_t B, int32_t F, int32_t n_iter, float momentum,
+               float* wav, gvc_stream s);
+/* kernel launches this context has enqueued so far (measurement) */
+long long gvc_gl_launches(gvc_gl* ctx);
+
 #ifdef __cplusplus
 }
 #endif
