@@ -139,6 +139,26 @@ class HubertDims(C.Structure):
                     "max_batch", "max_samples")]
 
 
+class GemmCase(C.Structure):
+    """gvc_gemm_case (include/genvc_hip.h): one launch of one fp32 GEMM kernel class on caller-owned device buffers (test hook)"""
+    _fields_ = [(n, C.c_int32) for n in ("kind", "M", "N", "K")] + \
+        [(n, C.c_void_p) for n in ("A", "W", "C", "work")] + \
+        [(n, C.c_int64) for n in ("a_batch_stride", "a_batch_stride2", "w_batch_stride", "c_batch_stride", "c_batch_stride2", "work_cap")] + \
+        [(n, C.c_int32) for n in ("lda", "ldw", "ldc", "w_bf16", "batch", "batch_inner", "conv_cin", "conv_tap_stride", "a_act")] + \
+        [("a_slope", C.c_float), ("att_part", C.c_void_p)] + \
+        [(n, C.c_int32) for n in ("att_nc", "att_heads", "att_hd", "sk", "raw_partials", "mtw", "sk_used")] + \
+        [(n, C.c_void_p) for n in ("bias", "resid", "resid2")] + \
+        [(n, C.c_int64) for n in ("bias_batch_stride", "resid_batch_stride", "resid_batch_stride2")] + \
+        [(n, C.c_int32) for n in ("act", "ldr", "resid_fm16", "geglu", "c_fm16", "qkv", "d", "n_head", "head_dim", "max_seq", "T",
+                                  "kv_bf16")] + \
+        [("out_scale", C.c_float), ("reserved", C.c_int32)] + \
+        [(n, C.c_void_p) for n in ("kcache", "vcache", "slots", "base_len", "x_in", "x_out", "part", "pbias", "ln_w", "ln_b", "stats")] + \
+        [("ln_sk", C.c_int32), ("ln_rows", C.c_int32)]
+
+
+# gvc_gemm_case.kind (GVC_GEMM_*)
+GEMM_TILED, GEMM_SKINNY, GEMM_SKINNY_LN, GEMM_STRIP, GEMM_STRIP_GEOM, GEMM_LN_ROWS, GEMM_LN_ROWS_B16, GEMM_TO_FM16, GEMM_TO_FM16_BF16 = range(9)
+
 _P = C.c_void_p
 _SIGNATURES = {
     "gvc_version": (C.c_int, []),
@@ -243,6 +263,7 @@ _SIGNATURES = {
     "gvc_gpt_time_kernel": (C.c_int, [_P, C.c_int32, _P, C.c_int32, _P, C.c_int32, c_f32p, c_i32p, _P]),
     "gvc_fb16_index": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     "gvc_gemm_probe": (C.c_int, [C.c_int32, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_f32p, _P]),
+    "gvc_gemm_probe_ex": (C.c_int, [C.POINTER(GemmCase), _P]),
     "gvc_perceiver_create": (C.c_int, [C.POINTER(PerceiverDims), C.POINTER(_P)]),
     "gvc_perceiver_destroy": (C.c_int, [_P]),
     "gvc_perceiver_bind_weight": (C.c_int, [_P, C.c_char_p, _P, C.c_int64, _P]),

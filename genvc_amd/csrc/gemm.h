@@ -270,6 +270,9 @@ int launch_gemm_skinny_ln(GemmArgs G, const LnFuse& P, hipStream_t s);
 // go to G.work[sk][M][N]; raw_partials = 1 leaves them for the consumer (k_ln_sum_rows) and reports the split in *sk_used,
 // raw_partials = 0 runs k_splitk_epilogue (G.e applied there).
 int launch_gemm_strip(GemmArgs G, int sk_max, long long work_cap, int raw_partials, int* sk_used, hipStream_t s);
+// the same launch with the geometry given instead of chosen: at most MTW (1..9) m tiles per workgroup, SK K splits; a pair the kernel
+// cannot run (kb / SK < 4, work too small) is refused.  launch_gemm_strip ends here; tests reach every width through it.
+int launch_gemm_strip_geom(GemmArgs G, int MTW, int SK, long long work_cap, int raw_partials, hipStream_t s);
 void gemm_init_attributes();        // raises dynamic-LDS limits; call once, outside stream capture
 // row-major [N][K] -> FM16
 __global__ void k_to_fm16(const float* src, float* dst, int N, int K);

@@ -365,8 +365,17 @@ __global__ __launch_bounds__(NW * 64) void k_gemm_skinny(const GemmArgs G) {
         }
         const int m = 16 * t + rr, n = n0 + 4 * k4;
         if (m < G.M) {
-            if (G.SK > 1) *reinterpret_cast<float4*>(G.work + ((size_t)blockIdx.y * G.M + m) * G.N + n) = v;
-            else gemm_store4_pre(G, m, n, v, pre);
+            if (G.SK > 1) { *reinterpret_cast<float4*>(G.work + ((size_t)blockIdx.y * G.M + m) * G.N + n) = v; continue; }
+            if constexpr (MT > NW) {        // a thread's second item is a row 64 below the one it prefetched for: its own slot and length
+                if (item >= NW * 64 && G.e.qkv && n >= G.e.d) {
+                    EpiPre p2 = pre;
+                    p2.slot = G.e.slots[m / G.e.T];
+                    p2.base = G.e.base_len ? G.e.base_len[p2.slot] : 0;
+                    gemm_store4_pre(G, m, n, v, p2);
+                    continue;
+                }
+            }
+            gemm_store4_pre(G, m, n, v, pre);
         }
     }
 }
@@ -574,8 +583,13 @@ int launch_ln_sum_rows_b16(const float* x_in, float* x_out, unsigned short* a_b1
 // ---- skinny GEMM for <= 16 rows with the row completion + LayerNorm in its prologue (K = d) ----
 // A = LayerNorm(x_in + bias + sum part) is built by the workgroup itself (wave w: rows w and w + 8) and staged in LDS in
 // the FM16 fragment order; workgroup 0 also writes the completed rows to x_out (a buffer other than x_in: the other
-// workgroups are still reading x_in).  Everything else as k_gemm_skinny<1, 8>: same per-element summation order, so the
-// result is bit-identical to k_ln_sum_rows_t followed by k_gemm_skinny.
+// workgroups are still reading x_in).  Everything else as k_gemm_skinny<1, 8>: same per-element summation order.  The completed
+// rows (x_out) are bit-identical to k_ln_sum_rows_t's (additions in one fixed order); the normalised rows, and so the GEMM result, are
+// NOT always: row_ln is compiled into each kernel on its own with fp contraction on, and nothing makes the compiler form the same
+// FMAs in both (a0 * a0 + a1 * a1 can keep either product inside, v - sum * inv_d can be one FMA or two roundings), so a row's mean /
+// rstd can differ in the last bit between the two kernels and with it the whole row (measured through identity weights: whole rows
+// differ, d = 768: most rows; d = 256 / 1024: about one row in 30; up to 1.5e-6 absolute on O(1) values).  Both are
+// within fp32 rounding of the exact LayerNorm (tests/test_gpu_gemm_modes.py checks each against fp64).
 
 // one completed row: kept in x_out by workgroup 0, normalised, staged in LDS in the FM16 fragment order (zeros past the last row)
 template <int NV>
@@ -880,16 +894,54 @@ __global__ __launch_bounds__(256 * KH) void k_gemm_strip(const GemmArgs G, const
     }
 }
 
-// geometry: the (tiles per group, K split) pair with the shortest modelled critical path, in units of one (m tile, k block) =
-// 4 MFMAs = 128 cycles: a CU runs its workgroups' MFMA work back to back, and every round of resident workgroups pays one
-// pipeline fill.  GVC_STRIP="MTW,SK" overrides (measurement).
-int launch_gemm_strip(GemmArgs G, int sk_max, long long work_cap, int raw_partials, int* sk_used, hipStream_t s) {
+// what every strip launch needs, whoever chose the geometry
+static int strip_check(const GemmArgs& G, long long work_cap, int raw_partials) {
     GVC_REQUIRE(G.M >= 1 && G.N % 64 == 0 && G.K % 16 == 0 && G.conv_cin == 0 && G.a_act == 0 && G.ldc % 4 == 0 &&
                     (!G.e.resid || G.e.ldr % 4 == 0) && (!G.e.qkv || (G.e.d % 64 == 0 && G.e.head_dim % 4 == 0)), GVC_ERR_ARG,
                 "strip gemm: unsupported shape M=%d N=%d K=%d (FM16 operands, N %% 64 == 0, 16-byte rows)", G.M, G.N, G.K);
+    // gemm_store4 has no GEGLU pairing and reads `resid` row-major only (the skinny kernels' epilogues have both)
+    GVC_REQUIRE(!G.e.geglu && !G.e.resid_fm16, GVC_ERR_UNSUPPORTED, "strip gemm: no geglu / resid_fm16 epilogue");
+    GVC_REQUIRE(!raw_partials || (G.work && (long long)G.M * G.N <= work_cap), GVC_ERR_ARG, "strip gemm: raw partials need a work buffer");
+    return GVC_OK;
+}
+
+// one strip GEMM with MTW m tiles per workgroup (the balanced partition's largest group) and SK K splits
+int launch_gemm_strip_geom(GemmArgs G, int MTW, int SK, long long work_cap, int raw_partials, hipStream_t s) {
+    if (const int rc = strip_check(G, work_cap, raw_partials)) return rc;
     StripGeom S;
     S.mt = cdiv(G.M, 16); S.NB = G.N / 64; S.kb = G.K / 16;
-    GVC_REQUIRE(!raw_partials || (G.work && (long long)G.M * G.N <= work_cap), GVC_ERR_ARG, "strip gemm: raw partials need a work buffer");
+    GVC_REQUIRE(MTW >= 1 && MTW <= 9 && SK >= 1 && SK <= 8 && cdiv(S.mt, cdiv(S.mt, MTW)) <= MTW && S.kb / SK >= 4, GVC_ERR_ARG,
+                "strip gemm: geometry MTW=%d SK=%d cannot run M=%d K=%d", MTW, SK, G.M, G.K);
+    GVC_REQUIRE(SK == 1 || (G.work && (long long)SK * G.M * G.N <= work_cap), GVC_ERR_ARG, "strip gemm: work buffer too small for SK=%d", SK);
+    S.MG = cdiv(S.mt, MTW); S.SK = SK;
+    S.raw = raw_partials && G.work ? 1 : 0;
+    G.SK = SK;
+    const dim3 grid(S.MG * S.NB * S.SK);
+#define GVC_STRIP(w)                                                                                                         \
+    case w:                                                                                                                  \
+        if (G.w_bf16) hipLaunchKernelGGL((k_gemm_strip<w, 1, 2>), grid, dim3(512), StripCfg<w>::lds_bytes, s, G, S);              \
+        else hipLaunchKernelGGL((k_gemm_strip<w, 0, 2>), grid, dim3(512), StripCfg<w>::lds_bytes, s, G, S);                       \
+        break;
+    switch (MTW) { GVC_STRIP(1) GVC_STRIP(2) GVC_STRIP(3) GVC_STRIP(4) GVC_STRIP(5) GVC_STRIP(6) GVC_STRIP(7) GVC_STRIP(8) GVC_STRIP(9) }
+#undef GVC_STRIP
+    GVC_LAUNCH_CHECK();
+    if (SK > 1 && !raw_partials) {
+        const long long mn = (long long)G.M * G.N;
+        int gx = (int)((mn + 255) / 256);
+        if (gx > 2048) gx = 2048;
+        hipLaunchKernelGGL(k_splitk_epilogue, dim3(gx, 1, 1), dim3(256), 0, s, G);
+        GVC_LAUNCH_CHECK();
+    }
+    return GVC_OK;
+}
+
+// geometry: the (tiles per group, K split) pair with the shortest modelled critical path, in units of one (m tile, k block) =
+// 4 MFMAs = 128 cycles: a CU runs its workgroups' MFMA work back to back, and every round of resident workgroups pays one
+// pipeline fill.  (launch_gemm_strip_geom runs a pair chosen by the caller.)
+int launch_gemm_strip(GemmArgs G, int sk_max, long long work_cap, int raw_partials, int* sk_used, hipStream_t s) {
+    if (const int rc = strip_check(G, work_cap, raw_partials)) return rc;
+    StripGeom S;
+    S.mt = cdiv(G.M, 16); S.NB = G.N / 64; S.kb = G.K / 16;
     if (!G.work) sk_max = 1;
     if (sk_max < 1) sk_max = 1;
     if (sk_max > 8) sk_max = 8;
@@ -910,27 +962,8 @@ int launch_gemm_strip(GemmArgs G, int sk_max, long long work_cap, int raw_partia
         }
     }
     GVC_REQUIRE(best_w > 0, GVC_ERR_ARG, "strip gemm: no geometry for M=%d N=%d K=%d", G.M, G.N, G.K);
-    S.MG = cdiv(S.mt, best_w); S.SK = best_sk;
-    S.raw = raw_partials && G.work ? 1 : 0;
-    G.SK = best_sk;
     if (sk_used) *sk_used = best_sk;
-    const dim3 grid(S.MG * S.NB * S.SK);
-#define GVC_STRIP(w)                                                                                                         \
-    case w:                                                                                                                  \
-        if (G.w_bf16) hipLaunchKernelGGL((k_gemm_strip<w, 1, 2>), grid, dim3(512), StripCfg<w>::lds_bytes, s, G, S);              \
-        else hipLaunchKernelGGL((k_gemm_strip<w, 0, 2>), grid, dim3(512), StripCfg<w>::lds_bytes, s, G, S);                       \
-        break;
-    switch (best_w) { GVC_STRIP(1) GVC_STRIP(2) GVC_STRIP(3) GVC_STRIP(4) GVC_STRIP(5) GVC_STRIP(6) GVC_STRIP(7) GVC_STRIP(8) GVC_STRIP(9) }
-#undef GVC_STRIP
-    GVC_LAUNCH_CHECK();
-    if (best_sk > 1 && !raw_partials) {
-        const long long mn = (long long)G.M * G.N;
-        int gx = (int)((mn + 255) / 256);
-        if (gx > 2048) gx = 2048;
-        hipLaunchKernelGGL(k_splitk_epilogue, dim3(gx, 1, 1), dim3(256), 0, s, G);
-        GVC_LAUNCH_CHECK();
-    }
-    return GVC_OK;
+    return launch_gemm_strip_geom(G, best_w, best_sk, work_cap, raw_partials, s);
 }
 
 void gemm_init_attributes() {
@@ -1003,5 +1036,77 @@ extern "C" int gvc_gemm_probe(int32_t variant, const float* A, const float* W, c
         hipEventDestroy(e0); hipEventDestroy(e1);
     }
     (void)hipStreamSynchronize(s);
+    return rc;
+}
+
+// Test hook (include/genvc_hip.h): one launch of one kernel class on the caller's buffers, every GemmArgs / GemmEpi / LnFuse field a
+// product caller sets taken from the case as it stands.
+extern "C" int gvc_gemm_probe_ex(gvc_gemm_case* c, gvc_stream sv) {
+    using namespace gvc;
+    GVC_REQUIRE(c && c->kind >= GVC_GEMM_TILED && c->kind <= GVC_GEMM_TO_FM16_BF16 && c->M >= 1 && c->K >= 1, GVC_ERR_ARG, "gemm_probe_ex: bad argument");
+    hipStream_t s = (hipStream_t)sv;
+    static bool attrs = false;
+    if (!attrs) { gemm_init_attributes(); gemm_b16_init_attributes(); attrs = true; }
+    GemmArgs G;
+    memset(&G, 0, sizeof(G));
+    G.A = static_cast<const float*>(c->A); G.lda = c->lda; G.a_batch_stride = c->a_batch_stride; G.a_batch_stride2 = c->a_batch_stride2;
+    G.Wt = static_cast<const float*>(c->W); G.ldw = c->ldw; G.w_batch_stride = c->w_batch_stride; G.w_bf16 = c->w_bf16;
+    G.C = c->C; G.ldc = c->ldc; G.c_batch_stride = c->c_batch_stride; G.c_batch_stride2 = c->c_batch_stride2;
+    G.batch_inner = c->batch_inner; G.M = c->M; G.N = c->N; G.K = c->K;
+    G.conv_cin = c->conv_cin; G.conv_tap_stride = c->conv_tap_stride; G.a_act = c->a_act; G.a_slope = c->a_slope;
+    G.att_part = c->att_part; G.att_nc = c->att_nc; G.att_heads = c->att_heads; G.att_hd = c->att_hd;
+    G.work = c->work;
+    GemmEpi& e = G.e;
+    e.bias = c->bias; e.bias_batch_stride = c->bias_batch_stride; e.act = c->act;
+    e.resid = c->resid; e.ldr = c->ldr; e.resid_batch_stride = c->resid_batch_stride; e.resid_batch_stride2 = c->resid_batch_stride2;
+    e.resid_fm16 = c->resid_fm16; e.geglu = c->geglu; e.resid2 = c->resid2; e.out_scale = c->out_scale;
+    e.c_fm16 = c->c_fm16; e.qkv = c->qkv; e.d = c->d; e.n_head = c->n_head; e.head_dim = c->head_dim; e.max_seq = c->max_seq; e.T = c->T;
+    e.kcache = static_cast<float*>(c->kcache); e.vcache = static_cast<float*>(c->vcache); e.kv_bf16 = c->kv_bf16;
+    e.slots = c->slots; e.base_len = c->base_len;
+    int rc = GVC_OK;
+    switch (c->kind) {
+    case GVC_GEMM_TILED:
+        GVC_REQUIRE(c->batch >= 1 && G.A && G.Wt && G.C, GVC_ERR_ARG, "gemm_probe_ex: tiled case needs A, W, C and batch >= 1");
+        rc = launch_gemm_cap(G, c->batch, c->work_cap, s);
+        break;
+    case GVC_GEMM_SKINNY:
+        GVC_REQUIRE((G.A || G.att_part) && G.Wt && (G.C || c->sk > 1), GVC_ERR_ARG, "gemm_probe_ex: skinny case needs A, W, C");
+        rc = launch_gemm_skinny(G, c->sk, c->work_cap, s);
+        break;
+    case GVC_GEMM_SKINNY_LN: {
+        LnFuse P;
+        P.x_in = c->x_in; P.x_out = c->x_out; P.part = c->part; P.SK = c->ln_sk; P.pbias = c->pbias; P.ln_w = c->ln_w; P.ln_b = c->ln_b;
+        P.rows = c->ln_rows;
+        GVC_REQUIRE(P.x_in && P.ln_w && P.ln_b && G.Wt && G.C && (!P.part || (P.pbias && P.x_out)), GVC_ERR_ARG, "gemm_probe_ex: skinny+LN case needs x_in, ln_w, ln_b, W, C");
+        rc = launch_gemm_skinny_ln(G, P, s);
+        break;
+    }
+    case GVC_GEMM_STRIP:
+        GVC_REQUIRE(G.A && G.Wt && (G.C || c->raw_partials), GVC_ERR_ARG, "gemm_probe_ex: strip case needs A, W, C");
+        c->sk_used = 0;
+        rc = launch_gemm_strip(G, c->sk, c->work_cap, c->raw_partials, &c->sk_used, s);
+        break;
+    case GVC_GEMM_STRIP_GEOM:
+        GVC_REQUIRE(G.A && G.Wt && (G.C || c->raw_partials), GVC_ERR_ARG, "gemm_probe_ex: strip case needs A, W, C");
+        rc = launch_gemm_strip_geom(G, c->mtw, c->sk, c->work_cap, c->raw_partials, s);
+        if (rc == GVC_OK) c->sk_used = c->sk;
+        break;
+    case GVC_GEMM_LN_ROWS:
+        GVC_REQUIRE(c->x_in && c->x_out && (!c->ln_w || (c->ln_b && c->C)) && (!c->part || c->pbias), GVC_ERR_ARG, "gemm_probe_ex: ln_sum_rows case needs x_in, x_out");
+        rc = launch_ln_sum_rows(c->x_in, c->x_out, c->C, c->part, c->ln_sk, c->pbias, c->M, c->K, c->ln_w, c->ln_b, c->c_fm16, s);
+        break;
+    case GVC_GEMM_LN_ROWS_B16:
+        GVC_REQUIRE(c->x_in && c->x_out && (!c->part || c->pbias), GVC_ERR_ARG, "gemm_probe_ex: ln_sum_rows_b16 case needs x_in, x_out");
+        rc = launch_ln_sum_rows_b16(c->x_in, c->x_out, reinterpret_cast<unsigned short*>(c->C), c->stats, c->part, c->ln_sk, c->pbias, c->M, c->K, s);
+        break;
+    default:        // GVC_GEMM_TO_FM16, GVC_GEMM_TO_FM16_BF16: [M][K] row-major A -> rows 0..M-1 of the FM16 C (rows up to the next multiple of 16 are left alone)
+        GVC_REQUIRE(G.A && G.C && c->K % 16 == 0, GVC_ERR_ARG, "gemm_probe_ex: FM16 needs K a multiple of 16 (K=%d)", c->K);
+        if (c->kind == GVC_GEMM_TO_FM16) hipLaunchKernelGGL(k_to_fm16, dim3(64), dim3(256), 0, s, G.A, G.C, c->M, c->K);
+        else hipLaunchKernelGGL(k_to_fm16_bf16, dim3(64), dim3(256), 0, s, G.A, reinterpret_cast<unsigned short*>(G.C), c->M, c->K);
+        GVC_LAUNCH_CHECK();
+        break;
+    }
+    const hipError_t he = hipStreamSynchronize(s);
+    if (rc == GVC_OK && he != hipSuccess) { set_error("gemm_probe_ex: %s", hipGetErrorString(he)); rc = GVC_ERR_HIP; }
     return rc;
 }

@@ -921,6 +921,40 @@ int gvc_gpt_time_kernel(gvc_gpt* ctx, int32_t which, const int32_t* slots, int32
 int gvc_gemm_probe(int32_t variant, const float* A, const float* W, const float* bias, float* C, int32_t M, int32_t N, int32_t K,
                    int32_t sk_max, int32_t iters, float* avg_us, gvc_stream s);
 
+/* Test hook for every operand mode and epilogue of the fp32 GEMM kernels (csrc/gemm.h; not a reference interface): one launch of one
+ * kernel class on CALLER-OWNED device buffers, described by the fields a product caller sets in GemmArgs / GemmEpi / LnFuse, so that a
+ * test can surround every buffer with guard regions.  No conversion, no allocation, no timing; synchronises the stream.
+ * kind: GVC_GEMM_TILED      launch_gemm_cap(batch, work_cap): row-major operands, implicit conv, batches, split-K chosen by the shape;
+ *       GVC_GEMM_SKINNY     launch_gemm_skinny(sk): FM16 operands (A padded to 16 rows), M <= 128; sk > 1 leaves raw planes in work;
+ *       GVC_GEMM_SKINNY_LN  launch_gemm_skinny_ln: A = LayerNorm(x_in + pbias + sum part) built in the prologue (the ln_* fields);
+ *       GVC_GEMM_STRIP      launch_gemm_strip(sk = sk_max, raw_partials); the chosen split comes back in sk_used;
+ *       GVC_GEMM_STRIP_GEOM the strip kernel with mtw M tiles per workgroup and K split sk (refused when the pair cannot run);
+ *       GVC_GEMM_LN_ROWS / _LN_ROWS_B16  launch_ln_sum_rows(_b16): rows = M, d = K, x_in / x_out / part / ln_sk / pbias / ln_w / ln_b,
+ *                           output a = C (a_fm16 = c_fm16; b16: C holds bf16 in the FB16 layout and stats gets (mean, rstd) per row);
+ *       GVC_GEMM_TO_FM16 / _TO_FM16_BF16  C = the FM16 copy of the row-major [N][K] matrix A (bf16: of its upper 16 bits). */
+enum { GVC_GEMM_TILED = 0, GVC_GEMM_SKINNY = 1, GVC_GEMM_SKINNY_LN = 2, GVC_GEMM_STRIP = 3, GVC_GEMM_STRIP_GEOM = 4, GVC_GEMM_LN_ROWS = 5,
+       GVC_GEMM_LN_ROWS_B16 = 6, GVC_GEMM_TO_FM16 = 7, GVC_GEMM_TO_FM16_BF16 = 8 };
+typedef struct gvc_gemm_case {
+    int32_t kind, M, N, K;
+    const void* A; const void* W; float* C; float* work;
+    int64_t a_batch_stride, a_batch_stride2, w_batch_stride, c_batch_stride, c_batch_stride2, work_cap;
+    int32_t lda, ldw, ldc, w_bf16, batch, batch_inner, conv_cin, conv_tap_stride, a_act;
+    float a_slope;
+    const float* att_part;
+    int32_t att_nc, att_heads, att_hd;
+    int32_t sk, raw_partials, mtw, sk_used;        /* sk_used: written by the call */
+    /* GemmEpi */
+    const float* bias; const float* resid; const float* resid2;
+    int64_t bias_batch_stride, resid_batch_stride, resid_batch_stride2;
+    int32_t act, ldr, resid_fm16, geglu, c_fm16, qkv, d, n_head, head_dim, max_seq, T, kv_bf16;
+    float out_scale; int32_t reserved;
+    void* kcache; void* vcache; const int32_t* slots; const int32_t* base_len;
+    /* LnFuse / the row kernels */
+    const float* x_in; float* x_out; const float* part; const float* pbias; const float* ln_w; const float* ln_b; float* stats;
+    int32_t ln_sk, ln_rows;
+} gvc_gemm_case;
+int gvc_gemm_probe_ex(gvc_gemm_case* c, gvc_stream s);
+
 /* Element index of (row m, column k) of an [M][K] bf16 matrix in the fragment-major layout of the bf16 matrix-core GEMMs
  * (csrc/gemm_b16.h: fb16_index; M % 16 == 0, K % 32 == 0): each (16 rows x 32 k) block is 64 fragments of 8 consecutive k, fragment
  * (m % 16) + 16 * ((k % 32) / 8) -- the lane of v_mfma_f32_16x16x32_bf16 that holds them.  Host arithmetic only. */
