@@ -982,7 +982,7 @@ static int persist_prepare(gvc_gpt* c) {
         hipMalloc((void**)&c->p_epoch, 16 * sizeof(unsigned)) != hipSuccess || hipMemset(c->p_epoch, 0, 16 * sizeof(unsigned)) != hipSuccess)
         return unavailable();
     if (getenv("GVC_PERSIST_STAMPS") && d == 1024) {        // (the stamping variant is instantiated for d_model 1024: persist_kernel)
-        const size_t nb = (size_t)(20 * (L + 2) + 2 * 5 * kPG + 8 * kPG) * sizeof(unsigned long long);
+        const size_t nb = (size_t)(20 * (L + 2) + 2 * 5 * kPG + 8 * kPG + 4 * kPG) * sizeof(unsigned long long);
         if (hipMalloc((void**)&c->p_dbg, nb) != hipSuccess || hipMemset(c->p_dbg, 0, nb) != hipSuccess) return unavailable();
     }
     // the memsets above went to the legacy default stream; the caller's stream may be a non-blocking one (no implicit ordering with it): they
@@ -3017,7 +3017,8 @@ extern "C" int gvc_gpt_debug_stamps(gvc_gpt* c, unsigned long long* host_out, in
     }
     if (c && c->p_dbg && max_launches < 0) {     // stamps of the last one-launch decode step (layout: persist_kernel.h)
         (void)hipDeviceSynchronize();
-        const int n = 20 * (c->dm.n_layer + 2) + 2 * 5 * kPG + 8 * kPG;
+        // -3: with the K/V arrival stamps of the fused phase behind them (4 words per workgroup); -1: the buffer as callers have sized it so far
+        const int n = 20 * (c->dm.n_layer + 2) + 2 * 5 * kPG + 8 * kPG + (max_launches == -3 ? 4 * kPG : 0);
         (void)hipMemcpy(host_out, c->p_dbg, (size_t)n * sizeof(unsigned long long), hipMemcpyDeviceToHost);
         return n;
     }

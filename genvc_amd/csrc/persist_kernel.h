@@ -415,8 +415,22 @@ __device__ __forceinline__ void persist_loader(const PersistArgs& A, PCtx& c, ch
     const bool fused = persist_fused_attn(A.n_head, A.head_dim, A.st.seq_len[A.slots[0]] + 1);
     unsigned fseq = 0;
     const int n_seg = 4 * A.n_layer + 2;
+    // The matrix a segment streams, read from the layer table ONE SEGMENT AHEAD: the read is requested in front of the fills of the segment
+    // before and has landed behind the first of them (vmcnt(0)).  Read where it is used, it is an L2 round trip with no fill in flight at
+    // every segment boundary, 120 per step, on the wave that the whole step waits for (profiles/decode_kv_locality.md).
+    auto seg_matrix = [&](int s) -> const float* {
+        if (s >= 4 * A.n_layer) return A.head_w;
+        constexpr size_t kField[4] = {offsetof(PersistLayer, qkv_w), offsetof(PersistLayer, proj_w), offsetof(PersistLayer, fc_w),
+                                      offsetof(PersistLayer, p2_w)};
+        const int ph = s & 3;
+        const size_t field = ph == 0 ? kField[0] : ph == 1 ? kField[1] : ph == 2 ? kField[2] : kField[3];
+        return *reinterpret_cast<const float* const*>(reinterpret_cast<const char*>(persist_layer(A.layers, s >> 2)) + field);
+    };
+    const float* wnext = seg_matrix(0);
 #pragma unroll 1
     for (int sgi = 0; sgi < n_seg; ++sgi) {
+        const float* const wmat = wnext;
+        if (sgi + 1 < n_seg) wnext = seg_matrix(sgi + 1);
         // segment = this workgroup's rows of one matrix: contiguous in the row-per-output layout
         // WB = 1: the matrices are bf16 (2 bytes per element, PersistLayer pointers then address the bf16 copies)
         const char* base;
@@ -426,29 +440,28 @@ __device__ __forceinline__ void persist_loader(const PersistArgs& A, PCtx& c, ch
         bool rowpair = false;                        // a row piece is TWO consecutive KiB (kib_stride then counts rows)
         auto wptr = [&](const float* w, size_t elems) { return reinterpret_cast<const char*>(w) + ((elems * 4) >> WB); };
         if (sgi < 4 * A.n_layer) {
-            const PLayerK Ly = persist_layer(A.layers, sgi >> 2);
             const int ph = sgi & 3;
-            if (ph == 0) { base = wptr(Ly->qkv_w, (size_t)c.wg * (3 * ND) * D); bytes = (3 * ND * D * 4) >> WB; }
+            if (ph == 0) { base = wptr(wmat, (size_t)c.wg * (3 * ND) * D); bytes = (3 * ND * D * 4) >> WB; }
             else if (ph == 1 && fused) {             // rows [i RF, (i+1) RF) x the 256-element K-slice of head h
                 const int h = c.wg % A.n_head, i = c.wg / A.n_head, RF = ND * A.n_head;
-                base = wptr(Ly->proj_w, (size_t)i * RF * D + h * 256); bytes = (RF * 1024) >> WB; kib_stride = D * 4;
+                base = wptr(wmat, (size_t)i * RF * D + h * 256); bytes = (RF * 1024) >> WB; kib_stride = D * 4;
                 // fp32: one KiB per row; bf16: a KiB of the segment is TWO rows' 512-byte slices (lanes 32.. take the second)
                 if (WB) lane_off = (c.lane >> 5) * (D * 2) + (c.lane & 31) * 16;
             }
-            else if (ph == 1) { base = wptr(Ly->proj_w, (size_t)c.wg * ND * D); bytes = (ND * D * 4) >> WB; }
+            else if (ph == 1) { base = wptr(wmat, (size_t)c.wg * ND * D); bytes = (ND * D * 4) >> WB; }
             else if (ph == 2) {
                 const int dwg = XL ? xx * 32 + jj : c.wg;          // XL: the XCD's workgroups own 512 consecutive hidden units
-                base = wptr(Ly->fc_w, (size_t)dwg * (4 * ND) * D); bytes = (4 * ND * D * 4) >> WB;
+                base = wptr(wmat, (size_t)dwg * (4 * ND) * D); bytes = (4 * ND * D * 4) >> WB;
             }
             else if (XL) {       // rows [32 j, +32) x the XCD's K-slice [512 x, +512) of mlp c_proj: 2 KiB (bf16: 1 KiB) per row
-                base = wptr(Ly->p2_w, (size_t)(32 * jj) * (4 * D) + 512 * xx); bytes = (32 * 2048) >> WB;
+                base = wptr(wmat, (size_t)(32 * jj) * (4 * D) + 512 * xx); bytes = (32 * 2048) >> WB;
                 kib_stride = (4 * D * 4) >> WB; rowpair = !WB;
             }
-            else { base = wptr(Ly->p2_w, (size_t)c.wg * ND * (4 * D)); bytes = (ND * 4 * D * 4) >> WB; }
+            else { base = wptr(wmat, (size_t)c.wg * ND * (4 * D)); bytes = (ND * 4 * D * 4) >> WB; }
         } else if (sgi == 4 * A.n_layer) {
-            base = wptr(A.head_w, (size_t)c.wg * rm * D); bytes = (rm * D * 4) >> WB;
+            base = wptr(wmat, (size_t)c.wg * rm * D); bytes = (rm * D * 4) >> WB;
         } else {
-            base = wptr(A.head_w, (size_t)(rm * kPG + c.wg) * D); bytes = c.wg < rem ? (D * 4) >> WB : 0;
+            base = wptr(wmat, (size_t)(rm * kPG + c.wg) * D); bytes = c.wg < rem ? (D * 4) >> WB : 0;
         }
 #pragma unroll 1
         for (unsigned off = 0; off < bytes; off += kPSlot) {
@@ -872,10 +885,21 @@ __global__ __launch_bounds__(kPThreads) void k_decode_persist(const PersistArgs 
                         }
                     }
                 }
+                // (diagnostics, layer 2, wave 0 of every workgroup: [baseK + wg * 4 + ..] 0 cached K/V rows requested, 1 all of them in,
+                // 2 q | k | v gathered by this wave, 3 its polls that found an old tag.  The stamping variant WAITS for the rows (and for
+                // whatever else the wave has outstanding) before it polls; the production variant does not, its poll queues behind them)
+                unsigned long long* gdK = nullptr;
+                if constexpr (STAMPS) {
+                    if (dbg && l == kPStampLayer && wave == 0 && lane == 0) gdK = dbg + base2 + 2 * 5 * kPG + 8 * kPG + wg * 4;
+                    if (gdK) gdK[0] = wall_clock64();
+                    if (dbg && l == kPStampLayer) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                    if (gdK) gdK[1] = wall_clock64();
+                }
                 const int r0 = wave, r1 = wave + kPCW;                   // this wave's rows of the block (RF <= 16)
                 const float bias0 = fh == 0 && r0 < RF ? Ly.proj_b[fi * RF + r0] : 0.f;
                 const float bias1 = fh == 0 && r1 < RF ? Ly.proj_b[fi * RF + r1] : 0.f;
                 // q_h | k_h | v_h of this step: 768 granules = 384 pairs, ONE 16-byte load per lane of waves 0..5 (a single round trip)
+                unsigned qfails = 0;
                 if (wave < 6 && !c.dead) {
                     const int t = 2 * (wave * 64 + lane), sg = t >> 8;
                     const int off = (iQ + sg * D + fh * 256 + (t & 255)) * 8;
@@ -887,8 +911,11 @@ __global__ __launch_bounds__(kPThreads) void k_decode_persist(const PersistArgs 
                         if (__all(v.y == tg && v.w == tg)) break;
                         if (spin_fail(c, spins, 200 + l, 3)) break;
                     }
+                    if constexpr (STAMPS) qfails = spins;
                     *reinterpret_cast<float2*>(ascr + t) = make_float2(__uint_as_float(v.x), __uint_as_float(v.z));
                 }
+                (void)qfails;
+                if constexpr (STAMPS) { if (gdK) { gdK[2] = wall_clock64(); gdK[3] = qfails; } }
                 cbar(c);
                 stamp_at(l, 1, 0);
                 const float4 q4 = *reinterpret_cast<const float4*>(ascr + lane * 4);

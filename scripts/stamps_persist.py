@@ -19,8 +19,8 @@ tok = torch.zeros(1, device=dev, dtype=torch.int32); lg = torch.empty(1, 1026, d
 L = _lib.lib(); L.gvc_gpt_debug_stamps.restype = C.c_int; L.gvc_gpt_debug_stamps.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
 for _ in range(4): eng.decode_step(slots, tok, lg, lt)
 nl = dims["n_layer"]
-hb = np.zeros(20 * (nl + 2) + 10 * 256 + 8 * 256, dtype=np.uint64)
-n = L.gvc_gpt_debug_stamps(eng._h, hb.ctypes.data_as(C.c_void_p), -1)
+hb = np.zeros(20 * (nl + 2) + 10 * 256 + 8 * 256 + 4 * 256, dtype=np.uint64)
+n = L.gvc_gpt_debug_stamps(eng._h, hb.ctypes.data_as(C.c_void_p), -3)       # (-3: with the K/V arrival stamps behind the others)
 t0 = int(hb[20 * (nl + 1)])
 us = lambda v: (int(v) - t0) / 100.0
 names = ["A qkv", "B attn", "C proj", "D fc", "E mlp"]
@@ -65,3 +65,22 @@ if gd[:, 0].any():
             m = xcd == x
             print(f"  XCD {x}: {m.sum():3d} | {np.median(a2[m,1])-ref:5.2f} | {np.median(a2[m,2])-ref:5.2f} | {np.median(a2[m,5])-ref:5.2f} / {a2[m,5].max()-ref:5.2f} | "
                   f"{np.median(t_sent[m]):5.2f} | {np.median(t_done[m]):5.2f} | {np.median(a2[m,7])-ref:5.2f} | {np.median(a2[m,9])-ref:5.2f}")
+
+# fused phase BC at layer 2, wave 0 of every workgroup: cached K/V rows requested -> all in -> q | k | v gathered, and when BC finished.
+# NOTE: the stamping variant waits (vmcnt) for the K/V rows before it polls q | k | v, so that the two arrivals can be told apart; the
+# production variant issues the poll behind the row loads without waiting, and the poll returns when both are in.
+b4 = b3 + 8 * 256
+kv = hb[b4:b4 + 4 * 256].reshape(256, 4)
+if kv[:, 0].any():
+    t_iss, t_kv, t_q = [np.array([us(v) for v in kv[:, k]]) for k in range(3)]
+    q4 = lambda v: f"min {v.min():6.2f}  median {np.median(v):6.2f}  p90 {np.percentile(v, 90):6.2f}  max {v.max():6.2f}"
+    print(f"layer {LS} BC, over 256 workgroups (us):")
+    print(f"  K/V requested -> K/V in      : {q4(t_kv - t_iss)}")
+    print(f"  K/V in -> q|k|v gathered     : {q4(t_q - t_kv)}")
+    print(f"  K/V requested -> q gathered  : {q4(t_q - t_iss)}")
+    print(f"  BC finished, after the first : {q4(a2[:, 5] - a2[:, 5].min())}")
+    print(f"  last A publish {a2[:, 1].max() - ref:.2f}, median K/V in {np.median(t_kv) - ref:.2f}, median q gathered {np.median(t_q) - ref:.2f} (us after the first workgroup's phase-A input)")
+    print(f"  polls of q|k|v that found an old tag (0: the seam was there when the K/V rows came in): median {np.median(kv[:, 3]):.0f}  max {kv[:, 3].max()}  "
+          f"workgroups with none: {int((kv[:, 3] == 0).sum())} of 256")
+    early = (t_q - t_kv) >= 0.3
+    print(f"  workgroups whose K/V rows were in >= 0.3 us before q|k|v was gathered: {int(early.sum())} of 256")
