@@ -992,7 +992,7 @@ static int persist_prepare(gvc_gpt* c) {
     const int ng_hd = kPCW * 256;                       // lane-group states of the attention phase: [kPCW * 64 / (hd / 4)][hd]
     c->p_hvec = 4 * d > d + ng_hd ? 4 * d : d + ng_hd;
     c->p_ascr = 3 * c->hd + 64;
-    const size_t other = ((size_t)c->p_hvec + d + c->p_ascr) * sizeof(float) + kCtlWords * sizeof(unsigned);
+    const size_t other = ((size_t)c->p_hvec + d + c->p_ascr) * sizeof(float) + kCtlWords * sizeof(unsigned) + kPStage * sizeof(float);
     // the ring takes what the device's opt-in LDS limit leaves (160 KiB on gfx950: 8 slots)
     int dev_id = 0, lds_optin = 0;
     if (hipGetDevice(&dev_id) != hipSuccess ||

@@ -6,7 +6,7 @@
 // tail of its own HBM burst, and the step sits at ~0.3 of the HBM roofline.  Here 256 resident workgroups (one per
 // CU) run the whole step:
 //   * a LOADER wave per workgroup streams that workgroup's weight rows (contiguous in the row-per-output layout) into
-//     an LDS ring with LDS-DMA (global_load_lds, non-temporal), at most two 16 KiB fills in flight, up to 8 fills
+//     an LDS ring with LDS-DMA (global_load_lds, non-temporal), ONE 16 KiB fill in flight (two were measured: +0.5 %), up to 8 fills
 //     (~1.5 phases) ahead of the consumers: the HBM stream keeps running across the dependency seams;
 //   * eight CONSUMER waves gather the phase input, do the LayerNorm / attention / dot products out of LDS and publish
 //     the phase output.  Consumer waves never have a weight load outstanding (vmcnt retires in order per wave), so
@@ -17,7 +17,9 @@
 //     and load) until its tag is the expected one.  A sweep of one or two loads per lane re-reads everything in every poll
 //     pass (one round trip once the data is there); larger sweeps poll one sentinel load per lane and read the rest when it
 //     has arrived.  The tag encodes (step epoch, layer, phase); nothing is zeroed between steps, the epoch lives in
-//     device memory and is bumped by the last workgroup to finish the step.
+//     device memory and is bumped by the last workgroup to finish the step.  Which wave stores a granule is free: the fused phase BC,
+//     whose sixteen granules per workgroup are one aligned 128-byte line, stages them in LDS and lets the wave that finishes last
+//     store the whole line with one instruction (stage_arrive below; profiles/decode_publish_lines.md).
 // Per layer: A [LN1, c_attn] -> B [attention, split over <= 8 key chunks per head, a few workgroups] ->
 //            C [merge of the chunk partials, attn c_proj, residual] -> D [LN2, c_fc, gelu_new] -> E [mlp c_proj, residual];
 // then the double-LayerNorm head.  Contexts of <= 80 keys (head_dim 256, <= 4 heads) fuse B and C (persist_fused_attn).
@@ -56,7 +58,8 @@ constexpr int kPUF = 10;            // ... in the fused attention + projection p
 constexpr unsigned kPSpinLimit = 400000;
 constexpr int kPStampLayer = 2;     // GVC_PERSIST_STAMPS: the layer whose phases every workgroup stamps
 // LDS control words
-constexpr int kCtlFilled = 0, kCtlDone = 1, kCtlArrive = 1 + kPCW, kCtlAbort = 2 + kPCW, kCtlXcd = 3 + kPCW, kCtlWords = 16;
+constexpr int kCtlFilled = 0, kCtlDone = 1, kCtlArrive = 1 + kPCW, kCtlAbort = 2 + kPCW, kCtlXcd = 3 + kPCW, kCtlPub = 4 + kPCW, kCtlWords = 16;
+constexpr int kPStage = 16;         // floats of the publish staging array behind the control words (one-stream step only): phase BC's granules of a workgroup
 
 typedef unsigned long long pu64;
 typedef unsigned int pu32x4 __attribute__((ext_vector_type(4)));
@@ -228,6 +231,28 @@ __device__ __forceinline__ void publish_local(__amdgpu_buffer_rsrc_t rs, int ind
     pu32x2 g;
     g.x = __float_as_uint(v); g.y = tag;
     __builtin_amdgcn_raw_buffer_store_b64(g, rs, index * 8, 0, 0);
+}
+
+// Whole-line publish (phase BC).  A 128-byte line that sixteen single-lane stores assemble is under construction for sixteen fabric writes
+// while every workgroup polls it: last store -> last workgroup ready 5.6 us idle / 5.9 us beside the weight stream, against 2.05 / 3.35 us
+// when ONE store instruction writes the line (scripts/ubench/publish_line.hip, profiles/decode_publish_lines.md).  So a wave puts its
+// finished values into the staging array behind the control words (index = granule number relative to the workgroup's first one) and bumps
+// an LDS arrival counter; the wave whose bump is the eighth of the phase stores all of the workgroup's granules with one instruction.
+// Nobody waits for anybody: every consumer wave bumps exactly once per phase, with or without values of its own, and the barrier that
+// every phase has behind its gather keeps the bumps (and the staging array) of one layer apart from the next one's.  Granule indices, tags
+// and values are what the per-wave publishes wrote.  Only BC publishes this way: phases A, C and E, whose lines a workgroup writes with a
+// few multi-lane stores already, lost time when their early waves' values had to wait for the last wave (same note).
+__device__ __forceinline__ bool stage_arrive(PCtx& c) {
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");        // this wave's staged values are in LDS before its bump
+    unsigned old = 0;
+    if (c.lane == 0) old = __hip_atomic_fetch_add(c.ctl + kCtlPub, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    old = __builtin_amdgcn_readfirstlane(old);
+    asm volatile("" ::: "memory");
+    return (old & (unsigned)(kPCW - 1)) == (unsigned)(kPCW - 1);
+}
+// n <= 64 consecutive granules from index `first` on, values stg[0 .. n): ONE store instruction, a lane per granule
+__device__ __forceinline__ void publish_run(__amdgpu_buffer_rsrc_t rs, int first, int n, unsigned tag, const float* stg, int lane) {
+    if (lane < n) publish(rs, first + lane, tag, stg[lane]);
 }
 
 // Sweep of a phase input by the consumer waves.  The input has NP planes of n granules (a K-split producer publishes
@@ -591,7 +616,8 @@ __global__ __launch_bounds__(kPThreads) void k_decode_persist(const PersistArgs 
         float* const hvec = smem + o_hvec; float* const ovec = hvec; float* const o_s = hvec + D;                                 \
         float* const xvec = smem + o_xvec; float* const ascr = xvec + D;                                                          \
         c.ctl = reinterpret_cast<unsigned*>(smem + o_ctl);                                                                        \
-        (void)ovec; (void)o_s; (void)ascr
+        float* const stg = smem + o_ctl + kCtlWords;  /* publish staging (stage_arrive) */                                       \
+        (void)ovec; (void)o_s; (void)ascr; (void)stg
         // what the layer loop needs of the arguments; the embedding's and the head's are read there
         const PArgsK K = persist_args();
         const unsigned rmask = K->ring_slots - 1;
@@ -627,6 +653,13 @@ __global__ __launch_bounds__(kPThreads) void k_decode_persist(const PersistArgs 
             if constexpr (STAMPS) {
                 if (stamp0 && wg == 0) dbg[(l * 5 + p) * 4 + k] = wall_clock64();
                 if (stamp0 && l == kPStampLayer && k < 2) dbg[base2 + (wg * 5 + p) * 2 + k] = wall_clock64();
+            }
+        };
+        // the wave that stores phase BC's granules (whichever staged last), workgroup 0: [(l * 5 + 2) * 4 + k], k = 2 staging complete,
+        // 3 store issued
+        auto stamp_pub = [&](int l, int p, int k) {
+            if constexpr (STAMPS) {
+                if (dbg && wg == 0 && lane == 0) dbg[(l * 5 + p) * 4 + k] = wall_clock64();
             }
         };
         unsigned fs = 0;                                 // first fill of the current weight segment
@@ -982,8 +1015,14 @@ __global__ __launch_bounds__(kPThreads) void k_decode_persist(const PersistArgs 
                         s0 = xvec[fi * RF + r0] + (s0 + bias0);
                         if (r1 < RF) s1 = xvec[fi * RF + r1] + (s1 + bias1);
                     }
-                    if (lane == 0) publish(grs, iX0 + fh * D + fi * RF + r0, tag_of(l, 2), s0);
-                    if (lane == 1 && r1 < RF) publish(grs, iX0 + fh * D + fi * RF + r1, tag_of(l, 2), s1);
+                    if (lane == 0) stg[r0] = s0;
+                    if (lane == 1 && r1 < RF) stg[r1] = s1;
+                }
+                // the block's RF granules of plane fh, stored by the wave that staged last: with 16 rows one aligned 128-byte line
+                if (stage_arrive(c)) {
+                    stamp_pub(l, 2, 2);
+                    publish_run(grs, iX0 + fh * D + fi * RF, RF, tag_of(l, 2), stg, lane);
+                    stamp_pub(l, 2, 3);
                 }
                 fs += nfC;
                 phase_done();

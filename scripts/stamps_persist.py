@@ -40,6 +40,11 @@ LS = 2          # the layer every workgroup stamps (csrc/persist_kernel.h: kPSta
 ex = np.array([[W(l, 0, 2) - W(l, 0, 0), W(l, 0, 3) - W(l, 0, 2), W(l, 0, 1) - W(l, 0, 3),
                 W(l, 1, 2) - W(l, 1, 0), W(l, 1, 3) - W(l, 1, 2), W(l, 1, 1) - W(l, 1, 3)] for l in range(2, nl)]).mean(axis=0)
 print("A: LN %.2f rows %.2f publish %.2f | B: scores+fold %.2f combine barrier %.2f merge+publish %.2f" % tuple(ex))
+# phase BC's whole-line publish (the wave that staged last stores the workgroup's granules; a library from before it leaves these zero).
+# NOTE: "C proj out" is wave 0's stamp; when another wave stages last, the line leaves after it
+if hb[(2 * 5 + 2) * 4 + 2]:
+    pl = np.array([[W(l, 2, 2) - W(l, 2, 0), W(l, 2, 3) - W(l, 2, 2), W(l, 3, 0) - W(l, 2, 3), W(l, 2, 3) - W(l, 2, 1)] for l in range(2, nl)]).mean(axis=0)
+    print("BC publish, workgroup 0: head merged -> last wave staged %.2f, -> line stored %.2f, -> D input ready %.2f; line stored after wave 0's out stamp %.2f" % tuple(pl))
 # every workgroup at layer 2
 b2 = 20 * (nl + 2)
 a2 = np.array([[us(hb[b2 + (w * 5 + p) * 2 + k]) for p in range(5) for k in range(2)] for w in range(256)])
