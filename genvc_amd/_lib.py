@@ -159,6 +159,25 @@ class GemmCase(C.Structure):
 # gvc_gemm_case.kind (GVC_GEMM_*)
 GEMM_TILED, GEMM_SKINNY, GEMM_SKINNY_LN, GEMM_STRIP, GEMM_STRIP_GEOM, GEMM_LN_ROWS, GEMM_LN_ROWS_B16, GEMM_TO_FM16, GEMM_TO_FM16_BF16 = range(9)
 
+class AttnCase(C.Structure):
+    """gvc_attn_case (include/genvc_hip.h): one launch of one attention kernel class on caller-owned device buffers (test hook)"""
+    _fields_ = [(n, C.c_int32) for n in ("kind", "head_dim", "n_head", "kv_bf16")] + \
+        [(n, C.c_void_p) for n in ("q", "kbase", "vbase")] + \
+        [(n, C.c_int64) for n in ("k_batch_stride", "k_head_stride")] + \
+        [(n, C.c_int32) for n in ("q_stride", "k_row_stride", "T", "causal", "n_keys", "out_stride", "out_fm16", "mask_stride")] + \
+        [("scale", C.c_float), ("reserved", C.c_int32)] + \
+        [(n, C.c_void_p) for n in ("slots", "base_len", "out", "key_mask")] + \
+        [(n, C.c_int32) for n in ("chunks", "rows", "direct", "wide", "batch", "max_keys", "taken", "ran")] + \
+        [(n, C.c_void_p) for n in ("seq_len", "Wp")] + \
+        [(n, C.c_int32) for n in ("max_seq", "d", "nw", "mask")] + \
+        [("fmask", C.c_void_p), ("ld", C.c_int64), ("bs", C.c_int64)] + \
+        [(n, C.c_int32) for n in ("Tq", "Tk", "out_rows", "E")]
+
+
+# gvc_attn_case.kind (GVC_ATTN_*) and .ran (GVC_ATTN_RAN_*)
+ATTN_ROWS, ATTN_TILE, ATTN_TILE_MASKED, ATTN_FUSED_PROJ, ATTN_64 = range(5)
+ATTN_RAN_NONE, ATTN_RAN_SHORT, ATTN_RAN_TILED = range(3)
+
 _P = C.c_void_p
 _SIGNATURES = {
     "gvc_version": (C.c_int, []),
@@ -264,6 +283,7 @@ _SIGNATURES = {
     "gvc_fb16_index": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     "gvc_gemm_probe": (C.c_int, [C.c_int32, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_f32p, _P]),
     "gvc_gemm_probe_ex": (C.c_int, [C.POINTER(GemmCase), _P]),
+    "gvc_attn_probe": (C.c_int, [C.POINTER(AttnCase), _P]),
     "gvc_perceiver_create": (C.c_int, [C.POINTER(PerceiverDims), C.POINTER(_P)]),
     "gvc_perceiver_destroy": (C.c_int, [_P]),
     "gvc_perceiver_bind_weight": (C.c_int, [_P, C.c_char_p, _P, C.c_int64, _P]),

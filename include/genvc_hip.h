@@ -955,6 +955,51 @@ typedef struct gvc_gemm_case {
 } gvc_gemm_case;
 int gvc_gemm_probe_ex(gvc_gemm_case* c, gvc_stream s);
 
+/* Test hook for every attention kernel (csrc/gpt_kernels.h, csrc/attn64.h; not a reference interface), after the pattern of
+ * gvc_gemm_probe_ex: one launch of one kernel class on CALLER-OWNED device buffers, described by the fields a product caller sets (AttnArgs,
+ * AttnProjArgs, the arguments of k_attn64_mfma), so that a test can surround every buffer with guard regions and poison what the call must
+ * not read.  No allocation, no conversion, no timing; synchronises the stream.  The kernels trust their arguments as they trust the
+ * product's: the caller owns every bound (strides, slot numbers, key counts against the cache it passes).
+ * kind: GVC_ATTN_ROWS         launch_attention_hd(head_dim, n_head, args, chunks, rows, direct, wide, kv_bf16): k_attention, one workgroup per
+ *                             (chunk, head, row).  direct: chunks = 1, out [rows][out_stride] row-major or FM16; otherwise out holds the chunk
+ *                             partials [rows][n_head][chunks][head_dim + 4] = (o unnormalised, m, l, two floats nobody writes);
+ *       GVC_ATTN_TILE         launch_attention_tile(head_dim, n_head, args, batch, max_keys, kv_bf16): `taken` comes back 1 when the chooser took
+ *                             the call (0: it left it to k_attention and nothing was launched) and `ran` names the kernel its rule selects
+ *                             (GVC_ATTN_RAN_SHORT: k_attention_tile_short, max_keys <= 128; GVC_ATTN_RAN_TILED: k_attention_tile).  `ran` is
+ *                             DERIVED, not observed: the probe restates the launchers' threshold (gpt_kernels.h launch_attention_tile,
+ *                             forward_eval.hip launch_attention_tile_masked) and must be kept equal to it when that rule changes;
+ *       GVC_ATTN_TILE_MASKED  launch_attention_tile_masked(head_dim, n_head, args, batch, max_keys): key_mask [batch][mask_stride], fp32 cache,
+ *                             no base_len; `taken` and `ran` as above (every shape is taken);
+ *       GVC_ATTN_FUSED_PROJ   k_attn_proj<256, kv_bf16> on grid (d / 16, n_head): q [d], kbase / vbase [slot][n_head][max_seq][256], slots[0],
+ *                             seq_len[slot] + 1 keys, Wp [d][d], out = part2 [n_head][d].  Refused (GVC_ERR_ARG) unless head_dim == 256,
+ *                             d == n_head * 256, d a multiple of 16, d <= 1024 and seq_len[slots[0]] + 1 <= 128 (the kernel has no place for more
+ *                             keys and would ignore them silently; the probe reads the two integers back to check);
+ *       GVC_ATTN_64           k_attn64_mfma<mask, nw> (nw 4 or 16) on grid (ceil(Tq / 16), n_head, batch): q / kbase / vbase fp32 matrices with
+ *                             row stride ld and batch stride bs, out [batch * out_rows][E] row-major or FM16, fmask int32 [batch][Tk]
+ *                             (nonzero = excluded; read only with mask != 0). */
+enum { GVC_ATTN_ROWS = 0, GVC_ATTN_TILE = 1, GVC_ATTN_TILE_MASKED = 2, GVC_ATTN_FUSED_PROJ = 3, GVC_ATTN_64 = 4 };
+enum { GVC_ATTN_RAN_NONE = 0, GVC_ATTN_RAN_SHORT = 1, GVC_ATTN_RAN_TILED = 2 };
+typedef struct gvc_attn_case {
+    int32_t kind, head_dim, n_head, kv_bf16;
+    /* AttnArgs */
+    const float* q; const void* kbase; const void* vbase;
+    int64_t k_batch_stride, k_head_stride;
+    int32_t q_stride, k_row_stride, T, causal, n_keys, out_stride, out_fm16, mask_stride;
+    float scale; int32_t reserved;
+    const int32_t* slots; const int32_t* base_len; float* out; const uint8_t* key_mask;
+    /* the launchers' own arguments; taken / ran: written by the call */
+    int32_t chunks, rows, direct, wide, batch, max_keys, taken, ran;
+    /* AttnProjArgs (with q, kbase, vbase, slots, n_head, scale, out) */
+    const int32_t* seq_len; const float* Wp;
+    int32_t max_seq, d;
+    /* k_attn64_mfma (with q, kbase, vbase, out, n_head, batch, scale, out_fm16) */
+    int32_t nw, mask;
+    const int32_t* fmask;
+    int64_t ld, bs;
+    int32_t Tq, Tk, out_rows, E;
+} gvc_attn_case;
+int gvc_attn_probe(gvc_attn_case* c, gvc_stream s);
+
 /* Element index of (row m, column k) of an [M][K] bf16 matrix in the fragment-major layout of the bf16 matrix-core GEMMs
  * (csrc/gemm_b16.h: fb16_index; M % 16 == 0, K % 32 == 0): each (16 rows x 32 k) block is 64 fragments of 8 consecutive k, fragment
  * (m % 16) + 16 * ((k % 32) / 8) -- the lane of v_mfma_f32_16x16x32_bf16 that holds them.  Host arithmetic only. */
