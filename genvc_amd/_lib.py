@@ -61,6 +61,15 @@ class LogitsWarpers(C.Structure):
     _fields_ = [("typical_p", C.c_float), ("epsilon_cutoff", C.c_float), ("eta_cutoff", C.c_float), ("reserved", C.c_int32)]
 
 
+RAS_MAX_WINDOW = 64                  # GVC_RAS_MAX_WINDOW
+RAS_SALT = 0x5241535F52454452        # GVC_RAS_SALT: the redraw's uniform is rng_uniform(seed ^ RAS_SALT, step, row)
+
+
+class LogitsRas(C.Structure):
+    """gvc_logits_ras (include/genvc_hip.h): repetition-aware sampling of one set (16 bytes); window 0 = off"""
+    _fields_ = [(n, C.c_int32) for n in ("window", "min_count", "prompt_len", "reserved")]
+
+
 BIAS_MAX_SEQS = 32     # GVC_BIAS_MAX_SEQS
 BIAS_MAX_LEN = 8       # GVC_BIAS_MAX_LEN
 
@@ -250,6 +259,13 @@ _SIGNATURES = {
                                         C.POINTER(RowSampling), C.POINTER(LogitsProcessors), C.POINTER(LogitsWarpers), C.c_int32, c_i32p,
                                         C.POINTER(LogitsBias), C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_int32, _P, _P,
                                         C.c_int32, C.c_int32, _P]),
+    "gvc_sample_ras": (C.c_int, [_P, C.c_int32, _P, C.c_int32, _P, _P, C.POINTER(SampleParams), C.POINTER(RowSampling),
+                                 C.POINTER(LogitsProcessors), C.POINTER(LogitsWarpers), C.c_int32, c_i32p, C.POINTER(LogitsBias),
+                                 C.POINTER(LogitsRas), _P, C.c_int32, _P, _P]),
+    "gvc_gpt_generate_ras": (C.c_int, [_P, _P, _P, C.c_int32, C.c_float, _P, C.c_int32, _P, _P, C.POINTER(SampleParams),
+                                       C.POINTER(RowSampling), C.POINTER(LogitsProcessors), C.POINTER(LogitsWarpers), C.c_int32, c_i32p,
+                                       C.POINTER(LogitsBias), C.POINTER(LogitsRas), _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32,
+                                       _P, C.c_int32, _P, _P, C.c_int32, C.c_int32, _P]),
     "gvc_transition_scores": (C.c_int, [_P, C.c_int64, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "gvc_gpt_verify": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, _P, _P, _P]),
     "gvc_gpt_truncate": (C.c_int, [_P, _P, C.c_int32, _P, _P]),

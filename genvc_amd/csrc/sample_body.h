@@ -230,6 +230,7 @@ __device__ __forceinline__ void sample_row(const SampleCall& C, int b, const flo
     __syncthreads();
 
     int tok;
+    float rmx;          // the largest entry of sc (the redraw of a gvc_logits_ras row takes its weights relative to it)
     if (top_k == 1) {
         // exactly one candidate survives TopK(1): argmax of the penalised scores, first index on ties
         float bv = -INFINITY; int bi = 0x7fffffff;
@@ -249,6 +250,7 @@ __device__ __forceinline__ void sample_row(const SampleCall& C, int b, const flo
         }
         __syncthreads();
         tok = s_tok;
+        rmx = sc[tok];
         if (so) {
             if (C.scores_warped) {
                 // TopK(1): the entries that equal the maximum stay (HF keeps ties), at their temperature-scaled score
@@ -377,9 +379,48 @@ __device__ __forceinline__ void sample_row(const SampleCall& C, int b, const flo
         }
         __syncthreads();
         tok = s_tok;
+        rmx = mx;
     }
 
     if constexpr (kWarpOnly) return;
+    // Repetition-aware sampling (gvc_logits_ras): the token stands unless it fills min_count of the row's last
+    // `window` generated ids; then it is drawn again from the whole row as the chain left it ahead of truncation (sc).  Every
+    // condition below is uniform over the workgroup; a row without RAS meets no barrier here
+    if (const gvc_logits_ras* A = row_ras(C, b); A && !C.finished[b] && len < C.ids_stride) {
+        const int n_gen = len - min(max(A->prompt_len, 0), len);          // the fake prompt ids never count
+        const int w = min(min(A->window, GVC_RAS_MAX_WINDOW), n_gen);
+        if (tid < 64) {                                                     // (wave 0: w <= 64 ids, ids[len - w .. len))
+            const unsigned long long hit = __ballot(tid < w && ids[len - 1 - tid] == tok);
+            if (tid == 0) s_nk = __popcll(hit);
+        }
+        __syncthreads();
+        if (s_nk >= A->min_count && tok != C.p.eos_token) {
+            // the draw's arithmetic on every finite entry: expf in fp32 relative to the row maximum, widened; running mass in double
+            // in vocabulary order; first index that reaches u2 * total; else the last kept index
+            const int i0v = 2 * tid, i1v = 2 * tid + 1;
+            const bool k0 = i0v < V && sc[i0v] > -INFINITY, k1 = i1v < V && sc[i1v] > -INFINITY;
+            const double w0 = k0 ? (double)expf(sc[i0v] - rmx) : 0.0, w1 = k1 ? (double)expf(sc[i1v] - rmx) : 0.0;
+            double total;
+            const double ex = block_scan_excl<double>(w0 + w1, dscr, &total);
+            const double target = (R ? (double)rng_uniform(R->seed ^ GVC_RAS_SALT, (uint64_t)(R->rng_step0 + step), (uint64_t)R->rng_row)
+                                     : (double)rng_uniform(C.p.seed ^ GVC_RAS_SALT, (uint64_t)(C.i0 + step), (uint64_t)b)) * total;
+            const double a0 = ex + w0, a1 = a0 + w1;
+            int pick = 0x7fffffff, lastk = -1;
+            if (k0) { lastk = i0v; if (a0 >= target) pick = i0v; }
+            if (k1) { lastk = i1v; if (a1 >= target && pick == 0x7fffffff) pick = i1v; }
+            if (tid == 0) { s_pick = 0x7fffffff; s_last = -1; }          // (behind the scan's barriers: every thread has read s_tok)
+            __syncthreads();
+            if (pick != 0x7fffffff) atomicMin(&s_pick, pick);
+            if (lastk >= 0) atomicMax(&s_last, lastk);
+            __syncthreads();
+            if (tid == 0) {
+                s_tok = s_pick != 0x7fffffff ? s_pick : (s_last >= 0 ? s_last : tok);
+                if (C.ras_redraws) C.ras_redraws[b] += 1;
+            }
+            __syncthreads();
+            tok = s_tok;
+        }
+    }
     // finished rows emit the pad (= eos) token (stream_generator.py:861-864, 872-874); a row whose ids buffer is
     // full is finished too (the caller sized it for the whole run: nothing past it can be accounted for)
     if (C.finished[b] || len >= C.ids_stride) tok = C.p.eos_token;

@@ -60,6 +60,12 @@ struct SampleCall {
     // memory), call-wide: independent of rows, proc_sets and warps.  Null: none, and the kernels compute exactly what they compute
     // without this field
     const gvc_logits_bias* bias;
+    // nullable: repetition-aware sampling (gvc_*_ras calls: gvc_logits_ras, device memory), one entry per set, indexed like warps: row b
+    // uses ras[set_of_row[b]] (none for -1), ras[0] when set_of_row is null.  Null, or an entry whose window is 0: none, and k_sample
+    // computes exactly what it computes without this field, through the same barriers
+    const gvc_logits_ras* ras;
+    // nullable: [B] redraws of each row, incremented by the step that redraws (read only with ras)
+    int32_t* ras_redraws;
 };
 
 // row b's entry of a per-step output buffer at this step (see SampleCall::scores_out)
@@ -81,6 +87,14 @@ __device__ __forceinline__ const gvc_logits_warpers* row_warps(const SampleCall&
     return k >= 0 ? C.warps + k : nullptr;
 }
 
+// the repetition-aware sampling of row b (uniform over the row's workgroup); null: off
+__device__ __forceinline__ const gvc_logits_ras* row_ras(const SampleCall& C, int b) {
+    if (!C.ras) return nullptr;
+    const int k = C.set_of_row ? C.set_of_row[b] : 0;
+    return k >= 0 && C.ras[k].window > 0 ? C.ras + k : nullptr;
+}
+
+// a call with a RAS table runs on k_sample whatever its top_k: the redraw reads the full row the greedy kernel never stores
 int launch_sample(const SampleCall& sc, hipStream_t s);
 // the call parameters live in device memory (graph replay)
 // greedy: the call has top_k == 1 (sample_greedy_ok), or every row of a keyed call has: the argmax-only kernel
@@ -125,6 +139,16 @@ int check_warp_sets(const gvc_logits_processors* sets, const gvc_logits_warpers*
                     int vocab);
 // warps[0..n_sets) -> dst[0..n_sets) on stream s (one small launch)
 int launch_stage_warps(gvc_logits_warpers* dst, const gvc_logits_warpers* warps, int n_sets, hipStream_t s);
+// RAS entries of a gvc_*_ras call, all n_sets of them BY VALUE in one launch (1 KB of kernel argument)
+struct RasTable {
+    gvc_logits_ras r[kMaxSampleRows];
+    int32_t n;
+};
+// host-side checks of a RAS table: 1 <= n_sets <= 64, window in [0, GVC_RAS_MAX_WINDOW], min_count >= 1 where the window is on,
+// prompt_len >= 0, reserved == 0
+int check_ras(const gvc_logits_ras* ras, int n_sets);
+// ras[0..n_sets) -> dst[0..n_sets) on stream s (one small launch)
+int launch_stage_ras(gvc_logits_ras* dst, const gvc_logits_ras* ras, int n_sets, hipStream_t s);
 // *bias -> *dst on stream s, BY VALUE in one small launch (1.3 KB of kernel argument); check_bias (logits_proc.h) comes first
 int launch_stage_bias(gvc_logits_bias* dst, const gvc_logits_bias* bias, hipStream_t s);
 

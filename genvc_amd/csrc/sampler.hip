@@ -152,6 +152,10 @@ __global__ void k_stage_warps(gvc_logits_warpers* dst, WarpTable t) {
     if ((int)threadIdx.x < t.n) dst[threadIdx.x] = t.w[threadIdx.x];
 }
 
+__global__ void k_stage_ras(gvc_logits_ras* dst, RasTable t) {
+    if ((int)threadIdx.x < t.n) dst[threadIdx.x] = t.r[threadIdx.x];
+}
+
 __global__ void k_stage_bias(gvc_logits_bias* dst, gvc_logits_bias src) {
     int32_t* d = reinterpret_cast<int32_t*>(dst);
     const int32_t* w = reinterpret_cast<const int32_t*>(&src);
@@ -313,9 +317,31 @@ int launch_stage_warps(gvc_logits_warpers* dst, const gvc_logits_warpers* warps,
     return GVC_OK;
 }
 
+int check_ras(const gvc_logits_ras* ras, int n_sets) {
+    GVC_REQUIRE(ras && n_sets >= 1 && n_sets <= kMaxSampleRows, GVC_ERR_ARG, "ras: need 1..%d entries, got %d", kMaxSampleRows, n_sets);
+    for (int k = 0; k < n_sets; ++k) {
+        const gvc_logits_ras& r = ras[k];
+        GVC_REQUIRE(r.window >= 0 && r.window <= GVC_RAS_MAX_WINDOW && (r.window == 0 || r.min_count >= 1) && r.prompt_len >= 0 &&
+                        r.reserved == 0,
+                    GVC_ERR_ARG, "ras: entry %d has window %d (0..%d), min_count %d (>= 1), prompt_len %d (>= 0), reserved %d (0)", k,
+                    r.window, GVC_RAS_MAX_WINDOW, r.min_count, r.prompt_len, r.reserved);
+    }
+    return GVC_OK;
+}
+
+int launch_stage_ras(gvc_logits_ras* dst, const gvc_logits_ras* ras, int n_sets, hipStream_t s) {
+    RasTable t;
+    memset(&t, 0, sizeof(t));
+    memcpy(t.r, ras, (size_t)n_sets * sizeof(gvc_logits_ras));
+    t.n = n_sets;
+    hipLaunchKernelGGL(k_stage_ras, dim3(1), dim3(kMaxSampleRows), 0, s, dst, t);
+    GVC_LAUNCH_CHECK();
+    return GVC_OK;
+}
+
 int launch_sample(const SampleCall& sc, hipStream_t s) {
     GVC_REQUIRE(sc.p.vocab > 0 && sc.p.vocab <= kSortN, GVC_ERR_UNSUPPORTED, "sample: vocab %d > %d", sc.p.vocab, kSortN);
-    if (sample_greedy_ok(sc.p.top_k, sc.latents_out ? sc.d : 0)) hipLaunchKernelGGL(k_sample_greedy, dim3(sc.B), dim3(kGreedyThreads), 0, s, sc, (const SampleCall*)nullptr);
+    if (!sc.ras && sample_greedy_ok(sc.p.top_k, sc.latents_out ? sc.d : 0)) hipLaunchKernelGGL(k_sample_greedy, dim3(sc.B), dim3(kGreedyThreads), 0, s, sc, (const SampleCall*)nullptr);
     else hipLaunchKernelGGL(k_sample, dim3(sc.B), dim3(kSampThreads), 0, s, sc, (const SampleCall*)nullptr);
     GVC_LAUNCH_CHECK();
     return GVC_OK;
@@ -346,6 +372,8 @@ struct SampleOptions {
     const int32_t* set_of_row = nullptr;
     const gvc_logits_bias* bias = nullptr;
     bool index = false;          // stage set_of_row and hand it to the kernel (the entries that take sets or warpers)
+    const gvc_logits_ras* ras = nullptr;          // n_sets RAS entries (gvc_sample_ras) ...
+    int32_t* ras_redraws = nullptr;               // ... and the rows' redraw counters (device)
 };
 
 static int sample_once(const float* logits, int B, int32_t* ids, int ids_stride, int32_t* ids_len, int32_t* finished,
@@ -358,8 +386,9 @@ static int sample_once(const float* logits, int B, int32_t* ids, int ids_stride,
     const size_t warp_bytes = o.warps ? (size_t)o.n_sets * sizeof(gvc_logits_warpers) : 0;
     const size_t row_bytes = o.rows ? (size_t)B * sizeof(gvc_row_sampling) : 0;
     const size_t sor_bytes = (size_t)B * sizeof(int32_t);          // (always there: the allocation is never empty)
+    const size_t ras_bytes = o.ras ? (size_t)o.n_sets * sizeof(gvc_logits_ras) : 0;
     char* d = nullptr;
-    GVC_CHECK_HIP(hipMallocAsync((void**)&d, bias_bytes + proc_bytes + set_bytes + warp_bytes + row_bytes + sor_bytes, s));
+    GVC_CHECK_HIP(hipMallocAsync((void**)&d, bias_bytes + proc_bytes + set_bytes + warp_bytes + row_bytes + sor_bytes + ras_bytes, s));
     char* at = d;
     auto carve = [&at](size_t bytes) { char* q = bytes ? at : nullptr; at += bytes; return q; };
     gvc_logits_bias* d_bias = reinterpret_cast<gvc_logits_bias*>(carve(bias_bytes));
@@ -368,6 +397,7 @@ static int sample_once(const float* logits, int B, int32_t* ids, int ids_stride,
     gvc_logits_warpers* d_warps = reinterpret_cast<gvc_logits_warpers*>(carve(warp_bytes));
     gvc_row_sampling* d_rows = reinterpret_cast<gvc_row_sampling*>(carve(row_bytes));
     int32_t* d_sor = reinterpret_cast<int32_t*>(carve(sor_bytes));
+    gvc_logits_ras* d_ras = reinterpret_cast<gvc_logits_ras*>(carve(ras_bytes));
     int rc = GVC_OK;
     if (o.bias) rc = launch_stage_bias(d_bias, o.bias, s);
     if (rc == GVC_OK && o.proc) rc = launch_stage_proc(d_proc, o.proc, s);
@@ -375,12 +405,14 @@ static int sample_once(const float* logits, int B, int32_t* ids, int ids_stride,
     if (rc == GVC_OK && o.warps) rc = launch_stage_warps(d_warps, o.warps, o.n_sets, s);
     if (rc == GVC_OK && o.index) rc = launch_stage_set_index(d_sor, sor, B, s);
     if (rc == GVC_OK && o.rows) rc = launch_stage_rows(d_rows, o.rows, B, s);
+    if (rc == GVC_OK && o.ras) rc = launch_stage_ras(d_ras, o.ras, o.n_sets, s);
     if (rc == GVC_OK) {
         SampleCall sc;
         memset(&sc, 0, sizeof(sc));
         sc.logits = logits; sc.B = B; sc.ids = ids; sc.ids_stride = ids_stride; sc.ids_len = ids_len;
         sc.finished = finished; sc.p = p; sc.step = step; sc.tok_out = tok_out; sc.rows = d_rows; sc.proc = d_proc;
         sc.proc_sets = d_sets; sc.set_of_row = o.index ? d_sor : nullptr; sc.warps = d_warps; sc.bias = d_bias;
+        sc.ras = d_ras; sc.ras_redraws = o.ras ? o.ras_redraws : nullptr;
         if (o.rows) sc.p.top_k = o.greedy ? 1 : 0;          // (kernel choice only: every row's settings come from d_rows)
         rc = launch_sample(sc, s);
     }
@@ -464,6 +496,25 @@ extern "C" int gvc_sample_bias(const float* logits, int32_t B, int32_t* ids, int
     if (any && (rc = gvc::check_warp_sets(sets, warps, n_sets, set_of_row, B, p->vocab))) return rc;
     gvc::SampleOptions o;
     o.rows = rows; o.sets = sets; o.warps = warps; o.n_sets = n_sets; o.set_of_row = set_of_row; o.bias = bias; o.index = any;
+    if (rows && (rc = gvc::check_sample_rows(rows, B, p->vocab, &o.greedy))) return rc;
+    return gvc::sample_once(logits, B, ids, ids_stride, ids_len, finished, *p, step, tok_out, o, (hipStream_t)sv);
+}
+
+extern "C" int gvc_sample_ras(const float* logits, int32_t B, int32_t* ids, int32_t ids_stride, int32_t* ids_len, int32_t* finished,
+                              const gvc_sample_params* p, const gvc_row_sampling* rows, const gvc_logits_processors* sets,
+                              const gvc_logits_warpers* warps, int32_t n_sets, const int32_t* set_of_row, const gvc_logits_bias* bias,
+                              const gvc_logits_ras* ras, int32_t* ras_redraws, int32_t step, int32_t* tok_out, gvc_stream sv) {
+    if (!ras) return gvc_sample_bias(logits, B, ids, ids_stride, ids_len, finished, p, rows, sets, warps, n_sets, set_of_row, bias, step, tok_out, sv);
+    GVC_REQUIRE(logits && ids && ids_len && finished && p && tok_out && B >= 1, GVC_ERR_ARG, "gvc_sample_ras: bad argument");
+    GVC_REQUIRE(B <= gvc::kMaxSampleRows, GVC_ERR_ARG, "gvc_sample_ras: need 1..%d rows, got %d", gvc::kMaxSampleRows, B);
+    int rc = gvc::check_ras(ras, n_sets);
+    if (rc) return rc;
+    if (bias && (rc = gvc::check_bias(*bias, p->vocab))) return rc;
+    // (check_warp_sets reads neither table when both are null: the bounds of n_sets and of the indices are what is left)
+    if ((rc = gvc::check_warp_sets(sets, warps, n_sets, set_of_row, B, p->vocab))) return rc;
+    gvc::SampleOptions o;
+    o.rows = rows; o.sets = sets; o.warps = warps; o.n_sets = n_sets; o.set_of_row = set_of_row; o.bias = bias; o.index = true;
+    o.ras = ras; o.ras_redraws = ras_redraws;
     if (rows && (rc = gvc::check_sample_rows(rows, B, p->vocab, &o.greedy))) return rc;
     return gvc::sample_once(logits, B, ids, ids_stride, ids_len, finished, *p, step, tok_out, o, (hipStream_t)sv);
 }

@@ -1,6 +1,7 @@
 """Thin Python owners of the libgenvc_hip contexts.  torch supplies device memory and the stream;
 all arithmetic runs in the HIP library."""
 import ctypes as C
+import math
 
 import torch
 
@@ -160,6 +161,55 @@ def logits_warpers(kw, sampling=True):
     return w
 
 
+# generation kwargs of repetition-aware sampling (include/genvc_hip.h: gvc_logits_ras): not HF's, the codec-LM decoders'
+RAS_KWARGS = ("ras_window", "ras_threshold")
+RAS_MAX_WINDOW = _lib.RAS_MAX_WINDOW
+RAS_DEFAULT_THRESHOLD = 0.1
+
+
+def ras_counts(kw):
+    """the RAS_KWARGS of one call -> (window K, min_count), or None when RAS is off (ras_window None or 0).
+    min_count = max(1, ceil(ras_threshold * K - 1e-9)): the device compares integers only.  ValueError: a window that is no integer
+    in 0..64 (a bool is none), a threshold outside (0, 1] or no number, a threshold without a window."""
+    K, tau = kw.get("ras_window"), kw.get("ras_threshold")
+    if K is not None and (isinstance(K, bool) or not isinstance(K, int)):
+        raise ValueError(f"ras_window must be an integer in 0..{RAS_MAX_WINDOW} (0 or None: off), not {K!r}")
+    if K is not None and not 0 <= K <= RAS_MAX_WINDOW:
+        raise ValueError(f"ras_window must be in 0..{RAS_MAX_WINDOW} (0 or None: off), not {K!r}")
+    if tau is not None and (isinstance(tau, bool) or not isinstance(tau, (int, float)) or not 0.0 < float(tau) <= 1.0):
+        raise ValueError(f"ras_threshold must be a number in (0, 1], not {tau!r}")
+    if not K:
+        if tau is not None:
+            raise ValueError(f"ras_threshold={tau!r} without ras_window: the threshold is a share of the window")
+        return None
+    tau = RAS_DEFAULT_THRESHOLD if tau is None else float(tau)
+    return int(K), max(1, math.ceil(tau * K - 1e-9))
+
+
+def logits_ras(kw, prompt_len):
+    """the RAS_KWARGS of one call -> a gvc_logits_ras, or None when RAS is off (the call then passes no table at all).
+    prompt_len: the prompt length of the rows (fake ids included), the one min_new_tokens counts from: only ids behind it are
+    generated tokens.  Malformed settings raise ValueError (ras_counts)."""
+    kc = ras_counts(kw)
+    if kc is None:
+        return None
+    r = _lib.LogitsRas()
+    r.window, r.min_count = kc
+    r.prompt_len = int(prompt_len)
+    return r
+
+
+class RasTable:
+    """the RAS entries of one call beside its sets (include/genvc_hip.h: gvc_gpt_generate_ras): `ras` holds one gvc_logits_ras per
+    entry of the call's ProcessorSets / WarperSets (window 0 where the entry has none), or one entry for every row of a call without
+    sets; `redraws` is the int32 [B] device counter of the rows (or None), which the caller zeroes."""
+
+    def __init__(self, entries, redraws=None):
+        self.n = len(entries)
+        self.ras = (_lib.LogitsRas * self.n)(*[_lib.LogitsRas() if r is None else r for r in entries])
+        self.redraws = redraws
+
+
 # HF generate kwargs of the call-wide sequence bias / bad words / forced EOS / renormalised scores (include/genvc_hip.h: gvc_logits_bias)
 BIAS_KWARGS = ("sequence_bias", "bad_words_ids", "forced_eos_token_id", "forced_bos_token_id", "renormalize_logits")
 BIAS_MAX_SEQS = _lib.BIAS_MAX_SEQS      # entries of sequence_bias and bad_words_ids together
@@ -264,15 +314,15 @@ def logits_bias(kw, prompt_len, max_new, vocab, eos):
 
 
 def check_proc_kwargs(kw, where):
-    """a per-row / per-group / per-job / per-session processor dict may hold PROC_KWARGS and WARP_KWARGS only: anything else raises
-    ValueError naming the key and `where` it came from"""
+    """a per-row / per-group / per-job / per-session processor dict may hold PROC_KWARGS, WARP_KWARGS and RAS_KWARGS only: anything else
+    raises ValueError naming the key and `where` it came from"""
     if kw is None:
         return
     if not isinstance(kw, dict):
         raise ValueError(f"{where}: processor kwargs must be a dict or None, not {type(kw).__name__}")
-    unknown = sorted(set(kw) - set(PROC_KWARGS) - set(WARP_KWARGS))
+    unknown = sorted(set(kw) - set(PROC_KWARGS) - set(WARP_KWARGS) - set(RAS_KWARGS))
     if unknown:
-        raise ValueError(f"{where}: {unknown[0]!r} is not a processor kwarg (allowed: {', '.join(PROC_KWARGS + WARP_KWARGS)})")
+        raise ValueError(f"{where}: {unknown[0]!r} is not a processor kwarg (allowed: {', '.join(PROC_KWARGS + WARP_KWARGS + RAS_KWARGS)})")
 
 
 def _kw_key(kw):
@@ -346,10 +396,12 @@ def logits_processor_sets(kws, prompt_len, vocab, sampling=True, prompt_lens=Non
 class WarperSets:
     """per-row processor sets with warpers (include/genvc_hip.h: gvc_gpt_generate_warp): n_sets entries, each a gvc_logits_processors
     (`sets` is None when no entry has one; an entry without one is the all-zero struct) paired with a gvc_logits_warpers, and
-    `set_of_row` (B int32 indices, -1 = neither), all host arrays.  `prompt_lens` keeps the caller's device tensor alive."""
+    `set_of_row` (B int32 indices, -1 = neither), all host arrays.  `prompt_lens` keeps the caller's device tensor alive.
+    `ras` (optional): a gvc_logits_ras or None per entry; with any set, `self.ras` is the call's RasTable (generate_call passes it on)."""
 
-    def __init__(self, procs, warps, set_of_row, prompt_lens=None):
+    def __init__(self, procs, warps, set_of_row, prompt_lens=None, ras=None):
         self.n_sets = len(warps)
+        self.ras = RasTable(list(ras)) if ras is not None and any(r is not None for r in ras) else None
         self.sets = None
         if any(p is not None for p in procs):
             self.sets = (_lib.LogitsProcessors * self.n_sets)(*[_lib.LogitsProcessors() if p is None else p for p in procs])
@@ -369,32 +421,38 @@ class WarperSets:
 
 
 def logits_sets(kws, prompt_len, vocab, sampling=True, prompt_lens=None):
-    """logits_processor_sets() whose per-row dicts may also hold WARP_KWARGS.  When no row has a warper on, this returns exactly what
-    logits_processor_sets() returns (a ProcessorSets or None); otherwise a WarperSets, rows with equal processors and warpers sharing
-    an entry.  Errors name the offending row."""
+    """logits_processor_sets() whose per-row dicts may also hold WARP_KWARGS and RAS_KWARGS.  When no row has a warper or RAS on, this
+    returns exactly what logits_processor_sets() returns (a ProcessorSets or None); otherwise a WarperSets, rows with equal processors,
+    warpers and RAS entries (window, count and prompt length) sharing an entry.  Errors name the offending row."""
     kws = list(kws)
     ps = logits_processor_sets(kws, prompt_len, vocab, sampling=sampling, prompt_lens=prompt_lens)      # (validates every row)
-    warps = []
+    plens = [prompt_len] * len(kws) if isinstance(prompt_len, int) else [int(x) for x in prompt_len]
+    warps, rass = [], []
     for b, kw in enumerate(kws):
         try:
             warps.append(logits_warpers(kw or {}, sampling))
+            rass.append(logits_ras(kw or {}, plens[b]))
         except ValueError as e:
             raise ValueError(f"row {b}: {e}") from None
-    if all(w is None for w in warps):
+    if all(w is None for w in warps) and all(r is None for r in rass):
         return ps
+    if prompt_lens is not None and any(r is not None for r in rass):
+        raise ValueError("ras_window counts a row's generated tokens from a host prompt length: pass prompt_len, not a device tensor")
     pidx = list(ps.set_of_row) if ps is not None else [-1] * len(kws)
-    by, procs, wl, index = {}, [], [], []
-    for b, w in enumerate(warps):
-        if pidx[b] < 0 and w is None:
+    by, procs, wl, rl, index = {}, [], [], [], []
+    for b, (w, r) in enumerate(zip(warps, rass)):
+        if pidx[b] < 0 and w is None and r is None:
             index.append(-1)
             continue
-        key = (pidx[b], None if w is None else C.string_at(C.addressof(w), C.sizeof(w)))
+        key = (pidx[b], None if w is None else C.string_at(C.addressof(w), C.sizeof(w)),
+               None if r is None else C.string_at(C.addressof(r), C.sizeof(r)))
         if key not in by:
             by[key] = len(wl)
             procs.append(ps.sets[pidx[b]] if pidx[b] >= 0 else None)
             wl.append(w)
+            rl.append(r)
         index.append(by[key])
-    return WarperSets(procs, wl, index, prompt_lens)
+    return WarperSets(procs, wl, index, prompt_lens, ras=rl)
 
 
 BEAM_LENGTH_MODES = {"4.33": 0, "generated": 1}
@@ -1136,18 +1194,55 @@ class GptEngine:
                               max_keys, rows, [None if bias is None else C.byref(bias)], sets=sets,
                               guided=(uncond_slots, scale), outputs=(scores_out, logits_out, do_sample))
 
+    def _ras_args(self, ras, sets, B):
+        """[ras table, redraw counters] of a RasTable beside `sets` over B rows"""
+        if ras.n != (1 if sets is None else sets.n_sets):
+            raise ValueError(f"{ras.n} RAS entries for {1 if sets is None else sets.n_sets} sets")
+        if ras.redraws is not None and tuple(ras.redraws.shape) != (B,):
+            raise ValueError(f"RAS redraw counters of shape {tuple(ras.redraws.shape)} for {B} rows")
+        return [ras.ras, None if ras.redraws is None else ptr(_i32(ras.redraws))]
+
+    def sample_ras(self, logits, ids, ids_len, finished, params, ras, step, sets=None, bias=None, rows=None):
+        """sample_bias() with repetition-aware sampling (a RasTable; include/genvc_hip.h: gvc_sample_ras): row b uses entry
+        sets.set_of_row[b] of the table (entry 0 without sets, none for -1).  Runs the full kernel whatever top_k is."""
+        B = logits.shape[0]
+        sa = self._sets_args(sets, B)
+        if sets is None:
+            sa[2] = 1
+        return self._sample("sample_ras", logits, ids, ids_len, finished, params, step, rows,
+                            sa + [None if bias is None else C.byref(bias)] + self._ras_args(ras, sets, B))
+
+    def generate_ras(self, slots, uncond_slots, scale, ids, ids_len, finished, params, sets, bias, ras, i0, n_steps, tokens_out,
+                     latents_out, scores_out=None, logits_out=None, do_sample=True, max_keys=0, rows=None):
+        """generate_bias() with repetition-aware sampling (a RasTable from logits_ras(); include/genvc_hip.h: gvc_gpt_generate_ras).
+        The table travels with the call in one staging launch; the step graphs are the sampling ones whatever top_k is
+        (warmup(top_k=0) prepares them), and nothing is allocated or captured once warm."""
+        B = slots.shape[0]
+        sa = self._sets_args(sets, B)
+        if sets is None:
+            sa[2] = 1
+        return self._generate("generate_ras", "generate_ras", slots, ids, ids_len, finished, params, i0, n_steps, tokens_out, latents_out,
+                              max_keys, rows, sa + [None if bias is None else C.byref(bias)] + self._ras_args(ras, sets, B),
+                              guided=(uncond_slots, scale), outputs=(scores_out, logits_out, do_sample))
+
     def generate_call(self, slots, ids, ids_len, finished, params, i0, n_steps, tokens_out, latents_out, max_keys=0, rows=None, proc=None,
-                      sets=None, bias=None, uncond_slots=None, scale=1.0, scores_out=None, logits_out=None, do_sample=True):
+                      sets=None, bias=None, uncond_slots=None, scale=1.0, scores_out=None, logits_out=None, do_sample=True, ras=None):
         """The generation call for whatever options a loop has, through the narrowest entry that carries them: generate_bias (bias),
         generate_scores (score / logit buffers), generate_cfg (uncond_slots), generate_proc_sets / generate_warp (sets), generate_rows
         (rows), else generate.  proc: the call-wide processors; sets (a ProcessorSets / WarperSets) supersedes it, and the entries
         without a `proc` argument take it as one call-wide entry.  A loop makes this one call instead of choosing.  It goes through
         the public methods, so a patched or overridden entry still sees its calls, and an engine stand-in that has no generate_call
         of its own (layers.gpt._generate_call) needs only the entries its options reach."""
-        wide = bias is not None or scores_out is not None or logits_out is not None or uncond_slots is not None
+        wide = bias is not None or scores_out is not None or logits_out is not None or uncond_slots is not None or ras is not None
         if wide and sets is None and proc is not None:
             sets = WarperSets.one(proc, None, slots.shape[0])
         pk = {} if proc is None or sets is not None else {"proc": proc}
+        if ras is None:
+            ras = getattr(sets, "ras", None)          # (per-row entries ride with the sets: logits_sets)
+        if ras is not None:          # (a RasTable: repetition-aware sampling, the widest entry)
+            return self.generate_ras(slots, uncond_slots, scale, ids, ids_len, finished, params, sets, bias, ras, i0, n_steps, tokens_out,
+                                     latents_out, scores_out=scores_out, logits_out=logits_out, do_sample=do_sample, max_keys=max_keys,
+                                     rows=rows)
         if bias is not None:
             return self.generate_bias(slots, uncond_slots, scale, ids, ids_len, finished, params, sets, bias, i0, n_steps, tokens_out,
                                       latents_out, scores_out=scores_out, logits_out=logits_out, do_sample=do_sample, max_keys=max_keys,

@@ -160,12 +160,17 @@ def synthesize_utt(genVC_mdl, src_wav, tgt_audio, seg_len=6.0, return_details=Fa
     more = {"token_logprobs": all_logprobs} if token_scores else {}
     if alignment:
         more["alignments"] = all_aligns
+    ras = return_details and gkw.get("ras_window")       # (details only: reading the counters waits for the segment)
+    if ras:
+        more["ras_redraws"] = []
     for src_seg in segments(src_wav, seg, min_len):
         feat = m.content_extractor.extract_content_features(src_seg)
         codes = m.content_dvae.get_codebook_indices(feat.transpose(1, 2))
         kw = _sampling_kwargs(m) if num_beams == 1 else dict(_sampling_kwargs(m), do_sample=False, num_beams=int(num_beams))
         res = m.gpt.generate(cond_latent, codes, output_attentions=False, **dict(kw, **gkw))
         gen = getattr(res, "sequences", res)[0]          # (a caller's own return_dict_in_generate in generate_kwargs: the tokens of the result)
+        if ras and m.gpt.last_ras_redraws is not None:
+            more["ras_redraws"].append(int(m.gpt.last_ras_redraws.sum()))
         keep = gen != m.gpt.stop_audio_token
         gen = gen[keep]                                                 # reference :68 (0-d collapse guarded)
         if gen.numel() == 0:
@@ -254,7 +259,8 @@ def synthesize_utt_chunked(genVC_mdl, src_wav, tgt_audio, seg_len=6.0, repass_la
 def synthesize_utt_streaming(genVC_mdl, src_wav, tgt_audio, seg_len=6.0, stream_chunk_size=8, verbose=True,
                              return_details=False, generate_kwargs=None):
     """streaming conversion (reference :135-217); the clock starts before the host->device copies (:148).  generate_kwargs: more
-    GPT.get_generator kwargs (the logits processors), merged into every segment's call.  sequence_bias / bad_words_ids /
+    GPT.get_generator kwargs (the logits processors, ras_window / ras_threshold), merged into every segment's call; with ras_window
+    the details carry "ras_redraws", the redraws of every segment.  sequence_bias / bad_words_ids /
     forced_eos_token_id / renormalize_logits and assistant_model raise NotImplementedError here (infer.py --streaming): synthesize_utt
     serves them"""
     from genvc_amd.layers.gpt import _no_assistant, _no_bias
@@ -264,6 +270,7 @@ def synthesize_utt_streaming(genVC_mdl, src_wav, tgt_audio, seg_len=6.0, stream_
     wav_gen_prev, wav_overlap = None, None
     total = src_wav.shape[-1]
     pred, chunks_lat, tokens = [], [], []
+    ras_redraws = []
     min_len = int(0.32 * m.content_sample_rate)
     begin = time.time()
     latency = None
@@ -319,6 +326,8 @@ def synthesize_utt_streaming(genVC_mdl, src_wav, tgt_audio, seg_len=6.0, stream_
                     latency = time.time() - begin
                     if verbose:
                         print(f"Latency: {latency:.3f}s")
+        if return_details and m.gpt.last_ras_redraws is not None and (generate_kwargs or {}).get("ras_window"):
+            ras_redraws.append(int(m.gpt.last_ras_redraws.sum()))
     if cond_latent is None and cond_future is not None:
         cond_future.result()          # no segment consumed the latents: still join the side stream (its scratch buffers are per context)
     torch.cuda.synchronize()
@@ -326,19 +335,26 @@ def synthesize_utt_streaming(genVC_mdl, src_wav, tgt_audio, seg_len=6.0, stream_
     if verbose:
         print(f"Real-time factor: {rtf:.3f}")
     if return_details or not pred:
-        return dict(wav=torch.cat(pred, -1) if pred else None, latents=chunks_lat, tokens=tokens, latency=latency, rtf=rtf)
+        more = {"ras_redraws": ras_redraws} if (generate_kwargs or {}).get("ras_window") else {}
+        return dict(wav=torch.cat(pred, -1) if pred else None, latents=chunks_lat, tokens=tokens, latency=latency, rtf=rtf, **more)
     return torch.cat(pred, dim=-1)
 
 
 @torch.inference_mode()
-def synthesize_streams_streaming(genVC_mdl, src_wavs, tgt_audios, seg_len=1.0, stream_chunk_size=8, return_details=True):
+def synthesize_streams_streaming(genVC_mdl, src_wavs, tgt_audios, seg_len=1.0, stream_chunk_size=8, return_details=True,
+                                 generate_kwargs=None):
     """BASELINE configs[3]: B concurrent streams stepped together.  Each stream is converted exactly as
     `synthesize_utt_streaming` converts it on its own (same segments, same per-stream EOS rule, same vocoder grouping and
     cross-fade); the streams only SHARE the launches: ContentVec / DVAE / prefill / vocoder run on the batch and one
     decode step serves every stream (the MFMA rows path from 5 streams up).
 
     src_wavs [B,T] (equal lengths), tgt_audios [B,Tr] or [1,Tr] (one reference for all).
+    generate_kwargs: more GPT.get_generator kwargs for every stream (the logits processors, ras_window / ras_threshold); with
+    ras_window the result carries "ras_redraws", per stream the redraws of its segments.
     Returns per-stream lists: wav [B] tensors, tokens, plus first-chunk latency and the batch RTF."""
+    from genvc_amd.layers.gpt import _no_assistant, _no_bias
+    _no_bias(generate_kwargs or {}, "the streaming (synthesize_streams_streaming) path")
+    _no_assistant(generate_kwargs or {}, "streaming (synthesize_streams_streaming)")
     m = genVC_mdl
     B, total = src_wavs.shape
     min_len = int(0.32 * m.content_sample_rate)
@@ -353,6 +369,7 @@ def synthesize_streams_streaming(genVC_mdl, src_wavs, tgt_audios, seg_len=1.0, s
     stop = m.gpt.stop_audio_token
     prev, overlap = [None] * B, [None] * B
     pred, tokens = [[] for _ in range(B)], [[] for _ in range(B)]
+    ras_redraws = [[] for _ in range(B)]
     cached = 0
     for src_seg in segments(src_wavs, seg, min_len):
         feat = m.content_extractor.extract_content_features(src_seg)
@@ -360,7 +377,7 @@ def synthesize_streams_streaming(genVC_mdl, src_wavs, tgt_audios, seg_len=1.0, s
         fake = m.gpt.compute_embeddings(cond_latent, codes)
         gen = m.gpt.get_generator(fake_inputs=fake, num_return_sequences=1, output_attentions=False,
                                   output_hidden_states=True, stream_group=max(stream_chunk_size, 1),
-                                  cached_cond_rows=cached, **_sampling_kwargs(m))
+                                  cached_cond_rows=cached, **dict(_sampling_kwargs(m), **(generate_kwargs or {})))
         cached = cond_latent.shape[1]
         alive = [True] * B                        # a stream stops with its own EOS step (latent included, :189-196)
         g_tok, g_lat = [], []
@@ -400,6 +417,10 @@ def synthesize_streams_streaming(genVC_mdl, src_wavs, tgt_audios, seg_len=1.0, s
                 if latency is None:
                     torch.cuda.synchronize()
                     latency = time.time() - begin
+        if m.gpt.last_ras_redraws is not None and (generate_kwargs or {}).get("ras_window"):
+            for b, c in enumerate(m.gpt.last_ras_redraws.cpu().tolist()):
+                ras_redraws[b].append(int(c))
     torch.cuda.synchronize()
     rtf = (time.time() - begin) / (total / m.content_sample_rate)
-    return dict(wav=[torch.cat(p, -1) if p else None for p in pred], tokens=tokens, latency=latency, rtf=rtf)
+    more = {"ras_redraws": ras_redraws} if (generate_kwargs or {}).get("ras_window") else {}
+    return dict(wav=[torch.cat(p, -1) if p else None for p in pred], tokens=tokens, latency=latency, rtf=rtf, **more)

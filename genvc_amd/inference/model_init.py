@@ -233,7 +233,7 @@ class GenVCModel(nn.Module):
 
     @torch.inference_mode()
     def warmup(self, seg_len=1.0, streams=1, ref_seconds=3.0, stream_chunk_size=8, top_k=None, max_new_tokens=None, num_beams=1,
-               contrastive_top_k=None, num_return_sequences=1, num_beam_groups=1, guidance=False):
+               contrastive_top_k=None, num_return_sequences=1, num_beam_groups=1, guidance=False, ras_window=None, ras_threshold=None):
         """Everything the FIRST conversion of this shape would otherwise pay inside its latency window (the reference leaves warm-up
         to the user: /root/reference/infer.py:27-30 runs a conversion first).  For `streams` concurrent streams of `seg_len`-second
         segments and a `ref_seconds` reference:
@@ -249,6 +249,9 @@ class GenVCModel(nn.Module):
         (GPT.generate(do_sample=True, num_return_sequences=N); the KV fan-out and the candidates' score need no warm-up).
         guidance=True: also the guided step graphs of `streams` items x 2 KV slots (GPT.generate(guidance_scale=s,
         negative_cond_latents=...)), for a negative prompt as long as the conditional one.
+        ras_window = K [, ras_threshold]: the calls will use repetition-aware sampling, which runs the full sampling kernel whatever
+        top_k is: with top_k == 1 the sampling step graphs of the same shapes are captured as well (with any other top_k they are the
+        ones already warmed), so a RAS call neither allocates nor captures.
         No token is generated and no KV slot is left occupied."""
         dev = self.device
         g = self.gpt
@@ -269,9 +272,12 @@ class GenVCModel(nn.Module):
         # the calls get_generator / _advance will make reach max_keys = n0 + grp ... n0 + max_new: the library warms every context class in
         # that range (its thresholds are its own: gvc_gpt_warmup_range)
         hi = min(n0 + max_new, eng.dims["max_seq"] - 1)
-        eng.warmup_range(streams, min(n0 + grp, hi), hi, top_k)
-        if int(num_return_sequences) > 1:
-            eng.warmup_range(streams * int(num_return_sequences), min(n0 + grp, hi), hi, top_k)
+        from genvc_amd.engine import ras_counts
+        ras = ras_counts(dict(ras_window=ras_window, ras_threshold=ras_threshold)) is not None
+        for k in [top_k] + ([0] if ras and top_k == 1 else []):          # (0: the graphs around the full sampling kernel)
+            eng.warmup_range(streams, min(n0 + grp, hi), hi, k)
+            if int(num_return_sequences) > 1:
+                eng.warmup_range(streams * int(num_return_sequences), min(n0 + grp, hi), hi, k)
         if int(num_beams) > 1 and int(num_beam_groups) > 1:
             eng.warmup_group_beam(streams, int(num_beams), int(num_beam_groups), hi)
         elif int(num_beams) > 1:
@@ -280,6 +286,8 @@ class GenVCModel(nn.Module):
             eng.warmup_contrastive(streams, int(contrastive_top_k), hi)
         if guidance:
             eng.warmup_cfg(streams, hi, top_k)
+            if ras and top_k == 1:
+                eng.warmup_cfg(streams, hi, 0)
         if self.hifigan is not None:
             lat = torch.zeros(streams, grp, g.model_dim, device=dev)
             for n in {grp, max(1, max_new % grp)}:

@@ -14,7 +14,8 @@ from torch.nn import functional as F
 
 from .._lib import GenvcHipError
 from ..engine import (MAX_ASSISTANT_TOKENS, MAX_LOOKUP_HISTORY, MAX_LOOKUP_NGRAM, MAX_VERIFY_ROWS, AssistedState, BEAM_LENGTH_MODES, beam_early_stopping, check_beam_groups, GroupBeamSearch, MAX_CONTRASTIVE_K, PROC_KWARGS, WARP_KWARGS, BeamSearch, ContrastiveSearch, GptEngine, WarperSets,
-                      check_proc_kwargs, logits_bias, logits_processors, logits_sets, logits_warpers, sample_params)
+                      RAS_KWARGS, RasTable, check_proc_kwargs, logits_bias, logits_processors, logits_ras, logits_sets, logits_warpers,
+                      ras_counts, sample_params)
 from .perceiver_encoder import PerceiverResampler
 
 
@@ -287,6 +288,26 @@ def _no_bias(kw, where):
                                   "num_return_sequences, guidance_scale), one call-wide set per call")
 
 
+def _ras_on(kw):
+    """the call asks for repetition-aware sampling (engine.RAS_KWARGS; ras_window None or 0 is off).  ValueError: malformed settings
+    (engine.ras_counts), and do_sample=False -- greedy search has no distribution to draw again from; "greedy with an escape" is
+    do_sample=True with top_k=1, whose redraw runs at the call's temperature"""
+    if ras_counts(kw) is None:
+        return False
+    if not kw.get("do_sample", True):
+        raise ValueError(f"ras_window={kw.get('ras_window')} with do_sample=False: greedy search has nothing to draw again from; pass "
+                         "do_sample=True with top_k=1 (the argmax, redrawn from the full distribution when it repeats)")
+    return True
+
+
+def _no_ras(kw, mode):
+    """the modes of GPT.generate that repetition-aware sampling does not serve raise, naming the combination (whatever do_sample is:
+    most of them are greedy modes)"""
+    if ras_counts(kw) is not None:
+        raise NotImplementedError(f"ras_window={kw.get('ras_window')} with {mode} is not implemented: repetition-aware sampling redraws "
+                                  "the token of a sampler step (greedy at top_k=1, sampling, num_return_sequences, guidance_scale)")
+
+
 ASSIST_KWARGS = ("assistant_model", "num_assistant_tokens", "num_assistant_tokens_schedule", "assistant_cond_latents",
                  "speculative_sampling")
 
@@ -418,7 +439,7 @@ def _per_item_procs(kw, item_kwargs, n, name, vocab):
     item_kwargs = list(item_kwargs)
     if len(item_kwargs) != n:
         raise ValueError(f"{name}: {len(item_kwargs)} processor dicts for {n} items")
-    base = {k: kw[k] for k in PROC_KWARGS + WARP_KWARGS if kw.get(k) is not None}
+    base = {k: kw[k] for k in PROC_KWARGS + WARP_KWARGS + RAS_KWARGS if kw.get(k) is not None}
     out = []
     for i, d in enumerate(item_kwargs):
         check_proc_kwargs(d, f"{name}[{i}]")
@@ -426,6 +447,7 @@ def _per_item_procs(kw, item_kwargs, n, name, vocab):
         try:
             logits_processors(m, 0, vocab)
             logits_warpers(m, sampling=kw.get("do_sample", True))
+            _ras_on(dict(m, do_sample=kw.get("do_sample", True)))
         except ValueError as e:
             raise ValueError(f"{name}[{i}]: {e}") from None
         out.append(m)
@@ -581,6 +603,7 @@ class GPT(nn.Module):
         self._prefix = None
         self.max_slots = 8
         self.recoveries = 0          # generations repeated after a hand-off time-out of a one-launch step (_recovering)
+        self.last_ras_redraws = None # int32 [rows] redraws of the last generate() / get_generator() that used ras_window, else None
 
     # ------------------------------------------------------------------------------------------
     def dims(self):
@@ -689,6 +712,11 @@ class GPT(nn.Module):
         st["warp"] = None if warp is None else WarperSets.one(st["proc"], warp, B)
         # sequence bias / bad words / forced EOS / renormalised scores (engine.BIAS_KWARGS): one call-wide struct, None when all are off
         st["bias"] = logits_bias(kw, n0, max_new, self.num_audio_tokens, self.stop_audio_token)
+        # repetition-aware sampling (engine.RAS_KWARGS): one call-wide entry counting from the fake ids, and the rows' redraw counters
+        st["ras"] = None
+        if _ras_on(kw):
+            st["ras"] = RasTable([logits_ras(kw, n0)], torch.zeros(B, device=dev, dtype=torch.int32))
+        self.last_ras_redraws = None if st["ras"] is None else st["ras"].redraws
         # `cached_cond_rows` (extension): the leading rows of the prefix -- the conditioning latents, identical for every
         # segment of an utterance -- are still in the KV cache from the previous segment's prefill of these slots
         if fan > 1:
@@ -711,7 +739,7 @@ class GPT(nn.Module):
                            st["lats"], max_keys=max(st["n0"], st.get("n0_uncond", 0)) + st["done"] + n, proc=st["proc"],
                            sets=st["warp"], bias=st.get("bias"), uncond_slots=st.get("uncond_slots"),
                            scale=st.get("guidance_scale", 1.0), scores_out=st.get("scores"), logits_out=st.get("raw_logits"),
-                           do_sample=st.get("do_sample", True))
+                           do_sample=st.get("do_sample", True), **({} if st.get("ras") is None else {"ras": st["ras"]}))
             st["done"] += n
         end = bool(st["finished"].all().item()) or st["done"] >= st["max_new"]
         self.engine.health()          # (the .item() above synchronised: a hand-off timeout of these steps surfaces here, not a call later)
@@ -739,6 +767,8 @@ class GPT(nn.Module):
                              sequences_scores=self.last_beam_scores if beams else None)
         if st and any(_trace_kwargs(kw)):
             out["attentions"], out["hidden_states"] = self._trace_steps(st, ids, kw)
+        if st and st.get("ras") is not None:          # (only in the result of a call that used RAS)
+            out["ras_redraws"] = st["ras"].redraws
         return out
 
     def _trace_ready(self, kw, rows):
@@ -862,6 +892,12 @@ class GPT(nn.Module):
         without it, bit for bit (no effect without output_scores).  forced_bos_token_id is accepted and does nothing: HF's processor
         fires at cur_len == 1, and no prompt of this model is that short.  Beams, beam groups and contrastive search raise
         NotImplementedError for them, as the grouped, rolling, session and streaming paths do.
+        ras_window = K (1..64) [, ras_threshold = t in (0, 1], default 0.1]: repetition-aware sampling (engine.logits_ras;
+        include/genvc_hip.h: gvc_logits_ras) on the same sampler paths: a step whose token fills max(1, ceil(t K)) of
+        the row's last K generated tokens draws again from the distribution ahead of top-k / top-p / the warpers.  top_k=1 with it is
+        greedy decoding with an escape; do_sample=False raises ValueError pointing there.  `last_ras_redraws` (and `ras_redraws` of a
+        GenerateOutput) count each row's redraws; scores and logits stay those of the first draw.  None or 0 is exactly the call
+        without it.  Beams, beam groups, contrastive search, assisted and prompt-lookup decoding raise NotImplementedError.
         assistant_model = another initialised GPT: assisted (speculative) greedy decoding (_generate_assisted), checked
         before every other mode; the tokens are those of the call without it.  None is exactly that call.  With
         speculative_sampling=True a sampled call is served too (speculative sampling: same distribution per token, other tokens than
@@ -872,7 +908,16 @@ class GPT(nn.Module):
         speculative_sampling=True.  With assistant_model, or max_matching_ngram_size alone: ValueError."""
         _num_return(generate_kwargs)
         if _lookup(generate_kwargs) or generate_kwargs.get("assistant_model") is not None:
+            _no_ras(generate_kwargs, _LOOKUP_MODE if _lookup(generate_kwargs) else "assisted decoding (assistant_model)")
             return self._generate_assisted(cond_latents, text_inputs, generate_kwargs)
+        if ras_counts(generate_kwargs) is not None:
+            if _contrastive_mode(generate_kwargs) is not None:
+                _no_ras(generate_kwargs, f"contrastive search (penalty_alpha={generate_kwargs.get('penalty_alpha')})")
+            if _grouped(generate_kwargs):
+                _no_ras(generate_kwargs, "beam groups (num_beam_groups / diversity_penalty)")
+            if int(generate_kwargs.get("num_beams", 1) or 1) > 1:
+                _no_ras(generate_kwargs, f"beam search (num_beams={generate_kwargs.get('num_beams')})")
+            _ras_on(generate_kwargs)          # (do_sample=False: ValueError)
         scale = _guidance_scale(generate_kwargs)
         if scale is not None:
             return self._generate_guided(cond_latents, text_inputs, scale, generate_kwargs)
@@ -1233,6 +1278,7 @@ class GPT(nn.Module):
         (gvc_gpt_generate_proc_sets, or gvc_gpt_generate_warp when a warper is on).
         Returns a list of int64 [B_i, n_i] (reference gpt.py:594-609 per group)."""
         _plain_rows_only(generate_kwargs, "grouped (generate_groups)")
+        _ras_on(generate_kwargs)          # (malformed ras_window / ras_threshold, or do_sample=False with them: ValueError)
         kw = dict(generate_kwargs)
         gkw = None
         if group_kwargs is not None:
@@ -1249,7 +1295,10 @@ class GPT(nn.Module):
             kw["max_new_tokens"] = max(budgets)
         else:
             budgets = None
-        greedy = kw.get("top_k", 0) == 1 or not kw.get("do_sample", True)
+        # (a call with RAS on anywhere draws -- the redraw's uniform is keyed by the group's seed -- so it takes the sampling schedule
+        # whatever its top_k: each group then gets what generate(seed=its class seed) returns for it)
+        ras_any = _ras_on(kw) or (gkw is not None and any(ras_counts(d) is not None for d in gkw))
+        greedy = (kw.get("top_k", 0) == 1 or not kw.get("do_sample", True)) and not ras_any
         total = sum(int(t.shape[0]) for _, t in groups)
         stats = getattr(self, "groups_stats", None)        # {"joint": n, "separate": n}: bench.py / tests count the two paths
         seeds = None
@@ -1290,8 +1339,8 @@ class GPT(nn.Module):
         groups = [groups[i] for i in order]
         seeds = [seeds[i] for i in order] if seeds is not None else None
         gkw = [gkw[i] for i in order] if gkw is not None else None
-        if gkw is None and seeds is not None and logits_warpers(kw) is not None:
-            # call-wide warpers: every group carries the call's processor and warper kwargs, one shared entry (logits_sets)
+        if gkw is None and seeds is not None and (logits_warpers(kw) is not None or ras_counts(kw) is not None):
+            # call-wide warpers / RAS: every group carries the call's processor, warper and RAS kwargs (logits_sets)
             gkw = _per_item_procs(kw, [None] * len(groups), len(groups), "generate_kwargs", self.num_audio_tokens)
         gb = [budgets[i] if budgets else max_new for i in order]
         prefixes = [self.engine.prefix_embeddings(c.to(torch.float32).contiguous(), t.to(torch.int32).contiguous()) for c, t in groups]
@@ -1372,6 +1421,7 @@ class GPT(nn.Module):
         the call-wide ones; job j then gets what generate(c_j, t_j, **its merged kwargs) returns (seed=job_seeds[j] when sampling), each
         row of a decode call carrying its job's set (gvc_gpt_generate_proc_sets, or gvc_gpt_generate_warp when a warper is on)."""
         _plain_rows_only(generate_kwargs, "rolling (generate_rolling)")
+        _ras_on(generate_kwargs)          # (malformed ras_window / ras_threshold, or do_sample=False with them: ValueError)
         kw = dict(generate_kwargs)
         jkw = None
         if job_kwargs is not None:
@@ -1381,7 +1431,8 @@ class GPT(nn.Module):
         kw.pop("class_seeds", None)
         job_seeds = kw.pop("job_seeds", None)
         max_rows = kw.pop("max_rows", None)      # streams in flight at most (default: every KV slot of the context)
-        greedy = kw.get("top_k", 0) == 1 or not kw.get("do_sample", True)
+        ras_any = _ras_on(kw) or (jkw is not None and any(ras_counts(d) is not None for d in jkw))
+        greedy = (kw.get("top_k", 0) == 1 or not kw.get("do_sample", True)) and not ras_any      # (RAS draws: it needs the jobs' seeds)
         if (not greedy and job_seeds is None) or kw.get("num_beams", 1) != 1:
             raise NotImplementedError("generate_rolling samples with one seed per job (job_seeds=...); without them it serves greedy "
                                       "decoding (top_k = 1) only")
@@ -1406,8 +1457,8 @@ class GPT(nn.Module):
 
     def _rolling(self, jobs, kw, budgets, group, n0s, width, S, seeds=None, jkw=None):
         dev = jobs[0][1].device
-        if jkw is None and seeds is not None and logits_warpers(kw) is not None:
-            # call-wide warpers: every job carries the call's processor and warper kwargs, one shared entry (logits_sets)
+        if jkw is None and seeds is not None and (logits_warpers(kw) is not None or ras_counts(kw) is not None):
+            # call-wide warpers / RAS: every job carries the call's processor, warper and RAS kwargs (logits_sets)
             jkw = _per_item_procs(kw, [None] * len(jobs), len(jobs), "generate_kwargs", self.num_audio_tokens)
         eng = self.engine
         stop = self.stop_audio_token
@@ -1513,6 +1564,7 @@ class GPT(nn.Module):
         the EOS step included.  Steps run in groups of `stream_group` (default 8, the vocoder chunk of
         inference_utils.py:195) with one host check of the finished flags per group."""
         _plain_rows_only(generate_kwargs, "streaming (get_generator)")
+        _ras_on(generate_kwargs)          # (malformed ras_window / ras_threshold, or do_sample=False with them: ValueError)
         self._need_engine()
         group = generate_kwargs.pop("stream_group", 8)
         B = int(fake_inputs.shape[0])

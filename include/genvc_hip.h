@@ -680,6 +680,50 @@ int gvc_gpt_generate_bias(gvc_gpt* ctx, const int32_t* slots, const int32_t* unc
                           int32_t n_sets, const int32_t* set_of_row, const gvc_logits_bias* bias, int32_t i0, int32_t n_steps,
                           int32_t max_keys, int32_t* tokens_out, int32_t tok_stride, float* latents_out, int32_t lat_stride,
                           float* scores_out, float* logits_out, int32_t out_stride, int32_t do_sample, gvc_stream s);
+/* ------------------------------------------------------------------------------------------
+ * Repetition-aware sampling (RAS; VALL-E 2, and the default decoder of CosyVoice with window 10 and ratio 0.1), on the full sampling
+ * kernel.  Per row and step, after the chain above has picked its token x exactly as without RAS:
+ *   n_gen = len - prompt_len (the fake prompt ids never count), w = min(window, n_gen), c = how many of the row's last w generated
+ *   ids equal x.  When c >= min_count, x is not the stop token, the row is not finished and its ids buffer is not full, x is thrown
+ *   away and drawn again from the row as the chain left it AHEAD OF TRUNCATION: every finite score behind the sequence bias, the
+ *   repetition penalty, the processors and Temperature (-inf entries -- suppressed ids, a banned EOS, bad words -- stay impossible),
+ *   with the arithmetic of the first draw: weights expf(s - max) in fp32 widened to double, running mass in double in vocabulary
+ *   order, first index whose mass reaches u2 * total, else the last finite index.  The redraw may return x again.
+ *   u2 = rng_uniform(seed ^ GVC_RAS_SALT, step, row) with the seed, step and row of the first draw (the row's own key when keyed).
+ * Otherwise x stands and the step is that of the call without RAS, bit for bit.  The caller turns a ratio into integers:
+ * min_count = max(1, ceil(ratio * window - 1e-9)); the device compares integers only.  top_k == 1 is served ("greedy with an
+ * escape"): x is the argmax and the redraw runs at the call's temperature; such a call runs on the full kernel, never on the argmax
+ * kernel.  Per-step scores and logits (gvc_gpt_generate_scores) are those of the first draw: RAS changes the token only.
+ * A null table, a -1 index or window == 0 computes exactly what the call without it computes.
+ * ------------------------------------------------------------------------------------------ */
+#define GVC_RAS_MAX_WINDOW 64
+#define GVC_RAS_SALT 0x5241535F52454452ull          /* "RAS_REDR" */
+typedef struct gvc_logits_ras {
+    int32_t window;                     /* 0 off, else 1..GVC_RAS_MAX_WINDOW */
+    int32_t min_count;                  /* >= 1 where the window is on */
+    int32_t prompt_len;                 /* prompt length of the rows of this entry (fake ids included), as gvc_logits_processors' */
+    int32_t reserved;                   /* 0 */
+} gvc_logits_ras;
+
+/* gvc_sample_ras: gvc_sample_bias with a RAS table; gvc_gpt_generate_ras: gvc_gpt_generate_bias with one.  ras (HOST, nullable: null
+ * is exactly the call without it): n_sets entries (1 <= n_sets <= B <= 64, as for sets and warps) indexed like warps -- row b uses ras[set_of_row[b]], none for
+ * -1, entry 0 for every row when set_of_row is null.  ras_redraws (DEVICE, nullable): int32 [B], the step that redraws row b adds 1
+ * to entry b; the caller zeroes it.  The table travels into the device-resident call state in one staging launch of its own (1 KB of
+ * kernel argument) ahead of the call's first launch, so nothing is allocated or synchronised per call; the step graphs are the
+ * sampling ones whatever top_k is (gvc_gpt_warmup with a top_k other than 1 prepares them).  GVC_ERR_ARG: a window outside
+ * [0, 64], min_count < 1 with the window on, prompt_len < 0, reserved != 0, n_sets outside [1, B].  Not on the beam, contrastive,
+ * assisted or lookup paths. */
+int gvc_sample_ras(const float* logits, int32_t B, int32_t* ids, int32_t ids_stride, int32_t* ids_len, int32_t* finished,
+                   const gvc_sample_params* p, const gvc_row_sampling* rows, const gvc_logits_processors* sets,
+                   const gvc_logits_warpers* warps, int32_t n_sets, const int32_t* set_of_row, const gvc_logits_bias* bias,
+                   const gvc_logits_ras* ras, int32_t* ras_redraws, int32_t step, int32_t* tok_out, gvc_stream s);
+int gvc_gpt_generate_ras(gvc_gpt* ctx, const int32_t* slots, const int32_t* uncond_slots, int32_t B, float scale, int32_t* ids,
+                         int32_t ids_stride, int32_t* ids_len, int32_t* finished, const gvc_sample_params* p,
+                         const gvc_row_sampling* rows, const gvc_logits_processors* sets, const gvc_logits_warpers* warps,
+                         int32_t n_sets, const int32_t* set_of_row, const gvc_logits_bias* bias, const gvc_logits_ras* ras,
+                         int32_t* ras_redraws, int32_t i0, int32_t n_steps, int32_t max_keys, int32_t* tokens_out, int32_t tok_stride,
+                         float* latents_out, int32_t lat_stride, float* scores_out, float* logits_out, int32_t out_stride,
+                         int32_t do_sample, gvc_stream s);
 /* gvc_gpt_warmup for gvc_gpt_generate_cfg over B items with this top_k: the guided step graphs of every context class up to max_keys
  * cached positions (and everything gvc_gpt_warmup(2B) prepares).  Afterwards such calls neither allocate nor synchronise */
 int gvc_gpt_warmup_cfg(gvc_gpt* ctx, int32_t B, int32_t max_keys, int32_t top_k);

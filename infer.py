@@ -52,6 +52,11 @@ if __name__ == "__main__":
     parser.add_argument("--typical_p", type=float, default=None, help="typical sampling mass in (0, 1] (1: off)")
     parser.add_argument("--epsilon_cutoff", type=float, default=None, help="epsilon sampling cut-off in [0, 1) (0: off)")
     parser.add_argument("--eta_cutoff", type=float, default=None, help="eta sampling cut-off in [0, 1) (0: off)")
+    parser.add_argument("--ras_window", type=int, default=None, metavar="K",
+                        help="repetition-aware sampling: a token that fills its share of the last K generated codes (1..64) is drawn again "
+                             "from the untruncated distribution; with --top_k 1 this is greedy decoding with an escape from loops")
+    parser.add_argument("--ras_threshold", type=float, default=None, metavar="T",
+                        help="with --ras_window: the share of the window in (0, 1] at which a token is drawn again (default 0.1)")
     parser.add_argument("--sequence_bias", action="append", default=None, metavar="IDS=VALUE",
                         help="non-streaming only, repeatable: add VALUE to the score of the last of the comma-separated codec ids when the "
                              "ids before it were just generated (HF sequence_bias), e.g. 1025=-2.0 makes every segment stop later")
@@ -162,6 +167,15 @@ if __name__ == "__main__":
     if args.penalty_alpha is not None:
         if args.streaming or not args.penalty_alpha > 0.0 or args.penalty_alpha == float("inf") or not 2 <= args.top_k <= 16:
             raise SystemExit("--penalty_alpha must be finite and > 0, non-streaming, with --top_k in [2, 16]")
+    if args.ras_threshold is not None and not args.ras_window:
+        raise SystemExit("--ras_threshold needs --ras_window")
+    if args.ras_window is not None:
+        if not 0 <= args.ras_window <= 64 or (args.ras_threshold is not None and not 0.0 < args.ras_threshold <= 1.0):
+            raise SystemExit("--ras_window must be in 0..64 (0: off) and --ras_threshold in (0, 1]")
+        if args.ras_window and (args.num_beams != 1 or args.num_beam_groups != 1 or args.penalty_alpha is not None
+                                or args.assistant_layers is not None or args.prompt_lookup_num_tokens is not None):
+            raise SystemExit("--ras_window does not combine with --num_beams, --num_beam_groups, --penalty_alpha, --assistant_layers or "
+                             "--prompt_lookup_num_tokens: it redraws the token of a sampler step")
     gen_kw = {k: v for k, v in (("min_new_tokens", args.min_new_tokens), ("no_repeat_ngram_size", args.no_repeat_ngram_size),
                                 ("min_p", args.min_p)) if v is not None}
     if args.eos_decay is not None:
@@ -177,6 +191,10 @@ if __name__ == "__main__":
         if not ((v > 0.0 if lo_open else v >= 0.0) and (v < 1.0 if hi_open else v <= 1.0)):
             raise SystemExit(f"bad warper flag: --{k} must be in {'(' if lo_open else '['}0, 1{')' if hi_open else ']'}, not {v}")
         gen_kw[k] = v
+    if args.ras_window:
+        gen_kw["ras_window"] = args.ras_window
+        if args.ras_threshold is not None:
+            gen_kw["ras_threshold"] = args.ras_threshold
     if args.num_beam_groups > 1:
         gen_kw.update(num_beam_groups=args.num_beam_groups, diversity_penalty=args.diversity_penalty)
     if args.sequence_bias or args.bad_words_ids or args.forced_eos:
@@ -286,6 +304,8 @@ if __name__ == "__main__":
                          **{f"argmax_{i}": a.argmax(1) for i, a in enumerate(al)}, **{f"mass_{i}": a.sum(1) for i, a in enumerate(al)})
                 print(f"{args.alignment}: alignment of {len(al)} segments, shapes {[a.shape for a in al]}")
         print(f"generated {toks.shape[-1]} codec tokens, latents {tuple(lat.shape)}")
+        if args.ras_window:
+            print(f"repetition-aware sampling (window {args.ras_window}): redraws per segment {out.get('ras_redraws', [])}")
         if args.decode_codes_to_mel is not None:
             import numpy as np
             dv = model.acoustic_dvae
