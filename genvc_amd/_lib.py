@@ -70,6 +70,15 @@ class LogitsRas(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("window", "min_count", "prompt_len", "reserved")]
 
 
+PENALTY_MAX = 2.0                    # GVC_PENALTY_MAX: |presence|, |frequency| <= 2
+
+
+class LogitsPenalties(C.Structure):
+    """gvc_logits_penalties (include/genvc_hip.h): presence / frequency / windowed repetition penalties of one set (16 bytes);
+    presence == frequency == 0 and window == 0: off"""
+    _fields_ = [("presence", C.c_float), ("frequency", C.c_float), ("window", C.c_int32), ("prompt_len", C.c_int32)]
+
+
 BIAS_MAX_SEQS = 32     # GVC_BIAS_MAX_SEQS
 BIAS_MAX_LEN = 8       # GVC_BIAS_MAX_LEN
 
@@ -266,6 +275,13 @@ _SIGNATURES = {
                                        C.POINTER(RowSampling), C.POINTER(LogitsProcessors), C.POINTER(LogitsWarpers), C.c_int32, c_i32p,
                                        C.POINTER(LogitsBias), C.POINTER(LogitsRas), _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32,
                                        _P, C.c_int32, _P, _P, C.c_int32, C.c_int32, _P]),
+    "gvc_sample_pen": (C.c_int, [_P, C.c_int32, _P, C.c_int32, _P, _P, C.POINTER(SampleParams), C.POINTER(RowSampling),
+                                 C.POINTER(LogitsProcessors), C.POINTER(LogitsWarpers), C.c_int32, c_i32p, C.POINTER(LogitsBias),
+                                 C.POINTER(LogitsRas), _P, C.POINTER(LogitsPenalties), C.c_int32, _P, _P]),
+    "gvc_gpt_generate_pen": (C.c_int, [_P, _P, _P, C.c_int32, C.c_float, _P, C.c_int32, _P, _P, C.POINTER(SampleParams),
+                                       C.POINTER(RowSampling), C.POINTER(LogitsProcessors), C.POINTER(LogitsWarpers), C.c_int32, c_i32p,
+                                       C.POINTER(LogitsBias), C.POINTER(LogitsRas), _P, C.POINTER(LogitsPenalties), C.c_int32, C.c_int32,
+                                       C.c_int32, _P, C.c_int32, _P, C.c_int32, _P, _P, C.c_int32, C.c_int32, _P]),
     "gvc_transition_scores": (C.c_int, [_P, C.c_int64, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "gvc_gpt_verify": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, _P, _P, _P]),
     "gvc_gpt_truncate": (C.c_int, [_P, _P, C.c_int32, _P, _P]),

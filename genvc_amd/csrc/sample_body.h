@@ -177,6 +177,7 @@ __device__ __forceinline__ void sample_row(const SampleCall& C, int b, const flo
     __shared__ float sc[kSortN];        // processed scores in vocabulary order
     __shared__ float srt[kSortN];       // descending sort of the scores
     __shared__ unsigned char seen[kSortN];
+    __shared__ int cnt[kSortN];         // counts of a gvc_logits_penalties row (touched only by such a row)
     __shared__ float red_v[16];
     __shared__ int red_i[16];
     __shared__ int s_tok, s_nk, s_pick, s_last;
@@ -200,7 +201,11 @@ __device__ __forceinline__ void sample_row(const SampleCall& C, int b, const flo
     const bool force = Z && Z->force_eos_at > 0 && len - Z->prompt_len == Z->force_eos_at - 1;
     const bool pr = P || Z;                   // a kill bitmap and a ProcStep exist
 
+    // presence / frequency / windowed repetition penalties of the row (uniform; off: `cnt` is neither cleared, added to nor read)
+    const PenRow Q = pen_row(C, b, len);
     for (int i = tid; i < kSortN; i += kSampThreads) seen[i] = 0;
+    if (Q.on)
+        for (int i = tid; i < kSortN; i += kSampThreads) cnt[i] = 0;
     ProcStep ps{false, 0.f, force};
     if (P) ps = proc_row_begin(*P, len, P->prompt_lens ? P->prompt_lens[b] : P->prompt_len, C.p.eos_token, kill, tid, force);
     else if (Z && tid < kProcWords) kill[tid] = 0u;
@@ -208,19 +213,25 @@ __device__ __forceinline__ void sample_row(const SampleCall& C, int b, const flo
     __syncthreads();
     for (int i = tid; i < len; i += kSampThreads) {
         const int id = ids[i];
-        if (id >= 0 && id < V) seen[id] = 1;
+        if (id >= 0 && id < V) {
+            seen[id] = 1;
+            if (i >= Q.lo) atomicAdd(&cnt[id], 1);          // (Q.lo == len without penalties; integer adds: any order, the same counts)
+        }
     }
     // (a forced EOS overrides the bans of the processors ahead of it in HF's list: n-gram and bad words)
     if (P && !force) proc_ngram(ids, len, P->no_repeat_ngram_size, V, kill, tid, kSampThreads);
     if (Z && !force) bias_bans(*Z, bh, V, kill, tid);
     const uint32_t hits = Z ? bh.hit & (uint32_t)((1ull << Z->n_bias) - 1ull) : 0u;
     __syncthreads();
-    // SequenceBias, RepetitionPenalty (every id of input_ids incl. the fake prefix, once), the processors, then Temperature
+    // SequenceBias, RepetitionPenalty (every id of input_ids incl. the fake prefix, once; the counted ids of a windowed row), the
+    // presence / frequency penalties, the processors, then Temperature
     for (int i = tid; i < kSortN; i += kSampThreads) {
         float v = -INFINITY;
         if (i < V) {
             v = bias_logit(lg[i], i, hits, bh);
-            if (seen[i]) v = v < 0.f ? v * rep_pen : v / rep_pen;
+            const int c = Q.on ? cnt[i] : 0;
+            if (Q.windowed ? c > 0 : seen[i]) v = v < 0.f ? v * rep_pen : v / rep_pen;
+            if (c > 0) v = pen_score(v, c, Q);
             if (pr) v = proc_score(v, i, C.p.eos_token, ps, kill);
             v = v / temp;
         }
@@ -260,7 +271,9 @@ __device__ __forceinline__ void sample_row(const SampleCall& C, int b, const flo
                 // greedy search has no Temperature: the row as it stood before the division above
                 for (int i = tid; i < V; i += kSampThreads) {
                     float v = bias_logit(lg[i], i, hits, bh);
-                    if (seen[i]) v = v < 0.f ? v * rep_pen : v / rep_pen;
+                    const int c = Q.on ? cnt[i] : 0;
+                    if (Q.windowed ? c > 0 : seen[i]) v = v < 0.f ? v * rep_pen : v / rep_pen;
+                    if (c > 0) v = pen_score(v, c, Q);
                     if (pr) v = proc_score(v, i, C.p.eos_token, ps, kill);
                     so[i] = v;
                 }

@@ -66,6 +66,10 @@ struct SampleCall {
     const gvc_logits_ras* ras;
     // nullable: [B] redraws of each row, incremented by the step that redraws (read only with ras)
     int32_t* ras_redraws;
+    // nullable: presence / frequency / windowed repetition penalties (gvc_*_pen calls: gvc_logits_penalties, device memory), one entry
+    // per set, indexed like warps and ras.  Null, or an entry with everything off: none, and both kernels compute exactly what they
+    // compute without this field, through the same barriers and with no more LDS traffic
+    const gvc_logits_penalties* pen;
 };
 
 // row b's entry of a per-step output buffer at this step (see SampleCall::scores_out)
@@ -92,6 +96,39 @@ __device__ __forceinline__ const gvc_logits_ras* row_ras(const SampleCall& C, in
     if (!C.ras) return nullptr;
     const int k = C.set_of_row ? C.set_of_row[b] : 0;
     return k >= 0 && C.ras[k].window > 0 ? C.ras + k : nullptr;
+}
+
+// the penalties of row b (uniform over the row's workgroup); null: off (no table, no entry, or an entry with everything off)
+__device__ __forceinline__ const gvc_logits_penalties* row_pen(const SampleCall& C, int b) {
+    if (!C.pen) return nullptr;
+    const int k = C.set_of_row ? C.set_of_row[b] : 0;
+    if (k < 0) return nullptr;
+    const gvc_logits_penalties& q = C.pen[k];
+    return q.presence != 0.f || q.frequency != 0.f || q.window > 0 ? C.pen + k : nullptr;
+}
+
+// What a row's penalties come to at one step: the span of ids that counts, and the settings in registers.  on == false: nothing below
+// is read and the kernels run as without a table
+struct PenRow {
+    bool on, windowed;          // windowed: the repetition penalty follows the counts instead of `seen`
+    int lo;                     // the counted ids are ids[lo .. len)
+    float presence, frequency;
+};
+__device__ __forceinline__ PenRow pen_row(const SampleCall& C, int b, int len) {
+    PenRow q{false, false, len, 0.f, 0.f};
+    if (const gvc_logits_penalties* Q = row_pen(C, b)) {
+        const int n_gen = len - min(max(Q->prompt_len, 0), len);          // the fake prompt ids never count
+        q.on = true;
+        q.windowed = Q->window > 0;
+        q.lo = len - (q.windowed ? min(Q->window, n_gen) : n_gen);
+        q.presence = Q->presence;
+        q.frequency = Q->frequency;
+    }
+    return q;
+}
+// score - (frequency * c + presence) for c > 0, each operation rounded on its own (include/genvc_hip.h: no fused multiply-add)
+__device__ __forceinline__ float pen_score(float v, int c, const PenRow& q) {
+    return __fsub_rn(v, __fadd_rn(__fmul_rn(q.frequency, (float)c), q.presence));
 }
 
 // a call with a RAS table runs on k_sample whatever its top_k: the redraw reads the full row the greedy kernel never stores
@@ -149,6 +186,15 @@ struct RasTable {
 int check_ras(const gvc_logits_ras* ras, int n_sets);
 // ras[0..n_sets) -> dst[0..n_sets) on stream s (one small launch)
 int launch_stage_ras(gvc_logits_ras* dst, const gvc_logits_ras* ras, int n_sets, hipStream_t s);
+// penalty entries of a gvc_*_pen call, all n_sets of them BY VALUE in one launch (1 KB of kernel argument)
+struct PenTable {
+    gvc_logits_penalties q[kMaxSampleRows];
+    int32_t n;
+};
+// host-side checks of a penalties table: 1 <= n_sets <= 64, presence and frequency finite in [-2, 2], window >= 0, prompt_len >= 0
+int check_pen(const gvc_logits_penalties* pen, int n_sets);
+// pen[0..n_sets) -> dst[0..n_sets) on stream s (one small launch)
+int launch_stage_pen(gvc_logits_penalties* dst, const gvc_logits_penalties* pen, int n_sets, hipStream_t s);
 // *bias -> *dst on stream s, BY VALUE in one small launch (1.3 KB of kernel argument); check_bias (logits_proc.h) comes first
 int launch_stage_bias(gvc_logits_bias* dst, const gvc_logits_bias* bias, hipStream_t s);
 

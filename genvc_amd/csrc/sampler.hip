@@ -17,6 +17,7 @@ __global__ __launch_bounds__(kSampThreads) void k_sample(SampleCall cv, const Sa
 constexpr int kGreedyThreads = 256;
 __global__ __launch_bounds__(kGreedyThreads) void k_sample_greedy(SampleCall cv, const SampleCall* cp) {
     __shared__ unsigned seen_w[kSortN / 4];          // one byte per vocabulary entry
+    __shared__ int cnt[kSortN];                      // counts of a gvc_logits_penalties row (touched only by such a row)
     __shared__ float red_v[kGreedyThreads / 64];
     __shared__ int red_i[kGreedyThreads / 64];
     __shared__ int s_tok;
@@ -40,6 +41,10 @@ __global__ __launch_bounds__(kGreedyThreads) void k_sample_greedy(SampleCall cv,
 #pragma unroll
     for (int u = 0; u < PER; ++u) { const int i = tid + u * kGreedyThreads; v[u] = i < V ? lg[i] : -INFINITY; }
     for (int i = tid; i < kSortN / 4; i += kGreedyThreads) seen_w[i] = 0u;
+    // presence / frequency / windowed repetition penalties of the row, as in k_sample (off: `cnt` is neither cleared, added to nor read)
+    const PenRow Q = pen_row(C, b, len);
+    if (Q.on)
+        for (int i = tid; i < kSortN; i += kGreedyThreads) cnt[i] = 0;
     const gvc_logits_processors* P = row_procs(C, b);
     // sequence bias / bad words / forced EOS of the call, as in k_sample
     const gvc_logits_bias* Z = C.bias;
@@ -52,7 +57,10 @@ __global__ __launch_bounds__(kGreedyThreads) void k_sample_greedy(SampleCall cv,
     __syncthreads();
     for (int i = tid; i < len; i += kGreedyThreads) {
         const int id = ids[i];
-        if (id >= 0 && id < V) seen[id] = 1;
+        if (id >= 0 && id < V) {
+            seen[id] = 1;
+            if (i >= Q.lo) atomicAdd(&cnt[id], 1);          // (Q.lo == len without penalties)
+        }
     }
     if (P && !force) proc_ngram(ids, len, P->no_repeat_ngram_size, V, kill, tid, kGreedyThreads);
     if (Z && !force) bias_bans(*Z, bh, V, kill, tid);
@@ -66,7 +74,9 @@ __global__ __launch_bounds__(kGreedyThreads) void k_sample_greedy(SampleCall cv,
         const int i = tid + u * kGreedyThreads;
         if (i < V) {
             float x = bias_logit(v[u], i, hits, bh);
-            if (seen[i]) x = x < 0.f ? x * rep_pen : x / rep_pen;
+            const int c = Q.on ? cnt[i] : 0;
+            if (Q.windowed ? c > 0 : seen[i]) x = x < 0.f ? x * rep_pen : x / rep_pen;
+            if (c > 0) x = pen_score(x, c, Q);
             if (pr) x = proc_score(x, i, C.p.eos_token, ps, kill);
             if (so) so[i] = x;                // greedy search: the processed row, no Temperature
             x = x / temp;
@@ -108,7 +118,9 @@ __global__ __launch_bounds__(kGreedyThreads) void k_sample_greedy(SampleCall cv,
             const int i = tid + u * kGreedyThreads;
             if (i < V) {
                 float x = bias_logit(v[u], i, hits, bh);
-                if (seen[i]) x = x < 0.f ? x * rep_pen : x / rep_pen;
+                const int c = Q.on ? cnt[i] : 0;
+                if (Q.windowed ? c > 0 : seen[i]) x = x < 0.f ? x * rep_pen : x / rep_pen;
+                if (c > 0) x = pen_score(x, c, Q);
                 if (pr) x = proc_score(x, i, C.p.eos_token, ps, kill);
                 x = x / temp;
                 sw[i] = x >= top ? x : -INFINITY;
@@ -154,6 +166,10 @@ __global__ void k_stage_warps(gvc_logits_warpers* dst, WarpTable t) {
 
 __global__ void k_stage_ras(gvc_logits_ras* dst, RasTable t) {
     if ((int)threadIdx.x < t.n) dst[threadIdx.x] = t.r[threadIdx.x];
+}
+
+__global__ void k_stage_pen(gvc_logits_penalties* dst, PenTable t) {
+    if ((int)threadIdx.x < t.n) dst[threadIdx.x] = t.q[threadIdx.x];
 }
 
 __global__ void k_stage_bias(gvc_logits_bias* dst, gvc_logits_bias src) {
@@ -339,6 +355,30 @@ int launch_stage_ras(gvc_logits_ras* dst, const gvc_logits_ras* ras, int n_sets,
     return GVC_OK;
 }
 
+int check_pen(const gvc_logits_penalties* pen, int n_sets) {
+    GVC_REQUIRE(pen && n_sets >= 1 && n_sets <= kMaxSampleRows, GVC_ERR_ARG, "penalties: need 1..%d entries, got %d", kMaxSampleRows,
+                n_sets);
+    for (int k = 0; k < n_sets; ++k) {
+        const gvc_logits_penalties& q = pen[k];
+        // (a NaN fails both comparisons of its pair)
+        GVC_REQUIRE(q.presence >= -GVC_PENALTY_MAX && q.presence <= GVC_PENALTY_MAX && q.frequency >= -GVC_PENALTY_MAX &&
+                        q.frequency <= GVC_PENALTY_MAX && q.window >= 0 && q.prompt_len >= 0,
+                    GVC_ERR_ARG, "penalties: entry %d has presence %g, frequency %g (each in [-2, 2]), window %d (>= 0), prompt_len %d (>= 0)",
+                    k, (double)q.presence, (double)q.frequency, q.window, q.prompt_len);
+    }
+    return GVC_OK;
+}
+
+int launch_stage_pen(gvc_logits_penalties* dst, const gvc_logits_penalties* pen, int n_sets, hipStream_t s) {
+    PenTable t;
+    memset(&t, 0, sizeof(t));
+    memcpy(t.q, pen, (size_t)n_sets * sizeof(gvc_logits_penalties));
+    t.n = n_sets;
+    hipLaunchKernelGGL(k_stage_pen, dim3(1), dim3(kMaxSampleRows), 0, s, dst, t);
+    GVC_LAUNCH_CHECK();
+    return GVC_OK;
+}
+
 int launch_sample(const SampleCall& sc, hipStream_t s) {
     GVC_REQUIRE(sc.p.vocab > 0 && sc.p.vocab <= kSortN, GVC_ERR_UNSUPPORTED, "sample: vocab %d > %d", sc.p.vocab, kSortN);
     if (!sc.ras && sample_greedy_ok(sc.p.top_k, sc.latents_out ? sc.d : 0)) hipLaunchKernelGGL(k_sample_greedy, dim3(sc.B), dim3(kGreedyThreads), 0, s, sc, (const SampleCall*)nullptr);
@@ -374,6 +414,7 @@ struct SampleOptions {
     bool index = false;          // stage set_of_row and hand it to the kernel (the entries that take sets or warpers)
     const gvc_logits_ras* ras = nullptr;          // n_sets RAS entries (gvc_sample_ras) ...
     int32_t* ras_redraws = nullptr;               // ... and the rows' redraw counters (device)
+    const gvc_logits_penalties* pen = nullptr;    // n_sets penalty entries (gvc_sample_pen)
 };
 
 static int sample_once(const float* logits, int B, int32_t* ids, int ids_stride, int32_t* ids_len, int32_t* finished,
@@ -387,8 +428,10 @@ static int sample_once(const float* logits, int B, int32_t* ids, int ids_stride,
     const size_t row_bytes = o.rows ? (size_t)B * sizeof(gvc_row_sampling) : 0;
     const size_t sor_bytes = (size_t)B * sizeof(int32_t);          // (always there: the allocation is never empty)
     const size_t ras_bytes = o.ras ? (size_t)o.n_sets * sizeof(gvc_logits_ras) : 0;
+    const size_t pen_bytes = o.pen ? (size_t)o.n_sets * sizeof(gvc_logits_penalties) : 0;
     char* d = nullptr;
-    GVC_CHECK_HIP(hipMallocAsync((void**)&d, bias_bytes + proc_bytes + set_bytes + warp_bytes + row_bytes + sor_bytes + ras_bytes, s));
+    GVC_CHECK_HIP(hipMallocAsync((void**)&d, bias_bytes + proc_bytes + set_bytes + warp_bytes + row_bytes + sor_bytes + ras_bytes + pen_bytes,
+                                 s));
     char* at = d;
     auto carve = [&at](size_t bytes) { char* q = bytes ? at : nullptr; at += bytes; return q; };
     gvc_logits_bias* d_bias = reinterpret_cast<gvc_logits_bias*>(carve(bias_bytes));
@@ -398,6 +441,7 @@ static int sample_once(const float* logits, int B, int32_t* ids, int ids_stride,
     gvc_row_sampling* d_rows = reinterpret_cast<gvc_row_sampling*>(carve(row_bytes));
     int32_t* d_sor = reinterpret_cast<int32_t*>(carve(sor_bytes));
     gvc_logits_ras* d_ras = reinterpret_cast<gvc_logits_ras*>(carve(ras_bytes));
+    gvc_logits_penalties* d_pen = reinterpret_cast<gvc_logits_penalties*>(carve(pen_bytes));
     int rc = GVC_OK;
     if (o.bias) rc = launch_stage_bias(d_bias, o.bias, s);
     if (rc == GVC_OK && o.proc) rc = launch_stage_proc(d_proc, o.proc, s);
@@ -406,6 +450,7 @@ static int sample_once(const float* logits, int B, int32_t* ids, int ids_stride,
     if (rc == GVC_OK && o.index) rc = launch_stage_set_index(d_sor, sor, B, s);
     if (rc == GVC_OK && o.rows) rc = launch_stage_rows(d_rows, o.rows, B, s);
     if (rc == GVC_OK && o.ras) rc = launch_stage_ras(d_ras, o.ras, o.n_sets, s);
+    if (rc == GVC_OK && o.pen) rc = launch_stage_pen(d_pen, o.pen, o.n_sets, s);
     if (rc == GVC_OK) {
         SampleCall sc;
         memset(&sc, 0, sizeof(sc));
@@ -413,6 +458,7 @@ static int sample_once(const float* logits, int B, int32_t* ids, int ids_stride,
         sc.finished = finished; sc.p = p; sc.step = step; sc.tok_out = tok_out; sc.rows = d_rows; sc.proc = d_proc;
         sc.proc_sets = d_sets; sc.set_of_row = o.index ? d_sor : nullptr; sc.warps = d_warps; sc.bias = d_bias;
         sc.ras = d_ras; sc.ras_redraws = o.ras ? o.ras_redraws : nullptr;
+        sc.pen = d_pen;
         if (o.rows) sc.p.top_k = o.greedy ? 1 : 0;          // (kernel choice only: every row's settings come from d_rows)
         rc = launch_sample(sc, s);
     }
@@ -515,6 +561,27 @@ extern "C" int gvc_sample_ras(const float* logits, int32_t B, int32_t* ids, int3
     gvc::SampleOptions o;
     o.rows = rows; o.sets = sets; o.warps = warps; o.n_sets = n_sets; o.set_of_row = set_of_row; o.bias = bias; o.index = true;
     o.ras = ras; o.ras_redraws = ras_redraws;
+    if (rows && (rc = gvc::check_sample_rows(rows, B, p->vocab, &o.greedy))) return rc;
+    return gvc::sample_once(logits, B, ids, ids_stride, ids_len, finished, *p, step, tok_out, o, (hipStream_t)sv);
+}
+
+extern "C" int gvc_sample_pen(const float* logits, int32_t B, int32_t* ids, int32_t ids_stride, int32_t* ids_len, int32_t* finished,
+                              const gvc_sample_params* p, const gvc_row_sampling* rows, const gvc_logits_processors* sets,
+                              const gvc_logits_warpers* warps, int32_t n_sets, const int32_t* set_of_row, const gvc_logits_bias* bias,
+                              const gvc_logits_ras* ras, int32_t* ras_redraws, const gvc_logits_penalties* pen, int32_t step,
+                              int32_t* tok_out, gvc_stream sv) {
+    if (!pen) return gvc_sample_ras(logits, B, ids, ids_stride, ids_len, finished, p, rows, sets, warps, n_sets, set_of_row, bias, ras, ras_redraws, step, tok_out, sv);
+    GVC_REQUIRE(logits && ids && ids_len && finished && p && tok_out && B >= 1, GVC_ERR_ARG, "gvc_sample_pen: bad argument");
+    GVC_REQUIRE(B <= gvc::kMaxSampleRows, GVC_ERR_ARG, "gvc_sample_pen: need 1..%d rows, got %d", gvc::kMaxSampleRows, B);
+    int rc = gvc::check_pen(pen, n_sets);
+    if (rc) return rc;
+    if (ras && (rc = gvc::check_ras(ras, n_sets))) return rc;
+    if (bias && (rc = gvc::check_bias(*bias, p->vocab))) return rc;
+    // (check_warp_sets reads neither table when both are null: the bounds of n_sets and of the indices are what is left)
+    if ((rc = gvc::check_warp_sets(sets, warps, n_sets, set_of_row, B, p->vocab))) return rc;
+    gvc::SampleOptions o;
+    o.rows = rows; o.sets = sets; o.warps = warps; o.n_sets = n_sets; o.set_of_row = set_of_row; o.bias = bias; o.index = true;
+    o.ras = ras; o.ras_redraws = ras_redraws; o.pen = pen;
     if (rows && (rc = gvc::check_sample_rows(rows, B, p->vocab, &o.greedy))) return rc;
     return gvc::sample_once(logits, B, ids, ids_stride, ids_len, finished, *p, step, tok_out, o, (hipStream_t)sv);
 }

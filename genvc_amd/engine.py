@@ -210,6 +210,55 @@ class RasTable:
         self.redraws = redraws
 
 
+# generation kwargs of the presence / frequency / windowed repetition penalties (include/genvc_hip.h: gvc_logits_penalties; DESIGN.md
+# 4.29): the OpenAI / vLLM definition of the first two, and a window of recent generated tokens for all three penalties
+PENALTY_KWARGS = ("presence_penalty", "frequency_penalty", "penalty_window")
+PENALTY_MAX = _lib.PENALTY_MAX
+
+
+def penalty_settings(kw):
+    """the PENALTY_KWARGS of one call -> (presence, frequency, window), or None when all are off (each None or 0).
+    ValueError: a presence / frequency that is no finite number in [-2, 2] (a bool is none), a window that is no integer >= 0."""
+    vals = []
+    for k in PENALTY_KWARGS[:2]:
+        v = kw.get(k)
+        if v is None:
+            vals.append(0.0)
+            continue
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or not -PENALTY_MAX <= v <= PENALTY_MAX:
+            raise ValueError(f"{k} must be a finite number in [-{PENALTY_MAX:g}, {PENALTY_MAX:g}] (0 or None: off), not {v!r}")
+        vals.append(float(v))
+    W = kw.get("penalty_window")
+    if W is not None and (isinstance(W, bool) or not isinstance(W, int) or W < 0 or W > 0x7fffffff):
+        raise ValueError(f"penalty_window must be an integer >= 0 (0 or None: every generated token), not {W!r}")
+    W = int(W or 0)
+    if vals[0] == 0.0 and vals[1] == 0.0 and W == 0:
+        return None
+    return vals[0], vals[1], W
+
+
+def logits_penalties(kw, prompt_len):
+    """the PENALTY_KWARGS of one call -> a gvc_logits_penalties, or None when they are off (the call then passes no table at all).
+    prompt_len: the prompt length of the rows (fake ids included): only ids behind it are generated tokens.  Malformed settings raise
+    ValueError (penalty_settings)."""
+    pfw = penalty_settings(kw)
+    if pfw is None:
+        return None
+    q = _lib.LogitsPenalties()
+    q.presence, q.frequency, q.window = pfw
+    q.prompt_len = int(prompt_len)
+    return q
+
+
+class PenaltyTable:
+    """the penalty entries of one call beside its sets (include/genvc_hip.h: gvc_gpt_generate_pen): one gvc_logits_penalties per entry
+    of the call's ProcessorSets / WarperSets (all-zero where the entry has none), or one entry for every row of a call without sets"""
+
+    def __init__(self, entries):
+        self.n = len(entries)
+        self.pen = (_lib.LogitsPenalties * self.n)(*[_lib.LogitsPenalties() if q is None else q for q in entries])
+
+
 # HF generate kwargs of the call-wide sequence bias / bad words / forced EOS / renormalised scores (include/genvc_hip.h: gvc_logits_bias)
 BIAS_KWARGS = ("sequence_bias", "bad_words_ids", "forced_eos_token_id", "forced_bos_token_id", "renormalize_logits")
 BIAS_MAX_SEQS = _lib.BIAS_MAX_SEQS      # entries of sequence_bias and bad_words_ids together
@@ -314,15 +363,16 @@ def logits_bias(kw, prompt_len, max_new, vocab, eos):
 
 
 def check_proc_kwargs(kw, where):
-    """a per-row / per-group / per-job / per-session processor dict may hold PROC_KWARGS, WARP_KWARGS and RAS_KWARGS only: anything else
-    raises ValueError naming the key and `where` it came from"""
+    """a per-row / per-group / per-job / per-session processor dict may hold PROC_KWARGS, WARP_KWARGS, RAS_KWARGS and PENALTY_KWARGS
+    only: anything else raises ValueError naming the key and `where` it came from"""
     if kw is None:
         return
     if not isinstance(kw, dict):
         raise ValueError(f"{where}: processor kwargs must be a dict or None, not {type(kw).__name__}")
-    unknown = sorted(set(kw) - set(PROC_KWARGS) - set(WARP_KWARGS) - set(RAS_KWARGS))
+    allowed = PROC_KWARGS + WARP_KWARGS + RAS_KWARGS + PENALTY_KWARGS
+    unknown = sorted(set(kw) - set(allowed))
     if unknown:
-        raise ValueError(f"{where}: {unknown[0]!r} is not a processor kwarg (allowed: {', '.join(PROC_KWARGS + WARP_KWARGS + RAS_KWARGS)})")
+        raise ValueError(f"{where}: {unknown[0]!r} is not a processor kwarg (allowed: {', '.join(allowed)})")
 
 
 def _kw_key(kw):
@@ -397,10 +447,12 @@ class WarperSets:
     """per-row processor sets with warpers (include/genvc_hip.h: gvc_gpt_generate_warp): n_sets entries, each a gvc_logits_processors
     (`sets` is None when no entry has one; an entry without one is the all-zero struct) paired with a gvc_logits_warpers, and
     `set_of_row` (B int32 indices, -1 = neither), all host arrays.  `prompt_lens` keeps the caller's device tensor alive.
-    `ras` (optional): a gvc_logits_ras or None per entry; with any set, `self.ras` is the call's RasTable (generate_call passes it on)."""
+    `ras` (optional): a gvc_logits_ras or None per entry; with any set, `self.ras` is the call's RasTable (generate_call passes it on).
+    `pen` (optional): a gvc_logits_penalties or None per entry; with any set, `self.pen` is the call's PenaltyTable likewise."""
 
-    def __init__(self, procs, warps, set_of_row, prompt_lens=None, ras=None):
+    def __init__(self, procs, warps, set_of_row, prompt_lens=None, ras=None, pen=None):
         self.n_sets = len(warps)
+        self.pen = PenaltyTable(list(pen)) if pen is not None and any(q is not None for q in pen) else None
         self.ras = RasTable(list(ras)) if ras is not None and any(r is not None for r in ras) else None
         self.sets = None
         if any(p is not None for p in procs):
@@ -421,38 +473,46 @@ class WarperSets:
 
 
 def logits_sets(kws, prompt_len, vocab, sampling=True, prompt_lens=None):
-    """logits_processor_sets() whose per-row dicts may also hold WARP_KWARGS and RAS_KWARGS.  When no row has a warper or RAS on, this
-    returns exactly what logits_processor_sets() returns (a ProcessorSets or None); otherwise a WarperSets, rows with equal processors,
-    warpers and RAS entries (window, count and prompt length) sharing an entry.  Errors name the offending row."""
+    """logits_processor_sets() whose per-row dicts may also hold WARP_KWARGS, RAS_KWARGS and PENALTY_KWARGS.  When no row has a warper,
+    RAS or a penalty on, this returns exactly what logits_processor_sets() returns (a ProcessorSets or None); otherwise a WarperSets,
+    rows with equal processors, warpers, RAS and penalty entries (settings and prompt length) sharing an entry.  Errors name the
+    offending row."""
     kws = list(kws)
     ps = logits_processor_sets(kws, prompt_len, vocab, sampling=sampling, prompt_lens=prompt_lens)      # (validates every row)
     plens = [prompt_len] * len(kws) if isinstance(prompt_len, int) else [int(x) for x in prompt_len]
-    warps, rass = [], []
+    warps, rass, pens = [], [], []
     for b, kw in enumerate(kws):
         try:
             warps.append(logits_warpers(kw or {}, sampling))
             rass.append(logits_ras(kw or {}, plens[b]))
+            pens.append(logits_penalties(kw or {}, plens[b]))
         except ValueError as e:
             raise ValueError(f"row {b}: {e}") from None
-    if all(w is None for w in warps) and all(r is None for r in rass):
+    if all(w is None for w in warps) and all(r is None for r in rass) and all(q is None for q in pens):
         return ps
     if prompt_lens is not None and any(r is not None for r in rass):
         raise ValueError("ras_window counts a row's generated tokens from a host prompt length: pass prompt_len, not a device tensor")
+    if prompt_lens is not None and any(q is not None for q in pens):
+        raise ValueError("the presence / frequency / windowed penalties count a row's generated tokens from a host prompt length: pass "
+                         "prompt_len, not a device tensor")
     pidx = list(ps.set_of_row) if ps is not None else [-1] * len(kws)
-    by, procs, wl, rl, index = {}, [], [], [], []
-    for b, (w, r) in enumerate(zip(warps, rass)):
-        if pidx[b] < 0 and w is None and r is None:
+    by, procs, wl, rl, ql, index = {}, [], [], [], [], []
+
+    def raw(x):
+        return None if x is None else C.string_at(C.addressof(x), C.sizeof(x))
+    for b, (w, r, q) in enumerate(zip(warps, rass, pens)):
+        if pidx[b] < 0 and w is None and r is None and q is None:
             index.append(-1)
             continue
-        key = (pidx[b], None if w is None else C.string_at(C.addressof(w), C.sizeof(w)),
-               None if r is None else C.string_at(C.addressof(r), C.sizeof(r)))
+        key = (pidx[b], raw(w), raw(r), raw(q))
         if key not in by:
             by[key] = len(wl)
             procs.append(ps.sets[pidx[b]] if pidx[b] >= 0 else None)
             wl.append(w)
             rl.append(r)
+            ql.append(q)
         index.append(by[key])
-    return WarperSets(procs, wl, index, prompt_lens, ras=rl)
+    return WarperSets(procs, wl, index, prompt_lens, ras=rl, pen=ql)
 
 
 BEAM_LENGTH_MODES = {"4.33": 0, "generated": 1}
@@ -1225,21 +1285,61 @@ class GptEngine:
                               max_keys, rows, sa + [None if bias is None else C.byref(bias)] + self._ras_args(ras, sets, B),
                               guided=(uncond_slots, scale), outputs=(scores_out, logits_out, do_sample))
 
+    def _pen_args(self, pen, sets):
+        """[penalties table] of a PenaltyTable beside `sets`"""
+        if pen.n != (1 if sets is None else sets.n_sets):
+            raise ValueError(f"{pen.n} penalty entries for {1 if sets is None else sets.n_sets} sets")
+        return [pen.pen]
+
+    def sample_pen(self, logits, ids, ids_len, finished, params, pen, step, sets=None, bias=None, ras=None, rows=None):
+        """sample_ras() (ras None: sample_bias()) with the presence / frequency / windowed repetition penalties of a PenaltyTable
+        (include/genvc_hip.h: gvc_sample_pen): row b uses entry sets.set_of_row[b] of the table (entry 0 without sets, none for -1).
+        The kernel is the one the call runs without the table."""
+        B = logits.shape[0]
+        sa = self._sets_args(sets, B)
+        if sets is None:
+            sa[2] = 1
+        return self._sample("sample_pen", logits, ids, ids_len, finished, params, step, rows,
+                            sa + [None if bias is None else C.byref(bias)] + ([None, None] if ras is None else self._ras_args(ras, sets, B))
+                            + self._pen_args(pen, sets))
+
+    def generate_pen(self, slots, uncond_slots, scale, ids, ids_len, finished, params, sets, bias, ras, pen, i0, n_steps, tokens_out,
+                     latents_out, scores_out=None, logits_out=None, do_sample=True, max_keys=0, rows=None):
+        """generate_ras() (ras None: generate_bias()) with a PenaltyTable from logits_penalties() (include/genvc_hip.h:
+        gvc_gpt_generate_pen).  The table travels with the call in one staging launch; the step graphs are those of the call without
+        it, and nothing is allocated or captured once warm."""
+        B = slots.shape[0]
+        sa = self._sets_args(sets, B)
+        if sets is None:
+            sa[2] = 1
+        return self._generate("generate_pen", "generate_pen", slots, ids, ids_len, finished, params, i0, n_steps, tokens_out, latents_out,
+                              max_keys, rows, sa + [None if bias is None else C.byref(bias)]
+                              + ([None, None] if ras is None else self._ras_args(ras, sets, B)) + self._pen_args(pen, sets),
+                              guided=(uncond_slots, scale), outputs=(scores_out, logits_out, do_sample))
+
     def generate_call(self, slots, ids, ids_len, finished, params, i0, n_steps, tokens_out, latents_out, max_keys=0, rows=None, proc=None,
-                      sets=None, bias=None, uncond_slots=None, scale=1.0, scores_out=None, logits_out=None, do_sample=True, ras=None):
+                      sets=None, bias=None, uncond_slots=None, scale=1.0, scores_out=None, logits_out=None, do_sample=True, ras=None,
+                      pen=None):
         """The generation call for whatever options a loop has, through the narrowest entry that carries them: generate_bias (bias),
         generate_scores (score / logit buffers), generate_cfg (uncond_slots), generate_proc_sets / generate_warp (sets), generate_rows
         (rows), else generate.  proc: the call-wide processors; sets (a ProcessorSets / WarperSets) supersedes it, and the entries
         without a `proc` argument take it as one call-wide entry.  A loop makes this one call instead of choosing.  It goes through
         the public methods, so a patched or overridden entry still sees its calls, and an engine stand-in that has no generate_call
         of its own (layers.gpt._generate_call) needs only the entries its options reach."""
-        wide = bias is not None or scores_out is not None or logits_out is not None or uncond_slots is not None or ras is not None
+        wide = (bias is not None or scores_out is not None or logits_out is not None or uncond_slots is not None or ras is not None
+                or pen is not None)
         if wide and sets is None and proc is not None:
             sets = WarperSets.one(proc, None, slots.shape[0])
         pk = {} if proc is None or sets is not None else {"proc": proc}
         if ras is None:
             ras = getattr(sets, "ras", None)          # (per-row entries ride with the sets: logits_sets)
-        if ras is not None:          # (a RasTable: repetition-aware sampling, the widest entry)
+        if pen is None:
+            pen = getattr(sets, "pen", None)
+        if pen is not None:          # (a PenaltyTable: presence / frequency / windowed penalties, the widest entry)
+            return self.generate_pen(slots, uncond_slots, scale, ids, ids_len, finished, params, sets, bias, ras, pen, i0, n_steps,
+                                     tokens_out, latents_out, scores_out=scores_out, logits_out=logits_out, do_sample=do_sample,
+                                     max_keys=max_keys, rows=rows)
+        if ras is not None:          # (a RasTable: repetition-aware sampling)
             return self.generate_ras(slots, uncond_slots, scale, ids, ids_len, finished, params, sets, bias, ras, i0, n_steps, tokens_out,
                                      latents_out, scores_out=scores_out, logits_out=logits_out, do_sample=do_sample, max_keys=max_keys,
                                      rows=rows)

@@ -112,7 +112,8 @@ def synthesize_utt(genVC_mdl, src_wav, tgt_audio, seg_len=6.0, return_details=Fa
     """non-streaming conversion, latent-level concatenation (reference :23-89).  num_beams = K > 1: every segment decodes with
     deterministic beam search (GPT.generate(num_beams=K, do_sample=False)); its latents come from the re-pass.
     generate_kwargs: more GPT.generate kwargs (the logits processors: min_new_tokens, no_repeat_ngram_size, ...; the
-    sampling warpers typical_p, epsilon_cutoff, eta_cutoff), merged into every segment's call.
+    sampling warpers typical_p, epsilon_cutoff, eta_cutoff; ras_window / ras_threshold; presence_penalty, frequency_penalty,
+    penalty_window), merged into every segment's call (synthesize_utt_chunked passes them on likewise).
     num_return_sequences = N > 1 (the keyword, or in generate_kwargs): a LIST of N results, candidate j of the utterance being the
     concatenation of candidate j of every segment (GPT.generate(num_return_sequences=N) per segment: one prefill, N rows); with
     return_details each dict also carries "score", the sum over the segments of the candidate's score (sampling: sequence_logprobs,
@@ -259,7 +260,8 @@ def synthesize_utt_chunked(genVC_mdl, src_wav, tgt_audio, seg_len=6.0, repass_la
 def synthesize_utt_streaming(genVC_mdl, src_wav, tgt_audio, seg_len=6.0, stream_chunk_size=8, verbose=True,
                              return_details=False, generate_kwargs=None):
     """streaming conversion (reference :135-217); the clock starts before the host->device copies (:148).  generate_kwargs: more
-    GPT.get_generator kwargs (the logits processors, ras_window / ras_threshold), merged into every segment's call; with ras_window
+    GPT.get_generator kwargs (the logits processors, ras_window / ras_threshold, presence_penalty / frequency_penalty /
+    penalty_window), merged into every segment's call; with ras_window
     the details carry "ras_redraws", the redraws of every segment.  sequence_bias / bad_words_ids /
     forced_eos_token_id / renormalize_logits and assistant_model raise NotImplementedError here (infer.py --streaming): synthesize_utt
     serves them"""
@@ -349,7 +351,8 @@ def synthesize_streams_streaming(genVC_mdl, src_wavs, tgt_audios, seg_len=1.0, s
     decode step serves every stream (the MFMA rows path from 5 streams up).
 
     src_wavs [B,T] (equal lengths), tgt_audios [B,Tr] or [1,Tr] (one reference for all).
-    generate_kwargs: more GPT.get_generator kwargs for every stream (the logits processors, ras_window / ras_threshold); with
+    generate_kwargs: more GPT.get_generator kwargs for every stream (the logits processors, ras_window / ras_threshold,
+    presence_penalty / frequency_penalty / penalty_window); with
     ras_window the result carries "ras_redraws", per stream the redraws of its segments.
     Returns per-stream lists: wav [B] tensors, tokens, plus first-chunk latency and the batch RTF."""
     from genvc_amd.layers.gpt import _no_assistant, _no_bias

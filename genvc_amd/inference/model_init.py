@@ -233,7 +233,8 @@ class GenVCModel(nn.Module):
 
     @torch.inference_mode()
     def warmup(self, seg_len=1.0, streams=1, ref_seconds=3.0, stream_chunk_size=8, top_k=None, max_new_tokens=None, num_beams=1,
-               contrastive_top_k=None, num_return_sequences=1, num_beam_groups=1, guidance=False, ras_window=None, ras_threshold=None):
+               contrastive_top_k=None, num_return_sequences=1, num_beam_groups=1, guidance=False, ras_window=None, ras_threshold=None,
+               presence_penalty=None, frequency_penalty=None, penalty_window=None):
         """Everything the FIRST conversion of this shape would otherwise pay inside its latency window (the reference leaves warm-up
         to the user: /root/reference/infer.py:27-30 runs a conversion first).  For `streams` concurrent streams of `seg_len`-second
         segments and a `ref_seconds` reference:
@@ -252,6 +253,9 @@ class GenVCModel(nn.Module):
         ras_window = K [, ras_threshold]: the calls will use repetition-aware sampling, which runs the full sampling kernel whatever
         top_k is: with top_k == 1 the sampling step graphs of the same shapes are captured as well (with any other top_k they are the
         ones already warmed), so a RAS call neither allocates nor captures.
+        presence_penalty / frequency_penalty / penalty_window: the calls will carry these penalties.  Both sampler kernels apply them
+        and the table travels in the device-resident call state, so the graphs warmed above are the ones such calls replay: the
+        values are validated (ValueError) and nothing more is captured.
         No token is generated and no KV slot is left occupied."""
         dev = self.device
         g = self.gpt
@@ -272,7 +276,8 @@ class GenVCModel(nn.Module):
         # the calls get_generator / _advance will make reach max_keys = n0 + grp ... n0 + max_new: the library warms every context class in
         # that range (its thresholds are its own: gvc_gpt_warmup_range)
         hi = min(n0 + max_new, eng.dims["max_seq"] - 1)
-        from genvc_amd.engine import ras_counts
+        from genvc_amd.engine import penalty_settings, ras_counts
+        penalty_settings(dict(presence_penalty=presence_penalty, frequency_penalty=frequency_penalty, penalty_window=penalty_window))
         ras = ras_counts(dict(ras_window=ras_window, ras_threshold=ras_threshold)) is not None
         for k in [top_k] + ([0] if ras and top_k == 1 else []):          # (0: the graphs around the full sampling kernel)
             eng.warmup_range(streams, min(n0 + grp, hi), hi, k)
@@ -305,7 +310,8 @@ class GenVCModel(nn.Module):
         interpolation -> HiFi-GAN.  (The reference's 0-d collapse at exactly one non-stop token, SURVEY appendix B.9, is
         guarded: boolean indexing keeps the dimension.)  The latents are the decode loop's own unless `repass_latents=True`
         (inference_utils._segment_latents).  generate_kwargs (extension): more GPT.generate kwargs (the logits processors:
-        min_new_tokens, no_repeat_ngram_size, ...; typical_p, epsilon_cutoff, eta_cutoff), merged over the ones above.
+        min_new_tokens, no_repeat_ngram_size, ...; typical_p, epsilon_cutoff, eta_cutoff; ras_window; presence_penalty,
+        frequency_penalty, penalty_window), merged over the ones above.
         num_return_sequences = N > 1 (the keyword, or in generate_kwargs; sampling only): a LIST of N waveforms, the candidates of
         GPT.generate(num_return_sequences=N) in row order, each stripped of its stop tokens and vocoded from the decode loop's own
         latents (or the re-pass with `repass_latents=True`); `last_sequence_logprobs` / `last_sequence_lengths` hold their scores

@@ -14,8 +14,8 @@ from torch.nn import functional as F
 
 from .._lib import GenvcHipError
 from ..engine import (MAX_ASSISTANT_TOKENS, MAX_LOOKUP_HISTORY, MAX_LOOKUP_NGRAM, MAX_VERIFY_ROWS, AssistedState, BEAM_LENGTH_MODES, beam_early_stopping, check_beam_groups, GroupBeamSearch, MAX_CONTRASTIVE_K, PROC_KWARGS, WARP_KWARGS, BeamSearch, ContrastiveSearch, GptEngine, WarperSets,
-                      RAS_KWARGS, RasTable, check_proc_kwargs, logits_bias, logits_processors, logits_ras, logits_sets, logits_warpers,
-                      ras_counts, sample_params)
+                      PENALTY_KWARGS, PenaltyTable, RAS_KWARGS, RasTable, check_proc_kwargs, logits_bias, logits_penalties,
+                      logits_processors, logits_ras, logits_sets, logits_warpers, penalty_settings, ras_counts, sample_params)
 from .perceiver_encoder import PerceiverResampler
 
 
@@ -308,6 +308,15 @@ def _no_ras(kw, mode):
                                   "the token of a sampler step (greedy at top_k=1, sampling, num_return_sequences, guidance_scale)")
 
 
+def _no_penalties(kw, mode):
+    """the modes of GPT.generate that the presence / frequency / windowed penalties do not serve raise, naming the kwarg and the mode
+    (malformed settings: ValueError, engine.penalty_settings)"""
+    if penalty_settings(kw) is not None:
+        k = next(k for k in PENALTY_KWARGS if kw.get(k))
+        raise NotImplementedError(f"{k}={kw.get(k)} with {mode} is not implemented: the presence / frequency / windowed repetition "
+                                  "penalties act in a sampler step (greedy, sampling, num_return_sequences, guidance_scale)")
+
+
 ASSIST_KWARGS = ("assistant_model", "num_assistant_tokens", "num_assistant_tokens_schedule", "assistant_cond_latents",
                  "speculative_sampling")
 
@@ -439,7 +448,7 @@ def _per_item_procs(kw, item_kwargs, n, name, vocab):
     item_kwargs = list(item_kwargs)
     if len(item_kwargs) != n:
         raise ValueError(f"{name}: {len(item_kwargs)} processor dicts for {n} items")
-    base = {k: kw[k] for k in PROC_KWARGS + WARP_KWARGS + RAS_KWARGS if kw.get(k) is not None}
+    base = {k: kw[k] for k in PROC_KWARGS + WARP_KWARGS + RAS_KWARGS + PENALTY_KWARGS if kw.get(k) is not None}
     out = []
     for i, d in enumerate(item_kwargs):
         check_proc_kwargs(d, f"{name}[{i}]")
@@ -448,6 +457,7 @@ def _per_item_procs(kw, item_kwargs, n, name, vocab):
             logits_processors(m, 0, vocab)
             logits_warpers(m, sampling=kw.get("do_sample", True))
             _ras_on(dict(m, do_sample=kw.get("do_sample", True)))
+            penalty_settings(m)
         except ValueError as e:
             raise ValueError(f"{name}[{i}]: {e}") from None
         out.append(m)
@@ -717,6 +727,9 @@ class GPT(nn.Module):
         if _ras_on(kw):
             st["ras"] = RasTable([logits_ras(kw, n0)], torch.zeros(B, device=dev, dtype=torch.int32))
         self.last_ras_redraws = None if st["ras"] is None else st["ras"].redraws
+        # presence / frequency / windowed repetition penalties (engine.PENALTY_KWARGS): one call-wide entry counting from the fake ids
+        pen = logits_penalties(kw, n0)
+        st["pen"] = None if pen is None else PenaltyTable([pen])
         # `cached_cond_rows` (extension): the leading rows of the prefix -- the conditioning latents, identical for every
         # segment of an utterance -- are still in the KV cache from the previous segment's prefill of these slots
         if fan > 1:
@@ -739,7 +752,8 @@ class GPT(nn.Module):
                            st["lats"], max_keys=max(st["n0"], st.get("n0_uncond", 0)) + st["done"] + n, proc=st["proc"],
                            sets=st["warp"], bias=st.get("bias"), uncond_slots=st.get("uncond_slots"),
                            scale=st.get("guidance_scale", 1.0), scores_out=st.get("scores"), logits_out=st.get("raw_logits"),
-                           do_sample=st.get("do_sample", True), **({} if st.get("ras") is None else {"ras": st["ras"]}))
+                           do_sample=st.get("do_sample", True), **({} if st.get("ras") is None else {"ras": st["ras"]}),
+                           **({} if st.get("pen") is None else {"pen": st["pen"]}))
             st["done"] += n
         end = bool(st["finished"].all().item()) or st["done"] >= st["max_new"]
         self.engine.health()          # (the .item() above synchronised: a hand-off timeout of these steps surfaces here, not a call later)
@@ -898,6 +912,13 @@ class GPT(nn.Module):
         greedy decoding with an escape; do_sample=False raises ValueError pointing there.  `last_ras_redraws` (and `ras_redraws` of a
         GenerateOutput) count each row's redraws; scores and logits stay those of the first draw.  None or 0 is exactly the call
         without it.  Beams, beam groups, contrastive search, assisted and prompt-lookup decoding raise NotImplementedError.
+        presence_penalty = p, frequency_penalty = f (each in [-2, 2]), penalty_window = W (engine.logits_penalties;
+        include/genvc_hip.h: gvc_logits_penalties) on the same sampler paths, greedy search included: an id that
+        occurs c > 0 times among the row's last W generated tokens (all of them without a window; the fake prompt ids never count)
+        loses f * c + p, directly behind the repetition penalty; with W > 0 the repetition penalty too covers only those ids
+        (repetition_penalty=2.0, penalty_window=16 is a windowed repetition penalty).  `scores` carry them, `logits` stay raw.
+        Each None or 0 is exactly the call without it.  Beams, beam groups, contrastive search, assisted and prompt-lookup
+        decoding raise NotImplementedError.
         assistant_model = another initialised GPT: assisted (speculative) greedy decoding (_generate_assisted), checked
         before every other mode; the tokens are those of the call without it.  None is exactly that call.  With
         speculative_sampling=True a sampled call is served too (speculative sampling: same distribution per token, other tokens than
@@ -909,6 +930,7 @@ class GPT(nn.Module):
         _num_return(generate_kwargs)
         if _lookup(generate_kwargs) or generate_kwargs.get("assistant_model") is not None:
             _no_ras(generate_kwargs, _LOOKUP_MODE if _lookup(generate_kwargs) else "assisted decoding (assistant_model)")
+            _no_penalties(generate_kwargs, _LOOKUP_MODE if _lookup(generate_kwargs) else "assisted decoding (assistant_model)")
             return self._generate_assisted(cond_latents, text_inputs, generate_kwargs)
         if ras_counts(generate_kwargs) is not None:
             if _contrastive_mode(generate_kwargs) is not None:
@@ -918,6 +940,13 @@ class GPT(nn.Module):
             if int(generate_kwargs.get("num_beams", 1) or 1) > 1:
                 _no_ras(generate_kwargs, f"beam search (num_beams={generate_kwargs.get('num_beams')})")
             _ras_on(generate_kwargs)          # (do_sample=False: ValueError)
+        if penalty_settings(generate_kwargs) is not None:
+            if _contrastive_mode(generate_kwargs) is not None:
+                _no_penalties(generate_kwargs, f"contrastive search (penalty_alpha={generate_kwargs.get('penalty_alpha')})")
+            if _grouped(generate_kwargs):
+                _no_penalties(generate_kwargs, "beam groups (num_beam_groups / diversity_penalty)")
+            if int(generate_kwargs.get("num_beams", 1) or 1) > 1:
+                _no_penalties(generate_kwargs, f"beam search (num_beams={generate_kwargs.get('num_beams')})")
         scale = _guidance_scale(generate_kwargs)
         if scale is not None:
             return self._generate_guided(cond_latents, text_inputs, scale, generate_kwargs)
@@ -1279,6 +1308,7 @@ class GPT(nn.Module):
         Returns a list of int64 [B_i, n_i] (reference gpt.py:594-609 per group)."""
         _plain_rows_only(generate_kwargs, "grouped (generate_groups)")
         _ras_on(generate_kwargs)          # (malformed ras_window / ras_threshold, or do_sample=False with them: ValueError)
+        penalty_settings(generate_kwargs)          # (malformed presence_penalty / frequency_penalty / penalty_window: ValueError)
         kw = dict(generate_kwargs)
         gkw = None
         if group_kwargs is not None:
@@ -1339,8 +1369,10 @@ class GPT(nn.Module):
         groups = [groups[i] for i in order]
         seeds = [seeds[i] for i in order] if seeds is not None else None
         gkw = [gkw[i] for i in order] if gkw is not None else None
-        if gkw is None and seeds is not None and (logits_warpers(kw) is not None or ras_counts(kw) is not None):
-            # call-wide warpers / RAS: every group carries the call's processor, warper and RAS kwargs (logits_sets)
+        if gkw is None and ((seeds is not None and (logits_warpers(kw) is not None or ras_counts(kw) is not None))
+                            or penalty_settings(kw) is not None):
+            # call-wide warpers / RAS / penalties: every group carries the call's processor, warper, RAS and penalty kwargs
+            # (logits_sets; the penalties count from each group's own prompt length, greedy calls included)
             gkw = _per_item_procs(kw, [None] * len(groups), len(groups), "generate_kwargs", self.num_audio_tokens)
         gb = [budgets[i] if budgets else max_new for i in order]
         prefixes = [self.engine.prefix_embeddings(c.to(torch.float32).contiguous(), t.to(torch.int32).contiguous()) for c, t in groups]
@@ -1422,6 +1454,7 @@ class GPT(nn.Module):
         row of a decode call carrying its job's set (gvc_gpt_generate_proc_sets, or gvc_gpt_generate_warp when a warper is on)."""
         _plain_rows_only(generate_kwargs, "rolling (generate_rolling)")
         _ras_on(generate_kwargs)          # (malformed ras_window / ras_threshold, or do_sample=False with them: ValueError)
+        penalty_settings(generate_kwargs)          # (malformed presence_penalty / frequency_penalty / penalty_window: ValueError)
         kw = dict(generate_kwargs)
         jkw = None
         if job_kwargs is not None:
@@ -1457,8 +1490,10 @@ class GPT(nn.Module):
 
     def _rolling(self, jobs, kw, budgets, group, n0s, width, S, seeds=None, jkw=None):
         dev = jobs[0][1].device
-        if jkw is None and seeds is not None and (logits_warpers(kw) is not None or ras_counts(kw) is not None):
-            # call-wide warpers / RAS: every job carries the call's processor, warper and RAS kwargs (logits_sets)
+        if jkw is None and ((seeds is not None and (logits_warpers(kw) is not None or ras_counts(kw) is not None))
+                            or penalty_settings(kw) is not None):
+            # call-wide warpers / RAS / penalties: every job carries the call's processor, warper, RAS and penalty kwargs
+            # (logits_sets; the penalties count from each job's own prompt length, greedy calls included)
             jkw = _per_item_procs(kw, [None] * len(jobs), len(jobs), "generate_kwargs", self.num_audio_tokens)
         eng = self.engine
         stop = self.stop_audio_token
@@ -1565,6 +1600,7 @@ class GPT(nn.Module):
         inference_utils.py:195) with one host check of the finished flags per group."""
         _plain_rows_only(generate_kwargs, "streaming (get_generator)")
         _ras_on(generate_kwargs)          # (malformed ras_window / ras_threshold, or do_sample=False with them: ValueError)
+        penalty_settings(generate_kwargs)          # (malformed presence_penalty / frequency_penalty / penalty_window: ValueError)
         self._need_engine()
         group = generate_kwargs.pop("stream_group", 8)
         B = int(fake_inputs.shape[0])

@@ -42,7 +42,7 @@ import time
 import torch
 
 from .inference.inference_utils import _sampling_kwargs, _vocode, handle_chunks
-from .engine import check_proc_kwargs, logits_processors, logits_sets, logits_warpers, ras_counts, sample_params
+from .engine import check_proc_kwargs, logits_processors, logits_sets, logits_warpers, penalty_settings, ras_counts, sample_params
 from .layers.gpt import _generate_call, _plain_rows_only
 from ._lib import GenvcHipError
 
@@ -102,8 +102,8 @@ class StreamSessions:
 
     # ------------------------------------------------------------------------------------------
     def _procs(self, kw, base, where):
-        """a processor dict (PROC_KWARGS, WARP_KWARGS and RAS_KWARGS only) merged over `base`, validated -> the merged dict, or None when it is
-        empty.  The contrastive-search kwargs raise NotImplementedError (sessions decode one row per stream)"""
+        """a processor dict (PROC_KWARGS, WARP_KWARGS, RAS_KWARGS and PENALTY_KWARGS only) merged over `base`, validated -> the merged
+        dict, or None when it is empty.  The contrastive-search kwargs raise NotImplementedError (sessions decode one row per stream)"""
         _plain_rows_only(kw or {}, f"session (StreamSessions, {where})", beams=False)
         check_proc_kwargs(kw, where)
         m = dict(base, **{k: v for k, v in (kw or {}).items() if v is not None})
@@ -111,6 +111,7 @@ class StreamSessions:
             logits_processors(m, 0, self.m.gpt.num_audio_tokens)
             logits_warpers(m)
             ras_counts(m)
+            penalty_settings(m)
         except ValueError as e:
             raise ValueError(f"{where}: {e}") from None
         return m or None
@@ -119,8 +120,9 @@ class StreamSessions:
     def open(self, ref_audio, sampling=None, seed=0, generate_kwargs=None):
         """ref_audio [1, n] at the model rate -> session id.  With per_session_sampling: `sampling` (top_k, top_p, temperature,
         repetition_penalty; missing keys come from the model config) and `seed` are this session's own; otherwise passing either raises.
-        `generate_kwargs`: the session's logits processors, warpers and repetition-aware sampling (PROC_KWARGS, WARP_KWARGS,
-        RAS_KWARGS: ras_window / ras_threshold), merged over the scheduler's default; any other key raises.  A session with RAS draws
+        `generate_kwargs`: the session's logits processors, warpers, repetition-aware sampling and penalties (PROC_KWARGS, WARP_KWARGS,
+        RAS_KWARGS: ras_window / ras_threshold, PENALTY_KWARGS: presence_penalty / frequency_penalty / penalty_window), merged over
+        the scheduler's default; any other key raises.  A session with RAS draws
         its redraws from its own key under per_session_sampling, and then gets the tokens of its solo run."""
         if not self.per_session_sampling and (sampling is not None or seed != 0):
             raise ValueError("open(sampling=..., seed=...) needs StreamSessions(..., per_session_sampling=True): this scheduler samples "

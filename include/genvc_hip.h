@@ -724,6 +724,53 @@ int gvc_gpt_generate_ras(gvc_gpt* ctx, const int32_t* slots, const int32_t* unco
                          int32_t* ras_redraws, int32_t i0, int32_t n_steps, int32_t max_keys, int32_t* tokens_out, int32_t tok_stride,
                          float* latents_out, int32_t lat_stride, float* scores_out, float* logits_out, int32_t out_stride,
                          int32_t do_sample, gvc_stream s);
+/* ------------------------------------------------------------------------------------------
+ * Presence, frequency and windowed repetition penalties (the OpenAI / vLLM definition of the first two), on both sampler kernels.
+ * Counts of a row at a step:
+ *   n_gen = len - prompt_len (the fake prompt ids never count, as for RAS);
+ *   w = n_gen when window == 0, else min(window, n_gen);
+ *   c_i = how often id i occurs among the row's last w generated ids, ids[len - w .. len); ids outside [0, vocab) are ignored.
+ * For every i with c_i > 0: score_i -= frequency * c_i + presence, in fp32 with this operation order and no fused multiply-add:
+ *   t = fl(fl(frequency * float(c_i)) + presence), score_i = fl(score_i - t).
+ * Place in the chain: directly behind RepetitionPenalty -- behind SequenceBias, ahead of the n-gram, length and suppress processors,
+ * the EOS decay and Temperature.  Under guidance they act on the guided row with the conditional row's ids, as the repetition
+ * penalty does.  Per-step scores (gvc_gpt_generate_scores) carry them: they are processors; logits stay raw.
+ * window > 0 also narrows the row's multiplicative repetition_penalty to the ids with c_i > 0 (the fake prompt ids are no longer
+ * penalised): the windowed repetition penalty, usable alone (presence = frequency = 0).  With window == 0 the repetition penalty is
+ * untouched: every id of input_ids, once.  The stop code is never in a row's history, so c_eos = 0.  A RAS redraw (gvc_logits_ras)
+ * draws from the row that carries the penalties.  The counts are integers built with integer LDS atomics: the same bits on every
+ * run, whatever the history length.
+ * A null table, a -1 index or an entry with presence == frequency == 0 and window == 0 computes exactly what the call without it
+ * computes, through the same barriers.
+ * ------------------------------------------------------------------------------------------ */
+#define GVC_PENALTY_MAX 2.0f            /* |presence|, |frequency| <= 2: the OpenAI range */
+typedef struct gvc_logits_penalties {
+    float presence;                     /* p in [-2, 2]; 0 off */
+    float frequency;                    /* f in [-2, 2]; 0 off */
+    int32_t window;                     /* 0: every generated id of the row; W > 0: the last W of them (and the repetition penalty too) */
+    int32_t prompt_len;                 /* prompt length of the rows of this entry (fake ids included), as gvc_logits_ras' */
+} gvc_logits_penalties;
+
+/* gvc_sample_pen: gvc_sample_ras with a penalties table; gvc_gpt_generate_pen: gvc_gpt_generate_ras with one.  pen (HOST, nullable:
+ * null is exactly the call without it): n_sets entries (1 <= n_sets <= B <= 64) indexed like warps / ras -- row b uses
+ * pen[set_of_row[b]], none for -1, entry 0 for every row when set_of_row is null.  The table travels into the device-resident call
+ * state in one staging launch of its own (1 KB of kernel argument) ahead of the call's first launch, so nothing is allocated or
+ * synchronised per call.  The kernels and step graphs are those of the call without the table (the argmax kernel at top_k == 1
+ * unless the call also has a RAS table), so gvc_gpt_warmup and its relatives prepare such calls as they stand.  GVC_ERR_ARG: a
+ * non-finite presence / frequency or one outside [-2, 2], window < 0, prompt_len < 0, n_sets outside [1, B].  Not on the beam,
+ * contrastive, assisted or lookup paths. */
+int gvc_sample_pen(const float* logits, int32_t B, int32_t* ids, int32_t ids_stride, int32_t* ids_len, int32_t* finished,
+                   const gvc_sample_params* p, const gvc_row_sampling* rows, const gvc_logits_processors* sets,
+                   const gvc_logits_warpers* warps, int32_t n_sets, const int32_t* set_of_row, const gvc_logits_bias* bias,
+                   const gvc_logits_ras* ras, int32_t* ras_redraws, const gvc_logits_penalties* pen, int32_t step, int32_t* tok_out,
+                   gvc_stream s);
+int gvc_gpt_generate_pen(gvc_gpt* ctx, const int32_t* slots, const int32_t* uncond_slots, int32_t B, float scale, int32_t* ids,
+                         int32_t ids_stride, int32_t* ids_len, int32_t* finished, const gvc_sample_params* p,
+                         const gvc_row_sampling* rows, const gvc_logits_processors* sets, const gvc_logits_warpers* warps,
+                         int32_t n_sets, const int32_t* set_of_row, const gvc_logits_bias* bias, const gvc_logits_ras* ras,
+                         int32_t* ras_redraws, const gvc_logits_penalties* pen, int32_t i0, int32_t n_steps, int32_t max_keys,
+                         int32_t* tokens_out, int32_t tok_stride, float* latents_out, int32_t lat_stride, float* scores_out,
+                         float* logits_out, int32_t out_stride, int32_t do_sample, gvc_stream s);
 /* gvc_gpt_warmup for gvc_gpt_generate_cfg over B items with this top_k: the guided step graphs of every context class up to max_keys
  * cached positions (and everything gvc_gpt_warmup(2B) prepares).  Afterwards such calls neither allocate nor synchronise */
 int gvc_gpt_warmup_cfg(gvc_gpt* ctx, int32_t B, int32_t max_keys, int32_t top_k);

@@ -57,6 +57,13 @@ if __name__ == "__main__":
                              "from the untruncated distribution; with --top_k 1 this is greedy decoding with an escape from loops")
     parser.add_argument("--ras_threshold", type=float, default=None, metavar="T",
                         help="with --ras_window: the share of the window in (0, 1] at which a token is drawn again (default 0.1)")
+    parser.add_argument("--presence_penalty", type=float, default=None, metavar="X",
+                        help="subtract X (in [-2, 2]) from the score of every code that occurs among the counted generated codes")
+    parser.add_argument("--frequency_penalty", type=float, default=None, metavar="Y",
+                        help="subtract Y (in [-2, 2]) times its count from the score of every code among the counted generated codes")
+    parser.add_argument("--penalty_window", type=int, default=None, metavar="W",
+                        help="count only the last W generated codes for --presence_penalty / --frequency_penalty, and apply "
+                             "--repetition_penalty to those codes only (default: every generated code; the repetition penalty unchanged)")
     parser.add_argument("--sequence_bias", action="append", default=None, metavar="IDS=VALUE",
                         help="non-streaming only, repeatable: add VALUE to the score of the last of the comma-separated codec ids when the "
                              "ids before it were just generated (HF sequence_bias), e.g. 1025=-2.0 makes every segment stop later")
@@ -176,6 +183,17 @@ if __name__ == "__main__":
                                 or args.assistant_layers is not None or args.prompt_lookup_num_tokens is not None):
             raise SystemExit("--ras_window does not combine with --num_beams, --num_beam_groups, --penalty_alpha, --assistant_layers or "
                              "--prompt_lookup_num_tokens: it redraws the token of a sampler step")
+    for k in ("presence_penalty", "frequency_penalty"):
+        v = getattr(args, k)
+        if v is not None and not -2.0 <= v <= 2.0:          # (a NaN fails both comparisons)
+            raise SystemExit(f"--{k} must be in [-2, 2], not {v}")
+    if args.penalty_window is not None and args.penalty_window < 0:
+        raise SystemExit("--penalty_window must be >= 0 (0: every generated code)")
+    if (args.presence_penalty or args.frequency_penalty or args.penalty_window) and (
+            args.num_beams != 1 or args.num_beam_groups != 1 or args.penalty_alpha is not None or args.assistant_layers is not None
+            or args.prompt_lookup_num_tokens is not None):
+        raise SystemExit("--presence_penalty / --frequency_penalty / --penalty_window do not combine with --num_beams, --num_beam_groups, "
+                         "--penalty_alpha, --assistant_layers or --prompt_lookup_num_tokens: they act in a sampler step")
     gen_kw = {k: v for k, v in (("min_new_tokens", args.min_new_tokens), ("no_repeat_ngram_size", args.no_repeat_ngram_size),
                                 ("min_p", args.min_p)) if v is not None}
     if args.eos_decay is not None:
@@ -191,6 +209,9 @@ if __name__ == "__main__":
         if not ((v > 0.0 if lo_open else v >= 0.0) and (v < 1.0 if hi_open else v <= 1.0)):
             raise SystemExit(f"bad warper flag: --{k} must be in {'(' if lo_open else '['}0, 1{')' if hi_open else ']'}, not {v}")
         gen_kw[k] = v
+    for k in ("presence_penalty", "frequency_penalty", "penalty_window"):
+        if getattr(args, k):
+            gen_kw[k] = getattr(args, k)
     if args.ras_window:
         gen_kw["ras_window"] = args.ras_window
         if args.ras_threshold is not None:
