@@ -150,6 +150,13 @@ class HifiganDims(C.Structure):
                 ("res_dilations", (C.c_int32 * 2) * 4), ("max_batch", C.c_int32), ("max_frames", C.c_int32)]
 
 
+class HifiganDimsEx(C.Structure):
+    """gvc_hifigan_dims_ex (include/genvc_hip.h): HifiganDims plus resblock_type and a third dilation per kernel"""
+    _fields_ = [("in_dim", C.c_int32), ("up_init_ch", C.c_int32), ("n_ups", C.c_int32), ("up_rates", C.c_int32 * 4),
+                ("up_kernels", C.c_int32 * 4), ("n_kernels", C.c_int32), ("res_kernels", C.c_int32 * 4), ("resblock_type", C.c_int32),
+                ("res_dilations", (C.c_int32 * 3) * 4), ("max_batch", C.c_int32), ("max_frames", C.c_int32)]
+
+
 class HubertDims(C.Structure):
     _fields_ = [("n_conv", C.c_int32), ("conv_dim", C.c_int32 * 8), ("conv_kernel", C.c_int32 * 8),
                 ("conv_stride", C.c_int32 * 8)] + [(n, C.c_int32) for n in (
@@ -357,6 +364,9 @@ _SIGNATURES = {
     "gvc_hubert_frames": (C.c_int, [_P, C.c_int32]),
     "gvc_hubert_forward": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P]),
     "gvc_hifigan_create": (C.c_int, [C.POINTER(HifiganDims), C.POINTER(_P)]),
+    "gvc_hifigan_create_ex": (C.c_int, [C.POINTER(HifiganDimsEx), C.POINTER(_P)]),
+    "gvc_hifigan_lds_stages": (C.c_int, [_P]),
+    "gvc_hifigan_graph_nodes": (C.c_int, [_P]),
     "gvc_hifigan_destroy": (C.c_int, [_P]),
     "gvc_hifigan_bind_weight": (C.c_int, [_P, C.c_char_p, _P, C.c_int64, _P]),
     "gvc_hifigan_missing_weights": (C.c_int, [_P]),

@@ -31,6 +31,9 @@ DEFAULT_VOCODER = dict(input_feat_dim=1024, upsample_initial_channel=256, resblo
                        sample_rate=24000, fft_size=1024, num_mels=100, mel_fmin=0, mel_fmax=12000, win_length=1024,
                        mpd_reshapes=[2, 3, 5, 7, 11], mpd_discriminator_channel_mult_factor=1, mpd_use_spectral_norm=False)
 TINY_VOCODER = dict(DEFAULT_VOCODER, input_feat_dim=256, upsample_initial_channel=64, mpd_discriminator_channel_mult_factor=0.25)
+# the residual blocks of the HiFi-GAN V1 generator (reference layers/hifigan.py:28-117, ResBlock1): what default_config(resblock_type="1")
+# puts into the vocoder config
+V1_RESBLOCKS = dict(resblock_type="1", resblock_kernel_sizes=[3, 7, 11], resblock_dilation_sizes=[[1, 3, 5], [1, 3, 5], [1, 3, 5]])
 
 # HuBERT-base / ContentVec (fairseq HubertModel): conv extractor (dim, kernel, stride), post-LN encoder
 DEFAULT_HUBERT = dict(conv_layers=[(512, 10, 5)] + [(512, 3, 2)] * 4 + [(512, 2, 2)] * 2, embed_dim=768, layers=12, heads=12,
@@ -82,9 +85,10 @@ def to_attr(d):
     return d
 
 
-def default_config(tiny=False, with_acoustic=False):
+def default_config(tiny=False, with_acoustic=False, resblock_type="2"):
     """with_acoustic=True adds `acoustic_dvae_config` (as a reference checkpoint's config has): GenVCModel then builds the acoustic
-    DVAE and its mel extractor (format_batch_on_device / evaluate / decode of generated codes)."""
+    DVAE and its mel extractor (format_batch_on_device / evaluate / decode of generated codes).  resblock_type "1": the vocoder config
+    of a generator built from ResBlock1s, with the HiFi-GAN V1 kernels and dilations (V1_RESBLOCKS)."""
     cfg = dict(
         model_args=copy.deepcopy(TINY_MODEL_ARGS if tiny else DEFAULT_MODEL_ARGS),
         content_dvae_config=copy.deepcopy(TINY_CONTENT_DVAE if tiny else DEFAULT_CONTENT_DVAE),
@@ -95,4 +99,6 @@ def default_config(tiny=False, with_acoustic=False):
     )
     if with_acoustic:
         cfg["acoustic_dvae_config"] = copy.deepcopy(TINY_ACOUSTIC_DVAE if tiny else DEFAULT_ACOUSTIC_DVAE)
+    if str(resblock_type) == "1":
+        cfg["vocoder_config"].update(copy.deepcopy(V1_RESBLOCKS))
     return to_attr(cfg)

@@ -12,6 +12,9 @@
 // graph: conv_pre (K-split over 64-channel slices, combined by the last workgroup to arrive), per stage the upsampling layer,
 // the first convs of the three ResBlocks in one launch and the second convs in another; the consumer of a stage adds the three
 // ResBlock planes and the 1/3 while it stages its input.  184 -> 85 us per call (profiles/r03_microbench_notes.md section 9).
+// A generator of ResBlock1s (:28-117, gvc_hifigan_create_ex with resblock_type 1: per dilation a dilated conv, a conv of dilation 1 and
+// the skip) runs six such launches per stage instead of two, its x planes ping-ponging through a second plane set (hf_resblock1_lds;
+// DESIGN.md section 4.30).
 // Shapes k_conv_lds does not take (and GVC_VOCODER_SMALL_CONV=0) run on the tiled fp32 MFMA GEMM of gemm.h, one launch per conv.
 // conv_post (Cout = 1) + tanh is a small dedicated kernel.  Weight-norm (weight_g, weight_v) is folded by the loader.
 #include <stdlib.h>
@@ -204,10 +207,12 @@ static void hf_destroy_plan(HfPlan& pl) {
 }
 
 struct gvc_hifigan {
-    gvc_hifigan_dims dm;
+    gvc_hifigan_dims_ex dm;
+    bool type1 = false;                      // ResBlock1 (convs1 / convs2, three dilations) instead of ResBlock2
+    int nconv = 2;                           // convs per ResBlock: 2, or 6 for ResBlock1
     HfConv pre, post;
     std::vector<HfUp> ups;
-    std::vector<HfConv> res;                 // [stage][kernel][2]
+    std::vector<HfConv> res;                 // ResBlock2 [stage][kernel][2]; ResBlock1 [stage][kernel][m][convs1[m], convs2[m]]
     std::map<std::string, int> bound;
     int n_expected = 0;
     float* x0 = nullptr;                     // interpolated input
@@ -215,7 +220,11 @@ struct gvc_hifigan {
     // per stage: U = upsampled signal; R, S = n_kernels planes each (outputs of the first ResBlock convs / of the ResBlocks; the
     // launch-per-conv path keeps its running sum in planes 0 and 1 of S)
     std::vector<float*> U, R, S;
+    // ResBlock1 only: a second plane set.  A block's x is updated three times and a launch never writes the planes it reads (the
+    // neighbouring workgroups read them as halo), so x ping-pongs S -> S2 -> S
+    std::vector<float*> S2;
     std::vector<long long> plane;            // floats per plane
+    int graph_nodes = 0;                     // kernel nodes of the most recently captured whole-call graph
     float* work = nullptr;
     long long work_cap = 0;
     float* pre_wp = nullptr;                 // conv_pre weights as 64-channel slices in FM16 (k_conv_lds<.., SPLIT>), null: shape not eligible
@@ -242,18 +251,36 @@ static int halloc(gvc_hifigan* c, float** p, size_t n) {
 
 constexpr int kPreSlice = 64, kPreCounters = 4096;
 
+// the ResBlock2 entry: the same generator through the dims of gvc_hifigan_create_ex
 extern "C" int gvc_hifigan_create(const gvc_hifigan_dims* dims, gvc_hifigan** out) {
     GVC_REQUIRE(dims && out, GVC_ERR_ARG, "gvc_hifigan_create: null argument");
-    const gvc_hifigan_dims& D = *dims;
+    gvc_hifigan_dims_ex E;
+    memset(&E, 0, sizeof(E));
+    E.in_dim = dims->in_dim; E.up_init_ch = dims->up_init_ch; E.n_ups = dims->n_ups; E.n_kernels = dims->n_kernels;
+    E.resblock_type = 2; E.max_batch = dims->max_batch; E.max_frames = dims->max_frames;
+    for (int i = 0; i < 4; ++i) {
+        E.up_rates[i] = dims->up_rates[i]; E.up_kernels[i] = dims->up_kernels[i]; E.res_kernels[i] = dims->res_kernels[i];
+        E.res_dilations[i][0] = dims->res_dilations[i][0]; E.res_dilations[i][1] = dims->res_dilations[i][1];
+    }
+    return gvc_hifigan_create_ex(&E, out);
+}
+
+extern "C" int gvc_hifigan_create_ex(const gvc_hifigan_dims_ex* dims, gvc_hifigan** out) {
+    GVC_REQUIRE(dims && out, GVC_ERR_ARG, "gvc_hifigan_create_ex: null argument");
+    const gvc_hifigan_dims_ex& D = *dims;
     GVC_REQUIRE(D.n_ups >= 1 && D.n_ups <= 4 && D.n_kernels >= 1 && D.n_kernels <= 4 && D.in_dim % 4 == 0, GVC_ERR_ARG,
                 "hifigan: bad dims");
+    GVC_REQUIRE(D.resblock_type == 1 || D.resblock_type == 2, GVC_ERR_ARG, "hifigan: resblock_type %d (1 or 2)", D.resblock_type);
     auto* c = new gvc_hifigan();
     c->dm = D;
+    c->type1 = D.resblock_type == 1;
+    c->nconv = c->type1 ? 6 : 2;
     int rc = GVC_OK;
-    auto mkconv = [&](HfConv& w, int Co, int Ci, int k, int dil) {
+    // lds_max_ci: the widest conv that gets an FM16 copy for k_conv_lds (ResBlock1 runs there up to 128 channels)
+    auto mkconv = [&](HfConv& w, int Co, int Ci, int k, int dil, int lds_max_ci = 512) {
         w.Co = Co; w.Ci = Ci; w.k = k; w.dil = dil;
         int r = halloc(c, &w.w, (size_t)Co * Ci * k);
-        if (!r && Co == Ci && conv_lds_ci_ok(Ci) && conv_lds_bytes(Ci, k, dil) <= kConvLdsMax) r = halloc(c, &w.wp, (size_t)Co * Ci * k);
+        if (!r && Co == Ci && Ci <= lds_max_ci && conv_lds_ci_ok(Ci) && conv_lds_bytes(Ci, k, dil) <= kConvLdsMax) r = halloc(c, &w.wp, (size_t)Co * Ci * k);
         return r ? r : halloc(c, &w.b, Co);
     };
     rc = mkconv(c->pre, D.up_init_ch, D.in_dim, 7, 1);
@@ -285,22 +312,24 @@ extern "C" int gvc_hifigan_create(const gvc_hifigan_dims* dims, gvc_hifigan** ou
         ch = u.Co;
         T *= u.s;
         for (int j = 0; j < D.n_kernels && !rc; ++j)
-            for (int q = 0; q < 2 && !rc; ++q) {
+            for (int q = 0; q < c->nconv && !rc; ++q) {
                 HfConv w;
-                rc = mkconv(w, ch, ch, D.res_kernels[j], D.res_dilations[j][q]);
+                // ResBlock1: convs1[m] (q = 2m) has the m-th dilation, convs2[m] (q = 2m + 1) dilation 1
+                if (c->type1) rc = mkconv(w, ch, ch, D.res_kernels[j], (q & 1) ? 1 : D.res_dilations[j][q >> 1], 128);
+                else rc = mkconv(w, ch, ch, D.res_kernels[j], D.res_dilations[j][q]);
                 GVC_REQUIRE(rc || w.dil * (w.k - 1) / 2 <= kHfPad, GVC_ERR_UNSUPPORTED, "hifigan: conv padding exceeds %d", kHfPad);
                 c->res.push_back(w);
             }
-        float *u_, *r_, *s_;
+        float *u_, *r_, *s_, *s2_ = nullptr;
         const size_t n = B * (T + 2 * kHfPad) * ch, np = n * (D.n_kernels > 2 ? D.n_kernels : 2);
-        if (!rc && !(rc = halloc(c, &u_, n)) && !(rc = halloc(c, &r_, np)) && !(rc = halloc(c, &s_, np))) {
-            c->U.push_back(u_); c->R.push_back(r_); c->S.push_back(s_); c->plane.push_back((long long)n);
+        if (!rc && !(rc = halloc(c, &u_, n)) && !(rc = halloc(c, &r_, np)) && !(rc = halloc(c, &s_, np)) && !(c->type1 && (rc = halloc(c, &s2_, np)))) {
+            c->U.push_back(u_); c->R.push_back(r_); c->S.push_back(s_); c->S2.push_back(s2_); c->plane.push_back((long long)n);
         }
     }
     if (!rc) rc = mkconv(c->post, 1, ch, 7, 1);
     c->work_cap = 4ll << 20;
     if (!rc) rc = halloc(c, &c->work, (size_t)c->work_cap);
-    c->n_expected = 2 * (2 + D.n_ups + 2 * D.n_ups * D.n_kernels);
+    c->n_expected = 2 * (2 + D.n_ups + c->nconv * D.n_ups * D.n_kernels);
     if (rc) { gvc_hifigan_destroy(c); return rc; }
     if (getenv("GVC_VOCODER_GRAPH")) c->use_graph = atoi(getenv("GVC_VOCODER_GRAPH"));
     if (getenv("GVC_VOCODER_SMALL_CONV")) c->small_conv = atoi(getenv("GVC_VOCODER_SMALL_CONV"));
@@ -337,7 +366,7 @@ static int hf_bind_conv(HfConv& w, bool is_bias, const float* src, int64_t numel
 }
 
 // names as in the reference state dict AFTER weight-norm folding: "conv_pre.weight", "ups.0.bias",
-// "resblocks.4.convs.1.weight", "conv_post.weight", ...
+// "resblocks.4.convs.1.weight", "conv_post.weight", ...; a ResBlock1 context takes "resblocks.4.convs1.2.weight", "resblocks.4.convs2.2.bias"
 extern "C" int gvc_hifigan_bind_weight(gvc_hifigan* c, const char* name, const float* src, int64_t numel, gvc_stream sv) {
     GVC_REQUIRE(c && name && src, GVC_ERR_ARG, "gvc_hifigan_bind_weight: null argument");
     hipStream_t s = (hipStream_t)sv;
@@ -376,11 +405,21 @@ extern "C" int gvc_hifigan_bind_weight(gvc_hifigan* c, const char* name, const f
         }
     } else if (n.rfind("resblocks.", 0) == 0) {
         const int bi = atoi(n.c_str() + 10);
-        const size_t pos = n.find(".convs.");
-        GVC_REQUIRE(pos != std::string::npos, GVC_ERR_ARG, "malformed weight name %s", name);
-        const int q = atoi(n.c_str() + pos + 7);
-        const int idx = bi * 2 + q;
-        GVC_REQUIRE(bi >= 0 && q >= 0 && q < 2 && idx < (int)c->res.size(), GVC_ERR_ARG, "%s: out of range", name);
+        int idx = -1;
+        if (c->type1) {                 // resblocks.{bi}.convs1.{m} / .convs2.{m}
+            const size_t p1 = n.find(".convs1."), p2 = n.find(".convs2.");
+            GVC_REQUIRE(p1 != std::string::npos || p2 != std::string::npos, GVC_ERR_ARG, "malformed ResBlock1 weight name %s", name);
+            const int m = atoi(n.c_str() + (p1 != std::string::npos ? p1 : p2) + 8);
+            GVC_REQUIRE(bi >= 0 && m >= 0 && m < 3, GVC_ERR_ARG, "%s: out of range", name);
+            idx = bi * 6 + 2 * m + (p1 != std::string::npos ? 0 : 1);
+        } else {
+            const size_t pos = n.find(".convs.");
+            GVC_REQUIRE(pos != std::string::npos, GVC_ERR_ARG, "malformed weight name %s", name);
+            const int q = atoi(n.c_str() + pos + 7);
+            GVC_REQUIRE(bi >= 0 && q >= 0 && q < 2, GVC_ERR_ARG, "%s: out of range", name);
+            idx = bi * 2 + q;
+        }
+        GVC_REQUIRE(idx < (int)c->res.size(), GVC_ERR_ARG, "%s: out of range", name);
         rc = hf_bind_conv(c->res[idx], is_bias, src, numel, name, s);
     } else {
         known = false;
@@ -390,6 +429,17 @@ extern "C" int gvc_hifigan_bind_weight(gvc_hifigan* c, const char* name, const f
 }
 
 extern "C" int gvc_hifigan_missing_weights(gvc_hifigan* c) { return c ? c->n_expected - (int)c->bound.size() : -1; }
+
+static bool hf_stage_on_lds(const gvc_hifigan* c, int i);
+
+extern "C" int gvc_hifigan_lds_stages(gvc_hifigan* c) {
+    if (!c) return -1;
+    int n = 0;
+    for (int i = 0; i < (int)c->ups.size(); ++i) n += hf_stage_on_lds(c, i);
+    return n;
+}
+
+extern "C" int gvc_hifigan_graph_nodes(gvc_hifigan* c) { return c ? c->graph_nodes : -1; }
 
 // tiled-GEMM conv: out rows [PAD, PAD+T) = epilogue(conv(lrelu?(src)))
 static int hf_conv_gemm(gvc_hifigan* c, const HfConv& w, const float* src, float* dst, int T, int B, float a_slope,
@@ -411,10 +461,87 @@ static int hf_conv_gemm(gvc_hifigan* c, const HfConv& w, const float* src, float
     return launch_gemm_cap(G, B, c->work_cap, s);
 }
 
+// do the ResBlocks of stage i run on k_conv_lds (one launch per conv position, a plane per block)?  Else: one tiled-GEMM launch per conv
+static bool hf_stage_on_lds(const gvc_hifigan* c, int i) {
+    const int nk = c->dm.n_kernels;
+    if (!c->small_conv || nk != 3) return false;
+    const HfConv* cv = &c->res[(size_t)i * nk * c->nconv];
+    for (int q = 0; q < nk * c->nconv; ++q)
+        if (!cv[q].wp) return false;
+    return true;
+}
+
+// ResBlock1 x 3 of stage i on k_conv_lds, six launches: for m = 0, 1, 2   t_j = convs1[m]_j(lrelu(x_j))  (U or x planes -> R),
+// x_j <- x_j + convs2[m]_j(lrelu(t_j))  (R -> S, S2, S; m = 0 reads x_j = U for every j).  The consumer adds the planes of S and divides.
+static int hf_resblock1_lds(gvc_hifigan* c, int i, int T, int B, hipStream_t s, HfIn* out) {
+    int rc;
+    const int nk = c->dm.n_kernels, ch = c->ups[i].Co;
+    const HfConv* cv = &c->res[(size_t)i * nk * 6];
+    ConvLdsArgs A;
+    memset(&A, 0, sizeof(A));
+    A.x_bs = (long long)(T + 2 * kHfPad) * ch; A.ldx = ch; A.slope = 0.1f; A.x_scale = 1.f;
+    A.x_row0 = kHfPad; A.x_rows = T + 2 * kHfPad; A.stride = 1;
+    A.y_bs = A.x_bs; A.y_ps = c->plane[i]; A.y_off = (long long)kHfPad * ch; A.ldy = ch;
+    A.T = T; A.ntiles = ch / 16;
+    auto launch = [&](int q) {          // conv q of every block: one job per block
+        size_t lds = 0;
+        int kmax = 0;
+        for (int j = 0; j < nk; ++j) {
+            const HfConv& w = cv[6 * j + q];
+            A.job[j].wp = reinterpret_cast<const float4*>(w.wp); A.job[j].b = w.b; A.job[j].k = w.k; A.job[j].dil = w.dil;
+            A.job[j].row_off = -(w.dil * (w.k - 1) / 2);
+            lds = std::max(lds, conv_lds_bytes(ch, w.k, w.dil));
+            kmax = std::max(kmax, w.k);
+        }
+        return conv_lds_k11_ok(ch, kmax) ? launch_conv_lds_k11(ch, A, nk, B, lds, s) : launch_conv_lds(ch, 1, A, nk, B, lds, s);
+    };
+    const float* x = c->U[i];
+    long long x_ps = 0;
+    float* const xo[3] = {c->S[i], c->S2[i], c->S[i]};
+    for (int m = 0; m < 3; ++m) {
+        A.x = x; A.x_ps = x_ps; A.y = c->R[i]; A.resid = nullptr; A.r_ps = 0;
+        if ((rc = launch(2 * m))) return rc;
+        A.x = c->R[i]; A.x_ps = c->plane[i]; A.y = xo[m]; A.resid = x; A.r_ps = x_ps;
+        if ((rc = launch(2 * m + 1))) return rc;
+        x = xo[m]; x_ps = c->plane[i];
+    }
+    *out = HfIn();
+    out->x = c->S[i]; out->nsum = nk; out->ss = c->plane[i]; out->scale = 1.0f / (float)nk;
+    return GVC_OK;
+}
+
+// ResBlock1 of stage i, one tiled-GEMM launch per conv: per block t = convs1[m](lrelu(x)) (-> R plane 0), x = x + convs2[m](lrelu(t))
+// (U -> R plane 1 -> S2 plane 0); the last conv of a block adds the running sum over blocks (planes 0 / 1 of S in turn) and, in the last
+// block, the 1 / n_kernels
+static int hf_resblock1_gemm(gvc_hifigan* c, int i, int T, int B, hipStream_t s, HfIn* out) {
+    int rc;
+    const int nk = c->dm.n_kernels;
+    const HfConv* cv = &c->res[(size_t)i * nk * 6];
+    float* const t = c->R[i];
+    float* const xo[2] = {c->R[i] + c->plane[i], c->S2[i]};
+    float* const acc[2] = {c->S[i], c->S[i] + c->plane[i]};
+    const float* prev = nullptr;
+    for (int j = 0; j < nk; ++j) {
+        const float* x = c->U[i];
+        for (int m = 0; m < 3; ++m) {
+            if ((rc = hf_conv_gemm(c, cv[6 * j + 2 * m], x, t, T, B, 0.1f, nullptr, nullptr, 0.f, s))) return rc;
+            float* dst = m < 2 ? xo[m] : acc[j & 1];
+            if ((rc = hf_conv_gemm(c, cv[6 * j + 2 * m + 1], t, dst, T, B, 0.1f, x, m == 2 ? prev : nullptr,
+                                   m == 2 && j == nk - 1 ? 1.0f / (float)nk : 0.f, s)))
+                return rc;
+            x = dst;
+        }
+        prev = x;
+    }
+    *out = HfIn();
+    out->x = prev;
+    return GVC_OK;
+}
+
 // conv_pre .. last ResBlock; returns what conv_post reads (a buffer, or the ResBlock planes of the last stage) and its length
 static int hf_body(gvc_hifigan* c, int B, int T0, hipStream_t s, HfIn* out, int* T_out) {
     int rc;
-    const gvc_hifigan_dims& D = c->dm;
+    const gvc_hifigan_dims_ex& D = c->dm;
     const int nk = D.n_kernels;
     const HfConv& pc = c->pre;
     const int nsplit = pc.Ci / kPreSlice, pre_tiles = pc.Co / 16;
@@ -465,11 +592,14 @@ static int hf_body(gvc_hifigan* c, int B, int T0, hipStream_t s, HfIn* out, int*
         }
         T = To;
         const int ch = u.Co;
-        const HfConv* cv = &c->res[(size_t)i * nk * 2];
-        bool planes = c->small_conv && nk == 3;
+        const HfConv* cv = &c->res[(size_t)i * nk * c->nconv];
+        bool planes = hf_stage_on_lds(c, i);
+        if (c->type1) {
+            if ((rc = planes ? hf_resblock1_lds(c, i, T, B, s, &in) : hf_resblock1_gemm(c, i, T, B, s, &in))) return rc;
+            continue;
+        }
         size_t lds_a = 0, lds_b = 0;
         for (int j = 0; j < nk && planes; ++j) {
-            planes = cv[2 * j].wp && cv[2 * j + 1].wp;
             lds_a = std::max(lds_a, conv_lds_bytes(ch, cv[2 * j].k, cv[2 * j].dil));
             lds_b = std::max(lds_b, conv_lds_bytes(ch, cv[2 * j + 1].k, cv[2 * j + 1].dil));
         }
@@ -601,6 +731,7 @@ static int hf_run(gvc_hifigan* c, int B, int T0, int head, const float* in, int 
                 if (kp.func == post_fn) { pl.post = nd; pl.post_grid = kp.gridDim; pl.post_block = kp.blockDim; pl.post_lds = kp.sharedMemBytes; }
             }
             GVC_REQUIRE(pl.head && pl.post, GVC_ERR_STATE, "hifigan: the captured graph has no input / output kernel node");
+            c->graph_nodes = (int)nn;
             pl.in[0] = in; pl.wav[0] = wav;
         }
         it = c->graphs.emplace(key, pl).first;
@@ -685,6 +816,7 @@ static int hf_prepare(gvc_hifigan* c, int B, int T0, hipStream_t s) {
             for (int p = 0; p < np; ++p) {
                 GVC_CHECK_HIP(hipMemsetAsync(c->R[i] + (size_t)p * c->plane[i], 0, bytes, s));
                 GVC_CHECK_HIP(hipMemsetAsync(c->S[i] + (size_t)p * c->plane[i], 0, bytes, s));
+                if (c->S2[i]) GVC_CHECK_HIP(hipMemsetAsync(c->S2[i] + (size_t)p * c->plane[i], 0, bytes, s));
             }
         }
         c->cur_T0 = T0; c->cur_B = B;

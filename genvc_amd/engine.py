@@ -1802,14 +1802,23 @@ class HifiganEngine:
 
     def __init__(self, cfg, max_batch=2, max_frames=2560):
         self.cfg = dict(cfg)
-        d = _lib.HifiganDims()
+        # the reference's rule (layers/hifigan.py:181): "1" is ResBlock1, anything else ResBlock2
+        self.resblock_type = 1 if str(cfg.get("resblock_type", "2")) == "1" else 2
+        d = _lib.HifiganDimsEx() if self.resblock_type == 1 else _lib.HifiganDims()
         d.in_dim, d.up_init_ch = cfg["input_feat_dim"], cfg["upsample_initial_channel"]
         d.n_ups, d.n_kernels = len(cfg["upsample_rates"]), len(cfg["resblock_kernel_sizes"])
         for i, (r, k) in enumerate(zip(cfg["upsample_rates"], cfg["upsample_kernel_sizes"])):
             d.up_rates[i], d.up_kernels[i] = r, k
         for j, (k, dl) in enumerate(zip(cfg["resblock_kernel_sizes"], cfg["resblock_dilation_sizes"])):
             d.res_kernels[j] = k
-            d.res_dilations[j][0], d.res_dilations[j][1] = dl
+            if self.resblock_type == 1:
+                if len(dl) != 3:
+                    raise ValueError(f"HiFi-GAN ResBlock1 takes 3 dilations per kernel, got {list(dl)}")
+                d.res_dilations[j][0], d.res_dilations[j][1], d.res_dilations[j][2] = dl
+            else:
+                d.res_dilations[j][0], d.res_dilations[j][1] = dl
+        if self.resblock_type == 1:
+            d.resblock_type = 1
         d.max_batch, d.max_frames = max_batch, max_frames
         self.max_frames = max_frames
         self.total_up = 1
@@ -1817,7 +1826,20 @@ class HifiganEngine:
             self.total_up *= r
         self.in_dim = cfg["input_feat_dim"]
         self._h = C.c_void_p()
-        check(lib().gvc_hifigan_create(C.byref(d), C.byref(self._h)), "gvc_hifigan_create")
+        if self.resblock_type == 1:
+            check(lib().gvc_hifigan_create_ex(C.byref(d), C.byref(self._h)), "gvc_hifigan_create_ex")
+        else:
+            check(lib().gvc_hifigan_create(C.byref(d), C.byref(self._h)), "gvc_hifigan_create")
+
+    @property
+    def lds_stages(self):
+        """upsampling stages whose ResBlocks run on the one-round-trip conv kernel (the rest: one tiled-GEMM launch per conv)"""
+        return lib().gvc_hifigan_lds_stages(self._h)
+
+    @property
+    def graph_nodes(self):
+        """nodes of the most recently captured whole-call graph (its launches: input staging .. conv_post)"""
+        return lib().gvc_hifigan_graph_nodes(self._h)
 
     def close(self):
         if self._h:

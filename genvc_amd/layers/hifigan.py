@@ -1,6 +1,7 @@
 """HiFi-GAN generator with the reference's constructor and `forward(x[B,d,T]) -> [B,1,256T]`
 (/root/reference/layers/hifigan.py:160-233) on libgenvc_hip (gvc_hifigan_forward).  Holds the
-weight-norm parametrised tensors under the reference's names (conv_pre.weight_g/_v, ups.{i}.*, resblocks.*).
+weight-norm parametrised tensors under the reference's names (conv_pre.weight_g/_v, ups.{i}.*, resblocks.*), with either residual
+block: ResBlock2 (resblocks.{i}.convs.{0,1}) or, for resblock_type "1", ResBlock1 (resblocks.{i}.convs1.{m} / convs2.{m}, :28-117).
 
 MultiScaleDiscriminator and MultiPeriodDiscriminator (:247-426) in eval mode on gvc_disc_forward; the STFT and CQT
 discriminators (:429-) are not served."""
@@ -26,12 +27,16 @@ class HiFiGAN(nn.Module):
     def __init__(self, input_feat_dim, upsample_initial_channel, resblock_kernel_sizes, resblock_dilation_sizes,
                  upsample_rates, upsample_kernel_sizes, resblock_type="1"):
         super().__init__()
-        if str(resblock_type) != "2":
-            raise NotImplementedError("GenVC's vocoder uses ResBlock2 (configs/vocoder_configs.py:20)")
+        # the reference's rule (:181): "1" is ResBlock1 (convs1 / convs2, three dilations per kernel), anything else ResBlock2
+        type1 = str(resblock_type) == "1"
+        for d in resblock_dilation_sizes:
+            if len(d) != (3 if type1 else 2):
+                raise ValueError(f"HiFiGAN: ResBlock{1 if type1 else 2} takes {3 if type1 else 2} dilations per kernel, got {list(d)}")
         self.cfg = dict(input_feat_dim=input_feat_dim, upsample_initial_channel=upsample_initial_channel,
                         resblock_kernel_sizes=list(resblock_kernel_sizes),
                         resblock_dilation_sizes=[list(d) for d in resblock_dilation_sizes],
-                        upsample_rates=list(upsample_rates), upsample_kernel_sizes=list(upsample_kernel_sizes))
+                        upsample_rates=list(upsample_rates), upsample_kernel_sizes=list(upsample_kernel_sizes),
+                        resblock_type="1" if type1 else "2")
         ch = upsample_initial_channel
         self.conv_pre = _wn((ch, input_feat_dim, 7), ch)
         self.ups = nn.ModuleList()
@@ -41,7 +46,11 @@ class HiFiGAN(nn.Module):
             ch //= 2
             for kk in resblock_kernel_sizes:
                 rb = _Holder()
-                rb.convs = nn.ModuleList([_wn((ch, ch, kk), ch), _wn((ch, ch, kk), ch)])
+                if type1:
+                    rb.convs1 = nn.ModuleList([_wn((ch, ch, kk), ch) for _ in range(3)])
+                    rb.convs2 = nn.ModuleList([_wn((ch, ch, kk), ch) for _ in range(3)])
+                else:
+                    rb.convs = nn.ModuleList([_wn((ch, ch, kk), ch), _wn((ch, ch, kk), ch)])
                 self.resblocks.append(rb)
         self.conv_post = _wn((1, ch, 7), 1)
         self._engine = None
@@ -58,11 +67,13 @@ class HiFiGAN(nn.Module):
     def receptive_frames(self):
         """input frames on either side that can reach one output sample (reference hifigan.py:119-157,218-233: conv_pre k = 7, per
         stage a transposed conv of kernel k_up at the stage's output rate and ResBlock2s whose two dilated convs reach
-        (k - 1) / 2 * d samples each; conv_post k = 7): 11.5 frames for the trained configuration"""
+        (k - 1) / 2 * d samples each; conv_post k = 7): 10.66 frames for the trained configuration.  A ResBlock1 (:28-117) follows each
+        dilated conv with one of dilation 1: (k - 1) / 2 * d + (k - 1) / 2 per dilation"""
         rf, cum = 3.0, 1.0
+        own = 1 if self.cfg["resblock_type"] == "1" else 0          # the dilation-1 conv behind every dilated one
         for r, ku in zip(self.cfg["upsample_rates"], self.cfg["upsample_kernel_sizes"]):
             cum *= r
-            reach = max(sum((k - 1) // 2 * d for d in ds) for k, ds in zip(self.cfg["resblock_kernel_sizes"], self.cfg["resblock_dilation_sizes"]))
+            reach = max(sum((k - 1) // 2 * (d + own) for d in ds) for k, ds in zip(self.cfg["resblock_kernel_sizes"], self.cfg["resblock_dilation_sizes"]))
             rf += (ku / 2.0 + reach) / cum
         return rf + 3.0 / cum
 

@@ -169,8 +169,11 @@ def dvae_full_weight_spec(cfg, prefix="", codebook_scale=1.0):
 
 def hifigan_weight_spec(cfg, prefix=""):
     """HiFi-GAN generator with weight-norm parametrisation, named as the reference state dict
-    (reference layers/hifigan.py:160-216): conv_pre, ups.{i}, resblocks.{i*nk+j}.convs.{0,1}, conv_post."""
+    (reference layers/hifigan.py:160-216): conv_pre, ups.{i}, resblocks.{i*nk+j}.convs.{0,1}, conv_post.  With
+    cfg["resblock_type"] == "1" the blocks are ResBlock1s: resblocks.{i*nk+j}.convs1.{m} and .convs2.{m}, m < 3, and the upsampling
+    gain is 1 instead of 2 (a ResBlock1 adds three branches to its input; at gain 2 the tanh of a two-stage generator saturates)."""
     spec = {}
+    type1 = str(cfg.get("resblock_type", "2")) == "1"
     ch = cfg["upsample_initial_channel"]
 
     def wn(name, shape, g_mean):
@@ -181,9 +184,14 @@ def hifigan_weight_spec(cfg, prefix=""):
     wn("conv_pre", (ch, cfg["input_feat_dim"], 7), 1.0)
     nk = len(cfg["resblock_kernel_sizes"])
     for i, (r, k) in enumerate(zip(cfg["upsample_rates"], cfg["upsample_kernel_sizes"])):
-        wn(f"ups.{i}", (ch, ch // 2, k), 2.0)                      # ConvTranspose1d weight [Cin, Cout, k]
+        wn(f"ups.{i}", (ch, ch // 2, k), 1.0 if type1 else 2.0)    # ConvTranspose1d weight [Cin, Cout, k]
         ch //= 2
         for j, kk in enumerate(cfg["resblock_kernel_sizes"]):
+            if type1:
+                for m in range(3):
+                    wn(f"resblocks.{i * nk + j}.convs1.{m}", (ch, ch, kk), 0.5)
+                    wn(f"resblocks.{i * nk + j}.convs2.{m}", (ch, ch, kk), 0.5)
+                continue
             for q in range(2):
                 wn(f"resblocks.{i * nk + j}.convs.{q}", (ch, ch, kk), 0.5)
     wn("conv_post", (1, ch, 7), 1.0)

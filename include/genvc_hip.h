@@ -1184,7 +1184,7 @@ int gvc_vq_argmin(const float* x, const float* embed, int32_t N, int32_t dim, in
 
 /* ------------------------------------------------------------------------------------------
  * HiFi-GAN generator.  Replaces layers/hifigan.py:HiFiGAN.forward (:218-233, ResBlock2
- * :119-157) and, for the latent entry point, the x4 linear interpolation in front of it
+ * :119-157, or ResBlock1 :28-117 through gvc_hifigan_create_ex) and, for the latent entry point, the x4 linear interpolation in front of it
  * (inference/inference_utils.py:81-85, 196-202).
  * ------------------------------------------------------------------------------------------ */
 typedef struct gvc_hifigan gvc_hifigan;
@@ -1200,11 +1200,32 @@ typedef struct gvc_hifigan_dims {
     int32_t max_batch, max_frames; /* capacity: input frames AFTER the interpolation */
 } gvc_hifigan_dims;
 int gvc_hifigan_create(const gvc_hifigan_dims* dims, gvc_hifigan** out);
+/* The generator with either residual block of the reference (layers/hifigan.py:181): resblock_type 1 = ResBlock1 (:28-117, per
+ * dilation d a conv of dilation d and one of dilation 1: the HiFi-GAN V1 generator has kernels 3 / 7 / 11 and dilations 1 / 3 / 5),
+ * 2 = ResBlock2 (only the first two entries of a res_dilations row are read).  gvc_hifigan_create is this call with resblock_type 2.
+ * ResBlock1 stages of 32 / 64 / 128 channels with three kernels of <= 11 taps run as six one-round-trip launches (csrc/conv_lds.h),
+ * every other shape as one tiled-GEMM launch per conv. */
+typedef struct gvc_hifigan_dims_ex {
+    int32_t in_dim, up_init_ch;
+    int32_t n_ups;                /* <= 4 */
+    int32_t up_rates[4], up_kernels[4];
+    int32_t n_kernels;            /* <= 4 */
+    int32_t res_kernels[4];
+    int32_t resblock_type;        /* 1 or 2 */
+    int32_t res_dilations[4][3];  /* ResBlock1: [[1,3,5]] * 3; ResBlock2: [[1,2,-],[2,6,-],[3,12,-]] */
+    int32_t max_batch, max_frames;
+} gvc_hifigan_dims_ex;
+int gvc_hifigan_create_ex(const gvc_hifigan_dims_ex* dims, gvc_hifigan** out);
 int gvc_hifigan_destroy(gvc_hifigan* ctx);
 /* names of the reference state dict with weight-norm folded (w = g * v / |v|, as remove_weight_norm leaves
- * them): "conv_pre.weight", "ups.1.bias", "resblocks.4.convs.0.weight", "conv_post.weight", ... */
+ * them): "conv_pre.weight", "ups.1.bias", "resblocks.4.convs.0.weight", "conv_post.weight", ...; a ResBlock1 context takes
+ * "resblocks.4.convs1.2.weight", "resblocks.4.convs2.2.bias", ... (12 tensors per block) */
 int gvc_hifigan_bind_weight(gvc_hifigan* ctx, const char* name, const float* src, int64_t numel, gvc_stream s);
 int gvc_hifigan_missing_weights(gvc_hifigan* ctx);
+/* how many upsampling stages run their ResBlocks on the one-round-trip kernel (the others: one launch per conv), and the node count
+ * of the most recently captured whole-call graph (0 before the first call) */
+int gvc_hifigan_lds_stages(gvc_hifigan* ctx);
+int gvc_hifigan_graph_nodes(gvc_hifigan* ctx);
 /* x [B,in_dim,T] (reference layout) -> wav [B, T * prod(up_rates)] */
 int gvc_hifigan_forward(gvc_hifigan* ctx, const float* x, int32_t B, int32_t T, float* wav, gvc_stream s);
 /* latents [B,n,in_dim] (as yielded by the generation loop) -> F.interpolate(scale, linear) -> wav

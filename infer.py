@@ -28,6 +28,9 @@ if __name__ == "__main__":
     parser.add_argument("--stream_chunk_size", type=int, default=8)
     parser.add_argument("--synthetic", action="store_true", help="deterministic synthetic weights instead of --model_path")
     parser.add_argument("--tiny", action="store_true", help="with --synthetic: the 2-layer test architecture")
+    parser.add_argument("--vocoder_resblock_type", type=str, default="2", choices=["1", "2"],
+                        help="with --synthetic: the vocoder's residual block (1: ResBlock1 with the HiFi-GAN V1 kernels 3 / 7 / 11 and "
+                             "dilations 1 / 3 / 5; a checkpoint brings its own vocoder_config.resblock_type)")
     parser.add_argument("--save_tokens", type=str, default=None)
     parser.add_argument("--weights", type=str, default="fp32", choices=["fp32", "bf16", "bf16_kv", "bf16_act", "bf16_mfma"],
                         help="GPT weight / KV-cache storage on the GPU (fp32 = the reference's numerics)")
@@ -242,7 +245,8 @@ if __name__ == "__main__":
 
     if args.synthetic:
         from genvc_amd import config as gcfg
-        model, config = model_init_synthetic(gcfg.default_config(tiny=args.tiny, with_acoustic=args.decode_codes_to_mel is not None),
+        model, config = model_init_synthetic(gcfg.default_config(tiny=args.tiny, with_acoustic=args.decode_codes_to_mel is not None,
+                                                                 resblock_type=args.vocoder_resblock_type),
                                              device=args.device, weight_dtype=args.weights)
     else:
         model, config = model_init(args.model_path, args.device, weight_dtype=args.weights)
