@@ -79,6 +79,17 @@ class LogitsPenalties(C.Structure):
     _fields_ = [("presence", C.c_float), ("frequency", C.c_float), ("window", C.c_int32), ("prompt_len", C.c_int32)]
 
 
+WM_LEFTHASH, WM_SELFHASH = 0, 1      # GVC_WM_LEFTHASH, GVC_WM_SELFHASH
+WM_SELFHASH_TOP = 40                 # GVC_WM_SELFHASH_TOP
+WM_MAX_SCORE_LEN = 8192              # gvc_wm_score: codes per row
+
+
+class LogitsWatermark(C.Structure):
+    """gvc_logits_watermark (include/genvc_hip.h): the green-list watermark of one set (24 bytes): a device table, the bias, the
+    scheme and the words of a table row; a null table: off"""
+    _fields_ = [("table", C.c_void_p), ("bias", C.c_float), ("scheme", C.c_int32), ("words", C.c_int32), ("reserved", C.c_int32)]
+
+
 BIAS_MAX_SEQS = 32     # GVC_BIAS_MAX_SEQS
 BIAS_MAX_LEN = 8       # GVC_BIAS_MAX_LEN
 
@@ -289,6 +300,15 @@ _SIGNATURES = {
                                        C.POINTER(RowSampling), C.POINTER(LogitsProcessors), C.POINTER(LogitsWarpers), C.c_int32, c_i32p,
                                        C.POINTER(LogitsBias), C.POINTER(LogitsRas), _P, C.POINTER(LogitsPenalties), C.c_int32, C.c_int32,
                                        C.c_int32, _P, C.c_int32, _P, C.c_int32, _P, _P, C.c_int32, C.c_int32, _P]),
+    "gvc_sample_wm": (C.c_int, [_P, C.c_int32, _P, C.c_int32, _P, _P, C.POINTER(SampleParams), C.POINTER(RowSampling),
+                                C.POINTER(LogitsProcessors), C.POINTER(LogitsWarpers), C.c_int32, c_i32p, C.POINTER(LogitsBias),
+                                C.POINTER(LogitsRas), _P, C.POINTER(LogitsPenalties), C.POINTER(LogitsWatermark), C.c_int32, _P, _P]),
+    "gvc_gpt_generate_wm": (C.c_int, [_P, _P, _P, C.c_int32, C.c_float, _P, C.c_int32, _P, _P, C.POINTER(SampleParams),
+                                      C.POINTER(RowSampling), C.POINTER(LogitsProcessors), C.POINTER(LogitsWarpers), C.c_int32, c_i32p,
+                                      C.POINTER(LogitsBias), C.POINTER(LogitsRas), _P, C.POINTER(LogitsPenalties),
+                                      C.POINTER(LogitsWatermark), C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_int32, _P, _P,
+                                      C.c_int32, C.c_int32, _P]),
+    "gvc_wm_score": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
     "gvc_transition_scores": (C.c_int, [_P, C.c_int64, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "gvc_gpt_verify": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, _P, _P, _P]),
     "gvc_gpt_truncate": (C.c_int, [_P, _P, C.c_int32, _P, _P]),

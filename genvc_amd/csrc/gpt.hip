@@ -196,6 +196,7 @@ struct GenCall {
     gvc_logits_bias bias;                    // sequence bias / bad words / forced EOS of a gvc_gpt_generate_bias call (sc.bias points here)
     gvc_logits_ras ras[kMaxSampleRows];      // RAS entries of a gvc_gpt_generate_ras call, one per set (sc.ras points here)
     gvc_logits_penalties pen[kMaxSampleRows];     // penalty entries of a gvc_gpt_generate_pen call, one per set (sc.pen points here)
+    gvc_logits_watermark wm[kMaxSampleRows];      // watermark entries of a gvc_gpt_generate_wm call, one per set (sc.wm points here)
 };
 
 // Start / end of a gvc_gpt_generate call in ONE launch each (they used to be a memset, k_set_gen_call and two k_stage_rows before the
@@ -2209,6 +2210,7 @@ struct GenOptions {
     const gvc_logits_ras* ras = nullptr;           // n_sets host RAS entries (gvc_gpt_generate_ras), indexed through set_of_row ...
     int32_t* ras_redraws = nullptr;                // ... and the rows' redraw counters (device, nullable)
     const gvc_logits_penalties* pen = nullptr;     // n_sets host penalty entries (gvc_gpt_generate_pen), indexed through set_of_row
+    const gvc_logits_watermark* wm = nullptr;      // n_sets host watermark entries (gvc_gpt_generate_wm), indexed through set_of_row
 };
 
 // the guards gvc_gpt_generate_cfg / _scores / _bias share, under the entry's name (a guided entry counts items, the others rows)
@@ -2232,7 +2234,7 @@ static int generate_impl(gvc_gpt* c, const int32_t* slots, int32_t B, int32_t* i
     const int32_t* uslots = o.uslots;
     // without sets and warpers there is nothing to index; with either, a null index means entry 0 for every row (the entries that allow
     // a null index have bounded B by kMaxSampleRows)
-    const bool any = o.sets || o.warps || o.ras || o.pen;
+    const bool any = o.sets || o.warps || o.ras || o.pen || o.wm;
     const gvc_logits_processors* sets = o.sets;
     const gvc_logits_warpers* warps = o.warps;
     const int n_sets = any ? o.n_sets : 0;
@@ -2252,7 +2254,8 @@ static int generate_impl(gvc_gpt* c, const int32_t* slots, int32_t B, int32_t* i
     if (bias && (rc = check_bias(*bias, c->dm.vocab))) return rc;
     if (o.ras && (rc = check_ras(o.ras, n_sets))) return rc;
     if (o.pen && (rc = check_pen(o.pen, n_sets))) return rc;
-    if (warps || o.ras || o.pen) {
+    if (o.wm && (rc = check_wm(o.wm, n_sets, c->dm.vocab))) return rc;
+    if (warps || o.ras || o.pen || o.wm) {
         if ((rc = check_warp_sets(sets, warps, n_sets, set_of_row, B, c->dm.vocab))) return rc;
     } else if (set_of_row && (rc = check_proc_sets(sets, n_sets, set_of_row, B, c->dm.vocab))) {
         return rc;
@@ -2266,7 +2269,7 @@ static int generate_impl(gvc_gpt* c, const int32_t* slots, int32_t B, int32_t* i
     GenPlan pl;
     // (a keyed call replays the greedy graphs when every row is greedy, the sampling ones otherwise: the step graphs are the same)
     // (a call with a RAS table replays the sampling graphs whatever its top_k: the redraw lives in the full kernel; a penalties
-    // table changes nothing here: both sampler kernels apply it)
+    // table or a watermark table changes nothing here: both sampler kernels apply them)
     if ((rc = plan_generate(c, Brows, key_bound, o.ras ? 0 : (rows ? (rows_greedy ? 1 : 0) : p->top_k), &pl))) return rc;
     GVC_REQUIRE(!uslots || !pl.defer, GVC_ERR_STATE, "generate_cfg: the one-stream step cannot serve %d rows", Brows);
     c->last_variant = pl.variant;
@@ -2305,6 +2308,7 @@ static int generate_impl(gvc_gpt* c, const int32_t* slots, int32_t B, int32_t* i
         if (warps && (rc = launch_stage_warps(c->gen_call->warps, warps, n_sets, s))) return rc;
         if (o.ras && (rc = launch_stage_ras(c->gen_call->ras, o.ras, n_sets, s))) return rc;
         if (o.pen && (rc = launch_stage_pen(c->gen_call->pen, o.pen, n_sets, s))) return rc;
+        if (o.wm && (rc = launch_stage_wm(c->gen_call->wm, o.wm, n_sets, s))) return rc;
         SampleRows sr;
         memset(&sr, 0, sizeof(sr));
         SetIndex si;
@@ -2316,6 +2320,7 @@ static int generate_impl(gvc_gpt* c, const int32_t* slots, int32_t B, int32_t* i
         sc.ras = o.ras ? c->gen_call->ras : nullptr;
         sc.ras_redraws = o.ras ? o.ras_redraws : nullptr;
         sc.pen = o.pen ? c->gen_call->pen : nullptr;
+        sc.wm = o.wm ? c->gen_call->wm : nullptr;
         if (rows) {
             memcpy(sr.r, rows, (size_t)B * sizeof(gvc_row_sampling));
             sc.rows = c->gen_call->rows;
@@ -2491,6 +2496,23 @@ extern "C" int gvc_gpt_generate_pen(gvc_gpt* c, const int32_t* slots, const int3
     o.uslots = uncond_slots; o.scale = scale; o.bias = bias; o.ras = ras; o.ras_redraws = ras_redraws; o.pen = pen;
     o.scores_out = scores_out; o.logits_out = logits_out; o.out_stride = out_stride; o.do_sample = do_sample != 0;
     const int rc = check_guided("generate_pen", c, slots, B, false, o);
+    return rc ? rc : generate_impl(c, slots, B, ids, ids_stride, ids_len, finished, p, i0, n_steps, max_keys, tokens_out, tok_stride,
+                                   latents_out, lat_stride, sv, o);
+}
+
+extern "C" int gvc_gpt_generate_wm(gvc_gpt* c, const int32_t* slots, const int32_t* uncond_slots, int32_t B, float scale, int32_t* ids,
+                                   int32_t ids_stride, int32_t* ids_len, int32_t* finished, const gvc_sample_params* p,
+                                   const gvc_row_sampling* rows, const gvc_logits_processors* sets, const gvc_logits_warpers* warps,
+                                   int32_t n_sets, const int32_t* set_of_row, const gvc_logits_bias* bias, const gvc_logits_ras* ras,
+                                   int32_t* ras_redraws, const gvc_logits_penalties* pen, const gvc_logits_watermark* wm, int32_t i0,
+                                   int32_t n_steps, int32_t max_keys, int32_t* tokens_out, int32_t tok_stride, float* latents_out,
+                                   int32_t lat_stride, float* scores_out, float* logits_out, int32_t out_stride, int32_t do_sample,
+                                   gvc_stream sv) {
+    GenOptions o;
+    o.rows = rows; o.sets = sets; o.warps = warps; o.n_sets = n_sets; o.set_of_row = set_of_row;
+    o.uslots = uncond_slots; o.scale = scale; o.bias = bias; o.ras = ras; o.ras_redraws = ras_redraws; o.pen = pen; o.wm = wm;
+    o.scores_out = scores_out; o.logits_out = logits_out; o.out_stride = out_stride; o.do_sample = do_sample != 0;
+    const int rc = check_guided("generate_wm", c, slots, B, false, o);
     return rc ? rc : generate_impl(c, slots, B, ids, ids_stride, ids_len, finished, p, i0, n_steps, max_keys, tokens_out, tok_stride,
                                    latents_out, lat_stride, sv, o);
 }

@@ -187,6 +187,7 @@ __device__ __forceinline__ void sample_row(const SampleCall& C, int b, const flo
     __shared__ float wscr[32];
     __shared__ uint32_t kill[kProcWords];
     __shared__ BiasHits bh;
+    __shared__ uint32_t wmg[kProcWords];          // this step's green list of a gvc_logits_watermark row (touched only by such a row)
     const int tid = threadIdx.x;
     const int V = C.p.vocab;
     // processor settings and RNG key of this row (uniform over the workgroup: one workgroup = one row)
@@ -210,6 +211,11 @@ __device__ __forceinline__ void sample_row(const SampleCall& C, int b, const flo
     if (P) ps = proc_row_begin(*P, len, P->prompt_lens ? P->prompt_lens[b] : P->prompt_len, C.p.eos_token, kill, tid, force);
     else if (Z && tid < kProcWords) kill[tid] = 0u;
     if (Z && tid < 64) bias_match(*Z, ids, len, &bh, tid);
+    // green-list watermark of the row (uniform; off: `wmg` is neither written nor read): the 33 words of this step's list, one
+    // coalesced read by the first lanes, visible behind the barrier below.  The warp-only kernel never sees a table
+    WmRow M{false, false, nullptr, 0, 0.f};
+    if constexpr (!kWarpOnly) M = wm_row(C, b, ids, len);
+    if (M.on && tid < M.words) wmg[tid] = M.row[tid];
     __syncthreads();
     for (int i = tid; i < len; i += kSampThreads) {
         const int id = ids[i];
@@ -244,9 +250,12 @@ __device__ __forceinline__ void sample_row(const SampleCall& C, int b, const flo
     float rmx;          // the largest entry of sc (the redraw of a gvc_logits_ras row takes its weights relative to it)
     if (top_k == 1) {
         // exactly one candidate survives TopK(1): argmax of the penalised scores, first index on ties
+        // (a watermarked row: of the scores with the bias on the green ids, one fp32 add each -- greedy search with the mark)
         float bv = -INFINITY; int bi = 0x7fffffff;
-        for (int i = tid; i < V; i += kSampThreads)
-            if (sc[i] > bv || (sc[i] == bv && i < bi)) { bv = sc[i]; bi = i; }
+        for (int i = tid; i < V; i += kSampThreads) {
+            const float x = M.on && wm_green(wmg, i) ? __fadd_rn(sc[i], M.bias) : sc[i];
+            if (x > bv || (x == bv && i < bi)) { bv = x; bi = i; }
+        }
         for (int off = 32; off > 0; off >>= 1) {
             const float ov = __shfl_xor(bv, off);
             const int oi = __shfl_xor(bi, off);
@@ -265,8 +274,11 @@ __device__ __forceinline__ void sample_row(const SampleCall& C, int b, const flo
         if (so) {
             if (C.scores_warped) {
                 // TopK(1): the entries that equal the maximum stay (HF keeps ties), at their temperature-scaled score
-                const float top = sc[tok];
-                for (int i = tid; i < V; i += kSampThreads) so[i] = sc[i] >= top ? sc[i] : -INFINITY;
+                const float top = M.on && wm_green(wmg, tok) ? __fadd_rn(sc[tok], M.bias) : sc[tok];
+                for (int i = tid; i < V; i += kSampThreads) {
+                    const float x = M.on && wm_green(wmg, i) ? __fadd_rn(sc[i], M.bias) : sc[i];
+                    so[i] = x >= top ? x : -INFINITY;
+                }
             } else {
                 // greedy search has no Temperature: the row as it stood before the division above
                 for (int i = tid; i < V; i += kSampThreads) {
@@ -275,6 +287,7 @@ __device__ __forceinline__ void sample_row(const SampleCall& C, int b, const flo
                     if (Q.windowed ? c > 0 : seen[i]) v = v < 0.f ? v * rep_pen : v / rep_pen;
                     if (c > 0) v = pen_score(v, c, Q);
                     if (pr) v = proc_score(v, i, C.p.eos_token, ps, kill);
+                    if (M.on && wm_green(wmg, i)) v = __fadd_rn(v, M.bias);          // (the mark is a processor: the biased row)
                     so[i] = v;
                 }
             }
@@ -361,9 +374,21 @@ __device__ __forceinline__ void sample_row(const SampleCall& C, int b, const flo
             const gvc_logits_warpers* W = row_warps(C, b);
             if (W && (W->typical_p > 0.f || W->epsilon_cutoff > 0.f || W->eta_cutoff > 0.f))
                 dmx = apply_warpers(*W, i0v < V ? sc[i0v] : -INFINITY, i1v < V ? sc[i1v] : -INFINITY, k0, k1, mx, wscr);
+            // Green-list watermark, behind the last warper (transformers appends it there): the survivors that are green gain the
+            // bias, one fp32 add; under selfhash only those among the GVC_WM_SELFHASH_TOP highest scores of the row (the survivors of
+            // TopK / TopP / MinP / epsilon / eta lead the sorted order, so srt[39] is that threshold; ties at it keep more).  The draw
+            // takes its weights relative to the largest biased survivor: one more workgroup maximum.  Off: b0 / b1 are the scores
+            // the lines below read where k0 / k1 hold and nothing else runs
+            float b0 = i0v < V ? sc[i0v] : -INFINITY, b1 = i1v < V ? sc[i1v] : -INFINITY;
+            if (M.on) {
+                const float t40 = M.self ? srt[GVC_WM_SELFHASH_TOP - 1] : -INFINITY;
+                if (k0 && b0 >= t40 && wm_green(wmg, i0v)) b0 = __fadd_rn(b0, M.bias);
+                if (k1 && b1 >= t40 && wm_green(wmg, i1v)) b1 = __fadd_rn(b1, M.bias);
+                dmx = block_max(fmaxf(k0 ? b0 : -INFINITY, k1 ? b1 : -INFINITY), wscr);
+            }
             if (so) {
                 // what survives the last warper keeps its temperature-scaled score, not renormalised; thread t stores its pair
-                const float o0 = k0 ? sc[i0v] : -INFINITY, o1 = k1 ? sc[i1v] : -INFINITY;
+                const float o0 = k0 ? b0 : -INFINITY, o1 = k1 ? b1 : -INFINITY;
                 if (i1v < V && (reinterpret_cast<uintptr_t>(so) & 7) == 0) {
                     *reinterpret_cast<float2*>(so + i0v) = make_float2(o0, o1);
                 } else {
@@ -372,7 +397,7 @@ __device__ __forceinline__ void sample_row(const SampleCall& C, int b, const flo
                 }
             }
             if constexpr (kWarpOnly) return;          // (uniform: every thread is past the last barrier of the chain)
-            const double w0 = k0 ? (double)expf(sc[i0v] - dmx) : 0.0, w1 = k1 ? (double)expf(sc[i1v] - dmx) : 0.0;
+            const double w0 = k0 ? (double)expf(b0 - dmx) : 0.0, w1 = k1 ? (double)expf(b1 - dmx) : 0.0;
             double total;
             const double ex = block_scan_excl<double>(w0 + w1, dscr, &total);
             // the RNG counter is the position of the step in the whole run of the stream (i0 + step, or rng_step0 + step of a keyed

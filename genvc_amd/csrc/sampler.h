@@ -6,6 +6,7 @@
 
 #include "common.h"
 #include "logits_proc.h"
+#include "watermark.h"
 
 namespace gvc {
 
@@ -70,6 +71,10 @@ struct SampleCall {
     // per set, indexed like warps and ras.  Null, or an entry with everything off: none, and both kernels compute exactly what they
     // compute without this field, through the same barriers and with no more LDS traffic
     const gvc_logits_penalties* pen;
+    // nullable: green-list watermark entries (gvc_*_wm calls: gvc_logits_watermark, device memory, each pointing at a device table), one
+    // entry per set, indexed like warps, ras and pen.  Null, or an entry with a null table: none, and both kernels compute exactly what
+    // they compute without this field, through the same barriers and with no more LDS traffic
+    const gvc_logits_watermark* wm;
 };
 
 // row b's entry of a per-step output buffer at this step (see SampleCall::scores_out)
@@ -130,6 +135,40 @@ __device__ __forceinline__ PenRow pen_row(const SampleCall& C, int b, int len) {
 __device__ __forceinline__ float pen_score(float v, int c, const PenRow& q) {
     return __fsub_rn(v, __fadd_rn(__fmul_rn(q.frequency, (float)c), q.presence));
 }
+
+// What a row's watermark comes to at one step (uniform over the row's workgroup): the table row to stage in LDS and the settings in
+// registers.  on == false (no table, no entry, a null table, or a previous id outside the vocabulary): nothing below is read and the
+// kernels run as without a table
+struct WmRow {
+    bool on, self;              // self: selfhash (one row; sampling biases only the green ids among the GVC_WM_SELFHASH_TOP highest scores)
+    const uint32_t* row;        // the `words` words of this step's green list (device)
+    int words;
+    float bias;
+};
+__device__ __forceinline__ WmRow wm_row(const SampleCall& C, int b, const int32_t* ids, int len) {
+    WmRow w{false, false, nullptr, 0, 0.f};
+    if (!C.wm) return w;
+    const int k = C.set_of_row ? C.set_of_row[b] : 0;
+    if (k < 0) return w;
+    const gvc_logits_watermark& M = C.wm[k];
+    if (!M.table) return w;
+    w.self = M.scheme == GVC_WM_SELFHASH;
+    w.words = min(max(M.words, 0), kProcWords);          // (checked on the host: ceil(vocab / 32) <= kProcWords)
+    w.bias = M.bias;
+    if (w.self) {
+        w.row = M.table;
+        w.on = true;
+    } else if (len >= 1) {
+        const int prev = ids[len - 1];
+        if (prev >= 0 && prev < C.p.vocab) {
+            w.row = M.table + (size_t)prev * w.words;
+            w.on = true;
+        }
+    }
+    return w;
+}
+// whether id i is green in the staged row g (LDS)
+__device__ __forceinline__ bool wm_green(const uint32_t* g, int i) { return (g[i >> 5] >> (i & 31)) & 1u; }
 
 // a call with a RAS table runs on k_sample whatever its top_k: the redraw reads the full row the greedy kernel never stores
 int launch_sample(const SampleCall& sc, hipStream_t s);
@@ -195,6 +234,16 @@ struct PenTable {
 int check_pen(const gvc_logits_penalties* pen, int n_sets);
 // pen[0..n_sets) -> dst[0..n_sets) on stream s (one small launch)
 int launch_stage_pen(gvc_logits_penalties* dst, const gvc_logits_penalties* pen, int n_sets, hipStream_t s);
+// watermark entries of a gvc_*_wm call, all n_sets of them BY VALUE in one launch (1.5 KB of kernel argument)
+struct WmTable {
+    gvc_logits_watermark m[kMaxSampleRows];
+    int32_t n;
+};
+// host-side checks of a watermark table: 1 <= n_sets <= 64; of every entry with a table: bias finite, scheme 0 / 1, words == ceil(vocab / 32) <= kProcWords,
+// reserved == 0 (watermark.h: wm_entry_ok is the per-entry part)
+int check_wm(const gvc_logits_watermark* wm, int n_sets, int vocab);
+// wm[0..n_sets) -> dst[0..n_sets) on stream s (one small launch)
+int launch_stage_wm(gvc_logits_watermark* dst, const gvc_logits_watermark* wm, int n_sets, hipStream_t s);
 // *bias -> *dst on stream s, BY VALUE in one small launch (1.3 KB of kernel argument); check_bias (logits_proc.h) comes first
 int launch_stage_bias(gvc_logits_bias* dst, const gvc_logits_bias* bias, hipStream_t s);
 

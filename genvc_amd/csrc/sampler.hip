@@ -25,6 +25,7 @@ __global__ __launch_bounds__(kGreedyThreads) void k_sample_greedy(SampleCall cv,
     __shared__ uint32_t kill[kProcWords];
     __shared__ BiasHits bh;
     __shared__ float rscr[32];
+    __shared__ uint32_t wmg[kProcWords];             // this step's green list of a gvc_logits_watermark row (touched only by such a row)
     unsigned char* seen = reinterpret_cast<unsigned char*>(seen_w);
     const SampleCall& C = cp ? *cp : cv;
     const int b = blockIdx.x, tid = threadIdx.x;
@@ -54,6 +55,9 @@ __global__ __launch_bounds__(kGreedyThreads) void k_sample_greedy(SampleCall cv,
     if (P) ps = proc_row_begin(*P, len, P->prompt_lens ? P->prompt_lens[b] : P->prompt_len, C.p.eos_token, kill, tid, force);
     else if (Z && tid < kProcWords) kill[tid] = 0u;
     if (Z && tid < 64) bias_match(*Z, ids, len, &bh, tid);
+    // green-list watermark of the row, as in k_sample (off: `wmg` is neither written nor read): greedy search with the mark
+    const WmRow M = wm_row(C, b, ids, len);
+    if (M.on && tid < M.words) wmg[tid] = M.row[tid];
     __syncthreads();
     for (int i = tid; i < len; i += kGreedyThreads) {
         const int id = ids[i];
@@ -78,8 +82,10 @@ __global__ __launch_bounds__(kGreedyThreads) void k_sample_greedy(SampleCall cv,
             if (Q.windowed ? c > 0 : seen[i]) x = x < 0.f ? x * rep_pen : x / rep_pen;
             if (c > 0) x = pen_score(x, c, Q);
             if (pr) x = proc_score(x, i, C.p.eos_token, ps, kill);
-            if (so) so[i] = x;                // greedy search: the processed row, no Temperature
+            const bool green = M.on && wm_green(wmg, i);
+            if (so) so[i] = green ? __fadd_rn(x, M.bias) : x;                // greedy search: the processed row, no Temperature
             x = x / temp;
+            if (green) x = __fadd_rn(x, M.bias);
             if (x > bv || (x == bv && i < bi)) { bv = x; bi = i; }
         }
     }
@@ -123,6 +129,7 @@ __global__ __launch_bounds__(kGreedyThreads) void k_sample_greedy(SampleCall cv,
                 if (c > 0) x = pen_score(x, c, Q);
                 if (pr) x = proc_score(x, i, C.p.eos_token, ps, kill);
                 x = x / temp;
+                if (M.on && wm_green(wmg, i)) x = __fadd_rn(x, M.bias);
                 sw[i] = x >= top ? x : -INFINITY;
             }
         }
@@ -170,6 +177,10 @@ __global__ void k_stage_ras(gvc_logits_ras* dst, RasTable t) {
 
 __global__ void k_stage_pen(gvc_logits_penalties* dst, PenTable t) {
     if ((int)threadIdx.x < t.n) dst[threadIdx.x] = t.q[threadIdx.x];
+}
+
+__global__ void k_stage_wm(gvc_logits_watermark* dst, WmTable t) {
+    if ((int)threadIdx.x < t.n) dst[threadIdx.x] = t.m[threadIdx.x];
 }
 
 __global__ void k_stage_bias(gvc_logits_bias* dst, gvc_logits_bias src) {
@@ -379,6 +390,29 @@ int launch_stage_pen(gvc_logits_penalties* dst, const gvc_logits_penalties* pen,
     return GVC_OK;
 }
 
+int check_wm(const gvc_logits_watermark* wm, int n_sets, int vocab) {
+    GVC_REQUIRE(wm && n_sets >= 1 && n_sets <= kMaxSampleRows, GVC_ERR_ARG, "watermark: need 1..%d entries, got %d", kMaxSampleRows,
+                n_sets);
+    for (int k = 0; k < n_sets; ++k) {
+        const gvc_logits_watermark& m = wm[k];
+        if (!m.table) continue;          // (an off entry: its other fields are not read)
+        GVC_REQUIRE(wm_entry_ok(m.bias, m.scheme, m.words, m.reserved, vocab, kProcWords), GVC_ERR_ARG,
+                    "watermark: entry %d has bias %g (finite), scheme %d (0 / 1), words %d (ceil(%d / 32), at most %d), reserved %d (0)", k,
+                    (double)m.bias, m.scheme, m.words, vocab, kProcWords, m.reserved);
+    }
+    return GVC_OK;
+}
+
+int launch_stage_wm(gvc_logits_watermark* dst, const gvc_logits_watermark* wm, int n_sets, hipStream_t s) {
+    WmTable t;
+    memset(&t, 0, sizeof(t));
+    memcpy(t.m, wm, (size_t)n_sets * sizeof(gvc_logits_watermark));
+    t.n = n_sets;
+    hipLaunchKernelGGL(k_stage_wm, dim3(1), dim3(kMaxSampleRows), 0, s, dst, t);
+    GVC_LAUNCH_CHECK();
+    return GVC_OK;
+}
+
 int launch_sample(const SampleCall& sc, hipStream_t s) {
     GVC_REQUIRE(sc.p.vocab > 0 && sc.p.vocab <= kSortN, GVC_ERR_UNSUPPORTED, "sample: vocab %d > %d", sc.p.vocab, kSortN);
     if (!sc.ras && sample_greedy_ok(sc.p.top_k, sc.latents_out ? sc.d : 0)) hipLaunchKernelGGL(k_sample_greedy, dim3(sc.B), dim3(kGreedyThreads), 0, s, sc, (const SampleCall*)nullptr);
@@ -415,6 +449,7 @@ struct SampleOptions {
     const gvc_logits_ras* ras = nullptr;          // n_sets RAS entries (gvc_sample_ras) ...
     int32_t* ras_redraws = nullptr;               // ... and the rows' redraw counters (device)
     const gvc_logits_penalties* pen = nullptr;    // n_sets penalty entries (gvc_sample_pen)
+    const gvc_logits_watermark* wm = nullptr;     // n_sets watermark entries (gvc_sample_wm)
 };
 
 static int sample_once(const float* logits, int B, int32_t* ids, int ids_stride, int32_t* ids_len, int32_t* finished,
@@ -429,8 +464,11 @@ static int sample_once(const float* logits, int B, int32_t* ids, int ids_stride,
     const size_t sor_bytes = (size_t)B * sizeof(int32_t);          // (always there: the allocation is never empty)
     const size_t ras_bytes = o.ras ? (size_t)o.n_sets * sizeof(gvc_logits_ras) : 0;
     const size_t pen_bytes = o.pen ? (size_t)o.n_sets * sizeof(gvc_logits_penalties) : 0;
+    // (8-byte entries -- a pointer each -- behind 4-byte ones: the carve below rounds their offset up)
+    const size_t wm_bytes = o.wm ? (size_t)o.n_sets * sizeof(gvc_logits_watermark) + 8 : 0;
     char* d = nullptr;
-    GVC_CHECK_HIP(hipMallocAsync((void**)&d, bias_bytes + proc_bytes + set_bytes + warp_bytes + row_bytes + sor_bytes + ras_bytes + pen_bytes,
+    GVC_CHECK_HIP(hipMallocAsync((void**)&d, bias_bytes + proc_bytes + set_bytes + warp_bytes + row_bytes + sor_bytes + ras_bytes + pen_bytes +
+                                     wm_bytes,
                                  s));
     char* at = d;
     auto carve = [&at](size_t bytes) { char* q = bytes ? at : nullptr; at += bytes; return q; };
@@ -442,6 +480,8 @@ static int sample_once(const float* logits, int B, int32_t* ids, int ids_stride,
     int32_t* d_sor = reinterpret_cast<int32_t*>(carve(sor_bytes));
     gvc_logits_ras* d_ras = reinterpret_cast<gvc_logits_ras*>(carve(ras_bytes));
     gvc_logits_penalties* d_pen = reinterpret_cast<gvc_logits_penalties*>(carve(pen_bytes));
+    gvc_logits_watermark* d_wm = nullptr;
+    if (o.wm) d_wm = reinterpret_cast<gvc_logits_watermark*>(d + (((size_t)(carve(wm_bytes) - d) + 7) & ~(size_t)7));
     int rc = GVC_OK;
     if (o.bias) rc = launch_stage_bias(d_bias, o.bias, s);
     if (rc == GVC_OK && o.proc) rc = launch_stage_proc(d_proc, o.proc, s);
@@ -451,6 +491,7 @@ static int sample_once(const float* logits, int B, int32_t* ids, int ids_stride,
     if (rc == GVC_OK && o.rows) rc = launch_stage_rows(d_rows, o.rows, B, s);
     if (rc == GVC_OK && o.ras) rc = launch_stage_ras(d_ras, o.ras, o.n_sets, s);
     if (rc == GVC_OK && o.pen) rc = launch_stage_pen(d_pen, o.pen, o.n_sets, s);
+    if (rc == GVC_OK && o.wm) rc = launch_stage_wm(d_wm, o.wm, o.n_sets, s);
     if (rc == GVC_OK) {
         SampleCall sc;
         memset(&sc, 0, sizeof(sc));
@@ -459,6 +500,7 @@ static int sample_once(const float* logits, int B, int32_t* ids, int ids_stride,
         sc.proc_sets = d_sets; sc.set_of_row = o.index ? d_sor : nullptr; sc.warps = d_warps; sc.bias = d_bias;
         sc.ras = d_ras; sc.ras_redraws = o.ras ? o.ras_redraws : nullptr;
         sc.pen = d_pen;
+        sc.wm = d_wm;
         if (o.rows) sc.p.top_k = o.greedy ? 1 : 0;          // (kernel choice only: every row's settings come from d_rows)
         rc = launch_sample(sc, s);
     }
@@ -582,6 +624,28 @@ extern "C" int gvc_sample_pen(const float* logits, int32_t B, int32_t* ids, int3
     gvc::SampleOptions o;
     o.rows = rows; o.sets = sets; o.warps = warps; o.n_sets = n_sets; o.set_of_row = set_of_row; o.bias = bias; o.index = true;
     o.ras = ras; o.ras_redraws = ras_redraws; o.pen = pen;
+    if (rows && (rc = gvc::check_sample_rows(rows, B, p->vocab, &o.greedy))) return rc;
+    return gvc::sample_once(logits, B, ids, ids_stride, ids_len, finished, *p, step, tok_out, o, (hipStream_t)sv);
+}
+
+extern "C" int gvc_sample_wm(const float* logits, int32_t B, int32_t* ids, int32_t ids_stride, int32_t* ids_len, int32_t* finished,
+                             const gvc_sample_params* p, const gvc_row_sampling* rows, const gvc_logits_processors* sets,
+                             const gvc_logits_warpers* warps, int32_t n_sets, const int32_t* set_of_row, const gvc_logits_bias* bias,
+                             const gvc_logits_ras* ras, int32_t* ras_redraws, const gvc_logits_penalties* pen,
+                             const gvc_logits_watermark* wm, int32_t step, int32_t* tok_out, gvc_stream sv) {
+    if (!wm) return gvc_sample_pen(logits, B, ids, ids_stride, ids_len, finished, p, rows, sets, warps, n_sets, set_of_row, bias, ras, ras_redraws, pen, step, tok_out, sv);
+    GVC_REQUIRE(logits && ids && ids_len && finished && p && tok_out && B >= 1, GVC_ERR_ARG, "gvc_sample_wm: bad argument");
+    GVC_REQUIRE(B <= gvc::kMaxSampleRows, GVC_ERR_ARG, "gvc_sample_wm: need 1..%d rows, got %d", gvc::kMaxSampleRows, B);
+    int rc = gvc::check_wm(wm, n_sets, p->vocab);
+    if (rc) return rc;
+    if (pen && (rc = gvc::check_pen(pen, n_sets))) return rc;
+    if (ras && (rc = gvc::check_ras(ras, n_sets))) return rc;
+    if (bias && (rc = gvc::check_bias(*bias, p->vocab))) return rc;
+    // (check_warp_sets reads neither table when both are null: the bounds of n_sets and of the indices are what is left)
+    if ((rc = gvc::check_warp_sets(sets, warps, n_sets, set_of_row, B, p->vocab))) return rc;
+    gvc::SampleOptions o;
+    o.rows = rows; o.sets = sets; o.warps = warps; o.n_sets = n_sets; o.set_of_row = set_of_row; o.bias = bias; o.index = true;
+    o.ras = ras; o.ras_redraws = ras_redraws; o.pen = pen; o.wm = wm;
     if (rows && (rc = gvc::check_sample_rows(rows, B, p->vocab, &o.greedy))) return rc;
     return gvc::sample_once(logits, B, ids, ids_stride, ids_len, finished, *p, step, tok_out, o, (hipStream_t)sv);
 }

@@ -1,5 +1,6 @@
 """Thin Python owners of the libgenvc_hip contexts.  torch supplies device memory and the stream;
 all arithmetic runs in the HIP library."""
+import collections
 import ctypes as C
 import math
 
@@ -259,6 +260,196 @@ class PenaltyTable:
         self.pen = (_lib.LogitsPenalties * self.n)(*[_lib.LogitsPenalties() if q is None else q for q in entries])
 
 
+# The green-list watermark (Kirchenbauer et al.; transformers' `watermarking_config` of generate and its WatermarkDetector; include/
+# genvc_hip.h: gvc_logits_watermark).  The kwarg is HF's; its value a dict with HF's keys, or an object with to_dict().
+# key -> table is DEFINED by the CPU torch.Generator (a CUDA generator gives other permutations): what this produces, and what the
+# detector accepts, is what transformers' processor / detector built with device="cpu" produce and accept.
+WATERMARK_KWARGS = ("watermarking_config",)
+WATERMARK_KEYS = ("greenlist_ratio", "bias", "hashing_key", "seeding_scheme", "context_width")
+WATERMARK_SCHEMES = {"lefthash": _lib.WM_LEFTHASH, "selfhash": _lib.WM_SELFHASH}
+MAX_WATERMARK_TABLES = 8          # device-resident tables of one GptEngine
+WatermarkSettings = collections.namedtuple("WatermarkSettings", WATERMARK_KEYS)
+_WM_DEFAULTS = dict(greenlist_ratio=0.25, bias=2.0, hashing_key=15485863, seeding_scheme="lefthash", context_width=1)
+_WM_FIXED_TABLE = 1_000_003       # transformers' table_size of the selfhash scheme
+_wm_tables = {}                   # (key, ratio, scheme, V) -> the host table, built once per process
+
+
+def watermark_settings(kw, vocab):
+    """kw["watermarking_config"] of one call -> WatermarkSettings, or None when it is absent or None (off: the call passes no table).
+    ValueError: a value that is neither a dict nor has to_dict(), an unknown key, an unknown seeding_scheme, a greenlist_ratio outside
+    (0, 1) or so small that int(vocab * ratio) == 0, a non-finite bias, a hashing_key that is no integer in [0, 2**63), a bool anywhere.
+    NotImplementedError: context_width != 1 (lefthash: the width changes nothing in generation; selfhash: width 2 needs vocab ** 2
+    permutations on the host)."""
+    cfg = (kw or {}).get("watermarking_config")
+    if cfg is None:
+        return None
+    if not isinstance(cfg, dict):
+        if isinstance(cfg, bool) or not callable(getattr(cfg, "to_dict", None)):
+            raise ValueError(f"watermarking_config must be a dict, an object with to_dict() or None, not {cfg!r}")
+        cfg = cfg.to_dict()
+    unknown = sorted(set(cfg) - set(WATERMARK_KEYS), key=str)
+    if unknown:
+        raise ValueError(f"watermarking_config: {unknown[0]!r} is not one of its keys ({', '.join(WATERMARK_KEYS)})")
+    v = dict(_WM_DEFAULTS, **{k: x for k, x in cfg.items() if x is not None})
+    for k, x in v.items():
+        if isinstance(x, bool):
+            raise ValueError(f"watermarking_config: {k} must not be a bool ({x!r})")
+    if v["seeding_scheme"] not in WATERMARK_SCHEMES:
+        raise ValueError(f"watermarking_config: seeding_scheme has to be one of ['selfhash', 'lefthash'], not {v['seeding_scheme']!r}")
+    r = v["greenlist_ratio"]
+    if not isinstance(r, (int, float)) or not 0.0 < r < 1.0:          # (a NaN fails both comparisons)
+        raise ValueError(f"watermarking_config: greenlist_ratio has to lie between 0.0 and 1.0, exclusively, not {r!r}")
+    if int(vocab * r) == 0:
+        raise ValueError(f"watermarking_config: greenlist_ratio {r!r} leaves no green id among {vocab}")
+    if not isinstance(v["bias"], (int, float)) or not math.isfinite(v["bias"]):
+        raise ValueError(f"watermarking_config: bias must be a finite number, not {v['bias']!r}")
+    key = v["hashing_key"]
+    if not isinstance(key, int) or not 0 <= key < 2 ** 63:
+        raise ValueError(f"watermarking_config: hashing_key must be an integer in [0, 2**63), not {key!r}")
+    w = v["context_width"]
+    if not isinstance(w, int):
+        raise ValueError(f"watermarking_config: context_width must be an integer, not {w!r}")
+    if w != 1:
+        raise NotImplementedError(f"watermarking_config: context_width={w} is not implemented (1 is): the green list of a step is a "
+                                  "table row chosen by the previous code alone")
+    return WatermarkSettings(float(r), float(v["bias"]), int(key), v["seeding_scheme"], 1)
+
+
+def watermark_table(settings, vocab):
+    """WatermarkSettings -> the green lists as a uint32 [rows, ceil(vocab / 32)] CPU tensor: bit (i & 31) of word (i >> 5) of row
+    `prev` is set when id i is green after prev (lefthash: vocab rows); selfhash: ONE row, the ids that are green after themselves.
+    Built as transformers' WatermarkLogitsProcessor(vocab, "cpu", ...) builds its lists: a CPU torch.Generator seeded with
+    (hashing_key * prev) % (2**64 - 1) (lefthash) or with the wrapped int64 product hashing_key * a * a, a = fixed_table[cand] + 1
+    (selfhash, fixed_table = randperm(1_000_003) under the key), and the first int(vocab * ratio) ids of randperm(vocab).  Cached per
+    (key, ratio, scheme, vocab) in the process; the tensor is shared: do not write to it."""
+    import numpy as np
+    ck = (settings.hashing_key, settings.greenlist_ratio, settings.seeding_scheme, int(vocab))
+    if ck in _wm_tables:
+        return _wm_tables[ck]
+    V = int(vocab)
+    words = (V + 31) // 32
+    n_green = int(V * settings.greenlist_ratio)
+    g = torch.Generator(device="cpu")
+    key = settings.hashing_key
+    selfhash = settings.seeding_scheme == "selfhash"
+    if selfhash:
+        g.manual_seed(key)
+        fixed = torch.randperm(_WM_FIXED_TABLE, generator=g, device="cpu")
+        ab = fixed[torch.arange(V) % _WM_FIXED_TABLE] + 1
+        seeds = [int(s) % (2 ** 64 - 1) for s in (key * ab * ab).tolist()]          # int64 tensor arithmetic: it wraps, as HF's does
+    else:
+        seeds = [(key * prev) % (2 ** 64 - 1) for prev in range(V)]
+    bits = np.zeros((1 if selfhash else V, words * 32), dtype=bool)
+    for c, seed in enumerate(seeds):
+        g.manual_seed(seed)
+        green = torch.randperm(V, generator=g, device="cpu")[:n_green].numpy()
+        if selfhash:
+            bits[0, c] = bool((green == c).any())
+        else:
+            bits[c, green] = True
+    packed = np.packbits(bits.reshape(bits.shape[0], words, 32), axis=-1, bitorder="little").view("<u4").reshape(bits.shape[0], words)
+    t = torch.from_numpy(np.ascontiguousarray(packed.astype(np.uint32)))
+    _wm_tables[ck] = t
+    return t
+
+
+class WatermarkTable:
+    """the watermark entries of one call beside its sets (include/genvc_hip.h: gvc_gpt_generate_wm): one gvc_logits_watermark per
+    entry of the call's ProcessorSets / WarperSets (a null table where the entry has none), or one entry for every row of a call
+    without sets.  entries: what GptEngine.watermark_entry() returned (or None).  The tables are slots of the engine's arena; this
+    object holds them (GptEngine.watermark_release on release() or when it is collected), so no other call can rewrite a slot while a
+    loop that reads it is alive."""
+
+    def __init__(self, entries, engine=None):
+        self.n = len(entries)
+        self.wm = (_lib.LogitsWatermark * self.n)(*[_lib.LogitsWatermark() if m is None else m[0] for m in entries])
+        self._engine = engine
+        self._held = [m[1] for m in entries if m is not None and m[1] is not None]
+
+    def release(self):
+        held, self._held = self._held, []
+        if self._engine is not None:
+            for k in held:
+                self._engine.watermark_release(k)
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:
+            pass
+
+
+class WatermarkDetector:
+    """transformers' WatermarkDetector for code sequences, the counts on the device (include/genvc_hip.h: gvc_wm_score).
+    watermarking_config: as the generation kwarg (dict / to_dict() object); vocab: the code vocabulary the mark was made with;
+    ignore_repeated_ngrams: count each distinct (prev, cur) pair -- each distinct code under selfhash -- once, at its first occurrence.
+    The tables are those of a CPU generator (watermark_table): this detects what this project marks and what an HF processor built
+    with device="cpu" marks, not the output of an HF processor on a CUDA generator.
+    __call__(codes [B, n] or [n] integer tensor (moved to the GPU if it is not there), lens=None ([B] valid lengths), z_threshold=3.0,
+    return_dict=False) -> the boolean predictions (numpy [B]), or with return_dict a dict of num_tokens_scored, num_green_tokens,
+    green_fraction, z_score, p_value, prediction, confidence (numpy, float64 where HF's are; HF's formulas on the host) and `flags`
+    (uint8 [B, n] CPU tensor: 1 green, 0 scored and not green, 2 unscored).  lefthash scores len - 1 codes of a row, selfhash len; an
+    id outside [0, vocab) makes its n-gram unscored.  A row with nothing scored has z = nan and prediction False.  n <= 8192."""
+
+    def __init__(self, watermarking_config, vocab, ignore_repeated_ngrams=False):
+        s = watermark_settings(dict(watermarking_config=watermarking_config), vocab)
+        if s is None:
+            raise ValueError("WatermarkDetector needs a watermarking_config (None detects nothing)")
+        self.settings, self.vocab, self.ignore_repeated_ngrams = s, int(vocab), bool(ignore_repeated_ngrams)
+        self._host = watermark_table(s, vocab)
+        self._dev = {}          # device -> the table there
+
+    def counts(self, codes, lens=None):
+        """-> (counts int32 [B, 2] (scored, green), flags uint8 [B, n]), both on the device"""
+        if codes.ndim == 1:
+            codes = codes[None]
+        if codes.ndim != 2 or codes.is_floating_point() or codes.shape[1] < 1 or codes.shape[0] < 1:
+            raise ValueError(f"WatermarkDetector: codes must be an integer tensor [B, n] with B, n >= 1, not {tuple(codes.shape)} {codes.dtype}")
+        if codes.shape[1] > _lib.WM_MAX_SCORE_LEN:
+            raise ValueError(f"WatermarkDetector: {codes.shape[1]} codes per row, at most {_lib.WM_MAX_SCORE_LEN}")
+        if not codes.is_cuda:
+            codes = codes.cuda()
+        dev = codes.device
+        codes = codes.to(torch.int32).contiguous()
+        B, n = codes.shape
+        if lens is not None:
+            lens = torch.as_tensor(lens, device=dev).to(torch.int32).contiguous()
+            if tuple(lens.shape) != (B,):
+                raise ValueError(f"WatermarkDetector: lens {tuple(lens.shape)} for {B} rows")
+        if dev not in self._dev:
+            self._dev[dev] = self._host.view(torch.int32).to(dev)
+        table = self._dev[dev]
+        counts = torch.empty(B, 2, device=dev, dtype=torch.int32)
+        flags = torch.empty(B, n, device=dev, dtype=torch.uint8)
+        check(lib().gvc_wm_score(ptr(codes), None if lens is None else ptr(lens), B, n, ptr(table),
+                                 WATERMARK_SCHEMES[self.settings.seeding_scheme], int(self._host.shape[1]), self.vocab,
+                                 int(self.ignore_repeated_ngrams), ptr(counts), ptr(flags), stream()), "wm_score")
+        return counts, flags
+
+    def __call__(self, codes, lens=None, z_threshold=3.0, return_dict=False):
+        counts, flags = self.counts(codes, lens)
+        out = watermark_statistics(counts.cpu().numpy(), self.settings.greenlist_ratio, z_threshold)
+        if not return_dict:
+            return out["prediction"]
+        out["flags"] = flags.cpu()
+        return out
+
+
+def watermark_statistics(counts, greenlist_ratio, z_threshold=3.0):
+    """counts [B, 2] (scored, green) -> transformers' WatermarkDetectorOutput fields as a dict of numpy arrays, float64 with HF's
+    formulas: z = (green - r * scored) / sqrt(scored * r * (1 - r)), p = 1 - 0.5 * (1 + sign(z) * (1 - exp(-2 z^2 / pi)))"""
+    import numpy as np
+    c = np.asarray(counts)
+    scored, green = c[:, 0].astype(np.float64), c[:, 1].astype(np.float64)
+    r = greenlist_ratio
+    with np.errstate(divide="ignore", invalid="ignore"):
+        z = (green - r * scored) / np.sqrt(scored * r * (1 - r))
+        p = 1 - (0.5 * (1 + np.sign(z) * (1 - np.exp(-2 * z ** 2 / np.pi))))
+        frac = green / scored
+    return dict(num_tokens_scored=scored, num_green_tokens=green, green_fraction=frac, z_score=z, p_value=p, prediction=z > z_threshold,
+                confidence=1 - p)
+
+
 # HF generate kwargs of the call-wide sequence bias / bad words / forced EOS / renormalised scores (include/genvc_hip.h: gvc_logits_bias)
 BIAS_KWARGS = ("sequence_bias", "bad_words_ids", "forced_eos_token_id", "forced_bos_token_id", "renormalize_logits")
 BIAS_MAX_SEQS = _lib.BIAS_MAX_SEQS      # entries of sequence_bias and bad_words_ids together
@@ -363,13 +554,13 @@ def logits_bias(kw, prompt_len, max_new, vocab, eos):
 
 
 def check_proc_kwargs(kw, where):
-    """a per-row / per-group / per-job / per-session processor dict may hold PROC_KWARGS, WARP_KWARGS, RAS_KWARGS and PENALTY_KWARGS
-    only: anything else raises ValueError naming the key and `where` it came from"""
+    """a per-row / per-group / per-job / per-session processor dict may hold PROC_KWARGS, WARP_KWARGS, RAS_KWARGS, PENALTY_KWARGS and
+    WATERMARK_KWARGS only: anything else raises ValueError naming the key and `where` it came from"""
     if kw is None:
         return
     if not isinstance(kw, dict):
         raise ValueError(f"{where}: processor kwargs must be a dict or None, not {type(kw).__name__}")
-    allowed = PROC_KWARGS + WARP_KWARGS + RAS_KWARGS + PENALTY_KWARGS
+    allowed = PROC_KWARGS + WARP_KWARGS + RAS_KWARGS + PENALTY_KWARGS + WATERMARK_KWARGS
     unknown = sorted(set(kw) - set(allowed))
     if unknown:
         raise ValueError(f"{where}: {unknown[0]!r} is not a processor kwarg (allowed: {', '.join(allowed)})")
@@ -377,7 +568,8 @@ def check_proc_kwargs(kw, where):
 
 def _kw_key(kw):
     """hashable form of a processor dict (lists become tuples), for de-duplication before packing"""
-    key = tuple(sorted((k, tuple(v) if isinstance(v, (list, tuple)) else v) for k, v in kw.items() if v is not None))
+    key = tuple(sorted((k, tuple(v) if isinstance(v, (list, tuple)) else v) for k, v in kw.items()
+                       if v is not None and k not in WATERMARK_KWARGS))          # (the mark is no part of a processor set)
     try:
         hash(key)
     except TypeError:           # (an array-like value: its repr still tells identical dicts apart)
@@ -448,10 +640,13 @@ class WarperSets:
     (`sets` is None when no entry has one; an entry without one is the all-zero struct) paired with a gvc_logits_warpers, and
     `set_of_row` (B int32 indices, -1 = neither), all host arrays.  `prompt_lens` keeps the caller's device tensor alive.
     `ras` (optional): a gvc_logits_ras or None per entry; with any set, `self.ras` is the call's RasTable (generate_call passes it on).
-    `pen` (optional): a gvc_logits_penalties or None per entry; with any set, `self.pen` is the call's PenaltyTable likewise."""
+    `pen` (optional): a gvc_logits_penalties or None per entry; with any set, `self.pen` is the call's PenaltyTable likewise.
+    `wm` (optional): what `engine`.watermark_entry() returned, or None, per entry; with any set, `self.wm` is the call's
+    WatermarkTable likewise (it holds the entries' table slots while this object lives)."""
 
-    def __init__(self, procs, warps, set_of_row, prompt_lens=None, ras=None, pen=None):
+    def __init__(self, procs, warps, set_of_row, prompt_lens=None, ras=None, pen=None, wm=None, engine=None):
         self.n_sets = len(warps)
+        self.wm = WatermarkTable(list(wm), engine) if wm is not None and any(m is not None for m in wm) else None
         self.pen = PenaltyTable(list(pen)) if pen is not None and any(q is not None for q in pen) else None
         self.ras = RasTable(list(ras)) if ras is not None and any(r is not None for r in ras) else None
         self.sets = None
@@ -472,47 +667,52 @@ class WarperSets:
         return len(self.set_of_row)
 
 
-def logits_sets(kws, prompt_len, vocab, sampling=True, prompt_lens=None):
-    """logits_processor_sets() whose per-row dicts may also hold WARP_KWARGS, RAS_KWARGS and PENALTY_KWARGS.  When no row has a warper,
-    RAS or a penalty on, this returns exactly what logits_processor_sets() returns (a ProcessorSets or None); otherwise a WarperSets,
-    rows with equal processors, warpers, RAS and penalty entries (settings and prompt length) sharing an entry.  Errors name the
-    offending row."""
+def logits_sets(kws, prompt_len, vocab, sampling=True, prompt_lens=None, engine=None):
+    """logits_processor_sets() whose per-row dicts may also hold WARP_KWARGS, RAS_KWARGS, PENALTY_KWARGS and WATERMARK_KWARGS.  When
+    no row has a warper, RAS, a penalty or a watermark on, this returns exactly what logits_processor_sets() returns (a ProcessorSets
+    or None); otherwise a WarperSets, rows with equal processors, warpers, RAS, penalty and watermark entries (settings and prompt
+    length) sharing an entry.  A row with watermarking_config needs `engine`, the GptEngine whose arena holds the tables: rows with
+    different keys get entries of their own, pointing at different slots.  Errors name the offending row."""
     kws = list(kws)
     ps = logits_processor_sets(kws, prompt_len, vocab, sampling=sampling, prompt_lens=prompt_lens)      # (validates every row)
     plens = [prompt_len] * len(kws) if isinstance(prompt_len, int) else [int(x) for x in prompt_len]
-    warps, rass, pens = [], [], []
+    warps, rass, pens, wms = [], [], [], []
     for b, kw in enumerate(kws):
         try:
             warps.append(logits_warpers(kw or {}, sampling))
             rass.append(logits_ras(kw or {}, plens[b]))
             pens.append(logits_penalties(kw or {}, plens[b]))
+            wms.append(watermark_settings(kw or {}, vocab))
         except ValueError as e:
             raise ValueError(f"row {b}: {e}") from None
-    if all(w is None for w in warps) and all(r is None for r in rass) and all(q is None for q in pens):
+    if all(w is None for w in warps) and all(r is None for r in rass) and all(q is None for q in pens) and all(m is None for m in wms):
         return ps
+    if engine is None and any(m is not None for m in wms):
+        raise ValueError("watermarking_config in a per-row dict needs the engine whose arena holds the tables: logits_sets(engine=...)")
     if prompt_lens is not None and any(r is not None for r in rass):
         raise ValueError("ras_window counts a row's generated tokens from a host prompt length: pass prompt_len, not a device tensor")
     if prompt_lens is not None and any(q is not None for q in pens):
         raise ValueError("the presence / frequency / windowed penalties count a row's generated tokens from a host prompt length: pass "
                          "prompt_len, not a device tensor")
     pidx = list(ps.set_of_row) if ps is not None else [-1] * len(kws)
-    by, procs, wl, rl, ql, index = {}, [], [], [], [], []
+    by, procs, wl, rl, ql, ml, index = {}, [], [], [], [], [], []
 
     def raw(x):
         return None if x is None else C.string_at(C.addressof(x), C.sizeof(x))
-    for b, (w, r, q) in enumerate(zip(warps, rass, pens)):
-        if pidx[b] < 0 and w is None and r is None and q is None:
+    for b, (w, r, q, m) in enumerate(zip(warps, rass, pens, wms)):
+        if pidx[b] < 0 and w is None and r is None and q is None and m is None:
             index.append(-1)
             continue
-        key = (pidx[b], raw(w), raw(r), raw(q))
+        key = (pidx[b], raw(w), raw(r), raw(q), m)
         if key not in by:
             by[key] = len(wl)
             procs.append(ps.sets[pidx[b]] if pidx[b] >= 0 else None)
             wl.append(w)
             rl.append(r)
             ql.append(q)
+            ml.append(None if m is None else engine.watermark_entry(m))
         index.append(by[key])
-    return WarperSets(procs, wl, index, prompt_lens, ras=rl, pen=ql)
+    return WarperSets(procs, wl, index, prompt_lens, ras=rl, pen=ql, wm=ml, engine=engine)
 
 
 BEAM_LENGTH_MODES = {"4.33": 0, "generated": 1}
@@ -1317,9 +1517,105 @@ class GptEngine:
                               + ([None, None] if ras is None else self._ras_args(ras, sets, B)) + self._pen_args(pen, sets),
                               guided=(uncond_slots, scale), outputs=(scores_out, logits_out, do_sample))
 
+    # ---- green-list watermark: the device-resident tables ----------------------------------------------------------------------
+    # One arena of MAX_WATERMARK_TABLES slots of vocab * ceil(vocab / 32) words (135 KB each at vocab 1026), allocated at first use or
+    # by GenVCModel.warmup(watermarking_config=...).  A slot is keyed by (hashing_key, ratio, scheme); a WatermarkTable (a call's loop
+    # state, a generator, a session) holds its slots while it lives.  Uploads are stream-ordered copies on the caller's stream from a
+    # pinned copy of the host table.  A slot is REWRITTEN only when no holder is left and a ninth table needs room, and then only behind
+    # torch.cuda.synchronize(): every launch that could still read the old table -- on any stream -- has finished before the copy is
+    # enqueued.  A slot that was never written needs no such wait.  Every upload records an event, and every later call that finds the
+    # table resident makes its own stream wait for that event, so a call on another stream never reads a table still being copied.
+    # The bookkeeping itself is host state of one thread: an engine is driven from one host thread at a time, as its other calls are.
+    def _wm_arena(self):
+        if getattr(self, "_wm", None) is None:
+            words = (self.V + 31) // 32
+            self._wm = dict(buf=torch.zeros(MAX_WATERMARK_TABLES, self.V * words, dtype=torch.int32, device="cuda"), words=words,
+                            slot={}, holds={}, used=[None] * MAX_WATERMARK_TABLES, tick=0, last={}, pinned={}, uploads=0, ready={})
+        return self._wm
+
+    def watermark_entry(self, settings, hold=True):
+        """WatermarkSettings -> (gvc_logits_watermark pointing at the settings' device table, the hold's key or None): the table is
+        uploaded on the current stream unless a slot already has it.  hold: the slot stays this table until watermark_release(key)
+        (WatermarkTable does that).  ValueError: MAX_WATERMARK_TABLES other tables are held."""
+        a = self._wm_arena()
+        key = (settings.hashing_key, settings.greenlist_ratio, settings.seeding_scheme)
+        a["tick"] += 1
+        if key not in a["slot"]:
+            free = [i for i, k in enumerate(a["used"]) if k is None]
+            idle = sorted((a["last"][k], i) for i, k in enumerate(a["used"]) if k is not None and a["holds"].get(k, 0) == 0)
+            if free:
+                i = free[0]
+            elif idle:
+                i = idle[0][1]
+                torch.cuda.synchronize()          # (nothing that reads the old table is in flight any more, on any stream)
+                del a["slot"][a["used"][i]]
+            else:
+                raise ValueError(f"watermarking_config: {MAX_WATERMARK_TABLES} other watermark tables are in use on this engine "
+                                 "(sessions and generators hold theirs while open); close one first")
+            host = watermark_table(settings, self.V)
+            if key not in a["pinned"]:
+                a["pinned"] = {key: host.view(torch.int32).reshape(-1).pin_memory()}          # (one pinned staging copy at a time)
+            src = a["pinned"][key]
+            a["buf"][i, :src.numel()].copy_(src, non_blocking=True)
+            a["ready"][key] = torch.cuda.Event()
+            a["ready"][key].record()          # (a call on another stream waits for this copy: below)
+            a["used"][i] = key
+            a["slot"][key] = i
+            a["uploads"] += 1
+        i = a["slot"][key]
+        torch.cuda.current_stream().wait_event(a["ready"][key])          # (the upload may have been enqueued on another stream)
+        a["last"][key] = a["tick"]
+        if hold:
+            a["holds"][key] = a["holds"].get(key, 0) + 1
+        m = _lib.LogitsWatermark(a["buf"][i].data_ptr(), float(settings.bias), WATERMARK_SCHEMES[settings.seeding_scheme], a["words"], 0)
+        return m, (key if hold else None)
+
+    def watermark_release(self, key):
+        a = getattr(self, "_wm", None)
+        if a is not None and a["holds"].get(key, 0) > 0:
+            a["holds"][key] -= 1
+
+    def watermark_uploads(self):
+        """how many tables this engine has uploaded (a warm marked call uploads none)"""
+        a = getattr(self, "_wm", None)
+        return 0 if a is None else a["uploads"]
+
+    def _wm_args(self, wm, sets):
+        """[watermark entries] of a WatermarkTable beside `sets`"""
+        if wm.n != (1 if sets is None else sets.n_sets):
+            raise ValueError(f"{wm.n} watermark entries for {1 if sets is None else sets.n_sets} sets")
+        return [wm.wm]
+
+    def sample_wm(self, logits, ids, ids_len, finished, params, wm, step, sets=None, bias=None, ras=None, pen=None, rows=None):
+        """sample_pen() (pen None: sample_ras() ...) with the green-list watermark of a WatermarkTable (include/genvc_hip.h:
+        gvc_sample_wm): row b uses entry sets.set_of_row[b] of the table (entry 0 without sets, none for -1).  The kernel is the one
+        the call runs without the table."""
+        B = logits.shape[0]
+        sa = self._sets_args(sets, B)
+        if sets is None:
+            sa[2] = 1
+        return self._sample("sample_wm", logits, ids, ids_len, finished, params, step, rows,
+                            sa + [None if bias is None else C.byref(bias)] + ([None, None] if ras is None else self._ras_args(ras, sets, B))
+                            + ([None] if pen is None else self._pen_args(pen, sets)) + self._wm_args(wm, sets))
+
+    def generate_wm(self, slots, uncond_slots, scale, ids, ids_len, finished, params, sets, bias, ras, pen, wm, i0, n_steps, tokens_out,
+                    latents_out, scores_out=None, logits_out=None, do_sample=True, max_keys=0, rows=None):
+        """generate_pen() (pen None: generate_ras() ...) with a WatermarkTable (include/genvc_hip.h: gvc_gpt_generate_wm).  The entries
+        travel with the call in one staging launch; the step graphs are those of the call without them, and nothing is allocated or
+        captured once the tables are resident."""
+        B = slots.shape[0]
+        sa = self._sets_args(sets, B)
+        if sets is None:
+            sa[2] = 1
+        return self._generate("generate_wm", "generate_wm", slots, ids, ids_len, finished, params, i0, n_steps, tokens_out, latents_out,
+                              max_keys, rows, sa + [None if bias is None else C.byref(bias)]
+                              + ([None, None] if ras is None else self._ras_args(ras, sets, B))
+                              + ([None] if pen is None else self._pen_args(pen, sets)) + self._wm_args(wm, sets),
+                              guided=(uncond_slots, scale), outputs=(scores_out, logits_out, do_sample))
+
     def generate_call(self, slots, ids, ids_len, finished, params, i0, n_steps, tokens_out, latents_out, max_keys=0, rows=None, proc=None,
                       sets=None, bias=None, uncond_slots=None, scale=1.0, scores_out=None, logits_out=None, do_sample=True, ras=None,
-                      pen=None):
+                      pen=None, wm=None):
         """The generation call for whatever options a loop has, through the narrowest entry that carries them: generate_bias (bias),
         generate_scores (score / logit buffers), generate_cfg (uncond_slots), generate_proc_sets / generate_warp (sets), generate_rows
         (rows), else generate.  proc: the call-wide processors; sets (a ProcessorSets / WarperSets) supersedes it, and the entries
@@ -1327,7 +1623,7 @@ class GptEngine:
         the public methods, so a patched or overridden entry still sees its calls, and an engine stand-in that has no generate_call
         of its own (layers.gpt._generate_call) needs only the entries its options reach."""
         wide = (bias is not None or scores_out is not None or logits_out is not None or uncond_slots is not None or ras is not None
-                or pen is not None)
+                or pen is not None or wm is not None)
         if wide and sets is None and proc is not None:
             sets = WarperSets.one(proc, None, slots.shape[0])
         pk = {} if proc is None or sets is not None else {"proc": proc}
@@ -1335,6 +1631,12 @@ class GptEngine:
             ras = getattr(sets, "ras", None)          # (per-row entries ride with the sets: logits_sets)
         if pen is None:
             pen = getattr(sets, "pen", None)
+        if wm is None:
+            wm = getattr(sets, "wm", None)
+        if wm is not None:           # (a WatermarkTable: the green-list watermark, the widest entry)
+            return self.generate_wm(slots, uncond_slots, scale, ids, ids_len, finished, params, sets, bias, ras, pen, wm, i0, n_steps,
+                                    tokens_out, latents_out, scores_out=scores_out, logits_out=logits_out, do_sample=do_sample,
+                                    max_keys=max_keys, rows=rows)
         if pen is not None:          # (a PenaltyTable: presence / frequency / windowed penalties, the widest entry)
             return self.generate_pen(slots, uncond_slots, scale, ids, ids_len, finished, params, sets, bias, ras, pen, i0, n_steps,
                                      tokens_out, latents_out, scores_out=scores_out, logits_out=logits_out, do_sample=do_sample,

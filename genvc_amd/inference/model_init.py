@@ -100,6 +100,34 @@ class GenVCModel(nn.Module):
         return batch
 
     @torch.inference_mode()
+    def detect_watermark(self, codes=None, wav=None, sr=None, watermarking_config=None, lens=None, z_threshold=3.0,
+                         ignore_repeated_ngrams=False, return_dict=True):
+        """engine.WatermarkDetector on generated codes: `codes` [B, n] (or [n]) as GPT.generate returns them -- give `lens` when rows
+        end in stop codes that should not count -- or, as a convenience, `wav` [B, T] / [B, 1, T] at `sr` (default and only served
+        rate: config.audio.sample_rate): the codes the acoustic DVAE assigns to it, format_batch_on_device's `audio_codes`.
+        watermarking_config: the one the codes were generated with (the key is the secret).  -> WatermarkDetector's result.
+        The `wav` form is exactly score(audio_codes(wav)).  Whether a mark SURVIVES vocoder -> waveform -> tokeniser is a property of
+        trained weights; no checkpoint was available to this project, so nobody has measured it: treat a negative result on audio
+        as no evidence, and a positive one with the caution any unmeasured detector deserves.  The codes form has no such caveat."""
+        from genvc_amd.engine import WatermarkDetector
+        if (codes is None) == (wav is None):
+            raise ValueError("detect_watermark: pass codes=... or wav=..., not both and not neither")
+        det = WatermarkDetector(watermarking_config, self.gpt.num_audio_tokens, ignore_repeated_ngrams=ignore_repeated_ngrams)
+        if wav is not None:
+            if self.acoustic_dvae is None:
+                raise NotImplementedError("detect_watermark(wav=...): the config has no acoustic_dvae_config "
+                                          "(default_config(with_acoustic=True))")
+            rate = int(self.config.audio.sample_rate)
+            if (sr is not None and int(sr) != rate) or int(self.acoustic_sample_rate) != rate:
+                raise NotImplementedError(f"detect_watermark(wav=...): audio at {sr or rate} Hz for an acoustic DVAE at "
+                                          f"{self.acoustic_sample_rate} Hz and a model at {rate} Hz needs a resampler this path does not have")
+            wav = wav.to(self.device)
+            if wav.ndim == 2:
+                wav = wav[:, None]
+            codes = self.acoustic_dvae.get_codebook_indices(self.torch_mel_spectrogram_dvae(wav))
+        return det(codes, lens=lens, z_threshold=z_threshold, return_dict=return_dict)
+
+    @torch.inference_mode()
     def audition_codes(self, audio_codes, n_iter=64, seed=0):
         """audio codes [B,n] -> waveform [B, hop (F - 1)] at the acoustic DVAE's rate, without the vocoder: the DVAE's decoded mel
         through TorchMelSpectrogram.invert (inverse mel scale, then Griffin-Lim from the seeded start).  Tells "the codes are bad" from
@@ -234,7 +262,7 @@ class GenVCModel(nn.Module):
     @torch.inference_mode()
     def warmup(self, seg_len=1.0, streams=1, ref_seconds=3.0, stream_chunk_size=8, top_k=None, max_new_tokens=None, num_beams=1,
                contrastive_top_k=None, num_return_sequences=1, num_beam_groups=1, guidance=False, ras_window=None, ras_threshold=None,
-               presence_penalty=None, frequency_penalty=None, penalty_window=None):
+               presence_penalty=None, frequency_penalty=None, penalty_window=None, watermarking_config=None):
         """Everything the FIRST conversion of this shape would otherwise pay inside its latency window (the reference leaves warm-up
         to the user: /root/reference/infer.py:27-30 runs a conversion first).  For `streams` concurrent streams of `seg_len`-second
         segments and a `ref_seconds` reference:
@@ -256,6 +284,9 @@ class GenVCModel(nn.Module):
         presence_penalty / frequency_penalty / penalty_window: the calls will carry these penalties.  Both sampler kernels apply them
         and the table travels in the device-resident call state, so the graphs warmed above are the ones such calls replay: the
         values are validated (ValueError) and nothing more is captured.
+        watermarking_config: the calls will carry this green-list watermark (GPT.generate).  It is validated, its table is built on
+        the host and uploaded into a slot of the engine's arena (allocated here); both sampler kernels apply it from the
+        device-resident call state, so such calls replay the graphs warmed above and neither allocate, upload nor capture.
         No token is generated and no KV slot is left occupied."""
         dev = self.device
         g = self.gpt
@@ -276,7 +307,10 @@ class GenVCModel(nn.Module):
         # the calls get_generator / _advance will make reach max_keys = n0 + grp ... n0 + max_new: the library warms every context class in
         # that range (its thresholds are its own: gvc_gpt_warmup_range)
         hi = min(n0 + max_new, eng.dims["max_seq"] - 1)
-        from genvc_amd.engine import penalty_settings, ras_counts
+        from genvc_amd.engine import penalty_settings, ras_counts, watermark_settings
+        wm = watermark_settings(dict(watermarking_config=watermarking_config), g.num_audio_tokens)
+        if wm is not None:
+            eng.watermark_entry(wm, hold=False)          # (the slot keeps the table until eight other tables have come after it)
         penalty_settings(dict(presence_penalty=presence_penalty, frequency_penalty=frequency_penalty, penalty_window=penalty_window))
         ras = ras_counts(dict(ras_window=ras_window, ras_threshold=ras_threshold)) is not None
         for k in [top_k] + ([0] if ras and top_k == 1 else []):          # (0: the graphs around the full sampling kernel)

@@ -14,7 +14,7 @@ from torch.nn import functional as F
 
 from .._lib import GenvcHipError
 from ..engine import (MAX_ASSISTANT_TOKENS, MAX_LOOKUP_HISTORY, MAX_LOOKUP_NGRAM, MAX_VERIFY_ROWS, AssistedState, BEAM_LENGTH_MODES, beam_early_stopping, check_beam_groups, GroupBeamSearch, MAX_CONTRASTIVE_K, PROC_KWARGS, WARP_KWARGS, BeamSearch, ContrastiveSearch, GptEngine, WarperSets,
-                      PENALTY_KWARGS, PenaltyTable, RAS_KWARGS, RasTable, check_proc_kwargs, logits_bias, logits_penalties,
+                      PENALTY_KWARGS, PenaltyTable, WATERMARK_KWARGS, WatermarkTable, watermark_settings, RAS_KWARGS, RasTable, check_proc_kwargs, logits_bias, logits_penalties,
                       logits_processors, logits_ras, logits_sets, logits_warpers, penalty_settings, ras_counts, sample_params)
 from .perceiver_encoder import PerceiverResampler
 
@@ -317,6 +317,64 @@ def _no_penalties(kw, mode):
                                   "penalties act in a sampler step (greedy, sampling, num_return_sequences, guidance_scale)")
 
 
+def _watermark(kw, vocab):
+    """the watermarking_config of a sampler-step call (GPT.generate: greedy search, sampling, num_return_sequences, guidance_scale;
+    get_generator) -> engine.WatermarkSettings, or None when it is off.  Malformed settings: ValueError / NotImplementedError
+    (engine.watermark_settings).  The combinations that cannot carry transformers' semantics raise instead of leaving the output
+    unmarked:
+    do_sample=True with top_k=1: ValueError -- after TopK(1) one entry survives, so the mark behind the warpers cannot move a token; a
+    marked greedy stream is do_sample=False;
+    selfhash under greedy search: NotImplementedError (the argmax path has no 40 highest scores);
+    selfhash with typical_p: NotImplementedError (typical decoding may drop the highest scores: its survivors do not lead the order);
+    ras_window: NotImplementedError (a redraw from the untruncated row would need a rule of its own)."""
+    s = watermark_settings(kw, vocab)
+    if s is None:
+        return None
+    sampling = kw.get("do_sample", True)
+    if sampling and kw.get("top_k", 0) == 1:
+        raise ValueError("watermarking_config with do_sample=True and top_k=1: TopK(1) leaves one candidate, so the watermark (behind "
+                         "the warpers, as in transformers) could not move a single token; pass do_sample=False for greedy search "
+                         "with the mark")
+    if not sampling and s.seeding_scheme == "selfhash":
+        raise NotImplementedError("watermarking_config with seeding_scheme='selfhash' and do_sample=False (greedy search) is not "
+                                  "implemented: the argmax path has no 40 highest scores to restrict the bias to; use 'lefthash'")
+    tp = kw.get("typical_p")
+    if s.seeding_scheme == "selfhash" and tp is not None and tp < 1.0:
+        raise NotImplementedError(f"watermarking_config with seeding_scheme='selfhash' and typical_p={tp} is not implemented: typical "
+                                  "decoding can drop the highest scores, so the 40 highest survivors are no prefix of the sorted row")
+    if ras_counts(kw) is not None:
+        raise NotImplementedError(f"watermarking_config with ras_window={kw.get('ras_window')} is not implemented: the redraw from the "
+                                  "untruncated row would need a rule of its own")
+    return s
+
+
+def _no_watermark(kw, mode, vocab):
+    """the modes and paths that do not carry the watermark raise, naming the kwarg and the mode: an unmarked output must never be
+    silent (malformed settings: engine.watermark_settings)"""
+    if watermark_settings(kw, vocab) is not None:
+        raise NotImplementedError(f"watermarking_config with {mode} is not implemented: the watermark acts in a sampler step of "
+                                  "GPT.generate (greedy search, sampling, num_return_sequences, guidance_scale), get_generator and the "
+                                  "sampled rows of generate_groups / generate_rolling / StreamSessions")
+
+
+def _watermark_rows(kw, items, where, vocab):
+    """the joint paths (generate_groups, generate_rolling; `items`: the merged per-item dicts or None): a mark, call-wide or on any
+    item, is served on sampled rows.  Greedy rows (top_k=1 or do_sample=False) raise NotImplementedError naming the path -- their
+    kernel adds the bias behind the division by the call's temperature, which is greedy search only at temperature 1 --: GPT.generate(
+    do_sample=False) serves greedy search with the mark.  The refused combinations of _watermark raise as they do there.
+    -> whether any mark is on"""
+    on = False
+    for d in ([kw] if items is None else [dict(kw, **(d or {})) for d in items]):
+        if watermark_settings(d, vocab) is None:
+            continue
+        on = True
+        if kw.get("top_k", 0) == 1 or not kw.get("do_sample", True):
+            raise NotImplementedError(f"watermarking_config with greedy rows (top_k=1 or do_sample=False) on {where} is not "
+                                      "implemented: GPT.generate(do_sample=False) serves greedy search with the mark")
+        _watermark(d, vocab)
+    return on
+
+
 ASSIST_KWARGS = ("assistant_model", "num_assistant_tokens", "num_assistant_tokens_schedule", "assistant_cond_latents",
                  "speculative_sampling")
 
@@ -448,7 +506,7 @@ def _per_item_procs(kw, item_kwargs, n, name, vocab):
     item_kwargs = list(item_kwargs)
     if len(item_kwargs) != n:
         raise ValueError(f"{name}: {len(item_kwargs)} processor dicts for {n} items")
-    base = {k: kw[k] for k in PROC_KWARGS + WARP_KWARGS + RAS_KWARGS + PENALTY_KWARGS if kw.get(k) is not None}
+    base = {k: kw[k] for k in PROC_KWARGS + WARP_KWARGS + RAS_KWARGS + PENALTY_KWARGS + WATERMARK_KWARGS if kw.get(k) is not None}
     out = []
     for i, d in enumerate(item_kwargs):
         check_proc_kwargs(d, f"{name}[{i}]")
@@ -458,6 +516,7 @@ def _per_item_procs(kw, item_kwargs, n, name, vocab):
             logits_warpers(m, sampling=kw.get("do_sample", True))
             _ras_on(dict(m, do_sample=kw.get("do_sample", True)))
             penalty_settings(m)
+            watermark_settings(m, vocab)
         except ValueError as e:
             raise ValueError(f"{name}[{i}]: {e}") from None
         out.append(m)
@@ -714,6 +773,14 @@ class GPT(nn.Module):
                   max_new=max_new, done=0, n0=n0)
         samp = dict(repetition_penalty=kw.get("repetition_penalty", 1.0), temperature=kw.get("temperature", 1.0),
                     top_p=kw.get("top_p", 1.0), top_k=kw.get("top_k", 0) if kw.get("do_sample", True) else 1)
+        # green-list watermark (engine.WATERMARK_KWARGS): one call-wide entry; its table sits in a slot of the engine's
+        # arena, held while this loop state lives.  Greedy search has no Temperature: the bias is added to the processed row as it is
+        wm = _watermark(kw, self.num_audio_tokens)
+        st["wm"] = None
+        if wm is not None:
+            st["wm"] = WatermarkTable([self.engine.watermark_entry(wm)], self.engine)
+            if not kw.get("do_sample", True):
+                samp["temperature"] = 1.0
         st["params"] = sample_params(samp, self.num_audio_tokens, self.stop_audio_token, kw.get("seed", 0))
         # length / repetition processors (HF kwargs, engine.PROC_KWARGS): the prompt is the fake ids
         st["proc"] = logits_processors(kw, n0, self.num_audio_tokens, sampling=kw.get("do_sample", True))
@@ -753,7 +820,8 @@ class GPT(nn.Module):
                            sets=st["warp"], bias=st.get("bias"), uncond_slots=st.get("uncond_slots"),
                            scale=st.get("guidance_scale", 1.0), scores_out=st.get("scores"), logits_out=st.get("raw_logits"),
                            do_sample=st.get("do_sample", True), **({} if st.get("ras") is None else {"ras": st["ras"]}),
-                           **({} if st.get("pen") is None else {"pen": st["pen"]}))
+                           **({} if st.get("pen") is None else {"pen": st["pen"]}),
+                           **({} if st.get("wm") is None else {"wm": st["wm"]}))
             st["done"] += n
         end = bool(st["finished"].all().item()) or st["done"] >= st["max_new"]
         self.engine.health()          # (the .item() above synchronised: a hand-off timeout of these steps surfaces here, not a call later)
@@ -919,6 +987,18 @@ class GPT(nn.Module):
         (repetition_penalty=2.0, penalty_window=16 is a windowed repetition penalty).  `scores` carry them, `logits` stay raw.
         Each None or 0 is exactly the call without it.  Beams, beam groups, contrastive search, assisted and prompt-lookup
         decoding raise NotImplementedError.
+        watermarking_config = a dict with transformers' keys (greenlist_ratio 0.25, bias 2.0, hashing_key 15485863, seeding_scheme
+        "lefthash" | "selfhash", context_width 1) or an object with to_dict() such as transformers' WatermarkingConfig
+        (engine.watermark_settings; include/genvc_hip.h: gvc_logits_watermark): the green-list watermark of
+        Kirchenbauer et al. with transformers' semantics -- behind every processor and warper, ahead of renormalize_logits, the green
+        list of a step chosen by the previous code (at the first step the fake prompt's last id).  key -> green lists is defined by
+        the CPU torch.Generator: engine.WatermarkDetector / GenVCModel.detect_watermark, or transformers' detector built with
+        device="cpu", find the mark.  `scores` carry the bias, `logits` stay raw.  A green stop code is biased like any other, so a
+        marked call can end earlier or later than the unmarked one.  Greedy search (do_sample=False, lefthash) takes the argmax of
+        the biased row; do_sample=True with top_k=1 raises ValueError (nothing could be marked), selfhash with greedy search or
+        typical_p, ras_window, beams, beam groups, contrastive search, assisted and prompt-lookup decoding raise
+        NotImplementedError.  None is exactly the call without it.  generate_groups / generate_rolling take it call-wide and per
+        group / job (group_kwargs / job_kwargs: two keys in one call), StreamSessions per session, on sampled rows.
         assistant_model = another initialised GPT: assisted (speculative) greedy decoding (_generate_assisted), checked
         before every other mode; the tokens are those of the call without it.  None is exactly that call.  With
         speculative_sampling=True a sampled call is served too (speculative sampling: same distribution per token, other tokens than
@@ -931,6 +1011,8 @@ class GPT(nn.Module):
         if _lookup(generate_kwargs) or generate_kwargs.get("assistant_model") is not None:
             _no_ras(generate_kwargs, _LOOKUP_MODE if _lookup(generate_kwargs) else "assisted decoding (assistant_model)")
             _no_penalties(generate_kwargs, _LOOKUP_MODE if _lookup(generate_kwargs) else "assisted decoding (assistant_model)")
+            _no_watermark(generate_kwargs, _LOOKUP_MODE if _lookup(generate_kwargs) else "assisted decoding (assistant_model)",
+                          self.num_audio_tokens)
             return self._generate_assisted(cond_latents, text_inputs, generate_kwargs)
         if ras_counts(generate_kwargs) is not None:
             if _contrastive_mode(generate_kwargs) is not None:
@@ -947,6 +1029,15 @@ class GPT(nn.Module):
                 _no_penalties(generate_kwargs, "beam groups (num_beam_groups / diversity_penalty)")
             if int(generate_kwargs.get("num_beams", 1) or 1) > 1:
                 _no_penalties(generate_kwargs, f"beam search (num_beams={generate_kwargs.get('num_beams')})")
+        if watermark_settings(generate_kwargs, self.num_audio_tokens) is not None:
+            if _contrastive_mode(generate_kwargs) is not None:
+                _no_watermark(generate_kwargs, f"contrastive search (penalty_alpha={generate_kwargs.get('penalty_alpha')})",
+                              self.num_audio_tokens)
+            if _grouped(generate_kwargs):
+                _no_watermark(generate_kwargs, "beam groups (num_beam_groups / diversity_penalty)", self.num_audio_tokens)
+            if int(generate_kwargs.get("num_beams", 1) or 1) > 1:
+                _no_watermark(generate_kwargs, f"beam search (num_beams={generate_kwargs.get('num_beams')})", self.num_audio_tokens)
+            _watermark(generate_kwargs, self.num_audio_tokens)          # (the refused combinations raise before any work is done)
         scale = _guidance_scale(generate_kwargs)
         if scale is not None:
             return self._generate_guided(cond_latents, text_inputs, scale, generate_kwargs)
@@ -990,6 +1081,8 @@ class GPT(nn.Module):
         self.last_sequence_logprobs = self.last_sequence_lengths = None
         if N > 1:
             self.last_sequence_logprobs, self.last_sequence_lengths = self.sequence_logprobs(toks[:, :n], self.last_latents)
+        if st.get("wm") is not None:
+            st["wm"].release()          # (the loop has ended: its table's slot is free for others, whatever still refers to st)
         return self._result(toks[:, :n], kw, st, n)
 
     def _generate_guided(self, cond_latents, text_inputs, scale, generate_kwargs):
@@ -1307,12 +1400,14 @@ class GPT(nn.Module):
         (gvc_gpt_generate_proc_sets, or gvc_gpt_generate_warp when a warper is on).
         Returns a list of int64 [B_i, n_i] (reference gpt.py:594-609 per group)."""
         _plain_rows_only(generate_kwargs, "grouped (generate_groups)")
+        watermark_settings(generate_kwargs, self.num_audio_tokens)          # (malformed watermarking_config: ValueError)
         _ras_on(generate_kwargs)          # (malformed ras_window / ras_threshold, or do_sample=False with them: ValueError)
         penalty_settings(generate_kwargs)          # (malformed presence_penalty / frequency_penalty / penalty_window: ValueError)
         kw = dict(generate_kwargs)
         gkw = None
         if group_kwargs is not None:
             gkw = _per_item_procs(kw, group_kwargs, len(groups), "group_kwargs", self.num_audio_tokens)
+        _watermark_rows(kw, gkw, "the grouped path (generate_groups)", self.num_audio_tokens)
         self._need_engine()
         group = kw.pop("group", 16)          # decode steps per engine call (one host look at the finished flags per call)
         class_seeds = kw.pop("class_seeds", None)      # sampling runs: one seed per group (default: seed + 7919 * group index)
@@ -1370,9 +1465,9 @@ class GPT(nn.Module):
         seeds = [seeds[i] for i in order] if seeds is not None else None
         gkw = [gkw[i] for i in order] if gkw is not None else None
         if gkw is None and ((seeds is not None and (logits_warpers(kw) is not None or ras_counts(kw) is not None))
-                            or penalty_settings(kw) is not None):
-            # call-wide warpers / RAS / penalties: every group carries the call's processor, warper, RAS and penalty kwargs
-            # (logits_sets; the penalties count from each group's own prompt length, greedy calls included)
+                            or penalty_settings(kw) is not None or watermark_settings(kw, self.num_audio_tokens) is not None):
+            # call-wide warpers / RAS / penalties / watermark: every group carries the call's processor, warper, RAS, penalty and
+            # watermark kwargs (logits_sets; the penalties count from each group's own prompt length, greedy calls included)
             gkw = _per_item_procs(kw, [None] * len(groups), len(groups), "generate_kwargs", self.num_audio_tokens)
         gb = [budgets[i] if budgets else max_new for i in order]
         prefixes = [self.engine.prefix_embeddings(c.to(torch.float32).contiguous(), t.to(torch.int32).contiguous()) for c, t in groups]
@@ -1413,7 +1508,7 @@ class GPT(nn.Module):
             if gkw is not None:
                 sets = logits_sets([gkw[g] for g in live_groups for _ in range(spans[g][1] - spans[g][0])],
                                    [n0s[g] for g in live_groups for _ in range(spans[g][1] - spans[g][0])],
-                                   self.num_audio_tokens, sampling=seeds is not None)
+                                   self.num_audio_tokens, sampling=seeds is not None, engine=self.engine)
             # sampling: row r of class g is keyed (class seed, r, done) -- what generate(seed=class seed) draws for it
             rows = None
             if seeds is not None:
@@ -1453,12 +1548,14 @@ class GPT(nn.Module):
         the call-wide ones; job j then gets what generate(c_j, t_j, **its merged kwargs) returns (seed=job_seeds[j] when sampling), each
         row of a decode call carrying its job's set (gvc_gpt_generate_proc_sets, or gvc_gpt_generate_warp when a warper is on)."""
         _plain_rows_only(generate_kwargs, "rolling (generate_rolling)")
+        watermark_settings(generate_kwargs, self.num_audio_tokens)          # (malformed watermarking_config: ValueError)
         _ras_on(generate_kwargs)          # (malformed ras_window / ras_threshold, or do_sample=False with them: ValueError)
         penalty_settings(generate_kwargs)          # (malformed presence_penalty / frequency_penalty / penalty_window: ValueError)
         kw = dict(generate_kwargs)
         jkw = None
         if job_kwargs is not None:
             jkw = _per_item_procs(kw, job_kwargs, len(jobs), "job_kwargs", self.num_audio_tokens)
+        _watermark_rows(kw, jkw, "the rolling path (generate_rolling)", self.num_audio_tokens)
         self._need_engine()
         group = kw.pop("group", 16)
         kw.pop("class_seeds", None)
@@ -1491,8 +1588,8 @@ class GPT(nn.Module):
     def _rolling(self, jobs, kw, budgets, group, n0s, width, S, seeds=None, jkw=None):
         dev = jobs[0][1].device
         if jkw is None and ((seeds is not None and (logits_warpers(kw) is not None or ras_counts(kw) is not None))
-                            or penalty_settings(kw) is not None):
-            # call-wide warpers / RAS / penalties: every job carries the call's processor, warper, RAS and penalty kwargs
+                            or penalty_settings(kw) is not None or watermark_settings(kw, self.num_audio_tokens) is not None):
+            # call-wide warpers / RAS / penalties / watermark: every job carries the call's processor, warper, RAS and penalty kwargs
             # (logits_sets; the penalties count from each job's own prompt length, greedy calls included)
             jkw = _per_item_procs(kw, [None] * len(jobs), len(jobs), "generate_kwargs", self.num_audio_tokens)
         eng = self.engine
@@ -1540,7 +1637,7 @@ class GPT(nn.Module):
             if jkw is not None:
                 # job_kwargs: every row its job's set, counted from its job's prompt (None: no row has a processor)
                 sets = logits_sets([jkw[j["job"]] for j in live for _ in j["alive"]], [j["n0"] for j in live for _ in j["alive"]],
-                                   self.num_audio_tokens, sampling=seeds is not None)
+                                   self.num_audio_tokens, sampling=seeds is not None, engine=self.engine)
             elif _any_proc(kw):
                 plens = torch.tensor([j["n0"] for j in live for _ in j["alive"]], dtype=torch.int32).to(dev)
                 proc = logits_processors(kw, 0, self.num_audio_tokens, sampling=seeds is not None, prompt_lens=plens)
@@ -1599,6 +1696,7 @@ class GPT(nn.Module):
         the EOS step included.  Steps run in groups of `stream_group` (default 8, the vocoder chunk of
         inference_utils.py:195) with one host check of the finished flags per group."""
         _plain_rows_only(generate_kwargs, "streaming (get_generator)")
+        _watermark(generate_kwargs, self.num_audio_tokens)          # (malformed or refused watermarking_config: raised before any work)
         _ras_on(generate_kwargs)          # (malformed ras_window / ras_threshold, or do_sample=False with them: ValueError)
         penalty_settings(generate_kwargs)          # (malformed presence_penalty / frequency_penalty / penalty_window: ValueError)
         self._need_engine()
@@ -1619,26 +1717,31 @@ class GPT(nn.Module):
             while s2["done"] < emitted and not self._advance(s2, min(group, emitted - s2["done"])):
                 pass
             return s2
-        while True:
-            try:
-                if st is None:
-                    st = self._start(fake_inputs, generate_kwargs)
-                end = self._advance(st, group)
-            except GenvcHipError as e:
-                if not e.is_handoff_timeout or retried:
-                    raise
-                retried = True
-                st = restart()
-                continue
-            toks = st["toks"][:, emitted:st["done"]].long()
-            n = toks.shape[1]
-            if end and n:
-                n = min(n, self._stop_len(st["toks"][:, :st["done"]].long()) - emitted)
-            for i in range(n):
-                yield toks[:, i], st["lats"][:, emitted + i]
-            emitted += n
-            if end:
-                return
+        try:
+            while True:
+                try:
+                    if st is None:
+                        st = self._start(fake_inputs, generate_kwargs)
+                    end = self._advance(st, group)
+                except GenvcHipError as e:
+                    if not e.is_handoff_timeout or retried:
+                        raise
+                    retried = True
+                    st = restart()
+                    continue
+                toks = st["toks"][:, emitted:st["done"]].long()
+                n = toks.shape[1]
+                if end and n:
+                    n = min(n, self._stop_len(st["toks"][:, :st["done"]].long()) - emitted)
+                for i in range(n):
+                    yield toks[:, i], st["lats"][:, emitted + i]
+                emitted += n
+                if end:
+                    return
+        finally:
+            # (the generator ended, was closed or collected: its table's slot in the engine's arena is free for others)
+            if st is not None and st.get("wm") is not None:
+                st["wm"].release()
 
     def inference(self, cond_latents, text_inputs, **generate_kwargs):
         return self.generate(cond_latents, text_inputs, **generate_kwargs)

@@ -42,7 +42,8 @@ import time
 import torch
 
 from .inference.inference_utils import _sampling_kwargs, _vocode, handle_chunks
-from .engine import check_proc_kwargs, logits_processors, logits_sets, logits_warpers, penalty_settings, ras_counts, sample_params
+from .engine import (WatermarkTable, check_proc_kwargs, logits_processors, logits_sets, logits_warpers, penalty_settings, ras_counts,
+                     sample_params, watermark_settings)
 from .layers.gpt import _generate_call, _plain_rows_only
 from ._lib import GenvcHipError
 
@@ -102,7 +103,7 @@ class StreamSessions:
 
     # ------------------------------------------------------------------------------------------
     def _procs(self, kw, base, where):
-        """a processor dict (PROC_KWARGS, WARP_KWARGS, RAS_KWARGS and PENALTY_KWARGS only) merged over `base`, validated -> the merged
+        """a processor dict (PROC_KWARGS, WARP_KWARGS, RAS_KWARGS, PENALTY_KWARGS and WATERMARK_KWARGS only) merged over `base`, validated -> the merged
         dict, or None when it is empty.  The contrastive-search kwargs raise NotImplementedError (sessions decode one row per stream)"""
         _plain_rows_only(kw or {}, f"session (StreamSessions, {where})", beams=False)
         check_proc_kwargs(kw, where)
@@ -112,6 +113,7 @@ class StreamSessions:
             logits_warpers(m)
             ras_counts(m)
             penalty_settings(m)
+            watermark_settings(m, self.m.gpt.num_audio_tokens)
         except ValueError as e:
             raise ValueError(f"{where}: {e}") from None
         return m or None
@@ -122,12 +124,15 @@ class StreamSessions:
         repetition_penalty; missing keys come from the model config) and `seed` are this session's own; otherwise passing either raises.
         `generate_kwargs`: the session's logits processors, warpers, repetition-aware sampling and penalties (PROC_KWARGS, WARP_KWARGS,
         RAS_KWARGS: ras_window / ras_threshold, PENALTY_KWARGS: presence_penalty / frequency_penalty / penalty_window), merged over
-        the scheduler's default; any other key raises.  A session with RAS draws
+        the scheduler's default, and `watermarking_config` (WATERMARK_KWARGS): the session's own green-list watermark --
+        one key per session tells the sessions' output apart; its table's slot is held until close(); needs top_k != 1; any other
+        key raises.  A session with RAS draws
         its redraws from its own key under per_session_sampling, and then gets the tokens of its solo run."""
         if not self.per_session_sampling and (sampling is not None or seed != 0):
             raise ValueError("open(sampling=..., seed=...) needs StreamSessions(..., per_session_sampling=True): this scheduler samples "
                              "every session with the model config's settings")
         procs = self._procs(generate_kwargs, self.default_procs or {}, "open(generate_kwargs=...)")
+        wm = watermark_settings(procs or {}, self.m.gpt.num_audio_tokens)
         samp = dict(self.default_sampling)
         if sampling is not None:
             unknown = set(sampling) - set(samp)
@@ -136,6 +141,14 @@ class StreamSessions:
             samp.update(sampling)
             if not float(samp["temperature"]) > 0.0 or int(samp["top_k"]) > self.m.gpt.num_audio_tokens:
                 raise ValueError(f"open: temperature must be > 0 and top_k <= {self.m.gpt.num_audio_tokens}, got {samp}")
+        if wm is not None:
+            # the mark of a session (one key per session: a multi-tenant server tells its tenants' output apart) is served on sampled
+            # rows; the combinations GPT.generate refuses are refused here, before the session takes a slot
+            from .layers.gpt import _watermark
+            if int(samp["top_k"]) == 1:
+                raise NotImplementedError("open: watermarking_config with top_k=1 is not implemented on sessions: TopK(1) leaves one "
+                                          "candidate, and greedy search with the mark is GPT.generate(do_sample=False)")
+            _watermark(dict(procs, top_k=int(samp["top_k"])), self.m.gpt.num_audio_tokens)
         if not self.free:
             raise RuntimeError("no free stream slot")
         cond = self.m.get_gpt_cond_latents(ref_audio.to(self.m.device), self.m.config.audio.sample_rate)
@@ -143,6 +156,15 @@ class StreamSessions:
         self._next_id += 1
         s = self.sessions[sid] = _Session(self.free.pop(0), cond)
         s.sampling, s.seed, s.procs = samp, int(seed), procs
+        # the session holds its table's slot in the engine's arena from here to close(): no other table can take it meanwhile
+        # (more than MAX_WATERMARK_TABLES distinct live tables: ValueError)
+        s.wm = None
+        if wm is not None:
+            try:
+                s.wm = WatermarkTable([self.eng.watermark_entry(wm)], self.eng)
+            except ValueError:
+                self.free.append(self.sessions.pop(sid).slot)
+                raise
         if self.prefill_speaker:
             # the speaker is known before the first source segment arrives: its 32 conditioning rows go into the slot's KV cache NOW
             # (gvc_gpt_prefill_cond), so the first segment too computes only its text rows + start token -- the first audio chunk of a
@@ -158,6 +180,8 @@ class StreamSessions:
     def close(self, sid):
         s = self.sessions.pop(sid)
         self.free.append(s.slot)
+        if getattr(s, "wm", None) is not None:
+            s.wm.release()
         return s.tokens
 
     def idle(self):
@@ -311,7 +335,7 @@ class StreamSessions:
         # each session's processors, counted from the prompt of the segment it decodes (None when no session has any: no sets at all)
         sets = None
         if any(s.procs for _, s in act):
-            sets = logits_sets([s.procs for _, s in act], [s.p1 for _, s in act], m.gpt.num_audio_tokens)
+            sets = logits_sets([s.procs for _, s in act], [s.p1 for _, s in act], m.gpt.num_audio_tokens, engine=self.eng)
         rows = None
         if self.per_session_sampling:
             # each session's row keyed by its own stream: (its seed, row 0 of a lone stream, tokens of this segment drawn so far)

@@ -771,6 +771,68 @@ int gvc_gpt_generate_pen(gvc_gpt* ctx, const int32_t* slots, const int32_t* unco
                          int32_t* ras_redraws, const gvc_logits_penalties* pen, int32_t i0, int32_t n_steps, int32_t max_keys,
                          int32_t* tokens_out, int32_t tok_stride, float* latents_out, int32_t lat_stride, float* scores_out,
                          float* logits_out, int32_t out_stride, int32_t do_sample, gvc_stream s);
+/* ------------------------------------------------------------------------------------------
+ * Green-list watermark of the generated codes (Kirchenbauer et al.; transformers' WatermarkLogitsProcessor and WatermarkDetector with
+ * context_width 1), on both sampler kernels, and its detector.
+ * The table (DEVICE memory, uint32): `words` = ceil(vocab / 32) words per row; id i is green when bit (i & 31) of word (i >> 5) of
+ * its row is set.  scheme 0 (lefthash): vocab rows, and the row of a step is that of prev = ids[len - 1], the last id of the row's
+ * input_ids (the fake prompt's last id at the first step); a prev outside [0, vocab) leaves the step unmarked.  scheme 1 (selfhash):
+ * one row, the ids that are green after themselves.  The caller builds the table (genvc_amd.engine.watermark_table: transformers'
+ * recipe with a CPU generator) and keeps it alive and unchanged until every launch that reads it has finished.
+ * Place in the chain: behind every processor and every warper, ahead of LogitNormalization (bias.renormalize), as transformers
+ * appends it.  Sampling (top_k != 1): score_i = fl(score_i + bias) (one fp32 add) for every id i that survives the warpers and is
+ * green; under selfhash only for those whose score is at least the 40th largest of the row ahead of truncation (transformers biases
+ * the green ids among the 40 highest scores; ties at that boundary keep more than 40).  The draw takes its weights from the biased
+ * survivors, relative to their maximum; per-step scores carry the bias, logits stay raw.  top_k == 1: the token is the argmax of
+ * fl(fl(score_i / temperature) + bias * green_i) -- greedy search with the mark (pass temperature 1, as greedy search has none); the
+ * stored scores of a greedy search are the biased row.  Scheme 1 at top_k == 1 computes the same without the 40-largest condition
+ * and is not transformers' selfhash: the Python layer refuses it.  The speculative warp kernel never sees a table.
+ * A null entries pointer, a -1 index or an entry with a null table computes exactly what the call without it computes, through the
+ * same barriers.
+ * What the C entries do NOT refuse (genvc_amd's Python layer does, by name): scheme 1 beside a typical_p warper -- typical decoding
+ * can drop the highest scores, so the 40-highest threshold above is then not transformers' --, scheme 1 at top_k == 1, and a RAS
+ * table beside a mark -- a redraw draws from the UNBIASED untruncated row relative to its unbiased maximum.
+ * ------------------------------------------------------------------------------------------ */
+#define GVC_WM_LEFTHASH 0
+#define GVC_WM_SELFHASH 1
+#define GVC_WM_SELFHASH_TOP 40          /* selfhash: only the green ids among this many highest scores are biased */
+typedef struct gvc_logits_watermark {
+    const uint32_t* table;              /* device: [vocab][words] (lefthash) or [words] (selfhash); null: off */
+    float bias;                         /* finite; added to the green survivors */
+    int32_t scheme;                     /* GVC_WM_LEFTHASH or GVC_WM_SELFHASH */
+    int32_t words;                      /* ceil(vocab / 32) */
+    int32_t reserved;                   /* 0 */
+} gvc_logits_watermark;
+
+/* gvc_sample_wm: gvc_sample_pen with a watermark table; gvc_gpt_generate_wm: gvc_gpt_generate_pen with one.  wm (HOST, nullable: null
+ * is exactly the call without it): n_sets entries (1 <= n_sets <= B <= 64) indexed like warps / ras / pen -- row b uses
+ * wm[set_of_row[b]], none for -1, entry 0 for every row when set_of_row is null.  The entries travel by value into the device-resident
+ * call state in one staging launch ahead of the call's first launch; the kernels and step graphs are those of the call without them.
+ * GVC_ERR_ARG (entries with a table): a non-finite bias, a scheme outside {0, 1}, words != ceil(vocab / 32), reserved != 0; n_sets
+ * outside [1, B].  Not on
+ * the beam, contrastive, assisted or lookup paths. */
+int gvc_sample_wm(const float* logits, int32_t B, int32_t* ids, int32_t ids_stride, int32_t* ids_len, int32_t* finished,
+                  const gvc_sample_params* p, const gvc_row_sampling* rows, const gvc_logits_processors* sets,
+                  const gvc_logits_warpers* warps, int32_t n_sets, const int32_t* set_of_row, const gvc_logits_bias* bias,
+                  const gvc_logits_ras* ras, int32_t* ras_redraws, const gvc_logits_penalties* pen, const gvc_logits_watermark* wm,
+                  int32_t step, int32_t* tok_out, gvc_stream s);
+int gvc_gpt_generate_wm(gvc_gpt* ctx, const int32_t* slots, const int32_t* uncond_slots, int32_t B, float scale, int32_t* ids,
+                        int32_t ids_stride, int32_t* ids_len, int32_t* finished, const gvc_sample_params* p,
+                        const gvc_row_sampling* rows, const gvc_logits_processors* sets, const gvc_logits_warpers* warps,
+                        int32_t n_sets, const int32_t* set_of_row, const gvc_logits_bias* bias, const gvc_logits_ras* ras,
+                        int32_t* ras_redraws, const gvc_logits_penalties* pen, const gvc_logits_watermark* wm, int32_t i0,
+                        int32_t n_steps, int32_t max_keys, int32_t* tokens_out, int32_t tok_stride, float* latents_out,
+                        int32_t lat_stride, float* scores_out, float* logits_out, int32_t out_stride, int32_t do_sample, gvc_stream s);
+/* The detector's counts.  codes int32 [B][n] (row stride n), lens [B] (nullable: every row has n codes; else 0 <= lens[b] <= n), all
+ * device memory; table / scheme / words as in gvc_logits_watermark, the table not null, vocab the table's.  One workgroup per row.
+ * lefthash: position t in [1, len) is scored with the bit (codes[t-1], codes[t]); position 0 is unscored.  selfhash: position t in
+ * [0, len) is scored with the self-green bit of codes[t].  A position whose id (or previous id, lefthash) lies outside [0, vocab) is
+ * unscored.  ignore_repeated 1: an n-gram -- the pair (codes[t-1], codes[t]), or codes[t] alone under selfhash -- counts at its first
+ * scored occurrence only; later ones are unscored.  counts int32 [B][2]: scored positions and green ones; flags uint8 [B][n]: 1 green,
+ * 0 scored and not green, 2 unscored (every position at or past len included).  Integer arithmetic only: the same bits on every run.
+ * GVC_ERR_ARG: a null pointer, B < 1, n < 1 or n > 8192 (the repeated-n-gram scan is quadratic in n), a scheme outside {0, 1}, words != ceil(vocab / 32), ignore_repeated not 0 / 1. */
+int gvc_wm_score(const int32_t* codes, const int32_t* lens, int32_t B, int32_t n, const uint32_t* table, int32_t scheme, int32_t words,
+                 int32_t vocab, int32_t ignore_repeated, int32_t* counts, uint8_t* flags, gvc_stream s);
 /* gvc_gpt_warmup for gvc_gpt_generate_cfg over B items with this top_k: the guided step graphs of every context class up to max_keys
  * cached positions (and everything gvc_gpt_warmup(2B) prepares).  Afterwards such calls neither allocate nor synchronise */
 int gvc_gpt_warmup_cfg(gvc_gpt* ctx, int32_t B, int32_t max_keys, int32_t top_k);

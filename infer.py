@@ -67,6 +67,16 @@ if __name__ == "__main__":
     parser.add_argument("--penalty_window", type=int, default=None, metavar="W",
                         help="count only the last W generated codes for --presence_penalty / --frequency_penalty, and apply "
                              "--repetition_penalty to those codes only (default: every generated code; the repetition penalty unchanged)")
+    parser.add_argument("--watermark_key", type=int, default=None, metavar="K",
+                        help="mark the generated codes with the green-list watermark under the hashing key K (an integer in [0, 2**63)); "
+                             "scripts/detect_watermark.py --tokens PATH.npz --watermark_key K finds it in the codes --token_scores "
+                             "writes.  With --top_k 1 pass --greedy: a marked greedy stream is greedy search (do_sample=False)")
+    parser.add_argument("--watermark_bias", type=float, default=2.0, metavar="D", help="with --watermark_key: added to the green scores")
+    parser.add_argument("--watermark_ratio", type=float, default=0.25, metavar="G",
+                        help="with --watermark_key: the share of the codes that is green at a step, in (0, 1)")
+    parser.add_argument("--watermark_scheme", type=str, default="lefthash", choices=("lefthash", "selfhash"),
+                        help="with --watermark_key: transformers' seeding scheme")
+    parser.add_argument("--greedy", action="store_true", help="greedy search (do_sample=False) instead of sampling")
     parser.add_argument("--sequence_bias", action="append", default=None, metavar="IDS=VALUE",
                         help="non-streaming only, repeatable: add VALUE to the score of the last of the comma-separated codec ids when the "
                              "ids before it were just generated (HF sequence_bias), e.g. 1025=-2.0 makes every segment stop later")
@@ -197,6 +207,24 @@ if __name__ == "__main__":
             or args.prompt_lookup_num_tokens is not None):
         raise SystemExit("--presence_penalty / --frequency_penalty / --penalty_window do not combine with --num_beams, --num_beam_groups, "
                          "--penalty_alpha, --assistant_layers or --prompt_lookup_num_tokens: they act in a sampler step")
+    wm_cfg = None
+    if args.watermark_key is not None:
+        import math
+        if not 0 <= args.watermark_key < 2 ** 63:
+            raise SystemExit(f"--watermark_key must be in [0, 2**63), not {args.watermark_key}")
+        if not math.isfinite(args.watermark_bias):
+            raise SystemExit(f"--watermark_bias must be finite, not {args.watermark_bias}")
+        if not 0.0 < args.watermark_ratio < 1.0:          # (a NaN fails both comparisons)
+            raise SystemExit(f"--watermark_ratio must be in (0, 1), not {args.watermark_ratio}")
+        if (args.num_beams != 1 or args.num_beam_groups != 1 or args.penalty_alpha is not None or args.assistant_layers is not None
+                or args.prompt_lookup_num_tokens is not None or args.ras_window):
+            raise SystemExit("--watermark_key does not combine with --num_beams, --num_beam_groups, --penalty_alpha, --assistant_layers, "
+                             "--prompt_lookup_num_tokens or --ras_window: the watermark acts in a plain sampler step")
+        if args.top_k == 1 and not args.greedy:
+            raise SystemExit("--watermark_key with --top_k 1 marks nothing (one candidate survives TopK(1)): pass --greedy for greedy "
+                             "search with the mark")
+        wm_cfg = dict(greenlist_ratio=args.watermark_ratio, bias=args.watermark_bias, hashing_key=args.watermark_key,
+                      seeding_scheme=args.watermark_scheme, context_width=1)
     gen_kw = {k: v for k, v in (("min_new_tokens", args.min_new_tokens), ("no_repeat_ngram_size", args.no_repeat_ngram_size),
                                 ("min_p", args.min_p)) if v is not None}
     if args.eos_decay is not None:
@@ -215,6 +243,10 @@ if __name__ == "__main__":
     for k in ("presence_penalty", "frequency_penalty", "penalty_window"):
         if getattr(args, k):
             gen_kw[k] = getattr(args, k)
+    if wm_cfg is not None:
+        gen_kw["watermarking_config"] = wm_cfg
+    if args.greedy:
+        gen_kw["do_sample"] = False
     if args.ras_window:
         gen_kw["ras_window"] = args.ras_window
         if args.ras_threshold is not None:
